@@ -91,7 +91,7 @@ def parse():
     ap.add_argument("--pairs-per-gpu", type=int, default=1,
                     help="pairs mode: independent (scan, map) pairs every rank keeps in flight through o3s_icp_compute_batch "
                          "(8 with --gpus 8 = BASELINE config 3's 64 pairs); value = iterations/s summed over all pairs")
-    ap.add_argument("--strict", action="store_true", help="exit with code 3 when the live kernel time and the committed rocprofv3 average differ by more than 15 %")
+    ap.add_argument("--strict", action="store_true", help="exit with code 3 when the live kernel time and the committed rocprofv3 average differ by more than 15 %%")
     ap.add_argument("--exchange", choices=["rccl", "torch"], default="rccl",
                     help="sharded mode: ncclAllReduce issued from C (libo3dslam_icp_rccl.so) or dist.all_reduce from Python")
     ap.add_argument("--batch-pairs", type=int, default=8, help="pairs kept in flight on one GPU for extra.batched_on_one_gpu (0/1: skip)")
@@ -100,7 +100,30 @@ def parse():
     ap.add_argument("--no-c5", action="store_true", help="skip extra.c5 (BASELINE config 5: the per-scan loop through the compiled driver; ~70 s, most of it ray casting)")
     ap.add_argument("--no-sharded-extra", action="store_true", help="N > 1: skip extra.sharded_one_pair (the one-pair-sharded mode on the same ranks)")
     ap.add_argument("--timing-only", action="store_true", help="only the timed region (for rocprofv3 runs): no roofline / PCIe / CPU legs")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (poses and ICP stats) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+# the IcpStats fields a caller of the timed step receives that do not depend on timing (gpu_ms does; the match counters are
+# only filled with match_stats on)
+DUMP_STATS = ("iterations", "max_iters_reached", "kept_pairs", "matched_pairs", "point_used_ratio", "weighted_point_used_ratio",
+              "last_trim_limit")
+
+
+def dump_outputs(out_dir, poses, stats, suffix=""):
+    """--dump-outputs: the last timed step's results, one row per pair: pose<suffix>.npy (P, 4, 4) float32 as returned, and one
+    (P,) float64 file per field of DUMP_STATS.  The inputs are seeded, so two builds run with the same arguments can be compared
+    file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"pose{suffix}.npy"), np.stack([np.asarray(T, np.float32) for T in poses]))
+    for name in DUMP_STATS:
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.array([float(getattr(st, name)) for st in stats], np.float64))
 
 
 def sharded_roofline(icp, make_sharded, pair, n_rank, iters):
@@ -193,6 +216,8 @@ def run_sharded(args, rank, world, device, dist, torch):
         torch.cuda.synchronize()
         dist.barrier()
         t1 = time.perf_counter()
+    if args.dump_outputs and rank == 0:   # every rank holds the same pose
+        dump_outputs(args.dump_outputs, [T], [icp.stats if args.exchange == "rccl" else ps.stats])
     t = torch.tensor([t1 - t0], dtype=torch.float64, device=f"cuda:{device}")
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
@@ -895,7 +920,7 @@ def _run():
         def step():
             poses, codes, _ = compute_batch(all_handles, T_inits)
             assert all(c == 0 for c in codes), codes
-            return poses[0]
+            return poses
     else:
         def step():
             return icp.compute_resident(pair.T_init, with_trace=False)
@@ -916,6 +941,12 @@ def _run():
         if dist is not None:
             dist.barrier()
         elapsed = time.perf_counter() - t0
+    if P > 1:
+        poses, T = T, T[0]
+    else:
+        poses = [T]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, poses, [h.stats for h in [icp] + extra_handles], "" if rank == 0 else f"_rank{rank}")
     gpu_ms_chain = icp.stats.gpu_ms
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{device}")

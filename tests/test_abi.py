@@ -229,6 +229,18 @@ def test_bench_refuses_more_gpus_than_the_node_has_with_one_line():
     assert out.stdout.strip() == ""
 
 
+def test_bench_refuses_a_run_without_timed_steps():
+    """`--steps` is the number of timed steps and `ms_per_step` is divided by it: zero steps is a usage error (exit 2), found before
+    anything touches the GPU."""
+    import subprocess
+    import sys
+
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0", "--warmup", "0"], capture_output=True,
+                         text=True, timeout=300)
+    assert out.returncode == 2, (out.returncode, out.stderr[-500:])
+    assert "--steps" in out.stderr and out.stdout.strip() == ""
+
+
 def test_a_forked_child_does_not_destroy_the_parents_handles():
     """multiprocessing workers forked from a process that holds device handles inherit the wrappers; a garbage collection in
     the worker must not call into the library (the HIP runtime does not survive a fork): close() drops the handle instead."""

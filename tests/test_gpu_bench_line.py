@@ -88,6 +88,32 @@ def test_default_bench_line_describes_the_run_that_was_timed():
     assert any("libamdhip64" in p_ for p_ in d["extra"]["rocm_runtime"])
 
 
+def test_dump_outputs_writes_the_last_timed_step_and_repeats_it(tmp_path):
+    """--dump-outputs DIR: the pose and ICP stats the last timed step returned, as .npy files; the inputs are seeded, so a second run
+    with the same arguments writes the same arrays, and `steps` / `ms_per_step` describe the timed loop that was asked for."""
+    import numpy as np
+
+    runs = []
+    for k, steps in enumerate((2, 3)):
+        d_out = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--timing-only",
+                              "--dump-outputs", str(d_out)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
+        assert d["ms_per_step"] > 0 and abs(d["value"] - 50 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+        files = sorted(os.listdir(d_out))
+        assert files == sorted(["pose.npy", "iterations.npy", "max_iters_reached.npy", "kept_pairs.npy", "matched_pairs.npy",
+                                "point_used_ratio.npy", "weighted_point_used_ratio.npy", "last_trim_limit.npy"]), files
+        arrs = {f[:-len(".npy")]: np.load(d_out / f) for f in files}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        runs.append(arrs)
+    a, b = runs
+    assert a["pose"].shape == (1, 4, 4) and a["iterations"].tolist() == [50.0] and a["kept_pairs"][0] > 0
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f
+
+
 def test_n_gpu_line_also_measures_the_one_pair_sharded_mode():
     """The driver's N > 1 run is the only one that will ever see several GPUs: besides the pairs measurement (mode 1) it must time
     the one-pair-sharded mode (mode 2) on the same ranks — rehearsed here with a process group of one rank on the one GPU
