@@ -338,6 +338,31 @@ __device__ __forceinline__ void block_excl_scan2(uint32_t va, uint32_t vb, uint3
   *ex_b = base_b + ib - vb;
 }
 
+// three of them (k_classify: the level-1 histogram and the two speculative digit histograms)
+__device__ __forceinline__ void block_excl_scan3(const uint32_t (&v)[3], uint32_t (&total)[3], uint32_t (&ex)[3], uint32_t* sh /*>= 48 words*/) {
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  uint32_t inc[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) inc[j] = wave_incl_scan_u32(v[j]);
+  __syncthreads();
+  if (l == 63) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) sh[16 * j + w] = inc[j];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    uint32_t base = 0, tot = 0;
+    for (int k = 0; k < nw; ++k) {
+      const uint32_t s = sh[16 * j + k];
+      if (k < w) base += s;
+      tot += s;
+    }
+    total[j] = tot;
+    ex[j] = base + inc[j] - v[j];
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // Block-wide sums of K fp64 components per thread through LDS, in a FIXED order (thread order inside a 32-thread
 // segment, then segment order): ~K stores + 32 loads + 31 adds per thread instead of K wave_sum trees (27 of those were
@@ -919,7 +944,8 @@ __global__ void __launch_bounds__(kBlock, FAR ? O3S_FAR_WAVES : 7) k_match2(cons
                                                       float4* __restrict__ mn /*out (nullable): the matched normal of every query*/,
                                                       const float* __restrict__ rnx, const float* __restrict__ rny,
                                                       const float* __restrict__ rnz /*FAR: the reading's normals (nullable): the seed probe's direction*/,
-                                                      int rep_mask /*level-1 replicas - 1 (15; fewer in the sharded mode, where they travel)*/
+                                                      int rep_mask /*level-1 replicas - 1 (15; fewer in the sharded mode, where they travel)*/,
+                                                      uint32_t* __restrict__ spec /*nullable: speculative digit histograms [kSpecWords]*/
                                                       O3S_DBG_PARAM /*hooks build only: timing experiments (o3s_icp_profile_match)*/) {
   __shared__ uint32_t s_hist[kHistBins];
   constexpr int TQ = kBlock / G;        // queries per block: ONE tile per block (straight-line code, nothing kept alive across tiles)
@@ -947,7 +973,16 @@ __global__ void __launch_bounds__(kBlock, FAR ? O3S_FAR_WAVES : 7) k_match2(cons
   if (blockIdx.x == 0) {
     for (int k = threadIdx.x; k < 1024; k += kBlock) hist_rep[(size_t)kHistReplicas * kHistBins + k] = 0u;
     if (threadIdx.x == 0 && hdr_i(hv, H_ITER) == 0) st->t_begin = wall_clock64();  // the chain's own clock (stats.gpu_ms): no HIP events on the call path
+    // the speculative histograms of the NEXT iteration (the other parity: k_classify of the previous iteration has read it)
+    if (spec)
+      for (int k = threadIdx.x; k < kSpecHalf; k += kBlock) spec[(size_t)((hdr_i(hv, H_ITER) + 1) & 1) * kSpecHalf + k] = 0u;
   }
+  // the previous iteration's limit of this call (the state is reset per call: +inf in iteration 0) predicts this one's: the
+  // pairs that share its leading 11 / 21 bits also count their next digit, so that k_classify can resolve the limit further
+  // than the level-1 bin.  Same population as the level-1 histogram (every found match).
+  const uint32_t hint = __float_as_uint(hdr_f(hv, H_LIMIT));
+  const bool spec_on = spec != nullptr && hdr_i(hv, H_ITER) > 0 && hint < 0x7f800000u;  // uniform
+  uint32_t* const spec_cur = spec_on ? spec + (size_t)(hdr_i(hv, H_ITER) & 1) * kSpecHalf : nullptr;
   float T[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) T[k] = hdr_f(hv, k);
@@ -1364,6 +1399,11 @@ __global__ void __launch_bounds__(kBlock, FAR ? O3S_FAR_WAVES : 7) k_match2(cons
       if (mn) mn[i] = nq;
       const int bin = (int)((__float_as_uint(b.d) >> 20) & (kHistBins - 1));
       if (!O3S_DBG(1) && atomicAdd(&s_hist[bin], 1u) == 0u) mybin = bin;
+      if (spec_on && !O3S_DBG(1)) {  // ~2 % of the lanes: plain global atomics
+        const uint32_t key = __float_as_uint(b.d) & 0x7fffffffu;
+        if ((key >> 20) == (hint >> 20)) atomicAdd(&spec_cur[(key >> 10) & 1023u], 1u);
+        if ((key >> 10) == (hint >> 10)) atomicAdd(&spec_cur[1024 + (key & 1023u)], 1u);
+      }
     } else if (!found && sub == 0) {
       pos_out[i] = -1;
       d2_out[i] = kInfF;
@@ -1450,9 +1490,11 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
                                                      double* __restrict__ part /*[7][grid]*/, int mode,
                                                      int n_rep /*level-1 replicas to sum: kHistReplicas; fewer in the sharded mode, where they travel*/,
                                                      int l2_shift = 10, uint32_t l2_mask = 1023u /*the level-2 digit: bits 19..10; the sharded chain takes
-                                                     thirteen bits (shift 7, mask 8191: csrc/icp_shard_kernels.h)*/) {
-  __shared__ uint32_t s_sc[32];
-  __shared__ uint32_t s_res[4];
+                                                     thirteen bits (shift 7, mask 8191: csrc/icp_shard_kernels.h)*/,
+                                                     const uint32_t* __restrict__ spec = nullptr /*k_match2's speculative digit histograms
+                                                     [kSpecWords] (+ the hooks build's depth trace); null: level 1 only*/) {
+  __shared__ uint32_t s_sc[48];
+  __shared__ uint32_t s_res[8];
   __shared__ uint32_t s_wcnt[kClsBlock / 64];
   using Sum = BlockSum<kCentComps, kClsBlock>;
   __shared__ double s_a[Sum::kWordsA];
@@ -1487,6 +1529,15 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
     c[2] += on ? u0.z : 0u;
     c[3] += on ? u0.w : 0u;
   }
+  // both parities of the speculative histograms (fixed addresses: the parity is only known once the header has arrived)
+  uint2 sp2[2] = {make_uint2(0u, 0u), make_uint2(0u, 0u)}, sp3[2] = {make_uint2(0u, 0u), make_uint2(0u, 0u)};
+  if (spec) {  // uniform
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      sp2[p] = *reinterpret_cast<const uint2*>(spec + p * kSpecHalf + 2 * threadIdx.x);
+      sp3[p] = *reinterpret_cast<const uint2*>(spec + p * kSpecHalf + 1024 + 2 * threadIdx.x);
+    }
+  }
   O3S_TSTAMP(41);
   if (hdr_i(hv, H_DONE)) return;
   float T[16];
@@ -1505,9 +1556,29 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
   uint32_t mine = 0;
 #pragma unroll
   for (int k = 0; k < kBpt; ++k) mine += c[k];
-  uint32_t n_fin;
-  const uint32_t ex = block_excl_scan(mine, &n_fin, s_sc);
+  // the previous limit of this call (+inf in its first iteration): when it is a finite number, the speculative histograms of this
+  // iteration's parity are scanned together with the level-1 histogram (their scans share the barriers; whether they are used
+  // is decided once B is known)
+  const int it = hdr_i(hv, H_ITER);
+  const uint32_t hint = __float_as_uint(hdr_f(hv, H_LIMIT));
+  const bool spec_try = spec != nullptr && cp.has_trim && it > 0 && hint < 0x7f800000u;  // uniform
+  const uint2 h2 = (it & 1) ? sp2[1] : sp2[0], h3 = (it & 1) ? sp3[1] : sp3[0];
+  uint32_t n_fin, ex, tot2 = 0, tot3 = 0, ex2 = 0, ex3 = 0;
+  if (spec_try) {
+    const uint32_t v[3] = {mine, h2.x + h2.y, h3.x + h3.y};
+    uint32_t tot[3], exs[3];
+    block_excl_scan3(v, tot, exs, s_sc);
+    n_fin = tot[0];
+    tot2 = tot[1];
+    tot3 = tot[2];
+    ex = exs[0];
+    ex2 = exs[1];
+    ex3 = exs[2];
+  } else {
+    ex = block_excl_scan(mine, &n_fin, s_sc);
+  }
   uint32_t bin = kHistBins;  // no Trimmed filter: every finite distance is "below"
+  uint32_t depth = 11, pref = kHistBins, kk_pub = 0;  // resolved leading bits of the limit, their value, the rank inside them
   bool skip = false;
   if (cp.has_trim) {
     if (n_fin == 0) {  // "No matches available for computing distance quantiles" (Matches.cpp:76-77)
@@ -1536,6 +1607,35 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
       }
       __syncthreads();
       bin = s_res[0];
+      pref = bin;
+      kk_pub = s_res[1];
+      // ---- the previous limit's prefix: when B is its bin, k_match2 has counted the level-2 digits of exactly the pairs in B
+      //      (and the level-3 digits of those that share its 21 bits), so the digits can be resolved here.  A histogram whose
+      //      total is not the count it must split (it cannot happen; it is checked for the cost of a compare) leaves level 1.
+      if (spec_try && bin == (hint >> 20)) {  // uniform
+        const uint32_t kk = s_res[1], c2 = h2.x + h2.y;
+        if (tot2 == s_res[2]) {
+          if (c2 > 0 && ex2 <= kk && kk < ex2 + c2) {
+            const bool first = kk < ex2 + h2.x;
+            s_res[3] = 2 * threadIdx.x + (first ? 0 : 1);
+            s_res[4] = first ? kk - ex2 : kk - ex2 - h2.x;
+            s_res[5] = first ? h2.x : h2.y;
+          }
+          __syncthreads();
+          depth = 21;
+          pref = (bin << 10) | s_res[3];
+          kk_pub = s_res[4];
+          if (pref == (hint >> 10)) {
+            const uint32_t kk2 = s_res[4], n21 = s_res[5], c3 = h3.x + h3.y;
+            if (tot3 == n21) {
+              if (c3 > 0 && ex3 <= kk2 && kk2 < ex3 + c3) s_res[6] = 2 * threadIdx.x + (kk2 < ex3 + h3.x ? 0 : 1);
+              __syncthreads();
+              depth = 32;
+              pref = (pref << 10) | s_res[6];
+            }
+          }
+        }
+      }
     }
   } else {
     skip = true;
@@ -1543,11 +1643,17 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     st->n_finite = n_fin;
     ss->skip = skip ? 1u : 0u;
+    ss->depth = depth;
     if (!skip) {
+      // depth 21: the selection finishes the 21-bit prefix like a level-1 bin whose candidates all carry one level-2 digit
       ss->bin = bin;
-      ss->kk = s_res[1];
+      ss->kk = kk_pub;
       ss->bin_count = s_res[2];
+      ss->limit_bits = pref;
     }
+#ifdef O3S_TEST_HOOKS
+    if (spec && hdr_i(hv, H_ITER) < kSpecTrace) const_cast<uint32_t*>(spec)[kSpecWords + hdr_i(hv, H_ITER)] = skip ? 0u : depth;
+#endif
   }
   if (cp.has_trim && n_fin == 0) return;
   O3S_TSTAMP(43);
@@ -1566,10 +1672,12 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
   if (!(d <= cp.max_out_r2)) keep = false;
   const uint32_t u = __float_as_uint(d);
   const bool finite = matched && d != kInfF;
-  const uint32_t pbin = (u >> 20) & (kHistBins - 1);
+  // the pair's leading `depth` bits against the resolved prefix: below it kept, equal undecided (depth 32: the limit itself, ties kept)
+  const uint32_t key = u & 0x7fffffffu;
+  const uint32_t pk = depth == 32 ? key : (depth == 21 ? key >> 10 : key >> 20);
   const float sx = xf_row(T, 0, x0, y0, z0), sy = xf_row(T, 1, x0, y0, z0), sz = xf_row(T, 2, x0, y0, z0);
-  const bool decided_kept = finite && keep && pbin < bin;
-  const bool undecided = finite && pbin == bin;
+  const bool decided_kept = finite && keep && (depth == 32 ? pk <= pref : pk < pref);
+  const bool undecided = finite && depth != 32 && pk == pref;
   // ---- undecided pairs -> THIS block's candidate region, in thread order: no reservation atomic, and the order in which
   //      k_sel_finish later adds them up is the same on every run.  Their level-2 digits (bits 19..10) are counted here
   //      (~2 000 atomics spread over 1 024 addresses), so the single finishing block starts from a ready histogram. ----
@@ -1833,13 +1941,14 @@ __global__ void __launch_bounds__(kFinThreads) k_sel_partial(const IcpState* __r
   __shared__ double s_a[Sum::kWordsA];
   __shared__ double s_b[Sum::kWordsB];
   const float hv = hdr_load(st);
-  const uint32_t ssw = reinterpret_cast<const uint32_t*>(ss)[threadIdx.x & 7];
+  const uint32_t ssw = reinterpret_cast<const uint32_t*>(ss)[threadIdx.x & 15];
   const uint2 h2 = *reinterpret_cast<const uint2*>(hist2 + 2 * threadIdx.x);
   if (hdr_i(hv, H_DONE)) return;
   const uint32_t bin = (uint32_t)__builtin_amdgcn_readlane((int)ssw, kSegs), kk = (uint32_t)__builtin_amdgcn_readlane((int)ssw, kSegs + 1),
-                 skip = (uint32_t)__builtin_amdgcn_readlane((int)ssw, kSegs + 3);
+                 skip = (uint32_t)__builtin_amdgcn_readlane((int)ssw, kSegs + 3),
+                 depth = (uint32_t)__builtin_amdgcn_readlane((int)ssw, kSelWordDepth);
   double a[kCentComps] = {0, 0, 0, 0, 0, 0, 0};
-  if (!skip) {  // uniform
+  if (!skip && depth != 32u) {  // uniform (k_classify resolved the whole limit: no candidates, k_sel_finish reads nothing of this)
     const uint32_t c2 = h2.x + h2.y;
     uint32_t tot2;
     const uint32_t ex2 = block_excl_scan(c2, &tot2, s_tmp);
@@ -1906,7 +2015,7 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
   extern __shared__ __align__(16) uint32_t s_dyn[];  // kSelCap words: the level-3 list, then the final block sum
   __shared__ uint32_t s_bins[1024];
   __shared__ uint32_t s_tmp[64];
-  __shared__ uint32_t s_ssw[8];
+  __shared__ uint32_t s_ssw[16];
   __shared__ uint32_t s_base_lds[kBaseCap + 1];
   using Sum = BlockSum<kCentComps, kFinThreads>;
   static_assert((Sum::kWordsA + Sum::kWordsB) * 8 <= kSelCap * 4, "the block sum borrows the selection buffer");
@@ -1914,7 +2023,7 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
   double* s_b = s_a + Sum::kWordsA;
   O3S_TSTAMP(0);
   // first round trip: header, hand-off words, this thread's share of the classify partials, candidate counts, level 2
-  const uint32_t ssw = reinterpret_cast<const uint32_t*>(ss)[threadIdx.x & 7];
+  const uint32_t ssw = reinterpret_cast<const uint32_t*>(ss)[threadIdx.x & 15];
   double a[kCentComps] = {0, 0, 0, 0, 0, 0, 0};
   if (mode & kModeCentroid) {
     for (int b = threadIdx.x; b < nb; b += kFinThreads) {
@@ -1941,7 +2050,7 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
     __syncthreads();  // every thread holds its level-2 words before anyone clears them
     for (int k = threadIdx.x; k < kHistReplicas * kHistBins + 1024; k += kFinThreads) hist_rep[k] = 0u;  // + level 2, ready for the next iteration
   }
-  if (threadIdx.x < 8) s_ssw[threadIdx.x] = ssw;  // seg_count[4] (unused), bin, kk, bin_count, skip
+  if (threadIdx.x < 16) s_ssw[threadIdx.x] = ssw;  // seg_count[4] (unused), bin, kk, bin_count, skip, ..., depth, limit_bits
   if (threadIdx.x == 0) {
     s_tmp[42] = 0x7f800000u;
     s_tmp[43] = 0u;
@@ -1950,9 +2059,14 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
   __syncthreads();
   const uint32_t bin = s_ssw[kSegs], skip = s_ssw[kSegs + 3];
   uint32_t kk = s_ssw[kSegs + 1];
+  // depth 32: k_classify resolved the limit from the previous limit's prefix and summed every kept pair itself — there are no
+  // candidates; the partials folded above are the whole sums.  Depth 21 and 11 go through the sweep below (at 21 its
+  // candidates are the few pairs that share the 21-bit prefix, and bin / kk describe that prefix).
+  const bool resolved = s_ssw[kSelWordDepth] == 32u;
   float limit = kInfF;
   O3S_TSTAMP(2);
-  if (!skip) {  // uniform
+  if (!skip && resolved) limit = __uint_as_float(s_ssw[kSelWordLimit]);
+  if (!skip && !resolved) {  // uniform
     uint32_t* s_base = nb <= kBaseCap ? s_base_lds : base_scratch;
     uint32_t total = 0, lbits, d1, kk2, prefix21;
     bool own = false;

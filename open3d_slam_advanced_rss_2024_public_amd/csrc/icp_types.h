@@ -31,7 +31,13 @@ constexpr int kHistRing = 16;         // quaternion / translation ring (smooth_l
 constexpr int kMaxPartialBlocks = 512;  // upper bound on blocks of the classify / normal-equation kernels
 constexpr int kCentComps = 7;         // sum p(3), sum q(3), count
 constexpr int kNeComps = 27;          // upper triangle of A (21) + b (6)
-constexpr int kSegs = 4;              // candidate segments of the trim selection (block b appends to segment b % 4); more segments lengthen the slot arithmetic of k_sel_finish (16: +3.7 us), fewer did not slow k_classify
+// Speculative digit histograms of the trim selection (k_match2 -> k_classify), double-buffered by iteration parity: per parity
+// the level-2 digits of the pairs in the previous limit's level-1 bin (1024) and the level-3 digits of the pairs that share its
+// 21 leading bits (1024).  k_match2 of iteration i fills parity i & 1 and clears the other one for iteration i + 1.
+constexpr int kSpecHalf = 2048;
+constexpr int kSpecWords = 2 * kSpecHalf;
+constexpr int kSpecTrace = 256;  // hooks build: the resolved depth of iterations 0..255 of the last call, behind the histograms
+constexpr int kSegs = 4;             // candidate segments of the trim selection (block b appends to segment b % 4); more segments lengthen the slot arithmetic of k_sel_finish (16: +3.7 us), fewer did not slow k_classify
 
 // Uniform grid over the mean-centred reference (the matcher index that replaces libnabo's kd-tree).
 struct GridParams {
@@ -115,7 +121,13 @@ struct SelScratch {
   uint32_t skip;              // 1: nothing to select (no Trimmed filter, or no finite match)
   uint32_t ne_ticket;         // k_sel_ne: blocks that have stored their 27 partial sums (the last one closes the iteration)
   uint32_t pad[3];            // sharded chain: [0] the level-2 digit, [1] the rank inside it (k_shard_moments -> k_solve_shard)
+  uint32_t depth;             // leading bits of the limit k_classify resolved: 11 (bin only), 21 (bin + level-2 digit: bin / kk above
+                              // are then the 21-bit prefix's bin and the rank inside the prefix), 32 (the limit itself, limit_bits)
+  uint32_t limit_bits;        // depth 32: the limit's bit pattern
+  uint32_t pad2[2];
 };
+static_assert(sizeof(SelScratch) == 64, "the selection kernels read the hand-off words one per lane (lanes 0..15)");
+constexpr int kSelWordDepth = 12, kSelWordLimit = 13;  // word offsets of depth / limit_bits
 
 // What the host polls instead of copying the state back (host-coherent pinned memory, one per handle): the kernel that closes
 // an iteration stores the progress word — sequence number of the call, iterations completed, done — with system-scope release;

@@ -587,7 +587,7 @@ int ensure_iteration_buffers(o3s_icp* h, int N) {
   HIP_TRY(h, h->d_d2.ensure((size_t)N * 4));
   HIP_TRY(h, h->d_mq.ensure((size_t)N * sizeof(float4)));
   HIP_TRY(h, h->d_mn.ensure((size_t)N * sizeof(float4)));
-  HIP_TRY(h, h->d_hist.ensure(kHistWords * 4));
+  HIP_TRY(h, h->d_hist.ensure((kHistWords + kSpecWords + kSpecTrace) * 4));  // + the speculative digit histograms (+ the hooks build's depth trace)
   HIP_TRY(h, h->d_cand.ensure((size_t)nblocks(N, kern::kClsBlock) * kern::kClsBlock * sizeof(CandRec)));  // one region per classify block
   HIP_TRY(h, h->d_cand_cnt.ensure(((size_t)nblocks(N, kern::kClsBlock) * 2 + 2) * 4));  // counts [nb] + bases [nb + 1]
   HIP_TRY(h, h->d_sel.ensure(sizeof(SelScratch)));
@@ -626,6 +626,7 @@ struct ChainArgs {
   int nb_match, nb_part, nb_cls;
   int nb_fused;  // blocks of the fused selection + normal-equation kernel (0: the two kernels are launched separately)
   bool has_n;
+  uint32_t* spec;  // the speculative digit histograms of the trim selection (k_match2 -> k_classify); null: level 1 only
   float *rx, *ry, *rz, *rnx, *rny, *rnz;
   ChainParams cp;
   GridParams g;
@@ -657,6 +658,11 @@ ChainArgs chain_args(o3s_icp* h, const ChainParams& cp) {
     a.nb_fused = (fuse && !h->shard.active && !h->many_in_flight && nbf <= kern::kFusedMaxBlocks && nbf == a.nb_part) ? nbf : 0;
   }
   a.has_n = h->read_has_normals;
+  {  // the previous limit's prefix resolves the limit in k_classify: single-GPU chains with a Trimmed filter (O3S_NO_SPEC_SELECT=1: level 1 only)
+    const char* ne = O3S_HOOK_ENV("O3S_NO_SPEC_SELECT");  // read per call: the tests run both in one process
+    const bool spec = cp.has_trim && !cp.mirror && !h->shard.active && !(ne && std::atoi(ne) != 0);
+    a.spec = spec ? h->d_hist.as<uint32_t>() + kHistWords : nullptr;
+  }
   float* r = h->d_r.as<float>();
   a.rx = r;
   a.ry = r + (size_t)h->N;
@@ -700,24 +706,24 @@ inline RefIndex chain_index(o3s_icp* h, int it) {
   return main_index(h);
 }
 template <bool STATS, int G>
-void launch_match2(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, const RefIndex& ix, hipStream_t s) {
+void launch_match2(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, const RefIndex& ix, uint32_t* spec, hipStream_t s) {
   const int nb = round_up8(nblocks(a.N, kern::kBlock / G));  // one tile of kBlock / G queries per block
   if (h->far_rows)
     hipLaunchKernelGGL((kern::k_match2<STATS, G, 2, 4, true>), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, ix.ref, ix.cell_start, ix.g,
                        h->d_state.as<IcpState>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_mq.as<float4>(), chain_hist(h), ix.refn,
                        normals_from_matcher(a) ? h->d_mn.as<float4>() : (float4*)nullptr, a.has_n ? a.rnx : (const float*)nullptr, a.rny, a.rnz,
-                       chain_replicas(h) - 1 O3S_DBG_ARG(cp.dbg));
+                       chain_replicas(h) - 1, spec O3S_DBG_ARG(cp.dbg));
   else
     hipLaunchKernelGGL((kern::k_match2<STATS, G, 2, 2, false>), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, ix.ref, ix.cell_start, ix.g,
                        h->d_state.as<IcpState>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_mq.as<float4>(), chain_hist(h), ix.refn,
                        normals_from_matcher(a) ? h->d_mn.as<float4>() : (float4*)nullptr, a.has_n ? a.rnx : (const float*)nullptr, a.rny, a.rnz,
-                       chain_replicas(h) - 1 O3S_DBG_ARG(cp.dbg));
+                       chain_replicas(h) - 1, spec O3S_DBG_ARG(cp.dbg));
 }
 // `first`: the first iteration of a call — no incumbents yet, half the queries go through the far search.  Up to 200 k points
 // it runs with FOUR lanes per query whatever the steady-state choice: the far search is a chain of dependent round trips per lane,
 // and twice the lanes halve the rows and candidates each has to walk (C2: 50 -> 39.5 us; at C4 the launch is candidate-bound and
 // gains nothing).  Results do not depend on the lanes per query (exact search, integer histogram).
-void launch_match2_any(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, bool stats, bool first, const RefIndex& ix, hipStream_t s) {
+void launch_match2_any(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, bool stats, bool first, const RefIndex& ix, uint32_t* spec, hipStream_t s) {
   if (cp.mirror) {
     hipLaunchKernelGGL(kern::k_match_mirror, dim3(nblocks(a.N)), dim3(kern::kBlock), 0, s, a.N, h->d_ref.as<float4>(), h->d_orig_to_sorted.as<int32_t>(),
                        h->d_perm.as<int32_t>(), h->d_state.as<IcpState>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_mq.as<float4>(),
@@ -726,21 +732,21 @@ void launch_match2_any(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, bo
   }
   const int G = (first && h->far_rows && !h->match_group_forced && a.N < 200000) ? h->first_group : a.match_g;
   if (stats) {
-    if (G == 1) launch_match2<true, 1>(h, a, cp, ix, s);
-    else if (G == 2) launch_match2<true, 2>(h, a, cp, ix, s);
-    else launch_match2<true, 4>(h, a, cp, ix, s);
+    if (G == 1) launch_match2<true, 1>(h, a, cp, ix, spec, s);
+    else if (G == 2) launch_match2<true, 2>(h, a, cp, ix, spec, s);
+    else launch_match2<true, 4>(h, a, cp, ix, spec, s);
   } else {
-    if (G == 1) launch_match2<false, 1>(h, a, cp, ix, s);
-    else if (G == 2) launch_match2<false, 2>(h, a, cp, ix, s);
-    else launch_match2<false, 4>(h, a, cp, ix, s);
+    if (G == 1) launch_match2<false, 1>(h, a, cp, ix, spec, s);
+    else if (G == 2) launch_match2<false, 2>(h, a, cp, ix, spec, s);
+    else launch_match2<false, 4>(h, a, cp, ix, spec, s);
   }
 }
 void launch_match_any(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, bool stats, hipStream_t s, bool first = false) {
-  launch_match2_any(h, a, cp, stats, first, main_index(h), s);
+  launch_match2_any(h, a, cp, stats, first, main_index(h), nullptr, s);  // module-level entry points: no speculation
 }
 // the matcher launch of iteration `it` of a chain, on the index chain_index() picks for it
 void launch_match_chain(o3s_icp* h, const ChainArgs& a, bool stats, hipStream_t s, int it, const RefIndex& ix) {
-  launch_match2_any(h, a, a.cp, stats, it == 0, ix, s);
+  launch_match2_any(h, a, a.cp, stats, it == 0, ix, a.spec, s);
 }
 
 void launch_iteration(o3s_icp* h, const ChainArgs& a, bool stats, hipEvent_t* ev /*6 events or null*/, int it) {
@@ -753,7 +759,8 @@ void launch_iteration(o3s_icp* h, const ChainArgs& a, bool stats, hipEvent_t* ev
   if (ev) (void)hipEventRecord(ev[1], s);
   hipLaunchKernelGGL(kern::k_classify, dim3(a.nb_cls), dim3(kern::kClsBlock), 0, s, a.rx, a.ry, a.rz, a.rnx, a.rny, a.rnz, a.N, ix.ref,
                      ix.refn, h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_hist.as<uint32_t>(), a.cp, st,
-                     h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(), h->d_cand_cnt.as<uint32_t>(), h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins, h->d_mq.as<float4>(), h->d_mn.as<float4>(), h->d_cent.as<double>(), mode, kHistReplicas);
+                     h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(), h->d_cand_cnt.as<uint32_t>(), h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins, h->d_mq.as<float4>(), h->d_mn.as<float4>(), h->d_cent.as<double>(), mode, kHistReplicas,
+                     10, 1023u, a.spec);
   if (ev) (void)hipEventRecord(ev[2], s);
   uint32_t* hist2 = h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins;
   if (a.nb_fused > 0) {  // selection + normal equations in one launch (kern::k_sel_ne); timed under "sel_finish"
@@ -864,6 +871,9 @@ int prepare_reading(o3s_icp* h, const float* T0, bool sort, bool reset_chain, bo
   if (reset_chain) {
     init.hist = chain_hist(h);
     init.hist_words = h->shard.active ? (int)(kXchgL1Words + kShardL2Bins) : (int)kHistWords;  // level-1 replicas + the level-2 histogram behind them
+#ifdef O3S_TEST_HOOKS
+    if (!h->shard.active) init.hist_words += kSpecWords + kSpecTrace;  // hooks build: the depth trace starts empty every call
+#endif
     init.sel = h->d_sel.as<uint32_t>();
     init.sel_words = (int)(sizeof(SelScratch) / 4);
     init.mq = h->d_mq.as<float4>();
@@ -1050,7 +1060,7 @@ int compute_launch(o3s_icp* h, const float* T_init) {
     key.ptrs[3] = h->d_ref.p;
     key.ptrs[4] = h->have_grid1 ? h->d_cell_start1.p : h->d_cell_start.p;  // (any re-allocation moves key.gen as well; this tells the two kinds of chain apart)
     key.ptrs[5] = h->d_trace_T.p;
-    key.ptrs[6] = (const void*)(uintptr_t)((want_stats ? 1 : 0) | (h->shard.active ? 2 : 0) | (h->fuse_tail ? 4 : 0) | ((uintptr_t)(h->shard.active ? h->shard.world : 0) << 8));
+    key.ptrs[6] = (const void*)(uintptr_t)((want_stats ? 1 : 0) | (h->shard.active ? 2 : 0) | (h->fuse_tail ? 4 : 0) | (a.spec ? 8 : 0) | ((uintptr_t)(h->shard.active ? h->shard.world : 0) << 8));
     key.ptrs[7] = h->d_perm.p;
     key.cp = cp;
     key.g = h->grid;
@@ -1657,6 +1667,20 @@ int o3s_icp_get_trace(const o3s_icp* h, float* T_iters, float* limits, int64_t* 
   if (kept && hipMemcpy(kept, h->d_trace_kept.p, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) return 0;
   return n;
 }
+
+#ifdef O3S_TEST_HOOKS
+// hooks build only (not declared in include/): how many leading bits of each iteration's trim limit k_classify resolved in the
+// last call — 32 (the limit itself, from the previous limit's prefix), 21 (one digit left), 11 (level 1 only), 0 (no speculation)
+int o3s_icp_hook_sel_depth(const o3s_icp* h, int32_t* depth, int32_t cap) {
+  if (!h || !depth || h->shard.active) return 0;
+  const int n = std::min({(int)cap, h->last_iters, kSpecTrace});
+  if (n <= 0) return 0;
+  if (hipSetDevice(h->device) != hipSuccess) return 0;
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return 0;
+  if (hipMemcpy(depth, h->d_hist.as<uint32_t>() + kHistWords + kSpecWords, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  return n;
+}
+#endif
 
 int64_t o3s_icp_get_reading_order(const o3s_icp* h, int32_t* order, int64_t cap) {
   if (!h || !order || cap <= 0 || h->prepared_N <= 0) return 0;
