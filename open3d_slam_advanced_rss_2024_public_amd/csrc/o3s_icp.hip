@@ -171,6 +171,8 @@ struct o3s_icp {
     const void* ptrs[8] = {nullptr};
     ChainParams cp{};
     GridParams g{};
+    bool have_grid1 = false;  // a captured iteration 0 bakes the first-iteration grid in by value (chain_index)
+    GridParams g1{};
   } graph_key, graph_candidate;
   bool graph_candidate_valid = false;
 
@@ -689,19 +691,21 @@ int chain_replicas(const o3s_icp* h) { return h->shard.active ? shard_replicas(h
 // to hide it) and k_classify streams it instead of gathering it as an exposed round trip: C4 k_classify 17.9 -> 14.8 us,
 // k_match2 54.3 -> 56.9 us, 9.41 -> 9.69 k it/s.  Below, the two cancel (C2: 26.7 k either way) and k_classify keeps the gather.
 inline bool normals_from_matcher(const ChainArgs& a) { return a.N >= 200000 && !a.cp.mirror; }
-// the index an iteration of the chain searches: the first-iteration index (init_reference_impl step 4) for iteration 0 of a chain when
-// the map has one, else the main one.  Slots (d_pos) are positions in THAT index's order: the kernels of the same iteration that gather
-// by slot (k_match2's own normal fetch, k_classify) get the same index; nothing carries a slot from one iteration to the next (the
-// incumbent is the matched POINT, d_mq).  The module entry points (find_closests & co.) always use the main index.
+// the index an iteration of the chain searches: the first-iteration index (init_reference_impl step 4) for iteration 0 of a KDTree
+// chain when the map has one, else the main one.  Slots (d_pos) are positions in THAT index's order: the kernels of the same iteration
+// that gather by slot (k_match2's own normal fetch, k_classify) get the same index; nothing carries a slot from one iteration to the
+// next (the incumbent is the matched POINT, d_mq).  A mirror chain always searches the main index: k_match_mirror writes slots in
+// the main index's order (d_orig_to_sorted).  The module entry points (find_closests & co.) always use the main index.
 struct RefIndex {
   const float4* ref;
   const float4* refn;
   const uint32_t* cell_start;
   GridParams g;
 };
+inline bool first_index_used(const o3s_icp* h, const ChainParams& cp) { return !cp.mirror && h->have_grid1 && h->far_rows; }
 inline RefIndex main_index(o3s_icp* h) { return RefIndex{h->d_ref.as<float4>(), h->d_refn.as<float4>(), h->d_cell_start.as<uint32_t>(), h->grid}; }
-inline RefIndex chain_index(o3s_icp* h, int it) {
-  if (it == 0 && h->have_grid1 && h->far_rows)
+inline RefIndex chain_index(o3s_icp* h, const ChainParams& cp, int it) {
+  if (it == 0 && first_index_used(h, cp))
     return RefIndex{h->d_ref1.as<float4>(), h->ref_has_normals ? h->d_refn1.as<float4>() : h->d_refn.as<float4>(), h->d_cell_start1.as<uint32_t>(), h->grid1};
   return main_index(h);
 }
@@ -723,6 +727,9 @@ void launch_match2(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, const 
 // it runs with FOUR lanes per query whatever the steady-state choice: the far search is a chain of dependent round trips per lane,
 // and twice the lanes halve the rows and candidates each has to walk (C2: 50 -> 39.5 us; at C4 the launch is candidate-bound and
 // gains nothing).  Results do not depend on the lanes per query (exact search, integer histogram).
+inline int match_lanes(const o3s_icp* h, const ChainArgs& a, bool first) {
+  return (first && h->far_rows && !h->match_group_forced && a.N < 200000) ? h->first_group : a.match_g;
+}
 void launch_match2_any(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, bool stats, bool first, const RefIndex& ix, uint32_t* spec, hipStream_t s) {
   if (cp.mirror) {
     hipLaunchKernelGGL(kern::k_match_mirror, dim3(nblocks(a.N)), dim3(kern::kBlock), 0, s, a.N, h->d_ref.as<float4>(), h->d_orig_to_sorted.as<int32_t>(),
@@ -730,7 +737,7 @@ void launch_match2_any(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, bo
                        chain_hist(h));
     return;
   }
-  const int G = (first && h->far_rows && !h->match_group_forced && a.N < 200000) ? h->first_group : a.match_g;
+  const int G = match_lanes(h, a, first);
   if (stats) {
     if (G == 1) launch_match2<true, 1>(h, a, cp, ix, spec, s);
     else if (G == 2) launch_match2<true, 2>(h, a, cp, ix, spec, s);
@@ -749,12 +756,19 @@ void launch_match_chain(o3s_icp* h, const ChainArgs& a, bool stats, hipStream_t 
   launch_match2_any(h, a, a.cp, stats, it == 0, ix, a.spec, s);
 }
 
+// large readings (more classify blocks than the finishing block has threads): the candidate sweep of the two-kernel chain runs on many
+// blocks first
+inline bool sel_partial(const ChainArgs& a) {
+  const char* pe = O3S_HOOK_ENV("O3S_SEL_PARTIAL");  // read per call (A/B runs, tests of both paths): 0 keeps the single-block sweep
+  return a.nb_cls > kern::kFinThreads && !(pe && std::atoi(pe) == 0);
+}
+
 void launch_iteration(o3s_icp* h, const ChainArgs& a, bool stats, hipEvent_t* ev /*6 events or null*/, int it) {
   IcpState* st = h->d_state.as<IcpState>();
   hipStream_t s = h->stream;
   const int mode = kern::kModeCentroid | kern::kModeGate | (normals_from_matcher(a) ? kern::kModeNormalReady : 0);
   if (ev) (void)hipEventRecord(ev[0], s);
-  const RefIndex ix = chain_index(h, it);
+  const RefIndex ix = chain_index(h, a.cp, it);
   launch_match_chain(h, a, stats, s, it, ix);
   if (ev) (void)hipEventRecord(ev[1], s);
   hipLaunchKernelGGL(kern::k_classify, dim3(a.nb_cls), dim3(kern::kClsBlock), 0, s, a.rx, a.ry, a.rz, a.rnx, a.rny, a.rnz, a.N, ix.ref,
@@ -785,9 +799,7 @@ void launch_iteration(o3s_icp* h, const ChainArgs& a, bool stats, hipEvent_t* ev
     return;
   }
   {
-    // large readings (more classify blocks than the finishing block has threads): the candidate sweep runs on many blocks first
-    const char* pe = O3S_HOOK_ENV("O3S_SEL_PARTIAL");  // read per call (A/B runs, tests of both paths): 0 keeps the single-block sweep
-    const bool partial = a.nb_cls > kern::kFinThreads && !(pe && std::atoi(pe) == 0);
+    const bool partial = sel_partial(a);
     const int nbp = partial ? std::min(kern::kSelPartMaxBlocks, nblocks(a.nb_cls, 4)) : 0;
     CandRec* park_rec = h->d_park.as<CandRec>();
     uint32_t* park_key = reinterpret_cast<uint32_t*>(h->d_park.as<char>() + (size_t)kern::kParkRecs * sizeof(CandRec));
@@ -830,7 +842,7 @@ int launch_iteration_sharded(o3s_icp* h, const ChainArgs& a, bool stats, int it)
   };
   int rc;
   const int R = chain_replicas(h);
-  const RefIndex ix = chain_index(h, it);  // (every rank holds the same reference, so every rank picks the same index)
+  const RefIndex ix = chain_index(h, a.cp, it);  // (every rank holds the same reference, so every rank picks the same index)
   launch_match_chain(h, a, stats, s, it, ix);  // level-1 replicas = region I of the exchange buffer (chain_hist), R of them
   if ((rc = exchange(kXchgI32Off, (int64_t)R * kHistBins, O3S_XCHG_INT32)) != O3S_OK) return rc;
   hipLaunchKernelGGL(kern::k_classify, dim3(a.nb_cls), dim3(kern::kClsBlock), 0, s, a.rx, a.ry, a.rz, a.rnx, a.rny, a.rnz, a.N, ix.ref,
@@ -856,7 +868,8 @@ void init_state(IcpState& st) {
 
 bool graph_key_equal(const o3s_icp::GraphKey& a, const o3s_icp::GraphKey& b) {
   return a.N == b.N && a.iters == b.iters && a.nb == b.nb && a.has_n == b.has_n && a.gen == b.gen && std::memcmp(a.ptrs, b.ptrs, sizeof(a.ptrs)) == 0 &&
-         std::memcmp(&a.cp, &b.cp, sizeof(ChainParams)) == 0 && std::memcmp(&a.g, &b.g, sizeof(GridParams)) == 0;
+         std::memcmp(&a.cp, &b.cp, sizeof(ChainParams)) == 0 && std::memcmp(&a.g, &b.g, sizeof(GridParams)) == 0 && a.have_grid1 == b.have_grid1 &&
+         std::memcmp(&a.g1, &b.g1, sizeof(GridParams)) == 0;
 }
 
 // transform + spatial sort of the reading; with reset_chain the first kernel also resets what a chain starts from
@@ -1064,6 +1077,8 @@ int compute_launch(o3s_icp* h, const float* T_init) {
     key.ptrs[7] = h->d_perm.p;
     key.cp = cp;
     key.g = h->grid;
+    key.have_grid1 = h->have_grid1;
+    if (h->have_grid1) key.g1 = h->grid1;
     const bool graph_ok = h->cfg.use_graph && cp.max_iters > 0 && (!h->shard.active || shard_graph);
     const bool have = graph_ok && h->graph_exec && graph_key_equal(key, h->graph_key);
     const bool seen_before = graph_ok && h->graph_candidate_valid && graph_key_equal(key, h->graph_candidate);
@@ -1149,6 +1164,18 @@ int compute_launch(o3s_icp* h, const float* T_init) {
       HIP_TRY(h, hipGetLastError());
     }
   }
+#ifdef O3S_TEST_HOOKS
+  if (O3S_HOOK_ENV("O3S_PRINT_CHAIN")) {  // hooks build: the side of every dispatch switch this call took (tests/test_gpu_dispatch_boundaries.py)
+    static const char* issued[] = {"eager", "captured", "replayed"};
+    std::fprintf(stderr,
+                 "o3s chain: N %d matcher %s far %s it0_index %s match_g %d first_g %d normals_from_matcher %d nb_fused %d partial %d spec %d "
+                 "has_n %d issued %s\n",
+                 N, cp.mirror ? "mirror" : "kdtree", h->far_rows ? "rows" : "ring", first_index_used(h, cp) ? "first" : "main",
+                 cp.mirror ? 0 : a.match_g, cp.mirror ? 0 : match_lanes(h, a, true), normals_from_matcher(a) ? 1 : 0, a.nb_fused,
+                 (!h->shard.active && a.nb_fused == 0 && sel_partial(a)) ? 1 : 0, a.spec ? 1 : 0, a.has_n ? 1 : 0,
+                 h->profiling ? "profiled" : issued[h->issue_mode]);
+  }
+#endif
   h->pend_valid = true;
   return O3S_OK;
 }
