@@ -46,6 +46,38 @@ void o3s_o3d_icp_default_criteria(o3s_o3d_icp_criteria* c);
 int o3s_o3d_registration_icp(int device, const double* source, int64_t Ns, const double* target,
                              const double* target_normals, int64_t Nt, double max_correspondence_distance,
                              const double init[16], const o3s_o3d_icp_criteria* criteria, o3s_o3d_icp_result* result);
+/* The estimation of a registration: CloudRegistrationType (O3S/include/open3d_slam/Parameters.hpp:37-45), the three branches
+ * of cloudRegistrationFactory (O3S/src/CloudRegistration.cpp:16-21, 57-61, 88-101).  Every parameter set the reference ships
+ * selects GeneralizedIcp for the loop-closure refinement (scan_to_map_refinement_type).
+ *   O3S_O3D_POINT_TO_PLANE  TransformationEstimationPointToPlane()                      (what o3s_o3d_registration_icp runs)
+ *   O3S_O3D_POINT_TO_POINT  TransformationEstimationPointToPoint(with_scaling = false)   (Eigen::umeyama over the correspondences)
+ *   O3S_O3D_GENERALIZED     RegistrationGeneralizedICP(..., TransformationEstimationForGeneralizedICP(gicp_epsilon), ...):
+ *                           per-point covariances C = Rx diag(eps, 1, 1) Rx^T from the normals as given
+ *                           (InitializePointCloudForGeneralizedICP, GeneralizedICP.cpp) unless covariances are passed;
+ *                           the source's covariances turn with the source (C <- R C R^T at init and at every update). */
+typedef enum o3s_o3d_estimation_type {
+  O3S_O3D_POINT_TO_PLANE = 0,
+  O3S_O3D_POINT_TO_POINT = 1,
+  O3S_O3D_GENERALIZED = 2
+} o3s_o3d_estimation_type;
+typedef struct o3s_o3d_estimation {
+  int32_t type;        /* o3s_o3d_estimation_type */
+  double gicp_epsilon; /* TransformationEstimationForGeneralizedICP::epsilon_ (1e-3); must be > 0 for every type */
+  int32_t reserved[4];
+} o3s_o3d_estimation;
+/* GENERALIZED with epsilon 1e-3: what the reference's parameters select. */
+void o3s_o3d_default_estimation(o3s_o3d_estimation* e);
+/* RegistrationICP with the estimation `est` (o3s_o3d_registration_icp with est->type == O3S_O3D_POINT_TO_PLANE returns the same
+ * bits).  Normals: 3 x N doubles, covariances: 9 x N doubles (a column-major 3 x 3 per point, Open3D's Matrix3d; symmetric: the
+ * upper triangle is read), all nullable.  GENERALIZED needs normals or covariances on each cloud (covariances win, as in Open3D;
+ * Open3D's KNN(20) normal estimation for a cloud with neither is not restated: O3S_ERR_BAD_SHAPE); POINT_TO_PLANE needs target
+ * normals (O3S_ERR_BAD_SHAPE); POINT_TO_POINT needs neither.  An unknown type, gicp_epsilon <= 0 or a NULL cloud / pose / result /
+ * est is O3S_ERR_BAD_ARGUMENT before any device call. */
+int o3s_o3d_registration_icp_ex(int device, const double* source, const double* source_normals, const double* source_cov,
+                                int64_t Ns, const double* target, const double* target_normals, const double* target_cov,
+                                int64_t Nt, double max_correspondence_distance, const double init[16],
+                                const o3s_o3d_estimation* est, const o3s_o3d_icp_criteria* criteria,
+                                o3s_o3d_icp_result* result);
 /* info: 6 x 6, column-major (symmetric). */
 int o3s_o3d_information_matrix(int device, const double* source, int64_t Ns, const double* target, int64_t Nt,
                                double max_correspondence_distance, const double T[16], double info[36]);

@@ -172,6 +172,24 @@ int o3s_o3d_registration_icp_submaps_overlap_batch(int32_t n, const o3s_submap* 
                                                    int64_t min_points_per_voxel, o3s_o3d_icp_result* results, double* infos,
                                                    int64_t* n_overlaps, int32_t* statuses);
 
+/* The two calls above with the estimation of o3s_registration.h (o3s_o3d_estimation; PlaceRecognition::updateRegistrationAlgorithm,
+ * O3S/src/PlaceRecognition.cpp:44-48, builds the refinement from scan_to_map_refinement_type, GeneralizedIcp in every parameter set
+ * of the reference).  GENERALIZED selects the source's normals with its points (both submaps must carry normals:
+ * O3S_ERR_BAD_SHAPE otherwise); POINT_TO_POINT needs no normals; POINT_TO_PLANE returns the bits of the calls above.  The
+ * information matrix is GetInformationMatrixFromPointClouds for every type, as in the reference.  An unknown type or
+ * gicp_epsilon <= 0 is O3S_ERR_BAD_ARGUMENT. */
+int o3s_o3d_registration_icp_submaps_overlap_ex(const o3s_submap* source, const o3s_submap* target,
+                                                double max_correspondence_distance, const double init[16],
+                                                const o3s_o3d_estimation* est, const o3s_o3d_icp_criteria* criteria,
+                                                double overlap_voxel_size, int64_t min_points_per_voxel,
+                                                o3s_o3d_icp_result* result, double* info36, int64_t* n_overlap);
+int o3s_o3d_registration_icp_submaps_overlap_batch_ex(int32_t n, const o3s_submap* const* sources,
+                                                      const o3s_submap* const* targets, double max_correspondence_distance,
+                                                      const double* inits, const o3s_o3d_estimation* est,
+                                                      const o3s_o3d_icp_criteria* criteria, double overlap_voxel_size,
+                                                      int64_t min_points_per_voxel, o3s_o3d_icp_result* results,
+                                                      double* infos, int64_t* n_overlaps, int32_t* statuses);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@
 
 #include "normals_dev.h"
 
+#include <algorithm>
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -84,6 +85,63 @@ __global__ void __launch_bounds__(kB) k_o3d_place(const double* __restrict__ p, 
   out[3 * i] = px;
   out[3 * i + 1] = py;
   out[3 * i + 2] = pz;
+}
+
+// ---- Generalized ICP: per-point covariances -------------------------------------------------------------------------------
+// The estimation types (o3s_o3d_estimation_type): the template parameter of k_o3d_corr
+constexpr int kEstPlane = 0, kEstPoint = 1, kEstGicp = 2;
+// InitializePointCloudForGeneralizedICP (Open3D v0.15.1, pipelines/registration/GeneralizedICP.cpp), one point:
+// C = Rx diag(eps, 1, 1) Rx^T with Rx = GetRotationFromE1ToX(n): v = e1 x n, c = e1 . n; c < -0.99 -> Rx = I, otherwise
+// Rx = I + [v]x + [v]x^2 / (1 + c) (factor = 1 / (1 + c) first).  The normal as given: a non-unit normal is NOT normalised.
+// from_cov: the input is a caller's covariance (9 doubles, column-major; "pre-computed covariances" are used as they are).
+// out: xx xy xz yy yz zz of point i, in the order `order` visits the input (nullptr: as given).  The source's covariances are
+// placed as its untransformed cloud has them; k_o3d_corr turns them by the rotation accumulated so far.
+__global__ void __launch_bounds__(kB) k_o3d_cov(const double* __restrict__ in, int from_cov, const uint32_t* __restrict__ order, int64_t N, double eps,
+                                                double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
+  if (i >= N) return;
+  const size_t j = order ? (size_t)order[i] : (size_t)i;
+  double c6[6];
+  if (from_cov) {
+    const double* m = in + 9 * j;
+    c6[0] = m[0];
+    c6[1] = m[3];
+    c6[2] = m[6];
+    c6[3] = m[4];
+    c6[4] = m[7];
+    c6[5] = m[8];
+  } else {
+    const double nx = in[3 * j], ny = in[3 * j + 1], nz = in[3 * j + 2];
+    double R[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    const double c = nx;  // e1 . n
+    if (!(c < -0.99)) {
+      const double vx = 0.0, vy = -nz, vz = ny;  // e1 x n
+      const double S[3][3] = {{0.0, -vz, vy}, {vz, 0.0, -vx}, {-vy, vx, 0.0}};
+      const double factor = 1.0 / (1.0 + c);
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+          double s2 = S[a][0] * S[0][b];
+          s2 = s2 + S[a][1] * S[1][b];
+          s2 = s2 + S[a][2] * S[2][b];
+          R[a][b] = (R[a][b] + S[a][b]) + s2 * factor;
+        }
+    }
+    const double d[3] = {eps, 1.0, 1.0};
+    int t = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = a; b < 3; ++b) {
+        double s = R[a][0] * d[0] * R[b][0];
+        s = s + R[a][1] * d[1] * R[b][1];
+        s = s + R[a][2] * d[2] * R[b][2];
+        c6[t++] = s;
+      }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) out[6 * (size_t)i + k] = c6[k];
 }
 
 // ---- the correspondence search ----------------------------------------------------------------------------------------
@@ -720,12 +778,29 @@ __global__ void __launch_bounds__(kB, W == 64 ? 1 : 5) k_o3d_search_far(const do
   }
 }
 
+// What the point-to-point and Generalized ICP sums read besides the points (point-to-plane: nothing; a trailing argument, so the
+// point-to-plane instantiation is the kernel it was).
+struct O3dEstArgs {
+  const double* scov;  // GICP: the source's covariances as placed (k_o3d_cov, search order, untransformed)
+  const double* tcov;  // GICP: the target's covariances (k_o3d_cov, original index order: fetched by the correspondence's index)
+  double R[9];         // GICP: the rotation the source has gone through since it was placed (column-major): C_s = R C R^T
+  double c[3];         // point-to-point: a fixed shift for the call (the centre of the target's grid): sums of s - c, t - c
+};
+
 // The sums of the NEXT ComputeTransformation (mode 0) or of the information matrix (mode 1) over the correspondences the search
 // left in corr[], one lane per source point; the distance is formed again from the same coordinates in the same order.
-template <int PHASE>
+// EST (mode 0 only): kEstPlane — TransformationEstimationPointToPlane, the 21 + 6 slots of J^T J, J^T r;
+//  kEstGicp — TransformationEstimationForGeneralizedICP (GeneralizedICP.cpp ComputeTransformation): with d = vs - vt,
+//   M = Ct + Cs, W = M^-1.sqrt(), J = W [-[vs]x | I], r = W d, Open3D adds J^T J and J^T r; W symmetric gives W^T W = M^-1,
+//   so the same sums are G^T M^-1 G and G^T M^-1 d with G = [-[vs]x | I]: one symmetric 3 x 3 inverse per pair, no square root
+//   (equal to Open3D's form to rounding; tests/o3d_registration_ref.py restates the W form);
+//  kEstPoint — TransformationEstimationPointToPoint (Eigen::umeyama): [0..2] sum (s - c), [3..5] sum (t - c), [6..14] sum
+//   (t - c)(s - c)^T (row-major), c a fixed shift near the clouds so that the host's centring cancels nothing large.
+// [28] sum d2 and [29] the count for every type (GetRegistrationResultAndCorrespondences).
+template <int PHASE, int EST = kEstPlane>
 __global__ void __launch_bounds__(kB) k_o3d_corr(const double* __restrict__ pcd, int64_t Ns, GridIndex gi, const double* __restrict__ tgt,
                                                  const double* __restrict__ tn, double r2, int mode, int32_t* __restrict__ corr,
-                                                 double* __restrict__ part /*[kAccComps][gridDim.x]*/) {
+                                                 double* __restrict__ part /*[kAccComps][gridDim.x]*/, O3dEstArgs ea) {
   static_assert(PHASE == 1, "the search is k_o3d_search");
   __shared__ double sh[4][kAccComps];
   double acc[kAccComps];
@@ -748,7 +823,77 @@ __global__ void __launch_bounds__(kB) k_o3d_corr(const double* __restrict__ pcd,
       }
       double J[6], rres = 0.0;
       double rows[3][6];
-      if (mode == 0) {  // TransformationEstimationPointToPlane: r = (vs - vt) . nt, J = [vs x nt ; nt]
+      if constexpr (EST == kEstGicp) {
+        // C_s = R S R^T: the covariance placed, turned with the source (PointCloud::Transform -> TransformCovariances)
+        const double* sc = ea.scov + 6 * (size_t)i;
+        const double S[3][3] = {{sc[0], sc[1], sc[2]}, {sc[1], sc[3], sc[4]}, {sc[2], sc[4], sc[5]}};
+        double P[3][3];  // R S
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+          for (int b = 0; b < 3; ++b) {
+            double v = ea.R[a] * S[0][b];
+            v = v + ea.R[3 + a] * S[1][b];
+            v = v + ea.R[6 + a] * S[2][b];
+            P[a][b] = v;
+          }
+        const double* tc = ea.tcov + 6 * (size_t)bj;
+        double m6[6];  // M = C_t + C_s, upper triangle
+        {
+          int t = 0;
+#pragma unroll
+          for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = a; b < 3; ++b) {
+              double v = P[a][0] * ea.R[b];
+              v = v + P[a][1] * ea.R[3 + b];
+              v = v + P[a][2] * ea.R[6 + b];
+              m6[t] = tc[t] + v;
+              ++t;
+            }
+        }
+        // A = M^-1 through the cofactors (symmetric)
+        const double c00 = m6[3] * m6[5] - m6[4] * m6[4], c01 = m6[2] * m6[4] - m6[1] * m6[5], c02 = m6[1] * m6[4] - m6[2] * m6[3];
+        const double c11 = m6[0] * m6[5] - m6[2] * m6[2], c12 = m6[1] * m6[2] - m6[0] * m6[4], c22 = m6[0] * m6[3] - m6[1] * m6[1];
+        const double inv = 1.0 / ((m6[0] * c00 + m6[1] * c01) + m6[2] * c02);
+        const double A[3][3] = {{c00 * inv, c01 * inv, c02 * inv}, {c01 * inv, c11 * inv, c12 * inv}, {c02 * inv, c12 * inv, c22 * inv}};
+        const double d[3] = {qx - tx, qy - ty, qz - tz};
+        double wv[3];  // A d
+#pragma unroll
+        for (int a = 0; a < 3; ++a) wv[a] = (A[a][0] * d[0] + A[a][1] * d[1]) + A[a][2] * d[2];
+        // G = [Sv | I], Sv = -[vs]x; B = A Sv
+        const double Sv[3][3] = {{0.0, qz, -qy}, {-qz, 0.0, qx}, {qy, -qx, 0.0}};
+        double B[3][3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+          for (int b = 0; b < 3; ++b) B[a][b] = (A[a][0] * Sv[0][b] + A[a][1] * Sv[1][b]) + A[a][2] * Sv[2][b];
+        int t = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+          for (int b = a; b < 6; ++b) {
+            double h;
+            if (a < 3 && b < 3) h = (Sv[0][a] * B[0][b] + Sv[1][a] * B[1][b]) + Sv[2][a] * B[2][b];  // Sv^T A Sv
+            else if (a < 3) h = B[b - 3][a];                                                             // Sv^T A
+            else h = A[a - 3][b - 3];                                                                    // A
+            acc[t++] += h;
+          }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) acc[21 + a] += (Sv[0][a] * wv[0] + Sv[1][a] * wv[1]) + Sv[2][a] * wv[2];  // Sv^T A d
+#pragma unroll
+        for (int a = 0; a < 3; ++a) acc[24 + a] += wv[a];                                                       // A d
+        acc[27] += (d[0] * wv[0] + d[1] * wv[1]) + d[2] * wv[2];                                              // |W d|^2
+      } else if constexpr (EST == kEstPoint) {
+        const double s3[3] = {qx - ea.c[0], qy - ea.c[1], qz - ea.c[2]}, t3[3] = {tx - ea.c[0], ty - ea.c[1], tz - ea.c[2]};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          acc[a] += s3[a];
+          acc[3 + a] += t3[a];
+#pragma unroll
+          for (int b = 0; b < 3; ++b) acc[6 + 3 * a + b] += t3[a] * s3[b];
+        }
+      } else if (mode == 0) {  // TransformationEstimationPointToPlane: r = (vs - vt) . nt, J = [vs x nt ; nt]
         const double nx = tn[3 * (size_t)bj], ny = tn[3 * (size_t)bj + 1], nz = tn[3 * (size_t)bj + 2];
         const double ex = qx - tx, ey = qy - ty, ez = qz - tz;
         rres = (ex * nx + ey * ny) + ez * nz;
@@ -950,6 +1095,120 @@ inline void h_vec6_to_T(const double* v, double* T) {
   T[3 * 4 + 2] = v[5];
 }
 
+// Eigen::JacobiSVD<Matrix3d> (ComputeFullU | ComputeFullV) as umeyama uses it: A = U diag(s) V^T, s descending.  One-sided
+// (Hestenes) Jacobi on the columns of A in fp64; a different rotation sequence from Eigen's two-sided one, the same factors to
+// rounding wherever they are unique — and R = U S V^T below is unique whenever A has rank >= 2.
+inline void h_svd3(const double Ain[3][3], double U[3][3], double sv[3], double V[3][3]) {
+  double A[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      A[r][c] = Ain[r][c];
+      V[r][c] = r == c ? 1.0 : 0.0;
+    }
+  static const int kP[3][2] = {{0, 1}, {0, 2}, {1, 2}};
+  for (int sweep = 0; sweep < 64; ++sweep) {
+    bool rotated = false;
+    for (const auto& pq : kP) {
+      const int p = pq[0], q = pq[1];
+      double al = 0, be = 0, ga = 0;
+      for (int i = 0; i < 3; ++i) {
+        al += A[i][p] * A[i][p];
+        be += A[i][q] * A[i][q];
+        ga += A[i][p] * A[i][q];
+      }
+      if (ga == 0.0 || !(std::fabs(ga) > 1e-15 * std::sqrt(al * be))) continue;
+      const double zeta = (be - al) / (2.0 * ga);
+      const double t = std::copysign(1.0, zeta) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+      if (t == 0.0) continue;
+      rotated = true;
+      const double cs = 1.0 / std::sqrt(1.0 + t * t), sn = cs * t;
+      for (int i = 0; i < 3; ++i) {
+        const double ap = A[i][p], aq = A[i][q];
+        A[i][p] = cs * ap - sn * aq;
+        A[i][q] = sn * ap + cs * aq;
+        const double vp = V[i][p], vq = V[i][q];
+        V[i][p] = cs * vp - sn * vq;
+        V[i][q] = sn * vp + cs * vq;
+      }
+    }
+    if (!rotated) break;
+  }
+  int ord[3] = {0, 1, 2};
+  double nrm[3];
+  for (int c = 0; c < 3; ++c) nrm[c] = std::sqrt(A[0][c] * A[0][c] + A[1][c] * A[1][c] + A[2][c] * A[2][c]);
+  std::sort(ord, ord + 3, [&](int a, int b) { return nrm[a] > nrm[b]; });
+  double Vs[3][3];
+  for (int k = 0; k < 3; ++k) {
+    sv[k] = nrm[ord[k]];
+    for (int i = 0; i < 3; ++i) {
+      Vs[i][k] = V[i][ord[k]];
+      U[i][k] = sv[k] > 0.0 ? A[i][ord[k]] / sv[k] : 0.0;
+    }
+  }
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) V[r][c] = Vs[r][c];
+  // columns of U for zero singular values: completed to an orthonormal basis (rank <= 2: R below does not depend on the choice
+  // while the rank is 2)
+  auto cross = [&](int a, int b, int o) {
+    U[0][o] = U[1][a] * U[2][b] - U[2][a] * U[1][b];
+    U[1][o] = U[2][a] * U[0][b] - U[0][a] * U[2][b];
+    U[2][o] = U[0][a] * U[1][b] - U[1][a] * U[0][b];
+  };
+  if (!(sv[0] > 0.0)) {
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) U[r][c] = r == c ? 1.0 : 0.0;
+  } else if (!(sv[1] > 0.0)) {
+    const int k = std::fabs(U[0][0]) < 0.9 ? 0 : 1;  // a unit axis not along u0, made orthogonal to it
+    double e[3] = {0, 0, 0};
+    e[k] = 1.0;
+    const double dt = U[k][0];
+    double l = 0;
+    for (int i = 0; i < 3; ++i) {
+      U[i][1] = e[i] - dt * U[i][0];
+      l += U[i][1] * U[i][1];
+    }
+    l = std::sqrt(l);
+    for (int i = 0; i < 3; ++i) U[i][1] /= l;
+    cross(0, 1, 2);
+  } else if (!(sv[2] > 0.0)) {
+    cross(0, 1, 2);
+  }
+}
+inline double h_det3(const double M[3][3]) {
+  return M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
+         M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+}
+// TransformationEstimationPointToPoint::ComputeTransformation (with_scaling = false) = Eigen::umeyama(source, target, false) over
+// the correspondences (Open3D TransformationEstimation.cpp; Eigen/src/Geometry/Umeyama.h): means, sigma = (1/n) sum (t - t_mean)
+// (s - s_mean)^T, its SVD U S V^T, S = diag(1, 1, -1) when det U det V < 0, R = U S V^T, t = t_mean - R s_mean.  v: the sums of
+// k_o3d_corr<1, kEstPoint> (relative to the shift c), v[29] > 0 correspondences.
+inline void h_umeyama(const double* v, const double* c, double* T) {
+  const double inv_n = 1.0 / v[29];
+  double ms[3], mt[3], Sg[3][3];
+  for (int a = 0; a < 3; ++a) {
+    ms[a] = v[a] * inv_n;
+    mt[a] = v[3 + a] * inv_n;
+  }
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) Sg[a][b] = v[6 + 3 * a + b] * inv_n - mt[a] * ms[b];
+  double U[3][3], sv[3], V[3][3];
+  h_svd3(Sg, U, sv, V);
+  const double sd[3] = {1.0, 1.0, h_det3(U) * h_det3(V) < 0 ? -1.0 : 1.0};
+  for (int i = 0; i < 16; ++i) T[i] = 0.0;
+  T[15] = 1.0;
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      double r = 0.0;
+      for (int k = 0; k < 3; ++k) r += U[a][k] * sd[k] * V[b][k];
+      T[b * 4 + a] = r;
+    }
+  for (int a = 0; a < 3; ++a) {
+    double t = mt[a] + c[a];
+    for (int b = 0; b < 3; ++b) t -= T[b * 4 + a] * (ms[b] + c[b]);
+    T[12 + a] = t;
+  }
+}
+
 struct O3dIcpWork {
   NormalsWork grid;  // index over the target
   Buf d_src, d_tgt, d_tn, d_corr, d_part, d_sum, d_rec, d_far, d_far_count, d_cert, d_list;
@@ -969,6 +1228,11 @@ struct O3dIcpWork {
   GridIndex gi{};
   int64_t n_src = 0;
   bool pair_ready = false;
+  // the estimation of the running registration (o3d_icp_run): what the passes' k_o3d_corr sums
+  int est = kEstPlane;
+  O3dEstArgs ea{};
+  Buf d_scov, d_tcov;  // GICP: 6 doubles per point, source in search order / target in index order (k_o3d_cov)
+  Buf d_sraw, d_traw;  // GICP from the host: the normals / covariances as uploaded
   O3dIcpWork() = default;
   O3dIcpWork(const O3dIcpWork&) = delete;
   O3dIcpWork& operator=(const O3dIcpWork&) = delete;
@@ -987,6 +1251,7 @@ struct RegArea {
   int device = -1;
   OverlapWork ov;                // overlap selection (overlap_impl.h)
   Buf ov_src, ov_tgt, ov_tgtn;   // the two selected clouds of o3s_o3d_registration_icp_submaps_overlap
+  Buf ov_srcn;                   // ... and the source's selected normals (Generalized ICP)
   O3dIcpWork reg;
 };
 struct RegPool {
@@ -1185,8 +1450,16 @@ inline int o3d_corr_pass(O3dIcpWork& w, int64_t Ns, const GridIndex& gi, double 
                        w.d_corr.as<int32_t>(), w.d_cert.as<O3dCert>(), w.d_far.as<O3dFarItem>(), counts);
   ++w.pass_no;
   w.corr_valid = true;
-  hipLaunchKernelGGL(k_o3d_corr<1>, dim3(w.nb), dim3(kB), 0, s, w.d_src.as<double>(), Ns, gi, w.tgt, w.tn, r2, mode,
-                     w.d_corr.as<int32_t>(), w.d_part.as<double>());
+  const int est = mode == 0 ? w.est : kEstPlane;  // the information matrix is the same sum for every estimation
+  if (est == kEstGicp)
+    hipLaunchKernelGGL((k_o3d_corr<1, kEstGicp>), dim3(w.nb), dim3(kB), 0, s, w.d_src.as<double>(), Ns, gi, w.tgt, w.tn, r2, mode,
+                       w.d_corr.as<int32_t>(), w.d_part.as<double>(), w.ea);
+  else if (est == kEstPoint)
+    hipLaunchKernelGGL((k_o3d_corr<1, kEstPoint>), dim3(w.nb), dim3(kB), 0, s, w.d_src.as<double>(), Ns, gi, w.tgt, w.tn, r2, mode,
+                       w.d_corr.as<int32_t>(), w.d_part.as<double>(), w.ea);
+  else
+    hipLaunchKernelGGL((k_o3d_corr<1, kEstPlane>), dim3(w.nb), dim3(kB), 0, s, w.d_src.as<double>(), Ns, gi, w.tgt, w.tn, r2, mode,
+                       w.d_corr.as<int32_t>(), w.d_part.as<double>(), w.ea);
   const bool post = w.h_post && w.h_post_dev;
   if (post && ++w.post_seq == 0) ++w.post_seq;
   hipLaunchKernelGGL(k_o3d_fold, dim3(kAccComps), dim3(64), 0, s, w.d_part.as<double>(), w.nb, w.d_sum.as<double>(), counts, post ? w.h_post_dev : nullptr,
@@ -1310,12 +1583,56 @@ void o3s_o3d_icp_default_criteria(o3s_o3d_icp_criteria* c) {
 namespace {
 using namespace o3s_cloud;
 
-// RegistrationICP for one pair on stream s (the device is already current on the calling thread); w: grow-only work area
+// What a registration other than point-to-plane reads besides the clouds (all nullable; device arrays when the clouds are)
+struct O3dEstIn {
+  int type = kEstPlane;
+  double eps = 1e-3;                 // TransformationEstimationForGeneralizedICP::epsilon_
+  const double* src_n = nullptr;     // GICP: the source's normals (3 per point) ...
+  const double* src_cov = nullptr;   // ... or covariances (9 per point, column-major), which win
+  const double* tgt_cov = nullptr;   // GICP: the target's covariances (else its normals)
+};
+// the two checks of o3s_o3d_estimation a call makes before it touches a device
+inline bool o3d_est_valid(const o3s_o3d_estimation* e) {
+  return e && (e->type == O3S_O3D_POINT_TO_PLANE || e->type == O3S_O3D_POINT_TO_POINT || e->type == O3S_O3D_GENERALIZED) && e->gicp_epsilon > 0.0;
+}
+
+// InitializePointCloudForGeneralizedICP of both clouds, after o3d_place_source: the source's covariances in search order
+// (untransformed: k_o3d_corr turns them), the target's in index order
+inline int o3d_gicp_covariances(O3dIcpWork& w, int64_t Ns, int64_t Nt, const O3dEstIn& e, bool on_device, hipStream_t s) {
+  const bool s_cov = e.src_cov != nullptr, t_cov = e.tgt_cov != nullptr;
+  const double* sin = s_cov ? e.src_cov : e.src_n;
+  const double* tin = t_cov ? e.tgt_cov : w.tn;  // target normals: already on the device (o3d_prepare)
+  if (!on_device) {
+    const size_t sb = (size_t)Ns * (s_cov ? 72 : 24);
+    CK(w.d_sraw.alloc(sb));
+    CK(hipMemcpyAsync(w.d_sraw.p, sin, sb, hipMemcpyHostToDevice, s));
+    sin = w.d_sraw.as<double>();
+    if (t_cov) {
+      CK(w.d_traw.alloc((size_t)Nt * 72));
+      CK(hipMemcpyAsync(w.d_traw.p, e.tgt_cov, (size_t)Nt * 72, hipMemcpyHostToDevice, s));
+      tin = w.d_traw.as<double>();
+    }
+  }
+  CK(w.d_scov.alloc((size_t)Ns * 48));
+  CK(w.d_tcov.alloc((size_t)Nt * 48));
+  hipLaunchKernelGGL(k_o3d_cov, dim3(nblk(Ns)), dim3(kB), 0, s, sin, s_cov ? 1 : 0, w.order, Ns, e.eps, w.d_scov.as<double>());
+  hipLaunchKernelGGL(k_o3d_cov, dim3(nblk(Nt)), dim3(kB), 0, s, tin, t_cov ? 1 : 0, (const uint32_t*)nullptr, Nt, e.eps, w.d_tcov.as<double>());
+  CK(hipGetLastError());
+  w.ea.scov = w.d_scov.as<double>();
+  w.ea.tcov = w.d_tcov.as<double>();
+  return O3S_OK;
+}
+
+// RegistrationICP for one pair on stream s (the device is already current on the calling thread); w: grow-only work area.
+// est (nullable: point-to-plane): the estimation; point-to-plane runs exactly the kernels and host arithmetic it always has.
 int o3d_icp_run(O3dIcpWork& w, const double* source, int64_t Ns, const double* target, const double* target_normals, int64_t Nt, double max_dist,
                 const double init[16], const o3s_o3d_icp_criteria* criteria, o3s_o3d_icp_result* result, hipStream_t s, bool on_device = false,
-                const unsigned long long* target_bounds = nullptr /*of the target, when the caller has them (build_grid_index)*/) {
+                const unsigned long long* target_bounds = nullptr /*of the target, when the caller has them (build_grid_index)*/,
+                const O3dEstIn* est = nullptr) {
   if (!source || !target || !init || !result || Ns <= 0 || Nt <= 0 || !(max_dist > 0.0)) return O3S_ERR_BAD_ARGUMENT;
-  if (!target_normals) return O3S_ERR_BAD_SHAPE;  // "requires target pointcloud to have normals"
+  const O3dEstIn e = est ? *est : O3dEstIn{};
+  if (e.type == kEstPlane && !target_normals) return O3S_ERR_BAD_SHAPE;  // "requires target pointcloud to have normals"
+  if (e.type == kEstGicp && ((!e.src_n && !e.src_cov) || (!target_normals && !e.tgt_cov))) return O3S_ERR_BAD_SHAPE;  // no KNN(20) normals here
   o3s_o3d_icp_criteria cr;
   o3s_o3d_icp_default_criteria(&cr);
   if (criteria) cr = *criteria;
@@ -1328,6 +1645,22 @@ int o3d_icp_run(O3dIcpWork& w, const double* source, int64_t Ns, const double* t
   std::memcpy(T, init, sizeof(T));
   rc = o3d_place_source(w, Ns, gi, init, s);
   if (rc != O3S_OK) return rc;
+  w.est = e.type;
+  // GICP: the rotation the source's covariances have gone through — init's (PointCloud::Transform(init), skipped for an identity),
+  // then every update's — applied where they are used (the covariances stay as placed: no 48 B per point rewritten per pass)
+  double Racc[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  if (e.type == kEstGicp) {
+    rc = o3d_gicp_covariances(w, Ns, Nt, e, on_device, s);
+    if (rc != O3S_OK) return rc;
+    if (!h_is_identity(init))
+      for (int c = 0; c < 3; ++c)
+        for (int r = 0; r < 3; ++r) Racc[c * 3 + r] = init[c * 4 + r];
+    std::memcpy(w.ea.R, Racc, sizeof(Racc));
+  } else if (e.type == kEstPoint) {
+    w.ea.c[0] = gi.g.ox + 0.5 * gi.g.nx * gi.g.cell;  // the centre of the target's grid
+    w.ea.c[1] = gi.g.oy + 0.5 * gi.g.ny * gi.g.cell;
+    w.ea.c[2] = gi.g.oz + 0.5 * gi.g.nz * gi.g.cell;
+  }
   double sums[kAccComps];
   rc = o3d_corr_pass(w, Ns, gi, r2, 0, sums, s);
   if (rc != O3S_OK) return rc;
@@ -1337,7 +1670,9 @@ int o3d_icp_run(O3dIcpWork& w, const double* source, int64_t Ns, const double* t
   for (int i = 0; i < cr.max_iteration; ++i) {
     double update[16];
     for (int k = 0; k < 16; ++k) update[k] = (k % 5 == 0) ? 1.0 : 0.0;
-    if (sums[29] > 0) {  // ComputeTransformation: empty correspondence set -> identity
+    if (sums[29] > 0 && e.type == kEstPoint) {  // ComputeTransformation: empty correspondence set -> identity
+      h_umeyama(sums, w.ea.c, update);
+    } else if (sums[29] > 0) {  // point-to-plane, GICP: SolveJacobianSystemAndObtainExtrinsicMatrix
       double JTJ[6][6], nb[6], x[6];
       int t = 0;
       for (int a = 0; a < 6; ++a)
@@ -1353,6 +1688,18 @@ int o3d_icp_run(O3dIcpWork& w, const double* source, int64_t Ns, const double* t
     double Tn[16];
     h_mul4(update, T, Tn);
     std::memcpy(T, Tn, sizeof(T));
+    if (e.type == kEstGicp) {  // TransformCovariances(update): R <- R_update R
+      double Rn[9];
+      for (int c = 0; c < 3; ++c)
+        for (int r = 0; r < 3; ++r) {
+          double v = update[r] * Racc[c * 3];
+          v = v + update[4 + r] * Racc[c * 3 + 1];
+          v = v + update[8 + r] * Racc[c * 3 + 2];
+          Rn[c * 3 + r] = v;
+        }
+      std::memcpy(Racc, Rn, sizeof(Racc));
+      std::memcpy(w.ea.R, Racc, sizeof(Racc));
+    }
     const double f0 = fitness(sums), e0 = rmse(sums);
     rc = o3d_corr_pass(w, Ns, gi, r2, 0, sums, s, update);  // pcd.Transform(update), then the correspondences at the new pose
     if (rc != O3S_OK) return rc;
@@ -1430,6 +1777,29 @@ int o3s_o3d_registration_icp(int device, const double* source, int64_t Ns, const
   if (rc != O3S_OK) return rc;
   RegLease area(device, nullptr);
   return area.end(o3d_icp_run(area->reg, source, Ns, target, target_normals, Nt, max_dist, init, criteria, result, nullptr));
+}
+
+void o3s_o3d_default_estimation(o3s_o3d_estimation* e) {
+  if (!e) return;
+  std::memset(e, 0, sizeof(*e));
+  e->type = O3S_O3D_GENERALIZED;
+  e->gicp_epsilon = 1e-3;
+}
+
+int o3s_o3d_registration_icp_ex(int device, const double* source, const double* source_normals, const double* source_cov, int64_t Ns,
+                                const double* target, const double* target_normals, const double* target_cov, int64_t Nt, double max_dist,
+                                const double init[16], const o3s_o3d_estimation* est, const o3s_o3d_icp_criteria* criteria, o3s_o3d_icp_result* result) {
+  if (!o3d_est_valid(est) || !source || !target || !init || !result || Ns <= 0 || Nt <= 0 || !(max_dist > 0.0)) return O3S_ERR_BAD_ARGUMENT;
+  O3dEstIn e;
+  e.type = est->type;
+  e.eps = est->gicp_epsilon;
+  e.src_n = source_normals;
+  e.src_cov = source_cov;
+  e.tgt_cov = target_cov;
+  const int rc = pick_device(device);
+  if (rc != O3S_OK) return rc;
+  RegLease area(device, nullptr);
+  return area.end(o3d_icp_run(area->reg, source, Ns, target, target_normals, Nt, max_dist, init, criteria, result, nullptr, false, nullptr, &e));
 }
 
 int o3s_o3d_information_matrix(int device, const double* source, int64_t Ns, const double* target, int64_t Nt, double max_dist, const double T[16],

@@ -187,7 +187,8 @@ __global__ void __launch_bounds__(64) k_ov_post(const uint32_t* __restrict__ fs,
 // selected target travel with the counts.
 struct OvSelect {
   const double* tgt_normals = nullptr;
-  double *out_src = nullptr, *out_tgt = nullptr, *out_tgt_n = nullptr;
+  const double* src_normals = nullptr;  // nullable: the source's normals are selected too (Generalized ICP builds its covariances from them)
+  double *out_src = nullptr, *out_tgt = nullptr, *out_tgt_n = nullptr, *out_src_n = nullptr;
   unsigned long long bounds[6] = {0, 0, 0, 0, 0, 0};  // of the selected target: minima, maxima (ordered bit patterns)
   bool have_bounds = false;  // ... and the two copies have been made
 };
@@ -264,8 +265,8 @@ inline int overlap_dev(OverlapWork& w, const double* d_src, int64_t Ns, const do
       const bool with_sel = sel && mailbox_enabled(pa);
       if (with_sel) {  // the two selections, enqueued before their sizes are known (the buffers hold either cloud whole)
         CK(hipMemsetAsync(bb, 0xFF, (size_t)kExtSlots * 6 * 8, s));
-        hipLaunchKernelGGL(k_compact, dim3(nblk(Ns)), dim3(kB), 0, s, d_src, (const double*)nullptr, Ns, (const uint32_t*)fs, (const uint32_t*)os, sel->out_src,
-                           (double*)nullptr, (int32_t*)nullptr);
+        hipLaunchKernelGGL(k_compact, dim3(nblk(Ns)), dim3(kB), 0, s, d_src, sel->src_normals, Ns, (const uint32_t*)fs, (const uint32_t*)os, sel->out_src,
+                           sel->out_src_n, (int32_t*)nullptr);
         hipLaunchKernelGGL(k_compact_bounds, dim3(std::min(nblk(Nt), 1024u)), dim3(kB), 0, s, d_tgt, sel->tgt_normals, Nt, (const uint32_t*)ft,
                            (const uint32_t*)ot, sel->out_tgt, sel->out_tgt_n, bb);
       }
@@ -363,26 +364,34 @@ int o3s_overlap_indices(int device, const double* source, int64_t Ns, const doub
 
 namespace {
 // the refinement of ONE pair on stream s (both submaps' own streams drained by the caller, the device current)
+// est_type: o3s_o3d_estimation_type (point-to-plane: the refinement as it always was); the source's normals are selected for GICP
 int refine_overlap_on(const o3s_submap* source, const o3s_submap* target, double max_dist, const double init[16], const o3s_o3d_icp_criteria* criteria,
                       double overlap_voxel_size, int64_t min_points_per_voxel, o3s_o3d_icp_result* result, double* info36, int64_t* n_overlap,
-                      hipStream_t s) {
+                      hipStream_t s, int est_type = o3s_cloud::kEstPlane, double gicp_epsilon = 1e-3) {
   using namespace o3s_cloud;
   int rc = O3S_OK;
+  const bool gicp = est_type == kEstGicp;
   const double* sp = source->pts[source->cur].d();
   const double* tp = target->pts[target->cur].d();
-  const double* tn = target->nrm[target->cur].d();
+  const double* tn = target->has_normals == 1 ? target->nrm[target->cur].d() : nullptr;
+  const double* sn = gicp ? source->nrm[source->cur].d() : nullptr;
   uint32_t *fs, *os, *ft, *ot;
   int64_t ns = 0, nt = 0;
   RegLease area(target->device, s);
+  if (gicp) CK(area->ov_srcn.alloc((size_t)source->n * 24));  // grows on the first GICP refinement of an area, then stays
   // with room for either cloud whole (o3s_o3d_registration_reserve) the two SelectByIndex copies and the bounds of the selected target
   // ride on the selection's own hand-over: no wait for the counts in front of the copies, none for the bounds in front of the index
+  // (a target without normals — point-to-point — takes the plain copies)
   OvSelect sel;
-  const bool roomy = area->ov_src.cap >= (size_t)source->n * 24 && area->ov_tgt.cap >= (size_t)target->n * 24 && area->ov_tgtn.cap >= (size_t)target->n * 24;
+  const bool roomy = tn && area->ov_src.cap >= (size_t)source->n * 24 && area->ov_tgt.cap >= (size_t)target->n * 24 &&
+                     area->ov_tgtn.cap >= (size_t)target->n * 24;
   if (roomy) {
     sel.tgt_normals = tn;
+    sel.src_normals = sn;
     sel.out_src = area->ov_src.as<double>();
     sel.out_tgt = area->ov_tgt.as<double>();
     sel.out_tgt_n = area->ov_tgtn.as<double>();
+    sel.out_src_n = gicp ? area->ov_srcn.as<double>() : nullptr;
   }
   rc = overlap_dev(area->ov, sp, source->n, tp, target->n, init, overlap_voxel_size, min_points_per_voxel, &fs, &os, &ns, &ft, &ot, &nt, s, roomy ? &sel : nullptr);
   if (rc != O3S_OK) return rc;
@@ -396,14 +405,18 @@ int refine_overlap_on(const o3s_submap* source, const o3s_submap* target, double
     CK(area->ov_src.alloc((size_t)ns * 24));
     CK(area->ov_tgt.alloc((size_t)nt * 24));
     CK(area->ov_tgtn.alloc((size_t)nt * 24));
-    hipLaunchKernelGGL(k_compact, dim3(nblk(source->n)), dim3(kB), 0, s, sp, (const double*)nullptr, source->n, fs, os, area->ov_src.as<double>(),
-                       (double*)nullptr, (int32_t*)nullptr);
+    hipLaunchKernelGGL(k_compact, dim3(nblk(source->n)), dim3(kB), 0, s, sp, sn, source->n, fs, os, area->ov_src.as<double>(),
+                       gicp ? area->ov_srcn.as<double>() : (double*)nullptr, (int32_t*)nullptr);
     hipLaunchKernelGGL(k_compact, dim3(nblk(target->n)), dim3(kB), 0, s, tp, tn, target->n, ft, ot, area->ov_tgt.as<double>(), area->ov_tgtn.as<double>(),
                        (int32_t*)nullptr);
     CK(hipGetLastError());
   }
-  rc = o3d_icp_run(area->reg, area->ov_src.as<double>(), ns, area->ov_tgt.as<double>(), area->ov_tgtn.as<double>(), nt, max_dist, init, criteria, result, s,
-                   /*on_device=*/true, sel.have_bounds ? sel.bounds : nullptr);
+  O3dEstIn e;
+  e.type = est_type;
+  e.eps = gicp_epsilon;
+  e.src_n = gicp ? area->ov_srcn.as<double>() : nullptr;
+  rc = o3d_icp_run(area->reg, area->ov_src.as<double>(), ns, area->ov_tgt.as<double>(), tn ? area->ov_tgtn.as<double>() : nullptr, nt, max_dist, init,
+                   criteria, result, s, /*on_device=*/true, sel.have_bounds ? sel.bounds : nullptr, &e);
   if (rc == O3S_OK && info36) rc = o3d_info_after_icp(area->reg, max_dist, result->transformation, info36, s);
   return area.end(rc);
 }
@@ -434,11 +447,12 @@ void reg_warm_lane_streams(int device) { (void)refine_streams().get(device, 0); 
 }  // namespace o3s_cloud
 }  // namespace
 
-extern "C" {
-
-int o3s_o3d_registration_icp_submaps_overlap(const o3s_submap* source, const o3s_submap* target, double max_dist, const double init[16],
-                                             const o3s_o3d_icp_criteria* criteria, double overlap_voxel_size, int64_t min_points_per_voxel,
-                                             o3s_o3d_icp_result* result, double* info36, int64_t* n_overlap) {
+namespace {
+// o3s_o3d_registration_icp_submaps_overlap[_ex]
+int refine_overlap_entry(const o3s_submap* source, const o3s_submap* target, double max_dist, const double init[16], const o3s_o3d_icp_criteria* criteria,
+                         double overlap_voxel_size, int64_t min_points_per_voxel, o3s_o3d_icp_result* result, double* info36, int64_t* n_overlap, int est_type,
+                         double gicp_epsilon) {
+  using namespace o3s_cloud;
   if (!source || !target || !init || !result || !(max_dist > 0.0) || !(overlap_voxel_size > 0.0) || min_points_per_voxel < 1)
     return O3S_ERR_BAD_ARGUMENT;
   if (source->device != target->device) return O3S_ERR_BAD_ARGUMENT;
@@ -446,18 +460,21 @@ int o3s_o3d_registration_icp_submaps_overlap(const o3s_submap* source, const o3s
   if (const int rs_ = submap_settle(source); rs_ != O3S_OK) return rs_;  // a pending insert is completed first
   if (const int rt_ = submap_settle(target); rt_ != O3S_OK) return rt_;
   if (source->n == 0 || target->n == 0) return O3S_ERR_EMPTY_REFERENCE;
-  if (target->has_normals != 1) return O3S_ERR_BAD_SHAPE;  // "requires target pointcloud to have normals"
+  if (est_type != kEstPoint && target->has_normals != 1) return O3S_ERR_BAD_SHAPE;  // "requires target pointcloud to have normals"
+  if (est_type == kEstGicp && source->has_normals != 1) return O3S_ERR_BAD_SHAPE;   // GICP's covariances come from the normals
   int rc = set_dev(target);
   if (rc != O3S_OK) return rc;
   CK(hipStreamSynchronize(source->stream));
   CK(hipStreamSynchronize(target->stream));
-  return refine_overlap_on(source, target, max_dist, init, criteria, overlap_voxel_size, min_points_per_voxel, result, info36, n_overlap, target->stream);
+  return refine_overlap_on(source, target, max_dist, init, criteria, overlap_voxel_size, min_points_per_voxel, result, info36, n_overlap, target->stream,
+                           est_type, gicp_epsilon);
 }
 
-int o3s_o3d_registration_icp_submaps_overlap_batch(int32_t n, const o3s_submap* const* sources, const o3s_submap* const* targets, double max_dist,
-                                                   const double* inits, const o3s_o3d_icp_criteria* criteria, double overlap_voxel_size,
-                                                   int64_t min_points_per_voxel, o3s_o3d_icp_result* results, double* infos, int64_t* n_overlaps,
-                                                   int32_t* statuses) {
+// o3s_o3d_registration_icp_submaps_overlap_batch[_ex]
+int refine_overlap_batch(int32_t n, const o3s_submap* const* sources, const o3s_submap* const* targets, double max_dist, const double* inits,
+                         const o3s_o3d_icp_criteria* criteria, double overlap_voxel_size, int64_t min_points_per_voxel, o3s_o3d_icp_result* results,
+                         double* infos, int64_t* n_overlaps, int32_t* statuses, int est_type, double gicp_epsilon) {
+  using namespace o3s_cloud;
   if (n < 0 || (n > 0 && (!sources || !targets || !inits || !results || !statuses)) || !(max_dist > 0.0) || !(overlap_voxel_size > 0.0) ||
       min_points_per_voxel < 1)
     return O3S_ERR_BAD_ARGUMENT;
@@ -486,9 +503,10 @@ int o3s_o3d_registration_icp_submaps_overlap_batch(int32_t n, const o3s_submap* 
   auto one = [&](int32_t k, hipStream_t s) {
     if (n_overlaps) n_overlaps[2 * k] = n_overlaps[2 * k + 1] = 0;
     if (sources[k]->n == 0 || targets[k]->n == 0) return (int)O3S_ERR_EMPTY_REFERENCE;
-    if (targets[k]->has_normals != 1) return (int)O3S_ERR_BAD_SHAPE;
+    if (est_type != kEstPoint && targets[k]->has_normals != 1) return (int)O3S_ERR_BAD_SHAPE;
+    if (est_type == kEstGicp && sources[k]->has_normals != 1) return (int)O3S_ERR_BAD_SHAPE;
     return refine_overlap_on(sources[k], targets[k], max_dist, inits + 16 * (size_t)k, criteria, overlap_voxel_size, min_points_per_voxel, &results[k],
-                             infos ? infos + 36 * (size_t)k : nullptr, n_overlaps ? n_overlaps + 2 * (size_t)k : nullptr, s);
+                             infos ? infos + 36 * (size_t)k : nullptr, n_overlaps ? n_overlaps + 2 * (size_t)k : nullptr, s, est_type, gicp_epsilon);
   };
   auto lane = [&](int l) {
     (void)hipSetDevice(device);
@@ -502,6 +520,41 @@ int o3s_o3d_registration_icp_submaps_overlap_batch(int32_t n, const o3s_submap* 
   for (int32_t k = 0; k < n; ++k)
     if (statuses[k] != O3S_OK && statuses[k] != O3S_ERR_EMPTY_REFERENCE) return statuses[k];
   return O3S_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int o3s_o3d_registration_icp_submaps_overlap(const o3s_submap* source, const o3s_submap* target, double max_dist, const double init[16],
+                                             const o3s_o3d_icp_criteria* criteria, double overlap_voxel_size, int64_t min_points_per_voxel,
+                                             o3s_o3d_icp_result* result, double* info36, int64_t* n_overlap) {
+  return refine_overlap_entry(source, target, max_dist, init, criteria, overlap_voxel_size, min_points_per_voxel, result, info36, n_overlap,
+                              o3s_cloud::kEstPlane, 1e-3);
+}
+
+int o3s_o3d_registration_icp_submaps_overlap_ex(const o3s_submap* source, const o3s_submap* target, double max_dist, const double init[16],
+                                                const o3s_o3d_estimation* est, const o3s_o3d_icp_criteria* criteria, double overlap_voxel_size,
+                                                int64_t min_points_per_voxel, o3s_o3d_icp_result* result, double* info36, int64_t* n_overlap) {
+  if (!o3d_est_valid(est)) return O3S_ERR_BAD_ARGUMENT;
+  return refine_overlap_entry(source, target, max_dist, init, criteria, overlap_voxel_size, min_points_per_voxel, result, info36, n_overlap, est->type,
+                              est->gicp_epsilon);
+}
+
+int o3s_o3d_registration_icp_submaps_overlap_batch(int32_t n, const o3s_submap* const* sources, const o3s_submap* const* targets, double max_dist,
+                                                   const double* inits, const o3s_o3d_icp_criteria* criteria, double overlap_voxel_size,
+                                                   int64_t min_points_per_voxel, o3s_o3d_icp_result* results, double* infos, int64_t* n_overlaps,
+                                                   int32_t* statuses) {
+  return refine_overlap_batch(n, sources, targets, max_dist, inits, criteria, overlap_voxel_size, min_points_per_voxel, results, infos, n_overlaps,
+                              statuses, o3s_cloud::kEstPlane, 1e-3);
+}
+
+int o3s_o3d_registration_icp_submaps_overlap_batch_ex(int32_t n, const o3s_submap* const* sources, const o3s_submap* const* targets, double max_dist,
+                                                      const double* inits, const o3s_o3d_estimation* est, const o3s_o3d_icp_criteria* criteria,
+                                                      double overlap_voxel_size, int64_t min_points_per_voxel, o3s_o3d_icp_result* results,
+                                                      double* infos, int64_t* n_overlaps, int32_t* statuses) {
+  if (!o3d_est_valid(est)) return O3S_ERR_BAD_ARGUMENT;
+  return refine_overlap_batch(n, sources, targets, max_dist, inits, criteria, overlap_voxel_size, min_points_per_voxel, results, infos, n_overlaps,
+                              statuses, est->type, est->gicp_epsilon);
 }
 
 }  // extern "C"

@@ -25,6 +25,20 @@ class _Pair(C.Structure):
                 ("target_normals", C.POINTER(C.c_double)), ("n_target", C.c_int64), ("init", C.c_double * 16)]
 
 
+class _Estimation(C.Structure):
+    _fields_ = [("type", C.c_int32), ("gicp_epsilon", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+# CloudRegistrationType (open3d_slam Parameters.hpp:37-42): the strings of scan_to_map_refinement_type -> o3s_o3d_estimation_type
+REGISTRATION_TYPES = {"PointToPlaneIcp": 0, "PointToPointIcp": 1, "GeneralizedIcp": 2}
+
+
+def _estimation(registration_type, epsilon=1e-3):
+    if registration_type not in REGISTRATION_TYPES:
+        raise ValueError(f"registration_type must be one of {sorted(REGISTRATION_TYPES)}, not {registration_type!r}")
+    return _Estimation(REGISTRATION_TYPES[registration_type], float(epsilon))
+
+
 @dataclass
 class RegistrationResult:
     transformation: np.ndarray
@@ -43,6 +57,10 @@ def _L():
         L.o3s_o3d_registration_icp.argtypes = [C.c_int, dp, C.c_int64, dp, dp, C.c_int64, C.c_double, dp, C.POINTER(_Criteria), C.POINTER(_Result)]
         L.o3s_o3d_information_matrix.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_double, dp, dp]
         L.o3s_o3d_registration_icp_submaps.argtypes = [C.c_void_p, C.c_void_p, C.c_double, dp, C.POINTER(_Criteria), C.POINTER(_Result), dp]
+        L.o3s_o3d_registration_icp_ex.argtypes = [C.c_int, dp, dp, dp, C.c_int64, dp, dp, dp, C.c_int64, C.c_double, dp, C.POINTER(_Estimation),
+                                                  C.POINTER(_Criteria), C.POINTER(_Result)]
+        L.o3s_o3d_default_estimation.argtypes = [C.POINTER(_Estimation)]
+        L.o3s_o3d_default_estimation.restype = None
         L.o3s_o3d_registration_icp_batch.argtypes = [C.c_int, C.c_int32, C.POINTER(_Pair), C.c_double, C.POINTER(_Criteria), C.POINTER(_Result), dp,
                                                      C.POINTER(C.c_int32)]
     return L
@@ -67,6 +85,65 @@ def registration_icp(source, target, target_normals, max_correspondence_distance
     if rc != _lib.OK:
         raise RuntimeError(f"o3s_o3d_registration_icp failed with o3s_status {rc}")
     return RegistrationResult(np.array(r.transformation).reshape(4, 4).T.copy(), r.fitness, r.inlier_rmse, int(r.correspondences), int(r.iterations))
+
+
+def _result(r):
+    return RegistrationResult(np.array(r.transformation).reshape(4, 4).T.copy(), r.fitness, r.inlier_rmse, int(r.correspondences), int(r.iterations))
+
+
+def _cloud(a, width):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, np.float64)
+    return a.reshape(a.shape[0], width) if width == 9 else a
+
+
+def _registration_icp_ex(est, source, target, max_correspondence_distance, init, source_normals, target_normals, source_covariances,
+                         target_covariances, relative_fitness, relative_rmse, max_iteration, device):
+    s_ = np.ascontiguousarray(source, np.float64)
+    t_ = np.ascontiguousarray(target, np.float64)
+    sn, tn = _cloud(source_normals, 3), _cloud(target_normals, 3)
+    sc, tc = _cloud(source_covariances, 9), _cloud(target_covariances, 9)
+    for a, n_, what in ((sn, s_.shape[0], "source normals"), (tn, t_.shape[0], "target normals"), (sc, s_.shape[0], "source covariances"),
+                        (tc, t_.shape[0], "target covariances")):
+        if a is not None and a.shape[0] != n_:
+            raise ValueError(f"{what}: {a.shape[0]} rows for {n_} points")
+    cr = _Criteria(float(relative_fitness), float(relative_rmse), int(max_iteration))
+    r = _Result()
+    rc = _L().o3s_o3d_registration_icp_ex(device, _d(s_), _d(sn), _d(sc), s_.shape[0], _d(t_), _d(tn), _d(tc), t_.shape[0],
+                                          float(max_correspondence_distance), _d(_pose(np.eye(4) if init is None else init)), C.byref(est),
+                                          C.byref(cr), C.byref(r))
+    if rc == _lib.ERR_BAD_SHAPE:
+        raise RuntimeError("the registration needs normals or covariances the clouds do not carry (point-to-plane: target normals; "
+                           "Generalized ICP: normals or covariances on both clouds)")
+    if rc != _lib.OK:
+        raise RuntimeError(f"o3s_o3d_registration_icp_ex failed with o3s_status {rc}")
+    return _result(r)
+
+
+def registration_generalized_icp(source, target, max_correspondence_distance, init=None, epsilon=1e-3, source_normals=None, target_normals=None,
+                                 source_covariances=None, target_covariances=None, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30,
+                                 device: int = 0) -> RegistrationResult:
+    """RegistrationGeneralizedICP(source, target, max_correspondence_distance, init, TransformationEstimationForGeneralizedICP(epsilon),
+    criteria) — the loop-closure refinement the reference's parameters select (CloudRegistration.cpp:16-21).  Each cloud needs normals
+    (covariances eps / 1 / 1 around them, the normal as given) or covariances (N x 3 x 3 or N x 9, column-major per point; they win)."""
+    return _registration_icp_ex(_estimation("GeneralizedIcp", epsilon), source, target, max_correspondence_distance, init, source_normals,
+                                target_normals, source_covariances, target_covariances, relative_fitness, relative_rmse, max_iteration, device)
+
+
+def registration_icp_point_to_point(source, target, max_correspondence_distance, init=None, relative_fitness=1e-6, relative_rmse=1e-6,
+                                    max_iteration=30, device: int = 0) -> RegistrationResult:
+    """RegistrationICP(source, target, max_correspondence_distance, init, TransformationEstimationPointToPoint(false), criteria)
+    (CloudRegistration.cpp:88-101): Eigen::umeyama over the correspondences, no normals needed."""
+    return _registration_icp_ex(_estimation("PointToPointIcp"), source, target, max_correspondence_distance, init, None, None, None, None,
+                                relative_fitness, relative_rmse, max_iteration, device)
+
+
+def default_estimation():
+    """o3s_o3d_default_estimation: (registration type name, epsilon) the reference's parameters select."""
+    e = _Estimation()
+    _L().o3s_o3d_default_estimation(C.byref(e))
+    return {v: k for k, v in REGISTRATION_TYPES.items()}[e.type], e.gicp_epsilon
 
 
 def get_information_matrix_from_point_clouds(source, target, max_correspondence_distance, transformation, device: int = 0) -> np.ndarray:
@@ -151,34 +228,51 @@ def compute_indices_of_overlapping_points(source, target, source_to_target, voxe
 
 def registration_icp_submaps_overlap(source_submap, target_submap, max_correspondence_distance, init, overlap_voxel_size,
                                      min_num_points_per_voxel: int = 1, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30,
-                                     with_information: bool = True):
+                                     with_information: bool = True, registration_type: str = "PointToPlaneIcp", gicp_epsilon: float = 1e-3):
     """The loop-closure refinement of PlaceRecognition::buildLoopClosureConstraints (PlaceRecognition.cpp:97-150) between two
     device-resident Submap objects: overlap selection at `init`, RegistrationICP on the selections, information matrix.
+    registration_type: the reference's CloudRegistrationType string ("PointToPlaneIcp", "PointToPointIcp", "GeneralizedIcp" — the
+    last is what its parameter sets select); the default keeps the point-to-plane refinement.
     Returns (RegistrationResult, information 6x6 or None, (n_source_overlap, n_target_overlap)); an empty overlap gives None."""
+    est = _estimation(registration_type, gicp_epsilon)
     cr = _Criteria(float(relative_fitness), float(relative_rmse), int(max_iteration))
     r = _Result()
     info = np.zeros(36) if with_information else None
     n_ov = (C.c_int64 * 2)()
     L = _L()
-    L.o3s_o3d_registration_icp_submaps_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(_Criteria), C.c_double,
-                                                           C.c_int64, C.POINTER(_Result), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    rc = L.o3s_o3d_registration_icp_submaps_overlap(source_submap._h, target_submap._h, float(max_correspondence_distance), _d(_pose(init)),
-                                                    C.byref(cr), float(overlap_voxel_size), int(min_num_points_per_voxel), C.byref(r), _d(info), n_ov)
+    if est.type == 0:
+        L.o3s_o3d_registration_icp_submaps_overlap.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(_Criteria),
+                                                               C.c_double, C.c_int64, C.POINTER(_Result), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        rc = L.o3s_o3d_registration_icp_submaps_overlap(source_submap._h, target_submap._h, float(max_correspondence_distance), _d(_pose(init)),
+                                                        C.byref(cr), float(overlap_voxel_size), int(min_num_points_per_voxel), C.byref(r), _d(info), n_ov)
+        name = "o3s_o3d_registration_icp_submaps_overlap"
+    else:
+        L.o3s_o3d_registration_icp_submaps_overlap_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(_Estimation),
+                                                                  C.POINTER(_Criteria), C.c_double, C.c_int64, C.POINTER(_Result), C.POINTER(C.c_double),
+                                                                  C.POINTER(C.c_int64)]
+        rc = L.o3s_o3d_registration_icp_submaps_overlap_ex(source_submap._h, target_submap._h, float(max_correspondence_distance), _d(_pose(init)),
+                                                           C.byref(est), C.byref(cr), float(overlap_voxel_size), int(min_num_points_per_voxel),
+                                                           C.byref(r), _d(info), n_ov)
+        name = "o3s_o3d_registration_icp_submaps_overlap_ex"
     if rc == _lib.ERR_EMPTY_REFERENCE:
         return None, None, (int(n_ov[0]), int(n_ov[1]))
     if rc == _lib.ERR_BAD_SHAPE:
-        raise RuntimeError("TransformationEstimationPointToPlane requires target normals")
+        raise RuntimeError("TransformationEstimationPointToPlane requires target normals" if est.type == 0 else
+                           f"{registration_type} needs normals the submaps do not carry")
     if rc != _lib.OK:
-        raise RuntimeError(f"o3s_o3d_registration_icp_submaps_overlap failed with o3s_status {rc}")
+        raise RuntimeError(f"{name} failed with o3s_status {rc}")
     res = RegistrationResult(np.array(r.transformation).reshape(4, 4).T.copy(), r.fitness, r.inlier_rmse, int(r.correspondences), int(r.iterations))
     return res, (info.reshape(6, 6).T.copy() if with_information else None), (int(n_ov[0]), int(n_ov[1]))
 
 
 def registration_icp_submaps_overlap_batch(pairs, max_correspondence_distance, overlap_voxel_size, min_num_points_per_voxel: int = 1,
-                                           relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30):
+                                           relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30, registration_type: str = "PointToPlaneIcp",
+                                           gicp_epsilon: float = 1e-3):
     """o3s_o3d_registration_icp_submaps_overlap_batch: the loop-closure refinement for several (source Submap, target Submap, init)
-    triples at once, up to four in flight on the device.  Returns a list of (RegistrationResult | None, information 6x6 | None,
-    (n_source_overlap, n_target_overlap), status) — None for a pair whose overlap is empty."""
+    triples at once, up to four in flight on the device.  registration_type as in registration_icp_submaps_overlap.  Returns a list
+    of (RegistrationResult | None, information 6x6 | None, (n_source_overlap, n_target_overlap), status) — None for a pair whose
+    overlap is empty (or, with status O3S_ERR_BAD_SHAPE, whose submaps lack the normals the type needs)."""
+    est = _estimation(registration_type, gicp_epsilon)
     n = len(pairs)
     if n == 0:
         return []
@@ -191,13 +285,23 @@ def registration_icp_submaps_overlap_batch(pairs, max_correspondence_distance, o
     novs = (C.c_int64 * (2 * n))()
     sts = (C.c_int32 * n)()
     L = _L()
-    L.o3s_o3d_registration_icp_submaps_overlap_batch.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_double, C.POINTER(C.c_double),
-                                                                 C.POINTER(_Criteria), C.c_double, C.c_int64, C.POINTER(_Result), C.POINTER(C.c_double),
-                                                                 C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-    rc = L.o3s_o3d_registration_icp_submaps_overlap_batch(n, srcs, tgts, float(max_correspondence_distance), _d(inits), C.byref(cr), float(overlap_voxel_size),
-                                                          int(min_num_points_per_voxel), res, _d(infos), novs, sts)
+    if est.type == 0:
+        L.o3s_o3d_registration_icp_submaps_overlap_batch.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_double,
+                                                                     C.POINTER(C.c_double), C.POINTER(_Criteria), C.c_double, C.c_int64, C.POINTER(_Result),
+                                                                     C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        rc = L.o3s_o3d_registration_icp_submaps_overlap_batch(n, srcs, tgts, float(max_correspondence_distance), _d(inits), C.byref(cr),
+                                                              float(overlap_voxel_size), int(min_num_points_per_voxel), res, _d(infos), novs, sts)
+        name = "o3s_o3d_registration_icp_submaps_overlap_batch"
+    else:
+        L.o3s_o3d_registration_icp_submaps_overlap_batch_ex.argtypes = [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_double,
+                                                                        C.POINTER(C.c_double), C.POINTER(_Estimation), C.POINTER(_Criteria), C.c_double,
+                                                                        C.c_int64, C.POINTER(_Result), C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                                                        C.POINTER(C.c_int32)]
+        rc = L.o3s_o3d_registration_icp_submaps_overlap_batch_ex(n, srcs, tgts, float(max_correspondence_distance), _d(inits), C.byref(est), C.byref(cr),
+                                                                 float(overlap_voxel_size), int(min_num_points_per_voxel), res, _d(infos), novs, sts)
+        name = "o3s_o3d_registration_icp_submaps_overlap_batch_ex"
     if rc != _lib.OK:
-        raise RuntimeError(f"o3s_o3d_registration_icp_submaps_overlap_batch failed with o3s_status {rc}")
+        raise RuntimeError(f"{name} failed with o3s_status {rc}")
     out = []
     for k in range(n):
         nov = (int(novs[2 * k]), int(novs[2 * k + 1]))

@@ -1,0 +1,161 @@
+"""CPU checks of the point-to-point and Generalized ICP registrations (include/o3s_registration.h, o3s_submap.h): the test
+restatement (tests/o3d_registration_ref.py) against the oracle's point-to-plane loop, GICP's covariance from a normal, the C
+declarations from plain C99, and the argument checks that refuse before any device call."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+from scipy.linalg import sqrtm
+
+from oracle import oracle as orc
+from open3d_slam_advanced_rss_2024_public_amd import _lib
+from open3d_slam_advanced_rss_2024_public_amd import registration as reg
+from open3d_slam_advanced_rss_2024_public_amd import synthetic as syn
+
+from o3d_registration_ref import covariances_from_normals, inv_sqrt_spd, registration_icp as ref_icp
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def pair(ns=3000, nt=5000, seed=3, noise=0.005):
+    world = syn.make_world(9000.0, seed=seed)
+    T = syn.make_T(syn.rot_axis_angle([0, 0, 1], 0.3), np.array([1.0, 2.0, 1.5]))
+    tp, tn = syn.make_scan(world, nt, T, radius=12.0, sigma=0.0, seed=seed + 1)
+    tgt = tp.astype(np.float64) @ T[:3, :3].T + T[:3, 3]
+    tgt_n = tn.astype(np.float64) @ T[:3, :3].T
+    sp, sn = syn.make_scan(world, ns, T, radius=10.0, sigma=noise, seed=seed + 2)
+    return sp.astype(np.float64), tgt, tgt_n, T, sn.astype(np.float64)
+
+
+@pytest.mark.parametrize("max_dist,max_iter", [(1.0, 30), (0.3, 30), (2.0, 3)])
+def test_restatement_point_to_plane_equals_oracle(max_dist, max_iter):
+    """The restatement's loop (NN, radius test, stop rule, pose composition) is pinned to the oracle's C++ RegistrationICP."""
+    src, tgt, tgt_n, T_gt, _ = pair()
+    init = syn.perturb_pose(T_gt, 0.1, 2.0, seed=5)
+    r = ref_icp(src, tgt, max_dist, init, "PointToPlaneIcp", target_normals=tgt_n, max_iteration=max_iter)
+    o = orc.o3d_registration_icp(src, tgt, tgt_n, max_dist, init, max_iteration=max_iter)
+    assert r["iterations"] == o["iterations"] and r["correspondences"] == o["correspondences"] and r["fitness"] == o["fitness"]
+    assert abs(r["inlier_rmse"] - o["inlier_rmse"]) <= 1e-9 * max(1.0, o["inlier_rmse"])
+    assert np.abs(r["transformation"] - o["transformation"]).max() <= 1e-9
+
+
+def test_covariance_from_normal():
+    """InitializePointCloudForGeneralizedICP's C = Rx diag(eps, 1, 1) Rx^T, Rx = GetRotationFromE1ToX(n)."""
+    eps = 1e-3
+    C1 = covariances_from_normals(np.array([[1.0, 0.0, 0.0]]), eps)[0]
+    assert np.allclose(C1, np.diag([eps, 1.0, 1.0]), atol=1e-15)
+    rng = np.random.default_rng(1)
+    n = rng.normal(size=(50, 3))
+    n /= np.linalg.norm(n, axis=1)[:, None]
+    n = n[n[:, 0] >= -0.99]
+    Cn = covariances_from_normals(n, eps)
+    want = eps * n[:, :, None] * n[:, None, :] + np.eye(3)[None] - n[:, :, None] * n[:, None, :]
+    assert np.abs(Cn - want).max() < 1e-12
+    # e1 . n < -0.99: Open3D's identity branch — diag(eps, 1, 1) whatever the normal
+    Cb = covariances_from_normals(np.array([[-0.995, 0.0998, 0.0]]), eps)[0]
+    assert np.array_equal(Cb, np.diag([eps, 1.0, 1.0]))
+    # a non-unit normal (a voxel's mean of unit normals) follows the formula, not the normalised one
+    m = np.array([[0.6, 0.5, 0.1]])
+    v = np.array([0.0, -0.1, 0.5])
+    S = np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]])
+    Rx = np.eye(3) + S + S @ S / (1.0 + 0.6)
+    Cm = covariances_from_normals(m, eps)[0]
+    assert np.abs(Cm - Rx @ np.diag([eps, 1, 1]) @ Rx.T).max() < 1e-15
+    u = m / np.linalg.norm(m)
+    assert np.abs(Cm - (eps * u.T @ u + np.eye(3) - u.T @ u)).max() > 1e-3
+
+
+def test_inverse_square_root_is_sqrtm():
+    """The restatement's W = M^-1.sqrt() equals scipy's sqrtm(inv(M)) on GICP-shaped covariance sums."""
+    rng = np.random.default_rng(2)
+    n = rng.normal(size=(20, 3))
+    n /= np.linalg.norm(n, axis=1)[:, None]
+    M = covariances_from_normals(n[:10]) + covariances_from_normals(n[10:])
+    W = inv_sqrt_spd(M)
+    for k in range(10):
+        assert np.abs(W[k] - np.real(sqrtm(np.linalg.inv(M[k])))).max() < 1e-9 * np.abs(W[k]).max()
+
+
+def test_restatement_types_converge():
+    """Point-to-point and GICP of the restatement land on the ground truth of a pair with 30 iterations."""
+    src, tgt, tgt_n, T_gt, src_n = pair(2000, 4000, seed=7)
+    init = syn.perturb_pose(T_gt, 0.1, 2.0, seed=5)
+    for kind, kw in (("PointToPointIcp", {}), ("GeneralizedIcp", {"source_normals": src_n, "target_normals": tgt_n})):
+        r = ref_icp(src, tgt, 1.0, init, kind, **kw)
+        dt, ang = orc.pose_error(T_gt, r["transformation"])
+        assert np.linalg.norm(dt) < 0.03 and ang < 0.01, (kind, dt, ang)
+
+
+def test_headers_compile_as_c99_and_link():
+    """A C99 translation unit with both headers calls the three new entry points (bad arguments: no device is touched) and links
+    against the built library."""
+    _lib.build()
+    src = r"""
+#include "o3s_registration.h"
+#include "o3s_submap.h"
+#include <stdio.h>
+int main(void) {
+  o3s_o3d_estimation e;
+  o3s_o3d_icp_criteria cr;
+  o3s_o3d_icp_result res;
+  double init[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, pts[3] = {0, 0, 0};
+  int32_t st = 0;
+  o3s_o3d_default_estimation(&e);
+  o3s_o3d_icp_default_criteria(&cr);
+  if (e.type != O3S_O3D_GENERALIZED || e.gicp_epsilon != 1e-3) return 10;
+  e.type = 7;
+  if (o3s_o3d_registration_icp_ex(0, pts, pts, NULL, 1, pts, pts, NULL, 1, 1.0, init, &e, &cr, &res) != O3S_ERR_BAD_ARGUMENT) return 11;
+  if (o3s_o3d_registration_icp_submaps_overlap_ex(NULL, NULL, 1.0, init, &e, &cr, 2.0, 1, &res, NULL, NULL) != O3S_ERR_BAD_ARGUMENT) return 12;
+  if (o3s_o3d_registration_icp_submaps_overlap_batch_ex(0, NULL, NULL, 1.0, init, &e, &cr, 2.0, 1, &res, NULL, NULL, &st) != O3S_ERR_BAD_ARGUMENT)
+    return 13;
+  printf("ok\n");
+  return 0;
+}
+"""
+    import tempfile
+
+    with tempfile.TemporaryDirectory() as d:
+        c = os.path.join(d, "t.c")
+        exe = os.path.join(d, "t")
+        open(c, "w").write(src)
+        libdir = os.path.dirname(_lib.variant_path(None))
+        subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), c, "-o", exe, "-L", libdir,
+                        "-l:libo3dslam_icp_hip.so", "-Wl,-rpath," + libdir], check=True)
+        out = subprocess.run([exe], capture_output=True, text=True)
+        assert out.returncode == 0 and out.stdout.strip() == "ok", (out.returncode, out.stdout, out.stderr)
+
+
+def test_bad_estimation_is_refused_without_a_device():
+    """An unknown type, epsilon <= 0, NULL clouds or a NULL estimation: O3S_ERR_BAD_ARGUMENT before any device call (this machine may
+    have none)."""
+    L = reg._L()
+    dp = C.POINTER(C.c_double)
+    pts = np.zeros((4, 3))
+    init = np.eye(4).reshape(16)
+    cr = reg._Criteria(1e-6, 1e-6, 30)
+    res = reg._Result()
+
+    def call(e, s=pts, t=pts):
+        return L.o3s_o3d_registration_icp_ex(0, reg._d(s), reg._d(pts), None, 4, reg._d(t), reg._d(pts), None, 4, 1.0, init.ctypes.data_as(dp),
+                                             None if e is None else C.byref(e), C.byref(cr), C.byref(res))
+
+    assert call(reg._Estimation(7, 1e-3)) == _lib.ERR_BAD_ARGUMENT
+    assert call(reg._Estimation(-1, 1e-3)) == _lib.ERR_BAD_ARGUMENT
+    assert call(reg._Estimation(2, 0.0)) == _lib.ERR_BAD_ARGUMENT
+    assert call(reg._Estimation(0, -1e-3)) == _lib.ERR_BAD_ARGUMENT
+    assert call(reg._Estimation(2, float("nan"))) == _lib.ERR_BAD_ARGUMENT
+    assert call(None) == _lib.ERR_BAD_ARGUMENT
+    assert call(reg._Estimation(2, 1e-3), s=None) == _lib.ERR_BAD_ARGUMENT
+    assert call(reg._Estimation(1, 1e-3), t=None) == _lib.ERR_BAD_ARGUMENT
+    sub = reg._L().o3s_o3d_registration_icp_submaps_overlap_ex
+    sub.argtypes = [C.c_void_p, C.c_void_p, C.c_double, dp, C.POINTER(reg._Estimation), C.POINTER(reg._Criteria), C.c_double, C.c_int64,
+                    C.POINTER(reg._Result), dp, C.POINTER(C.c_int64)]
+    assert sub(None, None, 1.0, init.ctypes.data_as(dp), C.byref(reg._Estimation(7, 1e-3)), C.byref(cr), 2.0, 1, C.byref(res), None, None) == \
+        _lib.ERR_BAD_ARGUMENT
+    assert sub(None, None, 1.0, init.ctypes.data_as(dp), C.byref(reg._Estimation(2, 1e-3)), C.byref(cr), 2.0, 1, C.byref(res), None, None) == \
+        _lib.ERR_BAD_ARGUMENT
+    with pytest.raises(ValueError):
+        reg._estimation("Icp")
+    assert reg.default_estimation() == ("GeneralizedIcp", 1e-3)
