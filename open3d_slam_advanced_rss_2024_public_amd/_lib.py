@@ -21,10 +21,9 @@ def variant_path(variant: str | None) -> str:
 
 
 # The product library is libo3dslam_icp_hip.so: no environment variable reaches it (no getenv in the binary).  Builds with
-# extra -D flags live beside it as libo3dslam_icp_hip_<name>.so (`make -C csrc hooks|ts|variant`):
+# extra -D flags live beside it as libo3dslam_icp_hip_<name>.so (`make -C csrc hooks`):
 #   hooks  -DO3S_TEST_HOOKS: the test hooks and tuning knobs (O3S_SCATTER_ORDER, O3S_FUSE, O3S_SEL_PARTIAL, O3S_NO_HINT, O3S_DBG, ...)
 #          read from the environment; tests that need them load it through `with _lib.variant("hooks"):`
-#   ts     in-kernel phase stamps (tools/ts.py)
 # O3S_LIB_VARIANT=<name> makes <name> the default library of the process (A/B runs of tools/, the whole suite on the hooks build).
 _variant = os.environ.get("O3S_LIB_VARIANT") or None
 LIB_PATH = variant_path(_variant)

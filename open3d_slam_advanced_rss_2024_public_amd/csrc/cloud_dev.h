@@ -99,20 +99,6 @@ int pick_device(int device) {
   return O3S_OK;
 }
 
-// Streams by role: `side` = the receiving side (staging a raw sweep, pre-processing a scan), everything else is the mapping
-// thread's critical path.  Experiment switch (hooks build): O3S_X_PRIO=1 side streams at the lowest priority, 2: main streams at the highest
-// as well, 3: only the main streams raised.
-inline hipError_t make_stream(hipStream_t* s, bool side) {
-  const char* e = O3S_HOOK_ENV("O3S_X_PRIO");
-  const int mode = e ? atoi(e) : 0;
-  int least = 0, greatest = 0;
-  if (mode && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
-    if (side && (mode == 1 || mode == 2)) return hipStreamCreateWithPriority(s, hipStreamNonBlocking, least);
-    if (!side && (mode == 2 || mode == 3)) return hipStreamCreateWithPriority(s, hipStreamNonBlocking, greatest);
-  }
-  return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-}
-
 // ---- kernels ---------------------------------------------------------------------------------------------------
 // getVoxelIdx(p, InverseVoxelSize): int(std::floor(p * inv))  (VoxelHashMap.hpp:48-51)
 __global__ void __launch_bounds__(kB) k_voxel_idx(const double* __restrict__ pts, int64_t n3, double inv, int32_t* __restrict__ idx) {

@@ -26,21 +26,6 @@ namespace kern {
 
 constexpr int kBlock = 256;
 
-// Phase timestamps for tuning (build with -DO3S_TS; read with o3s_debug_ts).  Not part of the product build.
-#ifdef O3S_TS
-__device__ unsigned long long g_ts[64];
-#define O3S_TSTAMP(k)                                                     \
-  do {                                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                    \
-    if (blockIdx.x == 0 && threadIdx.x == 0) {                            \
-      __builtin_amdgcn_s_waitcnt(0);                                      \
-      g_ts[k] = __builtin_amdgcn_s_memtime();                             \
-    }                                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                    \
-  } while (0)
-#else
-#define O3S_TSTAMP(k)
-#endif
 constexpr float kInfF = __builtin_huge_valf();
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -558,13 +543,10 @@ __global__ void __launch_bounds__(kBlock) k_read_prep(const float4* __restrict__
                                                       uint32_t* __restrict__ tile_cnt /*points per tile of kScanTile bins*/,
                                                       int32_t* __restrict__ perm /*no sort: slot -> original index = identity*/) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
-  O3S_TSTAMP(56);
   if (init.hist) {  // uniform
     const int stride = gridDim.x * kBlock;
-#ifndef O3S_X_NOZERO
     for (int k = i; k < init.hist_words; k += stride) init.hist[k] = 0u;
     for (int k = i; k < init.sel_words; k += stride) init.sel[k] = 0u;
-#endif
     if (blockIdx.x == 0) {
       constexpr int kWords = (int)(sizeof(IcpState) / 4);
       uint32_t* w = reinterpret_cast<uint32_t*>(init.state);
@@ -591,11 +573,8 @@ __global__ void __launch_bounds__(kBlock) k_read_prep(const float4* __restrict__
     __syncthreads();
   }
   int my_tile = -1;
-  O3S_TSTAMP(57);
   if (i < N) {
-#ifndef O3S_X_NOMQ
     if (init.mq) init.mq[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
     const float4 p = in_xyzw[i];
     float T[16];
 #pragma unroll
@@ -610,7 +589,6 @@ __global__ void __launch_bounds__(kBlock) k_read_prep(const float4* __restrict__
       tny[i] = rot_row(T, 1, a, b, c);
       tnz[i] = rot_row(T, 2, a, b, c);
     }
-    O3S_TSTAMP(58);
     if (counts) {
       const int cx = cell_coord(x, g.ox, g.inv_cell, g.nx);
       const int cy = cell_coord(y, g.oy, g.inv_cell, g.ny);
@@ -628,12 +606,10 @@ __global__ void __launch_bounds__(kBlock) k_read_prep(const float4* __restrict__
       perm[i] = i;
     }
   }
-  O3S_TSTAMP(59);
   if (counts) {  // uniform
     __syncthreads();
     if (my_tile >= 0) atomicAdd(&tile_cnt[(blockIdx.x & (kTileReplicas - 1)) * kMaxQTiles + my_tile], s_tile[my_tile]);
   }
-  O3S_TSTAMP(60);
 }
 
 // Starts of the reading's bins (exclusive scan of the per-bin counts) in ONE launch: block b owns tile b (kScanTile bins); its
@@ -901,41 +877,14 @@ __device__ __forceinline__ void group_min_di(float d, int idx, float& gd, int& g
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int kFarMaxCells = 4096;  // the host selects the ring search when maxDist reaches beyond this many cells (or is unbounded)
 
-// Bound sharing between neighbouring queries of a wave.  The reading is sorted by grid cell, so the queries a wave holds lie
-// next to each other, and ANY reference point is an upper bound of a query's nearest-neighbour distance: a lane takes the best
-// point its neighbours (the next two queries on either side) have found so far, measures its own distance to it and tightens
-// its pruning bound — never its match: the bound only decides which rows, cells and records are skipped, and it is never below
-// the distance of an existing reference point within maxDist, which is all the exactness argument asks for.  In a first
-// iteration (no incumbents) this is what spares a query the full-radius walk its neighbour has just made.
-template <int G>
-__device__ __forceinline__ float neighbour_bound(const Own& b, float sx, float sy, float sz, float lim, float bound) {
-  const int lane = (int)(threadIdx.x & 63);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int off = (k & 1 ? -1 : 1) * (k < 2 ? G : 2 * G);
-    const int src = min(max(lane + off, 0), 63);
-    const float nd = __shfl(b.d, src, 64), nx = __shfl(b.qx, src, 64), ny = __shfl(b.qy, src, 64), nz = __shfl(b.qz, src, 64);
-    const float dn = dist2(sx, sy, sz, nx, ny, nz);
-    bound = (nd < kInfF && dn <= lim) ? fminf(bound, dn) : bound;  // NaN / no find: unchanged
-  }
-  return bound;
-}
-
-// G lanes per query (4 at C2: 6 k waves fill the chip; 1 for large readings, where the per-query set-up that every lane
-// of a group repeats is the larger part of the work); UN candidate rounds per batch of loads.
+// G lanes per query (4 below 65 536 points: 6 k waves fill the chip; 2 for larger readings, where the per-query set-up that
+// every lane of a group repeats is the larger part of the work); UN candidate rounds per batch of loads.
 // RCB: ring candidates per round trip (2: the kernel stays at <= 72 VGPRs; 8 was measured and bought nothing).
 // FAR: queries that the 3 x 3 x 3 cells leave open go through the occupancy words (finite maxDist) instead of the ring search.
+constexpr int kFarWaves = 5;  // waves per SIMD the far variant is compiled for: 6 spills (80 VGPRs + 8-12 B of scratch), 5 does not and is as fast
+constexpr int kFarQ = 6;      // ranges per batch of the row-disc search (4: 53.9 us, 6: 50.6 us, 8: no better, for the first iteration at C2)
 template <bool STATS, int G, int UN, int RCB, bool FAR>
-#ifndef O3S_FAR_WAVES
-#define O3S_FAR_WAVES 5  // waves per SIMD the far variant is compiled for: 6 spills (80 VGPRs + 8-12 B of scratch), 5 does not and is as fast
-#endif
-#ifndef O3S_SHARE_BOUNDS
-#define O3S_SHARE_BOUNDS 0  // 1: neighbouring queries of a wave share what they have found as pruning bounds (neighbour_bound) — measured in round 4: slower (C2 first iteration 40.7 -> 45.1 us, C4 unchanged)
-#endif
-#ifndef O3S_FAR_Q
-#define O3S_FAR_Q 6  // ranges per batch of the row-disc search (4: 53.9 us, 6: 50.6 us, 8: no better, for the first iteration at C2)
-#endif
-__global__ void __launch_bounds__(kBlock, FAR ? O3S_FAR_WAVES : 7) k_match2(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz,
+__global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz,
                                                       int N, const float4* __restrict__ ref, const uint32_t* __restrict__ cell_start,
                                                       GridParams g, IcpState* __restrict__ st,
                                                       int32_t* __restrict__ pos_out, float* __restrict__ d2_out, float4* __restrict__ mq,
@@ -1139,15 +1088,6 @@ __global__ void __launch_bounds__(kBlock, FAR ? O3S_FAR_WAVES : 7) k_match2(cons
     }
   }
   group_min_di<G>(b.d, b.idx, gd, gi);
-  // what the queries next door found in their 27 cells — only in waves that hold a query without an incumbent (a first iteration,
-  // unmatched points): with incumbents everywhere the bound is tight already and the converged path stays as short as it was
-  if (FAR && O3S_SHARE_BOUNDS && __any(valid && inc.w == 0.f)) {
-    bound = neighbour_bound<G>(b, sx, sy, sz, lim, bound);
-    // every lane's value is a valid bound of the group's query: all lanes of a group go on with the smallest, so that whether the
-    // query enters the far search is one decision per query
-    if (G >= 2) bound = fminf(bound, __int_as_float(dpp_i32<0xB1>(__float_as_int(bound))));
-    if (G >= 4) bound = fminf(bound, __int_as_float(dpp_i32<0x4E>(__float_as_int(bound))));
-  }
   // ---- rings r >= 2: only queries whose bound / best reaches beyond the 3x3x3 block (far prior, no incumbent).  Ring 2
   //      lies at least cell - margin away, which settles almost every query without looking at its geometry again; the
   //      exact ring bounds are only worked out (from the query, not kept alive across the common path) when some lane of
@@ -1158,7 +1098,7 @@ __global__ void __launch_bounds__(kBlock, FAR ? O3S_FAR_WAVES : 7) k_match2(cons
   }
   if (FAR) {
     if (__any(active)) {
-      constexpr int Q = O3S_FAR_Q;  // ranges fetched per batch of loads
+      constexpr int Q = kFarQ;  // ranges fetched per batch of loads
       const CellGeom c = cell_geom(sx, sy, sz, g);
       const float m_yz = fminf(fminf(c.ly, g.cell - c.ly), fminf(c.lz, g.cell - c.lz));
       // rings that hold rows of the grid at all (a query outside the grid in y or z starts further out)
@@ -1286,7 +1226,6 @@ __global__ void __launch_bounds__(kBlock, FAR ? O3S_FAR_WAVES : 7) k_match2(cons
         }
         group_min_di<G>(b.d, b.idx, gd, gi);
         best = fminf(best, gd);
-        if (O3S_SHARE_BOUNDS) best = neighbour_bound<G>(b, sx, sy, sz, lim, best);  // ... and in the ring they have just walked
         if (active) {
           rho += 1;
           if (rho > rho_max || ring_lb2_yz(rho) > best) active = false;
@@ -1499,7 +1438,6 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
   using Sum = BlockSum<kCentComps, kClsBlock>;
   __shared__ double s_a[Sum::kWordsA];
   __shared__ double s_b[Sum::kWordsB];
-  O3S_TSTAMP(40);
   const float hv = hdr_load(st);
   // this thread's point and the level-1 histogram (8 replicas) are fetched in the same round trip as the header
   const int i = blockIdx.x * kClsBlock + threadIdx.x;
@@ -1538,7 +1476,6 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
       sp3[p] = *reinterpret_cast<const uint2*>(spec + p * kSpecHalf + 1024 + 2 * threadIdx.x);
     }
   }
-  O3S_TSTAMP(41);
   if (hdr_i(hv, H_DONE)) return;
   float T[16];
 #pragma unroll
@@ -1551,7 +1488,6 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
     if (matched && refn) rn = refn[slot0];
     if (inb) mn[i] = rn;
   }
-  O3S_TSTAMP(42);
   // ---- rank-k bin: every block repeats the same integer arithmetic on the same summed histogram ----
   uint32_t mine = 0;
 #pragma unroll
@@ -1656,7 +1592,6 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
 #endif
   }
   if (cp.has_trim && n_fin == 0) return;
-  O3S_TSTAMP(43);
   // ---- per-pair weights ----
   bool keep = matched && pe0 >= 0;  // caller-supplied zero weights arrive as pos <= -2 (module-level minimise)
   if (gate && matched) {  // w = (n_read . n_ref < cos(maxAngle)) ? 0 : 1 on the ROTATED reading normal
@@ -1683,7 +1618,6 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
   //      (~2 000 atomics spread over 1 024 addresses), so the single finishing block starts from a ready histogram. ----
   const unsigned long long umask = __ballot(undecided);
   if ((threadIdx.x & 63) == 0) s_wcnt[threadIdx.x >> 6] = (uint32_t)__popcll(umask);
-  O3S_TSTAMP(44);
   // ---- fp64 sums of the decided-kept pairs ----
   if (mode & kModeCentroid) {  // uniform
     double a[kCentComps];
@@ -1723,7 +1657,6 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
     }
     if (threadIdx.x == 0) cand_cnt[blockIdx.x] = cnt;
   }
-  O3S_TSTAMP(45);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1988,17 +1921,9 @@ __global__ void __launch_bounds__(kFinThreads) k_sel_partial(const IcpState* __r
 
 // The body of k_sel_finish as a block-wide device function, so that k_sel_ne can run it in EVERY block in front of the
 // normal equations (FUSED): all blocks then hold the same limit and means — the same integers, the same fixed-order fp64
-// sums — without a kernel boundary in between; only block 0 publishes them to the state.  Returns false when the iteration
-// ends here (chain done, an earlier error, no pair kept); otherwise s_out = {limit, mean of the reading points (3), mean of
-// the matched points (3)} is valid after the caller's next barrier.
-// What the fused kernel's blocks form for themselves instead of publishing it field by field (see solve_body)
-struct SolveOverride {
-  float limit, mp[3], mq[3];
-  int32_t kept;
-  int32_t status;     // != 0: this launch found that the iteration cannot go on (no pair kept): 6
-  int32_t has_limit;  // the limit above supersedes the state's
-};
-
+// sums — without a kernel boundary in between; only block 0 publishes them to the state (for k_solve, as the single-block
+// k_sel_finish does).  Returns false when the iteration ends here (chain done, an earlier error, no pair kept); otherwise
+// s_out = {limit, mean of the reading points (3), mean of the matched points (3)} is valid after the caller's next barrier.
 template <bool FUSED>
 __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep, const ChainParams& cp, IcpState* __restrict__ st,
                                                 const SelScratch* __restrict__ ss, const CandRec* __restrict__ cand,
@@ -2007,11 +1932,8 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
                                                 const double* __restrict__ part /*[7][nb]*/, int nb, int mode, float hv, float* s_out /*[8], LDS*/,
                                                 const double* __restrict__ part2 = nullptr /*[7][nbp]: k_sel_partial ran in front (large readings)*/,
                                                 int nbp = 0, const CandRec* __restrict__ park_rec = nullptr, const uint32_t* __restrict__ park_key = nullptr,
-                                                uint32_t* __restrict__ park_cnt = nullptr, SolveOverride* s_ov = nullptr /*LDS, FUSED only*/,
-                                                bool tail = false /*FUSED: the launch closes the iteration itself*/) {
-  // with the closing tail the fused kernel's last block writes limit / means / |K| with the rest of the state (solve_body);
-  // without it block 0 publishes them for k_solve, as the single-block k_sel_finish does
-  const bool publish = !FUSED || (!tail && blockIdx.x == 0);
+                                                uint32_t* __restrict__ park_cnt = nullptr) {
+  const bool publish = !FUSED || blockIdx.x == 0;
   extern __shared__ __align__(16) uint32_t s_dyn[];  // kSelCap words: the level-3 list, then the final block sum
   __shared__ uint32_t s_bins[1024];
   __shared__ uint32_t s_tmp[64];
@@ -2021,7 +1943,6 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
   static_assert((Sum::kWordsA + Sum::kWordsB) * 8 <= kSelCap * 4, "the block sum borrows the selection buffer");
   double* s_a = reinterpret_cast<double*>(s_dyn);
   double* s_b = s_a + Sum::kWordsA;
-  O3S_TSTAMP(0);
   // first round trip: header, hand-off words, this thread's share of the classify partials, candidate counts, level 2
   const uint32_t ssw = reinterpret_cast<const uint32_t*>(ss)[threadIdx.x & 15];
   double a[kCentComps] = {0, 0, 0, 0, 0, 0, 0};
@@ -2044,7 +1965,6 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
   for (int b = b0 + kCntRegs; b < b1; ++b) my_cnt += cand_cnt[b];  // larger readings: re-read below
   const uint2 h2 = *reinterpret_cast<const uint2*>(hist2 + 2 * threadIdx.x);
   const uint32_t parked_before = park_cnt ? *park_cnt : 0u;  // what k_sel_partial appended (uniform)
-  O3S_TSTAMP(1);
   if (hdr_i(hv, H_DONE)) return false;
   if (hist_rep) {  // NULL when k_normal_eq clears the replicas (the fused chain); uniform
     __syncthreads();  // every thread holds its level-2 words before anyone clears them
@@ -2064,7 +1984,6 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
   // candidates are the few pairs that share the 21-bit prefix, and bin / kk describe that prefix).
   const bool resolved = s_ssw[kSelWordDepth] == 32u;
   float limit = kInfF;
-  O3S_TSTAMP(2);
   if (!skip && resolved) limit = __uint_as_float(s_ssw[kSelWordLimit]);
   if (!skip && !resolved) {  // uniform
     uint32_t* s_base = nb <= kBaseCap ? s_base_lds : base_scratch;
@@ -2172,7 +2091,6 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
       if (total <= (uint32_t)(kFinThreads * kFinPerSmall)) sel_sweep<kFinPerSmall>(cand, s_base, nb, total, prefix21, s_dyn, s_tmp, mode, a);
       else sel_sweep<kFinPerBig>(cand, s_base, nb, total, prefix21, s_dyn, s_tmp, mode, a);
     }
-    O3S_TSTAMP(3);
     __syncthreads();
     const uint32_t m = s_tmp[43];  // parked = undecided candidates (typically a handful)
     if (m <= (uint32_t)kParkBits) {
@@ -2196,7 +2114,6 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
       __syncthreads();
       lbits = (prefix21 << 10) | s_tmp[44];
     }
-    O3S_TSTAMP(5);
     if (mode & kModeCentroid) {  // the parked candidates with d2 <= limit join the sums (ties at the limit are all kept)
       if (m <= (uint32_t)kParkRecs) {
         // They were parked in arrival order; they are added in FLAT order so that repeated runs form the same sums:
@@ -2241,12 +2158,10 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
     }
     limit = __uint_as_float(lbits);
   }
-  O3S_TSTAMP(6);
   if (mode & kModeCentroid) {  // uniform
     __syncthreads();  // the selection is done with s_dyn
     Sum::run(a, s_a, s_b);
   }
-  O3S_TSTAMP(7);
   // publish: lanes 0..5 each own one mean (fixed-order block sum of their component and of the count, one division);
   // lane 0 also owns limit / |K| / status.
   const int status = hdr_i(hv, H_STATUS);
@@ -2257,29 +2172,17 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
       const float lim_out = (!cp.has_trim || !skip) ? limit : hdr_f(hv, H_LIMIT);
       if (publish && (!cp.has_trim || !skip)) st->limit = limit;
       s_out[0] = lim_out;
-      if (s_ov) {
-        s_ov->limit = limit;
-        s_ov->has_limit = (!cp.has_trim || !skip) ? 1 : 0;
-        s_ov->status = 0;
-        s_ov->kept = hdr_i(hv, H_KEPT);
-      }
-    }
-    if (s_ov) {  // means of an iteration that ends here: the state's stay
-      if (threadIdx.x < 3) s_ov->mp[threadIdx.x] = hdr_f(hv, H_MP + threadIdx.x);
-      else s_ov->mq[threadIdx.x - 3] = hdr_f(hv, H_MQ + threadIdx.x - 3);
     }
     if (status != 0) {
       if (publish && threadIdx.x == 0) st->done = 1;
     } else if (mode & kModeCentroid) {
       const double sk = Sum::total(s_b, threadIdx.x), K = Sum::total(s_b, 6);
       if (publish && threadIdx.x == 0) st->kept = (int32_t)K;
-      if (s_ov && threadIdx.x == 0) s_ov->kept = (int32_t)K;
       if (K == 0.0) {  // "no point to minimize" (ErrorMinimizer.cpp:75-77)
         if (publish && threadIdx.x == 0) {
           st->status = 6;
           st->done = 1;
         }
-        if (s_ov && threadIdx.x == 0) s_ov->status = 6;
       } else {  // rowwise().mean(): fp64 sums rounded once to fp32
         const float mean = (float)(sk / K);
         s_out[1 + threadIdx.x] = mean;
@@ -2287,14 +2190,9 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
           if (threadIdx.x < 3) st->mp[threadIdx.x] = mean;
           else st->mq[threadIdx.x - 3] = mean;
         }
-        if (s_ov) {
-          if (threadIdx.x < 3) s_ov->mp[threadIdx.x] = mean;
-          else s_ov->mq[threadIdx.x - 3] = mean;
-        }
       }
     }
   }
-  O3S_TSTAMP(8);
   return go_on;
 }
 
@@ -2333,14 +2231,12 @@ __global__ void __launch_bounds__(kBlock) k_normal_eq(const float* __restrict__ 
   using Sum = BlockSum<kNeComps, kBlock>;
   __shared__ double s_a[Sum::kWordsA];
   __shared__ double s_b[Sum::kWordsB];
-  O3S_TSTAMP(32);
   const float hv = hdr_load(st);
   if (hdr_i(hv, H_DONE)) return;
   // the level-1 histogram was consumed by k_classify; clearing it for the next k_match here spreads the stores over all
   // blocks of this kernel instead of loading them onto the one block of k_sel_finish
   if (hist_zero)
     for (int k = blockIdx.x * kBlock + threadIdx.x; k < kHistReplicas * kHistBins + 1024; k += gridDim.x * kBlock) hist_zero[k] = 0u;  // + level 2
-  O3S_TSTAMP(33);
   float T[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) T[k] = hdr_f(hv, k);
@@ -2404,25 +2300,27 @@ __global__ void __launch_bounds__(kBlock) k_normal_eq(const float* __restrict__ 
       for (int a = 0; a < 6; ++a) acc[21 + a] += (double)(gv[a] * h);
     }
   }
-  O3S_TSTAMP(34);
   Sum::run(acc, s_a, s_b);
-  O3S_TSTAMP(35);
   if (threadIdx.x < kNeComps) part[threadIdx.x * gridDim.x + blockIdx.x] = Sum::total(s_b, threadIdx.x);
-  O3S_TSTAMP(36);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
 // The end of an iteration: reduce the 27 x nb block partials in block order, solve, build the step, update T_iter, run the
-// checkers, write the state back and tell the host.  A block-wide device function (NT threads, all of them call it) so that
-// it can run as a kernel of its own (k_solve) or as the tail of k_sel_ne in the block that stored its partials last.
+// checkers, write the state back and tell the host.  A block-wide device function (kBlock threads, all of them call it): the body
+// of k_solve, which closes every iteration of the chain, and of the sharded chain's k_solve_shard.  (Closing the iteration in
+// the last block of k_sel_ne instead was built and measured slower: LAB_NOTES_r04.md §2.)
 //   LDS   SolveLds (BlockSum scratch, the 6x6 work area, the state staged through LDS: lane 0 then works on LDS only)
-//   ov    (nullable) values this block formed itself in this launch and that supersede the state's: the fused kernel's blocks
-//         do not publish limit / means / |K| one by one — the closing block writes them with the rest of the state
+//   ov    (nullable) values formed in this launch that supersede the state's: the sharded chain's front forms the sums, limit,
+//         means and |K| itself and does not publish them one by one — solve_body writes them with the rest of the state
 //   post  (nullable) host-coherent HostPost: when the chain is done, the whole state and then the word the host polls
 //         (system-scope release) — instead of a copy command and a stream synchronisation
-//   SC1   the partials were handed over INSIDE this launch (stored write-through by the other blocks): every load of them
-//         bypasses this CU's L1 (relaxed agent-scope loads), which takes the place of an acquire fence
 // ------------------------------------------------------------------------------------------------------------------
+struct SolveOverride {
+  float limit, mp[3], mq[3];
+  int32_t kept;
+  int32_t status;     // != 0: this launch found that the iteration cannot go on (no pair kept): 6
+  int32_t has_limit;  // the limit above supersedes the state's
+};
 struct SolveLds {
   double s_a[BlockSum<kNeComps, kBlock>::kWordsA];
   double s_b[BlockSum<kNeComps, kBlock>::kWordsB];
@@ -2448,16 +2346,13 @@ __device__ __forceinline__ void post_state(const IcpState* S /*LDS*/, const IcpS
   }
 }
 
-template <int NT, bool SC1>
 __device__ __forceinline__ void solve_body(const double* __restrict__ part, int nb, int N, const ChainParams& cp, IcpState* __restrict__ st,
                                            float* __restrict__ trace_T, float* __restrict__ trace_limit, int64_t* __restrict__ trace_kept,
                                            int trace_cap, int update_pose, HostPost* __restrict__ post, SolveLds& L, const SolveOverride* ov /*LDS or null*/) {
   using Sum = BlockSum<kNeComps, kBlock>;
-  static_assert(NT >= kBlock, "the partial sums are folded by the first kBlock threads");
   constexpr int kWords = (int)(sizeof(IcpState) / 4);
   IcpState& s_st = L.st;
-  O3S_TSTAMP(16);
-  for (int k = threadIdx.x; k < kWords; k += NT) reinterpret_cast<uint32_t*>(&s_st)[k] = reinterpret_cast<const uint32_t*>(st)[k];
+  for (int k = threadIdx.x; k < kWords; k += kBlock) reinterpret_cast<uint32_t*>(&s_st)[k] = reinterpret_cast<const uint32_t*>(st)[k];
   // partials: thread t takes the 27 sums of block t (and of block t + 256 for readings beyond 131 k points).  The loads are
   // branch-free (clamped address, value masked afterwards: a predicated load compiles to an exec-mask region with its own
   // s_waitcnt, i.e. one memory round trip per component) and coalesced along the block index; the 27 x 256 values are
@@ -2471,26 +2366,19 @@ __device__ __forceinline__ void solve_body(const double* __restrict__ part, int 
 #pragma unroll
     for (int c = 0; c < kNeComps; ++c) v[c] = 0.0;
     if (t < kBlock) {
-      auto ld = [&](int idx) -> double {
-        if (SC1) return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(part) + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        return part[idx];
-      };
 #pragma unroll
-      for (int c = 0; c < kNeComps; ++c) v[c] = ld(c * nb + min(t, nbm1));
+      for (int c = 0; c < kNeComps; ++c) v[c] = part[c * nb + min(t, nbm1)];
 #pragma unroll
       for (int c = 0; c < kNeComps; ++c) v[c] = t < nb ? v[c] : 0.0;
       if (nb > kBlock) {  // uniform
         double u[kNeComps];
 #pragma unroll
-        for (int c = 0; c < kNeComps; ++c) u[c] = ld(c * nb + min(t + kBlock, nbm1));
+        for (int c = 0; c < kNeComps; ++c) u[c] = part[c * nb + min(t + kBlock, nbm1)];
 #pragma unroll
         for (int c = 0; c < kNeComps; ++c) v[c] += (t + kBlock < nb) ? u[c] : 0.0;
       }
     }
-    O3S_TSTAMP(24);
-    O3S_TSTAMP(25);
-    if (NT == kBlock) Sum::run(v, L.s_a, L.s_b);
-    else Sum::run_first(v, L.s_a, L.s_b);
+    Sum::run(v, L.s_a, L.s_b);
     if (t < kNeComps) L.s_sum[t] = Sum::total(L.s_b, t);
   }
   if (ov && threadIdx.x == 0) {  // what this launch formed: the state's copy is a launch old (barrier above: the staging is complete)
@@ -2519,7 +2407,6 @@ __device__ __forceinline__ void solve_body(const double* __restrict__ part, int 
     s_st.b[a] = v;
   }
   __syncthreads();
-  O3S_TSTAMP(17);
   if (s_st.done) {  // uniform.  Set by an EARLIER kernel of this iteration (an error found there) and not told yet: tell the host
     if (post && !s_st.posted) {
       if (threadIdx.x == 0) {
@@ -2534,7 +2421,6 @@ __device__ __forceinline__ void solve_body(const double* __restrict__ part, int 
     return;
   }
   const bool failed = s_st.status != 0;  // uniform: the state sits in LDS
-  O3S_TSTAMP(18);
   // the fast path's two halves side by side: lane 0 factors and solves, lane 64 (the next wave) factors again and bounds the
   // condition number — x is used only if both say yes, else lane 0 runs the reference's general sequence
   if (!failed && (threadIdx.x == 0 || threadIdx.x == 64)) {
@@ -2571,7 +2457,6 @@ __device__ __forceinline__ void solve_body(const double* __restrict__ part, int 
       } else {
         branch = dev::solve_sys6_general(W);
       }
-      O3S_TSTAMP(19);
       const float* x = W.x;
       float* dT = S->dT;
       if (O3S_CP_DBG(cp, 16)) { for (int k = 0; k < 16; ++k) dT[k] = (k % 5 == 0) ? 1.f : 0.f; } else dev::build_step(x, S->mp, S->mq, dT);
@@ -2610,9 +2495,7 @@ __device__ __forceinline__ void solve_body(const double* __restrict__ part, int 
     if (threadIdx.x == 0) {
       IcpState* S = &s_st;
       bool iterate = true;
-      O3S_TSTAMP(20);
       int status = dev::run_checkers(S, cp, L.Tn, &iterate);
-      O3S_TSTAMP(21);
       S->iter = it + 1;
       // the next iteration starts with transformations.apply(stepReading, T_iter) -> checkParameters (TransformationsImpl.cpp:73-74)
       if (status == 0 && iterate && !dev::rigid_ok(L.Tn)) status = 8;
@@ -2629,11 +2512,9 @@ __device__ __forceinline__ void solve_body(const double* __restrict__ part, int 
     s_st.t_end = wall_clock64();
   }
   __syncthreads();
-  O3S_TSTAMP(22);
   // cand_count / row_count (the last words) are only ever touched by k_match's atomics: leave them alone
-  for (int k = threadIdx.x; k < kWords - kStateTailWords; k += NT) reinterpret_cast<uint32_t*>(st)[k] = reinterpret_cast<const uint32_t*>(&s_st)[k];
+  for (int k = threadIdx.x; k < kWords - kStateTailWords; k += kBlock) reinterpret_cast<uint32_t*>(st)[k] = reinterpret_cast<const uint32_t*>(&s_st)[k];
   if (post && s_st.done) post_state(&s_st, st, post);
-  O3S_TSTAMP(23);
 }
 
 // k_solve — the closing step as a launch of its own (the two-kernel chain of large readings and of batches, the sharded chain,
@@ -2642,7 +2523,7 @@ __global__ void __launch_bounds__(kBlock) k_solve(const double* __restrict__ par
                                                   float* __restrict__ trace_T, float* __restrict__ trace_limit, int64_t* __restrict__ trace_kept,
                                                   int trace_cap, int update_pose, HostPost* __restrict__ post) {
   __shared__ SolveLds lds;
-  solve_body<kBlock, false>(part, nb, N, cp, st, trace_T, trace_limit, trace_kept, trace_cap, update_pose, post, lds, nullptr);
+  solve_body(part, nb, N, cp, st, trace_T, trace_limit, trace_kept, trace_cap, update_pose, post, lds, nullptr);
 }
 
 // k_sel_ne = k_sel_finish + k_normal_eq in one launch, for readings whose normal equations fit ONE generation of blocks
@@ -2655,10 +2536,7 @@ __global__ void __launch_bounds__(kBlock) k_solve(const double* __restrict__ par
 constexpr int kFusedMaxBlocks = 256;   // one block per CU (the selection's LDS plan fills most of a CU's LDS)
 // The normal-equation half uses the first kBlock (256) threads with kNePPT points each and the same fixed-order block sum
 // as k_normal_eq: with the same number of blocks the 27 x blocks partials — and therefore the pose — are bit-identical to the
-// two-kernel chain's (o3s_icp_compute_batch runs that one; a pair must not depend on how it was issued).
-// TAIL: the block that stores its partials last closes the iteration itself (solve_body; measured slower, LAB_NOTES_r04.md 2: only
-// the hooks build launches it); without it k_solve follows, and the instantiation carries none of the closing step's registers.
-template <bool TAIL>
+// two-kernel chain's (o3s_icp_compute_batch runs that one; a pair must not depend on how it was issued).  k_solve follows.
 __global__ void __launch_bounds__(kFinThreads) k_sel_ne(ChainParams cp, IcpState* __restrict__ st, SelScratch* __restrict__ ss,
                                                         const CandRec* __restrict__ cand, const uint32_t* __restrict__ cand_cnt,
                                                         const uint32_t* __restrict__ hist2, uint32_t* __restrict__ base_scratch,
@@ -2666,15 +2544,9 @@ __global__ void __launch_bounds__(kFinThreads) k_sel_ne(ChainParams cp, IcpState
                                                         const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz, int N,
                                                         const float4* __restrict__ mq, const float4* __restrict__ mn, const int32_t* __restrict__ pos,
                                                         const float* __restrict__ d2, double* __restrict__ part_ne /*[27][grid]*/,
-                                                        uint32_t* __restrict__ hist_zero /*level-1 replicas*/,
-                                                        float* __restrict__ trace_T, float* __restrict__ trace_limit, int64_t* __restrict__ trace_kept,
-                                                        int trace_cap, HostPost* __restrict__ post) {
-  constexpr bool tail = TAIL;
+                                                        uint32_t* __restrict__ hist_zero /*level-1 replicas*/) {
   extern __shared__ __align__(16) uint32_t s_dyn[];
   __shared__ float s_out[8];
-  __shared__ SolveOverride s_ov;
-  __shared__ uint32_t s_ticket;
-  static_assert(sizeof(SolveLds) <= kSelCap * 4, "the closing step borrows the selection buffer");
   using Sum = BlockSum<kNeComps, kBlock>;
   static_assert((Sum::kWordsA + Sum::kWordsB) * 8 <= kSelCap * 4, "the 27-component block sum borrows the selection buffer");
   static_assert(kFinThreads >= kBlock, "the normal-equation half runs on the first kBlock threads");
@@ -2697,16 +2569,9 @@ __global__ void __launch_bounds__(kFinThreads) k_sel_ne(ChainParams cp, IcpState
     n[u] = mn[ic];
   }
   if (hdr_i(hv, H_DONE)) return;  // the chain has ended in an earlier iteration: nothing to close
-  const bool go_on = sel_finish_body<true>(nullptr, cp, st, ss, cand, cand_cnt, hist2, base_scratch, part_cent, nb_cls, mode, hv, s_out, nullptr, 0, nullptr,
-                                           nullptr, nullptr, &s_ov, tail != 0);
-  __syncthreads();     // s_out / s_ov are complete, the selection is done with s_dyn
-  if (!go_on) {        // uniform, and the same in every block: an earlier error, or no pair kept — block 0 closes the iteration
-    if constexpr (TAIL)
-      if (blockIdx.x == 0)
-        solve_body<kFinThreads, false>(part_ne, (int)gridDim.x, N, cp, st, trace_T, trace_limit, trace_kept, trace_cap, 1, post,
-                                     *reinterpret_cast<SolveLds*>(s_dyn), &s_ov);
-    return;
-  }
+  const bool go_on = sel_finish_body<true>(nullptr, cp, st, ss, cand, cand_cnt, hist2, base_scratch, part_cent, nb_cls, mode, hv, s_out);
+  __syncthreads();        // s_out is complete, the selection is done with s_dyn
+  if (!go_on) return;     // uniform, and the same in every block: an earlier error, or no pair kept — k_solve closes the iteration
   if (hist_zero)
     for (int k = blockIdx.x * kFinThreads + threadIdx.x; k < kHistReplicas * kHistBins; k += gridDim.x * kFinThreads) hist_zero[k] = 0u;
   float T[16];
@@ -2747,27 +2612,7 @@ __global__ void __launch_bounds__(kFinThreads) k_sel_ne(ChainParams cp, IcpState
   double* s_a = reinterpret_cast<double*>(s_dyn);
   double* s_b = s_a + Sum::kWordsA;
   Sum::run_first(acc, s_a, s_b);
-  // ---- hand-over inside the launch (cdna_hip_programming.md, Guideline 16, counter form): the 27 partials go out write-through
-  //      (agent-scope stores), every wave drains its stores, the block's barrier, ONE relaxed agent-scope add to the ticket; the
-  //      block that draws the last ticket reads all partials with L1-bypassing loads (solve_body<.., true>), folds them in block
-  //      order — the order k_solve folds them in, same bits — and closes the iteration: one launch boundary less per iteration.
-  if constexpr (!TAIL) {  // k_solve folds the partials behind the launch boundary
-    if (threadIdx.x < kNeComps) part_ne[threadIdx.x * gridDim.x + blockIdx.x] = Sum::total(s_b, threadIdx.x);
-    return;
-  } else {
-  if (threadIdx.x < kNeComps)
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(part_ne) + threadIdx.x * gridDim.x + blockIdx.x,
-                       (unsigned long long)__double_as_longlong(Sum::total(s_b, threadIdx.x)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) s_ticket = __hip_atomic_fetch_add(&ss->ne_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  if (s_ticket != gridDim.x - 1u) return;  // uniform
-  if (threadIdx.x == 0) __hip_atomic_store(&ss->ne_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next iteration (k_read_prep zeroes it per call)
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: keeps the compiler from moving the loads below above the ticket
-  solve_body<kFinThreads, true>(part_ne, (int)gridDim.x, N, cp, st, trace_T, trace_limit, trace_kept, trace_cap, 1, post,
-                                *reinterpret_cast<SolveLds*>(s_dyn), &s_ov);
-  }
+  if (threadIdx.x < kNeComps) part_ne[threadIdx.x * gridDim.x + blockIdx.x] = Sum::total(s_b, threadIdx.x);  // k_solve folds them in block order
 }
 
 // ------------------------------------------------------------------------------------------------------------------

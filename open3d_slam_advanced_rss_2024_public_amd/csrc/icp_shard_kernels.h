@@ -306,7 +306,6 @@ __device__ __forceinline__ bool shard_solve_front(const ChainParams& cp, const I
                                                   uint32_t* __restrict__ l2, const double* __restrict__ xm, int nb_part, float hv, SolveLds& L,
                                                   SolveOverride& ov, uint32_t* s_tmp, double* s_tot /*[kMom]*/) {
   if (hdr_i(hv, H_DONE)) return false;
-  O3S_TSTAMP(48);
   const int status = hdr_i(hv, H_STATUS);
   const uint32_t skip = ss->skip;
   const bool sel = status == 0 && !skip;
@@ -315,7 +314,6 @@ __device__ __forceinline__ bool shard_solve_front(const ChainParams& cp, const I
   if (sel) {  // uniform
     const uint32_t d1 = ss->pad[0];  // level-2 digit and the rank inside it: block 0 of k_shard_moments left them
     uint32_t kk = ss->pad[1];
-    O3S_TSTAMP(49);
     // level 3: 128 bins, one per lane of the first two waves; the counts were summed as doubles (exact)
     const uint32_t c3 = threadIdx.x < kShardL3Bins ? (uint32_t)xm[kXmCnt + threadIdx.x] : 0u;
     uint32_t tot3;
@@ -329,7 +327,6 @@ __device__ __forceinline__ bool shard_solve_front(const ChainParams& cp, const I
     limit = __uint_as_float((ss->bin << 20) | (d1 << kShardL3Bits) | d0);
   }
   for (int k = threadIdx.x; k < kShardL2Bins; k += kBlock) l2[k] = 0u;  // k_shard_moments was its last reader: ready for the next iteration's k_classify
-  O3S_TSTAMP(50);
   // moments: block partials in block order, then the bins up to the digit in bin order — one fixed-order block sum per half
   const int nbm1 = nb_part > 0 ? nb_part - 1 : 0;
   const int t = threadIdx.x;
@@ -364,7 +361,6 @@ __device__ __forceinline__ bool shard_solve_front(const ChainParams& cp, const I
     if (t < 17) s_tot[half * 17 + t] = MomSum::total(L.s_b, t);
   }
   __syncthreads();
-  O3S_TSTAMP(51);
   if (t == 0) {
     ov.limit = limit;
     ov.has_limit = (!cp.has_trim || !skip) ? 1 : 0;
@@ -482,7 +478,6 @@ __device__ __forceinline__ bool shard_solve_front(const ChainParams& cp, const I
     }
   }
   __syncthreads();
-  O3S_TSTAMP(52);
   return true;
 }
 
@@ -497,8 +492,7 @@ __global__ void __launch_bounds__(kBlock) k_solve_shard(ChainParams cp, IcpState
   __shared__ double s_tot[kMom];
   const float hv = hdr_load(st);
   const bool formed = shard_solve_front(cp, st, ss, l2, xm, nb_part, hv, lds, s_ov, s_tmp, s_tot);
-  solve_body<kBlock, false>(nullptr, 0, N_total, cp, st, trace_T, trace_limit, trace_kept, trace_cap, 1, post, lds, formed ? &s_ov : nullptr);
-  O3S_TSTAMP(53);
+  solve_body(nullptr, 0, N_total, cp, st, trace_T, trace_limit, trace_kept, trace_cap, 1, post, lds, formed ? &s_ov : nullptr);
 }
 
 }  // namespace kern

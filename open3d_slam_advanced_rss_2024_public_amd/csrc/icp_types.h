@@ -119,7 +119,7 @@ struct SelScratch {
   uint32_t kk;                // rank inside that bin
   uint32_t bin_count;
   uint32_t skip;              // 1: nothing to select (no Trimmed filter, or no finite match)
-  uint32_t ne_ticket;         // k_sel_ne: blocks that have stored their 27 partial sums (the last one closes the iteration)
+  uint32_t reserved;          // unused: keeps the words below at their offsets
   uint32_t pad[3];            // sharded chain: [0] the level-2 digit, [1] the rank inside it (k_shard_moments -> k_solve_shard)
   uint32_t depth;             // leading bits of the limit k_classify resolved: 11 (bin only), 21 (bin + level-2 digit: bin / kk above
                               // are then the 21-bit prefix's bin and the rank inside the prefix), 32 (the limit itself, limit_bits)

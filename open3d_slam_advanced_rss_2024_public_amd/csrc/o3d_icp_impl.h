@@ -1397,8 +1397,7 @@ inline int o3d_place_source(O3dIcpWork& w, int64_t Ns, const GridIndex& gi, cons
 // (PointCloud::Transform(update), Registration.cpp RegistrationICP), then the correspondences and the sums.
 inline int o3d_corr_pass(O3dIcpWork& w, int64_t Ns, const GridIndex& gi, double r2, int mode, double* sums /*kAccComps*/, hipStream_t s,
                          const double* update = nullptr) {
-  int G = 4;  // lanes per source point in the search
-  if (const char* e = O3S_HOOK_ENV("O3S_O3D_G")) G = atoi(e);
+  constexpr int G = 4;  // lanes per source point in the search
   const unsigned nbs = (unsigned)((Ns * G + kB - 1) / kB);
   int kdbg = 0;  // hooks build: timing only: 1 = no own cell, 2 = no shell 1, 4 = no incumbent; 64 = certificates ignored (results stay valid)
   if (const char* e = O3S_HOOK_ENV("O3S_O3D_KDBG")) kdbg = atoi(e);
@@ -1408,15 +1407,13 @@ inline int o3d_corr_pass(O3dIcpWork& w, int64_t Ns, const GridIndex& gi, double 
   // how far beyond what exactness needs a search looks (O3dReach): 10 % of the radius without a neighbour, 2 % of it beyond one
   const double r = std::sqrt(r2);
   O3dReach rc;
-  double beyond = 1.1;
-  if (const char* e = O3S_HOOK_ENV("O3S_O3D_BEYOND")) beyond = atof(e);  // hooks build: A/B
+  constexpr double beyond = 1.1;
   rc.r2o = (beyond * r) * (beyond * r);
   {
     const double shells = std::ceil(beyond * r / gi.g.cell) + 1.0;
     rc.r_cap = (std::isfinite(shells) && shells < 1.0e9) ? (int)shells : 0x7fffffff;
   }
   rc.pad = 0.02 * r;  // closed-loop run, ms per refinement with pads of 0 / 1.5 / 3 / 6 / 10 %: 1.72 / 1.58 / 1.61 / 1.70 / 1.70 (the 8-pass one)
-  if (const char* e = O3S_HOOK_ENV("O3S_O3D_PAD")) rc.pad = atof(e) * r;  // hooks build: A/B of the pad
   if (w.corr_valid) {  // every pass but the first: most points keep their neighbour without a search
     O3dPose Tp{};
     if (update) std::memcpy(Tp.m, update, sizeof(Tp.m));
@@ -1426,14 +1423,8 @@ inline int o3d_corr_pass(O3dIcpWork& w, int64_t Ns, const GridIndex& gi, double 
   } else if (update) {
     return O3S_ERR_BAD_ARGUMENT;  // the first pass runs on the source as placed
   }
-#define O3S_O3D_SEARCH(GG) \
-  hipLaunchKernelGGL(k_o3d_search<GG>, dim3(list ? std::min(nbs, 2048u) : nbs), dim3(kB), 0, s, w.d_src.as<double>(), Ns, gi, w.d_rec.as<O3dRec>(), w.tgt, r2, rc, w.d_corr.as<int32_t>(), \
-                     w.d_cert.as<O3dCert>(), w.corr_valid ? 1 : 0, list, w.d_far.as<O3dFarItem>(), counts O3S_DBG_ARG(kdbg))
-  if (G == 1) O3S_O3D_SEARCH(1);
-  else if (G == 2) O3S_O3D_SEARCH(2);
-  else if (G == 8) O3S_O3D_SEARCH(8);
-  else O3S_O3D_SEARCH(4);
-#undef O3S_O3D_SEARCH
+  hipLaunchKernelGGL(k_o3d_search<G>, dim3(list ? std::min(nbs, 2048u) : nbs), dim3(kB), 0, s, w.d_src.as<double>(), Ns, gi, w.d_rec.as<O3dRec>(), w.tgt, r2, rc,
+                     w.d_corr.as<int32_t>(), w.d_cert.as<O3dCert>(), w.corr_valid ? 1 : 0, list, w.d_far.as<O3dFarItem>(), counts O3S_DBG_ARG(kdbg));
   if (O3S_HOOK_ENV("O3S_O3D_DBG")) {  // hooks build: how many points were searched / went onto the far list
     uint32_t n[2] = {0, 0};
     (void)hipMemcpyAsync(n, counts, 8, hipMemcpyDeviceToHost, s);
@@ -1819,8 +1810,7 @@ int o3s_o3d_registration_icp_batch(int device, int32_t n_pairs, const o3s_o3d_pa
   if (n_pairs == 0) return O3S_OK;
   int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
-  int kO3dBatchLanes = 2;  // measured: 16 pairs of 200 k vs 400 k points take 42 / 34 / 48 / 83 ms with 1 / 2 / 4 / 8 lanes (pageable H2D contends)
-  if (const char* e = O3S_HOOK_ENV("O3S_O3D_LANES")) kO3dBatchLanes = std::max(1, atoi(e));
+  constexpr int kO3dBatchLanes = 2;  // measured: 16 pairs of 200 k vs 400 k points take 42 / 34 / 48 / 83 ms with 1 / 2 / 4 / 8 lanes (pageable H2D contends)
   const int lanes = std::min<int>(kO3dBatchLanes, n_pairs);
   std::atomic<int32_t> next{0};
   auto worker = [&]() {

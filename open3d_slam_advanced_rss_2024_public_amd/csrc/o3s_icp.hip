@@ -69,9 +69,6 @@ struct HostStage {  // pinned staging block for small H2D / D2H transfers
 };
 
 constexpr int kNumKernels = 5;
-#ifndef O3S_FUSE_TAIL_DEFAULT
-#define O3S_FUSE_TAIL_DEFAULT false  // measured (round 4, C2): the in-launch hand-over lost to the launch boundary it replaces — see DESIGN.md
-#endif
 constexpr size_t kHistWords = (size_t)kHistReplicas * kHistBins + 1024;  // level-1 replicas + the level-2 histogram right behind them
 
 }  // namespace
@@ -189,11 +186,6 @@ struct o3s_icp {
   } shard;
 
   int eager_hint = 4;  // iterations the last call needed: where the eager (un-graphed) chain first looks at the `done` flag
-  bool fuse_tail = O3S_FUSE_TAIL_DEFAULT;  // k_sel_ne closes the iteration itself (last-block ticket) instead of a k_solve launch; hooks build: O3S_TAIL
-  int first_group = 4;  // lanes per query in the first iteration of a call up to 200 k points (hooks build: O3S_FIRST_GROUP)
-  int match_group = 4;
-  bool match_group_forced = false;  // lanes per query in k_match2: 1, 2 or 4 (tuning knob O3S_GROUP; default by reading size)
-  int nb_part_cap = kMaxPartialBlocks;  // blocks of the centroid / normal-equation kernels (tuning knob O3S_NB_PART)
 
   // profiling
   bool profiling = false;
@@ -550,10 +542,9 @@ int init_reference_impl(o3s_icp* h, const float4* d_xyzw, const float* d_normals
                  h->have_grid1 ? (double)h->grid1.cell : 0.0);
   {
     // the row-disc far search needs a finite bound to end; an unbounded maxDist (or one that reaches across more cells than an
-    // int comfortably indexes) keeps the ring search, which expands until something is found.  O3S_FAR=0 forces it (A/B runs).
-    const char* fe = O3S_HOOK_ENV("O3S_FAR");
+    // int comfortably indexes) keeps the ring search, which expands until something is found.
     const double reach = std::isfinite(h->cfg.max_dist) ? (double)h->cfg.max_dist / (double)g.cell : 1e30;
-    h->far_rows = reach <= (double)kern::kFarMaxCells && !(fe && std::atoi(fe) == 0);
+    h->far_rows = reach <= (double)kern::kFarMaxCells;
   }
   // the reading is sorted on a coarsened grid of at most 2^22 bins
   {
@@ -637,21 +628,21 @@ struct ChainArgs {
 ChainArgs chain_args(o3s_icp* h, const ChainParams& cp) {
   ChainArgs a{};
   a.N = h->N;
-  // k_match2: lanes per query.  O3S_GROUP forces 1 / 2 / 4; otherwise by reading size (kernels)
+  // k_match2: lanes per query, by reading size (kernels)
   //   measured (converged pose, us): C2 100k: G=4 10.6, G=2 8.9, G=1 9.4;  C4 500k: 37.2 / 27.8 / 33.1.  Two lanes halve the
   //   per-query set-up every lane of a group repeats; below ~32k queries four lanes are needed to fill 1024 SIMDs.  Between 32k and
   //   64k the two are equal on the synthetic pairs (50k: 30.6 k it/s either way) and four lanes win on ray-cast sweeps against a
   //   voxel map (47k queries, 17 candidates per query: registration stage 0.267 -> 0.239 ms); from 65k up two lanes win (-1..3 %).
-  a.match_g = h->match_group_forced ? h->match_group : (h->N < 65536 ? 4 : 2);
+  a.match_g = h->N < 65536 ? 4 : 2;
   a.nb_match = round_up8(nblocks(h->N, kern::kBlock / a.match_g));  // one tile per block (steady state; the launch sizes its own grid)
   a.nb_cls = nblocks(h->N, kern::kClsBlock);
-  a.nb_part = std::min(h->nb_part_cap, nblocks(h->N, kern::kBlock * kern::kNePPT));
+  a.nb_part = std::min(kMaxPartialBlocks, nblocks(h->N, kern::kBlock * kern::kNePPT));
   if (h->shard.active) {
     // sharded: the block partials of the normal equations are all-reduced AS THEY ARE ([27][blocks]), so the number of blocks must be
     // the same on every rank — derived from the whole reading and the world size, not from this rank's slice (slices differ by
     // one point: 2 * 512 * k + 1 points over two ranks gave 4 blocks here and 3 there, i.e. collectives of different lengths)
     const int64_t per_rank = (h->shard.n_total + h->shard.world - 1) / h->shard.world;
-    a.nb_part = std::min(h->nb_part_cap, nblocks(per_rank, kern::kBlock * kern::kNePPT));
+    a.nb_part = std::min(kMaxPartialBlocks, nblocks(per_rank, kern::kBlock * kern::kNePPT));
   }
   {  // fused selection + normal equations while the blocks fit one generation (O3S_FUSE=0 keeps the two kernels apart)
     const char* fe = O3S_HOOK_ENV("O3S_FUSE");  // read per call: the tests run both chains in one process
@@ -728,7 +719,7 @@ void launch_match2(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, const 
 // and twice the lanes halve the rows and candidates each has to walk (C2: 50 -> 39.5 us; at C4 the launch is candidate-bound and
 // gains nothing).  Results do not depend on the lanes per query (exact search, integer histogram).
 inline int match_lanes(const o3s_icp* h, const ChainArgs& a, bool first) {
-  return (first && h->far_rows && !h->match_group_forced && a.N < 200000) ? h->first_group : a.match_g;
+  return (first && h->far_rows && a.N < 200000) ? 4 : a.match_g;
 }
 void launch_match2_any(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, bool stats, bool first, const RefIndex& ix, uint32_t* spec, hipStream_t s) {
   if (cp.mirror) {
@@ -739,12 +730,10 @@ void launch_match2_any(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, bo
   }
   const int G = match_lanes(h, a, first);
   if (stats) {
-    if (G == 1) launch_match2<true, 1>(h, a, cp, ix, spec, s);
-    else if (G == 2) launch_match2<true, 2>(h, a, cp, ix, spec, s);
+    if (G == 2) launch_match2<true, 2>(h, a, cp, ix, spec, s);
     else launch_match2<true, 4>(h, a, cp, ix, spec, s);
   } else {
-    if (G == 1) launch_match2<false, 1>(h, a, cp, ix, spec, s);
-    else if (G == 2) launch_match2<false, 2>(h, a, cp, ix, spec, s);
+    if (G == 2) launch_match2<false, 2>(h, a, cp, ix, spec, s);
     else launch_match2<false, 4>(h, a, cp, ix, spec, s);
   }
 }
@@ -778,23 +767,14 @@ void launch_iteration(o3s_icp* h, const ChainArgs& a, bool stats, hipEvent_t* ev
   if (ev) (void)hipEventRecord(ev[2], s);
   uint32_t* hist2 = h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins;
   if (a.nb_fused > 0) {  // selection + normal equations in one launch (kern::k_sel_ne); timed under "sel_finish"
-#define O3S_SEL_NE_ARGS                                                                                                                            \
-  dim3(a.nb_fused), dim3(kern::kFinThreads), kern::kSelCap * 4, s, a.cp, st, h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(),                   \
-      h->d_cand_cnt.as<uint32_t>(), hist2, h->d_cand_cnt.as<uint32_t>() + a.nb_cls, h->d_cent.as<double>(), a.nb_cls, mode, a.rx, a.ry, a.rz, a.N, \
-      h->d_mq.as<float4>(), h->d_mn.as<float4>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_ne.as<double>(), h->d_hist.as<uint32_t>(),     \
-      h->d_trace_T.as<float>(), h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, h->post_dev
-#ifdef O3S_TEST_HOOKS  // the fused-tail instantiation exists in the hooks build only (round 4's measured-and-left-off experiment, O3S_TAIL)
-    if (h->fuse_tail) hipLaunchKernelGGL(kern::k_sel_ne<true>, O3S_SEL_NE_ARGS);
-    else
-#endif
-      hipLaunchKernelGGL(kern::k_sel_ne<false>, O3S_SEL_NE_ARGS);
-#undef O3S_SEL_NE_ARGS
+    hipLaunchKernelGGL(kern::k_sel_ne, dim3(a.nb_fused), dim3(kern::kFinThreads), kern::kSelCap * 4, s, a.cp, st, h->d_sel.as<SelScratch>(),
+                       h->d_cand.as<CandRec>(), h->d_cand_cnt.as<uint32_t>(), hist2, h->d_cand_cnt.as<uint32_t>() + a.nb_cls, h->d_cent.as<double>(),
+                       a.nb_cls, mode, a.rx, a.ry, a.rz, a.N, h->d_mq.as<float4>(), h->d_mn.as<float4>(), h->d_pos.as<int32_t>(),
+                       h->d_d2.as<float>(), h->d_ne.as<double>(), h->d_hist.as<uint32_t>());
     if (ev) (void)hipEventRecord(ev[3], s);
     if (ev) (void)hipEventRecord(ev[4], s);
-    // fuse_tail: the closing step (solve, checkers, post) is the tail of the block that stored its partials last — no k_solve
-    if (!h->fuse_tail)
-      hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), a.nb_fused, a.N, a.cp, st, h->d_trace_T.as<float>(),
-                         h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 1, h->post_dev);
+    hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), a.nb_fused, a.N, a.cp, st, h->d_trace_T.as<float>(),
+                       h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 1, h->post_dev);
     if (ev) (void)hipEventRecord(ev[5], s);
     return;
   }
@@ -1042,7 +1022,7 @@ int compute_launch(o3s_icp* h, const float* T_init) {
     const int ran = std::min(launched, h->stage->state.iter + (h->stage->state.status ? 1 : 0));
     for (int it = 0; it < ran; ++it)
       for (int k = 0; k < kNumKernels; ++k) {
-        if ((k == 3 || (k == 4 && h->fuse_tail)) && a.nb_fused > 0) continue;  // fused chain: k_sel_ne (timed as k = 2) holds the selection and the normal equations (and, with fuse_tail, the closing step)
+        if (k == 3 && a.nb_fused > 0) continue;  // fused chain: k_sel_ne (timed as k = 2) holds the selection and the normal equations
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, h->prof_events[(size_t)it * 6 + k], h->prof_events[(size_t)it * 6 + k + 1]) == hipSuccess) {
           h->kernel_ms[k] += ms;
@@ -1073,7 +1053,7 @@ int compute_launch(o3s_icp* h, const float* T_init) {
     key.ptrs[3] = h->d_ref.p;
     key.ptrs[4] = h->have_grid1 ? h->d_cell_start1.p : h->d_cell_start.p;  // (any re-allocation moves key.gen as well; this tells the two kinds of chain apart)
     key.ptrs[5] = h->d_trace_T.p;
-    key.ptrs[6] = (const void*)(uintptr_t)((want_stats ? 1 : 0) | (h->shard.active ? 2 : 0) | (h->fuse_tail ? 4 : 0) | (a.spec ? 8 : 0) | ((uintptr_t)(h->shard.active ? h->shard.world : 0) << 8));
+    key.ptrs[6] = (const void*)(uintptr_t)((want_stats ? 1 : 0) | (h->shard.active ? 2 : 0) | (a.spec ? 8 : 0) | ((uintptr_t)(h->shard.active ? h->shard.world : 0) << 8));
     key.ptrs[7] = h->d_perm.p;
     key.cp = cp;
     key.g = h->grid;
@@ -1302,13 +1282,6 @@ extern "C" {
 
 int o3s_abi_version(void) { return O3S_ABI_VERSION; }
 
-#ifdef O3S_TS
-// tuning builds only (-DO3S_TS): phase timestamps of block 0 of the small kernels, see O3S_TSTAMP in icp_kernels.h
-int o3s_debug_ts(unsigned long long* out64) {
-  return hipMemcpyFromSymbol(out64, HIP_SYMBOL(kern::g_ts), 64 * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
-}
-#endif
-
 void o3s_icp_default_config(o3s_icp_config* c) {
   if (!c) return;
   std::memset(c, 0, sizeof(*c));
@@ -1360,14 +1333,7 @@ int o3s_icp_create(const o3s_icp_config* cfg, int device, o3s_icp** out) {
   h->cfg = *cfg;
   h->device = device;
   hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) {
-    const char* px = O3S_HOOK_ENV("O3S_X_PRIO");  // experiment switch of the hooks build (cloud_dev.h make_stream): 2, 3 raise the mapping side's streams
-    int least = 0, greatest = 0;
-    if (px && (atoi(px) == 2 || atoi(px) == 3) && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-      e = hipStreamCreateWithPriority(&h->own_stream, hipStreamNonBlocking, greatest);
-    else
-      e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-  }
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipHostMalloc((void**)&h->stage, sizeof(HostStage), hipHostMallocDefault);
   if (e == hipSuccess) e = hipHostMalloc((void**)&h->mb, 64, hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent);
   if (e == hipSuccess) {
@@ -1387,24 +1353,13 @@ int o3s_icp_create(const o3s_icp_config* cfg, int device, o3s_icp** out) {
   if (e == hipSuccess) e = hipEventCreate(&h->ev_end);
   if (e == hipSuccess)
     e = hipFuncSetAttribute((const void*)kern::k_sel_finish, hipFuncAttributeMaxDynamicSharedMemorySize, kern::kSelCap * 4);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kern::k_sel_ne<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kern::kSelCap * 4);
-#ifdef O3S_TEST_HOOKS
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kern::k_sel_ne<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kern::kSelCap * 4);
-#endif
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kern::k_sel_ne, hipFuncAttributeMaxDynamicSharedMemorySize, kern::kSelCap * 4);
   if (e != hipSuccess) {
     g_create_error = std::string("HIP initialisation failed: ") + hipGetErrorString(e);
     o3s_icp_destroy(h);
     return O3S_ERR_HIP;
   }
   h->stream = h->own_stream;
-  if (const char* e = O3S_HOOK_ENV("O3S_GROUP")) {
-    const int g = std::atoi(e);
-    h->match_group = (g == 2 || g == 1) ? g : 4;
-    h->match_group_forced = true;
-  }
-  if (const char* e = O3S_HOOK_ENV("O3S_TAIL")) h->fuse_tail = std::atoi(e) != 0;
-  if (const char* e = O3S_HOOK_ENV("O3S_FIRST_GROUP")) h->first_group = std::atoi(e) == 2 ? 2 : (std::atoi(e) == 1 ? 1 : 4);
-  if (const char* e = O3S_HOOK_ENV("O3S_NB_PART")) h->nb_part_cap = std::max(1, std::min(kMaxPartialBlocks, std::atoi(e)));
   *out = h;
   return O3S_OK;
 }

@@ -285,7 +285,7 @@ struct SubmapStreamPool {
     // all of a device's streams are made with its first submap (a collection's constructor), not one per switch of submaps later
     while (v.size() < (size_t)kPerDevice) {
       hipStream_t s = nullptr;
-      if (make_stream(&s, false) != hipSuccess) break;
+      if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) break;
       v.push_back(s);
     }
     if (v.empty()) return nullptr;
@@ -311,7 +311,7 @@ static int submap_create_impl(int device, double map_voxel_size, const o3s_cropp
   m->cropper = *map_builder_cropper;
   m->owns_stream = own_stream;
   if (own_stream) {
-    if (make_stream(&m->stream, false) != hipSuccess) m->stream = nullptr;
+    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) m->stream = nullptr;
   } else {
     m->stream = submap_stream_pool().get(device);
   }
@@ -1086,7 +1086,7 @@ int o3s_raw_scan_create(int device, o3s_raw_scan** out) {
   if (rc != O3S_OK) return rc;
   o3s_raw_scan* r = new o3s_raw_scan();
   r->device = device;
-  if (make_stream(&r->stream, true) != hipSuccess) {
+  if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
     delete r;
     return O3S_ERR_HIP;
   }
@@ -1141,7 +1141,7 @@ int o3s_scan_create(int device, o3s_scan** out) {
   if (rc != O3S_OK) return rc;
   o3s_scan* sc = new o3s_scan();
   sc->device = device;
-  if (make_stream(&sc->stream, true) != hipSuccess ||
+  if (hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&sc->handover, hipEventDisableTiming) != hipSuccess) {
     if (sc->stream) (void)hipStreamDestroy(sc->stream);
     delete sc;

@@ -1,8 +1,5 @@
 """GPU-box helper: k_match2 in the FIRST iteration of a call (no incumbents, initial pose 0.1 m / 2 deg off) against a
-converged one, HIP events around every launch (o3s_icp_set_profiling).  CFG=c2 (default) | c4 | c5 (0.25 m map, ray cast).
-
-    O3S_FAR=0 python tools/first_iter3.py     # the ring search, for A/B
-"""
+converged one, HIP events around every launch (o3s_icp_set_profiling).  CFG=c2 (default) | c4 | c5 (0.25 m map, ray cast)."""
 import json
 import os
 import sys
@@ -19,7 +16,7 @@ elif cfg == "c1":
     pair = syn.make_scan_pair(10_000, 100_000, 0.1, seed=0)
 else:
     pair = syn.make_scan_pair(100_000, 2_000_000, 0.1, seed=0)
-out = {"cfg": cfg, "far_env": os.environ.get("O3S_FAR", "")}
+out = {"cfg": cfg}
 for iters in (1, 2, 20):
     icp = ICP(IcpConfig(use_differential=False, max_iters=iters, use_graph=False, match_stats=bool(int(os.environ.get("STATS", "0")))))
     icp.init_reference(pair.map_xyz, pair.map_normals)

@@ -23,11 +23,10 @@ timeout -k 10 300 python3 bench.py > $O/bench_c2.json 2> $O/bench_c2.err
 timeout -k 10 400 python3 bench.py --scan 500000 --map 20000000 --voxel 0.02 --steps 5 --warmup 2 --no-cpu --batch-pairs 0 > $O/bench_c4.json 2> $O/bench_c4.err
 fi
 if [ "$PART" = "b" ] || [ "$PART" = "all" ]; then
-# 4. the first iteration of a call against a converged one (row-disc far search vs the ring search)
+# 4. the first iteration of a call against a converged one (the *_ring.json records were taken with a knob that forced the
+#    ring search; it has been removed since)
 python3 tools/first_iter3.py > $O/first_iter_c2.json 2>/dev/null
-O3S_FAR=0 python3 tools/first_iter3.py > $O/first_iter_c2_ring.json 2>/dev/null
 CFG=c4 python3 tools/first_iter3.py > $O/first_iter_c4.json 2>/dev/null
-CFG=c4 O3S_FAR=0 python3 tools/first_iter3.py > $O/first_iter_c4_ring.json 2>/dev/null
 # 5. sharded mode at world size 1 (RCCL in the loop, chain + collectives replayed from one hipGraph) against the unsharded chain
 timeout -k 10 200 python3 bench.py --mode sharded --exchange rccl --no-cpu > $O/bench_sharded_w1.json 2> $O/bench_sharded_w1.err
 timeout -k 10 300 python3 bench.py --mode sharded --exchange rccl --no-cpu --scan 500000 --map 20000000 --voxel 0.02 --steps 5 --warmup 2 > $O/bench_sharded_w1_c4.json 2> $O/bench_sharded_w1_c4.err

@@ -1,4 +1,4 @@
-"""GPU-box helper (round 4 A/B runs; hooks build for the knobs: O3S_LIB_VARIANT=hooks O3S_TAIL=0|1 O3S_FIRST_GROUP=2|4 ...).
+"""GPU-box helper (round 4 A/B runs; hooks build for the knobs: O3S_LIB_VARIANT=hooks O3S_FUSE=0|1 ...).
 Prints one JSON line: the 50-iteration chain (graph replay) per iteration, the icp.yaml chain per registration with the host-side
 split (issue / wait / stream queries), the host-buffer call, and k_match2 in the first iteration vs converged (HIP events).
 CFG=c2 (default) | c4."""

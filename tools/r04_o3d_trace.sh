@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU box: per-pass durations of the loop-closure search kernels on tools/r04_closure.py (hooks build; O3S_O3D_KDBG / O3S_O3D_G pass through)
+# GPU box: per-pass durations of the loop-closure search kernels on tools/r04_closure.py (hooks build; O3S_O3D_KDBG passes through)
 R=${GRAFT_REPO_ROOT:-/root/repo}
 tag=${1:-t}
 cd /tmp && export TMPDIR=/tmp
