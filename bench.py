@@ -9,13 +9,18 @@ of the 100k-pt scan, then 50 fixed ICP iterations (match, trim select, centroid,
 2M-pt map index, then the 4x4 pose back to the host.  Workload = BASELINE.json configs[1] (C2).  With N > 1 every rank
 owns one GPU and an independent (scan, map) pair (different seed): no data-path collective, weak scaling.
 
-Rank 0 prints ONE JSON line.  `roofline` prices the matcher kernel (k_match2) with the algorithmic-byte model of
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline
+(`metric`, `value`, `ms_per_step`, `config` and the cheap facts of the timed run under `extra`); everything measured beyond
+that runs with --full only and is null in a plain line:
+
+`roofline` prices the matcher kernel (k_match2) with the algorithmic-byte model of
 SURVEY.md §8(d) / DESIGN.md and its average launch duration MEASURED IN THIS RUN: HIP events on the library's stream around
 every launch of a timed chain, minus what an event pair measures around an empty kernel (o3s_icp_event_gap_ms); the
 rocprofv3 --kernel-trace average committed under profiles/ rides along as `profiled_avg_ms`, and a disagreement beyond 15 %
 is reported on stderr and in the record (`--strict`: exit code 3).  `roofline_kernels` does the same for every kernel of
 the chain.  `cpu_baseline` times the CPU oracle (oracle/, the checker — never the thing shipped) on the same inputs on this
-box's host cores.
+box's host cores.  `extra` adds the icp.yaml chain call by call, the PCIe-inclusive rate, several pairs in flight on one GPU,
+BASELINE configs 3, 4 and 5, and (N > 1) the one-pair-sharded mode on the same ranks.
 """
 import argparse
 import json
@@ -80,7 +85,10 @@ def parse():
     ap.add_argument("--voxel", type=float, default=0.1)
     ap.add_argument("--iters", type=int, default=50, help="fixed ICP iterations per compute (C2: 50)")
     ap.add_argument("--grid-cell", type=float, default=0.0)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline, the CPU baseline and every extra (other configs, chains, "
+                         "modes); a plain run times the steps and prints the headline only")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-iters", type=int, default=100, help="iterations of the CPU sample (100: about 15 core-seconds on the box's 16-core share)")
     ap.add_argument("--no-sort", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
@@ -91,15 +99,15 @@ def parse():
     ap.add_argument("--pairs-per-gpu", type=int, default=1,
                     help="pairs mode: independent (scan, map) pairs every rank keeps in flight through o3s_icp_compute_batch "
                          "(8 with --gpus 8 = BASELINE config 3's 64 pairs); value = iterations/s summed over all pairs")
-    ap.add_argument("--strict", action="store_true", help="exit with code 3 when the live kernel time and the committed rocprofv3 average differ by more than 15 %%")
+    ap.add_argument("--strict", action="store_true", help="--full: exit with code 3 when the live kernel time and the committed rocprofv3 average differ by more than 15 %%")
     ap.add_argument("--exchange", choices=["rccl", "torch"], default="rccl",
                     help="sharded mode: ncclAllReduce issued from C (libo3dslam_icp_rccl.so) or dist.all_reduce from Python")
-    ap.add_argument("--batch-pairs", type=int, default=8, help="pairs kept in flight on one GPU for extra.batched_on_one_gpu (0/1: skip)")
-    ap.add_argument("--no-c4", action="store_true", help="skip extra.c4 (BASELINE config 4: 500k-pt scan vs 20M-pt map at 0.02 m; ~40 s of fixture generation)")
-    ap.add_argument("--no-c3", action="store_true", help="skip extra.c3 (BASELINE config 3: 64 pairs of 100k vs 400k on this GPU; ~20 s of fixture generation)")
-    ap.add_argument("--no-c5", action="store_true", help="skip extra.c5 (BASELINE config 5: the per-scan loop through the compiled driver; ~70 s, most of it ray casting)")
-    ap.add_argument("--no-sharded-extra", action="store_true", help="N > 1: skip extra.sharded_one_pair (the one-pair-sharded mode on the same ranks)")
-    ap.add_argument("--timing-only", action="store_true", help="only the timed region (for rocprofv3 runs): no roofline / PCIe / CPU legs")
+    ap.add_argument("--batch-pairs", type=int, default=8, help="--full: pairs kept in flight on one GPU for extra.batched_on_one_gpu (0/1: skip)")
+    ap.add_argument("--no-c4", action="store_true", help="--full: skip extra.c4 (BASELINE config 4: 500k-pt scan vs 20M-pt map at 0.02 m; ~40 s of fixture generation)")
+    ap.add_argument("--no-c3", action="store_true", help="--full: skip extra.c3 (BASELINE config 3: 64 pairs of 100k vs 400k on this GPU; ~20 s of fixture generation)")
+    ap.add_argument("--no-c5", action="store_true", help="--full: skip extra.c5 (BASELINE config 5: the per-scan loop through the compiled driver; ~70 s, most of it ray casting)")
+    ap.add_argument("--no-sharded-extra", action="store_true", help="--full, N > 1: skip extra.sharded_one_pair (the one-pair-sharded mode on the same ranks)")
+    ap.add_argument("--timing-only", action="store_true", help="only the timed region (for rocprofv3 runs): a short line without config or extras, even with --full")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (poses and ICP stats) as DIR/<name>.npy")
     args = ap.parse_args()
@@ -222,10 +230,10 @@ def run_sharded(args, rank, world, device, dist, torch):
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     roofline = None
-    if args.exchange == "rccl":   # every rank: the counted chains carry collectives
+    if args.full and args.exchange == "rccl":   # every rank: the counted chains carry collectives
         roofline = sharded_roofline(icp, make_sharded, pair, sl.stop - sl.start, iters)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline_record(args, pair, lambda **kw: IcpConfig(**dict(dict(use_differential=False, max_iters=iters), **kw)), device)
     line = None
     if rank == 0:
@@ -234,7 +242,7 @@ def run_sharded(args, rank, world, device, dist, torch):
             "metric": _metric_name(args.scan, args.map), "value": round(iters * args.steps / elapsed, 2),
             "unit": "ICP iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"ONE pair sharded: {N}-pt scan split over {world} rank(s) vs replicated {M}-pt voxel map, "
                                    f"{args.voxel} m voxels, {iters} iters, icp.yaml chain",
                        "scan_points": N, "map_points": M, "iterations_per_step": iters,
@@ -958,7 +966,7 @@ def _run():
         hk.close()
 
     sharded_extra = None
-    if dist is not None and not args.timing_only and not args.no_sharded_extra and (N, M) == (100_000, 2_000_000):
+    if args.full and dist is not None and not args.timing_only and not args.no_sharded_extra and (N, M) == (100_000, 2_000_000):
         # the one driver run on N GPUs measures BOTH modes of SURVEY 8(e): every rank takes part (collective calls inside)
         try:
             sharded_extra = measure_sharded_extra(args, rank, world, device, dist, torch)
@@ -973,10 +981,13 @@ def _run():
         dT = np.linalg.inv(pair.T_gt) @ T.astype(np.float64)
         pose_err_m = float(np.linalg.norm(dT[:3, 3]))
 
-        roofline, kernels, disagree = roofline_of(icp, cfg, pair, N, M, args.voxel, iters, value / (world * P), gpu_ms_chain, device)
+        # ---- everything below the headline is --full's: a plain line carries null in its place ----
+        roofline, kernels, disagree = None, None, []
+        if args.full:
+            roofline, kernels, disagree = roofline_of(icp, cfg, pair, N, M, args.voxel, iters, value / (world * P), gpu_ms_chain, device)
         # ---- the chain open3d_slam actually runs (icp.yaml: Differential 0.001 / 0.01 / 3 before Counter 15), same pair ----
         yaml_chain = None
-        if args.iters == 50:
+        if args.full and args.iters == 50:
             icp_y = ICP(IcpConfig(grid_cell=args.grid_cell, sort_queries=not args.no_sort, use_graph=not args.no_graph), device=device)
             icp_y.init_reference(pair.map_xyz, pair.map_normals)
             icp_y.set_reading(pair.scan_xyz, pair.scan_normals)
@@ -984,20 +995,22 @@ def _run():
             icp_y.close()
 
         # ---- PCIe-inclusive rate (host buffers handed over every call); never the headline value ----
-        for _ in range(3):  # the first calls allocate the upload buffer and re-capture the chain's graph behind it
-            icp.compute(pair.scan_xyz, pair.scan_normals, pair.T_init)
-        reps = max(2, min(5, args.steps))
-        with timed_region():
-            t1 = time.perf_counter()
-            for _ in range(reps):
+        pcie_value = None
+        if args.full:
+            for _ in range(3):  # the first calls allocate the upload buffer and re-capture the chain's graph behind it
                 icp.compute(pair.scan_xyz, pair.scan_normals, pair.T_init)
-            pcie_value = iters * reps / (time.perf_counter() - t1)
+            reps = max(2, min(5, args.steps))
+            with timed_region():
+                t1 = time.perf_counter()
+                for _ in range(reps):
+                    icp.compute(pair.scan_xyz, pair.scan_normals, pair.T_init)
+                pcie_value = iters * reps / (time.perf_counter() - t1)
 
         # ---- several pairs in flight on ONE GPU (BASELINE config 3's per-GPU share: o3s_icp_compute_batch, one stream per
         # pair).  Reported beside the headline, never as `value`: the chains of different pairs overlap, so the GPU's
         # idle slots between one pair's dependent kernels get filled. ----
         batched = None
-        if args.batch_pairs > 1:
+        if args.full and args.batch_pairs > 1:
             from open3d_slam_advanced_rss_2024_public_amd import compute_batch
             PB = args.batch_pairs   # NOT `P`: that is the timed run's pairs per GPU and goes into `config`
             handles = [ICP(cfg(), device=device) for _ in range(PB)]
@@ -1021,13 +1034,13 @@ def _run():
 
         # ---- CPU baseline: the oracle (a port of the reference's algorithm) on this box's host cores ----
         cpu = None
-        if not args.no_cpu and world == 1:  # the CPU leg belongs to the N = 1 line only
+        if args.full and not args.no_cpu and world == 1:  # the CPU leg belongs to the N = 1 line only
             cpu = cpu_baseline_record(args, pair, cfg, device)
         c4 = None
-        if world == 1 and dist is None and not args.no_c4 and (N, M) == (100_000, 2_000_000) and args.voxel == 0.1:
+        if args.full and world == 1 and dist is None and not args.no_c4 and (N, M) == (100_000, 2_000_000) and args.voxel == 0.1:
             c4 = measure_c4(args, device)
         c3 = c5 = None
-        if world == 1 and dist is None and (N, M) == (100_000, 2_000_000) and args.voxel == 0.1:
+        if args.full and world == 1 and dist is None and (N, M) == (100_000, 2_000_000) and args.voxel == 0.1:
             for name, on, fn in (("c3", not args.no_c3, lambda: measure_c3(args, device)), ("c5", not args.no_c5, lambda: measure_c5(args))):
                 if not on:
                     continue
@@ -1043,7 +1056,7 @@ def _run():
         out = {
             "metric": _metric_name(args.scan, args.map), "value": round(value, 2), "unit": "ICP iterations/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"{'C2' if (N, M) == (100_000, 2_000_000) else 'C4' if (N, M) == (500_000, 20_000_000) else 'custom'}: {N}-pt scan vs {M}-pt voxel map, {args.voxel} m voxels, {iters} iters, icp.yaml chain "
                                    "(KDTree maxDist 0.5 exact, Trimmed 0.9, SurfaceNormal 1.57, PointToPlane)",
                        "scan_points": N, "map_points": M, "iterations_per_step": iters, "pairs_per_gpu": P,
@@ -1053,7 +1066,7 @@ def _run():
             "roofline": roofline,
             "roofline_kernels": kernels,
             "cpu_baseline": cpu,
-            "extra": {"pcie_inclusive_value": round(pcie_value, 2), "gpu_chain_ms_per_step": round(gpu_ms_chain, 4),
+            "extra": {"pcie_inclusive_value": round(pcie_value, 2) if pcie_value is not None else None, "gpu_chain_ms_per_step": round(gpu_ms_chain, 4),
                       "init_reference_s": round(t_init_ref, 3), "fixture_generation_s": round(t_gen, 2),
                       "pose_error_vs_ground_truth_m": pose_err_m, "kept_pairs": int(icp.stats.kept_pairs),
                       "python_gc_in_timed_steps": tr_main.record(),

@@ -241,6 +241,17 @@ def test_bench_refuses_a_run_without_timed_steps():
     assert "--steps" in out.stderr and out.stdout.strip() == ""
 
 
+def test_bench_keeps_what_lies_beyond_the_headline_behind_full():
+    """A plain run prints the headline alone; the roofline, the CPU baseline and the extras are asked for with --full, which `--help`
+    lists without anything touching the GPU."""
+    import subprocess
+    import sys
+
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-500:]
+    assert "--full" in out.stdout
+
+
 def test_a_forked_child_does_not_destroy_the_parents_handles():
     """multiprocessing workers forked from a process that holds device handles inherit the wrappers; a garbage collection in
     the worker must not call into the library (the HIP runtime does not survive a fork): close() drops the handle instead."""

@@ -3,6 +3,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -11,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_default_bench_line_describes_the_run_that_was_timed():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu"], capture_output=True,
-                         text=True, timeout=900, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu", "--full"],
+                         capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, out.stdout            # exactly one line on stdout
@@ -40,7 +41,7 @@ def test_default_bench_line_describes_the_run_that_was_timed():
     assert f["cbar_candidates_per_query"] > c_["cbar_candidates_per_query"] and f["avg_launch_ms"] > c_["avg_launch_ms"]
     assert abs((f["cbar_candidates_per_query"] + 49 * c_["cbar_candidates_per_query"]) / 50 - r["cbar_candidates_per_query"]) < 0.02
     assert "converged_microbench_frac" not in r
-    # BASELINE config 4 rides in the same line (the driver only ever runs the default command): its own value, roofline and split
+    # BASELINE config 4 rides in the same --full line: its own value, roofline and split
     c4 = d["extra"]["c4"]
     assert c4["workload"].startswith("C4: 500000-pt scan vs 20000000-pt") and c4["value"] > 1000 and c4["pose_error_vs_ground_truth_m"] < 5e-3
     assert abs(c4["value"] - 50 * c4["steps"] / (c4["ms_per_step"] * c4["steps"] * 1e-3)) <= 1e-3 * c4["value"]
@@ -88,6 +89,30 @@ def test_default_bench_line_describes_the_run_that_was_timed():
     assert any("libamdhip64" in p_ for p_ in d["extra"]["rocm_runtime"])
 
 
+def test_plain_bench_line_is_the_headline_alone():
+    """Without --full the run sets up, warms up, times the steps and prints the headline: the contract's fields mean what they mean
+    in a --full line, every measurement beyond the timed steps is null, and the run spends at most 30 s outside its steps."""
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"], capture_output=True,
+                         text=True, timeout=300, cwd=ROOT)
+    wall_s = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
+    assert d["metric"] == "ICP iterations/s (100k-pt scan vs 2M-pt map)" and d["unit"] == "ICP iterations/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["scaling"] == "weak"
+    assert d["config"]["workload"].startswith("C2") and d["config"]["pairs_per_gpu"] == 1 and d["config"]["iterations_per_step"] == 50
+    assert abs(d["value"] - 50 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    assert d["roofline"] is None and d["roofline_kernels"] is None and d["cpu_baseline"] is None
+    e = d["extra"]
+    for k in ("pcie_inclusive_value", "batched_on_one_gpu", "icp_yaml_chain", "c3", "c4", "c5", "sharded_one_pair"):
+        assert e[k] is None, k
+    assert e["pose_error_vs_ground_truth_m"] < 5e-3 and e["kept_pairs"] > 0
+    assert wall_s - (d["steps"] + d["warmup"]) * d["ms_per_step"] * 1e-3 <= 30.0, wall_s
+
+
 def test_dump_outputs_writes_the_last_timed_step_and_repeats_it(tmp_path):
     """--dump-outputs DIR: the pose and ICP stats the last timed step returned, as .npy files; the inputs are seeded, so a second run
     with the same arguments writes the same arrays, and `steps` / `ms_per_step` describe the timed loop that was asked for."""
@@ -115,13 +140,13 @@ def test_dump_outputs_writes_the_last_timed_step_and_repeats_it(tmp_path):
 
 
 def test_n_gpu_line_also_measures_the_one_pair_sharded_mode():
-    """The driver's N > 1 run is the only one that will ever see several GPUs: besides the pairs measurement (mode 1) it must time
+    """The N > 1 run is the only one that will ever see several GPUs: besides the pairs measurement (mode 1) its --full line must time
     the one-pair-sharded mode (mode 2) on the same ranks — rehearsed here with a process group of one rank on the one GPU
     (O3S_BENCH_FORCE_DIST=1: RCCL at world size 1)."""
     env = dict(os.environ, O3S_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29547", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu", "--batch-pairs", "0"],
-                         capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu", "--batch-pairs", "0",
+                          "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
     assert d["scaling"] == "weak" and d["config"]["pairs_per_gpu"] == 1

@@ -7,7 +7,7 @@ mkdir -p $O
 PART=${1:-all}   # a | b | c | all (separate GPU calls keep each well under the time limit of one); d = the 2 000-sweep soak, on its own
 if [ "$PART" = "a" ] || [ "$PART" = "all" ]; then
 # 1. bench (C2) + kernel trace of the same timed region
-timeout -k 10 300 python3 bench.py > $O/bench_c2.json 2> $O/bench_c2.err
+timeout -k 10 300 python3 bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err
 tools/prof.sh r03z > $O/prof_c2.txt 2>&1
 cp gpurun_out/prof_r03z/r03z_kernel_stats.csv $O/kernel_stats_c2.csv
 # 2. PMC: HBM traffic of k_match2 (separate passes), then the SQ picture
@@ -19,8 +19,8 @@ cp gpurun_out/prof_r03z4/r03z4_kernel_stats.csv $O/kernel_stats_c4.csv
 PMC_ARGS="--scan 500000 --map 20000000 --voxel 0.02" tools/pmc2.sh r03z4_f k_match2 "FETCH_SIZE" "WRITE_SIZE" > $O/pmc_traffic_c4.txt 2>&1
 # roofline inputs from the traces just taken, then the benches that quote them
 python3 tools/make_roofline_inputs.py $O r03 > $O/roofline_inputs.txt 2>&1
-timeout -k 10 300 python3 bench.py > $O/bench_c2.json 2> $O/bench_c2.err
-timeout -k 10 400 python3 bench.py --scan 500000 --map 20000000 --voxel 0.02 --steps 5 --warmup 2 --no-cpu --batch-pairs 0 > $O/bench_c4.json 2> $O/bench_c4.err
+timeout -k 10 300 python3 bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err
+timeout -k 10 400 python3 bench.py --full --scan 500000 --map 20000000 --voxel 0.02 --steps 5 --warmup 2 --no-cpu --batch-pairs 0 > $O/bench_c4.json 2> $O/bench_c4.err
 fi
 if [ "$PART" = "b" ] || [ "$PART" = "all" ]; then
 # 4. the first iteration of a call against a converged one (the *_ring.json records were taken with a knob that forced the
@@ -28,12 +28,12 @@ if [ "$PART" = "b" ] || [ "$PART" = "all" ]; then
 python3 tools/first_iter3.py > $O/first_iter_c2.json 2>/dev/null
 CFG=c4 python3 tools/first_iter3.py > $O/first_iter_c4.json 2>/dev/null
 # 5. sharded mode at world size 1 (RCCL in the loop, chain + collectives replayed from one hipGraph) against the unsharded chain
-timeout -k 10 200 python3 bench.py --mode sharded --exchange rccl --no-cpu > $O/bench_sharded_w1.json 2> $O/bench_sharded_w1.err
-timeout -k 10 300 python3 bench.py --mode sharded --exchange rccl --no-cpu --scan 500000 --map 20000000 --voxel 0.02 --steps 5 --warmup 2 > $O/bench_sharded_w1_c4.json 2> $O/bench_sharded_w1_c4.err
+timeout -k 10 200 python3 bench.py --full --mode sharded --exchange rccl --no-cpu > $O/bench_sharded_w1.json 2> $O/bench_sharded_w1.err
+timeout -k 10 300 python3 bench.py --full --mode sharded --exchange rccl --no-cpu --scan 500000 --map 20000000 --voxel 0.02 --steps 5 --warmup 2 > $O/bench_sharded_w1_c4.json 2> $O/bench_sharded_w1_c4.err
 tools/prof_any.sh r03zs --mode sharded --exchange rccl --no-cpu --steps 6 --warmup 2 > $O/prof_sharded_w1.txt 2>&1
 # 6. config 3 on one GPU (64 pairs) and 8 pairs per GPU through bench.py, config 5 loops
 timeout -k 10 300 python3 tools/c3_pairs.py --out $O/c3_pairs.json > /dev/null 2> $O/c3.err
-timeout -k 10 300 python3 bench.py --pairs-per-gpu 8 --steps 5 --no-cpu --batch-pairs 0 > $O/bench_pairs8.json 2> $O/bench_pairs8.err
+timeout -k 10 300 python3 bench.py --full --pairs-per-gpu 8 --steps 5 --no-cpu --batch-pairs 0 > $O/bench_pairs8.json 2> $O/bench_pairs8.err
 LIDAR=1 SCANS=300 STEP=0.25 NORMALS=1 GEN_PROCS=12 timeout -k 10 300 python3 tools/mapping_loop.py > $O/c5_loop_300.json 2> $O/c5.err
 fi
 if [ "$PART" = "c" ] || [ "$PART" = "all" ]; then

@@ -18,7 +18,7 @@ PMC_ARGS="--scan 500000 --map 20000000 --voxel 0.02" tools/pmc2.sh r04z4_f k_mat
 python3 tools/make_roofline_inputs.py $O r04 > $O/roofline_inputs.txt 2>&1
 make -C open3d_slam_advanced_rss_2024_public_amd/csrc resource-usage 2>&1 | python3 tools/resource_table.py > $O/kernel_resources.txt
 # 2. the driver's command, with the roofline inputs just made in place
-timeout -k 10 600 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 600 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 fi
 if [ "$PART" = "b" ]; then
 # 3. first iteration / converged, far-search split (hooks build), yaml-chain kernel timeline, host-buffer calls
@@ -30,9 +30,9 @@ CFG=c4 O3S_LIB_VARIANT=hooks python3 tools/far_split.py > $O/far_split_c4.json 2
 python3 tools/r04_trace_summary.py gpurun_out/r04z_yaml_trace > $O/yaml_trace_summary.txt 2>&1
 python3 tools/r04_hostbuf.py > $O/host_buffers.json 2>/dev/null
 # 4. sharded mode at world size 1 (RCCL in the loop) against the unsharded chain; 8 pairs in flight; config 3
-timeout -k 10 200 python3 bench.py --mode sharded --exchange rccl --no-cpu > $O/bench_sharded_w1.json 2> $O/bench_sharded_w1.err
-timeout -k 10 300 python3 bench.py --mode sharded --exchange rccl --no-cpu --scan 500000 --map 20000000 --voxel 0.02 --steps 5 --warmup 2 > $O/bench_sharded_w1_c4.json 2> $O/bench_sharded_w1_c4.err
-timeout -k 10 300 python3 bench.py --pairs-per-gpu 8 --steps 5 --no-cpu --batch-pairs 0 --no-c4 > $O/bench_pairs8.json 2> $O/bench_pairs8.err
+timeout -k 10 200 python3 bench.py --full --mode sharded --exchange rccl --no-cpu > $O/bench_sharded_w1.json 2> $O/bench_sharded_w1.err
+timeout -k 10 300 python3 bench.py --full --mode sharded --exchange rccl --no-cpu --scan 500000 --map 20000000 --voxel 0.02 --steps 5 --warmup 2 > $O/bench_sharded_w1_c4.json 2> $O/bench_sharded_w1_c4.err
+timeout -k 10 300 python3 bench.py --full --pairs-per-gpu 8 --steps 5 --no-cpu --batch-pairs 0 --no-c4 > $O/bench_pairs8.json 2> $O/bench_pairs8.err
 timeout -k 10 300 python3 tools/c3_pairs.py --out $O/c3_pairs.json > /dev/null 2> $O/c3.err
 fi
 if [ "$PART" = "c" ]; then
