@@ -1425,12 +1425,12 @@ inline int o3d_corr_pass(O3dIcpWork& w, int64_t Ns, const GridIndex& gi, double 
   }
   hipLaunchKernelGGL(k_o3d_search<G>, dim3(list ? std::min(nbs, 2048u) : nbs), dim3(kB), 0, s, w.d_src.as<double>(), Ns, gi, w.d_rec.as<O3dRec>(), w.tgt, r2, rc,
                      w.d_corr.as<int32_t>(), w.d_cert.as<O3dCert>(), w.corr_valid ? 1 : 0, list, w.d_far.as<O3dFarItem>(), counts O3S_DBG_ARG(kdbg));
-  if (O3S_HOOK_ENV("O3S_O3D_DBG")) {  // hooks build: how many points were searched / went onto the far list
+  if (O3S_HOOK_ENV("O3S_O3D_DBG")) {  // hooks build: how many points were searched / went onto the far list, and which launches follow
     uint32_t n[2] = {0, 0};
     (void)hipMemcpyAsync(n, counts, 8, hipMemcpyDeviceToHost, s);
     (void)hipStreamSynchronize(s);
-    std::fprintf(stderr, "o3d pass: Ns=%lld searched=%u far=%u cell=%.3f grid=%dx%dx%d later_pass=%d\n", (long long)Ns, list ? n[0] : (uint32_t)Ns, n[1],
-                 gi.g.cell, gi.g.nx, gi.g.ny, gi.g.nz, (int)w.corr_valid);
+    std::fprintf(stderr, "o3d pass: Ns=%lld searched=%u far=%u cell=%.17g grid=%dx%dx%d later_pass=%d pass=%d r_cap=%d\n", (long long)Ns,
+                 list ? n[0] : (uint32_t)Ns, n[1], gi.g.cell, gi.g.nx, gi.g.ny, gi.g.nz, (int)w.corr_valid, w.pass_no, rc.r_cap);
   }
   if (w.pass_no < 3)
     hipLaunchKernelGGL(k_o3d_search_far<16>, dim3(kO3dFarBlocks), dim3(kB), 0, s, w.d_src.as<double>(), gi, w.d_rec.as<O3dRec>(), w.tgt, r2, rc,

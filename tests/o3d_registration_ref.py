@@ -7,7 +7,10 @@ estimation types, for the tests of include/o3s_registration.h:
 
 Written from Open3D's published source, independently of the library: exact nearest neighbours (cKDTree, eps 0) with the
 radius test d2 < r2, Open3D's W = (M^-1)^(1/2) form of the GICP term (the library sums G^T M^-1 G), the source's covariances
-turned with the source at init and at every update (PointCloud::Transform -> TransformCovariances), numpy's SVD for umeyama."""
+turned with the source at init and at every update (PointCloud::Transform -> TransformCovariances), numpy's SVD for umeyama.
+
+`workers` goes to every cKDTree.query (the answers do not depend on it); `bounded` gives each query distance_upper_bound
+r (1 + 1e-9), which only prunes candidates the exact d2 < r2 test would drop anyway."""
 import numpy as np
 from scipy.spatial import cKDTree
 
@@ -58,12 +61,17 @@ def covariances_from_normals(n, epsilon=1e-3):
     return R @ np.diag([epsilon, 1.0, 1.0])[None] @ np.transpose(R, (0, 2, 1))
 
 
-def correspondences(pcd, tree, tgt, r):
+def correspondences(pcd, tree, tgt, r, workers=1, bounded=False):
     """GetRegistrationResultAndCorrespondences: (source index, target index) pairs, fitness, inlier_rmse."""
     ns = len(pcd)
     fin = np.isfinite(pcd).all(axis=1)
     src_idx = np.nonzero(fin)[0]
-    _, j = tree.query(pcd[fin], k=1, eps=0.0)
+    if bounded:
+        _, j = tree.query(pcd[fin], k=1, eps=0.0, distance_upper_bound=r * (1.0 + 1e-9), workers=workers)
+        found = j < len(tgt)           # a miss comes back as index len(tgt)
+        src_idx, j = src_idx[found], j[found]
+    else:
+        _, j = tree.query(pcd[fin], k=1, eps=0.0, workers=workers)
     d = pcd[src_idx] - tgt[j]
     d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
     hit = d2 < r * r
@@ -146,7 +154,7 @@ def umeyama(src, dst):
 
 def registration_icp(source, target, max_correspondence_distance, init=None, registration_type="PointToPlaneIcp", target_normals=None,
                      source_normals=None, source_covariances=None, target_covariances=None, epsilon=1e-3, relative_fitness=1e-6,
-                     relative_rmse=1e-6, max_iteration=30):
+                     relative_rmse=1e-6, max_iteration=30, workers=1, bounded=False):
     """RegistrationICP(source, target, max_dist, init, <estimation>, criteria); GeneralizedIcp: RegistrationGeneralizedICP (the
     covariances of InitializePointCloudForGeneralizedICP first).  Returns the fields of RegistrationResult as a dict."""
     assert registration_type in TYPES
@@ -168,7 +176,7 @@ def registration_icp(source, target, max_correspondence_distance, init=None, reg
             cs = R[None] @ cs @ R.T[None]
     tree = cKDTree(tgt)
     r = float(max_correspondence_distance)
-    si, tj, fitness, rmse = correspondences(pcd, tree, tgt, r)
+    si, tj, fitness, rmse = correspondences(pcd, tree, tgt, r, workers, bounded)
     it = 0
     for _ in range(int(max_iteration)):
         if len(si) == 0:
@@ -185,8 +193,26 @@ def registration_icp(source, target, max_correspondence_distance, init=None, reg
             R = update[:3, :3]
             cs = R[None] @ cs @ R.T[None]
         f0, e0 = fitness, rmse
-        si, tj, fitness, rmse = correspondences(pcd, tree, tgt, r)
+        si, tj, fitness, rmse = correspondences(pcd, tree, tgt, r, workers, bounded)
         it += 1
         if abs(f0 - fitness) < relative_fitness and abs(e0 - rmse) < relative_rmse:
             break
     return {"transformation": T, "fitness": fitness, "inlier_rmse": rmse, "correspondences": len(si), "iterations": it}
+
+
+def information_matrix(source, target, max_correspondence_distance, transformation, workers=1, bounded=False):
+    """GetInformationMatrixFromPointClouds (pipelines/registration/Registration.cpp): the source placed by T, its nearest target
+    point within the radius, and for each correspondence the three rows G = [[0, z, -y, 1, 0, 0], [-z, 0, x, 0, 1, 0],
+    [y, -x, 0, 0, 0, 1]] of the TARGET point (x, y, z); returns the 6 x 6 sum of G^T G."""
+    src = np.asarray(source, np.float64)
+    tgt = np.ascontiguousarray(target, np.float64)
+    T = np.asarray(transformation, np.float64)
+    pcd = src if is_identity(T) else transform_points(T, src)
+    _, tj, _, _ = correspondences(pcd, cKDTree(tgt), tgt, float(max_correspondence_distance), workers, bounded)
+    x, y, z = tgt[tj, 0], tgt[tj, 1], tgt[tj, 2]
+    n = len(tj)
+    G = np.zeros((n, 3, 6))
+    G[:, 0, 1], G[:, 0, 2], G[:, 0, 3] = z, -y, 1.0
+    G[:, 1, 0], G[:, 1, 2], G[:, 1, 4] = -z, x, 1.0
+    G[:, 2, 0], G[:, 2, 1], G[:, 2, 5] = y, -x, 1.0
+    return np.einsum("nka,nkb->ab", G, G)

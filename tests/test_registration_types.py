@@ -14,7 +14,7 @@ from open3d_slam_advanced_rss_2024_public_amd import _lib
 from open3d_slam_advanced_rss_2024_public_amd import registration as reg
 from open3d_slam_advanced_rss_2024_public_amd import synthetic as syn
 
-from o3d_registration_ref import covariances_from_normals, inv_sqrt_spd, registration_icp as ref_icp
+from o3d_registration_ref import covariances_from_normals, information_matrix as ref_information, inv_sqrt_spd, registration_icp as ref_icp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -86,6 +86,38 @@ def test_restatement_types_converge():
         r = ref_icp(src, tgt, 1.0, init, kind, **kw)
         dt, ang = orc.pose_error(T_gt, r["transformation"])
         assert np.linalg.norm(dt) < 0.03 and ang < 0.01, (kind, dt, ang)
+
+
+@pytest.mark.parametrize("max_dist", [1.0, 0.3])
+def test_restatement_information_matrix_equals_oracle(max_dist):
+    """GetInformationMatrixFromPointClouds of the restatement (rows from the target point) is the oracle's, at a pose off the truth
+    and at identity, with part of the source beyond every target point."""
+    src, tgt, _, T_gt, _ = pair()
+    src[:200] += 30.0
+    for T in (syn.perturb_pose(T_gt, 0.1, 2.0, seed=5), np.eye(4)):
+        want = orc.o3d_information_matrix(src, tgt, max_dist, T)
+        got = ref_information(src, tgt, max_dist, T)
+        assert want[3, 3] > 0 or np.array_equal(T, np.eye(4))
+        assert np.abs(got - want).max() <= 1e-12 * max(1.0, np.abs(want).max()), np.abs(got - want).max()
+        assert np.array_equal(ref_information(src, tgt, max_dist, T, workers=4, bounded=True), got)
+
+
+@pytest.mark.parametrize("kind", ["PointToPlaneIcp", "PointToPointIcp", "GeneralizedIcp"])
+def test_restatement_workers_and_bound_change_nothing(kind):
+    """Threads in the tree queries and the query's upper bound r (1 + 1e-9) leave every field of the result as it was."""
+    src, tgt, tgt_n, T_gt, src_n = pair(4000, 6000, seed=9)
+    src[:100] = np.nan
+    src[100:300] += 5.0
+    init = syn.perturb_pose(T_gt, 0.1, 2.0, seed=5)
+    kw = {"target_normals": tgt_n, "source_normals": src_n} if kind == "GeneralizedIcp" else \
+        ({"target_normals": tgt_n} if kind == "PointToPlaneIcp" else {})
+    base = ref_icp(src, tgt, 0.8, init, kind, **kw)
+    assert base["correspondences"] > 0
+    for workers, bounded in ((16, False), (1, True), (16, True)):
+        r = ref_icp(src, tgt, 0.8, init, kind, workers=workers, bounded=bounded, **kw)
+        for k in ("iterations", "correspondences", "fitness", "inlier_rmse"):
+            assert r[k] == base[k], (workers, bounded, k)
+        assert np.array_equal(r["transformation"], base["transformation"])
 
 
 def test_headers_compile_as_c99_and_link():
