@@ -499,6 +499,13 @@ inline size_t grid_index_arena_bytes(int64_t N) {
 }
 constexpr size_t kGridMaxCells = (size_t)1 << 24;
 
+// hooks build: what the O3S_PRINT_NGRID line of build_grid_index reports (the product compiles none of it)
+#ifdef O3S_TEST_HOOKS
+#define O3S_NGRID_NOTE(x) x
+#else
+#define O3S_NGRID_NOTE(x)
+#endif
+
 // cell0: first guess of the cell edge; the cell is then re-sized once so that an occupied cell holds ~target_rho points
 // (surface-like data: density ~ cell^2), never above cell_max.  Any cell size keeps the searches exact.
 // known_bb (nullable): the cloud's bounds as the six order-preserving bit patterns k_bounds_post makes (minima, maxima) — a caller that has
@@ -560,6 +567,9 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
   double cell = std::max(std::max(cell0, ext / 512.0), 1e-9);
   const double kMaxCells = (double)kGridMaxCells;
   int64_t dims[3];
+  O3S_NGRID_NOTE(int cap_steps = 0);
+  O3S_NGRID_NOTE(bool resized = false);
+  O3S_NGRID_NOTE(int64_t occ_first = 0);
   auto size_grid = [&]() {
     for (;;) {
       double total = 1;
@@ -569,6 +579,7 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
       }
       if (total <= kMaxCells) break;
       cell *= 1.26;
+      O3S_NGRID_NOTE(++cap_steps);
     }
   };
   auto resize_for = [&](int64_t n_occ) {  // true: the cell edge changed
@@ -594,7 +605,11 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
       int64_t n_occ = 0;
       const int rc = scan_flags(head, ord, N, tmp, tb_scan, &n_occ, s);
       if (rc != O3S_OK) return rc;
-      if (resize_for(n_occ)) continue;
+      O3S_NGRID_NOTE(occ_first = n_occ);
+      if (resize_for(n_occ)) {
+        O3S_NGRID_NOTE(resized = true);
+        continue;
+      }
     }
     break;
   }
@@ -620,6 +635,21 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
   hipLaunchKernelGGL(k_cell_ranges, dim3(nblk(N)), dim3(kB), 0, s, keys2, N, cbeg, cend);
   hipLaunchKernelGGL(k_gather_sorted, dim3(nblk(N)), dim3(kB), 0, s, d_pts, vals2, N, sp);
   CK(hipGetLastError());
+#ifdef O3S_TEST_HOOKS
+  if (O3S_HOOK_ENV("O3S_PRINT_NGRID")) {  // hooks build: the sizing path this build took (tests/test_gpu_normals_scale.py)
+    int64_t occ = occ_first;  // the occupied cells of the final grid: counted again when the re-size moved the cell
+    if (resized) {
+      hipLaunchKernelGGL(k_heads, dim3(nblk(N)), dim3(kB), 0, s, keys2, N, ~0ull, head);
+      const int rc = scan_flags(head, ord, N, tmp, tb_scan, &occ, s);
+      if (rc != O3S_OK) return rc;
+    }
+    std::fprintf(stderr,
+                 "o3s ngrid: N %lld ext %.17g cell0 %.17g rho %.17g cell %.17g origin %.17g %.17g %.17g dims %lld %lld %lld occ_first %lld "
+                 "occ %lld resized %d cap_steps %d known_bb %d\n",
+                 (long long)N, ext, cell0, target_rho, cell, lo[0], lo[1], lo[2], (long long)dims[0], (long long)dims[1], (long long)dims[2],
+                 (long long)occ_first, (long long)occ, resized ? 1 : 0, cap_steps, known_bb ? 1 : 0);
+  }
+#endif
   out->g = g;
   out->cbeg = cbeg;
   out->cend = cend;
@@ -642,8 +672,12 @@ inline int estimate_normals_dev(NormalsWork& w, const double* d_pts, int64_t N, 
   const int rc = build_grid_index(w, d_pts, N, radius * 0.5, rho, radius, &gi, s);
   if (rc != O3S_OK) return rc;
   const double r2 = radius * radius;
-#define O3S_NORMALS_LAUNCH(KK) \
-  hipLaunchKernelGGL(k_normals<KK>, dim3(nblk(N)), dim3(kB), 0, s, gi.sp, gi.vals, d_pts, N, gi.g, gi.cbeg, gi.cend, max_nn, r2, d_out_n, d_out_idx)
+  O3S_NGRID_NOTE(int launched_k = 0);
+#define O3S_NORMALS_LAUNCH(KK)                                                                                                                         \
+  do {                                                                                                                                                 \
+    O3S_NGRID_NOTE(launched_k = KK);                                                                                                                   \
+    hipLaunchKernelGGL(k_normals<KK>, dim3(nblk(N)), dim3(kB), 0, s, gi.sp, gi.vals, d_pts, N, gi.g, gi.cbeg, gi.cend, max_nn, r2, d_out_n, d_out_idx); \
+  } while (0)
   if (max_nn <= 6) O3S_NORMALS_LAUNCH(6);
   else if (max_nn <= 8) O3S_NORMALS_LAUNCH(8);
   else if (max_nn <= 10) O3S_NORMALS_LAUNCH(10);
@@ -653,6 +687,10 @@ inline int estimate_normals_dev(NormalsWork& w, const double* d_pts, int64_t N, 
   else O3S_NORMALS_LAUNCH(32);
 #undef O3S_NORMALS_LAUNCH
   CK(hipGetLastError());
+#ifdef O3S_TEST_HOOKS
+  if (O3S_HOOK_ENV("O3S_PRINT_NGRID"))  // hooks build: the k_normals instantiation this call launched
+    std::fprintf(stderr, "o3s normals: N %lld max_nn %d K %d radius %.17g\n", (long long)N, max_nn, launched_k, radius);
+#endif
   return O3S_OK;
 }
 

@@ -1563,11 +1563,66 @@ V3 fast_eigen3x3(double A[3][3]) {
 }
 }  // namespace
 
+namespace {
+// EstimateNormals' work after the search, for one point: covariance of the neighbour list nn[0..k) (utility::ComputeCovariance:
+// cumulants in neighbour order), FastEigen3x3, NormalizeNormals(), OrientNormalsTowardsCameraLocation(camera = 0)
+void normal_from_list(const double* pts, int64_t i, const int32_t* nn, int64_t k, double* out) {
+  const double qx = pts[3 * i], qy = pts[3 * i + 1], qz = pts[3 * i + 2];
+  double C[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};  // fewer than 3 neighbours: identity covariance
+  if (k >= 3) {
+    double cu[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t t = 0; t < k; ++t) {
+      const double* p = pts + 3 * (int64_t)nn[t];
+      cu[0] += p[0];
+      cu[1] += p[1];
+      cu[2] += p[2];
+      cu[3] += p[0] * p[0];
+      cu[4] += p[0] * p[1];
+      cu[5] += p[0] * p[2];
+      cu[6] += p[1] * p[1];
+      cu[7] += p[1] * p[2];
+      cu[8] += p[2] * p[2];
+    }
+    for (int t = 0; t < 9; ++t) cu[t] /= (double)k;
+    C[0][0] = cu[3] - cu[0] * cu[0];
+    C[1][1] = cu[6] - cu[1] * cu[1];
+    C[2][2] = cu[8] - cu[2] * cu[2];
+    C[0][1] = C[1][0] = cu[4] - cu[0] * cu[1];
+    C[0][2] = C[2][0] = cu[5] - cu[0] * cu[2];
+    C[1][2] = C[2][1] = cu[7] - cu[1] * cu[2];
+  }
+  V3 n = fast_eigen3x3(C);
+  if (std::sqrt(dot3(n, n)) == 0.0) n = {0.0, 0.0, 1.0};  // EstimateNormals: zero normal -> (0, 0, 1)
+  {  // NormalizeNormals(): Eigen normalize()
+    const double z = dot3(n, n);
+    if (z > 0) {
+      const double s = std::sqrt(z);
+      n = {n.x / s, n.y / s, n.z / s};
+    }
+  }
+  {  // OrientNormalsTowardsCameraLocation(camera = 0)
+    const V3 ref{0.0 - qx, 0.0 - qy, 0.0 - qz};
+    if (std::sqrt(dot3(n, n)) == 0.0) {
+      n = ref;
+      const double l = std::sqrt(dot3(n, n));
+      if (l == 0.0) n = {0.0, 0.0, 1.0};
+      else n = {n.x / l, n.y / l, n.z / l};
+    } else if (dot3(n, ref) < 0.0) {
+      n = {n.x * -1.0, n.y * -1.0, n.z * -1.0};
+    }
+  }
+  out[3 * i] = n.x;
+  out[3 * i + 1] = n.y;
+  out[3 * i + 2] = n.z;
+}
+}  // namespace
+
 int orc_estimate_normals(const double* pts, int64_t N, double radius, int32_t max_nn, double* out_normals, int32_t* nn_idx) {
   const double r2 = radius * radius;
 #pragma omp parallel
   {
     std::vector<std::pair<double, int32_t>> cand((size_t)N);
+    std::vector<int32_t> nn((size_t)std::max<int32_t>(max_nn, 1));
 #pragma omp for schedule(dynamic, 64)
     for (int64_t i = 0; i < N; ++i) {
       const double qx = pts[3 * i], qy = pts[3 * i + 1], qz = pts[3 * i + 2];
@@ -1582,55 +1637,22 @@ int orc_estimate_normals(const double* pts, int64_t N, double radius, int32_t ma
       std::partial_sort(cand.begin(), cand.begin() + k0, cand.end());  // ascending (d2, index)
       int64_t k = 0;  // KDTreeFlann::SearchHybrid: knnSearch(max_nn), then cut at lower_bound(radius^2)
       while (k < k0 && cand[(size_t)k].first < r2) ++k;
+      for (int64_t t = 0; t < k; ++t) nn[(size_t)t] = cand[(size_t)t].second;
       if (nn_idx)
         for (int32_t t = 0; t < max_nn; ++t) nn_idx[i * max_nn + t] = t < k ? cand[(size_t)t].second : -1;
-      double C[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};  // fewer than 3 neighbours: identity covariance
-      if (k >= 3) {  // utility::ComputeCovariance: cumulants in neighbour order
-        double cu[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int64_t t = 0; t < k; ++t) {
-          const double* p = pts + 3 * (int64_t)cand[(size_t)t].second;
-          cu[0] += p[0];
-          cu[1] += p[1];
-          cu[2] += p[2];
-          cu[3] += p[0] * p[0];
-          cu[4] += p[0] * p[1];
-          cu[5] += p[0] * p[2];
-          cu[6] += p[1] * p[1];
-          cu[7] += p[1] * p[2];
-          cu[8] += p[2] * p[2];
-        }
-        for (int t = 0; t < 9; ++t) cu[t] /= (double)k;
-        C[0][0] = cu[3] - cu[0] * cu[0];
-        C[1][1] = cu[6] - cu[1] * cu[1];
-        C[2][2] = cu[8] - cu[2] * cu[2];
-        C[0][1] = C[1][0] = cu[4] - cu[0] * cu[1];
-        C[0][2] = C[2][0] = cu[5] - cu[0] * cu[2];
-        C[1][2] = C[2][1] = cu[7] - cu[1] * cu[2];
-      }
-      V3 n = fast_eigen3x3(C);
-      if (std::sqrt(dot3(n, n)) == 0.0) n = {0.0, 0.0, 1.0};  // EstimateNormals: zero normal -> (0, 0, 1)
-      {  // NormalizeNormals(): Eigen normalize()
-        const double z = dot3(n, n);
-        if (z > 0) {
-          const double s = std::sqrt(z);
-          n = {n.x / s, n.y / s, n.z / s};
-        }
-      }
-      {  // OrientNormalsTowardsCameraLocation(camera = 0)
-        const V3 ref{0.0 - qx, 0.0 - qy, 0.0 - qz};
-        if (std::sqrt(dot3(n, n)) == 0.0) {
-          n = ref;
-          const double l = std::sqrt(dot3(n, n));
-          if (l == 0.0) n = {0.0, 0.0, 1.0};
-          else n = {n.x / l, n.y / l, n.z / l};
-        } else if (dot3(n, ref) < 0.0) {
-          n = {n.x * -1.0, n.y * -1.0, n.z * -1.0};
-        }
-      }
-      out_normals[3 * i] = n.x;
-      out_normals[3 * i + 1] = n.y;
-      out_normals[3 * i + 2] = n.z;
+      normal_from_list(pts, i, nn.data(), k, out_normals);
     }
+  }
+  return 0;
+}
+
+int orc_normals_from_neighbours(const double* pts, int64_t N, const int32_t* nn_idx, int32_t max_nn, double* out_normals) {
+#pragma omp parallel for schedule(dynamic, 256)
+  for (int64_t i = 0; i < N; ++i) {
+    const int32_t* row = nn_idx + i * max_nn;
+    int64_t k = 0;
+    while (k < max_nn && row[k] >= 0) ++k;
+    normal_from_list(pts, i, row, k, out_normals);
   }
   return 0;
 }

@@ -170,6 +170,9 @@ int64_t orc_transform_cloud(const double* T, const double* pts, const double* no
  * Neighbours: the max_nn nearest points (the query itself included), ascending (d2, index), cut at d2 < radius^2;
  * brute force.  nn_idx (nullable): N x max_nn int32, -1 padded.  Returns 0. */
 int orc_estimate_normals(const double* pts, int64_t N, double radius, int32_t max_nn, double* out_normals, int32_t* nn_idx);
+/* The part of orc_estimate_normals after the search, on given lists: nn_idx is N x max_nn int32, each row the point's
+ * neighbours in order, -1 padded (what orc_estimate_normals writes).  Same bits as orc_estimate_normals on its own lists. */
+int orc_normals_from_neighbours(const double* pts, int64_t N, const int32_t* nn_idx, int32_t max_nn, double* out_normals);
 /* Open3D v0.15.1 pipelines::registration::RegistrationICP with TransformationEstimationPointToPlane (L2 loss) as the
  * reference calls it for loop closures and odometry constraints (O3S/src/CloudRegistration.cpp:57-61,
  * O3S/src/PlaceRecognition.cpp:111, O3S/src/constraint_builders.cpp:60-68), and GetInformationMatrixFromPointClouds

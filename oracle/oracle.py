@@ -124,6 +124,7 @@ def lib():
         L.orc_voxel_downsample_o3d.argtypes = [C.c_double, dp, dp, C.c_int64, dp, dp, ip]
         L.orc_o3d_to_pm.argtypes = [dp, dp, C.c_int64, fp, fp]
         L.orc_estimate_normals.argtypes = [dp, C.c_int64, C.c_double, C.c_int32, dp, ip]
+        L.orc_normals_from_neighbours.argtypes = [dp, C.c_int64, ip, C.c_int32, dp]
         L.orc_o3d_registration_icp.argtypes = [dp, C.c_int64, dp, dp, C.c_int64, C.c_double, dp, C.c_double, C.c_double, C.c_int32,
                                                C.POINTER(_O3dIcpResult)]
         L.orc_o3d_information_matrix.argtypes = [dp, C.c_int64, dp, C.c_int64, C.c_double, dp, dp]
@@ -410,6 +411,17 @@ def estimate_normals(pts, radius, max_nn, want_neighbours=False):
     nn = np.zeros((p.shape[0], max_nn), np.int32) if want_neighbours else None
     lib().orc_estimate_normals(_d(p), p.shape[0], float(radius), int(max_nn), _d(out), _i(nn))
     return (out, nn) if want_neighbours else out
+
+
+def normals_from_neighbours(pts, nn_idx):
+    """The part of estimate_normals after the search, on given lists (N x max_nn int32, -1 padded)."""
+    p = np.ascontiguousarray(pts, np.float64)
+    nn = np.ascontiguousarray(nn_idx, np.int32)
+    assert nn.ndim == 2 and nn.shape[0] == p.shape[0] and nn.shape[1] >= 1
+    assert ((nn >= -1) & (nn < p.shape[0])).all()
+    out = np.zeros_like(p)
+    lib().orc_normals_from_neighbours(_d(p), p.shape[0], _i(nn), nn.shape[1], _d(out))
+    return out
 
 
 def o3d_registration_icp(source, target, target_normals, max_correspondence_distance, init=None, relative_fitness=1e-6,
