@@ -132,11 +132,12 @@ int o3s_icp_set_reading_dev(o3s_icp* h, const void* d_xyzw, const void* d_normal
 int o3s_icp_reading_is_spatially_sorted(o3s_icp* h, int sorted);
 int o3s_icp_compute_resident(o3s_icp* h, const float T_init[16], float T_out[16], o3s_icp_stats* stats);
 /* The same call in two halves (round 5): _launch enqueues the reading's preparation and the chain on the handle's stream and returns
- * without looking at the result — a chain replayed from a graph goes out whole, one issued eagerly (a reading of a new size) goes
- * out as far as the handle's previous call needed; _finish waits, issues what is left if the chain is not done, and composes the
- * pose.  Same iterations, same bits as o3s_icp_compute_resident (where the host looks never decides what the chain computes).  A
- * host uses the gap for work that does not need the pose: MapperHip counts the map patch (Mapper.cpp:328-336) there on the scans
- * that do not renew the reference.  One call in flight per handle; nothing else may be called on the handle between the halves. */
+ * without looking at the result — a chain replayed from a graph goes out as one replay (whole, or the first chunk of a chain that
+ * can stop by itself), one issued eagerly (a reading of a new size) goes out as far as the handle's previous call needed (a sharded
+ * one: one chunk of its graph); _finish waits, issues what is left if the chain is not done, and composes the pose.
+ * Same iterations, same bits as o3s_icp_compute_resident (where the host looks never decides what the chain computes).  A host uses
+ * the gap for work that does not need the pose: MapperHip counts the map patch (Mapper.cpp:328-336) there on the scans that do not
+ * renew the reference.  One call in flight per handle; nothing else may be called on the handle between the halves. */
 int o3s_icp_compute_resident_launch(o3s_icp* h, const float T_init[16]);
 int o3s_icp_compute_resident_finish(o3s_icp* h, float T_out[16], o3s_icp_stats* stats);
 /* BASELINE config 3 (a collection of independent scan/submap pairs, e.g. loop-closure candidates, the serial loop at
@@ -203,7 +204,8 @@ int o3s_icp_get_trace(const o3s_icp* h, float* T_iters, float* limits, int64_t* 
 int64_t o3s_icp_get_reading_order(const o3s_icp* h, int32_t* order, int64_t cap);
 /* Mean subtracted from the reference at init (T_refIn_refMean translation, LPM/ICP.cpp:313-314). */
 int o3s_icp_reference_mean(const o3s_icp* h, float mean3[3]);
-/* Split of the last o3s_icp_compute / _compute_resident on this handle, in microseconds: out4[0] = issuing the call's work on
+/* Split of the last compute on this handle (o3s_icp_compute, _compute_resident, its two halves, or the handle's pair of
+ * o3s_icp_compute_batch), in microseconds: out4[0] = issuing the call's work on
  * the host (uploads, launches), out4[1] = the host waiting for the chain's post, out4[2] = event / stream queries made while
  * waiting, out4[3] = device time from the call's first kernel to its first matcher launch (transform + sort of the reading).
  * Diagnostics. */

@@ -71,6 +71,33 @@ struct HostStage {  // pinned staging block for small H2D / D2H transfers
 constexpr int kNumKernels = 5;
 constexpr size_t kHistWords = (size_t)kHistReplicas * kHistBins + 1024;  // level-1 replicas + the level-2 histogram right behind them
 
+struct ChainArgs {
+  int N;
+  int match_g;  // lanes per query of k_match2
+  int nb_match, nb_part, nb_cls;
+  int nb_fused;  // blocks of the fused selection + normal-equation kernel (0: the two kernels are launched separately)
+  bool has_n;
+  uint32_t* spec;  // the speculative digit histograms of the trim selection (k_match2 -> k_classify); null: level 1 only
+  float *rx, *ry, *rz, *rnx, *rny, *rnz;
+  ChainParams cp;
+  GridParams g;
+};
+
+// One compute() from compute_launch to compute_finish: the plan compute_launch builds once (what the chain computes, how its
+// iterations go onto the stream, how many go out before each look at its post) and how far the call has got.
+struct Call {
+  bool live = false;  // compute_launch succeeded and compute_finish has not run yet
+  ChainArgs a{};      // launch arguments; a.cp: the chain's parameters
+  bool stats = false;
+  float Tc[16], T0[16];  // T_refIn_refMean and the initial guess in the <refMean> frame
+  int iters_cap = 0;     // max_iters, or 4096 without a Counter checker
+  enum Issue { kEager, kReplay, kProfiled } issue = kEager;  // launch by launch, replays of the captured graph, launch by launch between events
+  int first = 0, step = 0;  // iterations issued before the first look at the post, and before each later one
+  int issued = 0;
+  // the chain is certain to end inside what was issued: a Counter checker and all of max_iters out
+  bool ends_inside() const { return a.cp.max_iters > 0 && issued >= a.cp.max_iters; }
+};
+
 }  // namespace
 
 struct o3s_icp {
@@ -126,9 +153,8 @@ struct o3s_icp {
   HostPost* post = nullptr;
   HostPost* post_dev = nullptr;
   uint32_t call_seq = 0;     // sequence number of the compute() in flight (k_read_prep writes it into the state)
-  int pend_issued = 0;       // iterations the call in flight has issued so far
   double wall_clock_khz = 100000.0;  // wall_clock64 rate (hipDeviceAttributeWallClockRate)
-  // host-side split of the last compute(): microseconds spent issuing (compute_launch) and waiting (wait_post), stream queries made
+  // host-side split of the last compute(): microseconds spent issuing (either half) and waiting (wait_post), stream queries made
   double host_issue_us = 0.0, host_wait_us = 0.0;
   int host_queries = 0;
   // what ended the waits of the last compute(): the chain's post, the `drained` event, the 2 ms stream guard; and how the chain was
@@ -141,15 +167,10 @@ struct o3s_icp {
   int trace_cap = 0;
   int last_iters = 0;
 
-  // a compute() in flight between compute_launch and compute_finish
-  bool pend_valid = false;
-  int pend_graph_left = 0, pend_graph_chunk = 0;  // iterations the chunked graph replay has not issued yet (compute_finish)
-  // o3s_icp_compute_resident_launch: an eagerly issued chain does not look at its `done` flag inside the launch — it issues as many
-  // iterations as the last call needed and returns; compute_finish looks, and issues the rest two at a time if the chain is not done
-  bool defer_looks = false, pend_eager = false;
-  int pend_iters_cap = 0, pend_look_step = 2;
-  float pend_Tc[16], pend_T0[16];
-  ChainParams pend_cp{};
+  Call call;  // the compute() in flight between compute_launch and compute_finish
+#ifdef O3S_TEST_HOOKS
+  std::vector<int> looks;  // hooks build (O3S_PRINT_CHAIN): iterations issued at each look at the post of the call in flight
+#endif
 
   // Every DevBuf of the handle reports (re)allocations here; the graph key carries the value, so a graph is never
   // replayed after ANY buffer a captured kernel points at has moved (the key's pointer list alone missed d_cand & co.).
@@ -319,6 +340,9 @@ inline double now_us() {
 
 int wait_post_impl(o3s_icp* h, uint32_t seq, hipEvent_t drained, bool* done);
 int wait_post(o3s_icp* h, uint32_t seq, hipEvent_t drained, bool* done) {
+#ifdef O3S_TEST_HOOKS
+  if (h->looks.empty() || h->looks.back() != h->call.issued) h->looks.push_back(h->call.issued);
+#endif
   const double t0 = now_us();
   const int rc = wait_post_impl(h, seq, drained, done);
   h->host_wait_us += now_us() - t0;
@@ -612,18 +636,6 @@ int ensure_trace(o3s_icp* h, int cap) {
   h->trace_cap = cap;
   return O3S_OK;
 }
-
-struct ChainArgs {
-  int N;
-  int match_g;  // lanes per query of k_match2
-  int nb_match, nb_part, nb_cls;
-  int nb_fused;  // blocks of the fused selection + normal-equation kernel (0: the two kernels are launched separately)
-  bool has_n;
-  uint32_t* spec;  // the speculative digit histograms of the trim selection (k_match2 -> k_classify); null: level 1 only
-  float *rx, *ry, *rz, *rnx, *rny, *rnz;
-  ChainParams cp;
-  GridParams g;
-};
 
 ChainArgs chain_args(o3s_icp* h, const ChainParams& cp) {
   ChainArgs a{};
@@ -922,13 +934,41 @@ int pull_state(o3s_icp* h) {
   return O3S_OK;
 }
 
-// Enqueues one whole compute() on the handle's stream (prepare, iteration chain, read-back of the state into pinned
-// memory).  Returns without waiting when the chain could be issued in one go (Counter checker present, no profiling):
-// compute_finish() then waits and composes the result, so several handles can be in flight at once.
-int compute_launch(o3s_icp* h, const float* T_init) {
-  h->pend_valid = false;
-  h->pend_graph_left = 0;
-  h->pend_eager = false;
+// Issues the call's next segment and counts it: one replay of the captured graph (`step` iterations; past max_iters they are
+// no-ops), or the next iterations launch by launch up to iters_cap, each between its six events when profiling.  Unless the chain
+// is certain to end inside what is now issued, ev_end is recorded right behind the segment's last launch: the look that follows
+// learns from it that everything issued has run without ending the chain.  The capture window (`capturing`) records the first
+// segment of an eager plan: no event, and a failed launch fails the capture without a message.  A failed exchange callback ends
+// the segment with its error.
+int issue_segment(o3s_icp* h, Call& c, bool capturing = false) {
+  const int n = c.issued ? c.step : c.first;
+  if (c.issue == Call::kReplay) {
+    HIP_TRY(h, hipGraphLaunch(h->graph_exec, h->stream));
+    c.issued += n;
+  } else {
+    for (const int end = std::min(c.issued + n, c.iters_cap); c.issued < end; ++c.issued) {
+      if (!h->shard.active) {
+        launch_iteration(h, c.a, c.stats, c.issue == Call::kProfiled ? &h->prof_events[(size_t)c.issued * 6] : nullptr, c.issued);
+        continue;
+      }
+      const int rc = launch_iteration_sharded(h, c.a, c.stats, c.issued);
+      if (rc != O3S_OK) return rc;
+    }
+    if (capturing) return hipGetLastError() == hipSuccess ? O3S_OK : O3S_ERR_HIP;
+    HIP_TRY(h, hipGetLastError());
+  }
+  if (!c.ends_inside()) HIP_TRY(h, hipEventRecord(h->ev_end, h->stream));
+  return O3S_OK;
+}
+
+// Plans one compute() (Call) and enqueues its first part on the handle's stream: the reading's preparation and the first segment
+// of the iteration chain.  Never looks at the chain's post: compute_finish does, so several handles can be in flight at once.
+int start_call(o3s_icp* h, const float* T_init) {
+  Call& c = h->call;
+  c.live = false;
+#ifdef O3S_TEST_HOOKS
+  h->looks.clear();
+#endif
   if (!h->ref_ready) return fail(h, O3S_ERR_NOT_INITIALIZED, "compute before a successful init_reference");
   if (!h->reading_ready || h->N <= 0) return fail(h, O3S_ERR_EMPTY_READING, "the reading point cloud is empty");
   if (!h->ref_has_normals) return fail(h, O3S_ERR_BAD_SHAPE, "point-to-plane needs reference normals");
@@ -938,114 +978,51 @@ int compute_launch(o3s_icp* h, const float* T_init) {
   int rc = ensure_iteration_buffers(h, N);
   if (rc != O3S_OK) return rc;
   const ChainParams cp = make_chain(h, h->read_has_normals);
-  const int iters_cap = cp.max_iters > 0 ? cp.max_iters : 4096;
-  rc = ensure_trace(h, std::min(iters_cap, 4096));
+  c.iters_cap = cp.max_iters > 0 ? cp.max_iters : 4096;
+  rc = ensure_trace(h, std::min(c.iters_cap, 4096));
   if (rc != O3S_OK) return rc;
 
   // T_refMean_readMean = T_refIn_refMean^-1 * T_refIn_readIn  (LPM/ICP.cpp:373-374; reading mean forced to 0 at :364)
-  float* Tc = h->pend_Tc;
-  float* T0 = h->pend_T0;
   float TcInv[16];
-  hidentity(Tc);
+  hidentity(c.Tc);
   hidentity(TcInv);
   for (int d = 0; d < 3; ++d) {
-    HM4(Tc, d, 3) = h->mean[d];
+    HM4(c.Tc, d, 3) = h->mean[d];
     HM4(TcInv, d, 3) = -h->mean[d];
   }
-  hmul4(TcInv, T_init, T0);
-  if (!hrigid(T0)) return fail(h, O3S_ERR_NOT_RIGID, "RigidTransformation: rotation matrix is not orthogonal (initial guess)");
+  hmul4(TcInv, T_init, c.T0);
+  if (!hrigid(c.T0)) return fail(h, O3S_ERR_NOT_RIGID, "RigidTransformation: rotation matrix is not orthogonal (initial guess)");
 
   if (++h->call_seq == 0) ++h->call_seq;  // what this call's posts carry (k_read_prep writes it into the state)
-  h->pend_issued = 0;
-  rc = prepare_reading(h, T0, h->cfg.sort_queries != 0 && h->cfg.matcher == 0 && !h->reading_presorted, /*reset_chain=*/true, cp.use_differential != 0);
+  c.issued = 0;
+  rc = prepare_reading(h, c.T0, h->cfg.sort_queries != 0 && h->cfg.matcher == 0 && !h->reading_presorted, /*reset_chain=*/true, cp.use_differential != 0);
   if (rc != O3S_OK) return rc;
-
-  const ChainArgs a = chain_args(h, cp);
-  const bool want_stats = h->cfg.match_stats != 0;
-  h->pend_cp = cp;
-  // looks at the chain's post after `upto` iterations have been issued: true when the chain is done
-  auto chain_done_after = [&](int /*upto*/, bool* done) -> int {
-    HIP_TRY(h, hipEventRecord(h->ev_end, h->stream));  // behind everything issued so far
-    const int w = wait_post(h, h->call_seq, h->ev_end, done);
-    if (w < 0) return fail(h, O3S_ERR_HIP, "compute: a kernel of the iteration chain failed");
-    if (w == 0) return fail(h, O3S_ERR_HIP, "compute: the iteration chain ended without posting its state");
-    return O3S_OK;
-  };
+  c.a = chain_args(h, cp);
+  c.stats = h->cfg.match_stats != 0;
+  c.issue = Call::kEager;
   if (h->shard.active && h->cfg.matcher != 0) return fail(h, O3S_ERR_BAD_CONFIG, "the sharded mode supports KDTreeMatcher only");
-  const bool shard_graph = h->shard.active && h->shard.capturable && h->cfg.use_graph && cp.max_iters > 0 && !h->profiling;
-  if (h->shard.active && !shard_graph) {
-    // every rank issues the same iterations: the state is bit-identical across ranks, so the chunked `done` test below
-    // breaks out on the same iteration everywhere and the collectives stay matched
-    // A chain that can only end at max_iters (no Differential checker) is issued in one go: no host round trip at all.
-    // One that may stop by itself is looked at every kChunk iterations (the same chunk as the graph replay of the
-    // unsharded chain); the flag every rank reads is bit-identical, so all ranks leave the loop together.
-    constexpr int kChunk = 5;
-    const bool may_stop_early = cp.use_differential != 0 || cp.max_iters <= 0;
-    for (int it = 0; it < iters_cap; ++it) {
-      rc = launch_iteration_sharded(h, a, want_stats, it);
-      if (rc != O3S_OK) return rc;
-      h->pend_issued = it + 1;
-      if (may_stop_early && (it % kChunk) == kChunk - 1 && it + 1 < iters_cap) {
-        bool done = false;
-        rc = chain_done_after(it + 1, &done);
-        if (rc != O3S_OK) return rc;
-        if (done) break;
-      }
-    }
-    HIP_TRY(h, hipGetLastError());
-  } else if (h->profiling) {
-    for (int k = 0; k < kNumKernels; ++k) {
-      h->kernel_ms[k] = 0.f;
-      h->kernel_launches[k] = 0;
-    }
-    const size_t need = (size_t)iters_cap * 6;
-    while (h->prof_events.size() < need) {
-      hipEvent_t e;
-      HIP_TRY(h, hipEventCreate(&e));
-      h->prof_events.push_back(e);
-    }
-    int launched = 0;
-    for (int it = 0; it < iters_cap; ++it) {
-      launch_iteration(h, a, want_stats, &h->prof_events[(size_t)it * 6], it);
-      ++launched;
-      h->pend_issued = launched;
-      if (cp.max_iters <= 0 && (it % 16) == 15) {
-        bool done = false;
-        rc = chain_done_after(launched, &done);
-        if (rc != O3S_OK) return rc;
-        if (done) break;
-      }
-    }
-    HIP_TRY(h, hipGetLastError());
-    rc = pull_state(h);  // the events have to be complete before they are read: this path waits for the stream
-    if (rc != O3S_OK) return rc;
-    const int ran = std::min(launched, h->stage->state.iter + (h->stage->state.status ? 1 : 0));
-    for (int it = 0; it < ran; ++it)
-      for (int k = 0; k < kNumKernels; ++k) {
-        if (k == 3 && a.nb_fused > 0) continue;  // fused chain: k_sel_ne (timed as k = 2) holds the selection and the normal equations
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, h->prof_events[(size_t)it * 6 + k], h->prof_events[(size_t)it * 6 + k + 1]) == hipSuccess) {
-          h->kernel_ms[k] += ms;
-          h->kernel_launches[k] += 1;
-        }
-      }
-  } else {
-    // Replay policy.  A hipGraph of the whole chain (5 launches x max_iters) pays off when the same shapes come back:
-    // it is captured the SECOND time a key is seen in a row and replayed from then on.  A call with new shapes (live
-    // scans change size every time) is issued eagerly in chunks; between chunks the host looks at the `done` flag, so
-    // a chain that converges after a few iterations does not pay for the rest of max_iters.
-    // With a Differential checker the chain usually stops long before max_iters, and a graph of all max_iters iterations
-    // would still issue 5 no-op launches (~1.8 us each) for every iteration after convergence.  The graph therefore holds
-    // kGraphChunk iterations and is replayed until the `done` flag comes back set (compute_finish); the first replay's
-    // read-back is the one every call needs anyway, so a chain that converges inside the first chunk pays nothing for it.
-    // Fixed-length chains (no Differential checker: the bench configurations) keep one graph of max_iters iterations.
-    constexpr int kGraphChunk = 5;
-    const int chunk = (cp.use_differential && cp.max_iters > kGraphChunk + 2) ? kGraphChunk : cp.max_iters;
+
+  // A chain that can stop by itself (a Differential checker and more than 7 iterations, or no Counter checker) is looked at every
+  // kChunk iterations; a fixed-length one goes out whole.  Sharded chains keep to that on every path: each iteration carries
+  // collectives the other ranks have to match, so the schedule may depend on the config only — never on this handle's history
+  // (eager_hint) nor on whether THIS rank's graph capture succeeded.
+  constexpr int kChunk = 5;
+  const bool chunked = cp.max_iters <= 0 || (cp.use_differential && cp.max_iters > kChunk + 2);
+  const int chunk = chunked ? kChunk : cp.max_iters;
+  // Replay policy.  A hipGraph of the chain pays off when the same shapes come back: it is captured the SECOND time a key is seen
+  // in a row and replayed from then on.  With a Differential checker the chain usually stops long before max_iters, and a graph of
+  // all max_iters iterations would still issue 5 no-op launches (~1.8 us each) for every iteration after convergence: the graph
+  // holds `chunk` iterations and is replayed until the post says done; the first replay's look is the one every call needs anyway.
+  // Fixed-length chains (no Differential checker: the bench configurations) keep one graph of max_iters iterations.  Sharded
+  // chains replay only with a capturable exchange (its collectives are graph nodes too); a profiled call is never replayed.
+  const bool graph_ok = !h->profiling && h->cfg.use_graph && cp.max_iters > 0 && (!h->shard.active || h->shard.capturable);
+  bool replay = false;
+  if (!h->profiling && (graph_ok || !h->shard.active)) {
     o3s_icp::GraphKey key;
     key.N = N;
     key.iters = chunk;
-    key.nb = a.nb_fused > 0 ? -a.nb_fused : a.nb_part;  // the fused and the two-kernel chain are different graphs
-    key.has_n = a.has_n ? 1 : 0;
+    key.nb = c.a.nb_fused > 0 ? -c.a.nb_fused : c.a.nb_part;  // the fused and the two-kernel chain are different graphs
+    key.has_n = c.a.has_n ? 1 : 0;
     key.gen = h->alloc_gen;  // every ensure() of this call has already run (ensure_iteration_buffers / ensure_trace / prepare)
     key.ptrs[0] = h->d_r.p;
     key.ptrs[1] = h->d_pos.p;
@@ -1053,13 +1030,12 @@ int compute_launch(o3s_icp* h, const float* T_init) {
     key.ptrs[3] = h->d_ref.p;
     key.ptrs[4] = h->have_grid1 ? h->d_cell_start1.p : h->d_cell_start.p;  // (any re-allocation moves key.gen as well; this tells the two kinds of chain apart)
     key.ptrs[5] = h->d_trace_T.p;
-    key.ptrs[6] = (const void*)(uintptr_t)((want_stats ? 1 : 0) | (h->shard.active ? 2 : 0) | (a.spec ? 8 : 0) | ((uintptr_t)(h->shard.active ? h->shard.world : 0) << 8));
+    key.ptrs[6] = (const void*)(uintptr_t)((c.stats ? 1 : 0) | (h->shard.active ? 2 : 0) | (c.a.spec ? 8 : 0) | ((uintptr_t)(h->shard.active ? h->shard.world : 0) << 8));
     key.ptrs[7] = h->d_perm.p;
     key.cp = cp;
     key.g = h->grid;
     key.have_grid1 = h->have_grid1;
     if (h->have_grid1) key.g1 = h->grid1;
-    const bool graph_ok = h->cfg.use_graph && cp.max_iters > 0 && (!h->shard.active || shard_graph);
     const bool have = graph_ok && h->graph_exec && graph_key_equal(key, h->graph_key);
     const bool seen_before = graph_ok && h->graph_candidate_valid && graph_key_equal(key, h->graph_candidate);
     bool capture_failed = false;
@@ -1069,25 +1045,20 @@ int compute_launch(o3s_icp* h, const float* T_init) {
         h->graph_exec = nullptr;
       }
       // Capture window: whatever fails inside it, the stream (possibly the caller's, o3s_icp_set_stream) must leave
-      // capture mode again and the partial graph must go; the call then falls back to the eager chunked path below.
+      // capture mode again and the partial graph must go; the call is then issued eagerly.
       hipGraph_t graph = nullptr;
       hipError_t ge = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal);
       if (ge == hipSuccess) {
-        int src = O3S_OK;
-        for (int it = 0; it < chunk && src == O3S_OK; ++it) {
-          // sharded + capturable exchange (ncclAllReduce on this stream): the four collectives of an iteration are graph nodes too
-          if (h->shard.active) src = launch_iteration_sharded(h, a, want_stats, it);
-          else launch_iteration(h, a, want_stats, nullptr, it);
-        }
-        hipError_t le = hipGetLastError();
-        if (le == hipSuccess && src != O3S_OK) le = hipErrorUnknown;
+        c.first = chunk;
+        const int src = issue_segment(h, c, /*capturing=*/true);
+        c.issued = 0;
         ge = hipStreamEndCapture(h->stream, &graph);  // always: ends the capture even after a failed launch
-        if (ge == hipSuccess && le != hipSuccess) ge = le;
+        if (ge == hipSuccess && src != O3S_OK) ge = hipErrorUnknown;
       }
       if (ge == hipSuccess) ge = hipGraphInstantiate(&h->graph_exec, graph, nullptr, nullptr, 0);
       if (graph) (void)hipGraphDestroy(graph);
       if (ge != hipSuccess) {
-        (void)hipGetLastError();  // clear the sticky error: the eager path below reports its own
+        (void)hipGetLastError();  // clear the sticky error: the eager chain reports its own
         h->graph_exec = nullptr;
         capture_failed = true;
       } else {
@@ -1097,111 +1068,120 @@ int compute_launch(o3s_icp* h, const float* T_init) {
     }
     h->graph_candidate = key;
     h->graph_candidate_valid = !capture_failed;
-    h->pend_graph_left = 0;
-    if (graph_ok && h->graph_exec && graph_key_equal(key, h->graph_key)) {
-      HIP_TRY(h, hipGraphLaunch(h->graph_exec, h->stream));
-      if (h->issue_mode != 1) h->issue_mode = 2;
-      h->pend_graph_left = cp.max_iters - chunk;
-      h->pend_graph_chunk = chunk;
-      h->pend_issued = chunk;
-      if (h->pend_graph_left > 0) HIP_TRY(h, hipEventRecord(h->ev_end, h->stream));  // the chain may go on beyond this chunk
-    } else {
-      // Where the host looks at the `done` flag: first after as many iterations as the LAST call on this handle needed (a
-      // mapping loop's registrations take the same three or four iterations sweep after sweep, and every iteration issued
-      // beyond the last one is four launches that return at once: ~20 us of launch time per sweep), then every second one.
-      // The iterations themselves, and so the result, do not depend on where the host looks.
-      // Sharded chains: every rank must issue the SAME iterations (each carries collectives its peers have to match), so the
-      // schedule may depend on the input only — never on this handle's history (eager_hint) nor on whether THIS rank's graph
-      // capture succeeded: the host looks exactly where the chunked graph replay would, after every `chunk` iterations.
-      const int first_look = h->shard.active ? chunk : std::min(std::max(h->eager_hint, 2), 8);
-      const int look_step = h->shard.active ? chunk : 2;
-      int next_look = first_look;
-      if (h->defer_looks && !h->shard.active) {  // the split entry points: the first look (and everything behind it) is compute_finish's
-        const int n0 = std::min(first_look, iters_cap);
-        for (int it = 0; it < n0; ++it) launch_iteration(h, a, want_stats, nullptr, it);
-        h->pend_issued = n0;
-        h->pend_eager = true;
-        h->pend_iters_cap = iters_cap;
-        h->pend_look_step = look_step;
-        next_look = iters_cap + 1;  // (skips the loop below)
-      }
-      for (int it = h->pend_eager ? iters_cap : 0; it < iters_cap; ++it) {
-        if (h->shard.active) {
-          rc = launch_iteration_sharded(h, a, want_stats, it);
-          if (rc != O3S_OK) return rc;
-        } else {
-          launch_iteration(h, a, want_stats, nullptr, it);
-        }
-        h->pend_issued = it + 1;
-        if (it + 1 == next_look && it + 1 < iters_cap) {
-          bool done = false;
-          rc = chain_done_after(it + 1, &done);  // the closing kernel's post: no copy, no stream synchronisation
-          if (rc != O3S_OK) return rc;
-          if (done) break;
-          next_look += look_step;
-        }
-      }
-      HIP_TRY(h, hipGetLastError());
+    replay = graph_ok && h->graph_exec && graph_key_equal(key, h->graph_key);
+  }
+  if (replay) {
+    c.issue = Call::kReplay;
+    c.first = c.step = chunk;
+    if (h->issue_mode != 1) h->issue_mode = 2;
+  } else if (h->profiling && !h->shard.active) {  // the whole chain between events, or 16 iterations at a time without a Counter checker
+    c.issue = Call::kProfiled;
+    c.first = c.step = cp.max_iters > 0 ? c.iters_cap : 16;
+    for (int k = 0; k < kNumKernels; ++k) {
+      h->kernel_ms[k] = 0.f;
+      h->kernel_launches[k] = 0;
     }
+    while (h->prof_events.size() < (size_t)c.iters_cap * 6) {
+      hipEvent_t e;
+      HIP_TRY(h, hipEventCreate(&e));
+      h->prof_events.push_back(e);
+    }
+  } else if (h->shard.active) {
+    c.first = c.step = chunk;
+  } else {
+    // An eager chain (a reading of a new size) is first looked at after as many iterations as the LAST call on this handle needed
+    // (a mapping loop's registrations take the same three or four iterations sweep after sweep, and every iteration issued beyond
+    // the last one is four launches that return at once: ~20 us of launch time per sweep), then after every second one.  The
+    // iterations themselves, and so the result, do not depend on where the host looks.
+    c.first = std::min(std::max(h->eager_hint, 2), 8);
+    c.step = 2;
   }
-#ifdef O3S_TEST_HOOKS
-  if (O3S_HOOK_ENV("O3S_PRINT_CHAIN")) {  // hooks build: the side of every dispatch switch this call took (tests/test_gpu_dispatch_boundaries.py)
-    static const char* issued[] = {"eager", "captured", "replayed"};
-    std::fprintf(stderr,
-                 "o3s chain: N %d matcher %s far %s it0_index %s match_g %d first_g %d normals_from_matcher %d nb_fused %d partial %d spec %d "
-                 "has_n %d issued %s\n",
-                 N, cp.mirror ? "mirror" : "kdtree", h->far_rows ? "rows" : "ring", first_index_used(h, cp) ? "first" : "main",
-                 cp.mirror ? 0 : a.match_g, cp.mirror ? 0 : match_lanes(h, a, true), normals_from_matcher(a) ? 1 : 0, a.nb_fused,
-                 (!h->shard.active && a.nb_fused == 0 && sel_partial(a)) ? 1 : 0, a.spec ? 1 : 0, a.has_n ? 1 : 0,
-                 h->profiling ? "profiled" : issued[h->issue_mode]);
-  }
-#endif
-  h->pend_valid = true;
+  rc = issue_segment(h, c);
+  if (rc != O3S_OK) return rc;
+  c.live = true;
   return O3S_OK;
 }
 
+// the per-call diagnostics of o3s_icp_host_split_ex
+void reset_call_diagnostics(o3s_icp* h) {
+  h->host_issue_us = h->host_wait_us = 0.0;
+  h->host_queries = 0;
+  h->wait_by_post = h->wait_by_event = h->wait_by_guard = h->issue_mode = 0;
+}
+
+int compute_launch(o3s_icp* h, const float* T_init) {
+  reset_call_diagnostics(h);
+  const double t0 = now_us();
+  const int rc = start_call(h, T_init);
+  h->host_issue_us += now_us() - t0;
+  return rc;
+}
+
+#ifdef O3S_TEST_HOOKS
+// hooks build: the side of every dispatch switch the call took (tests/test_gpu_dispatch_boundaries.py) and the iterations issued at
+// each look at the post, e.g. "looks 4,6"
+void print_chain(o3s_icp* h) {
+  if (!O3S_HOOK_ENV("O3S_PRINT_CHAIN")) return;
+  static const char* issued[] = {"eager", "captured", "replayed"};
+  const ChainArgs& a = h->call.a;
+  const ChainParams& cp = a.cp;
+  std::string looks;
+  for (int n : h->looks) looks += (looks.empty() ? "" : ",") + std::to_string(n);
+  std::fprintf(stderr,
+               "o3s chain: N %d matcher %s far %s it0_index %s match_g %d first_g %d normals_from_matcher %d nb_fused %d partial %d spec %d "
+               "has_n %d issued %s looks %s\n",
+               a.N, cp.mirror ? "mirror" : "kdtree", h->far_rows ? "rows" : "ring", first_index_used(h, cp) ? "first" : "main",
+               cp.mirror ? 0 : a.match_g, cp.mirror ? 0 : match_lanes(h, a, true), normals_from_matcher(a) ? 1 : 0, a.nb_fused,
+               (!h->shard.active && a.nb_fused == 0 && sel_partial(a)) ? 1 : 0, a.spec ? 1 : 0, a.has_n ? 1 : 0,
+               h->profiling ? "profiled" : issued[h->issue_mode], looks.c_str());
+}
+#endif
+
+// The only look at the chain's post: waits, and issues the next segment while the chain is not done and iterations are left; then
+// composes the pose.
 int compute_finish(o3s_icp* h, float* T_out, o3s_icp_stats* stats) {
   if (stats) std::memset(stats, 0, sizeof(*stats));
-  if (!h->pend_valid) return fail(h, O3S_ERR_BAD_ARGUMENT, "compute_finish without a successful compute_launch");
-  h->pend_valid = false;
+  Call& c = h->call;
+  if (!c.live) return fail(h, O3S_ERR_BAD_ARGUMENT, "compute_finish without a successful compute_launch");
+  c.live = false;
+#ifdef O3S_TEST_HOOKS
+  struct PrintAtExit {  // once per call, failed chains included
+    o3s_icp* h;
+    ~PrintAtExit() { print_chain(h); }
+  } print_at_exit{h};
+#endif
   HIP_TRY(h, hipSetDevice(h->device));  // compute_batch finishes handles in turn: the current device is the last launch's
+  const ChainParams& cp = c.a.cp;
   bool done = false;
   for (;;) {
-    // the chain is certain to end inside what was issued when a Counter checker is there and all of max_iters went out
-    const bool certain = h->pend_cp.max_iters > 0 && h->pend_issued >= h->pend_cp.max_iters && h->pend_graph_left <= 0;
-    if (!certain && h->pend_graph_left <= 0) HIP_TRY(h, hipEventRecord(h->ev_end, h->stream));
-    const int w = wait_post(h, h->call_seq, certain ? (hipEvent_t) nullptr : h->ev_end, &done);
+    const int w = wait_post(h, h->call_seq, c.ends_inside() ? (hipEvent_t) nullptr : h->ev_end, &done);  // (issue_segment recorded ev_end)
     if (w < 0) return fail(h, O3S_ERR_HIP, "compute: a kernel of the iteration chain failed");
     if (w == 0) return fail(h, O3S_ERR_HIP, "compute: the iteration chain ended without posting its state");
-    if (done) break;
-    if (h->pend_graph_left > 0) {
-      HIP_TRY(h, hipGraphLaunch(h->graph_exec, h->stream));  // chunked graph replay: not converged yet
-      h->pend_graph_left -= h->pend_graph_chunk;
-      h->pend_issued += h->pend_graph_chunk;
-      if (h->pend_graph_left > 0) HIP_TRY(h, hipEventRecord(h->ev_end, h->stream));
-      continue;
-    }
-    if (h->pend_eager && h->pend_issued < h->pend_iters_cap) {  // a deferred eager chain that is not done yet: two more iterations, look again
-      const ChainArgs a = chain_args(h, h->pend_cp);
-      const int upto = std::min(h->pend_issued + h->pend_look_step, h->pend_iters_cap);
-      for (int it = h->pend_issued; it < upto; ++it) launch_iteration(h, a, h->cfg.match_stats != 0, nullptr, it);
-      HIP_TRY(h, hipGetLastError());
-      h->pend_issued = upto;
-      continue;
-    }
-    break;
+    if (done || c.issued >= c.iters_cap) break;
+    const double t0 = now_us();
+    const int rc = issue_segment(h, c);
+    h->host_issue_us += now_us() - t0;
+    if (rc != O3S_OK) return rc;
   }
-  h->pend_graph_left = 0;
-  h->pend_eager = false;
-  const ChainParams& cp = h->pend_cp;
-  const float* Tc = h->pend_Tc;
-  const float* T0 = h->pend_T0;
-  if (!done) {  // every issued iteration ran and the chain is not done (no Counter checker and the cap reached): fetch the state the slow way
+  // every issued iteration ran and the chain is not done (no Counter checker and the cap reached): fetch the state the slow way;
+  // a profiled call waits for the stream anyway (its events have to be complete before they are read)
+  if (!done || c.issue == Call::kProfiled) {
     const int rc = pull_state(h);
     if (rc != O3S_OK) return rc;
-  } else {
-    std::memcpy(&h->stage->state, &h->post->state, sizeof(IcpState));  // posted in front of the progress word (system-scope release)
   }
+  if (c.issue == Call::kProfiled) {
+    const int ran = std::min(c.issued, h->stage->state.iter + (h->stage->state.status ? 1 : 0));
+    for (int it = 0; it < ran; ++it)
+      for (int k = 0; k < kNumKernels; ++k) {
+        if (k == 3 && c.a.nb_fused > 0) continue;  // fused chain: k_sel_ne (timed as k = 2) holds the selection and the normal equations
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, h->prof_events[(size_t)it * 6 + k], h->prof_events[(size_t)it * 6 + k + 1]) == hipSuccess) {
+          h->kernel_ms[k] += ms;
+          h->kernel_launches[k] += 1;
+        }
+      }
+  }
+  if (done) std::memcpy(&h->stage->state, &h->post->state, sizeof(IcpState));  // posted in front of the progress word (system-scope release)
   const IcpState& st = h->stage->state;
   h->last_iters = std::min(st.iter, h->trace_cap);  // the trace stays on the device until o3s_icp_get_trace asks for it
   h->eager_hint = st.iter;
@@ -1228,22 +1208,16 @@ int compute_finish(o3s_icp* h, float* T_out, o3s_icp_stats* stats) {
   if (!st.done && cp.max_iters <= 0) return fail(h, O3S_ERR_BAD_CONFIG, "iteration cap reached without a Counter checker");
   // icpCorrected_T_refIn_readIn = T_refIn_refMean * (T_iter * T_refMean_readMean)   (LPM/ICP.cpp:462-465)
   float tmp[16], out[16];
-  hmul4(st.T_iter, T0, tmp);
-  hmul4(Tc, tmp, out);
+  hmul4(st.T_iter, c.T0, tmp);
+  hmul4(c.Tc, tmp, out);
   std::memcpy(T_out, out, sizeof(out));
   return O3S_OK;
 }
 
 int compute_impl(o3s_icp* h, const float* T_init, float* T_out, o3s_icp_stats* stats) {
   if (stats) std::memset(stats, 0, sizeof(*stats));
-  h->host_wait_us = 0.0;
-  h->host_queries = 0;
-  h->wait_by_post = h->wait_by_event = h->wait_by_guard = h->issue_mode = 0;
-  const double t0 = now_us();
   const int rc = compute_launch(h, T_init);
-  h->host_issue_us = now_us() - t0 - h->host_wait_us;
-  if (rc != O3S_OK) return rc;
-  return compute_finish(h, T_out, stats);
+  return rc != O3S_OK ? rc : compute_finish(h, T_out, stats);
 }
 
 int upload_reading(o3s_icp* h, const float* xyzw, const float* normals, int64_t N) {
@@ -1592,15 +1566,7 @@ int o3s_icp_compute_resident(o3s_icp* h, const float T_init[16], float T_out[16]
 
 int o3s_icp_compute_resident_launch(o3s_icp* h, const float T_init[16]) {
   if (!h || !T_init) return O3S_ERR_BAD_ARGUMENT;
-  h->host_wait_us = 0.0;
-  h->host_queries = 0;
-  h->wait_by_post = h->wait_by_event = h->wait_by_guard = h->issue_mode = 0;
-  const double t0 = now_us();
-  h->defer_looks = true;
-  const int rc = compute_launch(h, T_init);
-  h->defer_looks = false;
-  h->host_issue_us = now_us() - t0 - h->host_wait_us;
-  return rc;
+  return compute_launch(h, T_init);
 }
 
 int o3s_icp_compute_resident_finish(o3s_icp* h, float T_out[16], o3s_icp_stats* stats) {
@@ -1620,7 +1586,7 @@ int o3s_icp_compute(o3s_icp* h, const float* xyzw, const float* normals, int64_t
 
 int o3s_icp_compute_batch(o3s_icp* const* handles, int32_t n, const float* T_inits, float* T_outs, o3s_icp_stats* stats, int32_t* statuses) {
   if (!handles || n < 0 || !T_inits || !T_outs || !statuses) return O3S_ERR_BAD_ARGUMENT;
-  for (int32_t k = 0; k < n; ++k)  // a handle holds ONE call in flight (pend_*, the pinned stage): the same handle twice is a caller error
+  for (int32_t k = 0; k < n; ++k)  // a handle holds ONE call in flight (its Call, the pinned stage): the same handle twice is a caller error
     for (int32_t j = 0; j < k; ++j)
       if (handles[k] && handles[k] == handles[j]) return O3S_ERR_BAD_ARGUMENT;
   for (int32_t k = 0; k < n; ++k) {  // issue every chain first (one stream per handle: the chains overlap on the GPU) ...

@@ -375,3 +375,92 @@ def test_graph_key_covers_the_first_iteration_grid(monkeypatch, hooks_lib, capfd
     for a, b in zip(again, fresh):
         assert_bit_identical(a, b, "re-initialised vs fresh")
     assert all(np.array_equal(T, fresh[0]["T"]) for T in before)   # exact search on either grid: the edge moves no bit
+
+
+# ---- 3f: where the host looks at the chain's post ---------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def schedule_pair():
+    """A small icp.yaml pair: 5 iterations from its initial guess, 7 from one 0.3 m further off, 3 from the truth."""
+    sp = syn.make_scan_pair(4000, 12000, 0.1, seed=3)
+    far = sp.T_init.copy()
+    far[:3, 3] += 0.3
+    return sp, {"init": sp.T_init, "far": far, "gt": sp.T_gt}
+
+
+def expected_looks(kw, n, prev, issued):
+    """The iterations issued at each look at the post of a call that ran n iterations on a handle whose previous call ran prev (4 on
+    a fresh handle): a replayed graph goes out `chunk` iterations at a time until max_iters or more are out (5 for a chain that can
+    stop by itself and has more than 7, else max_iters); an eager chain first as far as the previous call needed, clamped to
+    [2, 8], then 2 at a time; a profiled one whole, or 16 at a time without a Counter checker."""
+    mi = kw.get("max_iters", 15) or 0
+    cap = mi if mi > 0 else 4096
+    clamp = True
+    if issued == "profiled":
+        first = step = cap if mi > 0 else 16
+    elif issued in ("captured", "replayed"):
+        first = step = 5 if kw.get("use_differential", True) and mi > 7 else mi
+        clamp = False   # whole replays: the iterations past max_iters are no-ops
+    else:
+        first, step = min(max(prev, 2), 8), 2
+    k = min(first, cap)
+    looks = [k]
+    while k < n and k < cap:
+        k = min(k + step, cap) if clamp else k + step
+        looks.append(k)
+    return looks
+
+
+SCHEDULE_CASES = {   # config, the calls on one handle (initial guesses), how they are issued
+    "eager": (dict(use_graph=False), ["init", "far", "gt", "far"], "resident"),
+    "eager-split": (dict(use_graph=False), ["init", "far", "gt", "far"], "split"),
+    "chunked-graph": (dict(), ["far", "far", "far", "init"], "resident"),
+    "chunked-graph-split": (dict(), ["far", "far", "far", "init"], "split"),
+    "fixed-graph": (dict(use_differential=False, max_iters=6), ["init", "init", "far"], "resident"),
+    "profiled": (dict(), ["far", "init"], "profiled"),
+    "profiled-no-counter": (dict(max_iters=0), ["far", "init"], "profiled"),
+    "no-counter": (dict(max_iters=0), ["init", "far", "gt", "far"], "resident"),
+}
+
+
+@pytest.mark.parametrize("case", list(SCHEDULE_CASES))
+def test_host_looks_at_the_post_where_the_schedule_says(case, monkeypatch, hooks_lib, capfd):
+    """The O3S_PRINT_CHAIN report of every call lists the iterations issued at each look at the chain's post: they follow the
+    schedule of csrc/o3s_icp.hip for eager calls on a fresh and on a warm handle (compute_resident and the two halves), captured
+    and replayed chunked chains (one that needs a second chunk), a fixed-length graph, profiled calls and chains without a
+    Counter checker."""
+    kw, calls, how = SCHEDULE_CASES[case]
+    sp, guesses = schedule_pair()
+    monkeypatch.setenv("O3S_PRINT_CHAIN", "1")
+    capfd.readouterr()
+    g = ICP(IcpConfig(**kw))
+    assert g.init_reference(sp.map_xyz, sp.map_normals)
+    g.set_reading(sp.scan_xyz, sp.scan_normals)
+    g.set_profiling(how == "profiled")
+    iters = []
+    for name in calls:
+        if how == "split":
+            g.compute_resident_launch(guesses[name])
+            g.compute_resident_finish()
+        else:
+            g.compute_resident(guesses[name])
+        iters.append(g.stats.iterations)
+    g.close()
+    reps = parse_chain(capfd.readouterr().err)
+    assert len(reps) == len(calls), reps
+    issued = [r["issued"] for r in reps]
+    if how == "profiled":
+        assert issued == ["profiled"] * len(calls), issued
+    elif kw.get("use_graph", True) and kw.get("max_iters", 15):
+        assert issued == ["eager", "captured", "replayed", "replayed"][:len(calls)], issued
+    else:
+        assert issued == ["eager"] * len(calls), issued
+    looks = []
+    for k, rep in enumerate(reps):
+        prev = iters[k - 1] if k else 4
+        want = expected_looks(kw, iters[k], prev, rep["issued"])
+        looks.append(rep["looks"])
+        assert rep["looks"] == ",".join(map(str, want)), (case, k, iters, rep)
+    if case.startswith("chunked-graph"):
+        assert iters[1] > 5 and looks[1] == looks[2] == "5,10", (iters, looks)   # a second chunk replays
+    if case.startswith("eager"):
+        assert len(looks[1].split(",")) > 1, looks   # the warm call looks more than once

@@ -530,7 +530,9 @@ def test_ragged_sizes():
 
 def test_compute_batch_matches_sequential():
     """BASELINE configs[2] (scaled down): independent scan/submap pairs issued together must give exactly what each pair
-    gives on its own, including a failing pair (status reported per pair, Mapper.cpp:420-422 keeps the prior)."""
+    gives on its own, including a failing pair (status reported per pair, Mapper.cpp:420-422 keeps the prior).  Three batches on
+    the same handles: every one gives the solo results, and each handle's host split describes that batch's call alone — the
+    converging pairs' chains go out eager, captured, replayed."""
     from open3d_slam_advanced_rss_2024_public_amd import compute_batch, parallel
 
     pairs = [syn.make_scan_pair(4000, 30000, 0.1, seed=20 + k) for k in range(6)]
@@ -547,14 +549,20 @@ def test_compute_batch_matches_sequential():
             solo.append((one.compute(scan, p.scan_normals, p.T_init), 0, one.stats.iterations))
         except ConvergenceError:
             solo.append((None, 5, one.stats.iterations))
-    poses, codes, stats = compute_batch(icps, [p.T_init for p in pairs])
-    for k in range(6):
-        assert codes[k] == solo[k][1]
-        if codes[k] == 0:
-            assert np.array_equal(poses[k], solo[k][0])
-            assert stats[k].iterations == solo[k][2]
-        else:
-            assert poses[k] is None
+    for issued in ("eager", "captured", "replayed"):
+        poses, codes, stats = compute_batch(icps, [p.T_init for p in pairs])
+        for k in range(6):
+            assert codes[k] == solo[k][1]
+            if codes[k] == 0:
+                assert np.array_equal(poses[k], solo[k][0])
+                assert stats[k].iterations == solo[k][2]
+                split = icps[k].host_split_ex()
+                assert split["issued"] == issued, (k, issued, split)
+                # one wait per look at the post: these chains (4 or 5 iterations) are looked at once, an eager one of 5 twice
+                waits = split["waits_ended_by_post"] + split["waits_ended_by_event"] + split["waits_ended_by_stream_guard"]
+                assert 1 <= waits <= 2, (k, issued, split)
+            else:
+                assert poses[k] is None
     # the sharding front-end in single-process mode uses the same runner
     dicts = [dict(map_xyz=p.map_xyz, map_normals=p.map_normals, scan_xyz=p.scan_xyz, scan_normals=p.scan_normals, T_init=p.T_init)
              for p in pairs[:3]]

@@ -166,7 +166,9 @@ def test_sharded_eager_schedule_depends_on_the_input_only():
     ISSUES may not depend on its handle's history (the un-sharded eager chain looks at `done` where the last call on the handle
     stopped) nor on whether its graph capture worked.  Two world-1 handles with different histories — one fresh, one that has
     just run a 15-iteration chain and a 3-iteration one — get the same new pair with a Differential checker and the capturable
-    exchange: both must issue the same number of collectives, the number the chunked graph replay issues too."""
+    exchange: both must issue the same number of collectives, the number the chunked graph replay issues too.  A handle whose
+    exchange is not capturable issues every call eagerly, and per call exactly what a capturable handle issues in its eager call:
+    with the default chain, and with max_iters 7, whose graph is one chunk of 7 (the pair converges in fewer than 5)."""
     import ctypes as C
 
     from open3d_slam_advanced_rss_2024_public_amd import _lib
@@ -201,10 +203,30 @@ def test_sharded_eager_schedule_depends_on_the_input_only():
             iters.append(h.stats.iterations)
         counts.append(per_call)
     assert len(set(iters)) == 1 and 3 <= iters[0] < 15
+    assert iters[0] < 5   # max_iters 7 below: a look after 5 iterations would find the chain done and issue fewer than 7
     assert all(np.array_equal(poses[0], T) for T in poses[1:])
     assert counts[0][0] == counts[1][0] > 0, counts        # the eager calls issued the same collectives whatever the history
     assert counts[0][1] == counts[1][1] and counts[0][2] == counts[1][2] == 0, counts   # capture once, then replay from the graph
     for h in (fresh, used):
         h.close()
+    for cfg in (IcpConfig(), IcpConfig(max_iters=7)):
+        per_handle, cfg_poses = [], []
+        for comm, capture in ((comms[0], True), (comms[1], False)):
+            h = ICP(cfg)
+            assert h.init_reference(sp.map_xyz, sp.map_normals)
+            h.set_reading(sp.scan_xyz, sp.scan_normals)
+            h.shard_configure_rccl(sp.scan_xyz.shape[0], 0, 1, comm.value, capture=capture)
+            per_call = []
+            for _ in range(3):
+                before = R.o3s_rccl_collectives(comm)
+                cfg_poses.append(h.compute_resident(sp.T_init))
+                per_call.append(R.o3s_rccl_collectives(comm) - before)
+                assert h.stats.iterations == iters[0]
+            h.close()
+            per_handle.append(per_call)
+        assert all(np.array_equal(cfg_poses[0], T) for T in cfg_poses[1:])
+        capturable, not_capturable = per_handle
+        assert capturable[0] > 0 and capturable[2] == 0, (cfg.max_iters, per_handle)
+        assert not_capturable == [capturable[0]] * 3, (cfg.max_iters, per_handle)   # every call eager, on the same schedule
     for comm in comms:
         R.o3s_rccl_destroy(comm)
