@@ -11,6 +11,8 @@
  *   o3s_o3d_to_pm              open3dToPointmatcher                    CONV/src/open3d_conversions.cpp:57-118
  *   o3s_estimate_normals       EstimateNormals(Hybrid(radius, max_nn)) + NormalizeNormals + OrientNormalsTowardsCameraLocation
  *                              (Open3D v0.15.1)                        O3S/src/CloudRegistration.cpp:71-74, O3S/src/Submap.cpp:269-271
+ *   o3s_compute_fpfh           registration::ComputeFPFHFeature (Open3D v0.15.1)   O3S/src/Submap.cpp:272
+ *   o3s_feature_correspondences   head of RegistrationRANSACBasedOnFeatureMatching   O3S/src/PlaceRecognition.cpp:81-84
  *
  * Conventions: stateless; `device` is the HIP device ordinal; points / normals are 3 x N column-major doubles (the
  * memory of std::vector<Eigen::Vector3d>); the caller owns all buffers, which are HOST pointers (the library stages
@@ -95,6 +97,52 @@ int o3s_o3d_to_pm(int device, const double* pts, const double* normals, int64_t 
  * neighbour lists are bit-exact). */
 int o3s_estimate_normals(int device, const double* pts, int64_t N, double radius, int32_t max_nn, double* out_normals,
                          int32_t* out_nn_idx);
+
+/* ---- place-recognition front end on host buffers: FPFH features and feature correspondences -------------------------
+ *   o3s_compute_fpfh              registration::ComputeFPFHFeature(cloud, Hybrid(radius, max_nn))   (Open3D v0.15.1), the last
+ *                                 step of Submap::computeFeatures                    O3S/src/Submap.cpp:268-272
+ *   o3s_feature_correspondences   the head of RegistrationRANSACBasedOnFeatureMatching(source, target, source feature, target
+ *                                 feature, mutual_filter, ..., ransac_n, ...)         O3S/src/PlaceRecognition.cpp:81-84
+ * The RANSAC loop over the correspondence set (RegistrationRANSACBasedOnCorrespondence) is not here: the set returned is what
+ * a host implementation of it takes.  The same on resident submaps: o3s_submap.h (o3s_submap_compute_features).
+ *
+ * Open3D is not part of the reference tree; parity is against a restatement of its published source (tests/fpfh_ref.py),
+ * written from the contract below.  All arithmetic is IEEE fp64 without FMA contraction; dot(a, b) = (ax bx + ay by) + az bz,
+ * cross(a, b) = (ay bz - az by, az bx - ax bz, ax by - ay bx).
+ *
+ * Neighbour list of point i — KDTreeFlann::SearchHybrid(p_i, radius, max_nn): the max_nn nearest points of the same
+ *   cloud, the query included, squared distance d2 = ((dx dx + dy dy) + dz dz) < radius^2, ascending (d2, index).
+ *   1 <= max_nn <= 128.  The lists are exact.
+ * Pair feature of (p1, n1), (p2, n2) -> (f0, f1, f2, f3):
+ *   dp = p2 - p1; f3 = sqrt(dot(dp, dp)); f3 == 0 -> all zero.  a1 = dot(n1, dp) / f3, a2 = dot(n2, dp) / f3.
+ *   acos(|a1|) > acos(|a2|): n1' = n2, n2' = n1, dp = -dp, f2 = -a2; else n1' = n1, n2' = n2, f2 = a1.
+ *   v = cross(dp, n1'); |v| == 0 -> all zero; v /= |v|; w = cross(n1', v); f1 = dot(v, n2');
+ *   f0 = atan2(dot(w, n2'), dot(n1', n2')).
+ * SPFH (33 x N, zero-initialised): point i with list L, |L| > 1: inc = 100.0 / (|L| - 1); for k = 1 .. |L| - 1 (entry
+ *   0 is skipped whatever it is) f = pair(p_i, n_i, p_L[k], n_L[k]); h0 = floor(11 (f0 + pi) / (2 pi)),
+ *   h1 = floor(11 (f1 + 1) 0.5), h2 = floor(11 (f2 + 1) 0.5), each clamped to 0 .. 10 (a NaN goes to 0); rows h0,
+ *   11 + h1, 22 + h2 grow by inc — by repeated addition, so a bin's value depends on its count alone.
+ * FPFH (33 x N): point i with |L| > 1: for k = 1 .. |L| - 1 with d = d2_k != 0, for j = 0 .. 32:
+ *   val = spfh[j][L[k]] / d; sum[j / 11] += val; out[j][i] += val.  Then sum[t] = 100.0 / sum[t] where sum[t] != 0, and
+ *   out[j][i] = out[j][i] * sum[j / 11] + spfh[j][i] (two rounded operations).  Points with |L| <= 1 keep zeros.
+ *   Given the same lists and SPFH the result is bit-exact.  Against another math library only acos (the swap decision)
+ *   and atan2 / the bin edges can differ: tests/fpfh_ref.py lists the points where they could.
+ * Feature correspondences: ij[i] = the target column nearest to source column i, squared L2 as the running sum
+ *   d = d + (a_j - b_j)^2 over j = 0 .. dim - 1, ties to the lower index.  mutual_filter: ji[j] likewise; the pairs
+ *   (i, ij[i]) with ji[ij[i]] == i in ascending i; if fewer than 3 ransac_n survive, all (i, ij[i]) instead
+ *   (*used_fallback = 1).  Without mutual_filter: all (i, ij[i]).
+ * Features are dim x N column-major doubles (feature column i = 33 consecutive doubles). */
+
+/* out_fpfh: 33 x N.  out_spfh (nullable): 33 x N.  out_nn_idx (nullable): N x max_nn int32, ascending (d2, index), -1
+ * padded.  max_nn outside 1 .. 128 or radius <= 0: O3S_ERR_BAD_ARGUMENT.  N = 0 is fine. */
+int o3s_compute_fpfh(int device, const double* pts, const double* normals, int64_t N, double radius, int32_t max_nn,
+                     double* out_fpfh, double* out_spfh, int32_t* out_nn_idx);
+
+/* out_pairs: 2 x n_src int32 (pair k = out_pairs[2 k], out_pairs[2 k + 1] = source column, target column); *n_out pairs
+ * are written.  used_fallback is nullable.  1 <= dim <= 264; n_src = 0 or n_tgt = 0 gives no pairs. */
+int o3s_feature_correspondences(int device, const double* src_feat, int64_t n_src, const double* tgt_feat, int64_t n_tgt,
+                                int32_t dim, int32_t mutual_filter, int32_t ransac_n, int32_t* out_pairs, int64_t* n_out,
+                                int32_t* used_fallback);
 
 #ifdef __cplusplus
 }

@@ -190,6 +190,36 @@ int o3s_o3d_registration_icp_submaps_overlap_batch_ex(int32_t n, const o3s_subma
                                                       int64_t min_points_per_voxel, o3s_o3d_icp_result* results,
                                                       double* infos, int64_t* n_overlaps, int32_t* statuses);
 
+/* ---- place-recognition front end on the resident map (contract of the feature arithmetic: o3s_cloud_ops.h, o3s_compute_fpfh).
+ * minSecondsBetweenFeatureComputation_ (O3S/src/Submap.cpp:256) is a host timer and belongs to the caller. */
+/* PlaceRecognitionParameters (param/default/parameter_structure_definitions.lua:163-167) */
+typedef struct o3s_submap_feature_params {
+  double feature_voxel_size; /* 0.5 */
+  double normal_radius;      /* 2.0 */
+  int32_t normal_knn;        /* 20  (1 .. 32, o3s_estimate_normals) */
+  double feature_radius;     /* 2.5 */
+  int32_t feature_knn;       /* 100 (1 .. 128) */
+} o3s_submap_feature_params;
+void o3s_submap_feature_params_default(o3s_submap_feature_params* p);
+
+/* Submap::computeFeatures on the resident map, all in HBM: the map cloud -> Open3D VoxelDownSample(feature_voxel_size)
+ * (o3s_voxel_downsample: ascending (z, y, x) voxel order) -> normals (o3s_estimate_normals: estimated, unit length,
+ * oriented to the origin) -> FPFH.  The sparse cloud, its normals and the features stay resident in the submap until
+ * the next call replaces them; a later insert does not touch them (they describe the map as it was).  Completes a
+ * pending insert first, like every call that takes the submap.  An empty map gives an empty feature set.
+ *   o3s_submap_clone      copies the feature set with the map.
+ *   o3s_submap_hand_over  leaves it with `from` (the closed submap keeps its map and its features; `to` starts without).
+ *   o3s_submap_trim       keeps it and gives the feature work areas (grid, lists, SPFH) back to the allocator.
+ *   o3s_submap_upload     drops it (the map it described is gone). */
+int o3s_submap_compute_features(o3s_submap* m, const o3s_submap_feature_params* params);
+/* number of sparse points of the resident feature set; -1 while the submap has none */
+int64_t o3s_submap_features_size(const o3s_submap* m);
+/* sparse_pts, sparse_normals: 3 x n, fpfh: 33 x n (each nullable); O3S_ERR_NOT_INITIALIZED without a feature set */
+int o3s_submap_download_features(const o3s_submap* m, double* sparse_pts, double* sparse_normals, double* fpfh);
+/* o3s_feature_correspondences between two resident feature sets on one device (out_pairs: 2 x features_size(source)) */
+int o3s_submap_feature_correspondences(const o3s_submap* source, const o3s_submap* target, int32_t mutual_filter,
+                                       int32_t ransac_n, int32_t* out_pairs, int64_t* n_out, int32_t* used_fallback);
+
 #ifdef __cplusplus
 }
 #endif

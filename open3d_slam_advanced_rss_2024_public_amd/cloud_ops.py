@@ -32,6 +32,7 @@ def _L():
         L.o3s_voxel_downsample.argtypes = [C.c_int, C.c_double, dp, dp, C.c_int64, dp, dp, ip, C.POINTER(C.c_int64)]
         L.o3s_o3d_to_pm.argtypes = [C.c_int, dp, dp, C.c_int64, fp, fp]
         L.o3s_estimate_normals.argtypes = [C.c_int, dp, C.c_int64, C.c_double, C.c_int32, dp, ip]
+        L.o3s_compute_fpfh.argtypes = [C.c_int, dp, dp, C.c_int64, C.c_double, C.c_int32, dp, dp, ip]
     return L
 
 
@@ -124,6 +125,22 @@ def estimateNormals(points, max_radius: float, knn: int, want_neighbours: bool =
     nn = np.zeros((p.shape[0], knn), np.int32) if want_neighbours else None
     _check(_L().o3s_estimate_normals(device, _d(p), p.shape[0], float(max_radius), int(knn), _d(out), _i(nn)), "o3s_estimate_normals")
     return (out, nn) if want_neighbours else out
+
+
+def computeFPFHFeature(points, normals, radius: float, knn: int, want_spfh: bool = False, want_neighbours: bool = False, device: int = 0):
+    """registration::ComputeFPFHFeature(cloud, KDTreeSearchParamHybrid(radius, knn)) (Submap.cpp:272): the N x 33 features (row i =
+    Open3D's feature column i); with want_spfh / want_neighbours also the SPFH and the N x knn neighbour lists (-1 padded)."""
+    p = np.ascontiguousarray(points, np.float64)
+    n = np.ascontiguousarray(normals, np.float64)
+    if n.shape != p.shape:
+        raise ValueError("points and normals differ in shape")
+    N = p.shape[0]
+    out = np.zeros((N, 33), np.float64)
+    spfh = np.zeros((N, 33), np.float64) if want_spfh else None
+    nn = np.zeros((N, max(int(knn), 0)), np.int32) if want_neighbours else None
+    _check(_L().o3s_compute_fpfh(device, _d(p), _d(n), N, float(radius), int(knn), _d(out), _d(spfh), _i(nn)), "o3s_compute_fpfh")
+    res = (out,) + ((spfh,) if want_spfh else ()) + ((nn,) if want_neighbours else ())
+    return res if len(res) > 1 else out
 
 
 # ---- the same operators with colours / covariances riding along (include/o3s_cloud_ops.h, *_attr entry points) ----------

@@ -13,7 +13,9 @@
 //   :193-247   insertScan: buffer the scan; on a switch the scan
 //              still goes into the PREVIOUS submap, whose centre is then computed (Submap::computeSubmapCenter, Submap.cpp:
 //              282-286), it is queued as finished, an adjacency edge is added, the buffer is replayed into the new one
-// Not here: feature computation / place recognition / pose-graph transforms of finished submaps (host work, out of scope).
+//   computeFeatures(idx): Submap::computeFeatures (Submap.cpp:255-275) of a submap on the device (o3s_submap_compute_features);
+//              the caller keeps the reference's timer (minSecondsBetweenFeatureComputation_) and decides when to call it.
+// Not here: the RANSAC of place recognition / pose-graph transforms of finished submaps (host work, out of scope).
 // The scans the buffer keeps are resident o3s_scan objects: the caller hands over the scan it has just pre-processed and
 // gets another one to fill next (a ring of numScansOverlap_ + 1 handles, nothing is copied).
 #pragma once
@@ -114,6 +116,14 @@ class SubmapCollectionHip {
   std::size_t numSubmaps() const { return submaps_.size(); }
   std::size_t activeSubmapIdx() const { return activeIdx_; }
   SubmapHip& activeSubmap() { return *submaps_[activeIdx_].map; }
+  // Submap::computeFeatures of submap `idx` (sparse cloud, normals, FPFH stay resident in it); returns the number of sparse points
+  std::int64_t computeFeatures(std::size_t idx, const o3s_submap_feature_params* params = nullptr) {
+    o3s_submap_feature_params p;
+    o3s_submap_feature_params_default(&p);
+    if (params) p = *params;
+    if (o3s_submap_compute_features(submaps_.at(idx).map->handle(), &p) != O3S_OK) throw std::runtime_error("o3s_submap_compute_features failed");
+    return o3s_submap_features_size(submaps_.at(idx).map->handle());
+  }
   const Entry& submap(std::size_t i) const { return submaps_.at(i); }
   SubmapHip& submapMap(std::size_t i) { return *submaps_.at(i).map; }
   const AdjacencyHip& adjacency() const { return adjacency_; }

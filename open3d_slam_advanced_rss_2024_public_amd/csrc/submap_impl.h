@@ -6,6 +6,7 @@
 
 #include "cloud_dev.h"
 #include "normals_dev.h"
+#include "fpfh_dev.h"
 
 namespace {
 
@@ -256,6 +257,11 @@ struct o3s_submap {
   } pend;
   DArr d_post;                      // 4 words the pending insert's counts also go to (lazy_post_fetch's fallback)
   hipEvent_t scan_read = nullptr;   // recorded when an insert has read its device scan: the scan's stream waits for it before the object is rewritten
+  // the feature set of o3s_submap_compute_features: sparse cloud, its normals, FPFH (33 x n_feat); -1: none.  It describes the map
+  // as it was when it was computed; inserts leave it alone
+  DArr feat_p, feat_n, feat_f;
+  int64_t n_feat = -1;
+  FpfhWork feat_w;  // grid, neighbour lists and SPFH of the last computation (given back by o3s_submap_trim)
 };
 
 namespace {
@@ -390,6 +396,18 @@ int o3s_submap_clone(const o3s_submap* src, int device, o3s_submap** out) {
   m->has_colors = src->has_colors;
   m->n_pt = src->n_pt;
   m->layout_valid = src->layout_valid;
+  if (src->n_feat > 0) {  // the feature set travels with the snapshot
+    const size_t nf = (size_t)src->n_feat;
+    auto copy_n = [&](DArr& dst, const DArr& from, size_t b) -> bool {
+      if (dst.ensure(b, 0, s) != hipSuccess) return false;
+      if (m->device == src->device) return hipMemcpyAsync(dst.p, from.p, b, hipMemcpyDeviceToDevice, s) == hipSuccess;
+      return hipMemcpyPeerAsync(dst.p, m->device, from.p, src->device, b, s) == hipSuccess;
+    };
+    if (!copy_n(m->feat_p, src->feat_p, nf * 24) || !copy_n(m->feat_n, src->feat_n, nf * 24) || !copy_n(m->feat_f, src->feat_f, nf * kFpfhDim * 8))
+      return fail(O3S_ERR_HIP);
+    if (hipStreamSynchronize(s) != hipSuccess) return fail(O3S_ERR_HIP);
+  }
+  m->n_feat = src->n_feat;
   return O3S_OK;
 }
 
@@ -444,6 +462,11 @@ int o3s_submap_trim(o3s_submap* m) {
   if (m->arena.base) (void)hipFree(m->arena.base);
   m->arena.base = nullptr;
   m->arena.cap = m->arena.used = 0;
+  // the feature set stays (a closed submap is what place recognition matches against); its work areas go
+  drop_normals_work(m->feat_w.grid);
+  drop_buf(m->feat_w.idx);
+  drop_buf(m->feat_w.d2);
+  drop_buf(m->feat_w.spfh);
   // shrink the map arrays themselves to what the map holds (a submap closed by radius at a fraction of the reserved size)
   const size_t need = (size_t)m->n * 24;
   auto shrink = [&](DArr& a, bool used) -> hipError_t {
@@ -538,6 +561,8 @@ int64_t o3s_submap_device_bytes(const o3s_submap* m) {
   size_t b = m->arena.cap;
   for (int k = 0; k < 2; ++k) b += m->pts[k].cap + m->nrm[k].cap + m->col[k].cap;
   b += m->scan_p.cap + m->scan_n.cap + m->scan_c.cap + m->carve_scan.cap + m->d_T.cap + m->patch_xyzw.cap + m->patch_n32.cap;
+  b += m->feat_p.cap + m->feat_n.cap + m->feat_f.cap + m->feat_w.grid.arena.cap + m->feat_w.grid.cells_cap + m->feat_w.idx.cap + m->feat_w.d2.cap +
+       m->feat_w.spfh.cap;
   return (int64_t)b;
 }
 
@@ -627,6 +652,7 @@ int o3s_submap_upload(o3s_submap* m, const double* pts, const double* normals, i
   m->layout_valid = false;
   m->has_normals = N == 0 ? -1 : (normals ? 1 : 0);
   m->has_colors = 0;  // an uploaded map comes without colours
+  m->n_feat = -1;     // and without the features of the map it replaces
   return O3S_OK;
 }
 

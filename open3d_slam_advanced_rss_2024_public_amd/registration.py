@@ -63,7 +63,26 @@ def _L():
         L.o3s_o3d_default_estimation.restype = None
         L.o3s_o3d_registration_icp_batch.argtypes = [C.c_int, C.c_int32, C.POINTER(_Pair), C.c_double, C.POINTER(_Criteria), C.POINTER(_Result), dp,
                                                      C.POINTER(C.c_int32)]
+        ip = C.POINTER(C.c_int32)
+        L.o3s_feature_correspondences.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, ip, C.POINTER(C.c_int64), ip]
     return L
+
+
+def featureCorrespondences(source_feature, target_feature, mutual_filter: bool = True, ransac_n: int = 3, device: int = 0):
+    """The head of RegistrationRANSACBasedOnFeatureMatching (PlaceRecognition.cpp:81-84): (pairs, used_fallback) with pairs a K x 2
+    int32 array of (source index, target index) — nearest target feature of every source feature, kept where the relation is mutual
+    (all of them when fewer than 3 ransac_n are, or without mutual_filter).  Features are N x dim arrays (row i = feature column i)."""
+    a = np.ascontiguousarray(source_feature, np.float64)
+    b = np.ascontiguousarray(target_feature, np.float64)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError("features must be N x dim arrays of one dim")
+    pairs = np.zeros((a.shape[0], 2), np.int32)
+    n_out, fb = C.c_int64(0), C.c_int32(0)
+    rc = _L().o3s_feature_correspondences(device, _d(a), a.shape[0], _d(b), b.shape[0], a.shape[1], int(bool(mutual_filter)), int(ransac_n),
+                                          pairs.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n_out), C.byref(fb))
+    if rc != _lib.OK:
+        raise RuntimeError(f"o3s_feature_correspondences failed with o3s_status {rc}")
+    return pairs[:n_out.value].copy(), bool(fb.value)
 
 
 def _pose(T):

@@ -42,6 +42,14 @@ def _L():
         L.o3s_scan_get.restype = C.c_int64
         L.o3s_scan_set_reading.argtypes = [vp, vp]
         L.o3s_scan_set_normal_estimation.argtypes = [vp, C.c_double, C.c_int32]
+        ip = C.POINTER(C.c_int32)
+        L.o3s_submap_feature_params_default.argtypes = [C.POINTER(FeatureParamsC)]
+        L.o3s_submap_feature_params_default.restype = None
+        L.o3s_submap_compute_features.argtypes = [vp, C.POINTER(FeatureParamsC)]
+        L.o3s_submap_features_size.argtypes = [vp]
+        L.o3s_submap_features_size.restype = C.c_int64
+        L.o3s_submap_download_features.argtypes = [vp, dp, dp, dp]
+        L.o3s_submap_feature_correspondences.argtypes = [vp, vp, C.c_int32, C.c_int32, ip, C.POINTER(C.c_int64), ip]
     return L
 
 
@@ -53,6 +61,16 @@ def _pose(T) -> np.ndarray:
 class CarvingParamsC(C.Structure):
     _fields_ = [("voxel_size", C.c_double), ("max_raytracing_length", C.c_double), ("truncation_distance", C.c_double),
                 ("min_dot_product_with_normal", C.c_double)]
+
+
+class FeatureParamsC(C.Structure):
+    """o3s_submap_feature_params: PlaceRecognitionParameters' feature part (parameter_structure_definitions.lua:163-167)."""
+    _fields_ = [("feature_voxel_size", C.c_double), ("normal_radius", C.c_double), ("normal_knn", C.c_int32), ("feature_radius", C.c_double),
+                ("feature_knn", C.c_int32)]
+
+
+def featureParams(feature_voxel_size=0.5, normal_radius=2.0, normal_knn=20, feature_radius=2.5, feature_knn=100) -> FeatureParamsC:
+    return FeatureParamsC(float(feature_voxel_size), float(normal_radius), int(normal_knn), float(feature_radius), int(feature_knn))
 
 
 class Submap:
@@ -187,6 +205,50 @@ class Submap:
         nrm = np.zeros((n, 3), np.float64) if self.has_normals else None
         self._check(self._lib.o3s_submap_download(self._h, _d(pts), _d(nrm)), "o3s_submap_download")
         return pts, nrm
+
+    def computeFeatures(self, params: FeatureParamsC = None) -> int:
+        """Submap::computeFeatures (Submap.cpp:255-275) on the resident map: voxel down-sample, normals, FPFH — all in HBM, kept in
+        the submap until the next call.  Returns the number of sparse points.  The caller keeps the reference's timer
+        (minSecondsBetweenFeatureComputation_)."""
+        prm = featureParams() if params is None else params
+        self._check(self._lib.o3s_submap_compute_features(self._h, C.byref(prm)), "o3s_submap_compute_features")
+        return int(self._lib.o3s_submap_features_size(self._h))
+
+    def features_size(self) -> int:
+        """Sparse points of the resident feature set; -1 while there is none."""
+        return int(self._lib.o3s_submap_features_size(self._h))
+
+    def _download_features(self, want_cloud: bool, want_fpfh: bool):
+        n = self.features_size()
+        if n < 0:
+            raise RuntimeError("the submap has no features: call computeFeatures first")
+        pts = np.zeros((n, 3), np.float64) if want_cloud else None
+        nrm = np.zeros((n, 3), np.float64) if want_cloud else None
+        f = np.zeros((n, 33), np.float64) if want_fpfh else None
+        self._check(self._lib.o3s_submap_download_features(self._h, _d(pts), _d(nrm), _d(f)), "o3s_submap_download_features")
+        return pts, nrm, f
+
+    def getSparseMapPointCloud(self):
+        """Submap::getSparseMapPointCloud: (points, normals) of the cloud the features were computed on."""
+        pts, nrm, _ = self._download_features(True, False)
+        return pts, nrm
+
+    def getFeatures(self) -> np.ndarray:
+        """Submap::getFeatures: the n x 33 FPFH features (row i = Open3D's feature column i)."""
+        return self._download_features(False, True)[2]
+
+    def featureCorrespondences(self, target: "Submap", mutual_filter: bool = True, ransac_n: int = 3):
+        """(pairs, used_fallback) between this submap's resident features (source) and `target`'s: registration.featureCorrespondences
+        without a copy of either feature set leaving HBM."""
+        n = self.features_size()
+        if n < 0 or target.features_size() < 0:
+            raise RuntimeError("both submaps need features: call computeFeatures first")
+        pairs = np.zeros((n, 2), np.int32)
+        n_out, fb = C.c_int64(0), C.c_int32(0)
+        self._check(self._lib.o3s_submap_feature_correspondences(self._h, target._h, int(bool(mutual_filter)), int(ransac_n),
+                                                                 pairs.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n_out), C.byref(fb)),
+                    "o3s_submap_feature_correspondences")
+        return pairs[:n_out.value].copy(), bool(fb.value)
 
     def setMapPointCloud(self, points, normals):
         p = np.ascontiguousarray(points, np.float64)

@@ -1,0 +1,82 @@
+"""GPU-box helper: the place-recognition front end on resident submaps — Submap.computeFeatures (voxel down-sample, normals,
+FPFH) and Submap.featureCorrespondences — at two map sizes: a sweep-size map (~60 k points) and a closure-size map (0.4 M points),
+both at 0.1 m with 1 cm noise, features with the reference's default parameters (0.5 m voxel, normals 2.0 m / 20, FPFH 2.5 m / 100).
+Wall time around the blocking calls, median of REPS calls after WARM warm-ups with the garbage collector off during the timed
+calls; beside it, as context only, the wall time of the numpy restatement (tests/fpfh_ref.py) on this job's CPUs.  Run under
+`rocprofv3 --kernel-trace --stats` for the per-kernel times (REF=0 skips the CPU restatement there).  Stages in the trace: voxelise =
+k_vox_* / k_min_bound and their sort, normals = k_normals, lists = k_fpfh_lists, SPFH = k_spfh, FPFH = k_fpfh, correspondences =
+k_feat_nn / k_feat_nn_fold; k_bounds / k_grid_keys / k_cell_ranges / k_gather_sorted build a grid index (one for the normals, one for
+the lists).  REPS=11 WARM=3 by default; OUT=<path> also writes the JSON line there."""
+import gc
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
+
+from open3d_slam_advanced_rss_2024_public_amd import Submap, cloud_ops as co, submap as sm, synthetic as syn  # noqa: E402
+
+REPS = int(os.environ.get("REPS", "11"))
+WARM = int(os.environ.get("WARM", "3"))
+REF = os.environ.get("REF", "1") != "0"
+
+def timed(fn):
+    ms = []
+    for rep in range(WARM + REPS):
+        gc.collect()
+        gc.disable()
+        t0 = time.perf_counter()
+        r = fn()
+        dt = (time.perf_counter() - t0) * 1e3
+        gc.enable()
+        if rep >= WARM:
+            ms.append(dt)
+    return r, float(np.median(ms)), [round(x, 4) for x in ms]
+
+
+def one_size(area, n_map):
+    world = syn.make_world(area, seed=21)
+    mp, _ = syn.make_map(world, n_map, 0.1, seed=22)
+    mp = mp.astype(np.float64) + np.random.default_rng(23).normal(0.0, 0.01, (n_map, 3))
+    big = co.croppingVolumeFactory("MaxRadius", 1.0e6)
+    a, b = Submap(0.1, big), Submap(0.1, big)
+    half = mp[:, 0] < np.median(mp[:, 0]) + 0.15 * (mp[:, 0].max() - mp[:, 0].min())     # b: 65 % of the map, overlapping a's
+    a.setMapPointCloud(mp, None)
+    b.setMapPointCloud(np.ascontiguousarray(mp[half]), None)
+    prm = sm.featureParams()
+    n, med, ms = timed(lambda: a.computeFeatures(prm))
+    m = b.computeFeatures(prm)
+    (pairs, fb), cmed, cms = timed(lambda: a.featureCorrespondences(b, True, 3))
+    out = {"map_points": int(n_map), "sparse_points": int(n), "target_sparse_points": int(m),
+           "compute_features_median_ms": med, "compute_features_ms": ms,
+           "feature_correspondences_median_ms": cmed, "feature_correspondences_ms": cms, "mutual_pairs": int(len(pairs)),
+           "used_fallback": bool(fb),
+           # the search's operation count: a subtraction, a multiplication and an addition per row, both directions
+           "correspondence_flop": int(2 * n * m * 33 * 3)}
+    if REF:
+        import fpfh_ref as fr
+
+        sp, sn = a.getSparseMapPointCloud()
+        t0 = time.perf_counter()
+        r = fr.compute_fpfh(sp, sn, prm.feature_radius, prm.feature_knn)
+        out["numpy_restatement_fpfh_s"] = round(time.perf_counter() - t0, 3)
+        out["numpy_threads"] = fr.normals_ref.threads()
+        out["pairs"] = int(((r.nn >= 0).sum(axis=1) - 1).clip(0).sum())
+        fa, fb_ = a.getFeatures(), b.getFeatures()
+        t0 = time.perf_counter()
+        fr.feature_correspondences(fa, fb_, True, 3)
+        out["numpy_restatement_correspondences_s"] = round(time.perf_counter() - t0, 3)
+    return out
+
+
+res = {"tool": "features_bench", "reps": REPS, "warm": WARM,
+       "sweep_size": one_size(700.0, 60000), "closure_size": one_size(9000.0, 400000)}
+line = json.dumps(res)
+print(line)
+if os.environ.get("OUT"):
+    with open(os.environ["OUT"], "w") as f:
+        f.write(line + "\n")
