@@ -8,9 +8,9 @@
 #include "../../include/o3s_cloud_ops.h"
 #include "../../include/o3s_icp.h"
 #include "icp_types.h"  // O3S_HOOK_ENV
+#include "host_post.h"
 
 #include <string.h>
-#include <time.h>
 
 #include <cstring>
 
@@ -28,6 +28,7 @@
 
 namespace {  // internal linkage
 namespace o3s_cloud {
+using namespace o3s::host_post;
 
 
 constexpr int kB = 256;
@@ -528,33 +529,26 @@ __global__ void __launch_bounds__(kB) k_mask_cnt(o3s_cropper c, const double* __
   put_block_count(f, blk_cnt);
 }
 
-// the one read-back of a hinted pipeline: status and up to three counts (each the total of a flag / offset pair, or 0)
+// the one read-back of a hinted pipeline: status and up to three counts (each the total of a flag / offset pair, or 0), four words
+// from kPostVals.  kGuarded: the slot is a LazyPost's, read later (host_post.h, post)
+template <bool kGuarded>
 __global__ void k_post_counts(const uint32_t* __restrict__ status, const uint32_t* fa, const uint32_t* oa, int64_t na, const uint32_t* fb,
                               const uint32_t* ob, int64_t nb, const uint32_t* fc, const uint32_t* oc, int64_t nc, uint32_t* __restrict__ dev_out,
                               uint32_t* __restrict__ mailbox, uint32_t seq) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   const uint32_t w[4] = {status[0], fa ? oa[na - 1] + fa[na - 1] : 0u, fb ? ob[nb - 1] + fb[nb - 1] : 0u, fc ? oc[nc - 1] + fc[nc - 1] : 0u};
   for (int k = 0; k < 4; ++k) dev_out[k] = w[k];
-  if (mailbox) {
-    for (int k = 0; k < 4; ++k) __hip_atomic_store(mailbox + 2 + k, w[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(mailbox + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  if (mailbox) post<kGuarded>(mailbox, seq, kPostVals, w);
 }
 
 // small pinned landing area for the counts the host reads back between kernels (one per host thread): a device-to-host
 // copy into pageable memory is staged and costs a full round trip of its own (~20 us in the per-scan loop's trace)
 struct PinnedArea {
   uint32_t* p = nullptr;        // 4 KB landing area for small device-to-host copies
-  uint32_t* mb = nullptr;       // mailbox a kernel writes directly: [0] value, [1] sequence number (host-coherent memory)
-  uint32_t* mb_dev = nullptr;   // the same mailbox as the device addresses it
-  uint32_t seq = 0;
+  PostBlock<> mb;               // mailbox a kernel writes directly (host_post.h): 32 words, the last 8 the lazy slot (kLazySlot)
   PinnedArea() {
     if (hipHostMalloc(reinterpret_cast<void**>(&p), 4096, hipHostMallocPortable) != hipSuccess) p = nullptr;
-    if (hipHostMalloc(reinterpret_cast<void**>(&mb), 128, hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) mb = nullptr;  // 32 words
-    if (mb) {
-      mb[0] = mb[1] = 0;
-      if (hipHostGetDevicePointer(reinterpret_cast<void**>(&mb_dev), mb, 0) != hipSuccess) mb_dev = nullptr;
-    }
+    (void)mb.alloc(128);
   }
   // no destructor on purpose: areas live in a process-wide pool that is never torn down.  A hipHostFree from a
   // thread_local / static destructor can run after the HIP runtime has been unloaded (exit-time crashes), and the worker
@@ -592,43 +586,13 @@ inline PinnedArea& pinned_area() {
   return *lease.a;
 }
 inline uint32_t* pinned_words() { return pinned_area().p; }
-inline bool mailbox_enabled(const PinnedArea& pa) {
-  static const bool on = O3S_HOOK_ENV("O3S_NO_MAILBOX") == nullptr;
-  return on && pa.mb && pa.mb_dev;
-}
-inline uint32_t mailbox_next(PinnedArea& pa) {
-  if (++pa.seq == 0) ++pa.seq;  // never 0
-  return pa.seq;
-}
-// polls the mailbox until a kernel has posted `seq`; 1 = posted, 0 = the stream drained without the write becoming
-// visible (the caller reads the value the slow way), < 0 = error.  A fault upstream must not leave the host spinning:
-// the stream is queried every few thousand polls.
-inline double poll_now_us() {
-  timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return (double)ts.tv_sec * 1e6 + (double)ts.tv_nsec * 1e-3;
-}
-// hipStreamQuery is a call into the runtime (its locks, possibly a marker packet in the queue): it is only the guard against a fault
-// upstream, looked at every 200 us of waiting, never part of the polling itself.  (Round 5: polled every ~10 us, the receiving thread's
-// waits slowed the MAPPING thread's launches down whenever the two overlapped — the reference re-init took 0.34 ms instead of 0.11
-// with page-locked sweeps, where the receiving thread reaches its wait early.)
-constexpr double kPollGuardUs = 200.0;
-inline int mailbox_wait(PinnedArea& pa, uint32_t seq, hipStream_t s) {
-  double t_guard = poll_now_us();
-  for (;;) {
-    for (int spin = 0; spin < 4096; ++spin)
-      if (__atomic_load_n(pa.mb + 1, __ATOMIC_ACQUIRE) == seq) return 1;
-    const double t = poll_now_us();
-    if (t - t_guard < kPollGuardUs) continue;
-    t_guard = t;
-    const hipError_t q = hipStreamQuery(s);
-    if (q == hipSuccess) return __atomic_load_n(pa.mb + 1, __ATOMIC_ACQUIRE) == seq ? 1 : 0;
-    if (q != hipErrorNotReady) return -1;
-  }
-}
+inline bool mailbox_enabled(const PinnedArea& pa) { return posts_enabled() && pa.mb; }
+// the sequence number of the post a call is about to issue; 0 (no post: fetch_post copies) with the mailbox off
+inline uint32_t mailbox_open(PinnedArea& pa) { return mailbox_enabled(pa) ? pa.mb.next() : 0u; }
 // A post that is looked at LATER (o3s_submap_insert_processed: the counts of a merge insert, fetched by the next call that needs the
-// map).  It lands in the second half of the issuing thread's mailbox (words 16..31: sequence number at 17, values from 18), which no
-// other hand-over uses, and in `dev_out` (device memory the owner keeps) for a reader that finds the slot taken by a later post.
+// map).  It lands in the last quarter of the issuing thread's mailbox (kLazySlot: a slot of the common layout, written guarded), which
+// no other hand-over uses, and in `dev_out` (device memory the owner keeps) for a reader that finds the slot taken by a later post.
+constexpr int kLazySlot = 24;  // (the eager posts reach word 17: k_ov_post)
 struct LazyPost {
   uint32_t* mb_host = nullptr;  // the slot as the host reads it (pinned areas are never freed: any thread may poll it)
   uint32_t* mb_dev = nullptr;
@@ -651,15 +615,11 @@ inline LazySlotGuard& lazy_slot_guard() {
 inline bool lazy_post_open(PinnedArea& pa, uint32_t* dev_out, hipStream_t s, LazyPost* lp) {
   if (!mailbox_enabled(pa) || !dev_out) return false;
   LazySlotGuard& g = lazy_slot_guard();
-  while (g.busy) {
-    bool landed = false;
-    for (int spin = 0; spin < 4096 && !landed; ++spin) landed = __atomic_load_n(pa.mb + 16 + 1, __ATOMIC_ACQUIRE) == g.seq;
-    if (landed || hipStreamQuery(g.stream) != hipErrorNotReady) g.busy = false;
-  }
-  lp->mb_host = pa.mb + 16;
-  lp->mb_dev = pa.mb_dev + 16;
+  if (g.busy) (void)mailbox_wait(pa.mb.host + kLazySlot, g.seq, g.stream);  // landed, drained or gone
+  lp->mb_host = pa.mb.host + kLazySlot;
+  lp->mb_dev = pa.mb.dev + kLazySlot;
   lp->dev_out = dev_out;
-  lp->seq = mailbox_next(pa);
+  lp->seq = pa.mb.next();
   lp->stream = s;
   g.busy = true;
   g.seq = lp->seq;
@@ -668,38 +628,23 @@ inline bool lazy_post_open(PinnedArea& pa, uint32_t* dev_out, hipStream_t s, Laz
 }
 // the four words of a lazy post; waits for them if they are not there yet
 inline int lazy_post_fetch(const LazyPost& lp, uint32_t r[4]) {
-  double t_guard = poll_now_us() - kPollGuardUs;  // (the first look at the stream may come at once: the post is usually long there, or never will be)
-  for (;;) {
-    bool posted = false;
-    for (int spin = 0; spin < 4096 && !posted; ++spin) posted = __atomic_load_n(lp.mb_host + 1, __ATOMIC_ACQUIRE) == lp.seq;
-    if (posted) {
-      for (int k = 0; k < 4; ++k) r[k] = __atomic_load_n(lp.mb_host + 2 + k, __ATOMIC_RELAXED);
-      if (__atomic_load_n(lp.mb_host + 1, __ATOMIC_ACQUIRE) == lp.seq) return O3S_OK;  // (not overwritten by a later post meanwhile)
-    }
-    const double t = poll_now_us();
-    if (t - t_guard < kPollGuardUs) continue;
-    t_guard = t;
-    const hipError_t q = hipStreamQuery(lp.stream);
-    if (q == hipErrorNotReady) continue;
-    if (q != hipSuccess) return O3S_ERR_HIP;
-    if (__atomic_load_n(lp.mb_host + 1, __ATOMIC_ACQUIRE) == lp.seq) continue;  // drained and posted: read it above
-    // drained, and the slot holds another post (the issuing thread went on to another submap): the device copy
-    uint32_t local[4];
-    CK(hipMemcpy(local, lp.dev_out, 16, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 4; ++k) r[k] = local[k];
-    return O3S_OK;
-  }
+  const int w = poll_until([&] { return read_guarded(lp.mb_host, lp.seq, kPostVals, r, 4); }, lp.stream, kLazyCadence);
+  if (w == kPollError) return O3S_ERR_HIP;
+  // drained, and the slot holds another post (the issuing thread went on to another submap): the device copy
+  if (w == kPollDrained) CK(hipMemcpy(r, lp.dev_out, 16, hipMemcpyDeviceToHost));
+  return O3S_OK;
 }
 
-// folds the kExtSlots replicas of the int32 extrema and posts the six results (mailbox words 2..7)
+// folds the kExtSlots replicas of the int32 extrema and posts the six results (from kPostVals)
 __global__ void k_ext_post(const int32_t* __restrict__ slots, uint32_t* __restrict__ mailbox, uint32_t seq) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  int32_t v[6];
+#pragma unroll
   for (int a = 0; a < 6; ++a) {
-    int32_t v = a < 3 ? INT32_MAX : INT32_MIN;
-    for (int k = 0; k < kExtSlots; ++k) v = a < 3 ? min(v, slots[k * 6 + a]) : max(v, slots[k * 6 + a]);
-    __hip_atomic_store(mailbox + 2 + a, (uint32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    v[a] = a < 3 ? INT32_MAX : INT32_MIN;
+    for (int k = 0; k < kExtSlots; ++k) v[a] = a < 3 ? min(v[a], slots[k * 6 + a]) : max(v[a], slots[k * 6 + a]);
   }
-  __hip_atomic_store(mailbox + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  post(mailbox, seq, kPostVals, v);
 }
 
 // host side of the replicated extrema: initialise all replicas, read them back and fold
@@ -710,30 +655,27 @@ inline int ext_i32_init(int32_t* d, hipStream_t s) {
   CK(hipMemcpyAsync(d, init, sizeof(init), hipMemcpyHostToDevice, s));
   return O3S_OK;
 }
-// the same for the three u64 (order-preserving double bits) minima of k_min_bound: words 2..7 = lo/hi halves
+// the same for the three u64 (order-preserving double bits) minima of k_min_bound: three 8-byte values from kPostVals
 __global__ void k_mn_post(const unsigned long long* __restrict__ slots, uint32_t* __restrict__ mailbox, uint32_t seq) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  unsigned long long v[3];
+#pragma unroll
   for (int a = 0; a < 3; ++a) {
-    unsigned long long v = ~0ull;
-    for (int k = 0; k < kExtSlots; ++k) v = slots[k * 3 + a] < v ? slots[k * 3 + a] : v;
-    __hip_atomic_store(mailbox + 2 + 2 * a, (uint32_t)(v & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(mailbox + 3 + 2 * a, (uint32_t)(v >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    v[a] = ~0ull;
+    for (int k = 0; k < kExtSlots; ++k) v[a] = slots[k * 3 + a] < v[a] ? slots[k * 3 + a] : v[a];
   }
-  __hip_atomic_store(mailbox + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  post(mailbox, seq, kPostVals, v);
 }
 inline int ext_i32_fetch(const int32_t* d, int32_t out[6], hipStream_t s) {
   PinnedArea& pa = pinned_area();
-  if (mailbox_enabled(pa)) {
-    const uint32_t seq = mailbox_next(pa);
-    hipLaunchKernelGGL(k_ext_post, dim3(1), dim3(64), 0, s, d, pa.mb_dev, seq);
+  const uint32_t seq = mailbox_open(pa);
+  if (seq) {
+    hipLaunchKernelGGL(k_ext_post, dim3(1), dim3(64), 0, s, d, pa.mb.dev, seq);
     CK(hipGetLastError());
-    const int w = mailbox_wait(pa, seq, s);
-    if (w < 0) return O3S_ERR_HIP;
-    if (w == 1) {
-      for (int a = 0; a < 6; ++a) out[a] = (int32_t)__atomic_load_n(pa.mb + 2 + a, __ATOMIC_RELAXED);
-      return O3S_OK;
-    }
   }
+  const int w = fetch_post(pa.mb, seq, s, reinterpret_cast<uint32_t*>(out), 6, kPostVals, nullptr);
+  if (w == kPollError) return O3S_ERR_HIP;
+  if (w == kPollPosted) return O3S_OK;
   int32_t local[kExtSlots * 6];
   int32_t* h = pinned_words() ? reinterpret_cast<int32_t*>(pinned_words()) : local;
   CK(hipMemcpyAsync(h, d, sizeof(local), hipMemcpyDeviceToHost, s));
@@ -830,8 +772,8 @@ __global__ void k_scan_total(const uint32_t* __restrict__ flag, uint32_t* __rest
   const uint32_t total = off[n - 1] + flag[n - 1];
   off[n] = total;
   if (mailbox) {
-    __hip_atomic_store(mailbox, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(mailbox + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    const uint32_t v[1] = {total};
+    post(mailbox, seq, kPostCount, v);
   }
 }
 
@@ -844,24 +786,12 @@ inline int scan_flags(const uint32_t* flag, uint32_t* off, int64_t n, void* tmp,
     if (rc != O3S_OK) return rc;
   }
   PinnedArea& pa = pinned_area();
-  if (mailbox_enabled(pa)) {
-    const uint32_t seq = mailbox_next(pa);
-    hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(64), 0, s, flag, off, n, pa.mb_dev, seq);
-    CK(hipGetLastError());
-    const int w = mailbox_wait(pa, seq, s);
-    if (w < 0) return O3S_ERR_HIP;
-    if (w == 1) {
-      *count = (int64_t)__atomic_load_n(pa.mb, __ATOMIC_RELAXED);
-      return O3S_OK;
-    }
-  } else {
-    hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(64), 0, s, flag, off, n, (uint32_t*)nullptr, 0u);
-  }
-  uint32_t local = 0;
-  uint32_t* dst = pa.p ? pa.p : &local;
-  CK(hipMemcpyAsync(dst, off + n, 4, hipMemcpyDeviceToHost, s));
-  CK(hipStreamSynchronize(s));
-  *count = (int64_t)*dst;
+  const uint32_t seq = mailbox_open(pa);
+  hipLaunchKernelGGL(k_scan_total, dim3(1), dim3(64), 0, s, flag, off, n, seq ? pa.mb.dev : (uint32_t*)nullptr, seq);
+  CK(hipGetLastError());
+  uint32_t total = 0;
+  if (fetch_post(pa.mb, seq, s, &total, 1, kPostCount, off + n, pa.p) == kPollError) return O3S_ERR_HIP;
+  *count = (int64_t)total;
   return O3S_OK;
 }
 
@@ -932,19 +862,14 @@ inline int voxel_pipeline_dev(Arena& ar, int mode, const o3s_cropper* crop, doub
     hipLaunchKernelGGL(k_min_bound, dim3(nblk(N)), dim3(kB), 0, s, d_pts, N, d_mn);
     unsigned long long mn[3] = {~0ull, ~0ull, ~0ull};
     PinnedArea& pa = pinned_area();
-    int posted = 0;
-    if (mailbox_enabled(pa)) {
-      const uint32_t seq = mailbox_next(pa);
-      hipLaunchKernelGGL(k_mn_post, dim3(1), dim3(64), 0, s, d_mn, pa.mb_dev, seq);
+    const uint32_t seq = mailbox_open(pa);
+    if (seq) {
+      hipLaunchKernelGGL(k_mn_post, dim3(1), dim3(64), 0, s, d_mn, pa.mb.dev, seq);
       CK(hipGetLastError());
-      posted = mailbox_wait(pa, seq, s);
-      if (posted < 0) return O3S_ERR_HIP;
-      if (posted == 1)
-        for (int a = 0; a < 3; ++a)
-          mn[a] = (unsigned long long)__atomic_load_n(pa.mb + 2 + 2 * a, __ATOMIC_RELAXED) |
-                  ((unsigned long long)__atomic_load_n(pa.mb + 3 + 2 * a, __ATOMIC_RELAXED) << 32);
     }
-    if (posted != 1) {
+    const int posted = fetch_post(pa.mb, seq, s, reinterpret_cast<uint32_t*>(mn), 6, kPostVals, nullptr);
+    if (posted == kPollError) return O3S_ERR_HIP;
+    if (posted != kPollPosted) {
       unsigned long long mn_local[kExtSlots * 3];
       unsigned long long* mn_all = pa.p ? reinterpret_cast<unsigned long long*>(pa.p) : mn_local;
       CK(hipMemcpyAsync(mn_all, d_mn, sizeof(mn_local), hipMemcpyDeviceToHost, s));
@@ -1168,22 +1093,12 @@ inline int voxel_pipeline_hint_dev(Arena& ar, int mode, const o3s_cropper* crop,
   } else if (post_crop) {
     return O3S_ERR_BAD_ARGUMENT;
   }
-  const uint32_t seq = mailbox_next(pa);
-  hipLaunchKernelGGL(k_post_counts, dim3(1), dim3(64), 0, s, status, pass ? flag : nullptr, pass ? off : nullptr, N, head, ord, N,
-                     post ? flag : nullptr, post ? off : nullptr, N, status + 4, pa.mb_dev, seq);
+  const uint32_t seq = pa.mb.next();
+  hipLaunchKernelGGL(k_post_counts<false>, dim3(1), dim3(64), 0, s, status, pass ? flag : nullptr, pass ? off : nullptr, N, head, ord, N,
+                     post ? flag : nullptr, post ? off : nullptr, N, status + 4, pa.mb.dev, seq);
   CK(hipGetLastError());
-  const int w = mailbox_wait(pa, seq, s);
-  if (w < 0) return O3S_ERR_HIP;
   uint32_t r[4];
-  if (w == 1) {
-    for (int k = 0; k < 4; ++k) r[k] = __atomic_load_n(pa.mb + 2 + k, __ATOMIC_RELAXED);
-  } else {
-    uint32_t local[4];
-    uint32_t* dst = pa.p ? pa.p : local;
-    CK(hipMemcpyAsync(dst, status + 4, 16, hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-    for (int k = 0; k < 4; ++k) r[k] = dst[k];
-  }
+  if (fetch_post(pa.mb, seq, s, r, 4, kPostVals, status + 4, pa.p) == kPollError) return O3S_ERR_HIP;
   if (r[0] != 0u) return O3S_OK;  // *ok stays false
   counts[0] = (int64_t)r[1];
   counts[1] = (int64_t)r[2];
@@ -1338,28 +1253,18 @@ inline int voxel_insert_merge_dev(Arena& ar, const o3s_cropper& crop, const VoxH
   hipLaunchKernelGGL(k_vox_reduce, dim3(nblk(n_m)), dim3(kB), 0, s, keysM, valsM, head, ord, n_m, d_pts, d_nrm, (const int32_t*)nullptr, 1, 1, (int64_t)0,
                      d_opts, d_on, (int32_t*)nullptr, flag, off, n_tmp, 2);
   if (lazy) {
-    hipLaunchKernelGGL(k_post_counts, dim3(1), dim3(64), 0, s, status, flag, off, n_tmp, head, ord, n_m, (const uint32_t*)nullptr,
+    hipLaunchKernelGGL(k_post_counts<true>, dim3(1), dim3(64), 0, s, status, flag, off, n_tmp, head, ord, n_m, (const uint32_t*)nullptr,
                        (const uint32_t*)nullptr, (int64_t)0, lazy->dev_out, lazy->mb_dev, lazy->seq);
     CK(hipGetLastError());
     if (issued) *issued = true;
     return O3S_OK;
   }
-  const uint32_t seq = mailbox_next(pa);
-  hipLaunchKernelGGL(k_post_counts, dim3(1), dim3(64), 0, s, status, flag, off, n_tmp, head, ord, n_m, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
-                     (int64_t)0, status + 4, pa.mb_dev, seq);
+  const uint32_t seq = pa.mb.next();
+  hipLaunchKernelGGL(k_post_counts<false>, dim3(1), dim3(64), 0, s, status, flag, off, n_tmp, head, ord, n_m, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
+                     (int64_t)0, status + 4, pa.mb.dev, seq);
   CK(hipGetLastError());
-  const int w = mailbox_wait(pa, seq, s);
-  if (w < 0) return O3S_ERR_HIP;
   uint32_t r[4];
-  if (w == 1) {
-    for (int k = 0; k < 4; ++k) r[k] = __atomic_load_n(pa.mb + 2 + k, __ATOMIC_RELAXED);
-  } else {
-    uint32_t local[4];
-    uint32_t* dst = pa.p ? pa.p : local;
-    CK(hipMemcpyAsync(dst, status + 4, 16, hipMemcpyDeviceToHost, s));
-    CK(hipStreamSynchronize(s));
-    for (int k = 0; k < 4; ++k) r[k] = dst[k];
-  }
+  if (fetch_post(pa.mb, seq, s, r, 4, kPostVals, status + 4, pa.p) == kPollError) return O3S_ERR_HIP;
   if (r[0] != 0u) return O3S_OK;  // *ok stays false
   counts[0] = (int64_t)r[1];
   counts[1] = (int64_t)r[2];

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "host_post.h"
 #include "icp_types.h"
 #include "solve_device.h"
 
@@ -166,9 +167,12 @@ __global__ void __launch_bounds__(kBlock) k_ref_stats(const float4* __restrict__
 }
 
 // single block: folds the per-block results of k_ref_stats in a fixed order — wave c sums component c: lane l adds the
-// partials l, l + 64, ... in order, then the wave's DPP tree — and the bounds in any order, and posts mean / lo / hi (9
-// words, mailbox[2..10]) and then the sequence number into host-coherent pinned memory.  (A first version summed the
+// partials l, l + 64, ... in order, then the wave's DPP tree — and the bounds in any order, and posts mean / lo / hi and the
+// point count (RefStatsPost) and then the sequence number into host-coherent pinned memory.  (A first version summed the
 // partials sequentially in one lane per component, as the host loop had: 11.8 us for 1 024 partials.)
+struct RefStatsPost {  // the words of the post, from kPostVals
+  enum { kMean = host_post::kPostVals, kLo = kMean + 3, kHi = kLo + 3, kCount = kHi + 3 };
+};
 __global__ void __launch_bounds__(kBlock) k_ref_stats_post(const double* __restrict__ part, const float* __restrict__ bb, int G, int64_t M,
                                                            const uint32_t* __restrict__ d_M, uint32_t* __restrict__ mailbox, uint32_t seq) {
   if (d_M) {
@@ -214,9 +218,10 @@ __global__ void __launch_bounds__(kBlock) k_ref_stats_post(const double* __restr
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int k = 0; k < 9; ++k) __hip_atomic_store(mailbox + 2 + k, __float_as_uint(s_out[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(mailbox + 11, (uint32_t)M, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // the point count (device-counted references)
-    __hip_atomic_store(mailbox + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    uint32_t v[10];
+    for (int k = 0; k < 9; ++k) v[k] = __float_as_uint(s_out[k]);
+    v[9] = (uint32_t)M;  // the point count (device-counted references)
+    host_post::post(mailbox, seq, RefStatsPost::kMean, v);
   }
 }
 
@@ -452,8 +457,8 @@ __global__ void __launch_bounds__(1024) k_scan_sums(uint32_t* __restrict__ sums,
     if (threadIdx.x == 0) {
       uint32_t t = 0;
       for (int w = 0; w < 16; ++w) t += sh[w];
-      __hip_atomic_store(mailbox, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(mailbox + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      const uint32_t v[1] = {t};
+      host_post::post(mailbox, seq, host_post::kPostCount, v);
     }
   }
 }

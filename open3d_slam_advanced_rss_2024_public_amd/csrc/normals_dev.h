@@ -44,21 +44,22 @@ __global__ void __launch_bounds__(kB) k_bounds(const double* __restrict__ pts, i
     }
   }
 }
-// folds the replicas (one per lane) and posts the six bounds (mailbox words 2..13: lo / hi halves; the maxima un-complemented), then
-// the sequence number
+// the six bounds of the kExtSlots replicas (one per lane; the maxima un-complemented), as lane 0 holds them
+__device__ __forceinline__ void fold_bounds(const unsigned long long* __restrict__ slots, unsigned long long (&v)[6]) {
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    v[a] = wave_min_u64(slots[threadIdx.x * 6 + a]);
+    if (a >= 3) v[a] = ~v[a];
+  }
+}
+// folds the replicas (one per lane) and posts the six bounds (8-byte values from kPostVals; the maxima un-complemented), then the
+// sequence number
 __global__ void __launch_bounds__(64) k_bounds_post(const unsigned long long* __restrict__ slots, uint32_t* __restrict__ mailbox, uint32_t seq) {
   static_assert(kExtSlots == 64, "one replica per lane");
   if (blockIdx.x != 0) return;
-#pragma unroll
-  for (int a = 0; a < 6; ++a) {
-    unsigned long long v = wave_min_u64(slots[threadIdx.x * 6 + a]);
-    if (a >= 3) v = ~v;
-    if (threadIdx.x == 0) {
-      __hip_atomic_store(mailbox + 2 + 2 * a, (uint32_t)(v & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(mailbox + 3 + 2 * a, (uint32_t)(v >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(mailbox + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  unsigned long long v[6];
+  fold_bounds(slots, v);
+  if (threadIdx.x == 0) post(mailbox, seq, kPostVals, v);
 }
 inline double ordered_to_double(unsigned long long u) {
   u = (u & 0x8000000000000000ull) ? (u & 0x7fffffffffffffffull) : ~u;
@@ -537,19 +538,14 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
     for (int a = 0; a < 6; ++a) bb[a] = known_bb[a];
   } else {
     PinnedArea& pa = pinned_area();
-    int posted = 0;
-    if (mailbox_enabled(pa)) {
-      const uint32_t seq = mailbox_next(pa);
-      hipLaunchKernelGGL(k_bounds_post, dim3(1), dim3(64), 0, s, (const unsigned long long*)d_bb, pa.mb_dev, seq);
+    const uint32_t seq = mailbox_open(pa);
+    if (seq) {
+      hipLaunchKernelGGL(k_bounds_post, dim3(1), dim3(64), 0, s, (const unsigned long long*)d_bb, pa.mb.dev, seq);
       CK(hipGetLastError());
-      posted = mailbox_wait(pa, seq, s);
-      if (posted < 0) return O3S_ERR_HIP;
-      if (posted == 1)
-        for (int a = 0; a < 6; ++a)
-          bb[a] = (unsigned long long)__atomic_load_n(pa.mb + 2 + 2 * a, __ATOMIC_RELAXED) |
-                  ((unsigned long long)__atomic_load_n(pa.mb + 3 + 2 * a, __ATOMIC_RELAXED) << 32);
     }
-    if (posted != 1) {
+    const int posted = fetch_post(pa.mb, seq, s, reinterpret_cast<uint32_t*>(bb), 12, kPostVals, nullptr);
+    if (posted == kPollError) return O3S_ERR_HIP;
+    if (posted != kPollPosted) {
       unsigned long long bb_all[kExtSlots * 6];
       CK(hipMemcpyAsync(bb_all, d_bb, sizeof(bb_all), hipMemcpyDeviceToHost, s));
       CK(hipStreamSynchronize(s));

@@ -948,11 +948,11 @@ __global__ void __launch_bounds__(kB) k_o3d_corr(const double* __restrict__ pcd,
 // one wave per component (grid = kAccComps): lane l adds the partials l, l + 64, ... in that order, eight loads in flight at a
 // time, then the wave's fixed tree.  (One block walking all 30 components wave by wave took 65 us per pass: 256 dependent
 // round trips; the order of the additions — and so the result — is the same.)
-// counts[2]: the ticket of the blocks.  post (nullable): 30 doubles + a sequence word in host-coherent pinned memory — the block that
+// counts[2]: the ticket of the blocks.  post (nullable): the 30 sums (doubles from kPostVals) in a host post — the block that
 // draws the last ticket hands the sums to the host, which polls the word (a copy + stream synchronisation per pass was ~20 us of a
 // 100 us pass).  Hand-over between blocks: result stored, fence, ticket; the last block reads the results with agent-scope loads.
 __global__ void __launch_bounds__(64) k_o3d_fold(const double* __restrict__ part, int nb, double* __restrict__ out /*kAccComps*/, uint32_t* __restrict__ counts,
-                                                 double* __restrict__ post, uint32_t seq) {
+                                                 uint32_t* __restrict__ post, uint32_t seq) {
   const int c = blockIdx.x, l = threadIdx.x;
   if (c == 0 && l < 2) counts[l] = 0u;  // the search's two work lists are empty again for the next pass
   const double* p = part + (size_t)c * nb;
@@ -982,12 +982,12 @@ __global__ void __launch_bounds__(64) k_o3d_fold(const double* __restrict__ part
   __threadfence();
   if (l < (int)gridDim.x) {
     const double v = __hip_atomic_load(&out[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&post[l], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    post_store1(post, kPostVals + 2 * l, v);
   }
   __threadfence_system();
   if (l == 0) {
     counts[2] = 0u;
-    __hip_atomic_store(reinterpret_cast<uint32_t*>(post + 32), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    post_publish(post, seq);
   }
 }
 
@@ -1216,9 +1216,7 @@ struct O3dIcpWork {
   const double* tn = nullptr;
   Arena sort_arena;
   int nb = 0;
-  double* h_post = nullptr;      // 30 sums + sequence word (at double 32) in host-coherent pinned memory, written by k_o3d_fold
-  double* h_post_dev = nullptr;  // the same as the device addresses it
-  uint32_t post_seq = 0;
+  PostBlock<> h_post;            // the 30 sums of a pass, posted by k_o3d_fold
   int pass_no = 0;               // passes since the source was placed (o3d_place_source): the first two search nearly every point
   bool corr_valid = false;  // d_corr holds the correspondences of an earlier pass over the same source order: bounds for the next search
   // what a registration leaves behind for the information matrix of the same pair (o3d_info_after_icp)
@@ -1237,7 +1235,7 @@ struct O3dIcpWork {
   O3dIcpWork(const O3dIcpWork&) = delete;
   O3dIcpWork& operator=(const O3dIcpWork&) = delete;
   ~O3dIcpWork() {  // only ever runs through o3s_o3d_registration_release (the pool itself is never torn down)
-    if (h_post) (void)hipHostFree(h_post);
+    h_post.release();
   }
 };
 
@@ -1301,13 +1299,7 @@ struct RegLease {  // the calling thread's area for the duration of a call (the 
 // the pinned post of the sums: allocated once per work area (a pinned allocation takes milliseconds: o3s_o3d_registration_reserve
 // makes it ahead of time) and never freed (the areas live in a pool that is never torn down); without it the sums are copied back
 inline void o3d_ensure_post(O3dIcpWork& w) {
-  if (w.h_post) return;
-  if (hipHostMalloc(reinterpret_cast<void**>(&w.h_post), 512, hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
-    std::memset(w.h_post, 0, 512);
-    if (hipHostGetDevicePointer(reinterpret_cast<void**>(&w.h_post_dev), w.h_post, 0) != hipSuccess) w.h_post_dev = nullptr;
-  } else {
-    w.h_post = nullptr;
-  }
+  if (!w.h_post) (void)w.h_post.alloc(512);
 }
 
 // on_device: the pointers are device arrays (a resident submap): both clouds are read where they lie; the working copy of the
@@ -1451,29 +1443,13 @@ inline int o3d_corr_pass(O3dIcpWork& w, int64_t Ns, const GridIndex& gi, double 
   else
     hipLaunchKernelGGL((k_o3d_corr<1, kEstPlane>), dim3(w.nb), dim3(kB), 0, s, w.d_src.as<double>(), Ns, gi, w.tgt, w.tn, r2, mode,
                        w.d_corr.as<int32_t>(), w.d_part.as<double>(), w.ea);
-  const bool post = w.h_post && w.h_post_dev;
-  if (post && ++w.post_seq == 0) ++w.post_seq;
-  hipLaunchKernelGGL(k_o3d_fold, dim3(kAccComps), dim3(64), 0, s, w.d_part.as<double>(), w.nb, w.d_sum.as<double>(), counts, post ? w.h_post_dev : nullptr,
-                     w.post_seq);
+  const uint32_t seq = posts_enabled() && w.h_post ? w.h_post.next() : 0u;
+  hipLaunchKernelGGL(k_o3d_fold, dim3(kAccComps), dim3(64), 0, s, w.d_part.as<double>(), w.nb, w.d_sum.as<double>(), counts,
+                     seq ? w.h_post.dev : (uint32_t*)nullptr, seq);
   CK(hipGetLastError());
-  if (post) {
-    const uint32_t* word = reinterpret_cast<const uint32_t*>(w.h_post + 32);
-    double t_guard = o3s_cloud::poll_now_us();
-    for (;;) {
-      bool seen = false;
-      for (int spin = 0; spin < 4096 && !seen; ++spin) seen = __atomic_load_n(word, __ATOMIC_ACQUIRE) == w.post_seq;
-      if (seen) break;
-      const double t = o3s_cloud::poll_now_us();
-      if (t - t_guard < o3s_cloud::kPollGuardUs) continue;  // the stream is only looked at every 200 us of waiting (cloud_dev.h)
-      t_guard = t;
-      const hipError_t q = hipStreamQuery(s);  // a fault upstream must not leave the host spinning
-      if (q == hipSuccess) {
-        if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != w.post_seq) return O3S_ERR_HIP;
-        break;
-      }
-      if (q != hipErrorNotReady) return O3S_ERR_HIP;
-    }
-    for (int c = 0; c < kAccComps; ++c) sums[c] = w.h_post[c];
+  if (seq) {
+    if (mailbox_wait(w.h_post.host, seq, s) != kPollPosted) return O3S_ERR_HIP;  // a fault upstream, or drained without the post
+    for (int c = 0; c < kAccComps; ++c) sums[c] = post_get<double>(w.h_post.host, kPostVals + 2 * c);
     return O3S_OK;
   }
   CK(hipMemcpyAsync(sums, w.d_sum.p, kAccComps * 8, hipMemcpyDeviceToHost, s));

@@ -5,7 +5,6 @@
 #include "../../include/o3s_icp.h"
 
 #include <hip/hip_runtime.h>
-#include <time.h>
 
 #include <algorithm>
 #include <cmath>
@@ -143,15 +142,11 @@ struct o3s_icp {
   DevBuf d_pos, d_d2, d_hist, d_cand, d_sel, d_cent, d_ne, d_state, d_T0, d_trace_T, d_trace_limit, d_trace_kept;
   DevBuf d_mod_a, d_mod_b, d_mod_c, d_mod_d;  // module-level scratch
   HostStage* stage = nullptr;                // pinned
-  // mailbox: host-coherent pinned words a kernel writes and the host polls ([0] value, [1] sequence number, [2..10] the
-  // reference statistics) — init_reference's two read-backs without a copy or a stream synchronisation
-  uint32_t* mb = nullptr;
-  uint32_t* mb_dev = nullptr;
-  uint32_t mb_seq = 0;
+  // mailbox (host_post.h): init_reference's two read-backs without a copy or a stream synchronisation
+  host_post::PostBlock<> mb;
   // the chain's own mailbox (icp_types.h, HostPost): the kernel that closes an iteration posts the progress word and, when the
   // chain is done, the whole state — compute() polls it; no copy command, no stream synchronisation on the per-call path
-  HostPost* post = nullptr;
-  HostPost* post_dev = nullptr;
+  host_post::PostBlock<HostPost> post;
   uint32_t call_seq = 0;     // sequence number of the compute() in flight (k_read_prep writes it into the state)
   double wall_clock_khz = 100000.0;  // wall_clock64 rate (hipDeviceAttributeWallClockRate)
   // host-side split of the last compute(): microseconds spent issuing (either half) and waiting (wait_post), stream queries made
@@ -302,95 +297,38 @@ int device_scan(o3s_icp* h, uint32_t* in, int64_t n, uint32_t* out, bool zero_in
   uint32_t* nonzero = post_nonzero ? sums + nb : nullptr;
   uint32_t seq = 0;
   if (post_nonzero) {
-    if (++h->mb_seq == 0) ++h->mb_seq;
-    seq = h->mb_seq;
+    seq = h->mb.next();
     if (seq_out) *seq_out = seq;
   }
   hipLaunchKernelGGL(kern::k_scan_block_sums, dim3((unsigned)nb), dim3(kern::kBlock), 0, h->stream, in, n, sums, nonzero);
-  hipLaunchKernelGGL(kern::k_scan_sums, dim3(1), dim3(1024), 0, h->stream, sums, nb, nonzero, h->mb_dev, seq);
+  hipLaunchKernelGGL(kern::k_scan_sums, dim3(1), dim3(1024), 0, h->stream, sums, nb, nonzero, h->mb.dev, seq);
   hipLaunchKernelGGL(kern::k_scan_apply, dim3((unsigned)nb), dim3(kern::kBlock), 0, h->stream, in, n, sums, out, zero_in ? in : nullptr);
   HIP_TRY(h, hipGetLastError());
   return O3S_OK;
 }
 
-// polls the mailbox until a kernel has posted `seq`: 1 = posted, 0 = the stream drained without it (not expected), < 0 = a
-// HIP error.  The stream is queried every few thousand polls so that a fault upstream cannot leave the host spinning.
-inline double now_us();
-int mailbox_wait(o3s_icp* h, uint32_t seq) {
-  // hipStreamQuery is not free for the GPU side (the runtime may put a marker packet into the queue for every call): it is
-  // only the guard against a fault upstream, looked at every 200 us of waiting, never part of the polling itself
-  double t_guard = now_us();
-  for (;;) {
-    for (int spin = 0; spin < 4096; ++spin)
-      if (__atomic_load_n(h->mb + 1, __ATOMIC_ACQUIRE) == seq) return 1;
-    const double t = now_us();
-    if (t - t_guard < 200.0) continue;
-    t_guard = t;
-    const hipError_t q = hipStreamQuery(h->stream);
-    if (q == hipSuccess) return __atomic_load_n(h->mb + 1, __ATOMIC_ACQUIRE) == seq ? 1 : 0;
-    if (q != hipErrorNotReady) return -1;
-  }
-}
-
-inline double now_us() {
-  timespec ts;
-  clock_gettime(CLOCK_MONOTONIC, &ts);
-  return (double)ts.tv_sec * 1e6 + (double)ts.tv_nsec * 1e-3;
-}
-
-int wait_post_impl(o3s_icp* h, uint32_t seq, hipEvent_t drained, bool* done);
+// `drained` (nullable): an event recorded behind the last launch issued so far — how the host learns that everything issued has
+// run WITHOUT ending the chain (kernels post once, when the chain is done).  Chains that are certain to end inside what was
+// issued (a Counter checker and all of max_iters issued) pass none.  1 = the post is there (*done) or everything issued has run,
+// 0 = the stream drained without the post and there was no event, < 0 = a HIP error.
 int wait_post(o3s_icp* h, uint32_t seq, hipEvent_t drained, bool* done) {
 #ifdef O3S_TEST_HOOKS
   if (h->looks.empty() || h->looks.back() != h->call.issued) h->looks.push_back(h->call.issued);
 #endif
-  const double t0 = now_us();
-  const int rc = wait_post_impl(h, seq, drained, done);
-  h->host_wait_us += now_us() - t0;
-  return rc;
-}
-// `drained` (nullable): an event recorded behind the last launch issued so far — how the host learns that everything issued has
-// run WITHOUT ending the chain (kernels post once, when the chain is done).  Chains that are certain to end inside what was
-// issued (a Counter checker and all of max_iters issued) pass none.  Neither the event nor the stream is queried more than every
-// few microseconds: the polling itself is a load from host memory.
-int wait_post_impl(o3s_icp* h, uint32_t seq, hipEvent_t drained, bool* done) {
-  auto look = [&]() -> bool {  // the final post of THIS call
-    const unsigned long long w = __atomic_load_n(&h->post->word, __ATOMIC_ACQUIRE);
-    if ((uint32_t)(w >> 32) != seq || !(w & 1ull)) return false;
-    *done = true;
-    return true;
-  };
-  *done = false;
-  double t_guard = now_us(), t_event = t_guard;
-  for (;;) {
-    for (int spin = 0; spin < 256; ++spin)
-      if (look()) {
-        h->wait_by_post += 1;
-        return 1;
-      }
-    const double tn = now_us();
-    if (drained && tn - t_event >= 4.0) {  // every 4 us at most: the query is a call into the runtime, not a load
-      t_event = tn;
-      const hipError_t q = hipEventQuery(drained);
-      h->host_queries += 1;
-      if (q == hipSuccess) {  // everything issued has run: either the final post is there by now, or the chain is not done yet
-        (void)look();
-        h->wait_by_event += 1;
-        return 1;
-      }
-      if (q != hipErrorNotReady) return -1;
-    }
-    const double t = now_us();
-    if (t - t_guard < 2000.0) continue;
-    t_guard = t;  // a fault upstream must not leave the host spinning: the stream itself, every 2 ms
-    const hipError_t q = hipStreamQuery(h->stream);
-    h->host_queries += 1;
-    if (q == hipSuccess) {
-      (void)look();
-      h->wait_by_guard += 1;
-      return *done ? 1 : (drained ? 1 : 0);
-    }
-    if (q != hipErrorNotReady) return -1;
-  }
+  const double t0 = host_post::now_us();
+  host_post::PollTrace tr;
+  const int w = host_post::poll_until(
+      [&] {  // the final post of THIS call
+        const unsigned long long word = __atomic_load_n(&h->post.host->word, __ATOMIC_ACQUIRE);
+        return (uint32_t)(word >> 32) == seq && (word & 1ull);
+      },
+      h->stream, host_post::kChainCadence, drained, &tr);
+  h->host_wait_us += host_post::now_us() - t0;
+  h->host_queries += tr.queries;
+  *done = w == host_post::kPollPosted;
+  if (w == host_post::kPollError) return -1;
+  (tr.tier == host_post::kTierSpin ? h->wait_by_post : tr.tier == host_post::kTierEvent ? h->wait_by_event : h->wait_by_guard) += 1;
+  return *done || drained ? 1 : 0;
 }
 
 // ---- initReference on device-resident input --------------------------------------------------------------------
@@ -412,27 +350,25 @@ int init_reference_impl(o3s_icp* h, const float4* d_xyzw, const float* d_normals
   HIP_TRY(h, h->d_ref_bb.ensure((size_t)G * 6 * sizeof(float)));
   hipLaunchKernelGGL(kern::k_ref_stats, dim3(G), dim3(kern::kBlock), 0, h->stream, d_xyzw, M, d_count, h->d_ref_part.as<double>(),
                      h->d_ref_bb.as<float>());
-  if (++h->mb_seq == 0) ++h->mb_seq;
+  const uint32_t stats_seq = h->mb.next();
   hipLaunchKernelGGL(kern::k_ref_stats_post, dim3(1), dim3(kern::kBlock), 0, h->stream, h->d_ref_part.as<double>(), h->d_ref_bb.as<float>(), G, M,
-                     d_count, h->mb_dev, h->mb_seq);
+                     d_count, h->mb.dev, stats_seq);
   HIP_TRY(h, hipGetLastError());
   {
-    const int w = mailbox_wait(h, h->mb_seq);
+    const int w = host_post::mailbox_wait(h->mb.host, stats_seq, h->stream);
     if (w < 0) return fail(h, O3S_ERR_HIP, "init_reference: the statistics kernels failed");
     if (w == 0) return fail(h, O3S_ERR_HIP, "init_reference: the statistics were not posted");
   }
   if (d_count) {  // the count the device formed
-    M = (int64_t)__atomic_load_n(h->mb + 11, __ATOMIC_RELAXED);
+    M = (int64_t)host_post::post_get(h->mb.host, kern::RefStatsPost::kCount);
     if (M_out) *M_out = M;
     if (M <= 0) return fail(h, O3S_ERR_EMPTY_REFERENCE, "reference cloud is empty");
   }
   float lo[3], hi[3];
   for (int c = 0; c < 3; ++c) {
-    const uint32_t um = __atomic_load_n(h->mb + 2 + c, __ATOMIC_RELAXED), ul = __atomic_load_n(h->mb + 5 + c, __ATOMIC_RELAXED),
-                   uh = __atomic_load_n(h->mb + 8 + c, __ATOMIC_RELAXED);
-    std::memcpy(&h->mean[c], &um, 4);
-    std::memcpy(&lo[c], &ul, 4);
-    std::memcpy(&hi[c], &uh, 4);
+    h->mean[c] = host_post::post_get<float>(h->mb.host, kern::RefStatsPost::kMean + c);
+    lo[c] = host_post::post_get<float>(h->mb.host, kern::RefStatsPost::kLo + c);
+    hi[c] = host_post::post_get<float>(h->mb.host, kern::RefStatsPost::kHi + c);
     if (!center) h->mean[c] = 0.f;
   }
   for (int c = 0; c < 3; ++c) {
@@ -512,10 +448,10 @@ int init_reference_impl(o3s_icp* h, const float4* d_xyzw, const float* d_normals
                        h->d_refn.as<float4>(), h->d_orig_to_sorted.as<int32_t>());
     HIP_TRY(h, hipGetLastError());
     if (!probe) break;
-    const int w = mailbox_wait(h, seq);
+    const int w = host_post::mailbox_wait(h->mb.host, seq, h->stream);
     if (w < 0) return fail(h, O3S_ERR_HIP, "init_reference: the index kernels failed");
     if (w == 0) return fail(h, O3S_ERR_HIP, "init_reference: the occupied-cell count was not posted");
-    const uint32_t n_occ = __atomic_load_n(h->mb, __ATOMIC_RELAXED);
+    const uint32_t n_occ = host_post::post_get(h->mb.host, host_post::kPostCount);
     const double rho = (double)M / (double)std::max(1u, n_occ);
     if (rho <= 8.0) break;
     const float next = std::max(min_cell, cell * (float)std::sqrt(4.0 / rho));  // points per cell ~ cell^2 on surfaces
@@ -786,7 +722,7 @@ void launch_iteration(o3s_icp* h, const ChainArgs& a, bool stats, hipEvent_t* ev
     if (ev) (void)hipEventRecord(ev[3], s);
     if (ev) (void)hipEventRecord(ev[4], s);
     hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), a.nb_fused, a.N, a.cp, st, h->d_trace_T.as<float>(),
-                       h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 1, h->post_dev);
+                       h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 1, h->post.dev);
     if (ev) (void)hipEventRecord(ev[5], s);
     return;
   }
@@ -808,7 +744,7 @@ void launch_iteration(o3s_icp* h, const ChainArgs& a, bool stats, hipEvent_t* ev
                      h->d_mn.as<float4>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), a.cp, st, h->d_ne.as<double>(), h->d_hist.as<uint32_t>());
   if (ev) (void)hipEventRecord(ev[4], s);
   hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), a.nb_part, a.N, a.cp, st, h->d_trace_T.as<float>(),
-                     h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 1, h->post_dev);
+                     h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 1, h->post.dev);
   if (ev) (void)hipEventRecord(ev[5], s);
 }
 
@@ -848,7 +784,7 @@ int launch_iteration_sharded(o3s_icp* h, const ChainArgs& a, bool stats, int it)
   if ((rc = exchange(kXchgMOff, shard_moment_doubles(a.nb_part), O3S_XCHG_FLOAT64)) != O3S_OK) return rc;
   hipLaunchKernelGGL(kern::k_solve_shard, dim3(1), dim3(kern::kBlock), 0, s, a.cp, st, h->d_sel.as<SelScratch>(), l2, xm, a.nb_part,
                      (int)std::min<int64_t>(h->shard.n_total, 0x7fffffff), h->d_trace_T.as<float>(), h->d_trace_limit.as<float>(),
-                     h->d_trace_kept.as<int64_t>(), h->trace_cap, h->post_dev);
+                     h->d_trace_kept.as<int64_t>(), h->trace_cap, h->post.dev);
   return O3S_OK;
 }
 
@@ -1111,9 +1047,9 @@ void reset_call_diagnostics(o3s_icp* h) {
 
 int compute_launch(o3s_icp* h, const float* T_init) {
   reset_call_diagnostics(h);
-  const double t0 = now_us();
+  const double t0 = host_post::now_us();
   const int rc = start_call(h, T_init);
-  h->host_issue_us += now_us() - t0;
+  h->host_issue_us += host_post::now_us() - t0;
   return rc;
 }
 
@@ -1158,9 +1094,9 @@ int compute_finish(o3s_icp* h, float* T_out, o3s_icp_stats* stats) {
     if (w < 0) return fail(h, O3S_ERR_HIP, "compute: a kernel of the iteration chain failed");
     if (w == 0) return fail(h, O3S_ERR_HIP, "compute: the iteration chain ended without posting its state");
     if (done || c.issued >= c.iters_cap) break;
-    const double t0 = now_us();
+    const double t0 = host_post::now_us();
     const int rc = issue_segment(h, c);
-    h->host_issue_us += now_us() - t0;
+    h->host_issue_us += host_post::now_us() - t0;
     if (rc != O3S_OK) return rc;
   }
   // every issued iteration ran and the chain is not done (no Counter checker and the cap reached): fetch the state the slow way;
@@ -1181,7 +1117,7 @@ int compute_finish(o3s_icp* h, float* T_out, o3s_icp_stats* stats) {
         }
       }
   }
-  if (done) std::memcpy(&h->stage->state, &h->post->state, sizeof(IcpState));  // posted in front of the progress word (system-scope release)
+  if (done) std::memcpy(&h->stage->state, &h->post.host->state, sizeof(IcpState));  // posted in front of the progress word (system-scope release)
   const IcpState& st = h->stage->state;
   h->last_iters = std::min(st.iter, h->trace_cap);  // the trace stays on the device until o3s_icp_get_trace asks for it
   h->eager_hint = st.iter;
@@ -1309,16 +1245,8 @@ int o3s_icp_create(const o3s_icp_config* cfg, int device, o3s_icp** out) {
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipHostMalloc((void**)&h->stage, sizeof(HostStage), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&h->mb, 64, hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) {
-    std::memset(h->mb, 0, 64);
-    e = hipHostGetDevicePointer((void**)&h->mb_dev, h->mb, 0);
-  }
-  if (e == hipSuccess) e = hipHostMalloc((void**)&h->post, sizeof(HostPost), hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) {
-    std::memset(h->post, 0, sizeof(HostPost));
-    e = hipHostGetDevicePointer((void**)&h->post_dev, h->post, 0);
-  }
+  if (e == hipSuccess) e = h->mb.alloc(64);
+  if (e == hipSuccess) e = h->post.alloc();
   if (e == hipSuccess) {
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) h->wall_clock_khz = (double)khz;
@@ -1348,8 +1276,8 @@ void o3s_icp_destroy(o3s_icp* h) {
   if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
   if (h->ev_end) (void)hipEventDestroy(h->ev_end);
   if (h->stage) (void)hipHostFree(h->stage);
-  if (h->mb) (void)hipHostFree(h->mb);
-  if (h->post) (void)hipHostFree(h->post);
+  h->mb.release();
+  h->post.release();
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   delete h;
 }

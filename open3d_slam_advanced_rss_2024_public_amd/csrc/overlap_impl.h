@@ -150,35 +150,28 @@ __global__ void __launch_bounds__(kB) k_compact_bounds(const double* __restrict_
   }
 }
 
-// the selection's one hand-over to the host: both counts (off[n] = the number of set flags) and the two error words (mailbox words
-// 2..5), with `slots` also the folded bounds of the selected target (words 6..17: lo / hi halves, maxima un-complemented), then the
+// the selection's one hand-over to the host: both counts (off[n] = the number of set flags) and the two error words (kOvCounts),
+// with `slots` also the folded bounds of the selected target (kOvBounds: 8-byte values, maxima un-complemented), then the
 // sequence number.  One wave: a replica per lane.
+constexpr int kOvCounts = kPostVals, kOvBounds = kOvCounts + 4;
+static_assert(kOvBounds + 12 <= kLazySlot, "the eager posts stay clear of the slot that is read later");
 __global__ void __launch_bounds__(64) k_ov_post(const uint32_t* __restrict__ fs, uint32_t* __restrict__ os, int64_t Ns, const uint32_t* __restrict__ ft,
                                                 uint32_t* __restrict__ ot, int64_t Nt, const uint32_t* __restrict__ err,
                                                 const unsigned long long* __restrict__ slots /*nullable*/, uint32_t* __restrict__ mailbox, uint32_t seq) {
   static_assert(kExtSlots == 64, "one replica per lane");
   if (blockIdx.x != 0) return;
   if (slots && mailbox) {
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      unsigned long long v = wave_min_u64(slots[threadIdx.x * 6 + a]);
-      if (a >= 3) v = ~v;
-      if (threadIdx.x == 0) {
-        __hip_atomic_store(mailbox + 6 + 2 * a, (uint32_t)(v & 0xffffffffull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(mailbox + 7 + 2 * a, (uint32_t)(v >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
+    unsigned long long v[6];
+    fold_bounds(slots, v);
+    if (threadIdx.x == 0) post_store(mailbox, kOvBounds, v);
   }
   if (threadIdx.x != 0) return;
   const uint32_t ns = os[Ns - 1] + fs[Ns - 1], nt = ot[Nt - 1] + ft[Nt - 1];
   os[Ns] = ns;
   ot[Nt] = nt;
   if (mailbox) {
-    __hip_atomic_store(mailbox + 2, ns, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(mailbox + 3, nt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(mailbox + 4, err[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(mailbox + 5, err[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(mailbox + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    const uint32_t v[4] = {ns, nt, err[0], err[1]};
+    post(mailbox, seq, kOvCounts, v);
   }
 }
 
@@ -261,8 +254,8 @@ inline int overlap_dev(OverlapWork& w, const double* d_src, int64_t Ns, const do
     uint32_t herr[2] = {0, 0};
     {
       PinnedArea& pa = pinned_area();
-      int posted = 0;
-      const bool with_sel = sel && mailbox_enabled(pa);
+      const uint32_t seq = mailbox_open(pa);
+      const bool with_sel = sel && seq;
       if (with_sel) {  // the two selections, enqueued before their sizes are known (the buffers hold either cloud whole)
         CK(hipMemsetAsync(bb, 0xFF, (size_t)kExtSlots * 6 * 8, s));
         hipLaunchKernelGGL(k_compact, dim3(nblk(Ns)), dim3(kB), 0, s, d_src, sel->src_normals, Ns, (const uint32_t*)fs, (const uint32_t*)os, sel->out_src,
@@ -270,31 +263,22 @@ inline int overlap_dev(OverlapWork& w, const double* d_src, int64_t Ns, const do
         hipLaunchKernelGGL(k_compact_bounds, dim3(std::min(nblk(Nt), 1024u)), dim3(kB), 0, s, d_tgt, sel->tgt_normals, Nt, (const uint32_t*)ft,
                            (const uint32_t*)ot, sel->out_tgt, sel->out_tgt_n, bb);
       }
-      if (mailbox_enabled(pa)) {
-        const uint32_t seq = mailbox_next(pa);
-        hipLaunchKernelGGL(k_ov_post, dim3(1), dim3(64), 0, s, (const uint32_t*)fs, os, Ns, (const uint32_t*)ft, ot, Nt, (const uint32_t*)err,
-                           with_sel ? (const unsigned long long*)bb : (const unsigned long long*)nullptr, pa.mb_dev, seq);
-        CK(hipGetLastError());
-        posted = mailbox_wait(pa, seq, s);
-        if (posted < 0) return O3S_ERR_HIP;
-        if (posted == 1) {
-          *n_s = (int64_t)__atomic_load_n(pa.mb + 2, __ATOMIC_RELAXED);
-          *n_t = (int64_t)__atomic_load_n(pa.mb + 3, __ATOMIC_RELAXED);
-          herr[0] = __atomic_load_n(pa.mb + 4, __ATOMIC_RELAXED);
-          herr[1] = __atomic_load_n(pa.mb + 5, __ATOMIC_RELAXED);
-          if (with_sel) {
-            for (int a = 0; a < 6; ++a)
-              sel->bounds[a] = (unsigned long long)__atomic_load_n(pa.mb + 6 + 2 * a, __ATOMIC_RELAXED) |
-                               ((unsigned long long)__atomic_load_n(pa.mb + 7 + 2 * a, __ATOMIC_RELAXED) << 32);
-            sel->have_bounds = *n_t > 0;
-          }
+      hipLaunchKernelGGL(k_ov_post, dim3(1), dim3(64), 0, s, (const uint32_t*)fs, os, Ns, (const uint32_t*)ft, ot, Nt, (const uint32_t*)err,
+                         with_sel ? (const unsigned long long*)bb : (const unsigned long long*)nullptr, seq ? pa.mb.dev : (uint32_t*)nullptr, seq);
+      CK(hipGetLastError());
+      uint32_t r[4 + 12];
+      const int posted = fetch_post(pa.mb, seq, s, r, with_sel ? 16 : 4, kOvCounts, nullptr);
+      if (posted == kPollError) return O3S_ERR_HIP;
+      if (posted == kPollPosted) {
+        *n_s = (int64_t)r[0];
+        *n_t = (int64_t)r[1];
+        herr[0] = r[2];
+        herr[1] = r[3];
+        if (with_sel) {
+          std::memcpy(sel->bounds, r + 4, sizeof(sel->bounds));
+          sel->have_bounds = *n_t > 0;
         }
       } else {
-        hipLaunchKernelGGL(k_ov_post, dim3(1), dim3(64), 0, s, (const uint32_t*)fs, os, Ns, (const uint32_t*)ft, ot, Nt, (const uint32_t*)err,
-                           (const unsigned long long*)nullptr, (uint32_t*)nullptr, 0u);
-        CK(hipGetLastError());
-      }
-      if (posted != 1) {
         if (sel) sel->have_bounds = false;  // the caller falls back to its own compaction and bounds pass
         uint32_t cnt[2] = {0, 0};
         CK(hipMemcpyAsync(&cnt[0], os + Ns, 4, hipMemcpyDeviceToHost, s));

@@ -1,0 +1,91 @@
+"""Both sides of the host post (csrc/host_post.h).  MI355X only.
+
+Every small device-to-host answer — a count, six bounds, the sums of a registration pass — is posted by a kernel tail into pinned
+memory the host polls; without a post the same words are copied back behind a stream synchronisation.  O3S_NO_MAILBOX, a hook of
+the test build that is read per call, selects the copy.  Each operator that has both sides runs here once either way, in ONE
+process, and must give the same bits; the submap's insert statistics prove that the switch was seen at all."""
+import numpy as np
+import pytest
+
+from open3d_slam_advanced_rss_2024_public_amd import Submap
+from open3d_slam_advanced_rss_2024_public_amd import cloud_ops as co
+from open3d_slam_advanced_rss_2024_public_amd import registration as reg
+from open3d_slam_advanced_rss_2024_public_amd import synthetic as syn
+from test_gpu_registration import submap_pair
+
+pytestmark = pytest.mark.gpu
+
+
+def run_operators():
+    """name -> tuple of arrays / numbers, on the clouds the operators' own tests draw from their seeds"""
+    out = {}
+    rng = np.random.default_rng(1)
+    p = rng.uniform(-20, 20, (100_003, 3))
+    n = rng.normal(size=p.shape)
+    out["crop"] = co.crop(co.croppingVolumeFactory("MinMaxRadius", 5.0, 15.0, centre=(1.0, -2.0, 0.5)), p, n)
+    rng = np.random.default_rng(2)
+    p = rng.uniform(-6, 6, (120_000, 3))
+    n = rng.normal(size=p.shape)
+    n /= np.linalg.norm(n, axis=1, keepdims=True)
+    out["voxelize_within_crop"] = co.voxelizeWithinCroppingVolume(0.25, co.croppingVolumeFactory("MaxRadius", 4.0, centre=(0.5, 0.0, -0.5)), p, n)
+    out["voxelize"] = co.voxelize(0.25, p, n)      # Open3D's anchor: the minimum bound is a read-back of its own
+
+    src, tgt, tgt_n, T_gt = submap_pair()
+    out["estimate_normals"] = co.estimateNormals(tgt, 1.0, 10, want_neighbours=True)
+    init = syn.perturb_pose(T_gt, 0.1, 2.0, seed=5)
+    r = reg.registration_icp(src, tgt, tgt_n, 1.0, init)
+    assert r.iterations > 3
+    out["registration_icp"] = (r.transformation, r.fitness, r.inlier_rmse, r.correspondences, r.iterations)
+
+    src, tgt, tgt_n, T_gt = submap_pair(6000, 9000)
+    T = syn.make_T(None, np.array([7.0, -3.0, 0.0])) @ syn.perturb_pose(T_gt, 0.2, 3.0, seed=9)
+    gs, gt = reg.compute_indices_of_overlapping_points(src, tgt, T, 0.5, 1)
+    assert 0 < len(gs) < len(src) and 0 < len(gt) < len(tgt)
+    out["overlap_indices"] = (gs, gt)
+    # the selection inside a refinement between resident submaps, with reserved work memory: selections and bounds travel with the counts
+    big = co.croppingVolumeFactory("MaxRadius", 1.0e6)
+    a, b = Submap(0.0, big), Submap(0.0, big)
+    nudge = syn.make_T(None, np.array([0.25, 0.0, 0.0]))
+    a.insertScan(src - np.array([0.25, 0.0, 0.0]), np.tile([0.0, 0.0, 1.0], (len(src), 1)), nudge)
+    b.insertScan(tgt - np.array([0.25, 0.0, 0.0]), tgt_n, nudge)
+    reg.reserve(len(src), len(tgt))
+    try:
+        res, info, n_ov = reg.registration_icp_submaps_overlap(a, b, 1.0, syn.make_T(None, np.array([5.0, 0.0, 0.0])) @ T_gt, 2.0)
+    finally:
+        reg.release()
+    assert 0 < n_ov[0] < len(src)
+    out["overlap_refinement"] = (res.transformation, res.fitness, res.inlier_rmse, res.correspondences, res.iterations, info, np.array(n_ov))
+
+    # the outbound leg of test_gpu_submap's merge trajectory: scans that stay inside the volume, so every insert after the first merges
+    m = Submap(0.15, co.croppingVolumeFactory("MaxRadius", 9.0, 0.0, 0.0))
+    world = syn.make_world(9000.0, seed=5)
+    for k, x in enumerate([-8.0, -5.0, -2.0, 1.0, 4.0, 7.0]):
+        T = syn.make_T(syn.rot_axis_angle([0, 0, 1], 0.2 * k), np.array([x, 0.5, 1.5]))
+        sp, sn = syn.make_scan(world, 15000, T, radius=8.0, sigma=0.01, seed=400 + k)
+        assert m.insertScan(sp.astype(np.float64), sn.astype(np.float64), T)
+    out["submap_insert"] = m.getMapPointCloud()
+    return out, m.insert_stats()
+
+
+def same_bits(a, b):
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(same_bits(x, y) for x, y in zip(a, b))
+    if a is None or b is None:
+        return a is None and b is None
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def test_posted_and_copied_answers_are_the_same_bits(monkeypatch, hooks_lib):
+    monkeypatch.delenv("O3S_NO_MAILBOX", raising=False)
+    monkeypatch.delenv("O3S_NO_HINT", raising=False)
+    monkeypatch.delenv("O3S_HINT_MISS", raising=False)
+    posted, stats_posted = run_operators()
+    monkeypatch.setenv("O3S_NO_MAILBOX", "1")
+    copied, stats_copied = run_operators()
+    assert posted.keys() == copied.keys()
+    for name in posted:
+        assert same_bits(posted[name], copied[name]), name
+    # the switch was seen, in the same process and after the posts: a merge insert needs the mailbox, the measuring path does not
+    assert stats_posted[0] >= 1
+    assert stats_copied[0] == 0
