@@ -103,8 +103,9 @@ int o3s_estimate_normals(int device, const double* pts, int64_t N, double radius
  *                                 step of Submap::computeFeatures                    O3S/src/Submap.cpp:268-272
  *   o3s_feature_correspondences   the head of RegistrationRANSACBasedOnFeatureMatching(source, target, source feature, target
  *                                 feature, mutual_filter, ..., ransac_n, ...)         O3S/src/PlaceRecognition.cpp:81-84
- * The RANSAC loop over the correspondence set (RegistrationRANSACBasedOnCorrespondence) is not here: the set returned is what
- * a host implementation of it takes.  The same on resident submaps: o3s_submap.h (o3s_submap_compute_features).
+ * The RANSAC loop over the correspondence set (RegistrationRANSACBasedOnCorrespondence) takes the set returned here: it is in
+ * o3s_registration.h (o3s_registration_ransac_correspondence; o3s_registration_ransac_feature_matching chains the two).  The
+ * same on resident submaps: o3s_submap.h (o3s_submap_compute_features, o3s_submap_registration_ransac).
  *
  * Open3D is not part of the reference tree; parity is against a restatement of its published source (tests/fpfh_ref.py),
  * written from the contract below.  All arithmetic is IEEE fp64 without FMA contraction; dot(a, b) = (ax bx + ay by) + az bz,

@@ -124,6 +124,86 @@ int o3s_o3d_registration_reserve(int device, int64_t max_source_points, int64_t 
 int o3s_o3d_registration_reserve_n(int device, int64_t max_source_points, int64_t max_target_points, int32_t count);
 int o3s_o3d_registration_release(int device);
 
+/* ---- RANSAC ---------------------------------------------------------------------------------------------------------------
+ * RegistrationRANSACBasedOnCorrespondence / RegistrationRANSACBasedOnFeatureMatching (O3S/src/PlaceRecognition.cpp:81-84) with
+ * TransformationEstimationPointToPoint(false), CorrespondenceCheckerBasedOnEdgeLength and CorrespondenceCheckerBasedOnDistance,
+ * restated from Open3D's published source and made DETERMINISTIC: a counter-based sample stream and serial-order semantics, so the
+ * result does not depend on how the device batches the work.  fp64, no FMA contraction.
+ *
+ * Inputs: source 3 x Ns, target 3 x Nt, correspondences 2 x K int32 (source index, target index), o3s_ransac_params.  An empty
+ * result (identity, fitness 0, rmse 0, best_iteration -1) comes back when ransac_n < 3, K < ransac_n or
+ * max_correspondence_distance <= 0, as in Open3D.  ransac_n > 8 is O3S_ERR_BAD_ARGUMENT.
+ *
+ * Iteration itr (0-based) is fully defined by (seed, itr):
+ *  1. Sample.  ransac_n correspondence indices from Philox4x32-10: key (seed low word, seed high word), counter (itr low, itr
+ *     high, j / 4, 0), index j = (word[j mod 4] * K) >> 32.  With an explicit sample table (H x ransac_n int32, row-major) row itr
+ *     is used instead and the loop runs over min(max_iteration, H) iterations.  A sample with a repeated index is SKIPPED: the one
+ *     deliberate deviation from Open3D, which draws with replacement — such a sample defines no rigid motion, and umeyama on it
+ *     returns a rotation that depends on the SVD implementation.
+ *  2. Edge-length check.  For every pair a < b of the sample, ds = |s_a - s_b|, dt = |t_a - t_b|: ds >= dt * similarity and
+ *     dt >= ds * similarity.  It does not depend on T and runs before the estimation.
+ *  3. Estimate.  T = Eigen::umeyama(source sample, target sample, false): the means, sigma = (1/n) sum (t - mt)(s - ms)^T, its SVD
+ *     U S V^T, S(2) = -1 when det U det V < 0, R = U S V^T, t = mt - R ms.
+ *  4. Distance check.  |T s_j - t_j| <= distance_threshold for every pair of the sample.
+ *  5. Evaluate, over all K correspondences in ascending index: p = R s + t with each row as ((r0 sx + r1 sy) + r2 sz) + t,
+ *     d = sqrt((dx dx + dy dy) + dz dz); the pair is an inlier when d < max_correspondence_distance; n_in counts them.  err2 sums
+ *     d * d over the inliers in this fixed order: within each chunk of 512 consecutive correspondences ([0, 512), [512, 1024), ...)
+ *     sequentially from 0.0 in ascending index, then the chunk sums added sequentially from 0.0 in ascending chunk order.
+ *     fitness = n_in / K, rmse = sqrt(err2 / n_in), 0 when n_in is 0.
+ *  6. Select with serial semantics.  est_k = max_iteration and an empty best (fitness 0, rmse 0) to start with; iterations are
+ *     considered in ascending itr and the loop ends at the first itr >= est_k.  An iteration that passed the checkers replaces the
+ *     best when its fitness is larger, or equal with a smaller rmse; on replacement e = log(1 - confidence) /
+ *     log(1 - r^ransac_n) with r = n_in / K and r^n = ((r r) r) ..., and est_k = ceil(e) if e < est_k.  confidence = 1.0 never stops
+ *     early, r = 1 stops at once.  This is what Open3D computes on one thread; the device returns exactly this for any batch size and
+ *     any number of batches in flight.
+ *  7. Result: the winner's transformation, fitness, rmse, its inlier pairs in ascending order (optional), the winning itr, the final
+ *     est_k and the number of hypotheses evaluated (checker-passing iterations the serial loop reached). */
+typedef struct o3s_ransac_params {
+  double max_correspondence_distance; /* 0.75  ransac_max_correspondence_dist */
+  int32_t ransac_n;                   /* 3     ransac_model_size (3 .. 8) */
+  double distance_threshold;          /* 0.8   CorrespondenceCheckerBasedOnDistance */
+  double edge_length_similarity;      /* 0.6   CorrespondenceCheckerBasedOnEdgeLength */
+  int32_t check_distance;             /* 1; 0 switches the checker off */
+  int32_t check_edge_length;          /* 1; 0 switches the checker off */
+  int32_t max_iteration;              /* 10 000 000  ransac_num_iter */
+  double confidence;                  /* 0.999       ransac_probability (0 .. 1) */
+  uint64_t seed;                      /* 0 */
+} o3s_ransac_params;
+typedef struct o3s_ransac_result {
+  double transformation[16]; /* Eigen::Matrix4d::data() order */
+  double fitness;
+  double inlier_rmse;
+  int64_t correspondences; /* n_in of the winner = correspondence_set_.size() */
+  int64_t best_iteration;  /* the winning itr; -1: the empty result */
+  int64_t est_k;           /* the final est_k */
+  int64_t evaluated;       /* hypotheses evaluated */
+} o3s_ransac_result;
+void o3s_ransac_default_params(o3s_ransac_params* p);
+/* samples (nullable): n_samples x ransac_n int32, each in [0, K).  inlier_correspondences (nullable): 2 x K int32. */
+int o3s_registration_ransac_correspondence(int device, const double* source, int64_t Ns, const double* target, int64_t Nt,
+                                           const int32_t* correspondences, int64_t K, const o3s_ransac_params* params,
+                                           const int32_t* samples, int64_t n_samples, o3s_ransac_result* result,
+                                           int32_t* inlier_correspondences);
+/* o3s_feature_correspondences (dim x N features, o3s_cloud_ops.h) chained into the above.  inlier_correspondences (nullable):
+ * 2 x Ns int32; n_correspondences (nullable): K, the size of the correspondence set. */
+int o3s_registration_ransac_feature_matching(int device, const double* source, int64_t Ns, const double* target, int64_t Nt,
+                                             const double* source_feature, const double* target_feature, int32_t dim,
+                                             int32_t mutual_filter, const o3s_ransac_params* params, o3s_ransac_result* result,
+                                             int32_t* inlier_correspondences, int64_t* n_correspondences);
+/* Steps 1 - 5 for H hypotheses, nothing selected: rows 0 .. H - 1 of `samples`, or (samples NULL) the Philox draws of iterations
+ * first_iteration .. first_iteration + H - 1.  Per hypothesis: outcome (0 passed, 1 repeated index, 2 edge-length check failed,
+ * 3 distance check failed), the transformation (16 doubles, Eigen order; estimated for outcomes 0 and 3, else zero rotation),
+ * and for outcome 0 n_in and err2 (0 otherwise).  transformations, n_in, err2 are nullable. */
+int o3s_ransac_evaluate_samples(int device, const double* source, int64_t Ns, const double* target, int64_t Nt,
+                                const int32_t* correspondences, int64_t K, const o3s_ransac_params* params, const int32_t* samples,
+                                int64_t first_iteration, int64_t H, int32_t* outcome, double* transformations, int64_t* n_in,
+                                double* err2);
+/* The work area of the RANSAC entries (o3s_submap_registration_ransac included): leased per call from a pool per device and grown on
+ * demand; o3s_ransac_reserve sizes one for up to max_correspondences ahead of time, so that repeated closures do not allocate;
+ * o3s_ransac_release returns the device's idle areas to the allocator. */
+int o3s_ransac_reserve(int device, int64_t max_correspondences);
+int o3s_ransac_release(int device);
+
 #ifdef __cplusplus
 }
 #endif

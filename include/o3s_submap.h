@@ -219,6 +219,16 @@ int o3s_submap_download_features(const o3s_submap* m, double* sparse_pts, double
 /* o3s_feature_correspondences between two resident feature sets on one device (out_pairs: 2 x features_size(source)) */
 int o3s_submap_feature_correspondences(const o3s_submap* source, const o3s_submap* target, int32_t mutual_filter,
                                        int32_t ransac_n, int32_t* out_pairs, int64_t* n_out, int32_t* used_fallback);
+/* RegistrationRANSACBasedOnFeatureMatching (O3S/src/PlaceRecognition.cpp:81-84) between two RESIDENT feature sets on one device:
+ * o3s_submap_feature_correspondences chained into the RANSAC of o3s_registration.h ("RANSAC": the contract) on the two sparse
+ * clouds, on the source's stream.  Neither cloud and neither feature set leaves HBM; what crosses the bus is the two nearest-
+ * neighbour index arrays of the mutual filter (4 bytes per sparse point), the pairs going back up, and the result.
+ * inlier_correspondences (nullable): 2 x features_size(source) int32, the winner's inlier pairs in ascending order
+ * (result->correspondences of them); n_correspondences (nullable): K, the size of the correspondence set the RANSAC ran on.
+ * O3S_ERR_NOT_INITIALIZED when either submap has no feature set; submaps on two devices: O3S_ERR_BAD_ARGUMENT. */
+int o3s_submap_registration_ransac(const o3s_submap* source, const o3s_submap* target, int32_t mutual_filter,
+                                   const o3s_ransac_params* params, o3s_ransac_result* result,
+                                   int32_t* inlier_correspondences, int64_t* n_correspondences);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,8 @@
 //              282-286), it is queued as finished, an adjacency edge is added, the buffer is replayed into the new one
 //   computeFeatures(idx): Submap::computeFeatures (Submap.cpp:255-275) of a submap on the device (o3s_submap_compute_features);
 //              the caller keeps the reference's timer (minSecondsBetweenFeatureComputation_) and decides when to call it.
-// Not here: the RANSAC of place recognition / pose-graph transforms of finished submaps (host work, out of scope).
+// Not here: candidate selection and the pose-graph transforms of finished submaps (host policy).  The RANSAC of place recognition
+//              between two submaps of the collection is o3s_submap_registration_ransac (o3s_submap.h) on their feature sets.
 // The scans the buffer keeps are resident o3s_scan objects: the caller hands over the scan it has just pre-processed and
 // gets another one to fill next (a ring of numScansOverlap_ + 1 handles, nothing is copied).
 #pragma once

@@ -48,6 +48,51 @@ class RegistrationResult:
     iterations: int
 
 
+class _RansacParams(C.Structure):
+    _fields_ = [("max_correspondence_distance", C.c_double), ("ransac_n", C.c_int32), ("distance_threshold", C.c_double),
+                ("edge_length_similarity", C.c_double), ("check_distance", C.c_int32), ("check_edge_length", C.c_int32),
+                ("max_iteration", C.c_int32), ("confidence", C.c_double), ("seed", C.c_uint64)]
+
+
+class _RansacResult(C.Structure):
+    _fields_ = [("transformation", C.c_double * 16), ("fitness", C.c_double), ("inlier_rmse", C.c_double), ("correspondences", C.c_int64),
+                ("best_iteration", C.c_int64), ("est_k", C.c_int64), ("evaluated", C.c_int64)]
+
+
+@dataclass
+class RansacParams:
+    """o3s_ransac_params; the defaults are the reference's (param_robosense_rs16.lua place_recognition: ransac_max_correspondence_dist,
+    ransac_model_size, the two checkers of PlaceRecognition.cpp, ransac_num_iter, ransac_probability)."""
+    max_correspondence_distance: float = 0.75
+    ransac_n: int = 3
+    distance_threshold: float = 0.8
+    edge_length_similarity: float = 0.6
+    check_distance: bool = True
+    check_edge_length: bool = True
+    max_iteration: int = 10_000_000
+    confidence: float = 0.999
+    seed: int = 0
+
+    def to_c(self) -> _RansacParams:
+        return _RansacParams(float(self.max_correspondence_distance), int(self.ransac_n), float(self.distance_threshold),
+                             float(self.edge_length_similarity), int(bool(self.check_distance)), int(bool(self.check_edge_length)),
+                             int(self.max_iteration), float(self.confidence), int(self.seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+@dataclass
+class RansacResult:
+    """Open3D's RegistrationResult of a RANSAC (transformation_, fitness_, inlier_rmse_, correspondence_set_) and the deterministic
+    loop's account of itself: the winning iteration (-1: the empty result), the final est_k, the hypotheses evaluated."""
+    transformation: np.ndarray
+    fitness: float
+    inlier_rmse: float
+    correspondence_set: np.ndarray
+    best_iteration: int
+    est_k: int
+    evaluated: int
+    n_correspondences: int = 0   # K, the size of the correspondence set the RANSAC ran on
+
+
 
 
 def _L():
@@ -65,6 +110,15 @@ def _L():
                                                      C.POINTER(C.c_int32)]
         ip = C.POINTER(C.c_int32)
         L.o3s_feature_correspondences.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, ip, C.POINTER(C.c_int64), ip]
+        rp, rr, lp = C.POINTER(_RansacParams), C.POINTER(_RansacResult), C.POINTER(C.c_int64)
+        L.o3s_ransac_default_params.argtypes = [rp]
+        L.o3s_ransac_default_params.restype = None
+        L.o3s_registration_ransac_correspondence.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, ip, C.c_int64, rp, ip, C.c_int64, rr, ip]
+        L.o3s_registration_ransac_feature_matching.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, dp, dp, C.c_int32, C.c_int32, rp, rr, ip, lp]
+        L.o3s_ransac_evaluate_samples.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, ip, C.c_int64, rp, ip, C.c_int64, C.c_int64, ip, dp, lp, dp]
+        L.o3s_ransac_reserve.argtypes = [C.c_int, C.c_int64]
+        L.o3s_ransac_release.argtypes = [C.c_int]
+        L.o3s_submap_registration_ransac.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, rp, rr, ip, lp]
     return L
 
 
@@ -359,3 +413,140 @@ def release(device: int = 0):
     rc = L.o3s_o3d_registration_release(int(device))
     if rc != _lib.OK:
         raise RuntimeError(f"o3s_o3d_registration_release failed with o3s_status {rc}")
+
+
+# ---- RANSAC on feature correspondences (include/o3s_registration.h, "RANSAC": the contract) ------------------------------------
+def _ip(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _ransac_result(r, inl, k) -> RansacResult:
+    n = int(r.correspondences)
+    return RansacResult(np.array(r.transformation).reshape(4, 4).T.copy(), r.fitness, r.inlier_rmse, inl[:n].copy(), int(r.best_iteration),
+                        int(r.est_k), int(r.evaluated), int(k))
+
+
+def _ransac_params(params) -> _RansacParams:
+    return (RansacParams() if params is None else params).to_c()
+
+
+def default_ransac_params() -> RansacParams:
+    """o3s_ransac_default_params."""
+    c = _RansacParams()
+    _L().o3s_ransac_default_params(C.byref(c))
+    return RansacParams(c.max_correspondence_distance, c.ransac_n, c.distance_threshold, c.edge_length_similarity, bool(c.check_distance),
+                        bool(c.check_edge_length), c.max_iteration, c.confidence, c.seed)
+
+
+def registration_ransac_based_on_correspondence(source, target, corres, params: RansacParams = None, samples=None, device: int = 0) -> RansacResult:
+    """RegistrationRANSACBasedOnCorrespondence(source, target, corres, max_correspondence_distance, TransformationEstimationPointToPoint(false),
+    ransac_n, {edge length, distance}, RANSACConvergenceCriteria(max_iteration, confidence)), deterministic in (seed, iteration).
+    corres: K x 2 int32 (source index, target index); samples (optional): H x ransac_n rows used instead of the Philox draws."""
+    s_ = np.ascontiguousarray(source, np.float64)
+    t_ = np.ascontiguousarray(target, np.float64)
+    c_ = np.ascontiguousarray(corres, np.int32).reshape(-1, 2)
+    prm = _ransac_params(params)
+    tab = None if samples is None else np.ascontiguousarray(samples, np.int32).reshape(-1, max(int(prm.ransac_n), 1))
+    inl = np.zeros((max(c_.shape[0], 1), 2), np.int32)
+    r = _RansacResult()
+    rc = _L().o3s_registration_ransac_correspondence(device, _d(s_), s_.shape[0], _d(t_), t_.shape[0], _ip(c_), c_.shape[0], C.byref(prm), _ip(tab),
+                                                     0 if tab is None else tab.shape[0], C.byref(r), _ip(inl))
+    if rc == _lib.ERR_BAD_ARGUMENT:
+        raise ValueError("o3s_registration_ransac_correspondence: bad argument (ransac_n <= 8, confidence in [0, 1], indices within the clouds)")
+    if rc != _lib.OK:
+        raise RuntimeError(f"o3s_registration_ransac_correspondence failed with o3s_status {rc}")
+    return _ransac_result(r, inl, c_.shape[0])
+
+
+def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature, mutual_filter: bool = True,
+                                                  params: RansacParams = None, device: int = 0) -> RansacResult:
+    """RegistrationRANSACBasedOnFeatureMatching (PlaceRecognition.cpp:81-84): featureCorrespondences chained into the RANSAC above.
+    Features are N x dim arrays (row i = feature column i)."""
+    s_ = np.ascontiguousarray(source, np.float64)
+    t_ = np.ascontiguousarray(target, np.float64)
+    a = np.ascontiguousarray(source_feature, np.float64)
+    b = np.ascontiguousarray(target_feature, np.float64)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1] or a.shape[0] != s_.shape[0] or b.shape[0] != t_.shape[0]:
+        raise ValueError("features must be N x dim arrays of one dim, one row per point")
+    prm = _ransac_params(params)
+    inl = np.zeros((max(s_.shape[0], 1), 2), np.int32)
+    r, k = _RansacResult(), C.c_int64(0)
+    rc = _L().o3s_registration_ransac_feature_matching(device, _d(s_), s_.shape[0], _d(t_), t_.shape[0], _d(a), _d(b), a.shape[1],
+                                                       int(bool(mutual_filter)), C.byref(prm), C.byref(r), _ip(inl), C.byref(k))
+    if rc == _lib.ERR_BAD_ARGUMENT:
+        raise ValueError("o3s_registration_ransac_feature_matching: bad argument")
+    if rc != _lib.OK:
+        raise RuntimeError(f"o3s_registration_ransac_feature_matching failed with o3s_status {rc}")
+    return _ransac_result(r, inl, k.value)
+
+
+def ransac_evaluate_samples(source, target, corres, params: RansacParams = None, samples=None, first_iteration: int = 0, count: int = None,
+                            device: int = 0):
+    """Steps 1 - 5 of the contract for given sample rows (H x ransac_n), or for the Philox draws of iterations first_iteration ..
+    first_iteration + count - 1: (outcome H int32: 0 passed, 1 repeated index, 2 edge-length, 3 distance; T H x 4 x 4; n_in H; err2 H)."""
+    s_ = np.ascontiguousarray(source, np.float64)
+    t_ = np.ascontiguousarray(target, np.float64)
+    c_ = np.ascontiguousarray(corres, np.int32).reshape(-1, 2)
+    prm = _ransac_params(params)
+    tab = None if samples is None else np.ascontiguousarray(samples, np.int32).reshape(-1, max(int(prm.ransac_n), 1))
+    H = int(count) if tab is None else tab.shape[0]
+    out = np.zeros(max(H, 1), np.int32)
+    T = np.zeros((max(H, 1), 16))
+    n_in = np.zeros(max(H, 1), np.int64)
+    err2 = np.zeros(max(H, 1))
+    rc = _L().o3s_ransac_evaluate_samples(device, _d(s_), s_.shape[0], _d(t_), t_.shape[0], _ip(c_), c_.shape[0], C.byref(prm), _ip(tab),
+                                          int(first_iteration), H, _ip(out), _d(T), n_in.ctypes.data_as(C.POINTER(C.c_int64)), _d(err2))
+    if rc == _lib.ERR_BAD_ARGUMENT:
+        raise ValueError("o3s_ransac_evaluate_samples: bad argument")
+    if rc != _lib.OK:
+        raise RuntimeError(f"o3s_ransac_evaluate_samples failed with o3s_status {rc}")
+    return out[:H], T[:H].reshape(H, 4, 4).transpose(0, 2, 1).copy(), n_in[:H], err2[:H]
+
+
+def ransac_reserve(max_correspondences: int, device: int = 0):
+    """o3s_ransac_reserve: sizes one RANSAC work area ahead of time, so that closures up to that many correspondences do not allocate."""
+    rc = _L().o3s_ransac_reserve(int(device), int(max_correspondences))
+    if rc != _lib.OK:
+        raise RuntimeError(f"o3s_ransac_reserve failed with o3s_status {rc}")
+
+
+def ransac_release(device: int = 0):
+    rc = _L().o3s_ransac_release(int(device))
+    if rc != _lib.OK:
+        raise RuntimeError(f"o3s_ransac_release failed with o3s_status {rc}")
+
+
+@dataclass
+class LoopClosureConstraint:
+    """What PlaceRecognition::buildLoopClosureConstraints keeps of an accepted pair (Constraint: sourceToTarget_, informationMatrix_),
+    or why the pair was rejected (`rejected`: None when accepted)."""
+    rejected: str = None
+    source_to_target: np.ndarray = None
+    information_matrix: np.ndarray = None
+    ransac: RansacResult = None
+    refinement: RegistrationResult = None
+    n_overlap: tuple = None
+
+
+def loop_closure_constraint(source_submap, target_submap, ransac_params: RansacParams = None, mutual_filter: bool = True,
+                            ransac_min_correspondence_set_size: int = 25, max_icp_correspondence_distance: float = 0.3,
+                            overlap_voxel_size: float = None, min_refinement_fitness: float = 0.7, registration_type: str = "GeneralizedIcp",
+                            gicp_epsilon: float = 1e-3, max_iteration: int = 30) -> LoopClosureConstraint:
+    """One candidate pair of PlaceRecognition::buildLoopClosureConstraints (PlaceRecognition.cpp:78-152) on two resident submaps with
+    feature sets: RANSAC on the feature correspondences, the ransac_min_corresondence_set_size gate, overlap selection at the RANSAC
+    pose and refinement with the chosen registration type, the min_refinement_fitness gate, the information matrix.
+    overlap_voxel_size: magic::voxelExpansionFactorOverlapComputation x the map voxel size (the caller's; required).
+    isRegistrationConsistent and the choice of candidates are host policy and stay with the caller."""
+    if overlap_voxel_size is None:
+        raise ValueError("overlap_voxel_size is required (voxelExpansionFactorOverlapComputation x map voxel size)")
+    rr = source_submap.ransacRegistration(target_submap, ransac_params, mutual_filter)
+    if len(rr.correspondence_set) < ransac_min_correspondence_set_size:
+        return LoopClosureConstraint(rejected=f"ransac: {len(rr.correspondence_set)} correspondences", ransac=rr)
+    res, info, n_ov = registration_icp_submaps_overlap(source_submap, target_submap, max_icp_correspondence_distance, rr.transformation,
+                                                       overlap_voxel_size, 1, max_iteration=max_iteration, with_information=True,
+                                                       registration_type=registration_type, gicp_epsilon=gicp_epsilon)
+    if res is None:
+        return LoopClosureConstraint(rejected="refinement: empty overlap", ransac=rr, n_overlap=n_ov)
+    if res.fitness < min_refinement_fitness:
+        return LoopClosureConstraint(rejected=f"refinement score: {res.fitness}", ransac=rr, refinement=res, n_overlap=n_ov)
+    return LoopClosureConstraint(None, res.transformation, info, rr, res, n_ov)

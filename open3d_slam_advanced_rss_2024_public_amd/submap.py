@@ -250,6 +250,25 @@ class Submap:
                     "o3s_submap_feature_correspondences")
         return pairs[:n_out.value].copy(), bool(fb.value)
 
+    def ransacRegistration(self, target: "Submap", params=None, mutual_filter: bool = True):
+        """RegistrationRANSACBasedOnFeatureMatching (PlaceRecognition.cpp:81-84) between this submap's resident feature set (source)
+        and `target`'s: registration.RansacResult, with neither cloud nor feature set leaving HBM (o3s_submap_registration_ransac)."""
+        from . import registration as reg
+
+        reg._L()   # binds the argtypes on the library in use
+        n = self.features_size()
+        if n < 0 or target.features_size() < 0:
+            raise RuntimeError("both submaps need features: call computeFeatures first")
+        prm = reg._ransac_params(params)
+        inl = np.zeros((max(n, 1), 2), np.int32)
+        r, k = reg._RansacResult(), C.c_int64(0)
+        self._lib.o3s_submap_registration_ransac.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(reg._RansacParams),
+                                                             C.POINTER(reg._RansacResult), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        self._check(self._lib.o3s_submap_registration_ransac(self._h, target._h, int(bool(mutual_filter)), C.byref(prm), C.byref(r),
+                                                             inl.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(k)),
+                    "o3s_submap_registration_ransac")
+        return reg._ransac_result(r, inl, k.value)
+
     def setMapPointCloud(self, points, normals):
         p = np.ascontiguousarray(points, np.float64)
         n = None if normals is None else np.ascontiguousarray(normals, np.float64)
