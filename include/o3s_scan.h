@@ -10,6 +10,9 @@
  *                               + scanMatcherCropper_(identity pose)->crop(wide)  ScanToMapRegistration.cpp:62-64
  *   o3s_scan_set_reading        open3dToPointmatcher(*processed.match_) -> reading of icp_.compute   O3S/src/Mapper.cpp:307-309, 393
  *   o3s_submap_insert_processed submaps_->insertScan(rawScan, *processed.merge_, mapToRangeSensor_)   O3S/src/Mapper.cpp:487
+ *   o3s_raw_scan_undistort      ConstantVelocityMotionCompensation::undistortInputPointCloud          O3S/src/MotionCompensation.cpp:73-127
+ *   o3s_motion_from_poses       ...::estimateLinearAndAngularVelocity (host arithmetic only)          MotionCompensation.cpp:32-66
+ *   o3s_scan_registration_icp   cloudRegistration_->registerClouds(cloudPrev_, *preProcessed, I)      O3S/src/Odometry.cpp:53
  *
  * A cloud that carries normals keeps them (RegistrationIcpPointToPlane::estimateNormalsOrCovariancesIfNeeded returns
  * early, O3S/src/CloudRegistration.cpp:63-67); for a cloud without normals they are estimated on the voxelised wide cloud
@@ -55,6 +58,26 @@ int o3s_raw_scan_create(int device, o3s_raw_scan** out);
 void o3s_raw_scan_destroy(o3s_raw_scan* r);
 int o3s_raw_scan_upload(o3s_raw_scan* r, const double* pts, const double* normals, int64_t N);
 int64_t o3s_raw_scan_size(const o3s_raw_scan* r);
+/* Constant-velocity de-skew of a spinning-LiDAR sweep: ConstantVelocityMotionCompensation::undistortInputPointCloud
+ * (O3S/src/MotionCompensation.cpp:73-127).  Per point, in fp64: angle = atan2(y, x), wrapped into [0, 2 pi); phase = 0 where the
+ * wrapped angle is 0, else 1 - angle / 2 pi (clockwise) or angle / 2 pi; s = phase * scan_duration;
+ * q = yaw(s w_z) * pitch(s w_y) * roll(s w_x) (math.cpp:32-37), normalised; p' = R(q) p + s v.  Only the points are rewritten
+ * (normals and colours stay, as in the reference).  With all six velocity components zero nothing is launched (the result is p). */
+typedef struct o3s_motion {          /* what the per-point loop of MotionCompensation.cpp:91-109 reads */
+  double linear_velocity[3];         /* m/s, sensor frame */
+  double angular_velocity_rpy[3];    /* rad/s */
+  double scan_duration;              /* > 0 (assert_gt in setParameters); else O3S_ERR_BAD_ARGUMENT */
+  int32_t is_spinning_clockwise;
+  int32_t reserved[3];
+} o3s_motion;
+/* In place on the staged sweep, on r's stream; call it before o3s_scan_preprocess_staged.  Returns when the sweep is rewritten. */
+int o3s_raw_scan_undistort(o3s_raw_scan* r, const o3s_motion* m);
+/* The same on host buffers of N points (3 doubles each); out may alias pts.  N == 0 is O3S_OK. */
+int o3s_undistort_cloud(int device, const o3s_motion* m, const double* pts, int64_t N, double* out);
+/* estimateLinearAndAngularVelocity (MotionCompensation.cpp:32-66) for start / finish already taken from the buffer:
+ * dT = start^-1 * finish, dt = t_finish - t_start; dt > 0: v = dT.t / (dt + 1e-6), w = toRPY(quat(dT.R).normalized()) / (dt + 1e-6)
+ * (math.hpp:30-42); dt <= 0: zeros.  Fills only the two velocity arrays of *m.  No device call. */
+int o3s_motion_from_poses(const double T_start[16], double t_start, const double T_finish[16], double t_finish, o3s_motion* m);
 int o3s_scan_preprocess_staged(o3s_scan* s, const o3s_cropper* map_builder_cropper, double voxel_size,
                                const o3s_cropper* scan_matcher_cropper, const o3s_raw_scan* raw, int64_t* n_merge,
                                int64_t* n_match);
@@ -69,6 +92,13 @@ int64_t o3s_scan_get(const o3s_scan* s, int which, double* pts, double* normals)
 /* The match cloud becomes the ICP handle's resident reading (o3s_icp_set_reading_dev); run o3s_icp_compute_resident
  * afterwards.  The scan object must stay alive (and unchanged) until that compute has returned. */
 int o3s_scan_set_reading(o3s_scan* s, o3s_icp* icp);
+/* CloudRegistration::registerClouds (CloudRegistration.cpp:16-21, 57-61, 88-93) on two RESIDENT pre-processed scans of one device
+ * (LidarOdometry::addRangeScan, Odometry.cpp:53); which: 0 merge, 1 match (as o3s_scan_get).  Exactly what
+ * o3s_o3d_registration_icp_ex returns on the downloaded clouds, with its status codes; scans on different devices are
+ * O3S_ERR_BAD_ARGUMENT, an empty cloud is O3S_ERR_EMPTY_REFERENCE.  Blocking: both scans may be refilled when it returns. */
+int o3s_scan_registration_icp(const o3s_scan* source, int source_which, const o3s_scan* target, int target_which,
+                              double max_correspondence_distance, const double init[16], const o3s_o3d_estimation* est,
+                              const o3s_o3d_icp_criteria* criteria, o3s_o3d_icp_result* result);
 /* Submap::insertScan with the resident merge cloud (no host copy).
  * Completion may be PENDING when this returns (round 5): the whole insert is enqueued on the submap's stream and its counts are on
  * their way to the host, but nobody has waited for them — the mapping thread goes on (hands the pose out, takes the next sweep) while

@@ -4,5 +4,7 @@ from .icp import (ICP, IcpConfig, IcpStats, ConvergenceError, TransformationErro
 from .dense_map import DenseMap  # noqa: F401
 from .submap import ProcessedScan, Submap  # noqa: F401
 from .submap_collection import SubmapCollection  # noqa: F401
+from .odometry import ConstantVelocityMotionCompensation, LidarOdometry, RawScan, TransformBuffer  # noqa: F401
 
-__all__ = ["ICP", "IcpConfig", "IcpStats", "ConvergenceError", "TransformationError", "InvalidModuleType", "HipError", "compute_batch", "Submap", "ProcessedScan", "SubmapCollection", "DenseMap"]
+__all__ = ["ICP", "IcpConfig", "IcpStats", "ConvergenceError", "TransformationError", "InvalidModuleType", "HipError", "compute_batch", "Submap", "ProcessedScan", "SubmapCollection", "DenseMap", "LidarOdometry",
+           "ConstantVelocityMotionCompensation", "TransformBuffer", "RawScan"]

@@ -22,6 +22,8 @@
 //   :440-455      isNewValueSetMapper_: adopt the GIVEN pose, skip this scan's result and the insert, ignore odometry next time
 //   :465-479      initial-map mode: no merging (or not before mapMergeDelayInSeconds_)
 //   :483-489      insert the merge cloud if the sensor moved at least minMovementBetweenMappingSteps_
+//   :190, 228, 450, 460   mapToRangeSensorBuffer_.push: the registered poses, which motionCompensationMap_ reads
+//                 (SlamWrapper.cpp:445-447, 671: undistortInputPointCloud before the mapper sees the sweep) -> enableMotionCompensation
 // 4x4 matrices are column-major doubles (Eigen::Matrix4d::data()).  Isometry products / inverses are restated as plain
 // k = 0..3 accumulations (Eigen is not part of the tree: its evaluation order is not pinned).
 #pragma once
@@ -30,50 +32,17 @@
 #include <cmath>
 #include <cstdint>
 #include <map>
+#include <memory>
 #include <stdexcept>
 #include <string>
 
 #include "o3s_icp.hpp"
+#include "o3s_odometry.hpp"
+#include "o3s_pose.hpp"
 #include "o3s_scan.h"
 #include "o3s_submap_collection.hpp"
 
 namespace o3s {
-
-struct Mat4 {
-  double m[16];
-  static Mat4 identity() {
-    Mat4 r{};
-    r.m[0] = r.m[5] = r.m[10] = r.m[15] = 1.0;
-    return r;
-  }
-  double& operator()(int r, int c) { return m[c * 4 + r]; }
-  double operator()(int r, int c) const { return m[c * 4 + r]; }
-};
-inline Mat4 mul(const Mat4& A, const Mat4& B) {
-  Mat4 C{};
-  for (int c = 0; c < 4; ++c)
-    for (int r = 0; r < 4; ++r) {
-      double s = A(r, 0) * B(0, c);
-      s = s + A(r, 1) * B(1, c);
-      s = s + A(r, 2) * B(2, c);
-      s = s + A(r, 3) * B(3, c);
-      C(r, c) = s;
-    }
-  return C;
-}
-// Eigen::Isometry3d::inverse(): [R^T, -R^T t]
-inline Mat4 inverse_isometry(const Mat4& T) {
-  Mat4 R = Mat4::identity();
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) R(r, c) = T(c, r);
-  for (int r = 0; r < 3; ++r) {
-    double s = R(r, 0) * T(0, 3);
-    s = s + R(r, 1) * T(1, 3);
-    s = s + R(r, 2) * T(2, 3);
-    R(r, 3) = -s;
-  }
-  return R;
-}
 
 // o3d_slam::TransformInterpolationBuffer restricted to what the Mapper asks of it when the odometry is sampled at the
 // scan stamps: has(t), latest_time(), lookup(t) (exact stamp; the interpolation itself is a host utility, out of scope)
@@ -115,7 +84,8 @@ struct MapperParams {
 class MapperHip {
  public:
   MapperHip(const MapperParams& p, const o3s_icp_config& icpCfg, int device = 0)
-      : params_(p), icp_(icpCfg, device), submaps_(p.submaps, p.mapVoxelSize, p.mapBuilderCropper, p.isUseInitialMap, device) {}
+      : params_(p), icp_(icpCfg, device), submaps_(p.submaps, p.mapVoxelSize, p.mapBuilderCropper, p.isUseInitialMap, device), device_(device) {}
+  ~MapperHip() { o3s_raw_scan_destroy(deskewStage_); }
   MapperHip(const MapperHip&) = delete;
   MapperHip& operator=(const MapperHip&) = delete;
 
@@ -139,6 +109,22 @@ class MapperHip {
     isCalibrationSet_ = true;
   }
   bool isCalibrationSet() const { return isCalibrationSet_; }
+  // motion_compensation.is_undistort_scan (off by default): every sweep handed over as host arrays is staged, de-skewed with the
+  // velocities of the registered poses (ConstantVelocityMotionCompensation over getMapToRangeSensorBuffer()) and pre-processed from
+  // the staged copy.  A sweep the caller has staged itself is de-skewed with undistort(staged, stamp) before it is handed over, as
+  // SlamWrapper.cpp:671 does before the mapper sees the cloud; a sweep that arrives pre-processed was de-skewed before that.
+  void enableMotionCompensation(double scanDuration = 0.1, bool isSpinningClockwise = true, int numPosesVelocityEstimation = 3) {
+    motionCompensation_.reset(new ConstantVelocityMotionCompensation(mapToRangeSensorBuffer_, scanDuration, isSpinningClockwise,
+                                                                     numPosesVelocityEstimation));
+  }
+  bool isMotionCompensationEnabled() const { return (bool)motionCompensation_; }
+  o3s_motion undistort(o3s_raw_scan* staged, double timestamp) {
+    if (!motionCompensation_) throw std::runtime_error("undistort: motion compensation is not enabled");
+    lastMotion_ = motionCompensation_->undistort(staged, timestamp);
+    return lastMotion_;
+  }
+  const o3s_motion& lastMotion() const { return lastMotion_; }
+  const TransformBuffer& getMapToRangeSensorBuffer() const { return mapToRangeSensorBuffer_; }
   const MapperTimings& lastTimings() const { return lastTimings_; }
   MapperTimings meanTimings() const {  // Timer::getAvgMeasurementMsec over the scans that ran the stage
     MapperTimings m;
@@ -203,8 +189,9 @@ class MapperHip {
         submaps_.activeSubmap().insertScan(raw.pts, raw.normals, raw.N, mapToRangeSensor_.m);
       } else {
         mapToRangeSensorPrev_ = mapToRangeSensor_;
-        preprocess(raw);
+        preprocess(raw, timestamp);
         submaps_.insertScan(scan_, mapToRangeSensor_.m, timestamp);
+        mapToRangeSensorBuffer_.push(timestamp, mapToRangeSensor_);
         lastInserted_ = true;
       }
       return true;
@@ -214,6 +201,7 @@ class MapperHip {
       const double latest = odomToRangeSensorBuffer_.latest_time();
       const Mat4 motion = mul(inverse_isometry(odomInCloudFrame(lastMeasurementTimestamp_)), odomInCloudFrame(latest));
       mapToRangeSensor_ = mul(mapToRangeSensorPrev_, motion);
+      mapToRangeSensorBuffer_.push(latest, mapToRangeSensor_);
       mapToRangeSensorPrev_ = mapToRangeSensor_;
       return true;
     }
@@ -230,7 +218,7 @@ class MapperHip {
     lastPrior_ = estimate;
     // ---- pre-processing on the device (:307-309), under the "Auxilary time" stopwatch (:305-312) ----
     auto t0 = Clock::now();
-    preprocess(raw);
+    preprocess(raw, timestamp);
     stamp(t0, lastTimings_.auxiliaryMs, sumTimings_.auxiliaryMs, 0);
     float prior32[16], corrected32[16];
     for (int k = 0; k < 16; ++k) corrected32[k] = prior32[k] = (float)estimate.m[k];  // :323, :338
@@ -292,11 +280,13 @@ class MapperHip {
     if (isNewValueSetMapper_) {  // the GIVEN pose is adopted; lastMeasurementTimestamp_ is left as it was (:440-455)
       initTime_ = timestamp;
       mapToRangeSensorPrev_ = mapToRangeSensor_;
+      mapToRangeSensorBuffer_.push(timestamp, mapToRangeSensor_);
       isNewValueSetMapper_ = false;
       isIgnoreOdometryPrediction_ = true;
       return true;
     }
     mapToRangeSensor_ = corrected;
+    mapToRangeSensorBuffer_.push(timestamp, mapToRangeSensor_);
     // ---- localisation mode: no merging (:465-479) ----
     const double timeSinceInit = timestamp - initTime_;
     if ((params_.isUseInitialMap && !params_.isMergeScansIntoMap) ||
@@ -330,8 +320,17 @@ class MapperHip {
   }
   // getTransform(t, odomToRangeSensorBuffer_) * calibration_.inverse()   (:221-222, :270-273)
   Mat4 odomInCloudFrame(double t) const { return mul(odomToRangeSensorBuffer_.lookup(t), calibrationInv_); }
-  void preprocess(const Raw& raw) {
+  void preprocess(const Raw& raw, double timestamp) {
     std::int64_t nMerge = 0, nMatch = 0;
+    if (motionCompensation_ && !raw.ready && !raw.staged) {  // host arrays: stage, de-skew, pre-process from the staged copy
+      if (!deskewStage_) check(o3s_raw_scan_create(device_, &deskewStage_), "o3s_raw_scan_create");
+      check(o3s_raw_scan_upload(deskewStage_, raw.pts, raw.normals, raw.N), "o3s_raw_scan_upload");
+      lastMotion_ = motionCompensation_->undistort(deskewStage_, timestamp);
+      check(o3s_scan_preprocess_staged(scan_, &params_.mapBuilderCropper, params_.scanVoxelSize, &params_.scanMatcherCropper, deskewStage_, &nMerge,
+                                       &nMatch),
+            "o3s_scan_preprocess_staged");
+      return;
+    }
     if (raw.ready) {
       o3s_scan* filled = *raw.ready;
       *raw.ready = submaps_.exchangeScanForNextMeasurement(filled);
@@ -353,6 +352,11 @@ class MapperHip {
   SubmapCollectionHip submaps_;
   o3s_scan* scan_ = nullptr;  // owned by submaps_ (its ring of resident scans)
   PoseBuffer odomToRangeSensorBuffer_;
+  TransformBuffer mapToRangeSensorBuffer_;  // the registered poses (Mapper::getMapToRangeSensorBuffer)
+  std::unique_ptr<ConstantVelocityMotionCompensation> motionCompensation_;  // motionCompensationMap_; null: off
+  o3s_raw_scan* deskewStage_ = nullptr;     // where a sweep handed over as host arrays is de-skewed
+  o3s_motion lastMotion_{};
+  int device_ = 0;
   Mat4 mapToRangeSensor_ = Mat4::identity(), mapToRangeSensorPrev_ = Mat4::identity(), lastPrior_ = Mat4::identity();
   Mat4 mapToRangeSensorLastScanInsertion_ = Mat4::identity();
   double lastMeasurementTimestamp_ = 0.0, lastReferenceInitializationTimestamp_ = 0.0, initTime_ = 0.0;

@@ -2,6 +2,7 @@
 // The kernels and the device-level pipelines live in cloud_dev.h (shared with the device-resident submap, submap.hip);
 // this file stages the caller's buffers through HBM.
 #include "cloud_dev.h"
+#include "undistort_dev.h"
 
 using namespace o3s_cloud;
 
@@ -204,6 +205,33 @@ int o3s_voxel_downsample_attr(int device, double voxel_size, const double* pts, 
 int o3s_voxel_downsample(int device, double voxel_size, const double* pts, const double* normals, int64_t N, double* out_pts,
                          double* out_normals, int32_t* out_voxel_idx, int64_t* n_out) {
   return o3s_voxel_downsample_attr(device, voxel_size, pts, normals, nullptr, nullptr, N, out_pts, out_normals, nullptr, nullptr, out_voxel_idx, n_out);
+}
+
+// ConstantVelocityMotionCompensation::undistortInputPointCloud on host buffers (out may alias pts)
+int o3s_undistort_cloud(int device, const o3s_motion* m, const double* pts, int64_t N, double* out) {
+  if (!motion_valid(m) || N < 0 || (N > 0 && (!pts || !out))) return O3S_ERR_BAD_ARGUMENT;
+  if (N == 0) return O3S_OK;
+  if (motion_is_zero(*m)) {  // motion is the identity for every phase: the reference's result is p
+    if (out != pts) std::memmove(out, pts, (size_t)N * 24);
+    return O3S_OK;
+  }
+  int rc = pick_device(device);
+  if (rc != O3S_OK) return rc;
+  hipStream_t s = nullptr;
+  Buf d;
+  CK(d.alloc((size_t)N * 24));
+  CK(hipMemcpyAsync(d.p, pts, (size_t)N * 24, hipMemcpyHostToDevice, s));
+  rc = undistort_dev(d.as<double>(), N, *m, s);
+  if (rc != O3S_OK) return rc;
+  CK(hipMemcpyAsync(out, d.p, (size_t)N * 24, hipMemcpyDeviceToHost, s));
+  CK(hipStreamSynchronize(s));
+  return O3S_OK;
+}
+
+int o3s_motion_from_poses(const double T_start[16], double t_start, const double T_finish[16], double t_finish, o3s_motion* m) {
+  if (!T_start || !T_finish || !m) return O3S_ERR_BAD_ARGUMENT;
+  motion_from_poses(T_start, t_start, T_finish, t_finish, m);
+  return O3S_OK;
 }
 
 }  // extern "C"

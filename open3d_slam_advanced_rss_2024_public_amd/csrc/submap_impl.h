@@ -1150,6 +1150,17 @@ int o3s_raw_scan_upload(o3s_raw_scan* r, const double* pts, const double* normal
 
 int64_t o3s_raw_scan_size(const o3s_raw_scan* r) { return r ? r->N : -1; }
 
+// undistortInputPointCloud on the staged sweep, in place (undistort_dev.h): points only, the staged normals stay as they are
+int o3s_raw_scan_undistort(o3s_raw_scan* r, const o3s_motion* m) {
+  if (!r || !motion_valid(m)) return O3S_ERR_BAD_ARGUMENT;
+  if (r->N == 0 || motion_is_zero(*m)) return O3S_OK;
+  if (hipSetDevice(r->device) != hipSuccess) return O3S_ERR_HIP;
+  const int rc = undistort_dev(r->p.d(), r->N, *m, r->stream);
+  if (rc != O3S_OK) return rc;
+  CK(hipStreamSynchronize(r->stream));  // the pre-process reads the staged copy from another stream
+  return O3S_OK;
+}
+
 int o3s_host_alloc_pinned(size_t bytes, void** out) {
   if (!out || bytes == 0) return O3S_ERR_BAD_ARGUMENT;
   *out = nullptr;
@@ -1324,6 +1335,36 @@ int64_t o3s_scan_get(const o3s_scan* sc, int which, double* pts, double* normals
   if (hipMemcpy(pts, p.p, (size_t)n * 24, hipMemcpyDeviceToHost) != hipSuccess) return -1;
   if (normals && hipMemcpy(normals, q.p, (size_t)n * 24, hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return n;
+}
+
+// CloudRegistration::registerClouds between two resident pre-processed scans: nothing is downloaded; the work area's stream (the
+// target's) is ordered behind the source's by an event, and the call returns on a drained stream, so either scan may be refilled
+int o3s_scan_registration_icp(const o3s_scan* source, int source_which, const o3s_scan* target, int target_which, double max_dist,
+                              const double init[16], const o3s_o3d_estimation* est, const o3s_o3d_icp_criteria* criteria,
+                              o3s_o3d_icp_result* result) {
+  if (!o3d_est_valid(est) || !source || !target || !init || !result || !(max_dist > 0.0) || (source_which != 0 && source_which != 1) ||
+      (target_which != 0 && target_which != 1))
+    return O3S_ERR_BAD_ARGUMENT;
+  if (source->device != target->device) return O3S_ERR_BAD_ARGUMENT;
+  const int64_t Ns = source_which == 0 ? source->n_wide : source->n_narrow;
+  const int64_t Nt = target_which == 0 ? target->n_wide : target->n_narrow;
+  if (Ns == 0 || Nt == 0) return O3S_ERR_EMPTY_REFERENCE;
+  if (hipSetDevice(target->device) != hipSuccess) return O3S_ERR_HIP;
+  const double* sp = (source_which == 0 ? source->wide_p : source->narrow_p).d();
+  const double* sn = (source_which == 0 ? source->wide_n : source->narrow_n).d();
+  const double* tp = (target_which == 0 ? target->wide_p : target->narrow_p).d();
+  const double* tn = (target_which == 0 ? target->wide_n : target->narrow_n).d();
+  hipStream_t s = target->stream;
+  if (source->stream != s) {
+    CK(hipEventRecord(source->handover, source->stream));
+    CK(hipStreamWaitEvent(s, source->handover, 0));
+  }
+  O3dEstIn e;
+  e.type = est->type;
+  e.eps = est->gicp_epsilon;
+  e.src_n = sn;
+  o3s_cloud::RegLease area(target->device, s);
+  return area.end(o3d_icp_run(area->reg, sp, Ns, tp, tn, Nt, max_dist, init, criteria, result, s, /*on_device=*/true, nullptr, &e));
 }
 
 int o3s_scan_set_reading(o3s_scan* sc, o3s_icp* icp) {

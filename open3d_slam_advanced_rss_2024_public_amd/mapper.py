@@ -54,10 +54,23 @@ class Mapper:
         self.calib_inv = np.eye(4)          # calibration_.inverse(); identity until set, as in the reference (Mapper.hpp) and MapperHip
         self.is_calibration_set = False     # isCalibrationSet_ (Mapper.cpp:66-85): until it is, every scan is refused (:169-174)
         self.use_initial_map = False
+        # mapToRangeSensorBuffer_ (Mapper.cpp:190, 228, 450, 460): the registered poses; motionCompensationMap_ works over it
+        # (SlamWrapper.cpp:445-447, 671).  Off by default: the sweep then reaches the pre-processing as it came.
+        from .odometry import TransformBuffer
+        self.pose_buffer = TransformBuffer()
+        self.motion_compensation = None
+        self.last_motion = None
 
     def set_calibration(self, C_):
         self.calib_inv = inv_iso(np.asarray(C_, np.float64))
         self.is_calibration_set = True
+
+    def enable_motion_compensation(self, scan_duration=0.1, is_spinning_clockwise=True, num_poses_vel_estimation=3):
+        """motion_compensation.is_undistort_scan: every sweep is de-skewed with the velocities of the registered poses before the
+        pre-processing sees it (ConstantVelocityMotionCompensation over getMapToRangeSensorBuffer())."""
+        from .odometry import ConstantVelocityMotionCompensation
+        self.motion_compensation = ConstantVelocityMotionCompensation(self.pose_buffer, scan_duration, is_spinning_clockwise,
+                                                                      num_poses_vel_estimation)
 
     def _odom(self, stamp):
         """getTransform(t, odomToRangeSensorBuffer_) * calibration_.inverse()   (Mapper.cpp:221-222, 270-273)"""
@@ -67,7 +80,11 @@ class Mapper:
     def sm(self):
         return self.col.maps[self.col.active]
 
-    def preprocess(self, sp, sn):
+    def preprocess(self, sp, sn, stamp=None):
+        if self.motion_compensation is not None and stamp is not None:   # SlamWrapper.cpp:671: undistortInputPointCloud(raw.cloud_, raw.time_)
+            self.last_motion = self.motion_compensation.motion(stamp)
+            from .odometry import undistort_cloud
+            sp = undistort_cloud(sp, self.last_motion, getattr(self.icp, "device", 0))
         self.ps.preprocess(self.wide, self.scan_voxel, self.narrow, sp, sn)
 
     def add(self, sp, sn, stamp):
@@ -78,13 +95,15 @@ class Mapper:
         self.ps = self.col.scan_for_next()
         if len(self.sm) == 0:
             self.T_prev = self.T.copy()
-            self.preprocess(sp, sn)
+            self.preprocess(sp, sn, stamp)
             self.col.insert(self.ps, self.T, stamp)
+            self.pose_buffer.push(stamp, self.T)
             self.flags = (1, 0, 0)
             return True
         if self.last_stamp is not None and stamp <= self.last_stamp:
             latest = max(self.odom)
             self.T = mul4(self.T_prev, mul4(inv_iso(self._odom(self.last_stamp)), self._odom(latest)))
+            self.pose_buffer.push(latest, self.T)
             self.T_prev = self.T.copy()
             return True
         est = self.T_prev.copy()
@@ -92,7 +111,7 @@ class Mapper:
             est = mul4(self.T_prev, mul4(inv_iso(self._odom(self.last_stamp)), self._odom(stamp)))
         self.ignore_odom = False
         self.prior = est
-        self.preprocess(sp, sn)
+        self.preprocess(sp, sn, stamp)
         prior32 = est.astype(np.float32)
         corrected32 = prior32.copy()
         reset = self.new_value or self.last_ref is None or (stamp - self.last_ref) >= self.ref_period
@@ -120,11 +139,13 @@ class Mapper:
         corrected = corrected32.astype(np.float64)
         if self.new_value:
             self.T_prev = self.T.copy()
+            self.pose_buffer.push(stamp, self.T)
             self.new_value = False
             self.ignore_odom = True
             self.flags = (0, refreset, threw)
             return True
         self.T = corrected
+        self.pose_buffer.push(stamp, self.T)
         motion = mul4(inv_iso(self.T_last_insert), self.T)
         moved = np.sqrt(motion[0, 3] * motion[0, 3] + motion[1, 3] * motion[1, 3] + motion[2, 3] * motion[2, 3])
         if not (moved < self.min_move):

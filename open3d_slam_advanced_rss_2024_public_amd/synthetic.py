@@ -380,6 +380,74 @@ def make_lidar_scan(world: World, T_gt: np.ndarray, beams: int = 64, azimuths: i
     return ps.astype(np.float32), ns.astype(np.float32)
 
 
+def sweep_phase(x, y, clockwise: bool):
+    """Share of a sweep that has passed when the beam looks along (x, y) in the sensor frame: the azimuth wrapped into [0, 2 pi),
+    over 2 pi, counted down from 1 for a clockwise spin; 0 where the wrapped azimuth is 0."""
+    a = np.arctan2(np.asarray(y, np.float64), np.asarray(x, np.float64))
+    a = np.where(a < 0.0, a + 2.0 * math.pi, a)
+    ph = 1.0 - a / (2.0 * math.pi) if clockwise else a / (2.0 * math.pi)
+    return np.where(a == 0.0, 0.0, ph)
+
+
+def sweep_motion(s, lin_vel, ang_vel_rpy):
+    """Constant-velocity sensor motion after s seconds (s: array): rotations yaw(s wz) pitch(s wy) roll(s wx) as (n, 3, 3) and
+    translations s v as (n, 3)."""
+    s = np.atleast_1d(np.asarray(s, np.float64))
+    v, w = np.asarray(lin_vel, np.float64), np.asarray(ang_vel_rpy, np.float64)
+    r, p, y = s * w[0], s * w[1], s * w[2]
+    cr, sr, cp, sp, cy, sy = np.cos(r), np.sin(r), np.cos(p), np.sin(p), np.cos(y), np.sin(y)
+    R = np.empty((s.shape[0], 3, 3))
+    R[:, 0, 0], R[:, 0, 1], R[:, 0, 2] = cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr
+    R[:, 1, 0], R[:, 1, 1], R[:, 1, 2] = sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr
+    R[:, 2, 0], R[:, 2, 1], R[:, 2, 2] = -sp, cp * sr, cp * cr
+    return R, s[:, None] * v[None, :]
+
+
+def make_moving_lidar_scan(world: World, T_start: np.ndarray, lin_vel, ang_vel_rpy, scan_duration: float = 0.1, clockwise: bool = True,
+                           beams: int = 64, azimuths: int = 2048, elevation_deg=(-22.5, 22.5), max_range: float = 60.0, sigma: float = 0.01,
+                           seed: int = 5678, dtype=np.float32):
+    """make_lidar_scan for a sensor that moves while it sweeps: the ray of a (beam, azimuth) cell is cast from
+    T_start . motion(phase(azimuth) . scan_duration), with the constant sensor-frame velocities lin_vel (m/s) and ang_vel_rpy
+    (rad/s); the return is recorded in the frame the sensor had at that moment, which is what a spinning LiDAR delivers.
+    De-skewing the sweep with the true velocities therefore gives T_start^-1 . (hit point) for every return.
+    Points and the hit surfaces' normals (in the frame of the ray's moment) as `dtype`."""
+    rng = np.random.default_rng(seed)
+    el = np.deg2rad(np.linspace(elevation_deg[0], elevation_deg[1], beams))
+    az = np.linspace(-math.pi, math.pi, azimuths, endpoint=False)
+    ce, se = np.cos(el)[:, None], np.sin(el)[:, None]
+    d_s = np.stack([ce * np.cos(az)[None, :], ce * np.sin(az)[None, :], np.broadcast_to(se, (beams, azimuths))], axis=-1).reshape(-1, 3)
+    Rm, tm = sweep_motion(sweep_phase(d_s[:, 0], d_s[:, 1], clockwise) * scan_duration, lin_vel, ang_vel_rpy)
+    R0, o0 = T_start[:3, :3], T_start[:3, 3]
+    Rw = np.einsum("ij,njk->nik", R0, Rm)          # per-ray rotation sensor -> world
+    o = o0[None, :] + tm @ R0.T                     # per-ray origin
+    d = np.einsum("nij,nj->ni", Rw, d_s)
+    ext = np.linalg.norm(world.u, axis=1) + np.linalg.norm(world.v, axis=1)
+    reach = max_range + ext + float(np.linalg.norm(tm, axis=1).max())
+    near = np.nonzero(np.linalg.norm(world.centres - o0, axis=1) <= reach)[0]
+    t_best = np.full(d.shape[0], np.inf)
+    f_best = np.full(d.shape[0], -1, np.int64)
+    for f in near:
+        c, u, v, n = world.centres[f], world.u[f], world.v[f], world.normals[f]
+        denom = d @ n
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = ((c - o) @ n) / denom
+        ok = (np.abs(denom) > 1e-12) & (t > 0.05) & (t < t_best)
+        if not ok.any():
+            continue
+        idx = np.nonzero(ok)[0]
+        q = o[idx] + t[idx, None] * d[idx] - c
+        lu, lv = np.linalg.norm(u), np.linalg.norm(v)
+        inside = (np.abs(q @ (u / lu)) <= lu) & (np.abs(q @ (v / lv)) <= lv)
+        idx = idx[inside]
+        t_best[idx] = t[idx]
+        f_best[idx] = f
+    hit = (f_best >= 0) & (t_best <= max_range)
+    r = t_best[hit] + (rng.normal(0, sigma, int(hit.sum())) if sigma > 0 else 0.0)
+    ps = d_s[hit] * r[:, None]
+    ns = np.einsum("nji,nj->ni", Rw[hit], world.normals[f_best[hit]])   # R^T n per ray
+    return ps.astype(dtype), ns.astype(dtype)
+
+
 def perturb_pose(T_gt: np.ndarray, trans: float = 0.10, rot_deg: float = 2.0, seed: int = 91011) -> np.ndarray:
     rng = np.random.default_rng(seed)
     d = rng.normal(size=3)
