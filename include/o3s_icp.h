@@ -71,7 +71,10 @@ typedef struct o3s_icp_config {
   int32_t sort_queries;     /* 1 = process the reading in spatial (grid) order for cache locality (default 1)         */
   int32_t use_graph;        /* 1 = replay the iteration chain from a hipGraph (default 1)                             */
   int32_t match_stats;      /* 1 = count candidates / cell rows examined by the matcher (slower; default 0)           */
-  int32_t reserved[4];
+  int32_t error_minimizer;  /* 0 = PointToPlaneErrorMinimizer, 1 = PointToPlaneWithCovErrorMinimizer    icp.yaml:25-27     */
+  float sensor_std_dev;     /* PointToPlaneWithCovErrorMinimizer.sensorStdDev [m], >= 0; read only when error_minimizer
+                               is 1 (a zeroed struct is today's chain)                            default 0.01       */
+  int32_t reserved[2];
 } o3s_icp_config;
 
 typedef struct o3s_icp_stats {
@@ -252,6 +255,62 @@ int o3s_icp_outlier_weights(o3s_icp* h, const float* reading_normals, const int3
 int o3s_icp_minimize(o3s_icp* h, const float* reading_xyzw, const int32_t* ids, const float* dists2,
                      const float* weights, int64_t N, float T_out[16], float A_out[36], float b_out[6],
                      float x_out[6]);
+
+
+/* ---- pose covariance (PointToPlaneWithCovErrorMinimizer, LPM/ErrorMinimizers/PointToPlaneWithCov.cpp:60-168) --------
+ * Censi's closed-form covariance of the estimated pose, as the reference evaluates it on the ErrorElements of the LAST
+ * iteration of a compute (icp.errorMinimizer->getCovariance()).  Configured with o3s_icp_config::error_minimizer = 1; the
+ * chain itself (launches, graph, pose, trace, stats) is the same with and without it: the covariance is one more pass over
+ * the resident pairs (k_cov, csrc/icp_kernels.h) behind the iteration that ended the chain — whichever checker ended it —
+ * and one host round trip for its 42 sums.  Not available in the sharded mode (O3S_ERR_BAD_CONFIG).
+ *
+ * Arithmetic contract (a restatement of PointToPlaneWithCov.cpp:72-161).
+ *  Inputs: for every kept pair k of the last iteration, in processing-slot order, the centred values k_normal_eq formed
+ *  (PointToPlane.cpp:263-268): p = S - mp (fp32, S = T_iter(prev) * P), q = Q_id - mq (fp32), n = Nq_id; and T, that
+ *  iteration's step mOut = Trans(mq) [R,t] Trans(-mp) with the NaN guard of PointToPlane.cpp:326-332 applied.  The reference's
+ *  quirks are kept: "ranges" are measured on centroid-shifted points, the translation is the un-centred step's.
+ *  Once per call: beta = fl32(-asin(T20)), alpha = fl32(atan2(T21, T22)), gamma = fl32(atan2(T10 / cos beta, T00 / cos beta)):
+ *  asin, atan2, cos and the divisions in fp64 on the promoted fp32 values, cos of the already rounded beta, each result rounded
+ *  once to fp32; t = (T03, T13, T23).
+ *  Per pair, fp32, no FMA contraction, left to right:
+ *    r = sqrt((px^2 + py^2) + pz^2), d = p / r;   s = sqrt((qx^2 + qy^2) + qz^2), e = q / s
+ *    na = nz dy - ny dz, nb = nx dz - nz dx, ng = ny dx - nx dy
+ *    E  = nx ((((px - gamma py) + beta pz) + tx) - qx);  E += ny ((((gamma px + py) - alpha pz) + ty) - qy)
+ *    E += nz (((((-beta) px + alpha py) + pz) + tz) - qz)
+ *    Nr = the same three lines with d in place of p and without the t and q terms;   Nq = -((nx ex + ny ey) + nz ez)
+ *    h = [nx, ny, nz, r na, r nb, r ng];   w = E + r Nr
+ *    u = [nx Nr, ny Nr, nz Nr, na w, nb w, ng w];   v = [nx Nq, ny Nq, nz Nq, (s na) Nq, (s nb) Nq, (s ng) Nq]
+ *  Sums in fp64 in a fixed order (per-block partials folded in block order, no floating-point atomics), of exact products of
+ *  the promoted fp32 values: H = sum h h^T, M = sum (u u^T + v v^T), upper triangles.
+ *  Result: cov = sigma2 * H^-1 * M * H^-1 in fp64, sigma2 = fl32(sensor_std_dev * sensor_std_dev) promoted, H^-1 from a
+ *  partial-pivot LU in fp64.  A zero or non-finite pivot gives 36 NaN and O3S_OK (the reference returns non-finite garbage
+ *  there; callers test isfinite).
+ *  Two deliberate departures from the reference's fp32 evaluation: the sums and the inverse are fp64 (the reference sums
+ *  sequentially in fp32 and Eigen's product order is unspecified), and the angles are rounded from fp64.
+ * Output: 6 x 6 column-major double in the parameter order [t_x, t_y, t_z, alpha, beta, gamma] — translation FIRST, the
+ * reference's order, which differs from the minimiser's x = [rot; trans] (o3s_icp_minimize). */
+/* The matrix of the last successful compute on this handle (any compute entry point, o3s_icp_compute_batch included).
+ * error_minimizer 0: all zeros and O3S_OK, as the base class does (LPM/ErrorMinimizer.cpp:266-270).
+ * O3S_ERR_NOT_INITIALIZED before any compute or after a failed one. */
+int o3s_icp_get_covariance(const o3s_icp* h, double cov36[36]);
+/* PointToPlaneWithCovErrorMinimizer::estimateCovariance(mPts, transformation) at module level, beside o3s_icp_minimize: three
+ * 3 x K host arrays of pairs that are ALREADY centred (AoS [x y z] per pair) and the step; the same kernel as the fused path.
+ * Needs no reference and touches no state of a compute.  K <= 0: O3S_ERR_NO_POINTS. */
+int o3s_icp_estimate_covariance(o3s_icp* h, const float* reading_c, const float* reference_c, const float* normals, int64_t K,
+                                const float T_step[16], float sensor_std_dev, double cov36[36]);
+/* The ErrorElements of the last iteration of the last successful compute, in processing-slot order: the centred kept pairs
+ * (3 x K each, AoS) and reading_idx[k] = input index of pair k's reading point.  Returns K (<= 0: nothing to report — no
+ * successful compute, or the handle has been given other work since); writes min(K, cap) pairs; every pointer may be NULL.
+ * Either minimiser.  Diagnostics / tests: the pairs are downloaded. */
+int64_t o3s_icp_get_error_elements(o3s_icp* h, float* reading_c, float* reference_c, float* normals, int32_t* reading_idx, int64_t cap);
+/* The step mOut of that last iteration (4 x 4 column-major): the `transformation` the reference hands to estimateCovariance
+ * together with the ErrorElements above.  O3S_ERR_NOT_INITIALIZED before any compute or after a failed one.  Diagnostics / tests. */
+int o3s_icp_get_last_step(const o3s_icp* h, float T_step[16]);
+/* Device time of the last covariance pass on this handle (fused or o3s_icp_estimate_covariance), microseconds, from wall_clock64
+ * stamps like o3s_icp_stats::gpu_ms: out2[0] = start of k_cov -> end of k_cov_post; out2[1] = the chain's final post -> end of
+ * k_cov_post, i.e. what the configured covariance adds behind the chain on the device's clock, the host round trip that issues it
+ * included (0 unless the last compute ran with error_minimizer 1).  Diagnostics (tools/covariance_bench.py). */
+int o3s_icp_covariance_gpu_us(const o3s_icp* h, double out2[2]);
 
 #ifdef __cplusplus
 }

@@ -61,7 +61,9 @@ class IcpConfigC(C.Structure):
         ("sort_queries", C.c_int32),
         ("use_graph", C.c_int32),
         ("match_stats", C.c_int32),
-        ("reserved", C.c_int32 * 4),
+        ("error_minimizer", C.c_int32),   # 0 PointToPlaneErrorMinimizer, 1 PointToPlaneWithCovErrorMinimizer
+        ("sensor_std_dev", C.c_float),
+        ("reserved", C.c_int32 * 2),
     ]
 
 
@@ -221,6 +223,13 @@ def load(variant: str | None = None) -> C.CDLL:
     L.o3s_matcher_init.argtypes = [vp, fp, fp, C.c_int64]
     L.o3s_icp_host_split.argtypes = [vp, C.POINTER(C.c_double)]
     L.o3s_icp_host_split_ex.argtypes = [vp, C.POINTER(C.c_double)]
+    dp = C.POINTER(C.c_double)
+    L.o3s_icp_get_covariance.argtypes = [vp, dp]
+    L.o3s_icp_estimate_covariance.argtypes = [vp, fp, fp, fp, C.c_int64, fp, C.c_float, dp]
+    L.o3s_icp_get_error_elements.argtypes = [vp, fp, fp, fp, ip, C.c_int64]
+    L.o3s_icp_get_error_elements.restype = C.c_int64
+    L.o3s_icp_get_last_step.argtypes = [vp, fp]
+    L.o3s_icp_covariance_gpu_us.argtypes = [vp, dp]
     _loaded[key] = L
     return L
 

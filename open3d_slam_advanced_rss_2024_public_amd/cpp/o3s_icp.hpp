@@ -10,6 +10,7 @@
 // `PM::Matrix::data()` returns.  See INTEGRATION.md for the exact patch.
 #pragma once
 
+#include <array>
 #include <cstdint>
 #include <limits>
 #include <stdexcept>
@@ -58,6 +59,15 @@ class IcpHip {
 
   bool getMaxNumIterationsReached() const { return stats_.max_iters_reached != 0; }  // PointMatcher.h:786
   const o3s_icp_stats& stats() const { return stats_; }
+  // icp.errorMinimizer->getCovariance() (PointToPlaneWithCov.cpp:164-168): 6 x 6 column-major, parameters [t_x t_y t_z alpha beta gamma],
+  // of the last successful compute on this handle; all zeros under the plain minimiser (ErrorMinimizer.cpp:266-270).  Throws
+  // std::runtime_error before any compute or after a failed one.  Eigen::Map<const Eigen::Matrix<double, 6, 6>>(c.data()) reads it.
+  std::array<double, 36> getCovariance() const {
+    std::array<double, 36> c{};
+    const int rc = o3s_icp_get_covariance(h_, c.data());
+    if (rc != O3S_OK) throw std::runtime_error("o3s_icp_get_covariance: no successful compute on this handle (status " + std::to_string(rc) + ")");
+    return c;
+  }
   o3s_icp* handle() { return h_; }
 
  private:

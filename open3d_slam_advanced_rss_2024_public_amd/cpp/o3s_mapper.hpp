@@ -144,6 +144,9 @@ class MapperHip {
   bool lastReferenceReset() const { return lastReferenceReset_; }
   bool lastIcpThrew() const { return lastIcpThrew_; }
   int lastIterations() const { return lastIterations_; }
+  // covariance of the latest scan-to-map registration (IcpHip::getCovariance: zeros under the plain minimiser); NaN when that
+  // registration failed and the prior was kept (Mapper.cpp:420-422), or before the first one
+  const std::array<double, 36>& getLatestRegistrationCovariance() const { return lastCovariance_; }
 
   // rawScan in the sensor frame (3 x N doubles, normals nullable when normal estimation is configured on the scan object)
   bool addRangeMeasurement(const double* rawPts, const double* rawNormals, std::int64_t N, double timestamp) {
@@ -264,11 +267,13 @@ class MapperHip {
       }
       lastIterations_ = st.iterations;
       if (rc != O3S_OK) throw std::runtime_error(o3s_last_error(icp_.handle()));  // every libpointmatcher exception derives from it
+      lastCovariance_ = icp_.getCovariance();
       stamp(t0, lastTimings_.registrationMs, sumTimings_.registrationMs, 2);
     } catch (const std::runtime_error&) {
       // (a scan whose reading could not even be handed over: the reference would have looked at the patch first)
       if (!resetRef && nPatchNow < 0 && submaps_.activeSubmap().patchCount(patch, mapToRangeSensor_.m) == 0) return false;
       lastIcpThrew_ = true;  // :420-422: the prior stays (corrected32 must not hold a half-written result)
+      lastCovariance_.fill(std::numeric_limits<double>::quiet_NaN());
       for (int k = 0; k < 16; ++k) corrected32[k] = prior32[k];
       // a compute that failed before it waited for its stream may leave the asynchronous index build / the reading's hand-over in
       // flight: nothing below may rewrite the buffers they read until the handle's stream has drained
@@ -348,6 +353,11 @@ class MapperHip {
   }
 
   MapperParams params_;
+  static std::array<double, 36> nanCovariance() {
+    std::array<double, 36> c;
+    c.fill(std::numeric_limits<double>::quiet_NaN());
+    return c;
+  }
   IcpHip icp_;
   SubmapCollectionHip submaps_;
   o3s_scan* scan_ = nullptr;  // owned by submaps_ (its ring of resident scans)
@@ -363,6 +373,7 @@ class MapperHip {
   bool haveLast_ = false, haveRef_ = false;  // haveLast_: lastMeasurementTimestamp_ holds a stamp (the reference leaves it default-constructed after the first scan, whose lookup would throw: no odometry prior is formed then)
   bool isNewValueSetMapper_ = false, isIgnoreOdometryPrediction_ = false;
   bool lastInserted_ = false, lastReferenceReset_ = false, lastIcpThrew_ = false;
+  std::array<double, 36> lastCovariance_ = nanCovariance();
   int lastIterations_ = 0;
   Mat4 calibrationInv_ = Mat4::identity();
   bool isCalibrationSet_ = false;

@@ -9,6 +9,8 @@
 //   k_sel_finish  exact k-th smallest finite d2 (TrimmedDistOutlierFilter limit), means of the kept pairs
 //   k_normal_eq   27 fp64 partial sums of G G^T / G h per block (centred in fp32 exactly like the reference)
 //   k_solve       reduce partials, 6x6 solve, SE(3) step, T_iter update, stop rules
+// and, once per call behind the chain when the pose covariance is configured (PointToPlaneWithCovErrorMinimizer):
+//   k_cov         42 fp64 partial sums per block over the kept pairs of the last iteration;  k_cov_post folds and posts them
 // Data layout in HBM: the reading is SoA fp32 (x[], y[], z[], nx[], ny[], nz[]) and is streamed with fully coalesced
 // 4-byte loads; the reference is stored cell-sorted as 16-byte records {x,y,z,orig index} (+ a parallel {nx,ny,nz,0}
 // array) so that every candidate / winner gather is one 16-byte load from one cache-line sector.
@@ -2338,7 +2340,7 @@ __device__ __forceinline__ void post_state(const IcpState* S /*LDS*/, const IcpS
   // the FINAL state of a call, once: one wave's lanes store the state words, the wave's release fence covers them all, lane 0
   // stores the word the host polls.  Unfinished iterations post nothing (a store to host memory on every iteration's critical
   // path cost more than it saved): the host learns "not done yet" from the drained stream.
-  constexpr int kWords = (int)(sizeof(IcpState) / 4);
+  constexpr int kWords = kStateWords;
   if (threadIdx.x < 64) {
     uint32_t* dst = reinterpret_cast<uint32_t*>(&post->state);
     const uint32_t* src = reinterpret_cast<const uint32_t*>(S);
@@ -2355,7 +2357,7 @@ __device__ __forceinline__ void solve_body(const double* __restrict__ part, int 
                                            float* __restrict__ trace_T, float* __restrict__ trace_limit, int64_t* __restrict__ trace_kept,
                                            int trace_cap, int update_pose, HostPost* __restrict__ post, SolveLds& L, const SolveOverride* ov /*LDS or null*/) {
   using Sum = BlockSum<kNeComps, kBlock>;
-  constexpr int kWords = (int)(sizeof(IcpState) / 4);
+  constexpr int kWords = kStateWords;
   IcpState& s_st = L.st;
   for (int k = threadIdx.x; k < kWords; k += kBlock) reinterpret_cast<uint32_t*>(&s_st)[k] = reinterpret_cast<const uint32_t*>(st)[k];
   // partials: thread t takes the 27 sums of block t (and of block t + 256 for readings beyond 131 k points).  The loads are
@@ -2491,6 +2493,7 @@ __device__ __forceinline__ void solve_body(const double* __restrict__ part, int 
     }
     __syncthreads();
     if (threadIdx.x < 16) {
+      st->T_prev[threadIdx.x] = s_st.T_iter[threadIdx.x];  // what this iteration's pairs were formed under (k_cov, k_cov_elements): not staged
       s_st.T_iter[threadIdx.x] = L.Tn[threadIdx.x];
       if (it < trace_cap) trace_T[it * 16 + threadIdx.x] = L.Tn[threadIdx.x];
     } else if (threadIdx.x == 16 && it < trace_cap) {
@@ -2618,6 +2621,161 @@ __global__ void __launch_bounds__(kFinThreads) k_sel_ne(ChainParams cp, IcpState
   double* s_b = s_a + Sum::kWordsA;
   Sum::run_first(acc, s_a, s_b);
   if (threadIdx.x < kNeComps) part_ne[threadIdx.x * gridDim.x + blockIdx.x] = Sum::total(s_b, threadIdx.x);  // k_solve folds them in block order
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Pose covariance of the last iteration (PointToPlaneWithCovErrorMinimizer::estimateCovariance,
+// LPM/ErrorMinimizers/PointToPlaneWithCov.cpp:72-161; the contract is spelled out at o3s_icp_get_covariance in include/o3s_icp.h).
+// k_cov walks the reading like k_normal_eq — same kept-pair predicate, same matched-normal stream, same points per lane — and
+// leaves 42 fp64 sums per block: the upper triangles of H = sum h h^T and M = sum (u u^T + v v^T).  k_cov_post folds them in a
+// fixed order and posts the 42 totals; the host inverts H (csrc/o3s_icp.hip, cov_finish).
+// The pairs come from one of two sources:
+//   chain   (ext_p == null) the state the chain ended with: p = T_prev * reading - mp, q = matched point - mq, n = matched normal
+//   module  (ext_p != null) three 3 x K arrays of pairs that are already centred (o3s_icp_estimate_covariance)
+// ------------------------------------------------------------------------------------------------------------------
+struct CovAngles {  // formed once per call on the host: fp64 asin / atan2 of the step, each rounded once to fp32
+  float alpha, beta, gamma, tx, ty, tz;
+};
+// per-pair terms, fp32 in the reference's left-to-right order (the translation unit is compiled without FMA contraction)
+__device__ __forceinline__ void cov_terms(float px, float py, float pz, float qx, float qy, float qz, float nx, float ny, float nz, const CovAngles& g,
+                                          float (&h)[6], float (&u)[6], float (&v)[6]) {
+  // sqrtf and / are the correctly rounded ones (hipcc's default for fp32); the __fsqrt_rn intrinsic is the native, 1-ulp sqrt here
+  const float r = sqrtf((px * px + py * py) + pz * pz);
+  const float dx = px / r, dy = py / r, dz = pz / r;
+  const float s = sqrtf((qx * qx + qy * qy) + qz * qz);
+  const float ex = qx / s, ey = qy / s, ez = qz / s;
+  const float na = nz * dy - ny * dz, nb = nx * dz - nz * dx, ng = ny * dx - nx * dy;
+  float E = nx * ((((px - g.gamma * py) + g.beta * pz) + g.tx) - qx);
+  E = E + ny * ((((g.gamma * px + py) - g.alpha * pz) + g.ty) - qy);
+  E = E + nz * (((((-g.beta) * px + g.alpha * py) + pz) + g.tz) - qz);
+  float Nr = nx * ((dx - g.gamma * dy) + g.beta * dz);
+  Nr = Nr + ny * ((g.gamma * dx + dy) - g.alpha * dz);
+  Nr = Nr + nz * ((((-g.beta) * dx + g.alpha * dy)) + dz);
+  const float Nq = -((nx * ex + ny * ey) + nz * ez);
+  const float w = E + r * Nr;
+  h[0] = nx, h[1] = ny, h[2] = nz, h[3] = r * na, h[4] = r * nb, h[5] = r * ng;
+  u[0] = nx * Nr, u[1] = ny * Nr, u[2] = nz * Nr, u[3] = na * w, u[4] = nb * w, u[5] = ng * w;
+  v[0] = nx * Nq, v[1] = ny * Nq, v[2] = nz * Nq, v[3] = (s * na) * Nq, v[4] = (s * nb) * Nq, v[5] = (s * ng) * Nq;
+}
+// the centred pair of slot i as the last iteration's k_normal_eq formed it
+__device__ __forceinline__ void cov_chain_pair(const float* T, float x0, float y0, float z0, const float4& q, float mpx, float mpy, float mpz,
+                                               float mqx, float mqy, float mqz, float (&p)[3], float (&qc)[3]) {
+  p[0] = xf_row(T, 0, x0, y0, z0) - mpx;
+  p[1] = xf_row(T, 1, x0, y0, z0) - mpy;
+  p[2] = xf_row(T, 2, x0, y0, z0) - mpz;
+  qc[0] = q.x - mqx;
+  qc[1] = q.y - mqy;
+  qc[2] = q.z - mqz;
+}
+
+__global__ void __launch_bounds__(kBlock) k_cov(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz, int N,
+                                                const float4* __restrict__ mq, const float4* __restrict__ mn, const int32_t* __restrict__ pos,
+                                                const float* __restrict__ d2, float max_out_r2, const IcpState* __restrict__ st,
+                                                const float* __restrict__ ext_p, const float* __restrict__ ext_q, const float* __restrict__ ext_n,
+                                                CovAngles ang, double* __restrict__ part /*[42][grid]*/,
+                                                unsigned long long* __restrict__ t_start /*wall_clock64 of block 0's start*/) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *t_start = wall_clock64();
+  using Sum = BlockSum<kCovTri, kBlock>;  // two passes of 21: one pass of 42 would not fit 64 KB of LDS
+  __shared__ double s_a[Sum::kWordsA];
+  __shared__ double s_b[Sum::kWordsB];
+  const bool chain = ext_p == nullptr;  // uniform
+  float T[16], limit = kInfF, mpx = 0.f, mpy = 0.f, mpz = 0.f, mqx = 0.f, mqy = 0.f, mqz = 0.f;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.f : 0.f;
+  if (chain) {
+    const float hv = hdr_load(st);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) T[k] = st->T_prev[k];
+    limit = hdr_f(hv, H_LIMIT);
+    mpx = hdr_f(hv, H_MP), mpy = hdr_f(hv, H_MP + 1), mpz = hdr_f(hv, H_MP + 2);
+    mqx = hdr_f(hv, H_MQ), mqy = hdr_f(hv, H_MQ + 1), mqz = hdr_f(hv, H_MQ + 2);
+  }
+  double accH[kCovTri], accM[kCovTri];
+#pragma unroll
+  for (int c = 0; c < kCovTri; ++c) accH[c] = accM[c] = 0.0;
+  for (int base = blockIdx.x * (kBlock * kNePPT) + threadIdx.x; base < N; base += gridDim.x * (kBlock * kNePPT)) {
+#pragma unroll
+    for (int u_ = 0; u_ < kNePPT; ++u_) {
+      const int i = base + u_ * kBlock;
+      if (i >= N) continue;
+      float p[3], q[3], n[3];
+      if (chain) {
+        if (!kept_pair(pos[i], d2[i], limit, max_out_r2)) continue;
+        const float4 qq = mq[i], nn = mn[i];
+        cov_chain_pair(T, rx[i], ry[i], rz[i], qq, mpx, mpy, mpz, mqx, mqy, mqz, p, q);
+        n[0] = nn.x, n[1] = nn.y, n[2] = nn.z;
+      } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          p[c] = ext_p[3 * (size_t)i + c];
+          q[c] = ext_q[3 * (size_t)i + c];
+          n[c] = ext_n[3 * (size_t)i + c];
+        }
+      }
+      float h[6], u[6], v[6];
+      cov_terms(p[0], p[1], p[2], q[0], q[1], q[2], n[0], n[1], n[2], ang, h, u, v);
+      int t = 0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+#pragma unroll
+        for (int c = a; c < 6; ++c) {
+          accH[t] += (double)h[a] * (double)h[c];  // products of promoted fp32 values: exact
+          accM[t] += (double)u[a] * (double)u[c] + (double)v[a] * (double)v[c];
+          ++t;
+        }
+      }
+    }
+  }
+  Sum::run(accH, s_a, s_b);
+  if (threadIdx.x < kCovTri) part[threadIdx.x * gridDim.x + blockIdx.x] = Sum::total(s_b, threadIdx.x);
+  Sum::run(accM, s_a, s_b);  // (its first barrier stands between the totals above and the new segment sums)
+  if (threadIdx.x < kCovTri) part[(kCovTri + threadIdx.x) * gridDim.x + blockIdx.x] = Sum::total(s_b, threadIdx.x);
+}
+
+// One block: component c is folded by wave c % 4 — lane l adds the partials of blocks l, l + 64, ... in order, then the wave's
+// DPP tree — so the order is a function of the number of blocks alone.  Lane 0 posts the 42 totals (host_post.h) and leaves them
+// in `sums` for a host whose posts are switched off.
+__global__ void __launch_bounds__(kBlock) k_cov_post(const double* __restrict__ part /*[42][nb]*/, int nb, double* __restrict__ sums /*[42] + two stamps*/,
+                                                     const unsigned long long* __restrict__ t_start, uint32_t* __restrict__ mailbox, uint32_t seq) {
+  __shared__ double s_sum[kCovComps];
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  for (int c = w; c < kCovComps; c += kBlock / 64) {
+    double s = 0.0;
+    for (int b = l; b < nb; b += 64) s += part[(size_t)c * nb + b];
+    s = wave_sum(s);
+    if (l == 0) s_sum[c] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < kCovComps) sums[threadIdx.x] = s_sum[threadIdx.x];
+  if (threadIdx.x == 0) {
+    double v[kCovComps + 2];  // the totals, then the two wall_clock64 stamps of the pass (k_cov's start, here), bit patterns
+#pragma unroll
+    for (int c = 0; c < kCovComps; ++c) v[c] = s_sum[c];
+    v[kCovComps] = __longlong_as_double((long long)*t_start);
+    v[kCovComps + 1] = __longlong_as_double((long long)wall_clock64());
+    sums[kCovComps] = v[kCovComps];
+    sums[kCovComps + 1] = v[kCovComps + 1];
+    host_post::post(mailbox, seq, host_post::kPostVals, v);
+  }
+}
+
+// o3s_icp_get_error_elements: every slot's centred pair of the last iteration and whether it was kept (diagnostics)
+__global__ void __launch_bounds__(kBlock) k_cov_elements(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz, int N,
+                                                         const float4* __restrict__ mq, const float4* __restrict__ mn, const int32_t* __restrict__ pos,
+                                                         const float* __restrict__ d2, float max_out_r2, const IcpState* __restrict__ st,
+                                                         float* __restrict__ out /*[N][9]: p, q, n*/, int32_t* __restrict__ keep /*[N]*/) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= N) return;
+  float T[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) T[k] = st->T_prev[k];
+  const bool k = kept_pair(pos[i], d2[i], st->limit, max_out_r2);
+  float p[3], q[3];
+  const float4 nn = mn[i];
+  cov_chain_pair(T, rx[i], ry[i], rz[i], mq[i], st->mp[0], st->mp[1], st->mp[2], st->mq[0], st->mq[1], st->mq[2], p, q);
+  float* o = out + (size_t)i * 9;
+  o[0] = p[0], o[1] = p[1], o[2] = p[2], o[3] = q[0], o[4] = q[1], o[5] = q[2], o[6] = nn.x, o[7] = nn.y, o[8] = nn.z;
+  keep[i] = k ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 // icp_types.h — device-visible plain structs shared by the kernels and the host side of libo3dslam_icp_hip.so.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 
@@ -31,6 +32,8 @@ constexpr int kHistRing = 16;         // quaternion / translation ring (smooth_l
 constexpr int kMaxPartialBlocks = 512;  // upper bound on blocks of the classify / normal-equation kernels
 constexpr int kCentComps = 7;         // sum p(3), sum q(3), count
 constexpr int kNeComps = 27;          // upper triangle of A (21) + b (6)
+constexpr int kCovTri = 21;           // upper triangle of a symmetric 6x6
+constexpr int kCovComps = 2 * kCovTri;  // pose covariance (k_cov): H = sum h h^T, then M = sum (u u^T + v v^T)
 // Speculative digit histograms of the trim selection (k_match2 -> k_classify), double-buffered by iteration parity: per parity
 // the level-2 digits of the pairs in the previous limit's level-1 bin (1024) and the level-3 digits of the pairs that share its
 // 21 leading bits (1024).  k_match2 of iteration i fills parity i & 1 and clears the other one for iteration i + 1.
@@ -99,8 +102,15 @@ struct IcpState {
   unsigned long long t_prep;      // ... and the start of the call's first kernel (k_read_prep)
   unsigned long long cand_count;  // matcher statistics (sum over the call)
   unsigned long long row_count;
+  // ---- behind the words the chain stages, writes back and posts (kStateWords) ----
+  float T_prev[16];               // T_iter the LAST iteration started from (identity when one iteration ran): with mp, mq, limit and dT
+                                  // what the pose covariance (k_cov) and o3s_icp_get_error_elements rebuild that iteration's pairs from.
+                                  // Stored straight to the device state by the closing step (16 lanes, nobody waits for it) and read
+                                  // there: it takes no part in the staging of solve_body nor in the post, which stay 254 words
 };
-constexpr int kStateTailWords = 4;  // cand_count / row_count: only ever touched by the matcher's atomics, never by a state write-back
+constexpr int kStateWords = (int)(offsetof(IcpState, T_prev) / 4);  // the state as the closing step stages it through LDS and posts it
+constexpr int kStateTailWords = 4;  // cand_count / row_count, the last of those: only ever touched by the matcher's atomics, never by a state write-back
+static_assert(offsetof(IcpState, T_prev) == offsetof(IcpState, row_count) + 8, "the staged words end with the matcher's counters");
 static_assert(sizeof(IcpState) % 4 == 0, "IcpState is copied word-wise");
 
 // One in-bin candidate of the trim selection: everything the finishing kernel needs, so it never chases an index.

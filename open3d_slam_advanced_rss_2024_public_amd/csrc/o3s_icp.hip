@@ -68,6 +68,7 @@ struct HostStage {  // pinned staging block for small H2D / D2H transfers
 };
 
 constexpr int kNumKernels = 5;
+constexpr size_t kCovBufBytes = ((size_t)kMaxPartialBlocks * kCovComps + kCovComps + 3) * sizeof(double);  // k_cov's partials [42][blocks], the 42 totals + 2 stamps, k_cov's start
 constexpr size_t kHistWords = (size_t)kHistReplicas * kHistBins + 1024;  // level-1 replicas + the level-2 histogram right behind them
 
 struct ChainArgs {
@@ -141,6 +142,16 @@ struct o3s_icp {
   DevBuf d_sel_part2, d_park;  // k_sel_partial (large readings): block partials [7][blocks]; parked records [kParkRecs] + their order keys
   DevBuf d_pos, d_d2, d_hist, d_cand, d_sel, d_cent, d_ne, d_state, d_T0, d_trace_T, d_trace_limit, d_trace_kept;
   DevBuf d_mod_a, d_mod_b, d_mod_c, d_mod_d;  // module-level scratch
+  // pose covariance (error_minimizer 1, o3s_icp_estimate_covariance): k_cov's block partials [42][blocks] with the 42 totals behind
+  // them, and the mailbox k_cov_post posts the totals to
+  DevBuf d_cov;
+  host_post::PostBlock<> cov_mb;
+  double cov[36] = {0};
+  bool cov_valid = false;       // the last compute succeeded: o3s_icp_get_covariance has something to return
+  bool elements_valid = false;  // ... and nothing has touched the chain's buffers since: o3s_icp_get_error_elements can rebuild its pairs
+  float last_max_out_r2 = 0.f;  // the kept-pair predicate's MaxDist bound of that compute
+  float last_step[16] = {0};    // ... and its last iteration's step (IcpState::dT)
+  unsigned long long cov_t_start = 0, cov_t_end = 0;  // wall_clock64 stamps of the last covariance pass (k_cov's start, k_cov_post's end)
   HostStage* stage = nullptr;                // pinned
   // mailbox (host_post.h): init_reference's two read-backs without a copy or a stream synchronisation
   host_post::PostBlock<> mb;
@@ -173,7 +184,7 @@ struct o3s_icp {
   std::vector<DevBuf*> all_bufs() {
     return {&d_ref_in, &d_refn_in, &d_ref, &d_refn, &d_cell_start, &d_cell_tmp, &d_qstart, &d_orig_to_sorted, &d_cell_of, &d_scan_sums,
             &d_ref_part, &d_ref_bb, &d_ref1, &d_refn1, &d_cell_start1, &d_in_xyzw, &d_in_n, &d_t, &d_r, &d_perm, &d_qcell, &d_qcount, &d_pos, &d_d2, &d_hist, &d_cand, &d_cand_cnt, &d_sel_part2, &d_park, &d_sel, &d_cent,
-            &d_ne, &d_state, &d_T0, &d_mq, &d_mn, &d_trace_T, &d_trace_limit, &d_trace_kept, &d_mod_a, &d_mod_b, &d_mod_c, &d_mod_d, &shard.own};
+            &d_ne, &d_state, &d_T0, &d_mq, &d_mn, &d_trace_T, &d_trace_limit, &d_trace_kept, &d_mod_a, &d_mod_b, &d_mod_c, &d_mod_d, &d_cov, &shard.own};
   }
 
   // graph cache
@@ -284,6 +295,9 @@ int validate_config(const o3s_icp_config& c, std::string& why) {
     return why = "smooth_length must be in [0, 15]", O3S_ERR_BAD_CONFIG;
   if (c.max_iters <= 0 && !c.use_differential) return why = "no transformation checker configured", O3S_ERR_BAD_CONFIG;
   if (c.grid_cell < 0.f) return why = "grid_cell must be >= 0", O3S_ERR_BAD_CONFIG;
+  if (c.error_minimizer != 0 && c.error_minimizer != 1)
+    return why = "error_minimizer must be 0 (PointToPlaneErrorMinimizer) or 1 (PointToPlaneWithCovErrorMinimizer)", O3S_ERR_BAD_CONFIG;
+  if (c.error_minimizer == 1 && !(c.sensor_std_dev >= 0.f)) return why = "sensor_std_dev must be >= 0", O3S_ERR_BAD_CONFIG;
   return O3S_OK;
 }
 
@@ -339,6 +353,7 @@ int wait_post(o3s_icp* h, uint32_t seq, hipEvent_t drained, bool* done) {
 int init_reference_impl(o3s_icp* h, const float4* d_xyzw, const float* d_normals, int64_t M, bool wait_end = true, bool center = true,
                         const uint32_t* d_count = nullptr, int64_t* M_out = nullptr) {
   h->ref_ready = false;
+  h->elements_valid = false;
   if (M_out) *M_out = 0;
   if (M <= 0) return fail(h, O3S_ERR_EMPTY_REFERENCE, "reference cloud is empty");
   if (M > (int64_t)0x7fffffff) return fail(h, O3S_ERR_BAD_ARGUMENT, "reference larger than 2^31-1 points");
@@ -550,6 +565,9 @@ int ensure_iteration_buffers(o3s_icp* h, int N) {
   HIP_TRY(h, h->d_ne.ensure((size_t)kMaxPartialBlocks * kNeComps * sizeof(double)));
   HIP_TRY(h, h->d_state.ensure(sizeof(IcpState)));
   HIP_TRY(h, h->d_T0.ensure(16 * 4));
+  // the configured covariance's partials, here rather than at their first use behind the chain: an allocation moves alloc_gen, and
+  // one made after a call's graph key was formed would put the capture off by a call
+  if (h->cfg.error_minimizer == 1) HIP_TRY(h, h->d_cov.ensure(kCovBufBytes));
   return O3S_OK;
 }
 
@@ -902,6 +920,7 @@ int issue_segment(o3s_icp* h, Call& c, bool capturing = false) {
 int start_call(o3s_icp* h, const float* T_init) {
   Call& c = h->call;
   c.live = false;
+  h->cov_valid = h->elements_valid = false;
 #ifdef O3S_TEST_HOOKS
   h->looks.clear();
 #endif
@@ -966,7 +985,7 @@ int start_call(o3s_icp* h, const float* T_init) {
     key.ptrs[3] = h->d_ref.p;
     key.ptrs[4] = h->have_grid1 ? h->d_cell_start1.p : h->d_cell_start.p;  // (any re-allocation moves key.gen as well; this tells the two kinds of chain apart)
     key.ptrs[5] = h->d_trace_T.p;
-    key.ptrs[6] = (const void*)(uintptr_t)((c.stats ? 1 : 0) | (h->shard.active ? 2 : 0) | (c.a.spec ? 8 : 0) | ((uintptr_t)(h->shard.active ? h->shard.world : 0) << 8));
+    key.ptrs[6] = (const void*)(uintptr_t)((c.stats ? 1 : 0) | (h->shard.active ? 2 : 0) | (c.a.spec ? 8 : 0) | (h->cfg.error_minimizer == 1 ? 16 : 0) | ((uintptr_t)(h->shard.active ? h->shard.world : 0) << 8));
     key.ptrs[7] = h->d_perm.p;
     key.cp = cp;
     key.g = h->grid;
@@ -1036,6 +1055,103 @@ int start_call(o3s_icp* h, const float* T_init) {
   if (rc != O3S_OK) return rc;
   c.live = true;
   return O3S_OK;
+}
+
+// ---- pose covariance (include/o3s_icp.h, "pose covariance"): the host's share -------------------------------------------------
+// beta, alpha, gamma of the step: fp64 on the promoted fp32 entries, each rounded once
+kern::CovAngles cov_angles(const float* T /*column-major step*/) {
+  kern::CovAngles g{};
+  g.beta = (float)(-std::asin((double)HM4(T, 2, 0)));
+  g.alpha = (float)std::atan2((double)HM4(T, 2, 1), (double)HM4(T, 2, 2));
+  const double cb = std::cos((double)g.beta);
+  g.gamma = (float)std::atan2((double)HM4(T, 1, 0) / cb, (double)HM4(T, 0, 0) / cb);
+  g.tx = HM4(T, 0, 3);
+  g.ty = HM4(T, 1, 3);
+  g.tz = HM4(T, 2, 3);
+  return g;
+}
+// cov = sigma2 * H^-1 * M * H^-1 from the 42 sums; 36 NaN when H has a zero or non-finite pivot
+void cov_finish(const double* sums /*H upper triangle (21), M upper triangle (21)*/, float sensor_std_dev, double* cov36) {
+  double H[6][6], M[6][6], Hi[6][6], X[6][6];
+  int t = 0;
+  for (int a = 0; a < 6; ++a)
+    for (int c = a; c < 6; ++c, ++t) {
+      H[a][c] = H[c][a] = sums[t];
+      M[a][c] = M[c][a] = sums[kCovTri + t];
+    }
+  for (int a = 0; a < 6; ++a)
+    for (int c = 0; c < 6; ++c) Hi[a][c] = a == c ? 1.0 : 0.0;
+  bool ok = true;
+  for (int k = 0; k < 6 && ok; ++k) {  // partial-pivot LU, carried out on [H | I]
+    int piv = k;
+    for (int r = k + 1; r < 6; ++r)
+      if (std::fabs(H[r][k]) > std::fabs(H[piv][k])) piv = r;
+    if (!(std::isfinite(H[piv][k]) && H[piv][k] != 0.0)) {
+      ok = false;
+      break;
+    }
+    if (piv != k)
+      for (int c = 0; c < 6; ++c) {
+        std::swap(H[k][c], H[piv][c]);
+        std::swap(Hi[k][c], Hi[piv][c]);
+      }
+    for (int r = k + 1; r < 6; ++r) {
+      const double f = H[r][k] / H[k][k];
+      for (int c = k; c < 6; ++c) H[r][c] -= f * H[k][c];
+      for (int c = 0; c < 6; ++c) Hi[r][c] -= f * Hi[k][c];
+    }
+  }
+  if (ok)
+    for (int k = 5; k >= 0; --k)  // back substitution
+      for (int c = 0; c < 6; ++c) {
+        double v = Hi[k][c];
+        for (int j = k + 1; j < 6; ++j) v -= H[k][j] * Hi[j][c];
+        Hi[k][c] = v / H[k][k];
+      }
+  if (!ok) {
+    for (int k = 0; k < 36; ++k) cov36[k] = std::numeric_limits<double>::quiet_NaN();
+    return;
+  }
+  const double sigma2 = (double)(sensor_std_dev * sensor_std_dev);
+  for (int a = 0; a < 6; ++a)
+    for (int c = 0; c < 6; ++c) {
+      double v = 0.0;
+      for (int j = 0; j < 6; ++j) v += Hi[a][j] * M[j][c];
+      X[a][c] = v;
+    }
+  for (int a = 0; a < 6; ++a)
+    for (int c = 0; c < 6; ++c) {
+      double v = 0.0;
+      for (int j = 0; j < 6; ++j) v += X[a][j] * Hi[j][c];
+      cov36[c * 6 + a] = sigma2 * v;
+    }
+}
+// k_cov + k_cov_post on the handle's stream and the wait for the 42 totals.  ext_*: the module-level source (device, 3 x n AoS).
+int cov_run(o3s_icp* h, int n, const float* rx, const float* ry, const float* rz, float max_out_r2, const float* ext_p, const float* ext_q,
+            const float* ext_n, const float* T_step, float sensor_std_dev, double* cov36) {
+  const int nb = std::min(kMaxPartialBlocks, nblocks(n, kern::kBlock * kern::kNePPT));  // k_normal_eq's blocks: the same for every way a chain is issued
+  HIP_TRY(h, h->d_cov.ensure(kCovBufBytes));
+  double* part = h->d_cov.as<double>();
+  double* sums = part + (size_t)kMaxPartialBlocks * kCovComps;
+  unsigned long long* t_start = reinterpret_cast<unsigned long long*>(sums + kCovComps + 2);
+  const kern::CovAngles ang = cov_angles(T_step);
+  hipLaunchKernelGGL(kern::k_cov, dim3(nb), dim3(kern::kBlock), 0, h->stream, rx, ry, rz, n, h->d_mq.as<float4>(), h->d_mn.as<float4>(),
+                     h->d_pos.as<int32_t>(), h->d_d2.as<float>(), max_out_r2, h->d_state.as<IcpState>(), ext_p, ext_q, ext_n, ang, part, t_start);
+  const uint32_t seq = h->cov_mb.next();
+  hipLaunchKernelGGL(kern::k_cov_post, dim3(1), dim3(kern::kBlock), 0, h->stream, part, nb, sums, t_start, h->cov_mb.dev, seq);
+  HIP_TRY(h, hipGetLastError());
+  double s[kCovComps + 2];
+  const double t0 = host_post::now_us();
+  const int w = host_post::fetch_post(h->cov_mb, seq, h->stream, reinterpret_cast<uint32_t*>(s), 2 * (kCovComps + 2), host_post::kPostVals, sums);
+  h->host_wait_us += host_post::now_us() - t0;
+  if (w == host_post::kPollError) return fail(h, O3S_ERR_HIP, "covariance: the kernels failed");
+  std::memcpy(&h->cov_t_start, &s[kCovComps], 8);
+  std::memcpy(&h->cov_t_end, &s[kCovComps + 1], 8);
+  cov_finish(s, sensor_std_dev, cov36);
+  return O3S_OK;
+}
+int cov_chain(o3s_icp* h, const ChainArgs& a, const float* dT, float sensor_std_dev, double* cov36) {
+  return cov_run(h, a.N, a.rx, a.ry, a.rz, a.cp.max_out_r2, nullptr, nullptr, nullptr, dT, sensor_std_dev, cov36);
 }
 
 // the per-call diagnostics of o3s_icp_host_split_ex
@@ -1146,6 +1262,15 @@ int compute_finish(o3s_icp* h, float* T_out, o3s_icp_stats* stats) {
   float tmp[16], out[16];
   hmul4(st.T_iter, c.T0, tmp);
   hmul4(c.Tc, tmp, out);
+  h->last_max_out_r2 = cp.max_out_r2;
+  std::memcpy(h->last_step, st.dT, sizeof(st.dT));
+  if (h->cfg.error_minimizer == 1) {  // the one extra pass and round trip of the configured covariance
+    const int rc = cov_chain(h, c.a, st.dT, h->cfg.sensor_std_dev, h->cov);
+    if (rc != O3S_OK) return rc;
+  } else {
+    std::memset(h->cov, 0, sizeof(h->cov));  // ErrorMinimizer::getCovariance of the base class (LPM/ErrorMinimizer.cpp:266-270)
+  }
+  h->cov_valid = h->elements_valid = true;
   std::memcpy(T_out, out, sizeof(out));
   return O3S_OK;
 }
@@ -1158,6 +1283,7 @@ int compute_impl(o3s_icp* h, const float* T_init, float* T_out, o3s_icp_stats* s
 
 int upload_reading(o3s_icp* h, const float* xyzw, const float* normals, int64_t N) {
   h->reading_ready = false;
+  h->elements_valid = false;
   h->ext_xyzw = h->ext_n = nullptr;
   if (N <= 0) {
     h->N = 0;
@@ -1210,6 +1336,8 @@ void o3s_icp_default_config(o3s_icp_config* c) {
   c->grid_cell = 0.f;
   c->sort_queries = 1;
   c->use_graph = 1;
+  c->error_minimizer = 0;
+  c->sensor_std_dev = 0.01f;
 }
 
 int o3s_icp_create(const o3s_icp_config* cfg, int device, o3s_icp** out) {
@@ -1247,6 +1375,7 @@ int o3s_icp_create(const o3s_icp_config* cfg, int device, o3s_icp** out) {
   if (e == hipSuccess) e = hipHostMalloc((void**)&h->stage, sizeof(HostStage), hipHostMallocDefault);
   if (e == hipSuccess) e = h->mb.alloc(64);
   if (e == hipSuccess) e = h->post.alloc();
+  if (e == hipSuccess) e = h->cov_mb.alloc((size_t)(host_post::kPostVals + 2 * (kCovComps + 2)) * 4);
   if (e == hipSuccess) {
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) h->wall_clock_khz = (double)khz;
@@ -1278,6 +1407,7 @@ void o3s_icp_destroy(o3s_icp* h) {
   if (h->stage) (void)hipHostFree(h->stage);
   h->mb.release();
   h->post.release();
+  h->cov_mb.release();
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   delete h;
 }
@@ -1349,6 +1479,8 @@ int o3s_icp_shard_configure(o3s_icp* h, int32_t rank, int32_t world, int64_t n_t
     return O3S_OK;
   }
   if (!fn || world < 1 || rank < 0 || rank >= world || n_total <= 0) return fail(h, O3S_ERR_BAD_ARGUMENT, "shard_configure: bad rank / world / n_total / callback");
+  if (h->cfg.error_minimizer == 1)  // (it would take one more all-reduce per call, of the 42 sums)
+    return fail(h, O3S_ERR_BAD_CONFIG, "PointToPlaneWithCovErrorMinimizer (error_minimizer 1) is not available in the sharded mode");
   HIP_TRY(h, hipSetDevice(h->device));
   if (xbuf_dev) {
     h->shard.xbuf = reinterpret_cast<uint8_t*>(xbuf_dev);
@@ -1465,6 +1597,7 @@ int o3s_icp_set_reading(o3s_icp* h, const float* xyzw, const float* normals, int
 int o3s_icp_set_reading_dev(o3s_icp* h, const void* d_xyzw, const void* d_normals, int64_t N) {
   if (!h) return O3S_ERR_BAD_ARGUMENT;
   h->reading_ready = false;
+  h->elements_valid = false;
   if (N <= 0) {
     h->N = 0;
     return fail(h, O3S_ERR_EMPTY_READING, "the reading point cloud is empty");
@@ -1613,6 +1746,7 @@ int o3s_icp_profile_match(o3s_icp* h, const float T_iter[16], int32_t reps, int3
   if (!h || !T_iter || !avg_ms || reps <= 0) return O3S_ERR_BAD_ARGUMENT;
   if (!h->ref_ready) return fail(h, O3S_ERR_NOT_INITIALIZED, "profile_match before a successful init_reference");
   if (!h->reading_ready || h->N <= 0) return fail(h, O3S_ERR_EMPTY_READING, "profile_match needs a resident reading (set_reading + compute)");
+  h->elements_valid = false;  // the state is replaced below
   HIP_TRY(h, hipSetDevice(h->device));
   int rc = ensure_iteration_buffers(h, h->N);
   if (rc != O3S_OK) return rc;
@@ -1697,6 +1831,7 @@ int o3s_icp_outlier_weights(o3s_icp* h, const float* reading_normals, const int3
   if (!h || !ids || !dists2 || !weights) return O3S_ERR_BAD_ARGUMENT;
   if (!h->ref_ready) return fail(h, O3S_ERR_NOT_INITIALIZED, "outlier_weights before a successful init_reference");
   if (N <= 0) return fail(h, O3S_ERR_EMPTY_READING, "empty matches");
+  h->elements_valid = false;
   HIP_TRY(h, hipSetDevice(h->device));
   int rc = ensure_iteration_buffers(h, (int)N);
   if (rc != O3S_OK) return rc;
@@ -1793,6 +1928,83 @@ int o3s_icp_minimize(o3s_icp* h, const float* reading_xyzw, const int32_t* ids, 
   if (b_out) std::memcpy(b_out, s.b, sizeof(s.b));
   if (x_out) std::memcpy(x_out, s.x, sizeof(s.x));
   return O3S_OK;
+}
+
+int o3s_icp_get_covariance(const o3s_icp* h, double cov36[36]) {
+  if (!h || !cov36) return O3S_ERR_BAD_ARGUMENT;
+  if (!h->cov_valid) return O3S_ERR_NOT_INITIALIZED;
+  std::memcpy(cov36, h->cov, sizeof(h->cov));
+  return O3S_OK;
+}
+
+int o3s_icp_covariance_gpu_us(const o3s_icp* h, double out2[2]) {
+  if (!h || !out2) return O3S_ERR_BAD_ARGUMENT;
+  out2[0] = out2[1] = 0.0;
+  if (h->cov_t_end > h->cov_t_start) out2[0] = 1e3 * (double)(h->cov_t_end - h->cov_t_start) / h->wall_clock_khz;
+  const unsigned long long chain_end = h->stage->state.t_end;
+  if (h->cov_valid && h->cfg.error_minimizer == 1 && h->cov_t_end > chain_end) out2[1] = 1e3 * (double)(h->cov_t_end - chain_end) / h->wall_clock_khz;
+  return O3S_OK;
+}
+
+int o3s_icp_get_last_step(const o3s_icp* h, float T_step[16]) {
+  if (!h || !T_step) return O3S_ERR_BAD_ARGUMENT;
+  if (!h->cov_valid) return O3S_ERR_NOT_INITIALIZED;
+  std::memcpy(T_step, h->last_step, sizeof(h->last_step));
+  return O3S_OK;
+}
+
+int o3s_icp_estimate_covariance(o3s_icp* h, const float* reading_c, const float* reference_c, const float* normals, int64_t K,
+                                const float T_step[16], float sensor_std_dev, double cov36[36]) {
+  if (!h || !reading_c || !reference_c || !normals || !T_step || !cov36) return O3S_ERR_BAD_ARGUMENT;
+  if (K <= 0) return fail(h, O3S_ERR_NO_POINTS, "estimate_covariance: no pairs");
+  if (K > (int64_t)(1 << 30)) return fail(h, O3S_ERR_BAD_ARGUMENT, "estimate_covariance: more than 2^30 pairs");
+  if (!(sensor_std_dev >= 0.f)) return fail(h, O3S_ERR_BAD_CONFIG, "sensor_std_dev must be >= 0");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t bytes = (size_t)K * 12;
+  HIP_TRY(h, h->d_mod_a.ensure(bytes));
+  HIP_TRY(h, h->d_mod_b.ensure(bytes));
+  HIP_TRY(h, h->d_mod_c.ensure(bytes));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // (upload_reading: a copy from pageable memory into a busy stream takes the slow path)
+  HIP_TRY(h, hipMemcpyAsync(h->d_mod_a.p, reading_c, bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->d_mod_b.p, reference_c, bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->d_mod_c.p, normals, bytes, hipMemcpyHostToDevice, h->stream));
+  return cov_run(h, (int)K, nullptr, nullptr, nullptr, 0.f, h->d_mod_a.as<float>(), h->d_mod_b.as<float>(), h->d_mod_c.as<float>(), T_step,
+                 sensor_std_dev, cov36);
+}
+
+int64_t o3s_icp_get_error_elements(o3s_icp* h, float* reading_c, float* reference_c, float* normals, int32_t* reading_idx, int64_t cap) {
+  if (!h || !h->elements_valid || h->prepared_N <= 0) return 0;
+  const int N = h->prepared_N;
+  if (hipSetDevice(h->device) != hipSuccess) return 0;
+  if (h->d_mod_d.ensure((size_t)N * 10 * 4) != hipSuccess) return 0;
+  float* d_out = h->d_mod_d.as<float>();
+  int32_t* d_keep = reinterpret_cast<int32_t*>(d_out + (size_t)N * 9);
+  const float* r = h->d_r.as<float>();
+  hipLaunchKernelGGL(kern::k_cov_elements, dim3(nblocks(N)), dim3(kern::kBlock), 0, h->stream, r, r + (size_t)N, r + 2 * (size_t)N, N,
+                     h->d_mq.as<float4>(), h->d_mn.as<float4>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->last_max_out_r2,
+                     h->d_state.as<IcpState>(), d_out, d_keep);
+  std::vector<float> out((size_t)N * 9);
+  std::vector<int32_t> keep((size_t)N), perm((size_t)N);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+      hipMemcpy(out.data(), d_out, out.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(keep.data(), d_keep, keep.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(perm.data(), h->d_perm.p, perm.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return 0;
+  int64_t K = 0;
+  for (int i = 0; i < N; ++i) {
+    if (!keep[(size_t)i]) continue;
+    if (K < cap) {
+      const float* o = &out[(size_t)i * 9];
+      for (int c = 0; c < 3; ++c) {
+        if (reading_c) reading_c[K * 3 + c] = o[c];
+        if (reference_c) reference_c[K * 3 + c] = o[3 + c];
+        if (normals) normals[K * 3 + c] = o[6 + c];
+      }
+      if (reading_idx) reading_idx[K] = perm[(size_t)i];
+    }
+    ++K;
+  }
+  return K;
 }
 
 }  // extern "C"

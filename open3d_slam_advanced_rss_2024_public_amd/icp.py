@@ -48,6 +48,9 @@ _RAISE = {
 }
 
 
+_ERROR_MINIMIZERS = {"PointToPlaneErrorMinimizer": 0, "PointToPlaneWithCovErrorMinimizer": 1}
+
+
 @dataclass
 class IcpConfig:
     """The ICP chain of open3d_slam_ros/param/icp.yaml (defaults) — one field per YAML parameter on the path."""
@@ -68,6 +71,8 @@ class IcpConfig:
     sort_queries: bool = True
     use_graph: bool = True
     match_stats: bool = False
+    error_minimizer: str = "PointToPlaneErrorMinimizer"   # or "PointToPlaneWithCovErrorMinimizer" (icp.yaml:25-27)
+    sensor_std_dev: float = 0.01        # PointToPlaneWithCovErrorMinimizer.sensorStdDev
 
     def to_c(self) -> _lib.IcpConfigC:
         if self.knn != 1:
@@ -89,6 +94,10 @@ class IcpConfig:
         c.sort_queries = int(self.sort_queries)
         c.use_graph = int(self.use_graph)
         c.match_stats = int(self.match_stats)
+        if self.error_minimizer not in _ERROR_MINIMIZERS:
+            raise InvalidModuleType(f"error minimizer {self.error_minimizer}")
+        c.error_minimizer = _ERROR_MINIMIZERS[self.error_minimizer]
+        c.sensor_std_dev = float(self.sensor_std_dev)
         return c
 
     @staticmethod
@@ -136,9 +145,14 @@ class IcpConfig:
                 cfg.max_dist_outlier = float(p.get("maxDist", 1.0))
             elif name != "NullOutlierFilter":
                 raise InvalidModuleType(f"outlier filter {name}")
-        for name, _ in modules(doc.get("errorMinimizer")):
-            if name != "PointToPlaneErrorMinimizer":
+        for name, p in modules(doc.get("errorMinimizer")):
+            if name not in _ERROR_MINIMIZERS:
                 raise InvalidModuleType(f"error minimizer {name}")
+            if int(p.get("force2D", 0)) != 0:   # PointToPlane.cpp:61: the planar minimiser is not on the accelerated path
+                raise InvalidModuleType(f"error minimizer {name} with force2D")
+            cfg.error_minimizer = name
+            if name == "PointToPlaneWithCovErrorMinimizer":
+                cfg.sensor_std_dev = float(p.get("sensorStdDev", 0.01))
         order = []
         for name, p in modules(doc.get("transformationCheckers")):
             order.append(name)
@@ -387,6 +401,62 @@ class ICP:
             self._check(rc)
             return _from_colmajor(Tout)
         return self._finish(rc, st, Tout)
+
+    def get_covariance(self) -> np.ndarray:
+        """icp.errorMinimizer->getCovariance() of the last successful compute (o3s_icp_get_covariance): 6 x 6 float64 in the
+        reference's parameter order [t_x, t_y, t_z, alpha, beta, gamma]; zeros under PointToPlaneErrorMinimizer."""
+        c = np.zeros(36, np.float64)
+        self._check_cov(self._L.o3s_icp_get_covariance(self._h, c.ctypes.data_as(C.POINTER(C.c_double))))
+        return c.reshape(6, 6).T.copy()
+
+    getCovariance = get_covariance
+
+    def _check_cov(self, rc):
+        if rc == _lib.ERR_NOT_INITIALIZED:
+            raise RuntimeError(f"[{rc}] no successful compute on this handle")
+        self._check(rc)
+
+    def estimate_covariance(self, reading_c, reference_c, normals, T_step, sensor_std_dev: float | None = None) -> np.ndarray:
+        """PointToPlaneWithCovErrorMinimizer::estimateCovariance on (K, 3) arrays of ALREADY centred pairs and the 4x4 step
+        (o3s_icp_estimate_covariance: the kernel of the fused path)."""
+        p = np.ascontiguousarray(reading_c, np.float32).reshape(-1, 3)
+        q = np.ascontiguousarray(reference_c, np.float32).reshape(-1, 3)
+        n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if not (p.shape == q.shape == n.shape):
+            raise ValueError("reading_c, reference_c and normals must have the same shape (K, 3)")
+        sigma = self.config.sensor_std_dev if sensor_std_dev is None else sensor_std_dev
+        c = np.zeros(36, np.float64)
+        self._check(self._L.o3s_icp_estimate_covariance(self._h, _fp(p), _fp(q), _fp(n), p.shape[0], _fp(_colmajor(T_step)), float(sigma),
+                                                        c.ctypes.data_as(C.POINTER(C.c_double))))
+        return c.reshape(6, 6).T.copy()
+
+    def error_elements(self):
+        """The ErrorElements of the last iteration of the last successful compute (o3s_icp_get_error_elements): centred kept pairs
+        in processing-slot order as (reading_c, reference_c, normals, reading_idx), (K, 3) fp32 each and (K,) int32."""
+        K = int(self._L.o3s_icp_get_error_elements(self._h, None, None, None, None, 0))
+        p = np.zeros((max(K, 0), 3), np.float32)
+        q = np.zeros_like(p)
+        n = np.zeros_like(p)
+        idx = np.zeros(max(K, 0), np.int32)
+        if K > 0:
+            got = int(self._L.o3s_icp_get_error_elements(self._h, _fp(p), _fp(q), _fp(n), _ip(idx), K))
+            if got != K:
+                raise RuntimeError("o3s_icp_get_error_elements: the pairs changed between two calls")
+        return p, q, n, idx
+
+    def last_step(self) -> np.ndarray:
+        """The step of the last iteration of the last successful compute (o3s_icp_get_last_step): what estimateCovariance is handed
+        together with error_elements()."""
+        t = np.zeros(16, np.float32)
+        self._check_cov(self._L.o3s_icp_get_last_step(self._h, _fp(t)))
+        return _from_colmajor(t)
+
+    def covariance_gpu_us(self):
+        """(k_cov start -> k_cov_post end, chain's final post -> k_cov_post end) of the last covariance pass, microseconds of the
+        device's clock (o3s_icp_covariance_gpu_us)."""
+        out = (C.c_double * 2)()
+        self._check(self._L.o3s_icp_covariance_gpu_us(self._h, out))
+        return float(out[0]), float(out[1])
 
     def get_max_num_iterations_reached(self) -> bool:
         """ICP::getMaxNumIterationsReached (PointMatcher.h:786)."""

@@ -50,6 +50,9 @@ class Mapper:
         self.new_value = self.ignore_odom = False
         self.flags = (0, 0, 0)
         self.iters = 0
+        # covariance of the latest scan-to-map registration (ICP.get_covariance: 6 x 6, [t, alpha beta gamma]; zeros under the plain
+        # minimiser); NaN when that registration failed and the prior was kept (Mapper.cpp:420-422), or before the first one
+        self.last_covariance = np.full((6, 6), np.nan)
         self.check = None     # set to a callable(scan inputs, state) to validate a step against the oracle
         self.calib_inv = np.eye(4)          # calibration_.inverse(); identity until set, as in the reference (Mapper.hpp) and MapperHip
         self.is_calibration_set = False     # isCalibrationSet_ (Mapper.cpp:66-85): until it is, every scan is refused (:169-174)
@@ -130,11 +133,14 @@ class Mapper:
             self.ps.set_reading(self.icp)
             corrected32 = self.icp.compute_resident(prior32)
             self.iters = self.icp.stats.iterations
+            if hasattr(self.icp, "get_covariance"):   # (the CPU tests' stand-in handles register nothing and have none)
+                self.last_covariance = self.icp.get_covariance()
             if self.check and reset:
                 self.check(self, sp, sn, prior32, corrected32)
         except RuntimeError:
             threw = 1
             corrected32 = prior32.copy()
+            self.last_covariance = np.full((6, 6), np.nan)
             self.iters = self.icp.stats.iterations
         corrected = corrected32.astype(np.float64)
         if self.new_value:
