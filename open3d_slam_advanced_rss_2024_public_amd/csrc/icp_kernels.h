@@ -535,6 +535,7 @@ struct PrepInit {
   uint32_t* sel;
   int sel_words;
   float4* mq;
+  float* cert;  // the matcher's certificates: a call never reads what an earlier call left
   IcpState* state;
   int seed_differential;
   uint32_t seq;  // sequence number of this compute(): echoed by every post of the chain (HostPost)
@@ -582,6 +583,7 @@ __global__ void __launch_bounds__(kBlock) k_read_prep(const float4* __restrict__
   int my_tile = -1;
   if (i < N) {
     if (init.mq) init.mq[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (init.cert) init.cert[i] = 0.f;
     const float4 p = in_xyzw[i];
     float T[16];
 #pragma unroll
@@ -760,6 +762,16 @@ __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
 //               its longest query needs, instead of 18 masked slots per lane for every query.
 // Three dependent round trips as before (points + incumbent | row headers | candidates), ~half the instructions and a
 // register footprint that lets every wave of a 100k-point reading be resident at once.
+//   certificate `cert[i]` (nullable) is a lower bound of the squared distance from the query's position at
+//               THIS launch to every reference point other than its match (to every reference point when it has none); 0: none.
+//               The search leaves it: every candidate that lost and every row, cell window or ring turned away unopened
+//               contributes its squared distance / the conservative bound that closed it (`others`, as o3d_take and o3d_exclude
+//               do for the loop-closure refinement), scaled down by 1e-6 for the rounding of fp32 dist2.
+//               The next launch moves the query by delta = |T p - T_prev p|.  Every other point is then still at least
+//               L = sqrt(cert) - delta away, and when the incumbent's new distance is below L^2 (1 - 1e-5) it is strictly the
+//               nearest in computed fp32 arithmetic: no tie is possible, the search would return the same slot and the same bits
+//               of d2.  A wave whose valid queries are ALL settled that way writes d2, the decoded slot and the shrunk
+//               certificate, counts its histograms and skips round trips 2 and 3; a wave with one open query searches as before.
 // ------------------------------------------------------------------------------------------------------------------
 struct Own {  // a lane's best among ITS candidates, with the matched point itself (handed to the next iteration)
   float d;
@@ -768,9 +780,12 @@ struct Own {  // a lane's best among ITS candidates, with the matched point itse
   float qx, qy, qz;
 };
 
-__device__ __forceinline__ void own_take(Own& b, float d, const float4& q, int j, float lim, bool enable) {
+// `others`: the smallest squared distance among the examined candidates that are NOT the lane's best — the candidate that loses,
+// or the best it replaces (o3d_take's rule, csrc/o3d_icp_impl.h): what the query's certificate is built from
+__device__ __forceinline__ void own_take(Own& b, float& others, float d, const float4& q, int j, float lim, bool enable) {
   const int qi = __float_as_int(q.w);
   const bool c = enable & (d <= lim) & ((d < b.d) | ((d == b.d) & (qi < b.idx)));
+  others = enable ? fminf(others, c ? b.d : d) : others;
   b.d = c ? d : b.d;
   b.idx = c ? qi : b.idx;
   b.pos = c ? j : b.pos;
@@ -890,7 +905,10 @@ constexpr int kFarMaxCells = 4096;  // the host selects the ring search when max
 // FAR: queries that the 3 x 3 x 3 cells leave open go through the occupancy words (finite maxDist) instead of the ring search.
 constexpr int kFarWaves = 5;  // waves per SIMD the far variant is compiled for: 6 spills (80 VGPRs + 8-12 B of scratch), 5 does not and is as fast
 constexpr int kFarQ = 6;      // ranges per batch of the row-disc search (4: 53.9 us, 6: 50.6 us, 8: no better, for the first iteration at C2)
-template <bool STATS, int G, int UN, int RCB, bool FAR>
+// CERT: the launch reads and leaves certificates (`cert` is not null).  Without it the kernel is the one it was before there were
+// certificates — nothing of their book-keeping is compiled in: the first iteration of a call, whose far search is bound by
+// instruction issue and has nothing to settle, and every path that keeps none (module-level entry points, sharded chain).
+template <bool STATS, int G, int UN, int RCB, bool FAR, bool CERT>
 __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz,
                                                       int N, const float4* __restrict__ ref, const uint32_t* __restrict__ cell_start,
                                                       GridParams g, IcpState* __restrict__ st,
@@ -901,9 +919,16 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
                                                       const float* __restrict__ rnx, const float* __restrict__ rny,
                                                       const float* __restrict__ rnz /*FAR: the reading's normals (nullable): the seed probe's direction*/,
                                                       int rep_mask /*level-1 replicas - 1 (15; fewer in the sharded mode, where they travel)*/,
-                                                      uint32_t* __restrict__ spec /*nullable: speculative digit histograms [kSpecWords]*/
-                                                      O3S_DBG_PARAM /*hooks build only: timing experiments (o3s_icp_profile_match)*/) {
+                                                      uint32_t* __restrict__ spec /*nullable: speculative digit histograms [kSpecWords]*/,
+                                                      float* __restrict__ cert /*CERT: the queries' certificates [N], read and rewritten; else null*/
+                                                      O3S_DBG_PARAM /*hooks build only: timing experiments (o3s_icp_profile_match)*/
+                                                      O3S_HOOK_PARAM(uint32_t* __restrict__ settled_cnt /*nullable: [kHistReplicas][2][kSpecTrace]
+                                                      per iteration: queries whose certificate held, queries of the waves that skipped the search*/)) {
   __shared__ uint32_t s_hist[kHistBins];
+#ifdef O3S_TEST_HOOKS
+  __shared__ uint32_t s_set[2];  // the block's settled queries: one global atomic per block and counter, spread over the replicas
+  if (threadIdx.x < 2) s_set[threadIdx.x] = 0u;
+#endif
   constexpr int TQ = kBlock / G;        // queries per block: ONE tile per block (straight-line code, nothing kept alive across tiles)
   constexpr int NK = (9 + G - 1) / G;   // rows of the 3x3x3 block a lane owns: t = sub, sub + G, ...
   const int sub = threadIdx.x & (G - 1);
@@ -913,14 +938,23 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
   const int i = tile * TQ + qib;
   const bool valid = i < N;
   // the state header, the query and its incumbent travel in the same round trip
+  // ... and with a certificate: the pose of the previous launch (k_solve keeps it behind the staged words), the certificate and
+  // the slot that launch left (k_classify may have re-encoded it as -2 - slot since)
   const float hv = hdr_load(st);
+  const float hp = CERT ? reinterpret_cast<const float*>(st->T_prev)[threadIdx.x & 31] : 0.f;  // T_prev[16] and, behind it, cert_seq[2]
   float px = 0.f, py = 0.f, pz = 0.f;
   float4 inc = make_float4(0.f, 0.f, 0.f, 0.f);
+  float cq = 0.f;
+  int pe = -1;
   if (valid) {
     px = rx[i];
     py = ry[i];
     pz = rz[i];
     inc = mq[i];
+    if (CERT) {
+      cq = cert[i];
+      pe = pos_out[i];
+    }
   }
   for (int k = threadIdx.x; k < kHistBins; k += kBlock) s_hist[k] = 0u;
   if (hdr_i(hv, H_DONE)) return;
@@ -932,6 +966,8 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
     // the speculative histograms of the NEXT iteration (the other parity: k_classify of the previous iteration has read it)
     if (spec)
       for (int k = threadIdx.x; k < kSpecHalf; k += kBlock) spec[(size_t)((hdr_i(hv, H_ITER) + 1) & 1) * kSpecHalf + k] = 0u;
+    // this launch leaves a certificate for every query (the other slot is the one this launch reads)
+    if (CERT && threadIdx.x == 0) st->cert_seq[hdr_i(hv, H_ITER) & 1] = (uint32_t)hdr_i(hv, H_ITER) + 1u;
   }
   // the previous iteration's limit of this call (the state is reset per call: +inf in iteration 0) predicts this one's: the
   // pairs that share its leading 11 / 21 bits also count their next digit, so that k_classify can resolve the limit further
@@ -955,11 +991,78 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
   // maxDist the ring search would walk every ring of the grid for it
   bool active = valid && ((fabsf(sx) + fabsf(sy)) + fabsf(sz) < kInfF);
   float bound = lim;
+  // a found match is counted where it is written: the level-1 bin of its d2 in the block's histogram (the first toucher of a bin
+  // flushes it at the end) and, under a finite previous limit, the next digit of the pairs that share its leading 11 / 21 bits
+  int mybin = -1;
+  auto count_match = [&](float d) {
+    const int bin = (int)((__float_as_uint(d) >> 20) & (kHistBins - 1));
+    if (!O3S_DBG(1) && atomicAdd(&s_hist[bin], 1u) == 0u) mybin = bin;
+    if (spec_on && !O3S_DBG(1)) {  // ~2 % of the lanes: plain global atomics
+      const uint32_t key = __float_as_uint(d) & 0x7fffffffu;
+      if ((key >> 20) == (hint >> 20)) atomicAdd(&spec_cur[(key >> 10) & 1023u], 1u);
+      if ((key >> 10) == (hint >> 10)) atomicAdd(&spec_cur[1024 + (key & 1023u)], 1u);
+    }
+  };
+  // ---- the certificate's fast path: a query that moved by less than its certificate leaves room for keeps its match (or stays
+  //      unmatched) without a search; a wave of such queries writes its outputs here and is done ----
+  bool wave_settled = false;
+  if (CERT) {
+    float Tp[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) Tp[k] = hdr_f(hp, k);
+    bool settled = false;
+    float dn = 0.f, cn = 0.f;
+    // the certificates are those of the launch right before this one (IcpState::cert_seq): uniform
+    const bool fresh = (uint32_t)hdr_i(hp, 16 + ((hdr_i(hv, H_ITER) + 1) & 1)) == (uint32_t)hdr_i(hv, H_ITER);
+    if (fresh && active && cq > 0.f) {
+      const float ex = sx - xf_row(Tp, 0, px, py, pz), ey = sy - xf_row(Tp, 1, px, py, pz), ez = sz - xf_row(Tp, 2, px, py, pz);
+      const float delta = __builtin_sqrtf((ex * ex + ey * ey) + ez * ez) * (1.f + 1e-6f);  // rounded up
+      const float L = __builtin_sqrtf(cq) - delta;
+      const float L2 = L * L, thr = L2 * (1.f - 1e-5f);
+      cn = L2 * (1.f - 1e-6f);
+      if (inc.w != 0.f) {
+        dn = dist2(sx, sy, sz, inc.x, inc.y, inc.z);
+        settled = (L > 0.f) & (pe != -1) & (dn <= lim) & (dn < thr);
+      } else {
+        settled = (L > 0.f) & (thr > lim);
+      }
+    }
+    wave_settled = __all(!valid || settled);
+#ifdef O3S_TEST_HOOKS
+    if (settled_cnt && hdr_i(hv, H_ITER) < kSpecTrace) {
+      const int n_set = __popcll(__ballot(settled && sub == 0));
+      if ((threadIdx.x & 63) == 0 && n_set) {
+        atomicAdd(&s_set[0], (uint32_t)n_set);
+        if (wave_settled) atomicAdd(&s_set[1], (uint32_t)n_set);
+      }
+    }
+#endif
+    if (wave_settled && !O3S_DBG(8)) {
+      if (valid && sub == 0) {
+        if (inc.w != 0.f) {  // mq and mn keep the match they hold
+          pos_out[i] = pe >= 0 ? pe : -2 - pe;
+          d2_out[i] = dn;
+          count_match(dn);
+        }
+        cert[i] = cn;
+      }
+    }
+    active = active && !wave_settled;
+  }
   if (active) {
     // ---- pruning bound: the previous correspondence under the new pose (any reference point is an upper bound) ----
     const float di = dist2(sx, sy, sz, inc.x, inc.y, inc.z);
     bound = ((inc.w != 0.f) & (di <= lim)) ? di : lim;  // NaN -> lim
   }
+  float others = kInfF;  // this lane's part of the query's next certificate
+  // the certificate a search leaves: what every lane of the group turned away or saw lose, a lane's own best included unless it
+  // is the winner; a hair below, for the rounding of dist2.  None for a query that is not a number.
+  auto group_cert = [&](float o) {
+    float cn = (gi != 0x7fffffff && b.idx == gi) ? o : fminf(o, b.d);
+    if (G >= 2) cn = fminf(cn, __int_as_float(dpp_i32<0xB1>(__float_as_int(cn))));
+    if (G >= 4) cn = fminf(cn, __int_as_float(dpp_i32<0x4E>(__float_as_int(cn))));
+    return ((fabsf(sx) + fabsf(sy)) + fabsf(sz) < kInfF) ? cn * (1.f - 1e-6f) : 0.f;
+  };
   // ---- seed probe (first iteration of a call, unmatched points: no incumbent).  Without a bound the far search opens every row
   //      and every cell window at full radius until it finds something — at C4 that is 430 distance tests per query where 60
   //      would do.  A query that carries a normal looks along it: the cells the line  s +- k cell n  passes through, k = 1 ..
@@ -969,7 +1072,7 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
   //      misses (a query 0.3 m above a floor hits the cell under it; a bad normal just finds nothing).
   //      Only where the far search has many rings to walk (maxDist >= 5 cells: dense maps, C4): at C2's three cells the probe
   //      costs what it saves (first iteration 40.7 us without, 42.1 us with).
-  if (FAR && rnx != nullptr && lim * g.inv_cell * g.inv_cell >= 25.f && __any(valid && inc.w == 0.f)) {  // uniform
+  if (FAR && rnx != nullptr && lim * g.inv_cell * g.inv_cell >= 25.f && !wave_settled && __any(valid && inc.w == 0.f)) {  // uniform
     constexpr int kProbeSteps = 12;  // per direction; more cells than that to maxDist: the probe stops short (still a valid bound)
     constexpr int NP = (2 * kProbeSteps + G - 1) / G;  // probe cells per lane
     const bool want = valid && inc.w == 0.f;
@@ -1043,9 +1146,15 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
         const float gy2 = dy < 0 ? gyn2 : (dy > 0 ? gyp2 : 0.f);
         const float g2 = gz2 + gy2;
         const float rem = bound - g2;  // what the x direction may still spend (+inf stays +inf)
-        const int lo = max(c.cx - (int)!(gxn2 > rem), 0);
-        const int hi = min(c.cx + (int)!(gxp2 > rem), g.nx - 1);
-        const bool in = (t < 9) & (lo <= hi) & ((unsigned)y < (unsigned)g.ny) & ((unsigned)z < (unsigned)g.nz) & !(g2 > bound) & !O3S_DBG(4);
+        const bool lskip = gxn2 > rem, rskip = gxp2 > rem;
+        const int lo = max(c.cx - (int)!lskip, 0);
+        const int hi = min(c.cx + (int)!rskip, g.nx - 1);
+        const bool row = (t < 9) & ((unsigned)y < (unsigned)g.ny) & ((unsigned)z < (unsigned)g.nz);
+        const bool in = row & (lo <= hi) & !(g2 > bound) & !O3S_DBG(4);
+        // the certificate's share of what stays shut: the whole row, or its left / right cell (cells outside the grid hold nothing)
+        const float ol = (lskip & ((unsigned)(c.cx - 1) < (unsigned)g.nx)) ? g2 + gxn2 : kInfF;
+        const float orr = (rskip & ((unsigned)(c.cx + 1) < (unsigned)g.nx)) ? g2 + gxp2 : kInfF;
+        others = row ? fminf(others, (g2 > bound) ? g2 : fminf(ol, orr)) : others;
         inm[k] = (uint32_t) - (int)in;
         span[k] = hi - lo;  // 0..2 open cells beyond the first
         const uint32_t off = (((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx + (uint32_t)lo) & inm[k];
@@ -1091,7 +1200,7 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
         qv[u] = ref[jj[u]];
       }
 #pragma unroll
-      for (int u = 0; u < UN; ++u) own_take(b, dist2(sx, sy, sz, qv[u].x, qv[u].y, qv[u].z), qv[u], (int)jj[u], lim, ok[u]);
+      for (int u = 0; u < UN; ++u) own_take(b, others, dist2(sx, sy, sz, qv[u].x, qv[u].y, qv[u].z), qv[u], (int)jj[u], lim, ok[u]);
     }
   }
   group_min_di<G>(b.d, b.idx, gd, gi);
@@ -1101,7 +1210,16 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
   //      the wave is still open. ----
   {
     const float q = g.cell - g.margin;
-    active = active && !(q * q > fminf(gd, bound)) && !O3S_DBG(16);
+    const bool far = active && !(q * q > fminf(gd, bound)) && !O3S_DBG(16);
+    // a query that stops here leaves everything beyond the 3x3x3 block unopened: at least cell - margin away
+    if (active && !far) others = fminf(others, q * q);
+    // the ring search for an unbounded maxDist keeps no account of what it passes over: its queries get no certificate, and the
+    // others' is complete here — written now, so that it is not kept alive across the rings (the kernel is at its register limit)
+    if (!FAR && CERT && valid && !wave_settled && !O3S_DBG(8)) {
+      const float cn = group_cert(far ? 0.f : others);
+      if (sub == 0) cert[i] = cn;
+    }
+    active = far;
   }
   if (FAR) {
     if (__any(active)) {
@@ -1117,6 +1235,8 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
         const float lb = (float)(r - 1) * g.cell + m_yz - g.margin;
         return (r >= 2 && lb > 0.f) ? lb * lb : 0.f;
       };
+      // (the certificate: the rings from rho on are at least ring_lb2_yz(rho) away, here and where the walk ends below)
+      if (active && rho <= rho_max && ring_lb2_yz(rho) > best) others = fminf(others, ring_lb2_yz(rho));
       if (rho > rho_max || ring_lb2_yz(rho) > best) active = false;
       uint32_t qa[Q], qb[Q];  // queued cell ranges [qa, qb) of the cell-sorted reference
 #pragma unroll
@@ -1150,7 +1270,10 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
               const float gy = cell_gap(dy, c.ly, g.cell, g.margin), gz = cell_gap(dz, c.lz, g.cell, g.margin);
               const float g2 = gy * gy + gz * gz;
               const float bl = fminf(best, b.d);
-              if (g2 > bl) continue;
+              if (g2 > bl) {
+                others = fminf(others, g2);  // the row stays shut
+                continue;
+              }
               if (O3S_DBG(64)) continue;  // hooks build, timing only: the enumeration of the rings' rows and their gap test alone
               // x window: gap(dx) <= s  <=>  dx <= (s + lx) / cell  and  -dx <= (s - lx) / cell + 1, s = sqrt(rest) + margin; the float
               // estimate may fall one cell short, so the next cell out is tested with the bound's own comparison
@@ -1161,6 +1284,10 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
                 const float gr = cell_gap(kr + 1, c.lx, g.cell, g.margin), gl = cell_gap(-(kl + 1), c.lx, g.cell, g.margin);
                 kr += !(gr * gr > rest) ? 1 : 0;
                 kl += !(gl * gl > rest) ? 1 : 0;
+              }
+              {  // the cells of the row beyond the window stay shut: the first one out on either side bounds them all
+                const float gr = cell_gap(kr + 1, c.lx, g.cell, g.margin), gl = cell_gap(-(kl + 1), c.lx, g.cell, g.margin);
+                others = fminf(others, g2 + fminf(c.cx + kr + 1 < g.nx ? gr * gr : kInfF, c.cx - kl - 1 >= 0 ? gl * gl : kInfF));
               }
               const int x_lo = max(c.cx - kl, 0), x_hi = min(c.cx + kr, g.nx - 1);
               if (x_lo > x_hi) continue;
@@ -1225,7 +1352,7 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
                   qv[v] = ref[jj[v]];
                 }
 #pragma unroll
-                for (int v = 0; v < RCB; ++v) own_take(b, dist2(sx, sy, sz, qv[v].x, qv[v].y, qv[v].z), qv[v], (int)jj[v], lim, ok[v]);
+                for (int v = 0; v < RCB; ++v) own_take(b, others, dist2(sx, sy, sz, qv[v].x, qv[v].y, qv[v].z), qv[v], (int)jj[v], lim, ok[v]);
               }
             }
             if (t >= n_rows_r) break;
@@ -1235,6 +1362,7 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
         best = fminf(best, gd);
         if (active) {
           rho += 1;
+          if (rho <= rho_max && ring_lb2_yz(rho) > best) others = fminf(others, ring_lb2_yz(rho));
           if (rho > rho_max || ring_lb2_yz(rho) > best) active = false;
         }
       }
@@ -1246,6 +1374,7 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
     float m = 0.f;
     ring_range(c, g, r, rmax, m);
     const float extra2 = outside_extra2(sx, sy, sz, g);
+    float no_cert = 0.f;  // (what own_take would add to a certificate: these queries have none)
     if (r > rmax || ring_lb2(r, m, g) + extra2 > fminf(gd, bound)) active = false;
     while (__any(active)) {
       if (active) {
@@ -1303,7 +1432,7 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
 #pragma unroll
                 for (int v = 0; v < RCB; ++v) q[v] = ref[j + v < j1 ? j + v : j0];
 #pragma unroll
-                for (int v = 0; v < RCB; ++v) own_take(b, dist2(sx, sy, sz, q[v].x, q[v].y, q[v].z), q[v], (int)(j + v), lim, j + v < j1);
+                for (int v = 0; v < RCB; ++v) own_take(b, no_cert, dist2(sx, sy, sz, q[v].x, q[v].y, q[v].z), q[v], (int)(j + v), lim, j + v < j1);
               }
               if (STATS) {
                 n_rows += j1 > j0 ? 1 : 0;
@@ -1322,9 +1451,9 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
   }
   // ---- outputs: the lane that examined the winner writes it (slot, d2, the matched point for the next iteration);
   //      lane 0 of the group writes the "no match" record.  Level-1 histogram as in k_match. ----
-  int mybin = -1;
-  if (valid && !O3S_DBG(8)) {
+  if (valid && !wave_settled && !O3S_DBG(8)) {
     const bool found = gi != 0x7fffffff;
+    const float cn = (FAR && CERT) ? group_cert(others) : 0.f;  // (the ring-search variant has written its certificates before the rings)
     // two lanes of a group never examine the same reference point (disjoint rows; the central cells are left to the first
     // stage), but should they ever hold the same winner exactly one may write it and count it: the lowest lane that holds it
     bool mine = found && b.idx == gi && b.pos >= 0;
@@ -1343,21 +1472,21 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
       d2_out[i] = b.d;
       mq[i] = make_float4(b.qx, b.qy, b.qz, 1.f);
       if (mn) mn[i] = nq;
-      const int bin = (int)((__float_as_uint(b.d) >> 20) & (kHistBins - 1));
-      if (!O3S_DBG(1) && atomicAdd(&s_hist[bin], 1u) == 0u) mybin = bin;
-      if (spec_on && !O3S_DBG(1)) {  // ~2 % of the lanes: plain global atomics
-        const uint32_t key = __float_as_uint(b.d) & 0x7fffffffu;
-        if ((key >> 20) == (hint >> 20)) atomicAdd(&spec_cur[(key >> 10) & 1023u], 1u);
-        if ((key >> 10) == (hint >> 10)) atomicAdd(&spec_cur[1024 + (key & 1023u)], 1u);
-      }
+      if (FAR && CERT) cert[i] = cn;
+      count_match(b.d);
     } else if (!found && sub == 0) {
       pos_out[i] = -1;
       d2_out[i] = kInfF;
       mq[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (mn) mn[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (FAR && CERT) cert[i] = cn;
     }
   }
   __syncthreads();
+#ifdef O3S_TEST_HOOKS
+  if (CERT && settled_cnt && threadIdx.x < 2 && s_set[threadIdx.x] && hdr_i(hv, H_ITER) < kSpecTrace)
+    atomicAdd(&settled_cnt[((blockIdx.x & (kHistReplicas - 1)) * 2 + threadIdx.x) * kSpecTrace + hdr_i(hv, H_ITER)], s_set[threadIdx.x]);
+#endif
   if (mybin >= 0) atomicAdd(&hist_rep[(size_t)(blockIdx.x & (unsigned)rep_mask) * kHistBins + mybin], s_hist[mybin]);
   if (STATS) {
     n_cand = wave_sum_u64(n_cand);
@@ -2798,9 +2927,10 @@ __global__ void __launch_bounds__(kBlock) k_export_matches(int N, const int32_t*
 __global__ void __launch_bounds__(kBlock) k_import_matches(int N, const int32_t* __restrict__ ids, const float* __restrict__ dists,
                                                            const float* __restrict__ weights /*nullable*/, const int32_t* __restrict__ orig_to_sorted,
                                                            int64_t M, const float4* __restrict__ ref, int32_t* __restrict__ pos, float* __restrict__ d2,
-                                                           float4* __restrict__ mq) {
+                                                           float4* __restrict__ mq, float* __restrict__ cert /*nullable*/) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= N) return;
+  if (cert) cert[i] = 0.f;  // the matcher's certificates spoke of the matches this replaces
   const int id = ids[i];
   const float d = dists[i];
   int pe = -1;

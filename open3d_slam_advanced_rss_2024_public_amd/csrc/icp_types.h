@@ -8,17 +8,20 @@
 // -DO3S_TEST_HOOKS): the product library never reads the environment and its kernels carry no work-skipping switch.
 //   O3S_HOOK_ENV(name)   getenv in the hooks build, NULL in the product
 //   O3S_DBG(bits)        `dbg & bits` inside a kernel that received O3S_DBG_PARAM; constant false in the product
+//   O3S_HOOK_PARAM(decl) one more kernel parameter in the hooks build (its argument: O3S_DBG_ARG), none in the product
 #ifdef O3S_TEST_HOOKS
 #include <stdlib.h>
 #define O3S_HOOK_ENV(name) getenv(name)
 #define O3S_DBG_PARAM , int dbg
 #define O3S_DBG_ARG(x) , (x)
+#define O3S_HOOK_PARAM(decl) , decl
 #define O3S_DBG(bits) ((dbg & (bits)) != 0)
 #define O3S_CP_DBG(cp, bits) (((cp).dbg & (bits)) != 0)
 #else
 #define O3S_HOOK_ENV(name) ((const char*)0)
 #define O3S_DBG_PARAM
 #define O3S_DBG_ARG(x)
+#define O3S_HOOK_PARAM(decl)
 #define O3S_DBG(bits) false
 #define O3S_CP_DBG(cp, bits) false
 #endif
@@ -107,11 +110,19 @@ struct IcpState {
                                   // what the pose covariance (k_cov) and o3s_icp_get_error_elements rebuild that iteration's pairs from.
                                   // Stored straight to the device state by the closing step (16 lanes, nobody waits for it) and read
                                   // there: it takes no part in the staging of solve_body nor in the post, which stay 254 words
+  uint32_t cert_seq[2];           // k_match2's certificates: slot (i & 1) holds i + 1 once the matcher launch of iteration i has left a
+                                  // certificate for every query.  The next launch honours them only when it finds its own iteration
+                                  // number there: a launch that keeps none in between (the first node of a replayed graph chunk is the
+                                  // first-iteration kernel again) leaves the certificates behind the matches, and they must not be used.
+                                  // Two slots, so that no block reads the word block 0 of the same launch writes.
+  uint32_t tail_pad[14];          // T_prev and cert_seq arrive with one 128-byte load, like the header
 };
 constexpr int kStateWords = (int)(offsetof(IcpState, T_prev) / 4);  // the state as the closing step stages it through LDS and posts it
 constexpr int kStateTailWords = 4;  // cand_count / row_count, the last of those: only ever touched by the matcher's atomics, never by a state write-back
 static_assert(offsetof(IcpState, T_prev) == offsetof(IcpState, row_count) + 8, "the staged words end with the matcher's counters");
 static_assert(sizeof(IcpState) % 4 == 0, "IcpState is copied word-wise");
+static_assert(offsetof(IcpState, cert_seq) == offsetof(IcpState, T_prev) + 64 && sizeof(IcpState) == offsetof(IcpState, T_prev) + 128,
+              "k_match2 loads T_prev and cert_seq as one 32-word block");
 
 // One in-bin candidate of the trim selection: everything the finishing kernel needs, so it never chases an index.
 struct CandRec {

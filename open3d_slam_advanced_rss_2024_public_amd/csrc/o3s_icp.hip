@@ -70,6 +70,10 @@ struct HostStage {  // pinned staging block for small H2D / D2H transfers
 constexpr int kNumKernels = 5;
 constexpr size_t kCovBufBytes = ((size_t)kMaxPartialBlocks * kCovComps + kCovComps + 3) * sizeof(double);  // k_cov's partials [42][blocks], the 42 totals + 2 stamps, k_cov's start
 constexpr size_t kHistWords = (size_t)kHistReplicas * kHistBins + 1024;  // level-1 replicas + the level-2 histogram right behind them
+// hooks build: per-iteration traces behind the speculative histograms — the depth k_classify resolved, then the matcher's two
+// counters of settled queries (certificate held | the wave skipped its search) in kHistReplicas copies: one atomic per wave onto
+// one word made the hooks build's converged launch 39 us
+constexpr size_t kHookTraceWords = (1 + 2 * (size_t)kHistReplicas) * kSpecTrace;
 
 struct ChainArgs {
   int N;
@@ -78,6 +82,7 @@ struct ChainArgs {
   int nb_fused;  // blocks of the fused selection + normal-equation kernel (0: the two kernels are launched separately)
   bool has_n;
   uint32_t* spec;  // the speculative digit histograms of the trim selection (k_match2 -> k_classify); null: level 1 only
+  float* cert;     // the matcher's certificates (k_match2 -> the next k_match2); null: every query is searched in every iteration
   float *rx, *ry, *rz, *rnx, *rny, *rnz;
   ChainParams cp;
   GridParams g;
@@ -138,6 +143,7 @@ struct o3s_icp {
   // iteration chain
   DevBuf d_mn;  // matched reference normal of every query (written by k_classify, streamed by k_normal_eq)
   DevBuf d_mq;  // matched reference point of every query (k_match2: this iteration's output, the next one's pruning bound)
+  DevBuf d_cert;  // ... and its certificate: a lower bound of the squared distance to every OTHER reference point (0: none)
   DevBuf d_cand_cnt;
   DevBuf d_sel_part2, d_park;  // k_sel_partial (large readings): block partials [7][blocks]; parked records [kParkRecs] + their order keys
   DevBuf d_pos, d_d2, d_hist, d_cand, d_sel, d_cent, d_ne, d_state, d_T0, d_trace_T, d_trace_limit, d_trace_kept;
@@ -184,7 +190,7 @@ struct o3s_icp {
   std::vector<DevBuf*> all_bufs() {
     return {&d_ref_in, &d_refn_in, &d_ref, &d_refn, &d_cell_start, &d_cell_tmp, &d_qstart, &d_orig_to_sorted, &d_cell_of, &d_scan_sums,
             &d_ref_part, &d_ref_bb, &d_ref1, &d_refn1, &d_cell_start1, &d_in_xyzw, &d_in_n, &d_t, &d_r, &d_perm, &d_qcell, &d_qcount, &d_pos, &d_d2, &d_hist, &d_cand, &d_cand_cnt, &d_sel_part2, &d_park, &d_sel, &d_cent,
-            &d_ne, &d_state, &d_T0, &d_mq, &d_mn, &d_trace_T, &d_trace_limit, &d_trace_kept, &d_mod_a, &d_mod_b, &d_mod_c, &d_mod_d, &d_cov, &shard.own};
+            &d_ne, &d_state, &d_T0, &d_mq, &d_cert, &d_mn, &d_trace_T, &d_trace_limit, &d_trace_kept, &d_mod_a, &d_mod_b, &d_mod_c, &d_mod_d, &d_cov, &shard.own};
   }
 
   // graph cache
@@ -554,8 +560,9 @@ int ensure_iteration_buffers(o3s_icp* h, int N) {
   HIP_TRY(h, h->d_pos.ensure((size_t)N * 4));
   HIP_TRY(h, h->d_d2.ensure((size_t)N * 4));
   HIP_TRY(h, h->d_mq.ensure((size_t)N * sizeof(float4)));
+  HIP_TRY(h, h->d_cert.ensure((size_t)N * 4));
   HIP_TRY(h, h->d_mn.ensure((size_t)N * sizeof(float4)));
-  HIP_TRY(h, h->d_hist.ensure((kHistWords + kSpecWords + kSpecTrace) * 4));  // + the speculative digit histograms (+ the hooks build's depth trace)
+  HIP_TRY(h, h->d_hist.ensure((kHistWords + kSpecWords + kHookTraceWords) * 4));  // + the speculative digit histograms (+ the hooks build's traces)
   HIP_TRY(h, h->d_cand.ensure((size_t)nblocks(N, kern::kClsBlock) * kern::kClsBlock * sizeof(CandRec)));  // one region per classify block
   HIP_TRY(h, h->d_cand_cnt.ensure(((size_t)nblocks(N, kern::kClsBlock) * 2 + 2) * 4));  // counts [nb] + bases [nb + 1]
   HIP_TRY(h, h->d_sel.ensure(sizeof(SelScratch)));
@@ -622,6 +629,11 @@ ChainArgs chain_args(o3s_icp* h, const ChainParams& cp) {
     const bool spec = cp.has_trim && !cp.mirror && !h->shard.active && !(ne && std::atoi(ne) != 0);
     a.spec = spec ? h->d_hist.as<uint32_t>() + kHistWords : nullptr;
   }
+  {  // certificates: single-GPU KDTree chains (O3S_NO_CERT=1: none; a work-skipping switch of O3S_DBG would falsify them)
+    const char* nc = O3S_HOOK_ENV("O3S_NO_CERT");  // read per call: the tests run both in one process
+    const bool on = !cp.mirror && !h->shard.active && !(nc && std::atoi(nc) != 0) && !O3S_CP_DBG(cp, ~0);
+    a.cert = on ? h->d_cert.as<float>() : nullptr;
+  }
   float* r = h->d_r.as<float>();
   a.rx = r;
   a.ry = r + (size_t)h->N;
@@ -666,19 +678,22 @@ inline RefIndex chain_index(o3s_icp* h, const ChainParams& cp, int it) {
     return RefIndex{h->d_ref1.as<float4>(), h->ref_has_normals ? h->d_refn1.as<float4>() : h->d_refn.as<float4>(), h->d_cell_start1.as<uint32_t>(), h->grid1};
   return main_index(h);
 }
-template <bool STATS, int G>
-void launch_match2(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, const RefIndex& ix, uint32_t* spec, hipStream_t s) {
+template <bool STATS, int G, bool CERT>
+void launch_match2(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, const RefIndex& ix, uint32_t* spec, float* cert, hipStream_t s) {
+#ifdef O3S_TEST_HOOKS
+  uint32_t* const settled = CERT ? h->d_hist.as<uint32_t>() + kHistWords + kSpecWords + kSpecTrace : nullptr;
+#endif
   const int nb = round_up8(nblocks(a.N, kern::kBlock / G));  // one tile of kBlock / G queries per block
   if (h->far_rows)
-    hipLaunchKernelGGL((kern::k_match2<STATS, G, 2, 4, true>), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, ix.ref, ix.cell_start, ix.g,
+    hipLaunchKernelGGL((kern::k_match2<STATS, G, 2, 4, true, CERT>), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, ix.ref, ix.cell_start, ix.g,
                        h->d_state.as<IcpState>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_mq.as<float4>(), chain_hist(h), ix.refn,
                        normals_from_matcher(a) ? h->d_mn.as<float4>() : (float4*)nullptr, a.has_n ? a.rnx : (const float*)nullptr, a.rny, a.rnz,
-                       chain_replicas(h) - 1, spec O3S_DBG_ARG(cp.dbg));
+                       chain_replicas(h) - 1, spec, CERT ? cert : (float*)nullptr O3S_DBG_ARG(cp.dbg) O3S_DBG_ARG(settled));
   else
-    hipLaunchKernelGGL((kern::k_match2<STATS, G, 2, 2, false>), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, ix.ref, ix.cell_start, ix.g,
+    hipLaunchKernelGGL((kern::k_match2<STATS, G, 2, 2, false, CERT>), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, ix.ref, ix.cell_start, ix.g,
                        h->d_state.as<IcpState>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_mq.as<float4>(), chain_hist(h), ix.refn,
                        normals_from_matcher(a) ? h->d_mn.as<float4>() : (float4*)nullptr, a.has_n ? a.rnx : (const float*)nullptr, a.rny, a.rnz,
-                       chain_replicas(h) - 1, spec O3S_DBG_ARG(cp.dbg));
+                       chain_replicas(h) - 1, spec, CERT ? cert : (float*)nullptr O3S_DBG_ARG(cp.dbg) O3S_DBG_ARG(settled));
 }
 // `first`: the first iteration of a call — no incumbents yet, half the queries go through the far search.  Up to 200 k points
 // it runs with FOUR lanes per query whatever the steady-state choice: the far search is a chain of dependent round trips per lane,
@@ -687,7 +702,8 @@ void launch_match2(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, const 
 inline int match_lanes(const o3s_icp* h, const ChainArgs& a, bool first) {
   return (first && h->far_rows && a.N < 200000) ? 4 : a.match_g;
 }
-void launch_match2_any(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, bool stats, bool first, const RefIndex& ix, uint32_t* spec, hipStream_t s) {
+void launch_match2_any(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, bool stats, bool first, const RefIndex& ix, uint32_t* spec, float* cert,
+                       hipStream_t s) {
   if (cp.mirror) {
     hipLaunchKernelGGL(kern::k_match_mirror, dim3(nblocks(a.N)), dim3(kern::kBlock), 0, s, a.N, h->d_ref.as<float4>(), h->d_orig_to_sorted.as<int32_t>(),
                        h->d_perm.as<int32_t>(), h->d_state.as<IcpState>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_mq.as<float4>(),
@@ -695,20 +711,29 @@ void launch_match2_any(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, bo
     return;
   }
   const int G = match_lanes(h, a, first);
+  auto go = [&](auto st_, auto g_) {
+    if (cert) launch_match2<decltype(st_)::value, decltype(g_)::value, true>(h, a, cp, ix, spec, cert, s);
+    else launch_match2<decltype(st_)::value, decltype(g_)::value, false>(h, a, cp, ix, spec, cert, s);
+  };
+  using std::integral_constant;
   if (stats) {
-    if (G == 2) launch_match2<true, 2>(h, a, cp, ix, spec, s);
-    else launch_match2<true, 4>(h, a, cp, ix, spec, s);
+    if (G == 2) go(std::true_type{}, integral_constant<int, 2>{});
+    else go(std::true_type{}, integral_constant<int, 4>{});
   } else {
-    if (G == 2) launch_match2<false, 2>(h, a, cp, ix, spec, s);
-    else launch_match2<false, 4>(h, a, cp, ix, spec, s);
+    if (G == 2) go(std::false_type{}, integral_constant<int, 2>{});
+    else go(std::false_type{}, integral_constant<int, 4>{});
   }
 }
 void launch_match_any(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, bool stats, hipStream_t s, bool first = false) {
-  launch_match2_any(h, a, cp, stats, first, main_index(h), nullptr, s);  // module-level entry points: no speculation
+  launch_match2_any(h, a, cp, stats, first, main_index(h), nullptr, nullptr, s);  // module-level entry points: no speculation, no certificates
 }
 // the matcher launch of iteration `it` of a chain, on the index chain_index() picks for it
 void launch_match_chain(o3s_icp* h, const ChainArgs& a, bool stats, hipStream_t s, int it, const RefIndex& ix) {
-  launch_match2_any(h, a, a.cp, stats, it == 0, ix, a.spec, s);
+  // the first iteration of a call keeps no certificates: its far search is bound by instruction issue (their book-keeping cost it
+  // 6 us at C2), the pose still moves by millimetres behind it, and on the first-iteration index its slots are in THAT index's
+  // order, which nothing may carry on.  They stay 0, as k_read_prep left them: iteration 1 searches every query and leaves them.
+  float* const cert = it == 0 ? nullptr : a.cert;
+  launch_match2_any(h, a, a.cp, stats, it == 0, ix, a.spec, cert, s);
 }
 
 // large readings (more classify blocks than the finishing block has threads): the candidate sweep of the two-kernel chain runs on many
@@ -831,11 +856,12 @@ int prepare_reading(o3s_icp* h, const float* T0, bool sort, bool reset_chain, bo
     init.hist = chain_hist(h);
     init.hist_words = h->shard.active ? (int)(kXchgL1Words + kShardL2Bins) : (int)kHistWords;  // level-1 replicas + the level-2 histogram behind them
 #ifdef O3S_TEST_HOOKS
-    if (!h->shard.active) init.hist_words += kSpecWords + kSpecTrace;  // hooks build: the depth trace starts empty every call
+    if (!h->shard.active) init.hist_words += (int)(kSpecWords + kHookTraceWords);  // hooks build: the traces start empty every call
 #endif
     init.sel = h->d_sel.as<uint32_t>();
     init.sel_words = (int)(sizeof(SelScratch) / 4);
     init.mq = h->d_mq.as<float4>();
+    init.cert = h->d_cert.as<float>();
     init.state = h->d_state.as<IcpState>();
     init.seed_differential = seed_differential ? 1 : 0;
     init.seq = h->call_seq;
@@ -985,7 +1011,7 @@ int start_call(o3s_icp* h, const float* T_init) {
     key.ptrs[3] = h->d_ref.p;
     key.ptrs[4] = h->have_grid1 ? h->d_cell_start1.p : h->d_cell_start.p;  // (any re-allocation moves key.gen as well; this tells the two kinds of chain apart)
     key.ptrs[5] = h->d_trace_T.p;
-    key.ptrs[6] = (const void*)(uintptr_t)((c.stats ? 1 : 0) | (h->shard.active ? 2 : 0) | (c.a.spec ? 8 : 0) | (h->cfg.error_minimizer == 1 ? 16 : 0) | ((uintptr_t)(h->shard.active ? h->shard.world : 0) << 8));
+    key.ptrs[6] = (const void*)(uintptr_t)((c.stats ? 1 : 0) | (h->shard.active ? 2 : 0) | (c.a.spec ? 8 : 0) | (h->cfg.error_minimizer == 1 ? 16 : 0) | (c.a.cert ? 32 : 0) | ((uintptr_t)(h->shard.active ? h->shard.world : 0) << 8));
     key.ptrs[7] = h->d_perm.p;
     key.cp = cp;
     key.g = h->grid;
@@ -1689,6 +1715,39 @@ int o3s_icp_hook_sel_depth(const o3s_icp* h, int32_t* depth, int32_t cap) {
   if (hipMemcpy(depth, h->d_hist.as<uint32_t>() + kHistWords + kSpecWords, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) return 0;
   return n;
 }
+// hooks build only: per iteration of the last call, the queries whose certificate held at the head of k_match2 (`settled`) and those
+// of them whose whole wave skipped the search (`skipped`); all zeros for a chain without certificates (O3S_NO_CERT=1, mirror, sharded)
+int o3s_icp_hook_settled(const o3s_icp* h, int32_t* settled, int32_t* skipped, int32_t cap) {
+  if (!h || !settled || !skipped || h->shard.active) return 0;
+  const int n = std::min({(int)cap, h->last_iters, kSpecTrace});
+  if (n <= 0) return 0;
+  if (hipSetDevice(h->device) != hipSuccess) return 0;
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return 0;
+  std::vector<uint32_t> rep((size_t)kHistReplicas * 2 * kSpecTrace);
+  if (hipMemcpy(rep.data(), h->d_hist.as<uint32_t>() + kHistWords + kSpecWords + kSpecTrace, rep.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  for (int k = 0; k < n; ++k) {
+    settled[k] = skipped[k] = 0;
+    for (int r = 0; r < kHistReplicas; ++r) {
+      settled[k] += (int32_t)rep[((size_t)r * 2 + 0) * kSpecTrace + k];
+      skipped[k] += (int32_t)rep[((size_t)r * 2 + 1) * kSpecTrace + k];
+    }
+  }
+  return n;
+}
+// hooks build only: the matches the last call's chain ended with, in the reading's input order — reference ids (-1: none; a pair the
+// normal gate rejected keeps its id) and squared distances, as find_closests reports them
+int64_t o3s_icp_hook_export_matches(o3s_icp* h, int32_t* ids, float* dists2, int64_t cap) {
+  if (!h || !ids || !dists2 || h->shard.active || h->prepared_N <= 0 || cap < h->prepared_N) return 0;
+  const int64_t N = h->prepared_N;
+  if (hipSetDevice(h->device) != hipSuccess) return 0;
+  if (h->d_mod_a.ensure((size_t)N * 4) != hipSuccess || h->d_mod_b.ensure((size_t)N * 4) != hipSuccess) return 0;
+  hipLaunchKernelGGL(kern::k_export_matches, dim3(nblocks(N)), dim3(kern::kBlock), 0, h->stream, (int)N, h->d_pos.as<int32_t>(),
+                     h->d_d2.as<float>(), h->d_ref.as<float4>(), h->d_perm.as<int32_t>(), h->d_mod_a.as<int32_t>(), h->d_mod_b.as<float>());
+  if (hipMemcpyAsync(ids, h->d_mod_a.p, (size_t)N * 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return 0;
+  if (hipMemcpyAsync(dists2, h->d_mod_b.p, (size_t)N * 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return 0;
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return 0;
+  return N;
+}
 #endif
 
 int64_t o3s_icp_get_reading_order(const o3s_icp* h, int32_t* order, int64_t cap) {
@@ -1822,7 +1881,7 @@ static int import_matches(o3s_icp* h, const int32_t* ids, const float* dists2, c
   }
   hipLaunchKernelGGL(kern::k_import_matches, dim3(nblocks(N)), dim3(kern::kBlock), 0, h->stream, (int)N, h->d_mod_a.as<int32_t>(),
                      h->d_mod_b.as<float>(), weights ? h->d_mod_c.as<float>() : (const float*)nullptr, h->d_orig_to_sorted.as<int32_t>(), h->M,
-                     h->d_ref.as<float4>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_mq.as<float4>());
+                     h->d_ref.as<float4>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_mq.as<float4>(), h->d_cert.as<float>());
   HIP_TRY(h, hipGetLastError());
   return O3S_OK;
 }
