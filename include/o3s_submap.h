@@ -124,6 +124,22 @@ int o3s_submap_center(const o3s_submap* m, double center[3]);
 int o3s_submap_download(const o3s_submap* m, double* pts, double* normals);
 /* Replaces the resident map (e.g. a map loaded from disk). */
 int o3s_submap_upload(o3s_submap* m, const double* pts, const double* normals, int64_t N);
+/* The cloud part of Submap::transform (O3S/src/Submap.cpp:115-121), in place in HBM: Open3D's PointCloud::Transform on the map
+ * cloud and, when the submap holds a feature set with points, on its sparse cloud.  Per point v = T (x, y, z, 1), result
+ * v.head<3>() / v(3) (the division is always taken); per normal T (n, 0), head 3; fp64, the four products summed left to right
+ * without FMA contraction.  There is NO almost-identity branch (that one is o3d_slam::transform's, behind the inserts): T = I
+ * leaves size and bits unchanged.  Colours and the FPFH features are untouched; counts and has-normals stay.  A pending insert is
+ * completed first.  What was derived from the coordinates is dropped: the voxel layout (the next insert sorts the whole map, and
+ * the merge path is tried again right after it).  The patch an ICP handle was given before the call stays what it was: call
+ * o3s_submap_set_reference again to match against the moved map.  An empty submap is O3S_OK and nothing happens.  A NaN or Inf
+ * in T, or a last row of (0, 0, 0, 0), is O3S_ERR_BAD_ARGUMENT before anything is enqueued.  One launch on the submap's stream,
+ * which is drained before the call returns.  The dense map of the submap is o3s_dense_map_transform's. */
+int o3s_submap_transform(o3s_submap* m, const double T[16]);
+/* SubmapCollection::transform's device work (O3S/src/SubmapCollection.cpp:324-375) in one call: submap i gets T + 16 i.  Every
+ * launch goes to its submap's own stream (the submaps may live on different devices) and the streams are waited for once, after
+ * the last launch; no host wait sits between two submaps' launches once their pending inserts are completed.  Everything is
+ * checked before the first launch — a NULL or repeated pointer and an invalid T are O3S_ERR_BAD_ARGUMENT and change no submap. */
+int o3s_submaps_transform(int32_t n, o3s_submap* const* maps, const double* T /* n x 16 */);
 /* Crops the map around T_map_sensor with the scan-matcher cropper, converts the patch to PM::DataPoints precision and
  * makes it the ICP handle's reference (o3s_icp_init_reference_dev) — all in HBM.  *n_patch (nullable) = patch size.
  * An empty patch returns O3S_ERR_EMPTY_REFERENCE ("Map patch is empty", Mapper.cpp:330-336). */

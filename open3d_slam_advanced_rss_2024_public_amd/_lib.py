@@ -89,8 +89,9 @@ XCHG_INT32, XCHG_FLOAT64 = 0, 1
 
 def build(force: bool = False) -> str:
     """hipcc --offload-arch=gfx950 build of the shared library (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".cpp"))]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "o3s_icp.h"))
+    srcs.append(os.path.join(os.path.dirname(_HERE), "include", "pose_graph", "o3s_pose_graph.h"))
     stale = (not os.path.exists(LIB_PATH)) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s"] + (["-B"] if force else []))

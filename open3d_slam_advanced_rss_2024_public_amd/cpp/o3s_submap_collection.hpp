@@ -15,7 +15,11 @@
 //              282-286), it is queued as finished, an adjacency edge is added, the buffer is replayed into the new one
 //   computeFeatures(idx): Submap::computeFeatures (Submap.cpp:255-275) of a submap on the device (o3s_submap_compute_features);
 //              the caller keeps the reference's timer (minSecondsBetweenFeatureComputation_) and decides when to call it.
-// Not here: candidate selection and the pose-graph transforms of finished submaps (host policy).  The RANSAC of place recognition
+//   :324-375   transform: which increment goes to which submap (planSubmapTransforms, o3s_pose_graph.hpp), applied to all resident
+//              submaps by ONE o3s_submaps_transform call; per submap mapToRangeSensor_ * T, T * submapCenter_, the dense map where the
+//              driver keeps one (Submap.cpp:115-128); the overlap buffer is flushed
+//   :75-81     updateAdjacencyMatrix: the submaps of a loop-closure constraint become adjacent
+// Not here: candidate selection and isRegistrationConsistent (host policy).  The RANSAC of place recognition
 //              between two submaps of the collection is o3s_submap_registration_ransac (o3s_submap.h) on their feature sets.
 // The scans the buffer keeps are resident o3s_scan objects: the caller hands over the scan it has just pre-processed and
 // gets another one to fill next (a ring of numScansOverlap_ + 1 handles, nothing is copied).
@@ -33,6 +37,7 @@
 #include <vector>
 
 #include "o3s_icp.hpp"
+#include "o3s_pose_graph.hpp"
 #include "o3s_scan.h"
 
 namespace o3s {
@@ -70,6 +75,7 @@ class SubmapCollectionHip {
     double origin[3] = {0, 0, 0};   // mapToSubmap_.translation()
     double center[3] = {0, 0, 0};   // submapCenter_ once computed
     bool isCenterComputed = false;
+    Mat4 mapToRangeSensor = Mat4::identity();  // Submap::mapToRangeSensor_: the pose of the last scan that went in (Submap.cpp:45)
     const double* mapToSubmapCenter() const { return isCenterComputed ? center : origin; }  // Submap.cpp:203-205
   };
 
@@ -137,6 +143,46 @@ class SubmapCollectionHip {
     finished_.clear();
     return out;
   }
+  // SubmapCollection::updateAdjacencyMatrix (:75-81)
+  void updateAdjacencyMatrix(const Constraints& loopClosureConstraints) {
+    for (const auto& c : loopClosureConstraints) adjacency_.addEdge(c.sourceSubmapIdx, c.targetSubmapIdx);
+  }
+  // the dense map the driver keeps for submap `idx` (Submap::denseMap_): transform() moves it with the submap; not owned
+  void setDenseMap(std::size_t idx, DenseMapHip* dense) { denseMaps_[idx] = dense; }
+  // SubmapCollection::transform (:324-375).  A submap that more than one increment names is refused (the reference would move it
+  // twice; the batched device call takes every submap once).
+  void transform(const OptimizedTransforms& transformIncrements) {
+    std::vector<std::size_t> parents;
+    for (const Entry& e : submaps_) parents.push_back(e.parentId);
+    const auto plan = planSubmapTransforms(parents, transformIncrements);
+    std::vector<o3s_submap*> maps;
+    std::vector<double> Ts;
+    for (const auto& p : plan) {
+      maps.push_back(submaps_.at(p.first).map->handle());
+      Ts.insert(Ts.end(), p.second.m, p.second.m + 16);
+    }
+    if (!plan.empty()) {  // all device work: one call, one wait
+      const int rc = o3s_submaps_transform((std::int32_t)maps.size(), maps.data(), Ts.data());
+      if (rc == O3S_ERR_BAD_ARGUMENT) throw std::invalid_argument("SubmapCollection::transform: a submap named twice, or an invalid transform");
+      if (rc != O3S_OK) throw std::runtime_error("o3s_submaps_transform failed (status " + std::to_string(rc) + ")");
+    }
+    for (const auto& p : plan) {
+      Entry& e = submaps_[p.first];
+      const Mat4& T = p.second;
+      e.mapToRangeSensor = mul(e.mapToRangeSensor, T);  // Submap.cpp:126, a right-multiplication
+      if (e.isCenterComputed) {                         // :127 (submapCenter_ is zero until it is computed; nobody reads it before)
+        double v[3];
+        for (int r = 0; r < 3; ++r) v[r] = ((T(r, 0) * e.center[0] + T(r, 1) * e.center[1]) + T(r, 2) * e.center[2]) + T(r, 3);
+        for (int r = 0; r < 3; ++r) e.center[r] = v[r];
+      }
+      const auto it = denseMaps_.find(p.first);
+      if (it != denseMaps_.end() && it->second) it->second->transform(T.m);
+    }
+    while (!buffer_.empty()) {  // :374 overlapScansBuffer_.clear(): the scan objects are free again
+      free_.push_back(buffer_.front().scan);
+      buffer_.pop_front();
+    }
+  }
   bool lastInsertSwitchedSubmaps() const { return lastSwitched_; }
   // where the last switch of submaps spent its time, ms: creating the new object | the closing scan into the previous submap | its
   // centre | retiring it (hand-over / trim) | the buffered scans into the new one
@@ -189,6 +235,7 @@ class SubmapCollectionHip {
   };
 
   void insertInto(std::size_t idx, o3s_scan* scan, const double T[16]) {
+    for (int k = 0; k < 16; ++k) submaps_[idx].mapToRangeSensor.m[k] = T[k];
     const int rc = o3s_submap_insert_processed(submaps_[idx].map->handle(), scan, T);
     if (rc != O3S_OK) throw std::runtime_error("o3s_submap_insert_processed failed (status " + std::to_string(rc) + ")");
   }
@@ -304,6 +351,7 @@ class SubmapCollectionHip {
   std::vector<o3s_scan*> free_;
   std::deque<std::pair<std::size_t, double>> finished_;
   AdjacencyHip adjacency_;
+  std::map<std::size_t, DenseMapHip*> denseMaps_;
 };
 
 }  // namespace o3s

@@ -88,6 +88,53 @@ __device__ __forceinline__ void transform_append_one(const double* __restrict__ 
   }
 }
 
+// Open3D PointCloud::Transform on a resident submap, in place (o3s_submap_transform): lanes [0, n_map) take the map cloud, lanes
+// [n_map, n_map + n_feat) the feature cloud.  The arithmetic is transform_append_one's; there is no almost-identity branch here
+// (that one belongs to o3d_slam::transform).  A lane reads its own 24 + 24 bytes before it writes them and touches nobody else's,
+// which is what makes the in-place form safe (undistort_dev.h).  No LDS, no atomics, no scratch
+// (profiles/pose_graph/resource_usage.txt).
+__global__ void __launch_bounds__(kB) k_submap_transform(double* map_p, double* map_n /*nullable*/, int64_t n_map, double* feat_p, double* feat_n,
+                                                         int64_t n_feat, Mat4d Tm) {
+  int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
+  if (i >= n_map + n_feat) return;
+  double* p = map_p;
+  double* q = map_n;
+  if (i >= n_map) {
+    i -= n_map;
+    p = feat_p;
+    q = feat_n;
+  }
+  const double* T = Tm.m;
+  const double x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
+  double v[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    double s = T[r] * x;
+    s = s + T[4 + r] * y;
+    s = s + T[8 + r] * z;
+    s = s + T[12 + r] * 1.0;
+    v[r] = s;
+  }
+  p[3 * i] = v[0] / v[3];
+  p[3 * i + 1] = v[1] / v[3];
+  p[3 * i + 2] = v[2] / v[3];
+  if (q) {
+    const double a = q[3 * i], b = q[3 * i + 1], c = q[3 * i + 2];
+    double w[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      double s = T[r] * a;
+      s = s + T[4 + r] * b;
+      s = s + T[8 + r] * c;
+      s = s + T[12 + r] * 0.0;
+      w[r] = s;
+    }
+    q[3 * i] = w[0];
+    q[3 * i + 1] = w[1];
+    q[3 * i + 2] = w[2];
+  }
+}
+
 // o3d_slam::transform (helpers.cpp:283-318) on host buffers: points (/ w), normals, covariances R C R^T; an (almost-)identity
 // T returns the cloud TWICE (the copy of :285-288 followed by the loop's appends), which is what the reference does.
 __global__ void __launch_bounds__(kB) k_transform_cov(const double* __restrict__ cov, int64_t N, const double* __restrict__ Tm, double* __restrict__ out) {
@@ -668,6 +715,69 @@ int o3s_submap_download(const o3s_submap* m, double* pts, double* normals) {
     CK(hipMemcpy(normals, m->nrm[m->cur].p, (size_t)m->n * 24, hipMemcpyDeviceToHost));
   }
   return O3S_OK;
+}
+
+namespace {
+// every word finite, and a last row that is not (0, 0, 0, 0) (v(3) would be zero for every point)
+bool transform_valid(const double* T) {
+  if (!T) return false;
+  for (int k = 0; k < 16; ++k)
+    if (!std::isfinite(T[k])) return false;
+  return !(T[3] == 0.0 && T[7] == 0.0 && T[11] == 0.0 && T[15] == 0.0);
+}
+// enqueues the in-place transform of a settled, non-empty submap on its own stream and drops what was derived from the coordinates
+int submap_transform_enqueue(o3s_submap* m, const double* T) {
+  const int rc = set_dev(m);
+  if (rc != O3S_OK) return rc;
+  Mat4d Tv;
+  for (int k = 0; k < 16; ++k) Tv.m[k] = T[k];
+  const int c = m->cur;  // whichever ping-pong array is current (a closed submap's tight copy)
+  const int64_t nf = m->n_feat > 0 ? m->n_feat : 0;
+  hipLaunchKernelGGL(k_submap_transform, dim3(nblk(m->n + nf)), dim3(kB), 0, m->stream, m->pts[c].d(), m->has_normals == 1 ? m->nrm[c].d() : nullptr,
+                     m->n, nf ? m->feat_p.d() : nullptr, nf ? m->feat_n.d() : nullptr, nf, Tv);
+  CK(hipGetLastError());
+  // The voxel order of the map array is the order of the OLD coordinates: the next insert sorts, and tries the merge right after
+  // (a back-off counted revisits of the old frame).  The patch buffers and the feature work area (grid, lists, SPFH) carry no
+  // validity state: o3s_submap_set_reference and o3s_submap_compute_features rebuild them from the map on every call.
+  m->layout_valid = false;
+  m->merge_backoff = 0;
+  return O3S_OK;
+}
+}  // namespace
+
+int o3s_submap_transform(o3s_submap* m, const double T[16]) {
+  if (const int rs_ = submap_settle(m); rs_ != O3S_OK) return rs_;  // a pending insert is completed first
+  if (!m || !transform_valid(T)) return O3S_ERR_BAD_ARGUMENT;
+  if (m->n == 0) return O3S_OK;  // (a feature set of an empty map is empty)
+  const int rc = submap_transform_enqueue(m, T);
+  if (rc != O3S_OK) return rc;
+  CK(hipStreamSynchronize(m->stream));  // registrations read the map from other streams
+  return O3S_OK;
+}
+
+int o3s_submaps_transform(int32_t n, o3s_submap* const* maps, const double* T) {
+  if (n < 0 || (n > 0 && (!maps || !T))) return O3S_ERR_BAD_ARGUMENT;
+  // everything is checked before the first launch: a bad argument changes no submap
+  for (int32_t i = 0; i < n; ++i) {
+    if (!maps[i] || !transform_valid(T + 16 * (size_t)i)) return O3S_ERR_BAD_ARGUMENT;
+    for (int32_t j = 0; j < i; ++j)
+      if (maps[j] == maps[i]) return O3S_ERR_BAD_ARGUMENT;
+  }
+  for (int32_t i = 0; i < n; ++i)
+    if (const int rs_ = submap_settle(maps[i]); rs_ != O3S_OK) return rs_;  // pending inserts are completed first
+  int rc = O3S_OK;
+  int32_t issued = 0;
+  for (; issued < n && rc == O3S_OK; ++issued)
+    if (maps[issued]->n > 0) rc = submap_transform_enqueue(maps[issued], T + 16 * (size_t)issued);
+  // the one wait: each stream that was given work is drained, after the last launch (submaps share the streams of their device)
+  for (int32_t i = 0; i < issued; ++i) {
+    if (maps[i]->n == 0) continue;
+    bool seen = false;
+    for (int32_t j = 0; j < i && !seen; ++j) seen = maps[j]->n > 0 && maps[j]->stream == maps[i]->stream && maps[j]->device == maps[i]->device;
+    if (seen) continue;
+    if (hipSetDevice(maps[i]->device) != hipSuccess || hipStreamSynchronize(maps[i]->stream) != hipSuccess) rc = rc == O3S_OK ? O3S_ERR_HIP : rc;
+  }
+  return rc;
 }
 
 namespace {

@@ -75,6 +75,13 @@ class Mapper:
         self.motion_compensation = ConstantVelocityMotionCompensation(self.pose_buffer, scan_duration, is_spinning_clockwise,
                                                                       num_poses_vel_estimation)
 
+    def loopClosureUpdate(self, loopClosureCorrection):
+        """Mapper::loopClosureUpdate (Mapper.cpp:92-95).  The ICP reference is NOT renewed: until the next renewal the matcher still
+        holds the patch that was cut before the correction, as in the reference."""
+        dT = np.asarray(loopClosureCorrection, np.float64)
+        self.T = mul4(dT, self.T)
+        self.T_prev = mul4(dT, self.T_prev)
+
     def _odom(self, stamp):
         """getTransform(t, odomToRangeSensorBuffer_) * calibration_.inverse()   (Mapper.cpp:221-222, 270-273)"""
         return mul4(self.odom[stamp], self.calib_inv)

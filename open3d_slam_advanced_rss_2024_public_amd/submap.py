@@ -50,6 +50,8 @@ def _L():
         L.o3s_submap_features_size.restype = C.c_int64
         L.o3s_submap_download_features.argtypes = [vp, dp, dp, dp]
         L.o3s_submap_feature_correspondences.argtypes = [vp, vp, C.c_int32, C.c_int32, ip, C.POINTER(C.c_int64), ip]
+        L.o3s_submap_transform.argtypes = [vp, dp]
+        L.o3s_submaps_transform.argtypes = [C.c_int32, C.POINTER(vp), dp]
     return L
 
 
@@ -275,6 +277,14 @@ class Submap:
         self._check(self._lib.o3s_submap_upload(self._h, _d(p), _d(n), p.shape[0]), "o3s_submap_upload")
         self.has_normals = (n is not None) if p.shape[0] else None
 
+    def transform(self, T):
+        """The cloud part of Submap::transform (Submap.cpp:115-121) in place in HBM (o3s_submap_transform): Open3D's
+        PointCloud::Transform on the map cloud and on the feature cloud; no almost-identity doubling."""
+        rc = self._lib.o3s_submap_transform(self._h, _d(_pose(T)))
+        if rc == _lib.ERR_BAD_ARGUMENT:
+            raise ValueError("transform: T must be finite with a last row that is not zero")
+        self._check(rc, "o3s_submap_transform")
+
     def carve(self, rawScan, mapToRangeSensor, voxel_size=0.1, max_raytracing_length=20.0, truncation_distance=0.1,
               min_dot_product_with_normal=0.5) -> int:
         """Submap::carve (Submap.cpp:116-130) with SpaceCarvingParameters; returns the number of removed map points.
@@ -309,6 +319,27 @@ class Submap:
             msg = icp._L.o3s_last_error(icp._h).decode()
             raise RuntimeError(f"o3s_submap_set_reference failed with o3s_status {rc}: {msg}")
         return int(k.value)
+
+
+def transform_submaps(maps, Ts):
+    """SubmapCollection::transform's device work in one call (o3s_submaps_transform): maps[i] gets Ts[i]; every launch on its
+    submap's own stream, one wait at the end.  A repeated submap or an invalid T raises and changes no submap."""
+    maps = list(maps)
+    Ts = [np.asarray(T, np.float64) for T in Ts]
+    if len(maps) != len(Ts):
+        raise ValueError("transform_submaps: one transform per submap")
+    if not maps:
+        return
+    L = maps[0]._lib
+    if any(m._lib is not L for m in maps):
+        raise ValueError("transform_submaps: the submaps belong to different builds of the library")
+    hs = (C.c_void_p * len(maps))(*[m._h.value for m in maps])
+    flat = np.ascontiguousarray(np.concatenate([_pose(T) for T in Ts]))
+    rc = L.o3s_submaps_transform(len(maps), hs, _d(flat))
+    if rc == _lib.ERR_BAD_ARGUMENT:
+        raise ValueError("transform_submaps: a repeated submap, or a T that is not finite or has a zero last row")
+    if rc != _lib.OK:
+        raise RuntimeError(f"o3s_submaps_transform failed with o3s_status {rc}")
 
 
 class ProcessedScan:

@@ -4,22 +4,28 @@ step by step and by tools/mapping_loop.py.  No compute here — every cloud oper
 import numpy as np
 
 from . import cloud_ops as co
-from .submap import ProcessedScan, Submap
+from .mapper import mul4
+from .submap import ProcessedScan, Submap, transform_submaps
 
 
 class SubmapCollection:
     """SubmapCollection::insertScan / updateActiveSubmap (SubmapCollection.cpp:94-247) restated over the Python mirror — the
     same steps as cpp/o3s_submap_collection.hpp, resident scans in a ring of numScansOverlap + 1 objects."""
 
-    def __init__(self, radius, min_num, max_points, overlap, map_voxel, map_builder_cropper, submap_factory=None, scan_factory=None):
+    def __init__(self, radius, min_num, max_points, overlap, map_voxel, map_builder_cropper, submap_factory=None, scan_factory=None,
+                 transform_maps=None):
         """map_builder_cropper: (kind, p0[, p1, p2]) as for cloud_ops.croppingVolumeFactory.  submap_factory / scan_factory:
         stand-ins for the device-resident objects (insertProcessed / __len__ / computeSubmapCenter) — the CPU tests of the
-        switching rules use them; the default is the real thing."""
+        switching rules use them; the default is the real thing.  transform_maps(maps, Ts): the one batched device call of
+        transform() (submap.transform_submaps unless a stand-in is given)."""
+        self._transform_maps = transform_maps or transform_submaps
         self.radius, self.min_num, self.max_points, self.overlap = radius, min_num, max_points, overlap
         self.map_voxel, self.cropper = map_voxel, tuple(map_builder_cropper)
         self._new_submap = submap_factory or (lambda: Submap(self.map_voxel, co.croppingVolumeFactory(*self.cropper)))
         scan_factory = scan_factory or ProcessedScan
         self.maps, self.ids, self.parents, self.origins, self.centers = [], [], [], [], []
+        self.range_sensor_poses = []   # Submap::mapToRangeSensor_ of every submap: the pose of the last scan that went into it
+        self.dense_maps = {}           # submap index -> dense map object (transform(T)), where the driver keeps one
         self.active, self.next_id, self.merged, self.force = 0, 0, 0, False
         self.edges = set()
         self.buffer, self.free = [], [scan_factory() for _ in range(overlap + 1)]
@@ -33,6 +39,7 @@ class SubmapCollection:
         self.next_id += 1
         self.origins.append(np.array(origin, np.float64))
         self.centers.append(None)
+        self.range_sensor_poses.append(np.eye(4))
         self.active = len(self.maps) - 1
         self.merged = 0
 
@@ -85,7 +92,7 @@ class SubmapCollection:
         self.update_active(T[:3, 3].copy())
         if prev != self.active:
             self.switched = True
-            self.maps[prev].insertProcessed(ps, T)
+            self._insert_into(prev, ps, T)
             self.centers[prev] = self.maps[prev].computeSubmapCenter()
             self.finished.append((prev, stamp))
             self.finished_queue.append((prev, stamp))
@@ -94,14 +101,65 @@ class SubmapCollection:
             self.edges.add((min(a, b), max(a, b)))
             while self.buffer:
                 q, Tq, _ = self.buffer.pop(0)
-                self.maps[self.active].insertProcessed(q, Tq)
+                self._insert_into(self.active, q, Tq)
                 self.free.append(q)
             assert len(self.maps[self.active]) > 0
         else:
-            self.maps[self.active].insertProcessed(ps, T)
+            self._insert_into(self.active, ps, T)
         self.merged += 1
+
+    def _insert_into(self, i, ps, T):
+        self.range_sensor_poses[i] = np.array(T, np.float64)   # Submap.cpp:45
+        self.maps[i].insertProcessed(ps, T)
 
     def pop_finished(self):
         """SubmapCollection::popFinishedSubmapIds (:53-55)."""
         out, self.finished_queue = self.finished_queue, []
         return out
+
+    def update_adjacency_matrix(self, loop_closure_constraints):
+        """SubmapCollection::updateAdjacencyMatrix (:75-81): a loop-closure constraint makes its two submaps adjacent."""
+        for c in loop_closure_constraints:
+            a, b = c.source_submap_idx, c.target_submap_idx
+            self.edges.add((min(a, b), max(a, b)))
+
+    def transform(self, increments):
+        """SubmapCollection::transform (:324-375).  increments: objects with .dT (4x4) and .submap_id.  A submap an increment names
+        gets that increment; every other submap walks up its parents until one is not among the unnamed submaps and takes
+        increments[parent] — a POSITIONAL lookup, as written (:362).  All device work is one batched call; per submap also
+        (Submap.cpp:115-128) mapToRangeSensor_ = mapToRangeSensor_ * T, submapCenter_ = T * submapCenter_ and the dense map, where
+        one is kept.  The overlap buffer is flushed: its scan objects go back to the free ring."""
+        increments = list(increments)
+        n = len(self.maps)
+        plan = []                                    # (submap index, T) in the reference's order of application
+        optimized = []
+        for u in increments:
+            if u.submap_id < n:
+                plan.append((u.submap_id, np.asarray(u.dT, np.float64)))
+                optimized.append(u.submap_id)
+            # else: "trying to update submap ... but there are only ..." (:337): reported and skipped by the reference
+        to_update = [i for i in range(n) if i not in set(optimized)]
+        for idx in to_update:
+            current = idx
+            while increments:                        # "while (true && !transformIncrements.empty())"
+                current = self.parents[current]
+                if current not in to_update:         # the parent is in the pose graph
+                    plan.append((idx, np.asarray(increments[current].dT, np.float64)))   # .at(currentNode): IndexError out of range
+                    break
+                if current == self.parents[current]:
+                    raise RuntimeError("Stuck in a loop, this should not happen")
+        if len({i for i, _ in plan}) != len(plan):
+            # (the reference would transform such a submap twice; the batched device call takes every submap once)
+            raise ValueError("SubmapCollection.transform: a submap is named by more than one increment")
+        if plan:
+            self._transform_maps([self.maps[i] for i, _ in plan], [T for _, T in plan])
+        for i, T in plan:
+            self.range_sensor_poses[i] = mul4(self.range_sensor_poses[i], T)
+            if self.centers[i] is not None:          # (submapCenter_ is zero until it is computed; nobody reads it before)
+                c = self.centers[i]
+                v = [((T[r, 0] * c[0] + T[r, 1] * c[1]) + T[r, 2] * c[2]) + T[r, 3] for r in range(3)]
+                self.centers[i] = np.array(v)
+            if i in self.dense_maps:
+                self.dense_maps[i].transform(T)
+        while self.buffer:                           # :374 overlapScansBuffer_.clear()
+            self.free.append(self.buffer.pop(0)[0])
