@@ -233,6 +233,8 @@ def load(variant: str | None = None) -> C.CDLL:
     L.o3s_icp_covariance_gpu_us.argtypes = [vp, dp]
     if hasattr(L, "o3s_icp_hook_settled"):  # the hooks build: what its tests read back
         L.o3s_icp_hook_settled.argtypes = [vp, ip, ip, C.c_int32]
+        L.o3s_icp_hook_sel_depth.argtypes = [vp, ip, C.c_int32]
+        L.o3s_icp_hook_bin_path.argtypes = [vp, ip, C.c_int32]
         L.o3s_icp_hook_export_matches.argtypes = [vp, ip, fp, C.c_int64]
         L.o3s_icp_hook_export_matches.restype = C.c_int64
     _loaded[key] = L

@@ -770,8 +770,9 @@ __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
 //               The next launch moves the query by delta = |T p - T_prev p|.  Every other point is then still at least
 //               L = sqrt(cert) - delta away, and when the incumbent's new distance is below L^2 (1 - 1e-5) it is strictly the
 //               nearest in computed fp32 arithmetic: no tie is possible, the search would return the same slot and the same bits
-//               of d2.  A wave whose valid queries are ALL settled that way writes d2, the decoded slot and the shrunk
-//               certificate, counts its histograms and skips round trips 2 and 3; a wave with one open query searches as before.
+//               of d2.  A query settled that way writes d2, the decoded slot and the shrunk certificate, counts its histograms
+//               and leaves the search: a wave whose valid queries are ALL settled skips round trips 2 and 3, a wave with open
+//               queries walks only their candidates.
 // ------------------------------------------------------------------------------------------------------------------
 struct Own {  // a lane's best among ITS candidates, with the matched point itself (handed to the next iteration)
   float d;
@@ -925,6 +926,8 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
                                                       O3S_HOOK_PARAM(uint32_t* __restrict__ settled_cnt /*nullable: [kHistReplicas][2][kSpecTrace]
                                                       per iteration: queries whose certificate held, queries of the waves that skipped the search*/)) {
   __shared__ uint32_t s_hist[kHistBins];
+  __shared__ uint32_t s_cnt[2];  // the block's bin counters {F, Bl}: one LDS add per wave, one global atomic per block and counter
+  if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
 #ifdef O3S_TEST_HOOKS
   __shared__ uint32_t s_set[2];  // the block's settled queries: one global atomic per block and counter, spread over the replicas
   if (threadIdx.x < 2) s_set[threadIdx.x] = 0u;
@@ -1003,14 +1006,25 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
       if ((key >> 10) == (hint >> 10)) atomicAdd(&spec_cur[1024 + (key & 1023u)], 1u);
     }
   };
+  // ... and the two bin counters: the lanes that counted a match, and those of them whose level-1 bin lies below the previous limit's.
+  // Tallied per wave (ballot + popcount into two scalars, no register per lane: the kernel is at its limit) at the convergent point
+  // behind each of the two places that call count_match; a lane counts a match in at most one of them.
+  uint32_t n_found = 0u, n_below = 0u;  // uniform
+  auto tally = [&](bool counted, float d) {
+    if (spec_on && !O3S_DBG(1)) {  // uniform
+      const bool below = counted && ((__float_as_uint(d) & 0x7fffffffu) >> 20) < (hint >> 20);
+      n_found += (uint32_t)__popcll(__ballot(counted));
+      n_below += (uint32_t)__popcll(__ballot(below));
+    }
+  };
   // ---- the certificate's fast path: a query that moved by less than its certificate leaves room for keeps its match (or stays
   //      unmatched) without a search; a wave of such queries writes its outputs here and is done ----
-  bool wave_settled = false;
+  bool wave_settled = false;  // uniform: every valid query of the wave is settled (the seed probe's condition, the hooks' counter)
+  bool settled = false;       // this lane's query is (the same in the G lanes of a group: they hold the same query)
   if (CERT) {
     float Tp[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) Tp[k] = hdr_f(hp, k);
-    bool settled = false;
     float dn = 0.f, cn = 0.f;
     // the certificates are those of the launch right before this one (IcpState::cert_seq): uniform
     const bool fresh = (uint32_t)hdr_i(hp, 16 + ((hdr_i(hv, H_ITER) + 1) & 1)) == (uint32_t)hdr_i(hv, H_ITER);
@@ -1037,8 +1051,10 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
       }
     }
 #endif
-    if (wave_settled && !O3S_DBG(8)) {
-      if (valid && sub == 0) {
+    // a settled query writes its outputs here and leaves the search, whatever the other queries of its wave do: the wave goes on for
+    // its open queries only, and its candidate walk is as long as THEIR longest list
+    if (settled && !O3S_DBG(8)) {
+      if (sub == 0) {
         if (inc.w != 0.f) {  // mq and mn keep the match they hold
           pos_out[i] = pe >= 0 ? pe : -2 - pe;
           d2_out[i] = dn;
@@ -1047,7 +1063,8 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
         cert[i] = cn;
       }
     }
-    active = active && !wave_settled;
+    tally(settled && !O3S_DBG(8) && sub == 0 && inc.w != 0.f, dn);
+    active = active && !settled;
   }
   if (active) {
     // ---- pruning bound: the previous correspondence under the new pose (any reference point is an upper bound) ----
@@ -1072,10 +1089,10 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
   //      misses (a query 0.3 m above a floor hits the cell under it; a bad normal just finds nothing).
   //      Only where the far search has many rings to walk (maxDist >= 5 cells: dense maps, C4): at C2's three cells the probe
   //      costs what it saves (first iteration 40.7 us without, 42.1 us with).
-  if (FAR && rnx != nullptr && lim * g.inv_cell * g.inv_cell >= 25.f && !wave_settled && __any(valid && inc.w == 0.f)) {  // uniform
+  if (FAR && rnx != nullptr && lim * g.inv_cell * g.inv_cell >= 25.f && !wave_settled && __any(valid && !settled && inc.w == 0.f)) {  // uniform
     constexpr int kProbeSteps = 12;  // per direction; more cells than that to maxDist: the probe stops short (still a valid bound)
     constexpr int NP = (2 * kProbeSteps + G - 1) / G;  // probe cells per lane
-    const bool want = valid && inc.w == 0.f;
+    const bool want = valid && !settled && inc.w == 0.f;
     float nx = 0.f, ny = 0.f, nz = 0.f;
     if (want) {
       const float a = rnx[i], b_ = rny[i], c_ = rnz[i];
@@ -1215,7 +1232,7 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
     if (active && !far) others = fminf(others, q * q);
     // the ring search for an unbounded maxDist keeps no account of what it passes over: its queries get no certificate, and the
     // others' is complete here — written now, so that it is not kept alive across the rings (the kernel is at its register limit)
-    if (!FAR && CERT && valid && !wave_settled && !O3S_DBG(8)) {
+    if (!FAR && CERT && valid && !settled && !O3S_DBG(8)) {
       const float cn = group_cert(far ? 0.f : others);
       if (sub == 0) cert[i] = cn;
     }
@@ -1451,7 +1468,8 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
   }
   // ---- outputs: the lane that examined the winner writes it (slot, d2, the matched point for the next iteration);
   //      lane 0 of the group writes the "no match" record.  Level-1 histogram as in k_match. ----
-  if (valid && !wave_settled && !O3S_DBG(8)) {
+  bool counted = false;
+  if (valid && !settled && !O3S_DBG(8)) {
     const bool found = gi != 0x7fffffff;
     const float cn = (FAR && CERT) ? group_cert(others) : 0.f;  // (the ring-search variant has written its certificates before the rings)
     // two lanes of a group never examine the same reference point (disjoint rows; the central cells are left to the first
@@ -1474,6 +1492,7 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
       if (mn) mn[i] = nq;
       if (FAR && CERT) cert[i] = cn;
       count_match(b.d);
+      counted = true;
     } else if (!found && sub == 0) {
       pos_out[i] = -1;
       d2_out[i] = kInfF;
@@ -1482,7 +1501,14 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
       if (FAR && CERT) cert[i] = cn;
     }
   }
+  tally(counted, b.d);
+  if ((threadIdx.x & 63) == 0) {
+    if (n_found) atomicAdd(&s_cnt[0], n_found);
+    if (n_below) atomicAdd(&s_cnt[1], n_below);
+  }
   __syncthreads();
+  if (spec_on && threadIdx.x < 2 && s_cnt[threadIdx.x])
+    atomicAdd(&spec_cur[kSpecHist + 2 * (blockIdx.x & (kSpecCntCopies - 1)) + threadIdx.x], s_cnt[threadIdx.x]);
 #ifdef O3S_TEST_HOOKS
   if (CERT && settled_cnt && threadIdx.x < 2 && s_set[threadIdx.x] && hdr_i(hv, H_ITER) < kSpecTrace)
     atomicAdd(&settled_cnt[((blockIdx.x & (kHistReplicas - 1)) * 2 + threadIdx.x) * kSpecTrace + hdr_i(hv, H_ITER)], s_set[threadIdx.x]);
@@ -1566,16 +1592,20 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
                                                      int n_rep /*level-1 replicas to sum: kHistReplicas; fewer in the sharded mode, where they travel*/,
                                                      int l2_shift = 10, uint32_t l2_mask = 1023u /*the level-2 digit: bits 19..10; the sharded chain takes
                                                      thirteen bits (shift 7, mask 8191: csrc/icp_shard_kernels.h)*/,
-                                                     const uint32_t* __restrict__ spec = nullptr /*k_match2's speculative digit histograms
-                                                     [kSpecWords] (+ the hooks build's depth trace); null: level 1 only*/) {
-  __shared__ uint32_t s_sc[48];
+                                                     const uint32_t* __restrict__ spec = nullptr /*k_match2's speculative digit histograms and
+                                                     bin counters [kSpecWords] (+ the hooks build's depth trace); null: level 1 only*/,
+                                                     float max_r2 = kInfF /*the matcher's maxDist^2: no match lies in a level-1 bin above its own*/
+                                                     O3S_HOOK_PARAM(int no_bin_counters = 0 /*hooks build: always sum the replicas*/)) {
+  __shared__ uint32_t s_sc[48 + 2];
   __shared__ uint32_t s_res[8];
   __shared__ uint32_t s_wcnt[kClsBlock / 64];
   using Sum = BlockSum<kCentComps, kClsBlock>;
   __shared__ double s_a[Sum::kWordsA];
   __shared__ double s_b[Sum::kWordsB];
   const float hv = hdr_load(st);
-  // this thread's point and the level-1 histogram (8 replicas) are fetched in the same round trip as the header
+  // this thread's point and the histograms are fetched in the same round trip as the header: the speculative digit histograms
+  // and the bin counters when there are any (the level-1 replicas then follow in a second round trip, and only in the iterations
+  // whose bin the counters do not settle), else the 16 level-1 replicas
   const int i = blockIdx.x * kClsBlock + threadIdx.x;
   const bool inb = i < N;
   const int pe0 = inb ? pos[i] : -1;
@@ -1594,22 +1624,38 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
   constexpr int kBpt = kHistBins / kClsBlock;  // level-1 bins owned by a thread (4)
   static_assert(kBpt == 4, "one uint4 per replica and thread");
   uint32_t c[kBpt] = {0, 0, 0, 0};
+  // the matcher counts only matches with d2 <= maxDist^2: the bins above that of maxDist^2 are empty by construction (about half of
+  // them at maxDist 0.5), and a thread whose four bins all lie there has nothing to load
+  const uint32_t live_bin = (max_r2 >= 0.f && max_r2 < kInfF) ? (__float_as_uint(max_r2) >> 20) : (uint32_t)(kHistBins - 1);
+  auto load_replicas = [&]() {
+    if ((uint32_t)(threadIdx.x * kBpt) > live_bin) return;
 #pragma unroll
-  for (int r = 0; r < kHistReplicas; ++r) {  // branch-free: a replica beyond n_rep re-reads replica 0 and counts nothing
-    const bool on = r < n_rep;
-    const uint4 u0 = *reinterpret_cast<const uint4*>(hist_rep + (size_t)(on ? r : 0) * kHistBins + threadIdx.x * kBpt);
-    c[0] += on ? u0.x : 0u;
-    c[1] += on ? u0.y : 0u;
-    c[2] += on ? u0.z : 0u;
-    c[3] += on ? u0.w : 0u;
-  }
-  // both parities of the speculative histograms (fixed addresses: the parity is only known once the header has arrived)
+    for (int r = 0; r < kHistReplicas; ++r) {  // branch-free: a replica beyond n_rep re-reads replica 0 and counts nothing
+      const bool on = r < n_rep;
+      const uint4 u0 = *reinterpret_cast<const uint4*>(hist_rep + (size_t)(on ? r : 0) * kHistBins + threadIdx.x * kBpt);
+      c[0] += on ? u0.x : 0u;
+      c[1] += on ? u0.y : 0u;
+      c[2] += on ? u0.z : 0u;
+      c[3] += on ? u0.w : 0u;
+    }
+  };
+#ifdef O3S_TEST_HOOKS
+  const bool counters = spec != nullptr && !no_bin_counters;  // uniform
+#else
+  const bool counters = spec != nullptr;
+#endif
+  if (!counters) load_replicas();
+  // both parities of the speculative histograms and of the bin counters (fixed addresses: the parity is only known once the header
+  // has arrived); the 64 copies of {F, Bl} go to the first wave
   uint2 sp2[2] = {make_uint2(0u, 0u), make_uint2(0u, 0u)}, sp3[2] = {make_uint2(0u, 0u), make_uint2(0u, 0u)};
+  uint2 spc[2] = {make_uint2(0u, 0u), make_uint2(0u, 0u)};
+  static_assert(kSpecCntCopies == 64, "one copy of the bin counters per lane of the first wave");
   if (spec) {  // uniform
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       sp2[p] = *reinterpret_cast<const uint2*>(spec + p * kSpecHalf + 2 * threadIdx.x);
       sp3[p] = *reinterpret_cast<const uint2*>(spec + p * kSpecHalf + 1024 + 2 * threadIdx.x);
+      if (counters && threadIdx.x < kSpecCntCopies) spc[p] = *reinterpret_cast<const uint2*>(spec + p * kSpecHalf + kSpecHist + 2 * threadIdx.x);
     }
   }
   if (hdr_i(hv, H_DONE)) return;
@@ -1625,9 +1671,6 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
     if (inb) mn[i] = rn;
   }
   // ---- rank-k bin: every block repeats the same integer arithmetic on the same summed histogram ----
-  uint32_t mine = 0;
-#pragma unroll
-  for (int k = 0; k < kBpt; ++k) mine += c[k];
   // the previous limit of this call (+inf in its first iteration): when it is a finite number, the speculative histograms of this
   // iteration's parity are scanned together with the level-1 histogram (their scans share the barriers; whether they are used
   // is decided once B is known)
@@ -1635,58 +1678,97 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
   const uint32_t hint = __float_as_uint(hdr_f(hv, H_LIMIT));
   const bool spec_try = spec != nullptr && cp.has_trim && it > 0 && hint < 0x7f800000u;  // uniform
   const uint2 h2 = (it & 1) ? sp2[1] : sp2[0], h3 = (it & 1) ? sp3[1] : sp3[0];
-  uint32_t n_fin, ex, tot2 = 0, tot3 = 0, ex2 = 0, ex3 = 0;
-  if (spec_try) {
-    const uint32_t v[3] = {mine, h2.x + h2.y, h3.x + h3.y};
-    uint32_t tot[3], exs[3];
-    block_excl_scan3(v, tot, exs, s_sc);
-    n_fin = tot[0];
-    tot2 = tot[1];
-    tot3 = tot[2];
-    ex = exs[0];
-    ex2 = exs[1];
-    ex3 = exs[2];
+  // index: values.size() * quantile evaluated in fp32, truncated (Matches.cpp:85-86); ratio == 1 -> max element
+  auto rank_of = [&](uint32_t n) {
+    if (cp.trim_ratio == 1.0f) return n - 1;
+    const uint32_t k = (uint32_t)((float)n * cp.trim_ratio);
+    return k >= n ? n - 1 : k;
+  };
+  uint32_t mine = 0, n_fin, ex = 0, tot2 = 0, tot3 = 0, ex2 = 0, ex3 = 0, below = 0;
+  bool quick = false;  // uniform: the counters place rank k in the predicted bin, the level-1 replicas stay unread
+  if (spec_try && counters) {
+    // F and Bl: the first wave sums its 64 copies; the totals travel through the barriers of the two digit scans
+    const uint2 cc = (it & 1) ? spc[1] : spc[0];
+    if (threadIdx.x < 64) {
+      const uint32_t f = wave_incl_scan_u32(cc.x), l = wave_incl_scan_u32(cc.y);
+      if (threadIdx.x == 63) {
+        s_sc[48] = f;
+        s_sc[49] = l;
+      }
+    }
+    block_excl_scan2(h2.x + h2.y, h3.x + h3.y, &tot2, &tot3, &ex2, &ex3, s_sc);
+    n_fin = s_sc[48];
+    below = s_sc[49];
+    // the level-1 histogram would give: n_fin = F (same population), ex of the predicted bin = Bl (the bins below it), its count =
+    // tot2 (k_match2 counts the level-2 digit of exactly the pairs in that bin).  Rank k lies in it iff Bl <= k < Bl + tot2.
+    if (n_fin > 0) {
+      const uint32_t k = rank_of(n_fin);
+      quick = below <= k && k < below + tot2;
+    }
+    if (!quick) {  // the limit left the predicted bin (or there is no match at all): the replicas, a second round trip
+      load_replicas();
+#pragma unroll
+      for (int k = 0; k < kBpt; ++k) mine += c[k];
+      ex = block_excl_scan(mine, &n_fin, s_sc);
+    }
   } else {
-    ex = block_excl_scan(mine, &n_fin, s_sc);
+    if (counters) load_replicas();  // (no prediction: the first iteration of a call)
+#pragma unroll
+    for (int k = 0; k < kBpt; ++k) mine += c[k];
+    if (spec_try) {
+      const uint32_t v[3] = {mine, h2.x + h2.y, h3.x + h3.y};
+      uint32_t tot[3], exs[3];
+      block_excl_scan3(v, tot, exs, s_sc);
+      n_fin = tot[0];
+      tot2 = tot[1];
+      tot3 = tot[2];
+      ex = exs[0];
+      ex2 = exs[1];
+      ex3 = exs[2];
+    } else {
+      ex = block_excl_scan(mine, &n_fin, s_sc);
+    }
   }
   uint32_t bin = kHistBins;  // no Trimmed filter: every finite distance is "below"
-  uint32_t depth = 11, pref = kHistBins, kk_pub = 0;  // resolved leading bits of the limit, their value, the rank inside them
+  uint32_t depth = 11, pref = kHistBins, kk_pub = 0, bin_count = 0;  // resolved leading bits of the limit, their value, the rank inside them
   bool skip = false;
   if (cp.has_trim) {
     if (n_fin == 0) {  // "No matches available for computing distance quantiles" (Matches.cpp:76-77)
       skip = true;
       if (blockIdx.x == 0 && threadIdx.x == 0) st->status = 5;
     } else {
-      // index: values.size() * quantile evaluated in fp32, truncated (Matches.cpp:85-86); ratio == 1 -> max element
-      uint32_t k;
-      if (cp.trim_ratio == 1.0f) {
-        k = n_fin - 1;
+      const uint32_t k = rank_of(n_fin);
+      uint32_t kk1;  // rank inside the bin
+      if (quick) {
+        bin = hint >> 20;
+        kk1 = k - below;
+        bin_count = tot2;
       } else {
-        k = (uint32_t)((float)n_fin * cp.trim_ratio);
-        if (k >= n_fin) k = n_fin - 1;
-      }
-      if (mine > 0 && ex <= k && k < ex + mine) {
-        uint32_t acc = ex;
+        if (mine > 0 && ex <= k && k < ex + mine) {
+          uint32_t acc = ex;
 #pragma unroll
-        for (int qd = 0; qd < kBpt; ++qd) {
-          if (c[qd] > 0 && acc <= k && k < acc + c[qd]) {
-            s_res[0] = threadIdx.x * kBpt + qd;
-            s_res[1] = k - acc;
-            s_res[2] = c[qd];
+          for (int qd = 0; qd < kBpt; ++qd) {
+            if (c[qd] > 0 && acc <= k && k < acc + c[qd]) {
+              s_res[0] = threadIdx.x * kBpt + qd;
+              s_res[1] = k - acc;
+              s_res[2] = c[qd];
+            }
+            acc += c[qd];
           }
-          acc += c[qd];
         }
+        __syncthreads();
+        bin = s_res[0];
+        kk1 = s_res[1];
+        bin_count = s_res[2];
       }
-      __syncthreads();
-      bin = s_res[0];
       pref = bin;
-      kk_pub = s_res[1];
+      kk_pub = kk1;
       // ---- the previous limit's prefix: when B is its bin, k_match2 has counted the level-2 digits of exactly the pairs in B
       //      (and the level-3 digits of those that share its 21 bits), so the digits can be resolved here.  A histogram whose
       //      total is not the count it must split (it cannot happen; it is checked for the cost of a compare) leaves level 1.
       if (spec_try && bin == (hint >> 20)) {  // uniform
-        const uint32_t kk = s_res[1], c2 = h2.x + h2.y;
-        if (tot2 == s_res[2]) {
+        const uint32_t kk = kk1, c2 = h2.x + h2.y;
+        if (tot2 == bin_count) {
           if (c2 > 0 && ex2 <= kk && kk < ex2 + c2) {
             const bool first = kk < ex2 + h2.x;
             s_res[3] = 2 * threadIdx.x + (first ? 0 : 1);
@@ -1720,11 +1802,11 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
       // depth 21: the selection finishes the 21-bit prefix like a level-1 bin whose candidates all carry one level-2 digit
       ss->bin = bin;
       ss->kk = kk_pub;
-      ss->bin_count = s_res[2];
+      ss->bin_count = bin_count;
       ss->limit_bits = pref;
     }
 #ifdef O3S_TEST_HOOKS
-    if (spec && hdr_i(hv, H_ITER) < kSpecTrace) const_cast<uint32_t*>(spec)[kSpecWords + hdr_i(hv, H_ITER)] = skip ? 0u : depth;
+    if (spec && hdr_i(hv, H_ITER) < kSpecTrace) const_cast<uint32_t*>(spec)[kSpecWords + hdr_i(hv, H_ITER)] = skip ? 0u : (depth | (quick ? 2u << 8 : 1u << 8));  // + which path found the bin
 #endif
   }
   if (cp.has_trim && n_fin == 0) return;

@@ -40,7 +40,13 @@ constexpr int kCovComps = 2 * kCovTri;  // pose covariance (k_cov): H = sum h h^
 // Speculative digit histograms of the trim selection (k_match2 -> k_classify), double-buffered by iteration parity: per parity
 // the level-2 digits of the pairs in the previous limit's level-1 bin (1024) and the level-3 digits of the pairs that share its
 // 21 leading bits (1024).  k_match2 of iteration i fills parity i & 1 and clears the other one for iteration i + 1.
-constexpr int kSpecHalf = 2048;
+// Behind them, per parity, the bin counters {F, Bl} in kSpecCntCopies copies (a block adds to copy blockIdx % 64: a single word would
+// serialise one atomic per block): F = found matches (the population of the level-1 histogram), Bl = those whose level-1 bin lies
+// below the previous limit's.  With the level-2 total they are all k_classify needs of the level-1 histogram when the limit stays in
+// the predicted bin.
+constexpr int kSpecHist = 2048;
+constexpr int kSpecCntCopies = 64;
+constexpr int kSpecHalf = kSpecHist + 2 * kSpecCntCopies;
 constexpr int kSpecWords = 2 * kSpecHalf;
 constexpr int kSpecTrace = 256;  // hooks build: the resolved depth of iterations 0..255 of the last call, behind the histograms
 constexpr int kSegs = 4;             // candidate segments of the trim selection (block b appends to segment b % 4); more segments lengthen the slot arithmetic of k_sel_finish (16: +3.7 us), fewer did not slow k_classify

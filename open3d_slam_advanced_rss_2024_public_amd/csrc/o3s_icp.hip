@@ -81,7 +81,8 @@ struct ChainArgs {
   int nb_match, nb_part, nb_cls;
   int nb_fused;  // blocks of the fused selection + normal-equation kernel (0: the two kernels are launched separately)
   bool has_n;
-  uint32_t* spec;  // the speculative digit histograms of the trim selection (k_match2 -> k_classify); null: level 1 only
+  uint32_t* spec;  // the speculative digit histograms and bin counters of the trim selection (k_match2 -> k_classify); null: level 1 only
+  int no_bin_counters;  // hooks build (O3S_NO_BIN_COUNTERS=1): k_classify sums the level-1 replicas in every iteration
   float* cert;     // the matcher's certificates (k_match2 -> the next k_match2); null: every query is searched in every iteration
   float *rx, *ry, *rz, *rnx, *rny, *rnz;
   ChainParams cp;
@@ -628,6 +629,8 @@ ChainArgs chain_args(o3s_icp* h, const ChainParams& cp) {
     const char* ne = O3S_HOOK_ENV("O3S_NO_SPEC_SELECT");  // read per call: the tests run both in one process
     const bool spec = cp.has_trim && !cp.mirror && !h->shard.active && !(ne && std::atoi(ne) != 0);
     a.spec = spec ? h->d_hist.as<uint32_t>() + kHistWords : nullptr;
+    const char* nb = O3S_HOOK_ENV("O3S_NO_BIN_COUNTERS");
+    a.no_bin_counters = (nb && std::atoi(nb) != 0) ? 1 : 0;
   }
   {  // certificates: single-GPU KDTree chains (O3S_NO_CERT=1: none; a work-skipping switch of O3S_DBG would falsify them)
     const char* nc = O3S_HOOK_ENV("O3S_NO_CERT");  // read per call: the tests run both in one process
@@ -754,7 +757,7 @@ void launch_iteration(o3s_icp* h, const ChainArgs& a, bool stats, hipEvent_t* ev
   hipLaunchKernelGGL(kern::k_classify, dim3(a.nb_cls), dim3(kern::kClsBlock), 0, s, a.rx, a.ry, a.rz, a.rnx, a.rny, a.rnz, a.N, ix.ref,
                      ix.refn, h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_hist.as<uint32_t>(), a.cp, st,
                      h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(), h->d_cand_cnt.as<uint32_t>(), h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins, h->d_mq.as<float4>(), h->d_mn.as<float4>(), h->d_cent.as<double>(), mode, kHistReplicas,
-                     10, 1023u, a.spec);
+                     10, 1023u, a.spec, a.cp.mirror ? kern::kInfF : ix.g.max_r2 O3S_DBG_ARG(a.no_bin_counters));
   if (ev) (void)hipEventRecord(ev[2], s);
   uint32_t* hist2 = h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins;
   if (a.nb_fused > 0) {  // selection + normal equations in one launch (kern::k_sel_ne); timed under "sel_finish"
@@ -1705,16 +1708,22 @@ int o3s_icp_get_trace(const o3s_icp* h, float* T_iters, float* limits, int64_t* 
 
 #ifdef O3S_TEST_HOOKS
 // hooks build only (not declared in include/): how many leading bits of each iteration's trim limit k_classify resolved in the
-// last call — 32 (the limit itself, from the previous limit's prefix), 21 (one digit left), 11 (level 1 only), 0 (no speculation)
-int o3s_icp_hook_sel_depth(const o3s_icp* h, int32_t* depth, int32_t cap) {
-  if (!h || !depth || h->shard.active) return 0;
+// last call — 32 (the limit itself, from the previous limit's prefix), 21 (one digit left), 11 (level 1 only), 0 (no speculation).
+// The trace word holds the depth in its low byte and, above it, the path that found the level-1 bin.
+static int hook_sel_trace(const o3s_icp* h, int32_t* out, int32_t cap, int shift) {
+  if (!h || !out || h->shard.active) return 0;
   const int n = std::min({(int)cap, h->last_iters, kSpecTrace});
   if (n <= 0) return 0;
   if (hipSetDevice(h->device) != hipSuccess) return 0;
   if (hipStreamSynchronize(h->stream) != hipSuccess) return 0;
-  if (hipMemcpy(depth, h->d_hist.as<uint32_t>() + kHistWords + kSpecWords, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  if (hipMemcpy(out, h->d_hist.as<uint32_t>() + kHistWords + kSpecWords, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  for (int k = 0; k < n; ++k) out[k] = (out[k] >> shift) & 0xff;
   return n;
 }
+int o3s_icp_hook_sel_depth(const o3s_icp* h, int32_t* depth, int32_t cap) { return hook_sel_trace(h, depth, cap, 0); }
+// hooks build only: which path resolved the level-1 bin in each iteration of the last call — 2: the bin counters (the replicas
+// stayed unread), 1: the scan of the level-1 replicas, 0: no selection (no Trimmed filter, no match at all, no speculation area)
+int o3s_icp_hook_bin_path(const o3s_icp* h, int32_t* path, int32_t cap) { return hook_sel_trace(h, path, cap, 8); }
 // hooks build only: per iteration of the last call, the queries whose certificate held at the head of k_match2 (`settled`) and those
 // of them whose whole wave skipped the search (`skipped`); all zeros for a chain without certificates (O3S_NO_CERT=1, mirror, sharded)
 int o3s_icp_hook_settled(const o3s_icp* h, int32_t* settled, int32_t* skipped, int32_t cap) {
