@@ -1627,16 +1627,22 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
   // the matcher counts only matches with d2 <= maxDist^2: the bins above that of maxDist^2 are empty by construction (about half of
   // them at maxDist 0.5), and a thread whose four bins all lie there has nothing to load
   const uint32_t live_bin = (max_r2 >= 0.f && max_r2 < kInfF) ? (__float_as_uint(max_r2) >> 20) : (uint32_t)(kHistBins - 1);
+  // the 16 loads are requested as ONE batch and summed afterwards, in replica order: with the sum inside the loading loop behind an
+  // early `return` the compiler waited for every load on its own, sixteen round trips (tests/test_isa_round_trips.py pins the batch)
   auto load_replicas = [&]() {
-    if ((uint32_t)(threadIdx.x * kBpt) > live_bin) return;
+    if ((uint32_t)(threadIdx.x * kBpt) <= live_bin) {
+      uint4 u0[kHistReplicas];
 #pragma unroll
-    for (int r = 0; r < kHistReplicas; ++r) {  // branch-free: a replica beyond n_rep re-reads replica 0 and counts nothing
-      const bool on = r < n_rep;
-      const uint4 u0 = *reinterpret_cast<const uint4*>(hist_rep + (size_t)(on ? r : 0) * kHistBins + threadIdx.x * kBpt);
-      c[0] += on ? u0.x : 0u;
-      c[1] += on ? u0.y : 0u;
-      c[2] += on ? u0.z : 0u;
-      c[3] += on ? u0.w : 0u;
+      for (int r = 0; r < kHistReplicas; ++r)  // branch-free: a replica beyond n_rep re-reads replica 0 and counts nothing
+        u0[r] = *reinterpret_cast<const uint4*>(hist_rep + (size_t)(r < n_rep ? r : 0) * kHistBins + threadIdx.x * kBpt);
+#pragma unroll
+      for (int r = 0; r < kHistReplicas; ++r) {
+        const bool on = r < n_rep;
+        c[0] += on ? u0[r].x : 0u;
+        c[1] += on ? u0[r].y : 0u;
+        c[2] += on ? u0[r].z : 0u;
+        c[3] += on ? u0[r].w : 0u;
+      }
     }
   };
 #ifdef O3S_TEST_HOOKS
@@ -1662,14 +1668,13 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
   float T[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) T[k] = hdr_f(hv, k);
-  // dependent gather of the matched reference normal; it is handed on (coalesced) to k_normal_eq
+  // dependent gather of the matched reference normal, requested here branch-free (an unmatched query reads slot 0 and masks the
+  // value) and consumed behind the bin scans, so its round trip overlaps their barriers; it is handed on (coalesced) to k_normal_eq
   const int slot0 = pe0 >= 0 ? pe0 : (pe0 <= -2 ? -2 - pe0 : -1);
   const bool matched = pe0 >= 0 || pe0 <= -2;
-  float4 rn = rn_in;
-  if (!nready) {  // uniform
-    if (matched && refn) rn = refn[slot0];
-    if (inb) mn[i] = rn;
-  }
+  const bool gather = !nready && refn != nullptr;  // uniform
+  float4 rn_g = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (gather) rn_g = refn[matched ? slot0 : 0];
   // ---- rank-k bin: every block repeats the same integer arithmetic on the same summed histogram ----
   // the previous limit of this call (+inf in its first iteration): when it is a finite number, the speculative histograms of this
   // iteration's parity are scanned together with the level-1 histogram (their scans share the barriers; whether they are used
@@ -1809,6 +1814,8 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
     if (spec && hdr_i(hv, H_ITER) < kSpecTrace) const_cast<uint32_t*>(spec)[kSpecWords + hdr_i(hv, H_ITER)] = skip ? 0u : (depth | (quick ? 2u << 8 : 1u << 8));  // + which path found the bin
 #endif
   }
+  const float4 rn = (gather && matched) ? rn_g : rn_in;
+  if (!nready && inb) mn[i] = rn;
   if (cp.has_trim && n_fin == 0) return;
   // ---- per-pair weights ----
   bool keep = matched && pe0 >= 0;  // caller-supplied zero weights arrive as pos <= -2 (module-level minimise)
@@ -2094,6 +2101,9 @@ __global__ void __launch_bounds__(kFinThreads) k_sel_partial(const IcpState* __r
   const float hv = hdr_load(st);
   const uint32_t ssw = reinterpret_cast<const uint32_t*>(ss)[threadIdx.x & 15];
   const uint2 h2 = *reinterpret_cast<const uint2*>(hist2 + 2 * threadIdx.x);
+  // the compiler must not sink these two below the exit (it did: three serial trips).  The hand-off words now travel with the header;
+  // the level-2 words are still requested behind the wait for the header, so the kernel takes two trips, not one
+  asm volatile("" ::"v"(ssw), "v"(h2.x), "v"(h2.y));
   if (hdr_i(hv, H_DONE)) return;
   const uint32_t bin = (uint32_t)__builtin_amdgcn_readlane((int)ssw, kSegs), kk = (uint32_t)__builtin_amdgcn_readlane((int)ssw, kSegs + 1),
                  skip = (uint32_t)__builtin_amdgcn_readlane((int)ssw, kSegs + 3),
@@ -2161,40 +2171,56 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
   static_assert((Sum::kWordsA + Sum::kWordsB) * 8 <= kSelCap * 4, "the block sum borrows the selection buffer");
   double* s_a = reinterpret_cast<double*>(s_dyn);
   double* s_b = s_a + Sum::kWordsA;
-  // first round trip: header, hand-off words, this thread's share of the classify partials, candidate counts, level 2
+  // first round trip: header (the caller's), hand-off words, this thread's share of the classify partials, candidate counts, level 2
+  // and the parked-list counter.  Every request is branch-free — clamped index, unconditional load, value masked afterwards: a
+  // predicated load compiles to an exec-mask region that waits for its value on the spot — and all of them stand in front of the
+  // first barrier, the chain's exit behind it: an exit in between makes the compiler wait for the header alone and sink the other
+  // requests below the branch.  A launch behind the end of the chain therefore issues these loads (every address is valid
+  // whatever the state says), stages the hand-off words in LDS and returns without a store to memory.
   const uint32_t ssw = reinterpret_cast<const uint32_t*>(ss)[threadIdx.x & 15];
-  double a[kCentComps] = {0, 0, 0, 0, 0, 0, 0};
+  const int nbm1 = nb > 0 ? nb - 1 : 0;
+  double p[kCentComps] = {0, 0, 0, 0, 0, 0, 0};  // the partials of classify block threadIdx.x: the first trip of the fold below, peeled
   if (mode & kModeCentroid) {
-    for (int b = threadIdx.x; b < nb; b += kFinThreads) {
 #pragma unroll
-      for (int k = 0; k < kCentComps; ++k) a[k] += part[k * nb + b];
-    }
+    for (int k = 0; k < kCentComps; ++k) p[k] = part[k * nb + min((int)threadIdx.x, nbm1)];
   }
   const int per_thread = (nb + kFinThreads - 1) / kFinThreads;  // consecutive classify blocks owned by a thread
   const int b0 = min(threadIdx.x * per_thread, nb), b1 = min(b0 + per_thread, nb);
   constexpr int kCntRegs = kBaseCap / kFinThreads;  // counts a thread keeps in registers (readings up to 1 M points)
   uint32_t cnts[kCntRegs];
-  uint32_t my_cnt = 0;
 #pragma unroll
-  for (int j = 0; j < kCntRegs; ++j) {
-    cnts[j] = b0 + j < b1 ? cand_cnt[b0 + j] : 0u;
-    my_cnt += cnts[j];
-  }
-  for (int b = b0 + kCntRegs; b < b1; ++b) my_cnt += cand_cnt[b];  // larger readings: re-read below
+  for (int j = 0; j < kCntRegs; ++j) cnts[j] = cand_cnt[min(b0 + j, nbm1)];
   const uint2 h2 = *reinterpret_cast<const uint2*>(hist2 + 2 * threadIdx.x);
   const uint32_t parked_before = park_cnt ? *park_cnt : 0u;  // what k_sel_partial appended (uniform)
-  if (hdr_i(hv, H_DONE)) return false;
-  if (hist_rep) {  // NULL when k_normal_eq clears the replicas (the fused chain); uniform
-    __syncthreads();  // every thread holds its level-2 words before anyone clears them
-    for (int k = threadIdx.x; k < kHistReplicas * kHistBins + 1024; k += kFinThreads) hist_rep[k] = 0u;  // + level 2, ready for the next iteration
-  }
   if (threadIdx.x < 16) s_ssw[threadIdx.x] = ssw;  // seg_count[4] (unused), bin, kk, bin_count, skip, ..., depth, limit_bits
   if (threadIdx.x == 0) {
     s_tmp[42] = 0x7f800000u;
     s_tmp[43] = 0u;
     s_tmp[45] = 0u;
   }
+  if (hist_rep) asm volatile("" ::"v"(h2.x), "v"(h2.y));  // every thread holds its level-2 words before anyone clears them (below)
   __syncthreads();
+  if (hdr_i(hv, H_DONE)) return false;
+  // the values of the first round trip are consumed from here on; what follows it are the later trips of larger readings
+  double a[kCentComps];
+#pragma unroll
+  for (int k = 0; k < kCentComps; ++k) a[k] = 0.0 + ((int)threadIdx.x < nb ? p[k] : 0.0);
+  if (mode & kModeCentroid) {
+    for (int b = threadIdx.x + kFinThreads; b < nb; b += kFinThreads) {
+#pragma unroll
+      for (int k = 0; k < kCentComps; ++k) a[k] += part[k * nb + b];
+    }
+  }
+  uint32_t my_cnt = 0;
+#pragma unroll
+  for (int j = 0; j < kCntRegs; ++j) {
+    cnts[j] = b0 + j < b1 ? cnts[j] : 0u;
+    my_cnt += cnts[j];
+  }
+  for (int b = b0 + kCntRegs; b < b1; ++b) my_cnt += cand_cnt[b];  // larger readings: re-read below
+  if (hist_rep) {  // NULL when k_normal_eq clears the replicas (the fused chain); uniform
+    for (int k = threadIdx.x; k < kHistReplicas * kHistBins + 1024; k += kFinThreads) hist_rep[k] = 0u;  // + level 2, ready for the next iteration
+  }
   const uint32_t bin = s_ssw[kSegs], skip = s_ssw[kSegs + 3];
   uint32_t kk = s_ssw[kSegs + 1];
   // depth 32: k_classify resolved the limit from the previous limit's prefix and summed every kept pair itself — there are no
@@ -2749,8 +2775,9 @@ __global__ void __launch_bounds__(kBlock) k_solve(const double* __restrict__ par
 // (<= kFusedMaxBlocks): every block first repeats the (small) exact selection for itself — sel_finish_body<true>; costs
 // ~0.5 us more than one block doing it alone, measured with 196 redundant blocks — and then accumulates its share of the
 // 27 sums with the limit and the means it has just formed.  Saves the second kernel's start-up round trip and the hand-over
-// through the state header.  This block's points are requested before the selection starts, so their round trip hides
-// behind it.  The level-1 replicas are cleared here as k_normal_eq does; the level-2 histogram — still being read by other
+// through the state header.  This block's points travel in the same round trip as the selection's own requests (header, points,
+// hand-off words, partials, counts, level 2: one batch ahead of the first barrier — tools/isa_round_trips.py).
+// The level-1 replicas are cleared here as k_normal_eq does; the level-2 histogram — still being read by other
 // blocks of this launch — is cleared by block 0 of the next k_match2.
 constexpr int kFusedMaxBlocks = 256;   // one block per CU (the selection's LDS plan fills most of a CU's LDS)
 // The normal-equation half uses the first kBlock (256) threads with kNePPT points each and the same fixed-order block sum
@@ -2777,18 +2804,24 @@ __global__ void __launch_bounds__(kFinThreads) k_sel_ne(ChainParams cp, IcpState
 #pragma unroll
   for (int u = 0; u < kNePPT; ++u) {  // this block's points: same assignment as k_normal_eq (one trip: gridDim covers N)
     const int i = blockIdx.x * (kBlock * kNePPT) + u * kBlock + (worker ? threadIdx.x : 0);
-    const bool in = worker && i < N;
     const int ic = i < N ? i : N - 1;
-    pe[u] = in ? pos[ic] : -1;
-    d[u] = in ? d2[ic] : kInfF;
+    pe[u] = pos[ic];  // unconditional, masked below
+    d[u] = d2[ic];
     x0[u] = rx[ic];
     y0[u] = ry[ic];
     z0[u] = rz[ic];
     q[u] = mq[ic];
     n[u] = mn[ic];
   }
-  if (hdr_i(hv, H_DONE)) return;  // the chain has ended in an earlier iteration: nothing to close
+  // (no exit of its own in front of the selection: its requests belong to the same round trip as the ones above; when the chain
+  // has ended in an earlier iteration sel_finish_body returns false without a side effect)
   const bool go_on = sel_finish_body<true>(nullptr, cp, st, ss, cand, cand_cnt, hist2, base_scratch, part_cent, nb_cls, mode, hv, s_out);
+#pragma unroll
+  for (int u = 0; u < kNePPT; ++u) {
+    const bool in = worker && blockIdx.x * (kBlock * kNePPT) + u * kBlock + (int)threadIdx.x < N;
+    pe[u] = in ? pe[u] : -1;
+    d[u] = in ? d[u] : kInfF;
+  }
   __syncthreads();        // s_out is complete, the selection is done with s_dyn
   if (!go_on) return;     // uniform, and the same in every block: an earlier error, or no pair kept — k_solve closes the iteration
   if (hist_zero)
