@@ -2,10 +2,10 @@
 from .icp import (ICP, IcpConfig, IcpStats, ConvergenceError, TransformationError, InvalidModuleType, HipError,  # noqa: F401
                   compute_batch)
 from .dense_map import DenseMap  # noqa: F401
-from .submap import ProcessedScan, Submap  # noqa: F401
+from .submap import AssembledMap, ProcessedScan, Submap  # noqa: F401
 from .submap_collection import SubmapCollection  # noqa: F401
 from .odometry import ConstantVelocityMotionCompensation, LidarOdometry, RawScan, TransformBuffer  # noqa: F401
 from .pose_graph import Constraint, OptimizationProblem, update_submaps_and_trajectory  # noqa: F401
 
-__all__ = ["ICP", "IcpConfig", "IcpStats", "ConvergenceError", "TransformationError", "InvalidModuleType", "HipError", "compute_batch", "Submap", "ProcessedScan", "SubmapCollection", "DenseMap", "LidarOdometry",
+__all__ = ["ICP", "IcpConfig", "IcpStats", "ConvergenceError", "TransformationError", "InvalidModuleType", "HipError", "compute_batch", "Submap", "AssembledMap", "ProcessedScan", "SubmapCollection", "DenseMap", "LidarOdometry",
            "ConstantVelocityMotionCompensation", "TransformBuffer", "RawScan", "Constraint", "OptimizationProblem", "update_submaps_and_trajectory"]

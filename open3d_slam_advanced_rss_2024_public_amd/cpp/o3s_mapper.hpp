@@ -24,6 +24,7 @@
 //   :483-489      insert the merge cloud if the sensor moved at least minMovementBetweenMappingSteps_
 //   :190, 228, 450, 460   mapToRangeSensorBuffer_.push: the registered poses, which motionCompensationMap_ reads
 //                 (SlamWrapper.cpp:445-447, 671: undistortInputPointCloud before the mapper sees the sweep) -> enableMotionCompensation
+//   :506-538      getAssembledMapPointCloud: the map of all submaps                -> o3s_assembled_map_build (AssembledMapHip)
 // 4x4 matrices are column-major doubles (Eigen::Matrix4d::data()).  Isometry products / inverses are restated as plain
 // k = 0..3 accumulations (Eigen is not part of the tree: its evaluation order is not pinned).
 #pragma once
@@ -137,6 +138,10 @@ class MapperHip {
   // initial map for the localisation mode (isUseInitialMap_): Mapper.cpp:180-183 inserts it as the first "scan"
   SubmapHip& activeSubmap() { return submaps_.activeSubmap(); }
   SubmapCollectionHip& submaps() { return submaps_; }
+  // Mapper::getAssembledMapPointCloud (Mapper.cpp:506-538) into the resident `out`: the map clouds of all submaps in index order with
+  // the normals and colours every submap carries; voxelSize > 0 also down-samples it (SlamWrapperRos::publishMaps).  Returns the size;
+  // out.download() is the one copy to the host.  Call it from the mapping thread.
+  std::int64_t getAssembledMapPointCloud(AssembledMapHip& out, double voxelSize = 0.0) { return submaps_.assembleMap(out, voxelSize); }
   IcpHip& icp() { return icp_; }
   const Mat4& mapToRangeSensor() const { return mapToRangeSensor_; }
   const Mat4& lastPrior() const { return lastPrior_; }

@@ -19,6 +19,8 @@
 //              submaps by ONE o3s_submaps_transform call; per submap mapToRangeSensor_ * T, T * submapCenter_, the dense map where the
 //              driver keeps one (Submap.cpp:115-128); the overlap buffer is flushed
 //   :75-81     updateAdjacencyMatrix: the submaps of a loop-closure constraint become adjacent
+//   :69-73     getTotalNumPoints; assembleMap: the loop of Mapper::getAssembledMapPointCloud (Mapper.cpp:524-535) over the resident
+//              submaps as ONE o3s_assembled_map_build call into an AssembledMapHip (the map of all submaps, optionally down-sampled)
 // Not here: candidate selection and isRegistrationConsistent (host policy).  The RANSAC of place recognition
 //              between two submaps of the collection is o3s_submap_registration_ransac (o3s_submap.h) on their feature sets.
 // The scans the buffer keeps are resident o3s_scan objects: the caller hands over the scan it has just pre-processed and
@@ -36,6 +38,7 @@
 #include <utility>
 #include <vector>
 
+#include "assembled_map/o3s_assembled_map.h"
 #include "o3s_icp.hpp"
 #include "o3s_pose_graph.hpp"
 #include "o3s_scan.h"
@@ -65,6 +68,39 @@ class AdjacencyHip {
 
  private:
   std::map<std::size_t, std::set<std::size_t>> adj_;
+};
+
+// The map of all submaps, resident on the device (assembled_map/o3s_assembled_map.h): the result of
+// SubmapCollectionHip::assembleMap / MapperHip::getAssembledMapPointCloud.  Keep ONE object for the life of the mapper: its arrays
+// only grow, so the periodic caller (SlamWrapperRos::publishMaps, every 250 ms) neither frees nor allocates in steady state.
+class AssembledMapHip {
+ public:
+  explicit AssembledMapHip(int device = 0) {
+    const int rc = o3s_assembled_map_create(device, &a_);
+    if (rc != O3S_OK) throw std::runtime_error("o3s_assembled_map_create failed (status " + std::to_string(rc) + ")");
+  }
+  ~AssembledMapHip() { o3s_assembled_map_destroy(a_); }
+  AssembledMapHip(const AssembledMapHip&) = delete;
+  AssembledMapHip& operator=(const AssembledMapHip&) = delete;
+
+  std::int64_t size() const { return o3s_assembled_map_size(a_); }
+  bool hasNormals() const { return o3s_assembled_map_has_normals(a_) != 0; }
+  bool hasColors() const { return o3s_assembled_map_has_colors(a_) != 0; }
+  // 3 x size() doubles each (std::vector<Eigen::Vector3d>::data()); normals / colors nullable, refused when the map carries none
+  void download(double* points3xN, double* normals3xN = nullptr, double* colors3xN = nullptr) const {
+    const int rc = o3s_assembled_map_download(a_, points3xN, normals3xN, colors3xN);
+    if (rc == O3S_ERR_BAD_SHAPE) throw std::invalid_argument("AssembledMapHip::download: the map carries no such attribute");
+    if (rc != O3S_OK) throw std::runtime_error("o3s_assembled_map_download failed (status " + std::to_string(rc) + ")");
+  }
+  // the assembled map becomes dst's map cloud without leaving HBM (an ICP reference over the whole map, features of the whole map)
+  void toSubmap(SubmapHip& dst) const {
+    if (o3s_assembled_map_to_submap(a_, dst.handle()) != O3S_OK) throw std::runtime_error("o3s_assembled_map_to_submap failed");
+  }
+  std::int64_t deviceBytes() const { return o3s_assembled_map_device_bytes(a_); }
+  o3s_assembled_map* handle() { return a_; }
+
+ private:
+  o3s_assembled_map* a_ = nullptr;
 };
 
 class SubmapCollectionHip {
@@ -182,6 +218,25 @@ class SubmapCollectionHip {
       free_.push_back(buffer_.front().scan);
       buffer_.pop_front();
     }
+  }
+  // SubmapCollection::getTotalNumPoints (:69-73); completes pending inserts (o3s_submap_size)
+  std::size_t getTotalNumPoints() const {
+    std::size_t sum = 0;
+    for (const Entry& e : submaps_) sum += (std::size_t)e.map->size();
+    return sum;
+  }
+  // The loop of Mapper::getAssembledMapPointCloud (Mapper.cpp:524-535) as one device call: every submap in index order — the active
+  // one is not special — into `out`.  voxelSize <= 0: the plain concatenation (what saveMap writes); > 0: Open3D VoxelDownSample of it
+  // (publishMaps).  attrs: O3S_ASSEMBLE_NORMALS | O3S_ASSEMBLE_COLORS; an attribute not every non-empty submap carries is dropped.
+  // Call it from the thread that inserts (the rule of o3s_submap_clone).  Returns the size of the result.
+  std::int64_t assembleMap(AssembledMapHip& out, double voxelSize = 0.0, int attrs = O3S_ASSEMBLE_NORMALS | O3S_ASSEMBLE_COLORS) {
+    std::vector<o3s_submap*> maps;
+    for (Entry& e : submaps_) maps.push_back(e.map->handle());
+    std::int64_t n = 0;
+    const int rc = o3s_assembled_map_build(out.handle(), (std::int32_t)maps.size(), maps.data(), voxelSize, (std::int32_t)attrs, &n);
+    if (rc == O3S_ERR_BAD_ARGUMENT) throw std::invalid_argument("SubmapCollection::assembleMap: too many points, or a voxel size the map's extent does not pack with");
+    if (rc != O3S_OK) throw std::runtime_error("o3s_assembled_map_build failed (status " + std::to_string(rc) + ")");
+    return n;
   }
   bool lastInsertSwitchedSubmaps() const { return lastSwitched_; }
   // where the last switch of submaps spent its time, ms: creating the new object | the closing scan into the previous submap | its

@@ -238,6 +238,7 @@ int o3s_motion_from_poses(const double T_start[16], double t_start, const double
 
 #include "o3d_icp_impl.h"
 #include "submap_impl.h"
+#include "assemble_impl.h"
 #include "features_impl.h"
 #include "ransac_impl.h"
 #include "dense_map_impl.h"

@@ -82,6 +82,12 @@ class Mapper:
         self.T = mul4(dT, self.T)
         self.T_prev = mul4(dT, self.T_prev)
 
+    def getAssembledMapPointCloud(self, out, voxel_size=0.0):
+        """Mapper::getAssembledMapPointCloud (Mapper.cpp:506-538) into the resident `out` (submap.AssembledMap): the map clouds of
+        all submaps in index order, normals and colours where every submap carries them; voxel_size > 0 also down-samples it
+        (SlamWrapperRos::publishMaps).  Returns the size; out.getPointCloud() is the one copy to the host."""
+        return self.col.assembleMap(out, voxel_size)
+
     def _odom(self, stamp):
         """getTransform(t, odomToRangeSensorBuffer_) * calibration_.inverse()   (Mapper.cpp:221-222, 270-273)"""
         return mul4(self.odom[stamp], self.calib_inv)

@@ -52,6 +52,18 @@ def _L():
         L.o3s_submap_feature_correspondences.argtypes = [vp, vp, C.c_int32, C.c_int32, ip, C.POINTER(C.c_int64), ip]
         L.o3s_submap_transform.argtypes = [vp, dp]
         L.o3s_submaps_transform.argtypes = [C.c_int32, C.POINTER(vp), dp]
+        L.o3s_assembled_map_create.argtypes = [C.c_int, C.POINTER(vp)]
+        L.o3s_assembled_map_destroy.argtypes = [vp]
+        L.o3s_assembled_map_destroy.restype = None
+        L.o3s_assembled_map_build.argtypes = [vp, C.c_int32, C.POINTER(vp), C.c_double, C.c_int32, C.POINTER(C.c_int64)]
+        L.o3s_assembled_map_size.argtypes = [vp]
+        L.o3s_assembled_map_size.restype = C.c_int64
+        L.o3s_assembled_map_has_normals.argtypes = [vp]
+        L.o3s_assembled_map_has_colors.argtypes = [vp]
+        L.o3s_assembled_map_download.argtypes = [vp, dp, dp, dp]
+        L.o3s_assembled_map_to_submap.argtypes = [vp, vp]
+        L.o3s_assembled_map_device_bytes.argtypes = [vp]
+        L.o3s_assembled_map_device_bytes.restype = C.c_int64
     return L
 
 
@@ -340,6 +352,91 @@ def transform_submaps(maps, Ts):
         raise ValueError("transform_submaps: a repeated submap, or a T that is not finite or has a zero last row")
     if rc != _lib.OK:
         raise RuntimeError(f"o3s_submaps_transform failed with o3s_status {rc}")
+
+
+class AssembledMap:
+    """The map clouds of several resident submaps assembled into one cloud on the device (include/assembled_map/o3s_assembled_map.h):
+    Mapper::getAssembledMapPointCloud (Mapper.cpp:506-538) and, with a voxel size, Open3D's VoxelDownSample of it — what
+    SlamWrapper::saveMap writes and SlamWrapperRos::publishMaps publishes.  The result and the work area stay resident and only
+    grow; nothing but the result ever crosses the bus, and only when getPointCloud() asks for it."""
+
+    NORMALS, COLORS = 1, 2   # bits of the C call's `attrs`
+
+    def __init__(self, device: int = 0):
+        self._lib = _L()   # the library this handle belongs to (product or a hooks build): every later call goes through it
+        self._pid = os.getpid()   # _lib.forked_copy: a forked child must not destroy the handle
+        self._h = C.c_void_p()
+        rc = self._lib.o3s_assembled_map_create(device, C.byref(self._h))
+        if rc != _lib.OK:
+            self._h = C.c_void_p()
+            raise RuntimeError(f"o3s_assembled_map_create failed with o3s_status {rc} (no CPU fallback)")
+        self.device = int(device)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            if not _lib.forked_copy(self):   # a forked child drops its copy of the wrapper, the handle is the parent's
+                self._lib.o3s_assembled_map_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def build(self, maps, voxel_size: float = 0.0, normals: bool = True, colors: bool = True) -> int:
+        """Assembles `maps` (Submap objects, or None for a NULL pointer) in the order given; voxel_size <= 0: the plain concatenation,
+        > 0: VoxelDownSample of it with the per-voxel sums in concatenation order.  The result carries normals / colours iff they
+        are asked for and every non-empty submap has them.  A NULL or repeated submap, a submap of another device, more than
+        2^31 - 1 points or a voxel index range that does not pack raises ValueError and leaves the previous result.  Returns the size."""
+        maps = list(maps)
+        if any(m is not None and m._lib is not self._lib for m in maps):
+            raise ValueError("AssembledMap.build: the submaps belong to another build of the library")
+        hs = (C.c_void_p * max(len(maps), 1))(*[None if m is None else m._h.value for m in maps])
+        k = C.c_int64(0)
+        attrs = (self.NORMALS if normals else 0) | (self.COLORS if colors else 0)
+        rc = self._lib.o3s_assembled_map_build(self._h, len(maps), hs, float(voxel_size), attrs, C.byref(k))
+        if rc == _lib.ERR_BAD_ARGUMENT:
+            raise ValueError("AssembledMap.build: a NULL or repeated submap, a submap of another device, more than 2^31 - 1 points, or a "
+                             "voxel index range that does not pack into 63 bits")
+        if rc != _lib.OK:
+            raise RuntimeError(f"o3s_assembled_map_build failed with o3s_status {rc}")
+        return int(k.value)
+
+    def __len__(self) -> int:
+        return int(self._lib.o3s_assembled_map_size(self._h))
+
+    @property
+    def has_normals(self) -> bool:
+        return bool(self._lib.o3s_assembled_map_has_normals(self._h))
+
+    @property
+    def has_colors(self) -> bool:
+        return bool(self._lib.o3s_assembled_map_has_colors(self._h))
+
+    def getPointCloud(self):
+        """(points, normals | None, colors | None) copied to the host: the one transfer of the assembled map."""
+        n = len(self)
+        pts = np.zeros((n, 3), np.float64)
+        nrm = np.zeros((n, 3), np.float64) if self.has_normals else None
+        col = np.zeros((n, 3), np.float64) if self.has_colors else None
+        rc = self._lib.o3s_assembled_map_download(self._h, _d(pts), _d(nrm), _d(col))
+        if rc != _lib.OK:
+            raise RuntimeError(f"o3s_assembled_map_download failed with o3s_status {rc}")
+        return pts, nrm, col
+
+    def toSubmap(self, dst: "Submap"):
+        """Replaces dst's map cloud with the assembled map without leaving HBM (o3s_assembled_map_to_submap): colours are kept,
+        dst's voxel layout and features are dropped.  dst may then serve as an ICP reference (set_reference) or get features."""
+        rc = self._lib.o3s_assembled_map_to_submap(self._h, dst._h)
+        if rc == _lib.ERR_BAD_ARGUMENT:
+            raise ValueError("AssembledMap.toSubmap: the submap lives on another device")
+        if rc != _lib.OK:
+            raise RuntimeError(f"o3s_assembled_map_to_submap failed with o3s_status {rc}")
+        dst.has_normals = self.has_normals if len(self) else None
+
+    def device_bytes(self) -> int:
+        return int(self._lib.o3s_assembled_map_device_bytes(self._h))
 
 
 class ProcessedScan:

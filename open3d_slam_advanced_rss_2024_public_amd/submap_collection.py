@@ -5,7 +5,7 @@ import numpy as np
 
 from . import cloud_ops as co
 from .mapper import mul4
-from .submap import ProcessedScan, Submap, transform_submaps
+from .submap import AssembledMap, ProcessedScan, Submap, transform_submaps
 
 
 class SubmapCollection:
@@ -13,12 +13,14 @@ class SubmapCollection:
     same steps as cpp/o3s_submap_collection.hpp, resident scans in a ring of numScansOverlap + 1 objects."""
 
     def __init__(self, radius, min_num, max_points, overlap, map_voxel, map_builder_cropper, submap_factory=None, scan_factory=None,
-                 transform_maps=None):
+                 transform_maps=None, assemble_maps=None):
         """map_builder_cropper: (kind, p0[, p1, p2]) as for cloud_ops.croppingVolumeFactory.  submap_factory / scan_factory:
         stand-ins for the device-resident objects (insertProcessed / __len__ / computeSubmapCenter) — the CPU tests of the
         switching rules use them; the default is the real thing.  transform_maps(maps, Ts): the one batched device call of
-        transform() (submap.transform_submaps unless a stand-in is given)."""
+        transform() (submap.transform_submaps unless a stand-in is given).  assemble_maps(out, maps, voxel_size, normals, colors):
+        the one device call of assembleMap() (AssembledMap.build unless a stand-in is given)."""
         self._transform_maps = transform_maps or transform_submaps
+        self._assemble_maps = assemble_maps or AssembledMap.build
         self.radius, self.min_num, self.max_points, self.overlap = radius, min_num, max_points, overlap
         self.map_voxel, self.cropper = map_voxel, tuple(map_builder_cropper)
         self._new_submap = submap_factory or (lambda: Submap(self.map_voxel, co.croppingVolumeFactory(*self.cropper)))
@@ -122,6 +124,16 @@ class SubmapCollection:
         for c in loop_closure_constraints:
             a, b = c.source_submap_idx, c.target_submap_idx
             self.edges.add((min(a, b), max(a, b)))
+
+    def getTotalNumPoints(self) -> int:
+        """SubmapCollection::getTotalNumPoints (:69-73): the sum of the submaps' map sizes."""
+        return sum(len(m) for m in self.maps)
+
+    def assembleMap(self, out: AssembledMap, voxel_size=0.0, normals=True, colors=True) -> int:
+        """Mapper::getAssembledMapPointCloud's loop over the collection (Mapper.cpp:524-535) as one device call: every submap in
+        index order — the active one is not special — into `out`; voxel_size > 0 down-samples the assembled cloud the way
+        SlamWrapperRos::publishMaps does.  Returns the size of the result."""
+        return self._assemble_maps(out, list(self.maps), voxel_size, normals, colors)
 
     def transform(self, increments):
         """SubmapCollection::transform (:324-375).  increments: objects with .dT (4x4) and .submap_id.  A submap an increment names

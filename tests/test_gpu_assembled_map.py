@@ -1,0 +1,362 @@
+"""o3s_assembled_map_* (include/assembled_map/o3s_assembled_map.h): the map clouds of several resident submaps assembled into one
+cloud on the device — Mapper::getAssembledMapPointCloud (Mapper.cpp:506-538) and Open3D's VoxelDownSample of it.  MI355X only.
+
+The yardstick is the CPU oracle applied to the DOWNLOADED submaps: np.concatenate for the plain form, oracle.voxel_downsample_o3d
+(points, normals, voxel indices) and oracle.voxelize_attrs(1, ...) (colours) on that concatenation for the voxelised form.  Every
+comparison is bit for bit.  Points are uniform in a +-4 m cube, voxel 0.5 m: 16^3 voxels for a few thousand points, so most voxels
+hold points of several submaps."""
+import ctypes as C
+import types
+
+import numpy as np
+import pytest
+
+import pose_graph_ref as ref
+from oracle import oracle as orc
+from open3d_slam_advanced_rss_2024_public_amd import AssembledMap, ICP, IcpConfig, ProcessedScan, Submap, _lib
+from open3d_slam_advanced_rss_2024_public_amd import cloud_ops as co
+from open3d_slam_advanced_rss_2024_public_amd import synthetic as syn
+from open3d_slam_advanced_rss_2024_public_amd.cloud_ops import _d
+from open3d_slam_advanced_rss_2024_public_amd.mapper import Mapper
+from open3d_slam_advanced_rss_2024_public_amd.submap_collection import SubmapCollection
+
+pytestmark = pytest.mark.gpu
+
+BIG = co.croppingVolumeFactory("MaxRadius", 1000.0)
+VOX = 0.5
+SIZES = (1, 257, 0, 1023, 5003)          # an empty submap in the middle, segment ends off the block boundaries (256)
+SHIFT = ref.exp6(np.array([0, 0, 0, 1.0, 0, 0]))   # a pose that is not (almost) the identity: the insert does not double the scan
+
+
+def same(a, b):
+    return a.shape == b.shape and a.tobytes() == b.tobytes()         # bit for bit (the sign of a zero included)
+
+
+def raw_cloud(n, seed):
+    rng = np.random.default_rng(seed)
+    p = rng.uniform(-4.0, 4.0, (n, 3))
+    nr = rng.normal(size=(n, 3))
+    return p, nr / np.linalg.norm(nr, axis=1)[:, None], rng.uniform(0.0, 1.0, (n, 3))
+
+
+def coloured_submap(n, seed, planted=None):
+    m = Submap(0.0, BIG)                 # map voxel size 0: the map is never voxelised, the cloud is what was inserted
+    if n:
+        p, nr, col = raw_cloud(n, seed)
+        if planted is not None:
+            p[n // 2] = planted
+        m.insertScanColored(p, nr, col, SHIFT)
+    return m
+
+
+def download(m):
+    """(points, normals | None, colours | None) of a submap; empty arrays for an empty one."""
+    p, n = m.getMapPointCloud()
+    c = m.getMapColors() if len(m) and m.hasColors() else None
+    return p, n, c
+
+
+def cat(parts):
+    parts = [x for x in parts if x is not None and len(x)]
+    return np.concatenate(parts) if parts else np.zeros((0, 3))
+
+
+def oracle_voxelised(P, N, Cc, voxel=VOX):
+    """Open3D VoxelDownSample of one host cloud by the oracle, in ascending (z, y, x) voxel order: (p, n, col, voxel idx)."""
+    op, on, oi = orc.voxel_downsample_o3d(voxel, P, N)
+    ocol = orc.voxelize_attrs(1, None, voxel, P, Cc, None)[0] if Cc is not None else None
+    order = np.lexsort((oi[:, 0], oi[:, 1], oi[:, 2]))
+    return op[order], (None if on is None else on[order]), (None if ocol is None else ocol[order]), oi[order]
+
+
+def check_cloud(got, want):
+    for g, w, name in zip(got, want, ("points", "normals", "colours")):
+        assert (g is None) == (w is None), name
+        if w is not None:
+            assert same(g, w), name
+
+
+@pytest.fixture(scope="module")
+def five():
+    """Five coloured submaps with normals of SIZES points (computed once, left unchanged) and their downloads.  Submap 3 carries a
+    planted point below everybody else's x: the global min bound of that axis does not come from the first submap."""
+    maps = [coloured_submap(n, 40 + k, planted=(-5.7, 0.3, -0.2) if k == 3 else None) for k, n in enumerate(SIZES)]
+    clouds = [download(m) for m in maps]
+    assert [len(m) for m in maps] == list(SIZES)
+    return maps, clouds
+
+
+# ---- 1. concatenation ------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("normals,colors", [(True, True), (True, False), (False, False)])
+def test_concatenation_is_bit_equal(five, normals, colors):
+    maps, clouds = five
+    am = AssembledMap()
+    assert am.build(maps, 0.0, normals, colors) == sum(SIZES) == len(am)
+    assert (am.has_normals, am.has_colors) == (normals, colors)
+    want = (cat(c[0] for c in clouds), cat(c[1] for c in clouds) if normals else None, cat(c[2] for c in clouds) if colors else None)
+    check_cloud(am.getPointCloud(), want)
+
+
+# ---- 2. voxelised ----------------------------------------------------------------------------------------------------------
+
+def test_voxelised_equals_the_oracle_on_the_concatenation(five):
+    maps, clouds = five
+    P, N, Cc = (cat(c[k] for c in clouds) for k in range(3))
+    owner = np.concatenate([np.full(len(c[0]), k) for k, c in enumerate(clouds)])
+    # (a) from the oracle's voxel indices of the INPUTS: at least one voxel holds points of two or more submaps
+    idx = orc.voxel_idx_div(P, VOX, P.min(axis=0) - VOX * 0.5)
+    _, inv = np.unique(idx, axis=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    shared = sum(1 for v in np.unique(inv) if len(set(owner[inv == v])) >= 2)
+    assert shared >= 1
+    # (b) the global min bound of at least one axis comes from a submap other than the first
+    assert any(owner[np.argmin(P[:, a])] != 0 and P[:, a].min() < clouds[0][0][:, a].min() for a in range(3))
+    am = AssembledMap()
+    n = am.build(maps, VOX)
+    op, on, ocol, _ = oracle_voxelised(P, N, Cc)
+    assert n == len(op) and n < len(P)
+    print(f"{len(P)} points of {len(maps)} submaps -> {n} voxels, {shared} of them shared between submaps")
+    check_cloud(am.getPointCloud(), (op, on, ocol))
+
+
+# ---- 3. one submap -----------------------------------------------------------------------------------------------------------
+
+def test_one_submap_equals_the_host_buffer_voxeliser(five):
+    maps, clouds = five
+    am = AssembledMap()
+    am.build([maps[4]], VOX)
+    gp, gn, gcol, _, _ = co.voxelize_attr(VOX, *clouds[4])
+    check_cloud(am.getPointCloud(), (gp, gn, gcol))
+
+
+# ---- 4. order ------------------------------------------------------------------------------------------------------------------
+
+def test_reversed_submap_order_is_the_oracle_on_the_reversed_concatenation(five):
+    """The summation-order contract, not commutativity: a shared voxel's sums run in the order the submaps are given."""
+    maps, clouds = five
+    rc = clouds[::-1]
+    P, N, Cc = (cat(c[k] for c in rc) for k in range(3))
+    am = AssembledMap()
+    am.build(maps[::-1], VOX)
+    check_cloud(am.getPointCloud(), oracle_voxelised(P, N, Cc)[:3])
+
+
+# ---- 5. mixed attributes, empty input ----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("voxel", [0.0, VOX])
+def test_an_attribute_only_some_submaps_carry_is_dropped(five, voxel):
+    maps, clouds = five
+    p, nr, col = raw_cloud(700, 77)
+    no_normals = Submap(0.0, BIG)
+    no_normals.insertScanColored(p, None, col, SHIFT)
+    no_colours = Submap(0.0, BIG)
+    no_colours.insertScan(p, nr, SHIFT)
+    assert no_normals.hasColors() and not no_colours.hasColors()
+    am = AssembledMap()
+    for extra, (hn, hc) in ((no_normals, (False, True)), (no_colours, (True, False))):
+        ms = [maps[1], extra, maps[3]]
+        cl = [clouds[1], download(extra), clouds[3]]
+        am.build(ms, voxel)
+        assert (am.has_normals, am.has_colors) == (hn, hc)
+        P = cat(c[0] for c in cl)
+        N = cat(c[1] for c in cl) if hn else None
+        Cc = cat(c[2] for c in cl) if hc else None
+        check_cloud(am.getPointCloud(), (P, N, Cc) if voxel == 0.0 else oracle_voxelised(P, N, Cc)[:3])   # the points are unchanged by the drop
+
+
+def test_empty_input_is_ok_and_empty(five):
+    maps, _ = five
+    am = AssembledMap()
+    am.build(maps, VOX)
+    assert len(am) > 0
+    for ms in ([Submap(0.0, BIG), Submap(0.0, BIG)], []):
+        for voxel in (0.0, VOX):
+            assert am.build(ms, voxel) == 0 == len(am)
+            assert not am.has_normals and not am.has_colors
+            p, n, c = am.getPointCloud()
+            assert p.shape == (0, 3) and n is None and c is None
+        am.build(maps, VOX)
+
+
+# ---- 6. read-only --------------------------------------------------------------------------------------------------------------
+
+WIDE, NARROW = ("MaxRadius", 9.0), ("MaxRadius", 8.0)
+
+
+@pytest.fixture(scope="module")
+def corridor():
+    """Six sweeps of a drive that stays inside the map-builder volume (tests/test_gpu_submap_transform.py's): every insert after
+    the first takes the merge path and may be left pending."""
+    world = syn.make_world(60000.0, seed=11)
+    poses = [np.asarray(syn.corridor_pose(world, k, 1.5), np.float64) for k in range(6)]
+    sweeps = [syn.make_lidar_scan(world, T, 32, 512, max_range=40.0, sigma=0.01, seed=500 + k) for k, T in enumerate(poses)]
+    return [(sp.astype(np.float64), sn.astype(np.float64), T) for (sp, sn), T in zip(sweeps, poses)]
+
+
+def _insert(m, ps, sweep):
+    sp, sn, T = sweep
+    ps.preprocess(co.croppingVolumeFactory(*WIDE), 0.1, co.croppingVolumeFactory(*NARROW), sp, sn)
+    m.insertProcessed(ps, T)
+
+
+def test_the_submaps_are_only_read(five):
+    maps, clouds = five
+    before = [m.device_bytes() for m in maps]
+    am = AssembledMap()
+    for voxel in (0.0, VOX):
+        am.build(maps, voxel)
+        for m, c in zip(maps, clouds):
+            check_cloud(download(m), c)
+    assert [m.device_bytes() for m in maps] == before
+
+
+def test_the_active_submap_still_merges_after_a_build(corridor):
+    a, twin = Submap(0.1, co.croppingVolumeFactory(*WIDE)), Submap(0.1, co.croppingVolumeFactory(*WIDE))
+    ps = ProcessedScan()
+    for k in range(3):
+        _insert(a, ps, corridor[k])
+        _insert(twin, ps, corridor[k])
+    stats = a.insert_stats()
+    assert stats[0] >= 1 and stats == twin.insert_stats()      # the merge path is in use (a voxelised map, two inserts behind the first)
+    am = AssembledMap()
+    other = Submap(0.0, BIG)
+    other.setMapPointCloud(*raw_cloud(300, 5)[:2])
+    for voxel in (0.0, VOX):
+        am.build([a, other], voxel)
+    _insert(a, ps, corridor[3])
+    _insert(twin, ps, corridor[3])
+    assert a.insert_stats() == twin.insert_stats() == (stats[0] + 1, stats[1], stats[2])      # the next insert: merged
+    (pa, na), (pt, nt) = a.getMapPointCloud(), twin.getMapPointCloud()
+    assert same(pa, pt) and same(na, nt)
+
+
+def test_a_pending_insert_is_settled_and_included(corridor):
+    a, b = Submap(0.1, co.croppingVolumeFactory(*WIDE)), Submap(0.1, co.croppingVolumeFactory(*WIDE))
+    psa, psb = ProcessedScan(), ProcessedScan()
+    for k in range(3):
+        _insert(a, psa, corridor[k])
+        if k < 2:
+            len(a)
+        _insert(b, psb, corridor[k])
+        len(b)                                     # b: settled before anything else
+    lo, hi = a.size_bounds()
+    assert hi > lo, "the insert was not pending: the test did not test it"
+    am = AssembledMap()
+    am.build([a], 0.0)                             # a: straight after the insert, nothing in between
+    pb, nb = b.getMapPointCloud()
+    check_cloud(am.getPointCloud(), (pb, nb, None))
+    assert a.insert_stats() == b.insert_stats()
+
+
+# ---- 7. determinism and steady state --------------------------------------------------------------------------------------------
+
+def test_two_builds_give_the_same_bytes_and_the_second_allocates_nothing(five):
+    maps, _ = five
+    am = AssembledMap()
+    for voxel in (VOX, 0.0):
+        am.build(maps, voxel)
+        first, held = am.getPointCloud(), am.device_bytes()
+        assert held > 0
+        am.build(maps, voxel)
+        check_cloud(am.getPointCloud(), first)
+        assert am.device_bytes() == held
+
+
+# ---- 8. errors -------------------------------------------------------------------------------------------------------------------
+
+def test_bad_arguments_keep_the_previous_result(five):
+    maps, _ = five
+    am = AssembledMap()
+    am.build(maps, VOX)
+    kept = am.getPointCloud()
+    for bad in ([maps[1], maps[3], maps[1]], [maps[1], None, maps[3]]):          # a repeated submap; a NULL pointer
+        for voxel in (0.0, VOX):
+            with pytest.raises(ValueError):
+                am.build(bad, voxel)
+            assert len(am) == len(kept[0])
+            check_cloud(am.getPointCloud(), kept)
+    L = am._lib
+    assert L.o3s_assembled_map_build(None, 0, None, 0.0, 3, None) == _lib.ERR_BAD_ARGUMENT
+    assert L.o3s_assembled_map_build(am._h, 2, None, 0.0, 3, None) == _lib.ERR_BAD_ARGUMENT
+    with pytest.raises(ValueError):
+        am.build(maps, 1e-300)                     # a voxel index range that packs into nothing
+    check_cloud(am.getPointCloud(), kept)
+    # an attribute the result does not carry
+    am.build(maps, VOX, True, False)
+    n = len(am)
+    p, x = np.zeros((n, 3)), np.zeros((n, 3))
+    assert L.o3s_assembled_map_download(am._h, _d(p), _d(x), _d(x)) == _lib.ERR_BAD_SHAPE
+    assert L.o3s_assembled_map_download(am._h, _d(p), _d(x), None) == _lib.OK
+    am.build(maps, VOX, False, True)
+    assert L.o3s_assembled_map_download(am._h, _d(p), _d(x), None) == _lib.ERR_BAD_SHAPE
+
+
+# ---- 9. toSubmap -----------------------------------------------------------------------------------------------------------------
+
+def test_to_submap_keeps_the_bytes_and_the_colours(five):
+    maps, _ = five
+    am = AssembledMap()
+    dst = Submap(0.1, BIG)
+    dst.setMapPointCloud(*raw_cloud(50, 3)[:2])
+    dst.computeFeatures()
+    for voxel in (0.0, VOX):
+        am.build(maps, voxel)
+        got = am.getPointCloud()
+        am.toSubmap(dst)
+        assert len(dst) == len(am) and dst.hasColors() and dst.features_size() == -1
+        check_cloud(download(dst), got)
+    am.build(maps, VOX, True, False)
+    am.toSubmap(dst)
+    assert not dst.hasColors()
+    check_cloud(download(dst), am.getPointCloud())
+    am.build([], 0.0)
+    am.toSubmap(dst)
+    assert len(dst) == 0
+
+
+def test_the_assembled_map_as_an_icp_reference(corridor):
+    a, b = Submap(0.1, co.croppingVolumeFactory(*WIDE)), Submap(0.1, co.croppingVolumeFactory(*WIDE))
+    ps = ProcessedScan()
+    for k in range(6):
+        _insert(a if k < 3 else b, ps, corridor[k])
+    am = AssembledMap()
+    n = am.build([a, b], 0.1)
+    assert 1000 < n < len(a) + len(b)              # the two submaps overlap: shared voxels were folded
+    whole = Submap(0.1, co.croppingVolumeFactory(*WIDE))
+    am.toSubmap(whole)
+    sp, sn, T = corridor[3]
+    ps.preprocess(co.croppingVolumeFactory(*WIDE), 0.1, co.croppingVolumeFactory(*NARROW), sp, sn)
+    icp = ICP(IcpConfig())
+    assert whole.set_reference(co.croppingVolumeFactory(*NARROW), T, icp) > 1000
+    mp, mn = ps.match
+    prior = (T @ ref.exp6(np.array([0.0, 0.0, 0.01, 0.05, -0.04, 0.0]))).astype(np.float32)
+    out = icp.compute(mp.astype(np.float32), mn.astype(np.float32), prior)       # raises unless O3S_OK
+    assert np.isfinite(out).all() and icp.stats.iterations >= 1
+
+
+# ---- 10. after a loop-closure correction ---------------------------------------------------------------------------------------
+
+def test_assemble_after_a_correction():
+    col = SubmapCollection(1e9, 10 ** 9, 10 ** 9, 2, 0.0, ("MaxRadius", 1000.0))
+    col.create(np.zeros(3))
+    col.create(np.zeros(3))
+    assert col.parents == [0, 0, 1]
+    for k, m in enumerate(col.maps):
+        m.setMapPointCloud(*raw_cloud(900 + 211 * k, 60 + k)[:2])
+    before = [m.getMapPointCloud() for m in col.maps]
+    incs = [types.SimpleNamespace(dT=ref.exp6(np.array([0.02, -0.01, 0.3, 0.4, -0.2, 0.1])), submap_id=0),
+            types.SimpleNamespace(dT=ref.exp6(np.array([-0.01, 0.03, -0.2, -0.3, 0.5, 0.05])), submap_id=1)]
+    col.transform(incs)                            # submap 2 is not named: it takes its parent's increment
+    after = [m.getMapPointCloud() for m in col.maps]
+    assert all(not same(a[0], b[0]) for a, b in zip(after, before))
+    assert col.getTotalNumPoints() == sum(len(p) for p, _ in after)
+    P, N = cat(c[0] for c in after), cat(c[1] for c in after)
+    am = AssembledMap()
+    assert col.assembleMap(am) == len(P)
+    check_cloud(am.getPointCloud(), (P, N, None))
+    col.assembleMap(am, VOX)
+    check_cloud(am.getPointCloud(), oracle_voxelised(P, N, None)[:3])
+    mapper = Mapper(None, col, None, None, 0.1, 1.0, 0.0)
+    assert mapper.getAssembledMapPointCloud(am) == len(P)
+    check_cloud(am.getPointCloud(), (P, N, None))
