@@ -7,10 +7,12 @@
 // carries as its value; a lane finds the segment of an ordinal by binary search over the <= K + 1 starts, which a block keeps in LDS.
 //
 //   voxel_size <= 0   k_asm_concat                                                      1 launch
-//   voxel_size  > 0   k_asm_bounds -> k_asm_bounds_post (the one read-back before the   2 + 1 + sort + 1 + scan + 1 launches
-//                     keys: exact min / max bound, from which the host derives the
-//                     anchor AND the index extents) -> k_asm_keys -> sort_pairs
-//                     (stable) -> k_heads -> flag scan -> k_asm_reduce
+//   voxel_size  > 0   k_bounds<AsmPoints> -> k_bounds_post (cloud_bounds: the one         2 + 1 + sort + 1 + scan + 1 launches
+//                     read-back before the keys: exact min / max bound, from which the
+//                     host derives the anchor AND the index extents) ->
+//                     k_grid_keys<AsmPoints> -> sort_pairs (stable) -> k_heads ->
+//                     flag scan -> k_asm_reduce
+// The bound and key kernels are the flat clouds' own (cloud_bounds.h, normals_dev.h) over the segmented point source below.
 // The existing voxelisers (voxel_pipeline_dev, k_vox_reduce*) are untouched; k_asm_reduce restates their mode-1 arithmetic over
 // segments: sums in ascending ordinal = input order of the concatenation, mean = sum / count, normals not renormalised.
 #pragma once
@@ -47,6 +49,24 @@ __device__ __forceinline__ int asm_find(const int64_t* st, int K, int64_t g) {
   }
   return lo;
 }
+// The concatenation as a point source (cloud_bounds.h): point g of [0, total).  open() is asm_starts — the block-wide LDS prologue
+// that every thread reaches before any returns.
+struct AsmPoints {
+  AsmTable t;
+  struct Opened {
+    const int64_t* st;
+    const double* const* pts;
+    int K;
+    __device__ __forceinline__ const double* at(int64_t g) const {
+      const int s = asm_find(st, K, g);
+      return pts[s] + 3 * (g - st[s]);
+    }
+  };
+  __device__ __forceinline__ Opened open() const {
+    __shared__ int64_t sh[kAsmLds];
+    return {asm_starts(t, sh), t.pts, t.K};
+  }
+};
 
 // Mapper::getAssembledMapPointCloud (Mapper.cpp:524-535): one lane per DOUBLE of the output, so that a wave reads and writes 512
 // contiguous bytes wherever a segment does not end inside it.  out_n / out_c nullable.
@@ -61,76 +81,6 @@ __global__ void __launch_bounds__(kB) k_asm_concat(AsmTable t, int64_t total, do
   out_p[i] = t.pts[s][r];
   if (out_n) out_n[i] = t.nrm[s][r];
   if (out_c) out_c[i] = t.col[s][r];
-}
-
-__device__ __forceinline__ unsigned long long asm_ordered_bits(double v) {  // order-preserving map of a double to u64 (k_min_bound)
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-inline double asm_from_ordered_bits(unsigned long long u) {
-  u = (u & 0x8000000000000000ull) ? (u & 0x7fffffffffffffffull) : ~u;
-  double d;
-  std::memcpy(&d, &u, 8);
-  return d;
-}
-
-// min AND max bound over all segments in one pass: exact extrema are order-independent, so atomics may fold them.  The replicated
-// slots of k_min_bound: [kExtSlots][3] minima (initialised to ~0) and [kExtSlots][3] maxima (initialised to 0).
-__global__ void __launch_bounds__(kB) k_asm_bounds(AsmTable t, int64_t total, unsigned long long* __restrict__ mn_slots,
-                                                   unsigned long long* __restrict__ mx_slots) {
-  __shared__ int64_t sh[kAsmLds];
-  const int64_t* st = asm_starts(t, sh);
-  unsigned long long* mn = mn_slots + 3 * (blockIdx.x & (kExtSlots - 1));
-  unsigned long long* mx = mx_slots + 3 * (blockIdx.x & (kExtSlots - 1));
-  const int64_t g = (int64_t)blockIdx.x * kB + threadIdx.x;
-  const bool live = g < total;
-  const double* p = nullptr;
-  if (live) {
-    const int s = asm_find(st, t.K, g);
-    p = t.pts[s] + 3 * (g - st[s]);
-  }
-  for (int a = 0; a < 3; ++a) {  // all lanes take part in the wave reductions; dead lanes carry the neutral elements
-    const unsigned long long u = live ? asm_ordered_bits(p[a]) : 0ull;
-    const unsigned long long lo = wave_min_u64(live ? u : ~0ull), hi = wave_max_u64(u);
-    if ((threadIdx.x & 63) == 0) {  // a (possibly stale) look first: extrema are monotone, so skipping is safe
-      if (lo < __atomic_load_n(&mn[a], __ATOMIC_RELAXED)) atomicMin(&mn[a], lo);
-      if (hi > __atomic_load_n(&mx[a], __ATOMIC_RELAXED)) atomicMax(&mx[a], hi);
-    }
-  }
-}
-// folds the replicas into folded[0..2] = min, folded[3..5] = max (device memory, the copy a drained wait falls back to) and posts them
-__global__ void k_asm_bounds_post(const unsigned long long* __restrict__ mn_slots, const unsigned long long* __restrict__ mx_slots,
-                                  unsigned long long* __restrict__ folded, uint32_t* __restrict__ mailbox, uint32_t seq) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  unsigned long long v[6];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    v[a] = ~0ull;
-    v[3 + a] = 0ull;
-    for (int k = 0; k < kExtSlots; ++k) {
-      v[a] = mn_slots[k * 3 + a] < v[a] ? mn_slots[k * 3 + a] : v[a];
-      v[3 + a] = mx_slots[k * 3 + a] > v[3 + a] ? mx_slots[k * 3 + a] : v[3 + a];
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 6; ++a) folded[a] = v[a];
-  if (mailbox) post(mailbox, seq, kPostVals, v);
-}
-
-// Open3D's voxel index floor((p - anchor) / voxel) and the packed (z, y, x) key straight from the segments; the value is the global
-// ordinal.  The extents come from the exact bounds (floor((x - a) / v) is monotone in x), so every index is inside them.
-__global__ void __launch_bounds__(kB) k_asm_keys(AsmTable t, int64_t total, double ax, double ay, double az, double voxel, uint64_t ex, uint64_t ey,
-                                                 uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-  __shared__ int64_t sh[kAsmLds];
-  const int64_t* st = asm_starts(t, sh);
-  const int64_t g = (int64_t)blockIdx.x * kB + threadIdx.x;
-  if (g >= total) return;
-  const int s = asm_find(st, t.K, g);
-  const double* p = t.pts[s] + 3 * (g - st[s]);
-  const uint64_t x = (uint64_t)(int64_t)(int32_t)floor((p[0] - ax) / voxel), y = (uint64_t)(int64_t)(int32_t)floor((p[1] - ay) / voxel),
-                 z = (uint64_t)(int64_t)(int32_t)floor((p[2] - az) / voxel);
-  keys[g] = (z * ey + y) * ex + x;
-  vals[g] = (uint32_t)g;
 }
 
 // One lane per voxel, the run structure of k_vox_reduce: the voxel's members follow its head in ascending ordinal (stable sort), which
@@ -180,7 +130,7 @@ __global__ void __launch_bounds__(kB) k_asm_reduce(AsmTable t, const uint64_t* _
 
 inline size_t assemble_arena_bytes(int64_t N) {
   const size_t n = (size_t)N;
-  return 2 * Arena::pad(kExtSlots * 3 * 8) + Arena::pad(64)        // min / max replicas, folded bounds
+  return Arena::pad(kBoundsWords * 8)                              // bounds block
          + 2 * Arena::pad(n * 8) + 2 * Arena::pad(n * 4)           // keys x2, vals x2
          + Arena::pad(n * 4) + Arena::pad((n + 1) * 4)             // head, ord
          + Arena::pad(std::max(scan_temp_bytes(N), sort_temp_bytes(N))) + 4096;
@@ -317,9 +267,7 @@ int o3s_assembled_map_build(o3s_assembled_map* a, int32_t n, o3s_submap* const* 
   const int64_t N = total;
   CK(a->arena.reserve(assemble_arena_bytes(N)));
   Arena& ar = a->arena;
-  unsigned long long* d_mn = ar.take<unsigned long long>(kExtSlots * 3);
-  unsigned long long* d_mx = ar.take<unsigned long long>(kExtSlots * 3);
-  unsigned long long* d_fold = ar.take<unsigned long long>(8);
+  unsigned long long* d_bb = ar.take<unsigned long long>(kBoundsWords);
   uint64_t* keys = ar.take<uint64_t>((size_t)N);
   uint64_t* keys2 = ar.take<uint64_t>((size_t)N);
   uint32_t* vals = ar.take<uint32_t>((size_t)N);
@@ -331,31 +279,24 @@ int o3s_assembled_map_build(o3s_assembled_map* a, int32_t n, o3s_submap* const* 
   uint32_t* blk = reinterpret_cast<uint32_t*>(tmp);  // k_heads' per-block counts (room: scan_temp_bytes), consumed by the scan right behind
   const unsigned nb = nblk(N);
   // 1. exact min and max bound over all segments, read back once
-  CK(hipMemsetAsync(d_mn, 0xff, kExtSlots * 24, s));
-  CK(hipMemsetAsync(d_mx, 0x00, kExtSlots * 24, s));
-  hipLaunchKernelGGL(k_asm_bounds, dim3(nb), dim3(kB), 0, s, t, N, d_mn, d_mx);
+  const AsmPoints cloud{t};
   unsigned long long bnd[6];
-  {
-    PinnedArea& pa = pinned_area();
-    const uint32_t seq = mailbox_open(pa);
-    hipLaunchKernelGGL(k_asm_bounds_post, dim3(1), dim3(64), 0, s, d_mn, d_mx, d_fold, seq ? pa.mb.dev : (uint32_t*)nullptr, seq);
-    CK(hipGetLastError());
-    if (fetch_post(pa.mb, seq, s, reinterpret_cast<uint32_t*>(bnd), 12, kPostVals, d_fold, pa.p) == kPollError) return O3S_ERR_HIP;
-  }
+  if (const int rc = cloud_bounds(cloud, N, d_bb, s, bnd); rc != O3S_OK) return rc;
   // anchor = min_bound - voxel / 2; extents from the max bound with the kernel's own expression (IEEE fp64 on both sides)
   double anchor[3];
   uint64_t ext[3];
   for (int k = 0; k < 3; ++k) {
-    anchor[k] = asm_from_ordered_bits(bnd[k]) - voxel_size * 0.5;
-    const double top = std::floor((asm_from_ordered_bits(bnd[3 + k]) - anchor[k]) / voxel_size);
+    anchor[k] = from_ordered_bits(bnd[k]) - voxel_size * 0.5;
+    const double top = std::floor((from_ordered_bits(bnd[3 + k]) - anchor[k]) / voxel_size);
     if (!std::isfinite(top) || top < 0.0 || top > 2147483646.0) return O3S_ERR_BAD_ARGUMENT;  // (the previous result is untouched)
     ext[k] = (uint64_t)top + 1;
   }
   const long double prod = (long double)ext[0] * (long double)ext[1] * (long double)ext[2];
   if (prod >= 9.0e18L) return O3S_ERR_BAD_ARGUMENT;  // voxel index range does not pack into 63 bits
   const int bits = key_bits((uint64_t)prod);
-  // 2. - 4. keys from the segments, stable sort, heads, flag scan
-  hipLaunchKernelGGL(k_asm_keys, dim3(nb), dim3(kB), 0, s, t, N, anchor[0], anchor[1], anchor[2], voxel_size, ext[0], ext[1], keys, vals);
+  // 2. - 4. keys from the segments (Open3D's voxel index floor((p - anchor) / voxel), packed (z, y, x); the value is the global
+  // ordinal; floor((x - a) / v) is monotone in x, so every index is inside the extents), stable sort, heads, flag scan
+  hipLaunchKernelGGL(k_grid_keys<AsmPoints>, dim3(nb), dim3(kB), 0, s, cloud, N, voxel_size, anchor[0], anchor[1], anchor[2], ext[0], ext[1], keys, vals);
   size_t tb = tb_sort;
   CK(sort_pairs(tmp, tb, keys, keys2, vals, vals2, (size_t)N, bits, s));
   hipLaunchKernelGGL(k_heads, dim3(nb), dim3(kB), 0, s, keys2, N, ~0ull /*no key is excluded*/, head, 0, blk);

@@ -34,7 +34,7 @@ using namespace o3s::host_post;
 constexpr int kB = 256;
 inline unsigned nblk(int64_t n) { return (unsigned)((n + kB - 1) / kB); }
 
-// Global extrema live in kExtSlots replicas (block b uses replica b % kExtSlots) that the host folds after the read-back:
+// Global extrema live in kExtSlots replicas (block b uses replica b % kExtSlots) that are folded once behind the kernel:
 // together with the wave reduction and the look-before-atomic below this keeps same-address atomics off the critical path.
 constexpr int kExtSlots = 64;
 
@@ -99,6 +99,55 @@ int pick_device(int device) {
   if (hipSetDevice(device) != hipSuccess) return O3S_ERR_HIP;
   return O3S_OK;
 }
+
+// small pinned landing area for the counts the host reads back between kernels (one per host thread): a device-to-host
+// copy into pageable memory is staged and costs a full round trip of its own (~20 us in the per-scan loop's trace)
+struct PinnedArea {
+  uint32_t* p = nullptr;        // 4 KB landing area for small device-to-host copies
+  PostBlock<> mb;               // mailbox a kernel writes directly (host_post.h): 32 words, the last 8 the lazy slot (kLazySlot)
+  PinnedArea() {
+    if (hipHostMalloc(reinterpret_cast<void**>(&p), 4096, hipHostMallocPortable) != hipSuccess) p = nullptr;
+    (void)mb.alloc(128);
+  }
+  // no destructor on purpose: areas live in a process-wide pool that is never torn down.  A hipHostFree from a
+  // thread_local / static destructor can run after the HIP runtime has been unloaded (exit-time crashes), and the worker
+  // threads of o3s_o3d_registration_icp_batch would otherwise allocate and free two pinned buffers per call.
+};
+struct PinnedPool {
+  std::mutex mu;
+  std::vector<PinnedArea*> idle;
+};
+inline PinnedPool& pinned_pool() {
+  static PinnedPool* pool = new PinnedPool();  // leaked deliberately (see PinnedArea)
+  return *pool;
+}
+struct PinnedLease {  // one per host thread; hands the area back to the pool when the thread ends
+  PinnedArea* a = nullptr;
+  PinnedLease() {
+    PinnedPool& pool = pinned_pool();
+    {
+      std::lock_guard<std::mutex> lk(pool.mu);
+      if (!pool.idle.empty()) {
+        a = pool.idle.back();
+        pool.idle.pop_back();
+      }
+    }
+    if (!a) a = new PinnedArea();
+  }
+  ~PinnedLease() {
+    PinnedPool& pool = pinned_pool();
+    std::lock_guard<std::mutex> lk(pool.mu);
+    pool.idle.push_back(a);
+  }
+};
+inline PinnedArea& pinned_area() {
+  static thread_local PinnedLease lease;
+  return *lease.a;
+}
+inline uint32_t* pinned_words() { return pinned_area().p; }
+inline bool mailbox_enabled(const PinnedArea& pa) { return posts_enabled() && pa.mb; }
+// the sequence number of the post a call is about to issue; 0 (no post: fetch_post copies) with the mailbox off
+inline uint32_t mailbox_open(PinnedArea& pa) { return mailbox_enabled(pa) ? pa.mb.next() : 0u; }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------
 // getVoxelIdx(p, InverseVoxelSize): int(std::floor(p * inv))  (VoxelHashMap.hpp:48-51)
@@ -395,20 +444,7 @@ __global__ void __launch_bounds__(kB) k_vox_reduce_attr(const uint64_t* __restri
     for (int a = 0; a < 9; ++a) out_cov[9 * o + a] = sv[a] / dn;
 }
 
-__global__ void __launch_bounds__(kB) k_min_bound(const double* __restrict__ pts, int64_t N, unsigned long long* __restrict__ mn_slots /*[kExtSlots][3], ordered bits*/) {
-  unsigned long long* mn = mn_slots + 3 * (blockIdx.x & (kExtSlots - 1));
-  const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
-  for (int a = 0; a < 3; ++a) {
-    // order-preserving map of a double to u64 so that atomicMin works on negatives too
-    unsigned long long u = ~0ull;
-    if (i < N) {
-      u = (unsigned long long)__double_as_longlong(pts[3 * i + a]);
-      u = (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-    }
-    u = wave_min_u64(u);
-    if ((threadIdx.x & 63) == 0 && u < __atomic_load_n(&mn[a], __ATOMIC_RELAXED)) atomicMin(&mn[a], u);
-  }
-}
+#include "cloud_bounds.h"
 
 // ---- the same pipelines without host round trips in the middle ("hinted"): when the cropping volume bounds the voxel
 // index range, keys are packed against that range straight away (no extrema, no read-back of them), every count stays on
@@ -435,12 +471,7 @@ __global__ void __launch_bounds__(kB) k_min_part(o3s_cropper c, int use_crop, co
   }
   const double v[3] = {x, y, z};
   for (int a = 0; a < 3; ++a) {
-    unsigned long long u = ~0ull;
-    if (live) {
-      u = (unsigned long long)__double_as_longlong(v[a]);
-      u = (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-    }
-    u = wave_min_u64(u);
+    const unsigned long long u = wave_min_u64(live ? ordered_bits(v[a]) : ~0ull);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][a] = u;
   }
   __syncthreads();
@@ -476,8 +507,7 @@ __global__ void __launch_bounds__(kB) k_vox_key_direct(const double* __restrict_
     if (threadIdx.x < 3) {
       unsigned long long u = sh[0][threadIdx.x];
       for (int w = 1; w < kB / 64; ++w) u = sh[w][threadIdx.x] < u ? sh[w][threadIdx.x] : u;
-      u = (u & 0x8000000000000000ull) ? (u & 0x7fffffffffffffffull) : ~u;
-      s_anchor[threadIdx.x] = __longlong_as_double((long long)u) - voxel * 0.5;
+      s_anchor[threadIdx.x] = from_ordered_bits(u) - voxel * 0.5;
     }
     __syncthreads();
   }
@@ -541,54 +571,6 @@ __global__ void k_post_counts(const uint32_t* __restrict__ status, const uint32_
   if (mailbox) post<kGuarded>(mailbox, seq, kPostVals, w);
 }
 
-// small pinned landing area for the counts the host reads back between kernels (one per host thread): a device-to-host
-// copy into pageable memory is staged and costs a full round trip of its own (~20 us in the per-scan loop's trace)
-struct PinnedArea {
-  uint32_t* p = nullptr;        // 4 KB landing area for small device-to-host copies
-  PostBlock<> mb;               // mailbox a kernel writes directly (host_post.h): 32 words, the last 8 the lazy slot (kLazySlot)
-  PinnedArea() {
-    if (hipHostMalloc(reinterpret_cast<void**>(&p), 4096, hipHostMallocPortable) != hipSuccess) p = nullptr;
-    (void)mb.alloc(128);
-  }
-  // no destructor on purpose: areas live in a process-wide pool that is never torn down.  A hipHostFree from a
-  // thread_local / static destructor can run after the HIP runtime has been unloaded (exit-time crashes), and the worker
-  // threads of o3s_o3d_registration_icp_batch would otherwise allocate and free two pinned buffers per call.
-};
-struct PinnedPool {
-  std::mutex mu;
-  std::vector<PinnedArea*> idle;
-};
-inline PinnedPool& pinned_pool() {
-  static PinnedPool* pool = new PinnedPool();  // leaked deliberately (see PinnedArea)
-  return *pool;
-}
-struct PinnedLease {  // one per host thread; hands the area back to the pool when the thread ends
-  PinnedArea* a = nullptr;
-  PinnedLease() {
-    PinnedPool& pool = pinned_pool();
-    {
-      std::lock_guard<std::mutex> lk(pool.mu);
-      if (!pool.idle.empty()) {
-        a = pool.idle.back();
-        pool.idle.pop_back();
-      }
-    }
-    if (!a) a = new PinnedArea();
-  }
-  ~PinnedLease() {
-    PinnedPool& pool = pinned_pool();
-    std::lock_guard<std::mutex> lk(pool.mu);
-    pool.idle.push_back(a);
-  }
-};
-inline PinnedArea& pinned_area() {
-  static thread_local PinnedLease lease;
-  return *lease.a;
-}
-inline uint32_t* pinned_words() { return pinned_area().p; }
-inline bool mailbox_enabled(const PinnedArea& pa) { return posts_enabled() && pa.mb; }
-// the sequence number of the post a call is about to issue; 0 (no post: fetch_post copies) with the mailbox off
-inline uint32_t mailbox_open(PinnedArea& pa) { return mailbox_enabled(pa) ? pa.mb.next() : 0u; }
 // A post that is looked at LATER (o3s_submap_insert_processed: the counts of a merge insert, fetched by the next call that needs the
 // map).  It lands in the last quarter of the issuing thread's mailbox (kLazySlot: a slot of the common layout, written guarded), which
 // no other hand-over uses, and in `dev_out` (device memory the owner keeps) for a reader that finds the slot taken by a later post.
@@ -654,17 +636,6 @@ inline int ext_i32_init(int32_t* d, hipStream_t s) {
     for (int a = 0; a < 6; ++a) init[k * 6 + a] = a < 3 ? INT32_MAX : INT32_MIN;
   CK(hipMemcpyAsync(d, init, sizeof(init), hipMemcpyHostToDevice, s));
   return O3S_OK;
-}
-// the same for the three u64 (order-preserving double bits) minima of k_min_bound: three 8-byte values from kPostVals
-__global__ void k_mn_post(const unsigned long long* __restrict__ slots, uint32_t* __restrict__ mailbox, uint32_t seq) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  unsigned long long v[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    v[a] = ~0ull;
-    for (int k = 0; k < kExtSlots; ++k) v[a] = slots[k * 3 + a] < v[a] ? slots[k * 3 + a] : v[a];
-  }
-  post(mailbox, seq, kPostVals, v);
 }
 inline int ext_i32_fetch(const int32_t* d, int32_t out[6], hipStream_t s) {
   PinnedArea& pa = pinned_area();
@@ -819,7 +790,7 @@ inline int crop_dev(Arena& ar, const o3s_cropper& c, const double* d_pts, const 
 inline size_t voxel_arena_bytes(int64_t N) {
   const size_t n = (size_t)N;
   return Arena::pad(n * 4) + Arena::pad((n + 1) * 4)                 // flag, off
-         + Arena::pad(n * 12) + Arena::pad(kExtSlots * 6 * 4) + Arena::pad(kExtSlots * 3 * 8)  // vidx, mm, mn
+         + Arena::pad(n * 12) + Arena::pad(kExtSlots * 6 * 4) + Arena::pad(kBoundsWords * 8)  // vidx, mm, bounds block
          + 2 * Arena::pad(n * 8) + 2 * Arena::pad(n * 4)             // keys x2, vals x2
          + Arena::pad(n * 4) + Arena::pad((n + 1) * 4)               // head, ord
          + Arena::pad(std::max(scan_temp_bytes(N), sort_temp_bytes(N))) + 4096;
@@ -837,7 +808,7 @@ inline int voxel_pipeline_dev(Arena& ar, int mode, const o3s_cropper* crop, doub
   uint32_t* off = ar.take<uint32_t>((size_t)N + 1);
   int32_t* vidx = ar.take<int32_t>((size_t)N * 3);
   int32_t* d_mm = ar.take<int32_t>(kExtSlots * 6);
-  unsigned long long* d_mn = ar.take<unsigned long long>(kExtSlots * 3);
+  unsigned long long* d_bb = ar.take<unsigned long long>(kBoundsWords);
   uint64_t* keys = ar.take<uint64_t>((size_t)N);
   uint64_t* keys2 = ar.take<uint64_t>((size_t)N);
   uint32_t* vals = ar.take<uint32_t>((size_t)N);
@@ -858,31 +829,10 @@ inline int voxel_pipeline_dev(Arena& ar, int mode, const o3s_cropper* crop, doub
   }
   double ax = 0, ay = 0, az = 0;
   if (mode == 1) {  // Open3D: anchor = min_bound - voxel/2
-    CK(hipMemsetAsync(d_mn, 0xff, kExtSlots * 24, s));
-    hipLaunchKernelGGL(k_min_bound, dim3(nblk(N)), dim3(kB), 0, s, d_pts, N, d_mn);
-    unsigned long long mn[3] = {~0ull, ~0ull, ~0ull};
-    PinnedArea& pa = pinned_area();
-    const uint32_t seq = mailbox_open(pa);
-    if (seq) {
-      hipLaunchKernelGGL(k_mn_post, dim3(1), dim3(64), 0, s, d_mn, pa.mb.dev, seq);
-      CK(hipGetLastError());
-    }
-    const int posted = fetch_post(pa.mb, seq, s, reinterpret_cast<uint32_t*>(mn), 6, kPostVals, nullptr);
-    if (posted == kPollError) return O3S_ERR_HIP;
-    if (posted != kPollPosted) {
-      unsigned long long mn_local[kExtSlots * 3];
-      unsigned long long* mn_all = pa.p ? reinterpret_cast<unsigned long long*>(pa.p) : mn_local;
-      CK(hipMemcpyAsync(mn_all, d_mn, sizeof(mn_local), hipMemcpyDeviceToHost, s));
-      CK(hipStreamSynchronize(s));
-      for (int k = 0; k < kExtSlots; ++k)
-        for (int a = 0; a < 3; ++a) mn[a] = std::min(mn[a], mn_all[k * 3 + a]);
-    }
-    double m[3];
-    for (int a = 0; a < 3; ++a) {
-      unsigned long long u = mn[a];
-      u = (u & 0x8000000000000000ull) ? (u & 0x7fffffffffffffffull) : ~u;
-      std::memcpy(&m[a], &u, 8);
-    }
+    unsigned long long bb[6];
+    const int rc = cloud_bounds<false>(FlatPoints{d_pts}, N, d_bb, s, bb);  // the minima only: the anchor
+    if (rc != O3S_OK) return rc;
+    const double m[3] = {from_ordered_bits(bb[0]), from_ordered_bits(bb[1]), from_ordered_bits(bb[2])};
     ax = m[0] - voxel * 0.5;
     ay = m[1] - voxel * 0.5;
     az = m[2] - voxel * 0.5;

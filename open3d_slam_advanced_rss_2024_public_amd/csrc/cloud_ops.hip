@@ -265,4 +265,21 @@ extern "C" int o3s_test_sort_pairs(int device, const uint64_t* keys, const uint3
   CK(hipMemcpy(vals_out, v2.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   return O3S_OK;
 }
+// hooks build only (tests/test_gpu_cloud_ops.py): the bounds of a host cloud through the shared reduction (cloud_bounds.h) — fill,
+// k_bounds over the flat source on the production grid, fold and fetch; out6 = min x, y, z, max x, y, z
+extern "C" int o3s_test_cloud_bounds(int device, const double* pts, int64_t n, double* out6) {
+  using namespace o3s_cloud;
+  if (n <= 0 || !pts || !out6) return O3S_ERR_BAD_ARGUMENT;
+  const int rc = pick_device(device);
+  if (rc != O3S_OK) return rc;
+  Buf d_pts, d_bb;
+  CK(d_pts.alloc((size_t)n * 24));
+  CK(d_bb.alloc((size_t)kBoundsWords * 8));
+  CK(hipMemcpy(d_pts.p, pts, (size_t)n * 24, hipMemcpyHostToDevice));
+  unsigned long long bb[6];
+  const int rb = cloud_bounds(FlatPoints{d_pts.as<double>()}, n, d_bb.as<unsigned long long>(), nullptr, bb);
+  if (rb != O3S_OK) return rb;
+  for (int a = 0; a < 6; ++a) out6[a] = from_ordered_bits(bb[a]);
+  return O3S_OK;
+}
 #endif

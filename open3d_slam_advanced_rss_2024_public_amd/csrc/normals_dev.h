@@ -20,54 +20,6 @@ namespace o3s_cloud {
 
 constexpr int kNnMax = 32;  // largest max_nn served (the reference's parameter files use 5 .. 20)
 
-// Bounds of a cloud as order-preserving u64 bit patterns.  Every slot is a MINIMUM — the maxima are kept as the minimum of the
-// complemented pattern — so that one byte fill (0xFF) initialises all replicas.
-__global__ void __launch_bounds__(kB) k_bounds(const double* __restrict__ pts, int64_t N, unsigned long long* __restrict__ slots /*[kExtSlots][min[3], ~max[3]], ordered bits*/) {
-  unsigned long long* mnmx = slots + 6 * (blockIdx.x & (kExtSlots - 1));
-  // a thread folds its points first (blocks stride over the cloud): one wave reduction per 8+ points instead of one per point — the
-  // reduction's 72 lane permutes were the kernel (35 us at 0.76 M points)
-  unsigned long long lo[3] = {~0ull, ~0ull, ~0ull}, hi[3] = {0ull, 0ull, 0ull};
-  for (int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x; i < N; i += (int64_t)gridDim.x * kB)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      unsigned long long u = (unsigned long long)__double_as_longlong(pts[3 * i + a]);
-      u = (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-      lo[a] = u < lo[a] ? u : lo[a];
-      hi[a] = u > hi[a] ? u : hi[a];
-    }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const unsigned long long l = wave_min_u64(lo[a]), h = wave_max_u64(hi[a]);
-    if ((threadIdx.x & 63) == 0 && l <= h) {
-      if (l < __atomic_load_n(&mnmx[a], __ATOMIC_RELAXED)) atomicMin(&mnmx[a], l);
-      if (~h < __atomic_load_n(&mnmx[3 + a], __ATOMIC_RELAXED)) atomicMin(&mnmx[3 + a], ~h);
-    }
-  }
-}
-// the six bounds of the kExtSlots replicas (one per lane; the maxima un-complemented), as lane 0 holds them
-__device__ __forceinline__ void fold_bounds(const unsigned long long* __restrict__ slots, unsigned long long (&v)[6]) {
-#pragma unroll
-  for (int a = 0; a < 6; ++a) {
-    v[a] = wave_min_u64(slots[threadIdx.x * 6 + a]);
-    if (a >= 3) v[a] = ~v[a];
-  }
-}
-// folds the replicas (one per lane) and posts the six bounds (8-byte values from kPostVals; the maxima un-complemented), then the
-// sequence number
-__global__ void __launch_bounds__(64) k_bounds_post(const unsigned long long* __restrict__ slots, uint32_t* __restrict__ mailbox, uint32_t seq) {
-  static_assert(kExtSlots == 64, "one replica per lane");
-  if (blockIdx.x != 0) return;
-  unsigned long long v[6];
-  fold_bounds(slots, v);
-  if (threadIdx.x == 0) post(mailbox, seq, kPostVals, v);
-}
-inline double ordered_to_double(unsigned long long u) {
-  u = (u & 0x8000000000000000ull) ? (u & 0x7fffffffffffffffull) : ~u;
-  double d;
-  std::memcpy(&d, &u, 8);
-  return d;
-}
-
 // begin / end of every occupied cell in the key-sorted order (empty cells keep begin = end = 0)
 __global__ void __launch_bounds__(kB) k_cell_ranges(const uint64_t* __restrict__ keys, int64_t N, uint32_t* __restrict__ cbeg, uint32_t* __restrict__ cend) {
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
@@ -482,12 +434,16 @@ struct GridIndex {  // uniform grid over a cloud: cell-sorted copy + dense per-c
 };
 
 // cell keys of the grid index in one pass: what k_vox_keys_idx (mode 1) + k_vox_pack make of a point — floor((p - a) / cell) per
-// axis, (z ey + y) ex + x — without the index array in between and without the extrema nobody reads here (27 us -> 7 at 0.5 M points)
-__global__ void __launch_bounds__(kB) k_grid_keys(const double* __restrict__ pts, int64_t N, double cell, double ax, double ay, double az, uint64_t ex,
-                                                  uint64_t ey, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+// axis, (z ey + y) ex + x — without the index array in between and without the extrema nobody reads here (27 us -> 7 at 0.5 M points).
+// Src: a point source (cloud_bounds.h); the value is the point's ordinal in it.
+template <class Src>
+__global__ void __launch_bounds__(kB) k_grid_keys(Src src, int64_t N, double cell, double ax, double ay, double az, uint64_t ex, uint64_t ey,
+                                                  uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const auto cloud = src.open();  // every thread, before any returns
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
   if (i >= N) return;
-  const int32_t vx = (int32_t)floor((pts[3 * i] - ax) / cell), vy = (int32_t)floor((pts[3 * i + 1] - ay) / cell), vz = (int32_t)floor((pts[3 * i + 2] - az) / cell);
+  const double* p = cloud.at(i);
+  const int32_t vx = (int32_t)floor((p[0] - ax) / cell), vy = (int32_t)floor((p[1] - ay) / cell), vz = (int32_t)floor((p[2] - az) / cell);
   const uint64_t x = (uint64_t)(int64_t)vx, y = (uint64_t)(int64_t)vy, z = (uint64_t)(int64_t)vz;
   keys[i] = (z * ey + y) * ex + x;
   vals[i] = (uint32_t)i;
@@ -495,7 +451,7 @@ __global__ void __launch_bounds__(kB) k_grid_keys(const double* __restrict__ pts
 
 inline size_t grid_index_arena_bytes(int64_t N) {
   const size_t n = (size_t)N;
-  return Arena::pad(kExtSlots * 6 * 8) + 2 * Arena::pad(n * 8) + 2 * Arena::pad(n * 4) + Arena::pad(n * 4) + Arena::pad((n + 1) * 4) +
+  return Arena::pad(kBoundsWords * 8) + 2 * Arena::pad(n * 8) + 2 * Arena::pad(n * 4) + Arena::pad(n * 4) + Arena::pad((n + 1) * 4) +
          Arena::pad(n * 24) + Arena::pad(std::max(scan_temp_bytes(N), sort_temp_bytes(N))) + 8192;
 }
 constexpr size_t kGridMaxCells = (size_t)1 << 24;
@@ -509,7 +465,7 @@ constexpr size_t kGridMaxCells = (size_t)1 << 24;
 
 // cell0: first guess of the cell edge; the cell is then re-sized once so that an occupied cell holds ~target_rho points
 // (surface-like data: density ~ cell^2), never above cell_max.  Any cell size keeps the searches exact.
-// known_bb (nullable): the cloud's bounds as the six order-preserving bit patterns k_bounds_post makes (minima, maxima) — a caller that has
+// known_bb (nullable): the cloud's bounds as the six order-preserving bit patterns bounds_fetch gives (minima, maxima) — a caller that has
 // just written the cloud has them for free, and the build then starts without its first pass over the cloud and its first wait
 inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, double cell0, double target_rho, double cell_max, GridIndex* out,
                             hipStream_t s, const unsigned long long* known_bb = nullptr) {
@@ -517,7 +473,7 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
   const size_t n = (size_t)N;
   CK(w.arena.reserve(grid_index_arena_bytes(N)));
   Arena& ar = w.arena;
-  unsigned long long* d_bb = ar.take<unsigned long long>(kExtSlots * 6);
+  unsigned long long* d_bb = ar.take<unsigned long long>(kBoundsWords);
   uint64_t* keys = ar.take<uint64_t>(n);
   uint64_t* keys2 = ar.take<uint64_t>(n);
   uint32_t* vals = ar.take<uint32_t>(n);
@@ -527,36 +483,19 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
   double* sp = ar.take<double>(n * 3);
   const size_t tb_scan = scan_temp_bytes(N), tb_sort = sort_temp_bytes(N);
   void* tmp = ar.take<char>(std::max(tb_scan, tb_sort));
-  // bounds: replicas initialised by one byte fill, folded on the device and posted into the mailbox the host polls (the copy of
-  // the replicas into pageable memory plus a stream synchronisation was 25-40 us of every build)
-  if (!known_bb) {
-  CK(hipMemsetAsync(d_bb, 0xFF, (size_t)kExtSlots * 6 * 8, s));
-  hipLaunchKernelGGL(k_bounds, dim3(std::min(nblk(N), 1024u)), dim3(kB), 0, s, d_pts, N, d_bb);
-  }
-  unsigned long long bb[6] = {~0ull, ~0ull, ~0ull, 0ull, 0ull, 0ull};
+  // bounds: folded on the device and posted into the mailbox the host polls (the copy of the replicas into pageable memory plus a
+  // stream synchronisation was 25-40 us of every build)
+  unsigned long long bb[6];
   if (known_bb) {
     for (int a = 0; a < 6; ++a) bb[a] = known_bb[a];
   } else {
-    PinnedArea& pa = pinned_area();
-    const uint32_t seq = mailbox_open(pa);
-    if (seq) {
-      hipLaunchKernelGGL(k_bounds_post, dim3(1), dim3(64), 0, s, (const unsigned long long*)d_bb, pa.mb.dev, seq);
-      CK(hipGetLastError());
-    }
-    const int posted = fetch_post(pa.mb, seq, s, reinterpret_cast<uint32_t*>(bb), 12, kPostVals, nullptr);
-    if (posted == kPollError) return O3S_ERR_HIP;
-    if (posted != kPollPosted) {
-      unsigned long long bb_all[kExtSlots * 6];
-      CK(hipMemcpyAsync(bb_all, d_bb, sizeof(bb_all), hipMemcpyDeviceToHost, s));
-      CK(hipStreamSynchronize(s));
-      for (int k = 0; k < kExtSlots; ++k)
-        for (int a = 0; a < 6; ++a) bb[a] = a < 3 ? std::min(bb[a], bb_all[k * 6 + a]) : std::max(bb[a], ~bb_all[k * 6 + a]);
-    }
+    const int rc = cloud_bounds(FlatPoints{d_pts}, N, d_bb, s, bb);
+    if (rc != O3S_OK) return rc;
   }
   double lo[3], hi[3];
   for (int a = 0; a < 3; ++a) {
-    lo[a] = ordered_to_double(bb[a]);
-    hi[a] = ordered_to_double(bb[3 + a]);
+    lo[a] = from_ordered_bits(bb[a]);
+    hi[a] = from_ordered_bits(bb[3 + a]);
     if (!(std::isfinite(lo[a]) && std::isfinite(hi[a]))) return O3S_ERR_BAD_ARGUMENT;
   }
   const double ext = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
@@ -593,7 +532,7 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
   // ~130 us of the key + sort + count pass it replaces — bits of one word set from eight L2s.)
   for (int attempt = 0; attempt < 2; ++attempt) {
     size_grid();
-    hipLaunchKernelGGL(k_grid_keys, dim3(nblk(N)), dim3(kB), 0, s, d_pts, N, cell, lo[0], lo[1], lo[2], (uint64_t)dims[0], (uint64_t)dims[1], keys, vals);
+    hipLaunchKernelGGL(k_grid_keys<FlatPoints>, dim3(nblk(N)), dim3(kB), 0, s, FlatPoints{d_pts}, N, cell, lo[0], lo[1], lo[2], (uint64_t)dims[0], (uint64_t)dims[1], keys, vals);
     size_t tb = tb_sort;
     CK(sort_pairs(tmp, tb, keys, keys2, vals, vals2, n, key_bits((uint64_t)dims[0] * (uint64_t)dims[1] * (uint64_t)dims[2]), s));  // keys are cell indices of the grid just sized
     if (attempt == 0) {

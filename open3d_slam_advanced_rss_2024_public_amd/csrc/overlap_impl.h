@@ -118,36 +118,26 @@ __global__ void __launch_bounds__(kB) k_ov_flag(const uint32_t* __restrict__ slo
   flag[i] = in ? 1u : 0u;
 }
 
-// SelectByIndex of the target with its normals (k_compact) that also keeps the bounds of what it writes, in the replicas k_bounds
-// uses (every slot a minimum, the maxima complemented; filled with 0xFF before): the index over the selection is built next, and
-// the pass over it that would find its bounds again, with a wait of its own, is saved.  A thread folds its points first.
+// SelectByIndex of the target with its normals (k_compact) that also keeps the bounds of what it writes, in the replicas of a bounds
+// block (cloud_bounds.h; bounds_begin before): the index over the selection is built next, and the pass over it that would find its
+// bounds again, with a wait of its own, is saved.
 __global__ void __launch_bounds__(kB) k_compact_bounds(const double* __restrict__ pts, const double* __restrict__ nrm, int64_t N,
                                                        const uint32_t* __restrict__ flag, const uint32_t* __restrict__ off, double* __restrict__ out_pts,
                                                        double* __restrict__ out_n, unsigned long long* __restrict__ slots) {
-  unsigned long long* mnmx = slots + 6 * (blockIdx.x & (kExtSlots - 1));
-  unsigned long long lo[3] = {~0ull, ~0ull, ~0ull}, hi[3] = {0ull, 0ull, 0ull};
+  BoundsAcc<> acc;
   for (int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x; i < N; i += (int64_t)gridDim.x * kB) {
     if (!flag[i]) continue;
     const int64_t o = (int64_t)off[i];
+    double v[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      const double v = pts[3 * i + a];
-      out_pts[3 * o + a] = v;
+      v[a] = pts[3 * i + a];
+      out_pts[3 * o + a] = v[a];
       out_n[3 * o + a] = nrm[3 * i + a];
-      unsigned long long u = (unsigned long long)__double_as_longlong(v);
-      u = (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-      lo[a] = u < lo[a] ? u : lo[a];
-      hi[a] = u > hi[a] ? u : hi[a];
     }
+    acc.add(v[0], v[1], v[2]);
   }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const unsigned long long l = wave_min_u64(lo[a]), h = wave_max_u64(hi[a]);
-    if ((threadIdx.x & 63) == 0 && l <= h) {
-      if (l < __atomic_load_n(&mnmx[a], __ATOMIC_RELAXED)) atomicMin(&mnmx[a], l);
-      if (~h < __atomic_load_n(&mnmx[3 + a], __ATOMIC_RELAXED)) atomicMin(&mnmx[3 + a], ~h);
-    }
-  }
+  bounds_flush(acc, slots);
 }
 
 // the selection's one hand-over to the host: both counts (off[n] = the number of set flags) and the two error words (kOvCounts),
@@ -158,7 +148,6 @@ static_assert(kOvBounds + 12 <= kLazySlot, "the eager posts stay clear of the sl
 __global__ void __launch_bounds__(64) k_ov_post(const uint32_t* __restrict__ fs, uint32_t* __restrict__ os, int64_t Ns, const uint32_t* __restrict__ ft,
                                                 uint32_t* __restrict__ ot, int64_t Nt, const uint32_t* __restrict__ err,
                                                 const unsigned long long* __restrict__ slots /*nullable*/, uint32_t* __restrict__ mailbox, uint32_t seq) {
-  static_assert(kExtSlots == 64, "one replica per lane");
   if (blockIdx.x != 0) return;
   if (slots && mailbox) {
     unsigned long long v[6];
@@ -202,7 +191,7 @@ inline size_t overlap_arena_bytes(int64_t Ns, int64_t Nt, uint32_t slots) {
   const size_t ns = (size_t)Ns, nt = (size_t)Nt, nmax = std::max(ns, nt);
   return Arena::pad(ns * 8) + Arena::pad(nt * 8) + Arena::pad(ns * 4) + Arena::pad(nt * 4) + Arena::pad((ns + 1) * 4) + Arena::pad((nt + 1) * 4) +
          Arena::pad(scan_temp_bytes((int64_t)nmax)) + Arena::pad((size_t)slots * sizeof(OvSlot)) + Arena::pad(64) + Arena::pad(128) +
-         Arena::pad(kExtSlots * 6 * 8) + 4096;
+         Arena::pad(kBoundsReplicaWords * 8) + 4096;
 }
 
 size_t reg_overlap_arena_bytes(int64_t Ns, int64_t Nt) { return overlap_arena_bytes(Ns, Nt, ov_slots_for(Ns + Nt)); }
@@ -232,7 +221,7 @@ inline int overlap_dev(OverlapWork& w, const double* d_src, int64_t Ns, const do
     OvSlot* tab = ar.take<OvSlot>((size_t)slots);
     err = ar.take<uint32_t>(16);
     double* d_T = ar.take<double>(16);
-    unsigned long long* bb = ar.take<unsigned long long>(kExtSlots * 6);
+    unsigned long long* bb = ar.take<unsigned long long>(kBoundsReplicaWords);  // folded by k_ov_post, with the counts
     CK(hipMemsetAsync(err, 0, 8, s));
     CK(hipMemsetAsync(tab, 0, (size_t)slots * sizeof(OvSlot), s));
     CK(hipMemcpyAsync(d_T, T, 16 * sizeof(double), hipMemcpyHostToDevice, s));  // pageable source: staged before the call returns
@@ -257,7 +246,7 @@ inline int overlap_dev(OverlapWork& w, const double* d_src, int64_t Ns, const do
       const uint32_t seq = mailbox_open(pa);
       const bool with_sel = sel && seq;
       if (with_sel) {  // the two selections, enqueued before their sizes are known (the buffers hold either cloud whole)
-        CK(hipMemsetAsync(bb, 0xFF, (size_t)kExtSlots * 6 * 8, s));
+        if (const int rb = bounds_begin(bb, s); rb != O3S_OK) return rb;
         hipLaunchKernelGGL(k_compact, dim3(nblk(Ns)), dim3(kB), 0, s, d_src, sel->src_normals, Ns, (const uint32_t*)fs, (const uint32_t*)os, sel->out_src,
                            sel->out_src_n, (int32_t*)nullptr);
         hipLaunchKernelGGL(k_compact_bounds, dim3(std::min(nblk(Nt), 1024u)), dim3(kB), 0, s, d_tgt, sel->tgt_normals, Nt, (const uint32_t*)ft,

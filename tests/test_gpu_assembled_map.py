@@ -120,6 +120,40 @@ def test_voxelised_equals_the_oracle_on_the_concatenation(five):
     check_cloud(am.getPointCloud(), (op, on, ocol))
 
 
+def test_bounds_planted_at_segment_boundaries_equal_the_oracle():
+    """The segmented point source under k_bounds and k_grid_keys: submaps of 1, 63, 65, 257 and 300 points, so that segment boundaries
+    fall inside waves and inside a block.  Every axis's minimum and maximum is an isolated point of its own: the very first and the very
+    last point of the concatenation, the two points on either side of a segment boundary, and two inside segments.  A bound that is
+    missed moves the anchor or the extents, and with them the voxels."""
+    sizes = (1, 63, 65, 257, 300)
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    planted = {0: (0, -6.1), starts[5] - 1: (0, 6.3), starts[2] - 1: (1, -6.6), starts[2]: (1, 7.2), starts[3] + 100: (2, -7.7),
+               starts[4] + 150: (2, 6.9)}                                   # ordinal in the concatenation -> (axis, value)
+    maps = []
+    for k, n in enumerate(sizes):
+        pts, nr, col = raw_cloud(n, 90 + k)
+        for g, (axis, value) in planted.items():
+            if starts[k] <= g < starts[k + 1]:
+                pts[g - starts[k], axis] = value
+        m = Submap(0.0, BIG)
+        m.insertScanColored(pts, nr, col, SHIFT)
+        maps.append(m)
+    clouds = [download(m) for m in maps]
+    P, N, Cc = (cat(c[k] for c in clouds) for k in range(3))
+    assert len(P) == starts[5]
+    # on the CPU, with the oracle alone: each planted point is the extreme of its axis, at least three voxels outside the bulk, and alone in its voxel
+    idx = orc.voxel_idx_div(P, VOX, P.min(axis=0) - VOX * 0.5)
+    for g, (axis, value) in planted.items():
+        others = np.delete(P[:, axis], g)
+        assert (P[g, axis] < others.min() - 3 * VOX) if value < 0 else (P[g, axis] > others.max() + 3 * VOX), g
+        assert int((idx == idx[g]).all(axis=1).sum()) == 1, g
+    am = AssembledMap()
+    n = am.build(maps, VOX)
+    op, on, ocol, _ = oracle_voxelised(P, N, Cc)
+    assert n == len(op)
+    check_cloud(am.getPointCloud(), (op, on, ocol))
+
+
 # ---- 3. one submap -----------------------------------------------------------------------------------------------------------
 
 def test_one_submap_equals_the_host_buffer_voxeliser(five):

@@ -185,3 +185,52 @@ def test_pair_sort_of_the_work_areas_is_a_stable_sort(hooks_lib, n):
     assert f(0, keys.ctypes.data, vals.ctypes.data, n, 64, ko.ctypes.data, vo.ctypes.data) == 0
     order = np.argsort(keys, kind="stable")
     assert np.array_equal(ko, keys[order]) and np.array_equal(vo, vals[order])
+
+
+def _bounds_cloud(n):
+    """n points whose six extremes are planted at distinct indices drawn from {0, 63, n // 2, 16384, 262144, n - 1} (those that exist):
+    the first lane, the last lane of a wave, a lane of the ragged tail, a block that wraps onto a used replica and a point only the
+    second stride round sees.  Signs are mixed, +-0.0 and a denormal lie in the bulk, the extremes reach +-1e300 and a denormal."""
+    rng = np.random.default_rng(n)
+    p = np.empty((n, 3))
+    p[:, 0] = rng.uniform(-100.0, 100.0, n)
+    p[:, 1] = rng.uniform(-2.0, -1.0, n)             # all negative: the planted maximum is a denormal
+    p[:, 2] = rng.uniform(1.0, 2.0, n)               # all positive: the planted minimum is a zero
+    p[rng.integers(0, n, max(1, n // 40)), 0] = 0.0
+    p[rng.integers(0, n, max(1, n // 40)), 0] = -0.0
+    p[rng.integers(0, n, max(1, n // 40)), 0] = 5e-324
+    p[rng.integers(0, n, max(1, n // 40)), 2] = 0.0  # ties with the planted -0.0 minimum of this axis: the bound is the negative zero
+    where = sorted({i for i in (0, 63, n // 2, 16384, 262144, n - 1) if i < n})
+    # (axis, value); ordered so that extremes which share an index (fewer than six indices exist) lie on different axes.  One point is
+    # its own minimum and maximum.
+    extremes = [(0, -1e300), (0, 1e300), (1, 5e-324), (1, -1e300), (2, 7.5), (2, -0.0)]
+    for k, (axis, value) in enumerate(extremes):
+        p[where[k % len(where)], axis] = value
+    return p
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 256, 257, 16385, 262144, 262145, 300000])
+def test_cloud_bounds_are_the_exact_extremes(hooks_lib, monkeypatch, n):
+    """csrc/cloud_bounds.h: fill, k_bounds over the flat source on the production grid (min(blocks, 1024): block 64 is the first to share
+    a replica, 262 144 points the last size without a second stride round), fold, fetch — posted and, under O3S_NO_MAILBOX, copied."""
+    import ctypes as C
+    p = _bounds_cloud(n)
+    want = np.concatenate([p.min(axis=0), p.max(axis=0)])
+    for k in range(6):                               # numpy's min / max do not order the zeros: -0.0 < +0.0, as the encoding has it
+        if want[k] == 0.0:
+            negative = np.signbit(p[:, k % 3][p[:, k % 3] == 0.0])
+            want[k] = (-0.0 if negative.any() else 0.0) if k < 3 else (0.0 if not negative.all() else -0.0)
+    f = hooks_lib.o3s_test_cloud_bounds
+    f.restype = C.c_int
+    f.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+    got = {}
+    for side in ("posted", "copied"):
+        if side == "copied":
+            monkeypatch.setenv("O3S_NO_MAILBOX", "1")
+        else:
+            monkeypatch.delenv("O3S_NO_MAILBOX", raising=False)
+        out = np.full(6, np.nan)
+        assert f(0, p.ctypes.data, n, out.ctypes.data) == 0
+        assert np.array_equal(out, want) and out.tobytes() == want.tobytes(), (side, out, want)
+        got[side] = out
+    assert got["posted"].tobytes() == got["copied"].tobytes()

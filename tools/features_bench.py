@@ -4,9 +4,9 @@ both at 0.1 m with 1 cm noise, features with the reference's default parameters 
 Wall time around the blocking calls, median of REPS calls after WARM warm-ups with the garbage collector off during the timed
 calls; beside it, as context only, the wall time of the numpy restatement (tests/fpfh_ref.py) on this job's CPUs.  Run under
 `rocprofv3 --kernel-trace --stats` for the per-kernel times (REF=0 skips the CPU restatement there).  Stages in the trace: voxelise =
-k_vox_* / k_min_bound and their sort, normals = k_normals, lists = k_fpfh_lists, SPFH = k_spfh, FPFH = k_fpfh, correspondences =
-k_feat_nn / k_feat_nn_fold; k_bounds / k_grid_keys / k_cell_ranges / k_gather_sorted build a grid index (one for the normals, one for
-the lists).  REPS=11 WARM=3 by default; OUT=<path> also writes the JSON line there."""
+k_vox_* / k_bounds + k_bounds_post (the anchor's min bound) and their sort, normals = k_normals, lists = k_fpfh_lists, SPFH = k_spfh, FPFH = k_fpfh, correspondences =
+k_feat_nn / k_feat_nn_fold; k_bounds / k_bounds_post / k_grid_keys / k_cell_ranges / k_gather_sorted build a grid index (one for the
+normals, one for the lists).  REPS=11 WARM=3 by default; OUT=<path> also writes the JSON line there."""
 import gc
 import json
 import os
