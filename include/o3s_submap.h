@@ -70,7 +70,8 @@ typedef struct o3s_carving_params {
  * the pose of the PREVIOUS insert, as in the reference: setPose follows the carve, Submap.cpp:66-86) that lies in a
  * visited voxel is removed when |ray . normal| > min_dot (always, for a map without normals).  The survivors keep their
  * order.  Call it before o3s_submap_insert_* on the scans the host's cadence selects (carveSpaceEveryNscans_).
- * n_removed: nullable. */
+ * A coordinate that is not finite, or whose voxel index does not fit int32, names no voxel (the reference's cast of it
+ * is undefined): such a map point is never carved, a stop of a ray with one finds nothing.  n_removed: nullable. */
 int o3s_submap_carve(o3s_submap* m, const o3s_carving_params* p, const double* raw_pts, int64_t N,
                      const double T_map_sensor[16], int64_t* n_removed);
 int64_t o3s_submap_size(const o3s_submap* m);

@@ -162,29 +162,43 @@ __global__ void __launch_bounds__(kB) k_transform_cov(const double* __restrict__
     }
 }
 
-// voxel key of the carving VoxelMap: getVoxelIdx(p, 1 / voxel) (VoxelHashMap.hpp:48-51), packed relative to the subset's
-// index box; points outside the subset get `out_key` — the next power of two above every packed key — and sort last
+// getVoxelIdx(p, 1 / voxel) (VoxelHashMap.hpp:48-51) of the carving VoxelMap, made total: the reference's int cast is undefined for a
+// floor that is NaN, infinite or beyond int32 (x86 gives INT_MIN, which names no voxel of any map; the conversion here gives 0 for
+// NaN and saturates otherwise — 0 is the voxel at the map's origin).  Such a coordinate names no voxel: a map point that has one is
+// in no voxel and is never carved, a stop of a ray that has one finds nothing.  Finite in-range input takes the cast it always took.
+__device__ __forceinline__ bool carve_idx_ok(double f) { return f >= -2147483648.0 && f <= 2147483647.0; }  // false for NaN
+__device__ __forceinline__ bool carve_voxel_of(double x, double y, double z, double inv, int32_t v[3]) {
+  const double fx = floor(x * inv), fy = floor(y * inv), fz = floor(z * inv);
+  if (!(carve_idx_ok(fx) && carve_idx_ok(fy) && carve_idx_ok(fz))) return false;
+  v[0] = (int32_t)fx;
+  v[1] = (int32_t)fy;
+  v[2] = (int32_t)fz;
+  return true;
+}
+// voxel key of the carving VoxelMap, packed relative to the subset's index box; points outside the subset (and points of it that
+// are in no voxel) get `out_key` — the next power of two above every packed key — and sort last
 __global__ void __launch_bounds__(kB) k_carve_keys(const double* __restrict__ pts, int64_t N, const uint32_t* __restrict__ inflag, double inv,
                                                    int32_t x0, int32_t y0, int32_t z0, uint64_t ex, uint64_t ey, uint64_t out_key,
                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
   if (i >= N) return;
   vals[i] = (uint32_t)i;
-  if (!inflag[i]) {
+  int32_t v[3];
+  if (!inflag[i] || !carve_voxel_of(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], inv, v)) {
     keys[i] = out_key;
     return;
   }
-  const int64_t x = (int64_t)(int32_t)floor(pts[3 * i] * inv) - x0, y = (int64_t)(int32_t)floor(pts[3 * i + 1] * inv) - y0,
-                z = (int64_t)(int32_t)floor(pts[3 * i + 2] * inv) - z0;
+  const int64_t x = (int64_t)v[0] - x0, y = (int64_t)v[1] - y0, z = (int64_t)v[2] - z0;
   keys[i] = ((uint64_t)z * ey + (uint64_t)y) * ex + (uint64_t)x;
 }
 __global__ void __launch_bounds__(kB) k_carve_box(const double* __restrict__ pts, int64_t N, const uint32_t* __restrict__ inflag, double inv,
                                                   int32_t* __restrict__ mm_slots /*[kExtSlots][min[3], max[3]]*/) {
   int32_t* mm = mm_slots + 6 * (blockIdx.x & (kExtSlots - 1));
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
-  const bool live = i < N && inflag[i];
+  int32_t vx[3] = {0, 0, 0};
+  const bool live = i < N && inflag[i] && carve_voxel_of(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], inv, vx);
   for (int a = 0; a < 3; ++a) {
-    const int32_t v = live ? (int32_t)floor(pts[3 * i + a] * inv) : 0;
+    const int32_t v = vx[a];
     const int32_t lo = wave_min_i32(live ? v : INT32_MAX), hi = wave_max_i32(live ? v : INT32_MIN);
     if ((threadIdx.x & 63) == 0 && lo <= hi) {  // a (possibly stale) look first: extrema are monotone, so skipping is safe
       if (lo < __atomic_load_n(&mm[a], __ATOMIC_RELAXED)) atomicMin(&mm[a], lo);
@@ -208,8 +222,10 @@ __global__ void __launch_bounds__(kB) k_carve_rays(const double* __restrict__ sc
   const double max_path = fmax(voxel, fmin(length - trunc, max_len));
   while (distance < max_path) {  // NaN lengths (a return at the sensor origin) make this false, like the reference
     const double cx = distance * ux + sx, cy = distance * uy + sy, cz = distance * uz + sz;
-    const int64_t x = (int64_t)(int32_t)floor(cx * inv) - x0, y = (int64_t)(int32_t)floor(cy * inv) - y0, z = (int64_t)(int32_t)floor(cz * inv) - z0;
-    if (x >= 0 && x < ex && y >= 0 && y < ey && z >= 0 && z < ez) {
+    int32_t v[3] = {0, 0, 0};
+    const bool named = carve_voxel_of(cx, cy, cz, inv, v);  // false: an overflowed return has length inf and a NaN direction
+    const int64_t x = (int64_t)v[0] - x0, y = (int64_t)v[1] - y0, z = (int64_t)v[2] - z0;
+    if (named && x >= 0 && x < ex && y >= 0 && y < ey && z >= 0 && z < ez) {
       const uint64_t key = ((uint64_t)z * (uint64_t)ey + (uint64_t)y) * (uint64_t)ex + (uint64_t)x;
       int64_t lo = 0, hi = n_in;  // lower_bound in the sorted subset keys
       while (lo < hi) {
@@ -1052,6 +1068,7 @@ int o3s_submap_carve(o3s_submap* m, const o3s_carving_params* cp, const double* 
   int32_t mm[6];
   rc = ext_i32_fetch(d_mm, mm, s);
   if (rc != O3S_OK) return rc;
+  if (mm[0] > mm[3]) return O3S_OK;  // no point of the subset is in a voxel (all of them non-finite): nothing can be carved
   const int64_t ex = (int64_t)mm[3] - mm[0] + 1, ey = (int64_t)mm[4] - mm[1] + 1, ez = (int64_t)mm[5] - mm[2] + 1;
   if ((long double)ex * (long double)ey * (long double)ez >= 9.0e18L) return O3S_ERR_BAD_ARGUMENT;
   // sort bits: the packed range plus one bit for the key of the points outside the volume (the whole map is sorted: nine passes

@@ -1900,6 +1900,17 @@ int orc_o3d_information_matrix(const double* src, int64_t Ns, const double* tgt,
   return 0;
 }
 
+// getVoxelIdx's int cast is undefined for a value that is not finite or does not fit int32 (x86 gives INT_MIN, other targets 0 or
+// a saturated value).  Here such a coordinate names no voxel: a map point that has one is in no voxel, a stop that has one finds none.
+static bool carve_voxel_of(double x, double y, double z, double inv, std::array<int32_t, 3>& k) {
+  const double f[3] = {std::floor(x * inv), std::floor(y * inv), std::floor(z * inv)};
+  for (int d = 0; d < 3; ++d) {
+    if (!(f[d] >= -2147483648.0 && f[d] <= 2147483647.0)) return false;  // false for NaN
+    k[d] = (int32_t)f[d];
+  }
+  return true;
+}
+
 // getIdxsOfCarvedPoints (O3S/src/helpers.cpp:245-281) over a VoxelMap of the subset (O3S/src/Voxel.cpp:123-149)
 void orc_carve(const double* scan, int64_t Ns, const double* map, const double* map_normals, int64_t Nm, const uint8_t* subset,
                const double* sensor, double voxel, double max_length, double truncation, double min_dot, uint8_t* remove) {
@@ -1909,7 +1920,8 @@ void orc_carve(const double* scan, int64_t Ns, const double* map, const double* 
     remove[i] = 0;
     if (subset && !subset[i]) continue;
     const double* p = map + 3 * i;
-    vox[{(int32_t)std::floor(p[0] * inv), (int32_t)std::floor(p[1] * inv), (int32_t)std::floor(p[2] * inv)}].push_back(i);
+    std::array<int32_t, 3> k;
+    if (carve_voxel_of(p[0], p[1], p[2], inv, k)) vox[k].push_back(i);
   }
   for (int64_t i = 0; i < Ns; ++i) {
     const double dx = scan[3 * i] - sensor[0], dy = scan[3 * i + 1] - sensor[1], dz = scan[3 * i + 2] - sensor[2];
@@ -1919,7 +1931,8 @@ void orc_carve(const double* scan, int64_t Ns, const double* map, const double* 
     const double maxPath = std::max(voxel, std::min(length - truncation, max_length));
     while (distance < maxPath) {
       const double cx = distance * ux + sensor[0], cy = distance * uy + sensor[1], cz = distance * uz + sensor[2];
-      const auto it = vox.find({(int32_t)std::floor(cx * inv), (int32_t)std::floor(cy * inv), (int32_t)std::floor(cz * inv)});
+      std::array<int32_t, 3> k;
+      const auto it = carve_voxel_of(cx, cy, cz, inv, k) ? vox.find(k) : vox.end();
       if (it != vox.end()) {
         for (const int64_t id : it->second) {
           bool rm = true;

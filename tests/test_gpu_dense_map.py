@@ -124,6 +124,116 @@ def test_carve_matches_oracle(radius, voxel):
     same_map(dm, om)
 
 
+def offsets_per_axis(radius, voxel):
+    """How many values the reference's `for (d = -radius; d <= radius; d += voxel)` loop takes, in double precision."""
+    n, d = 0, -radius
+    while d <= radius:
+        n += 1
+        d += voxel
+    return n
+
+
+def small_carve_input(seed=17):
+    rng = np.random.default_rng(seed)
+    pts = rng.uniform(-2.0, 2.0, (20000, 3))
+    sensor = np.array([0.03, -0.02, 0.01])
+    d = rng.normal(size=(200, 3))
+    rays = sensor + d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(1.0, 3.0, (200, 1))
+    return pts, rng.normal(size=pts.shape), sensor, rays
+
+
+# k_dm_carve_rays<NX> exists for 1..7 offsets per axis plus a generic body for 8..16; the rows of test_carve_matches_oracle reach
+# 2, 3, 4 and 5.  (0.3, 0.1) gives SIX values, not seven: the loop's sum overshoots 0.3 by rounding — "the values the loop takes".
+@pytest.mark.parametrize("radius,voxel,n", [(0.04, 0.1, 1), (0.3, 0.1, 6), (0.35, 0.1, 7), (0.36, 0.1, 8), (0.21, 0.06, 8), (0.75, 0.1, 16)])
+def test_carve_matches_oracle_for_every_offset_count(radius, voxel, n):
+    assert offsets_per_axis(radius, voxel) == n
+    pts, nrm, sensor, rays = small_carve_input()
+    dm, om = DenseMap(voxel), orc.DenseMap(voxel)
+    dm.insert(pts, nrm)
+    om.insert(pts, nrm)
+    cp = DenseCarvingParamsC.make(radius, 3.0, 0.1)
+    expected = om.carve(rays, sensor, radius, 3.0, 0.1)
+    assert expected > 100
+    removed = dm.carve(rays, sensor, cp)
+    print(f"dense carve radius {radius} voxel {voxel} (n = {n}): oracle removes {expected}, device {removed}, left {dm.size()}")
+    assert removed == expected
+    same_map(dm, om)
+    extra = np.concatenate([rays[:50] * 0.9, [sensor], rays[:5] * 0.9])     # shorter rays, one of zero length, exact duplicates
+    assert dm.carve(extra, sensor, cp) == om.carve(extra, sensor, radius, 3.0, 0.1)
+    same_map(dm, om)
+
+
+def test_more_offsets_than_the_table_holds_are_refused_and_the_map_untouched():
+    assert offsets_per_axis(0.8, 0.1) == 17
+    pts, nrm, sensor, rays = small_carve_input()
+    dm, om = DenseMap(0.1), orc.DenseMap(0.1)
+    dm.insert(pts, nrm)
+    om.insert(pts, nrm)
+    with pytest.raises(RuntimeError):
+        dm.carve(rays, sensor, DenseCarvingParamsC.make(0.8, 3.0, 0.1))
+    same_map(dm, om)
+    assert dm.carve(rays, sensor, DenseCarvingParamsC.make(0.75, 3.0, 0.1)) == om.carve(rays, sensor, 0.75, 3.0, 0.1) > 0
+    same_map(dm, om)
+
+
+def test_rays_whose_stops_leave_the_index_range():
+    """Voxel 0.05: indices reach +-2^20 at +-52 428.8 m.  Two rays along +-x from a sensor at x = 52 420 march 1e5 m (5e5 stops each,
+    under the 1e6 limit): the +x ray leaves the index range after 8.8 m and keeps going — a stop or a neighbour out there names a
+    voxel that cannot be in the map and must not alias one that is — the -x ray crosses the map and stops 4 849 m short of the
+    voxel at -52 428.79.  A scan point must itself have a voxel key (include/o3s_dense_map.h), so returns at +-60 000 are refused; the
+    same march — same sensor, same unit directions, same stops — is made with returns inside the range and a negative truncation
+    distance, which carries the march past the return to the full ray length."""
+    voxel = 0.05
+    pts = np.array([[52428.0, 0.01, 0.01], [52428.7, 0.01, 0.01], [-52428.79, 0.01, 0.01], [1.0, 0.01, 0.01]])
+    sensor = np.array([52420.0, 0.01, 0.01])
+    dm, om = DenseMap(voxel), orc.DenseMap(voxel)
+    dm.insert(pts)
+    om.insert(pts)
+    with pytest.raises(RuntimeError):
+        dm.carve(np.array([[60000.0, 0.01, 0.01], [-60000.0, 0.01, 0.01]]), sensor, DenseCarvingParamsC.make(0.1, 1.0e5, 0.1))
+    same_map(dm, om)
+    scan = np.array([[52428.75, 0.01, 0.01], [-52428.75, 0.01, 0.01]])
+    expected = om.carve(scan, sensor, 0.1, 1.0e5, -1.0e5)
+    assert expected == 3 and om.size() == 1
+    assert dm.carve(scan, sensor, DenseCarvingParamsC.make(0.1, 1.0e5, -1.0e5)) == 3
+    same_map(dm, om)
+    assert dm.toPointCloud(with_keys=True)[2].tolist() == [[-1048576, 0, 0]]
+
+
+def test_clear_then_insert_and_carve_equals_a_fresh_map():
+    pts, nrm, sensor, rays = small_carve_input(18)
+    cp = DenseCarvingParamsC.make(0.1, 3.0, 0.1)
+    dm, fresh, om = DenseMap(0.1), DenseMap(0.1), orc.DenseMap(0.1)
+    dm.insert(pts[:12000] + 0.5, nrm[:12000])
+    assert dm.carve(rays, sensor, cp) > 0                  # the table that is cleared holds tombstones
+    dm.clear()
+    assert dm.size() == 0 and dm.empty()
+    assert dm.carve(rays, sensor, cp) == 0
+    for m in (dm, fresh, om):
+        m.insert(pts, nrm)
+    removed = dm.carve(rays, sensor, cp)
+    assert removed == fresh.carve(rays, sensor, cp) == om.carve(rays, sensor, 0.1, 3.0, 0.1) > 100
+    same_map(dm, om)
+    same_map(fresh, om)
+
+
+def test_transform_of_a_table_with_tombstones():
+    pts, nrm, sensor, rays = small_carve_input(19)
+    dm, om = DenseMap(0.1), orc.DenseMap(0.1)
+    dm.insert(pts, nrm)
+    om.insert(pts, nrm)
+    assert dm.carve(rays, sensor, DenseCarvingParamsC.make(0.1, 3.0, 0.1)) == om.carve(rays, sensor, 0.1, 3.0, 0.1) > 100
+    T = syn.make_T(syn.rot_axis_angle([0.3, -0.2, 1.0], 0.7), np.array([0.4, -0.3, 0.2]))
+    dm.transform(T)
+    om.transform(T)
+    same_map(dm, om)
+    dm.insert(pts[:5000] * 0.5, nrm[:5000])                # into carved space: tombstones on the probe paths get re-used
+    om.insert(pts[:5000] * 0.5, nrm[:5000])
+    same_map(dm, om)
+    assert dm.carve(rays, sensor, DenseCarvingParamsC.make(0.1, 3.0, 0.1)) == om.carve(rays, sensor, 0.1, 3.0, 0.1)
+    same_map(dm, om)
+
+
 def test_insert_scan_dense_map_sequence():
     """Submap::insertScanDenseMap (Submap.cpp:97-113): crop at the identity pose -> transform (emitting the cloud twice
     for a near-identity pose) -> insert -> carve with the RAW scan when scans-inserted % every == 1."""

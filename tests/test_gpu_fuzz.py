@@ -124,6 +124,73 @@ def test_random_dense_map_histories_agree_with_the_oracle():
     assert steps >= 40
 
 
+def test_random_sparse_carve_histories_agree_with_the_oracle():
+    """Random sequences of insertScan / carve on the device-resident sparse map with random cropping volumes (bounded, unbounded),
+    map voxels, carving voxels of 0.5, 1 and 2.5 map voxels, ray lengths, truncations, min_dot and maps with and without normals;
+    scans with exact duplicates, one zero-length ray and half their points snapped to nominal voxel boundaries (with poses that are
+    pure translations along the grid, so that they stay there in the map frame).  After every step the whole map equals the
+    oracle's bit for bit."""
+    import os
+
+    from open3d_slam_advanced_rss_2024_public_amd import Submap
+    from open3d_slam_advanced_rss_2024_public_amd import cloud_ops as co
+    from test_gpu_submap import oracle_insert
+
+    rng = np.random.default_rng(int(os.environ.get("O3S_FUZZ_SEED", "123")))   # other seeds: longer campaigns from the shell
+    world = syn.make_world(9000.0, seed=3)
+    same = lambda a, b: a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+    steps = carves = carves_that_removed = 0
+    for case in range(int(os.environ.get("O3S_FUZZ_CASES", "12"))):
+        with_normals = bool(rng.random() < 0.6)
+        kind = str(rng.choice(["MaxRadius", "Cylinder", "MinMaxRadius", "MinRadius", "Base"], p=[0.4, 0.2, 0.15, 0.15, 0.1]))
+        r = float(rng.uniform(6.0, 11.0))
+        params = {"MaxRadius": (r,), "Cylinder": (r, float(rng.uniform(-3.0, -0.5)), float(rng.uniform(2.0, 7.0))),
+                  "MinMaxRadius": (float(rng.uniform(0.5, 2.0)), r), "MinRadius": (float(rng.uniform(0.5, 3.0)),), "Base": ()}[kind]
+        map_voxel = float(rng.choice([0.1, 0.2, 0.35]))
+        sm = Submap(map_voxel, co.croppingVolumeFactory("CroppingVolume" if kind == "Base" else kind, *params))
+        mp = mn = centre = None
+        base = np.array([rng.uniform(-6, 6), rng.uniform(-6, 6), 1.5])
+        for step in range(int(rng.integers(3, 8))):
+            op = "insert" if mp is None else str(rng.choice(["insert", "carve", "carve"]))
+            pos = base + rng.uniform(-1.0, 1.0, 3) * np.array([1.0, 1.0, 0.2])
+            if rng.random() < 0.4:       # a pure translation along the map's voxel grid: snapped points stay on voxel boundaries
+                T = syn.make_T(None, np.round(pos / map_voxel) * map_voxel)
+            else:
+                T = syn.make_T(syn.rot_axis_angle(rng.normal(size=3) * np.array([0.1, 0.1, 1.0]), float(rng.uniform(-1, 1))), pos)
+            n = int(rng.integers(500, 8000))
+            sp, sn = syn.make_scan(world, n, T, radius=9.0, sigma=0.01, seed=int(rng.integers(0, 10**6)))
+            sp, sn = sp.astype(np.float64), sn.astype(np.float64)
+            sp[: n // 2] = np.round(sp[: n // 2] / map_voxel) * map_voxel
+            sp[n // 2: n // 2 + n // 8] = sp[: n // 8]
+            sn[n // 2: n // 2 + n // 8] = sn[: n // 8]
+            ctx = (case, step, op, kind, params, map_voxel, with_normals)
+            if op == "insert":
+                assert sm.insertScan(sp, sn if with_normals else None, T)
+                mp, mn = oracle_insert(mp, mn, sp, sn if with_normals else None, T, map_voxel, kind, params)
+                centre = T[:3, 3].copy()
+            else:
+                carve_voxel = float(rng.choice([0.5, 1.0, 2.5])) * map_voxel
+                max_len, trunc = float(rng.uniform(0.5, 12.0)), float(rng.choice([0.0, 0.1, 0.3, 1.0]))
+                min_dot = float(rng.choice([-0.1, 0.0, 0.2, 0.5, 0.9]))
+                sp[0] = 0.0              # a return at the sensor origin: a zero-length ray
+                scan_map, _ = orc.transform_cloud(T, sp, None)
+                subset = orc.crop_mask(orc.make_cropper(kind, *params, centre=centre), mp)
+                rm = orc.carve(scan_map, mp, mn, T[:3, 3], carve_voxel, max_len, trunc, min_dot, subset=subset)
+                k = sm.carve(sp, T, voxel_size=carve_voxel, max_raytracing_length=max_len, truncation_distance=trunc,
+                             min_dot_product_with_normal=min_dot)
+                assert k == int(rm.sum()), ctx
+                mp, mn = mp[~rm], (None if mn is None else mn[~rm])
+                carves += 1
+                carves_that_removed += int(k > 0)
+            gp, gn = sm.getMapPointCloud()
+            assert len(sm) == len(mp) and same(gp, mp), ctx
+            assert (gn is None) == (mn is None) and (mn is None or same(gn, mn)), ctx
+            steps += 1
+    print(f"sparse carve fuzz: {steps} steps, {carves} carves, {carves_that_removed} of them removed points")
+    assert steps >= 40
+    assert carves and 3 * carves_that_removed >= carves, (carves, carves_that_removed)
+
+
 def test_random_resident_scan_loops_agree_with_the_oracle():
     """Random histories through the resident side pipelines — pre-process (wide crop, Open3D down-sample, narrow crop), map
     insert (transform, append, re-voxelise inside the map-builder volume) — with random cropping volumes (bounded ones take

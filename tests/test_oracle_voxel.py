@@ -166,6 +166,49 @@ def test_carve_known_answer():
     assert orc.carve(wall, mp, mn, sensor, 0.1, 2.0, 0.1, 0.5).sum() == 0   # rays cut at 2 m never reach the blob
 
 
+def test_carve_edges_hand_derived():
+    """orc.carve on the edges the GPU carve tests lean on, small enough to do by hand.  Voxel 0.25 and dyadic coordinates: every
+    stop k * 0.25 and every index is exact.  Sensor (0.125, 0.125, 0.125) in voxel (0, 0, 0), one ray along +x of length 2."""
+    from oracle import oracle as orc
+
+    sensor = np.array([0.125, 0.125, 0.125])
+    ray = np.array([[2.125, 0.125, 0.125]])
+    mp = np.array([[0.0625, 0.0625, 0.0625],     # 0: the sensor's own voxel
+                   [0.1875, 0.125, 0.2],         # 1: the same voxel: several map points under one key
+                   [0.8, 0.2, 0.1],              # 2: voxel (3, 0, 0), stop 3
+                   [1.6, 0.1, 0.1],              # 3: voxel (6, 0, 0), the last stop: 1.5 < 2 - 0.25, 1.75 is not
+                   [1.8, 0.1, 0.1],              # 4: voxel (7, 0, 0): kept by the truncation
+                   [2.125, 0.125, 0.125],        # 5: the surface the ray ends on
+                   [0.8, 0.3, 0.1],              # 6: voxel (3, 1, 0): beside the ray
+                   [-0.1, 0.1, 0.1]])            # 7: voxel (-1, 0, 0): behind the sensor
+    c = lambda **kw: orc.carve(ray, mp, kw.pop("normals", None), sensor, 0.25, kw.pop("max_length", 20.0), kw.pop("truncation", 0.25),
+                               kw.pop("min_dot", 0.5)).tolist()
+    F, T = False, True
+    assert c() == [T, T, T, T, F, F, F, F]
+    # a single stop, at the sensor: max_path = max(voxel, min(length - truncation, max_length)) = voxel
+    assert c(max_length=0.2) == [T, T, F, F, F, F, F, F]          # ray length below one voxel
+    assert c(truncation=50.0) == [T, T, F, F, F, F, F, F]         # truncation beyond the ray: length - truncation < 0
+    assert c(max_length=1.0) == [T, T, T, F, F, F, F, F]          # stops 0 .. 0.75: voxels 0 .. 3
+    # normals: the direction is (1, 0, 0) exactly; a zero normal is not normalised and gives a dot product of exactly 0
+    mn = np.array([[0.0, 0.0, 0.0], [2.0, 0.0, 0.0], [0.0, 0.0, 0.0], [0.0, 3.0, 0.0], [1.0, 0, 0], [1.0, 0, 0], [1.0, 0, 0], [1.0, 0, 0]])
+    assert c(normals=mn, min_dot=-0.1) == [T, T, T, T, F, F, F, F]   # 0 > -0.1: zero and perpendicular normals go
+    assert c(normals=mn, min_dot=0.0) == [F, T, F, F, F, F, F, F]    # 0 > 0 is false
+    assert c(normals=mn, min_dot=0.5) == [F, T, F, F, F, F, F, F]
+    assert c(normals=mn, min_dot=1.0) == [F, F, F, F, F, F, F, F]    # |dot| = 1 exactly, and 1 > 1 is false
+    # rays that are not finite remove nothing: length inf or NaN, direction NaN, no stop names a voxel — also with map points in
+    # voxel (0, 0, 0) and at the sensor, where an index made from NaN by a saturating or zeroing cast would land
+    for bad in ([np.inf, 0.125, 0.125], [-np.inf, np.inf, 0.125], [np.nan, 1.0, 1.0], [np.inf, np.inf, np.inf]):
+        for origin in (sensor, np.array([1.125, 1.125, 1.125])):
+            assert not orc.carve(np.array([bad]), mp, None, origin, 0.25, 20.0, 0.25, 0.5).any(), (bad, origin)
+    # a map point that is not finite is in no voxel, and changes nothing for the others
+    mp2 = np.vstack([mp, [[np.nan, 0.1, 0.1]], [[np.inf, 0.1, 0.1]], [[0.1, np.nan, np.nan]]])
+    assert orc.carve(ray, mp2, None, sensor, 0.25, 20.0, 0.25, 0.5).tolist() == [T, T, T, T, F, F, F, F, F, F, F]
+    # a squared length that overflows: length inf, direction 0: every stop is the sensor
+    assert orc.carve(np.array([[1e300, 0.125, 0.125]]), mp, None, sensor, 0.25, 20.0, 0.25, 0.5).tolist() == [T, T, F, F, F, F, F, F]
+    assert orc.carve(np.array([[1e300, 0.125, 0.125]]), mp, mn, sensor, 0.25, 20.0, 0.25, -0.1).tolist() == [T, T, F, F, F, F, F, F]
+    assert not orc.carve(np.array([[1e300, 0.125, 0.125]]), mp, mn, sensor, 0.25, 20.0, 0.25, 0.0).any()   # direction 0: dot 0
+
+
 def test_overlap_indices_hand_derived():
     """computeIndicesOfOverlappingPoints (open3d_slam/src/helpers.cpp:319-345) on a case small enough to do by hand: 1 m
     voxels, the source shifted by +1 m in x by sourceToTarget."""
