@@ -6,6 +6,8 @@ from .submap import AssembledMap, ProcessedScan, Submap  # noqa: F401
 from .submap_collection import SubmapCollection  # noqa: F401
 from .odometry import ConstantVelocityMotionCompensation, LidarOdometry, RawScan, TransformBuffer  # noqa: F401
 from .pose_graph import Constraint, OptimizationProblem, update_submaps_and_trajectory  # noqa: F401
+from .place_recognition import PlaceRecognition, PlaceRecognitionParameters  # noqa: F401
 
 __all__ = ["ICP", "IcpConfig", "IcpStats", "ConvergenceError", "TransformationError", "InvalidModuleType", "HipError", "compute_batch", "Submap", "AssembledMap", "ProcessedScan", "SubmapCollection", "DenseMap", "LidarOdometry",
-           "ConstantVelocityMotionCompensation", "TransformBuffer", "RawScan", "Constraint", "OptimizationProblem", "update_submaps_and_trajectory"]
+           "ConstantVelocityMotionCompensation", "TransformBuffer", "RawScan", "Constraint", "OptimizationProblem", "update_submaps_and_trajectory",
+           "PlaceRecognition", "PlaceRecognitionParameters"]

@@ -21,16 +21,19 @@
 //   :75-81     updateAdjacencyMatrix: the submaps of a loop-closure constraint become adjacent
 //   :69-73     getTotalNumPoints; assembleMap: the loop of Mapper::getAssembledMapPointCloud (Mapper.cpp:524-535) over the resident
 //              submaps as ONE o3s_assembled_map_build call into an AssembledMapHip (the map of all submaps, optionally down-sampled)
-// Not here: candidate selection and isRegistrationConsistent (host policy).  The RANSAC of place recognition
-//              between two submaps of the collection is o3s_submap_registration_ransac (o3s_submap.h) on their feature sets.
+// Place recognition of a finished submap against the collection — candidate selection, the one-to-many RANSAC, the consistency
+//              gates, the batched refinement — is PlaceRecognitionHip (o3s_place_recognition.hpp); the RANSAC between two submaps
+//              is o3s_submap_registration_ransac (o3s_submap.h) on their feature sets.
 // The scans the buffer keeps are resident o3s_scan objects: the caller hands over the scan it has just pre-processed and
 // gets another one to fill next (a ring of numScansOverlap_ + 1 handles, nothing is copied).
 #pragma once
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <deque>
+#include <limits>
 #include <map>
 #include <memory>
 #include <set>
@@ -52,22 +55,54 @@ struct SubmapParams {            // o3d_slam::SubmapParameters (Parameters.hpp:1
   int numScansOverlap = 3;
 };
 
-// o3d_slam::AdjacencyMatrix (AdjacencyMatrix.cpp:16-21, 61-71), the part updateActiveSubmap asks
+// o3d_slam::AdjacencyMatrix (AdjacencyMatrix.cpp:16-71): the edges updateActiveSubmap asks about, and the loop-closure flags
+// getLoopClosureCandidatesIdxs asks about (o3s_place_recognition.hpp)
 class AdjacencyHip {
  public:
-  void addEdge(std::size_t a, std::size_t b) {
+  void addEdge(std::size_t a, std::size_t b) {  // :16-21: BOTH ends lose their loop-closure flag
     adj_[a].insert(b);
     adj_[b].insert(a);
+    isLoopClosureSubmap_[a] = false;
+    isLoopClosureSubmap_[b] = false;
   }
   bool isAdjacent(std::size_t a, std::size_t b) const {
     if (a == b) return true;
     const auto it = adj_.find(a);
     return it != adj_.end() && it->second.count(b) != 0;
   }
+  void markAsLoopClosureSubmap(std::size_t id) { isLoopClosureSubmap_.at(id) = true; }  // :57-59 (std::out_of_range for an id no edge names)
+  // :23-55 as written: INT_MAX while no edge has been added; else a breadth-first walk from `id` that stops at the first flagged
+  // submap it takes from the queue — or, when none is reachable, at the LAST submap it visits — and returns max(0, hops - 1)
+  int getDistanceToNearestLoopClosureSubmap(std::size_t id) const {
+    if (isLoopClosureSubmap_.empty()) return std::numeric_limits<int>::max();
+    std::deque<std::size_t> toProcess;
+    std::set<std::size_t> visited;
+    std::map<std::size_t, std::size_t> parents;
+    std::size_t v = id;
+    visited.insert(id);
+    toProcess.push_back(id);
+    while (!toProcess.empty()) {
+      v = toProcess.front();
+      toProcess.pop_front();
+      if (isLoopClosureSubmap_.at(v)) break;
+      for (const std::size_t adj : adj_.at(v))
+        if (visited.insert(adj).second) {
+          toProcess.push_back(adj);
+          parents.insert({adj, v});
+        }
+    }
+    int distance = 0;
+    while (v != id) {
+      v = parents.at(v);
+      ++distance;
+    }
+    return std::max(0, distance - 1);
+  }
   const std::map<std::size_t, std::set<std::size_t>>& edges() const { return adj_; }
 
  private:
   std::map<std::size_t, std::set<std::size_t>> adj_;
+  std::map<std::size_t, bool> isLoopClosureSubmap_;
 };
 
 // The map of all submaps, resident on the device (assembled_map/o3s_assembled_map.h): the result of
@@ -181,7 +216,11 @@ class SubmapCollectionHip {
   }
   // SubmapCollection::updateAdjacencyMatrix (:75-81)
   void updateAdjacencyMatrix(const Constraints& loopClosureConstraints) {
-    for (const auto& c : loopClosureConstraints) adjacency_.addEdge(c.sourceSubmapIdx, c.targetSubmapIdx);
+    for (const auto& c : loopClosureConstraints) {
+      adjacency_.addEdge(c.sourceSubmapIdx, c.targetSubmapIdx);
+      adjacency_.markAsLoopClosureSubmap(c.sourceSubmapIdx);
+      adjacency_.markAsLoopClosureSubmap(c.targetSubmapIdx);
+    }
   }
   // the dense map the driver keeps for submap `idx` (Submap::denseMap_): transform() moves it with the submap; not owned
   void setDenseMap(std::size_t idx, DenseMapHip* dense) { denseMaps_[idx] = dense; }

@@ -241,6 +241,7 @@ int o3s_motion_from_poses(const double T_start[16], double t_start, const double
 #include "assemble_impl.h"
 #include "features_impl.h"
 #include "ransac_impl.h"
+#include "place_impl.h"
 #include "dense_map_impl.h"
 #include "overlap_impl.h"
 

@@ -11,6 +11,9 @@
 //   k_fpfh           a lane per (point, group of 11 rows): distance-weighted sum of the neighbours' SPFH in list order
 //   k_feat_nn        brute-force 1-NN in feature space, target columns tiled through LDS, one partial winner per target chunk
 //   k_feat_nn_fold   folds the chunks' winners (ties to the lower index)
+//   k_feat_nn_fwd_multi / k_feat_nn_fwd_fold / k_feat_nn_bwd_multi   the same search of ONE source against up to 16 targets read through a
+//                    table (FeatSegs): all targets in one launch per direction, chunks snapped to the targets' boundaries
+//   k_place_count / k_place_flags / k_place_scatter   mutual filter, per-target fall-back and order-preserving compaction on the device
 #pragma once
 #include "normals_dev.h"
 
@@ -481,6 +484,317 @@ inline int feature_correspondences_dev(FeatNnWork& w, const double* d_src, int64
     }
   }
   *n_out = k;
+  return O3S_OK;
+}
+
+// ---- one source against several targets (include/place_recognition/o3s_place_recognition.h) -----------------------------------
+// The feature arrays of up to kPlaceMaxTargets targets as a table passed by value: nothing is concatenated or copied.  beg[k] is
+// the first column of target k in the concatenated column space, beg[K] the number of columns of all targets; cbeg[k] the first
+// chunk of target k in the forward search, whose chunks all hold `chunk` columns (a whole number of tiles) and never straddle
+// two targets.  The arithmetic is k_feat_nn's: per-segment results do not depend on the partition.
+constexpr int kPlaceMaxTargets = 16;
+struct FeatSegs {
+  const double* f[kPlaceMaxTargets];
+  int64_t beg[kPlaceMaxTargets + 1];
+  int32_t cbeg[kPlaceMaxTargets + 1];
+  int32_t K;
+  int64_t chunk;
+};
+// the segment that holds element g of a table of begins (statically indexed: the table stays in scalar registers)
+template <class T>
+__device__ __forceinline__ int seg_of(const T (&beg)[kPlaceMaxTargets + 1], int K, T g) {
+  int k = 0;
+#pragma unroll
+  for (int q = 1; q < kPlaceMaxTargets; ++q)
+    if (q < K && g >= beg[q]) k = q;
+  return k;
+}
+template <class T>
+__device__ __forceinline__ T seg_pick(const T (&v)[kPlaceMaxTargets], int k) {
+  T r = v[0];
+#pragma unroll
+  for (int q = 1; q < kPlaceMaxTargets; ++q)
+    if (q == k) r = v[q];
+  return r;
+}
+template <class T>
+__device__ __forceinline__ T seg_pick1(const T (&v)[kPlaceMaxTargets + 1], int k) {
+  T r = v[0];
+#pragma unroll
+  for (int q = 1; q <= kPlaceMaxTargets; ++q)
+    if (q == k) r = v[q];
+  return r;
+}
+
+// Forward: nearest column of every target for every source column, one launch.  blockIdx.y is a chunk of ONE target; the winner's
+// index is local to that target.
+template <int DIM>
+__global__ void __launch_bounds__(kFcBlock) k_feat_nn_fwd_multi(const double* __restrict__ src, int64_t n, FeatSegs sg, int dim_rt,
+                                                                double* __restrict__ part_d /*[chunks][n]*/, int32_t* __restrict__ part_j) {
+  __shared__ double s_t[kFcTileDoubles];
+  const int dim = DIM > 0 ? DIM : dim_rt;
+  const int tile = kFcTileDoubles / dim;
+  const int64_t i = (int64_t)blockIdx.x * kFcBlock + threadIdx.x;
+  const int k = seg_of(sg.cbeg, sg.K, (int32_t)blockIdx.y);
+  const double* __restrict__ tgt = seg_pick(sg.f, k);
+  const int64_t m = seg_pick1(sg.beg, k + 1) - seg_pick1(sg.beg, k);
+  const int64_t t0 = (int64_t)((int32_t)blockIdx.y - seg_pick1(sg.cbeg, k)) * sg.chunk, t1 = t0 + sg.chunk < m ? t0 + sg.chunk : m;
+  const double* a_g = src + (size_t)(i < n ? i : 0) * (size_t)dim;
+  double a[DIM > 0 ? DIM : 1];
+  if (DIM > 0) {
+#pragma unroll
+    for (int j = 0; j < DIM; ++j) a[j] = a_g[j];
+  }
+  double best = __builtin_huge_val();
+  int32_t bj = -1;
+  for (int64_t tb = t0; tb < t1; tb += tile) {
+    const int nt = (int)(t1 - tb < (int64_t)tile ? t1 - tb : (int64_t)tile);
+    __syncthreads();
+    for (int e = threadIdx.x; e < nt * dim; e += kFcBlock) s_t[e] = tgt[(size_t)tb * (size_t)dim + (size_t)e];
+    __syncthreads();
+    for (int u = 0; u < nt; ++u) {
+      double d = 0.0;
+      if (DIM > 0) {
+#pragma unroll
+        for (int j = 0; j < DIM; ++j) {
+          const double df = a[j] - s_t[u * DIM + j];
+          d = d + df * df;
+        }
+      } else {
+        for (int j = 0; j < dim; ++j) {
+          const double df = a_g[j] - s_t[u * dim + j];
+          d = d + df * df;
+        }
+      }
+      if (d < best) {
+        best = d;
+        bj = (int32_t)(tb + u);
+      }
+    }
+  }
+  if (i < n) {
+    part_d[(size_t)blockIdx.y * (size_t)n + (size_t)i] = best;
+    part_j[(size_t)blockIdx.y * (size_t)n + (size_t)i] = bj;
+  }
+}
+// ij[k][i]: the chunks of target k in ascending order (blockIdx.y = k); a target without columns has no chunk and gives -1
+__global__ void __launch_bounds__(kFcBlock) k_feat_nn_fwd_fold(const double* __restrict__ part_d, const int32_t* __restrict__ part_j, int64_t n, FeatSegs sg,
+                                                               int32_t* __restrict__ ij /*[K][n]*/) {
+  const int64_t i = (int64_t)blockIdx.x * kFcBlock + threadIdx.x;
+  if (i >= n) return;
+  const int k = (int)blockIdx.y;
+  const int c0 = seg_pick1(sg.cbeg, k), c1 = seg_pick1(sg.cbeg, k + 1);
+  double best = __builtin_huge_val();
+  int32_t bj = -1;
+  for (int c = c0; c < c1; ++c) {
+    const double d = part_d[(size_t)c * (size_t)n + (size_t)i];
+    if (d < best) {
+      best = d;
+      bj = part_j[(size_t)c * (size_t)n + (size_t)i];
+    }
+  }
+  ij[(size_t)k * (size_t)n + (size_t)i] = bj;
+}
+
+// Backward: nearest source column of every column of every target, one launch.  A thread owns column g of the concatenated
+// targets, read through the table; the block stages tiles of the source, blockIdx.y walks chunks of it.
+template <int DIM>
+__global__ void __launch_bounds__(kFcBlock) k_feat_nn_bwd_multi(FeatSegs sg, const double* __restrict__ src, int64_t n, int dim_rt, int64_t chunk,
+                                                                double* __restrict__ part_d /*[chunks][M]*/, int32_t* __restrict__ part_j) {
+  __shared__ double s_t[kFcTileDoubles];
+  const int dim = DIM > 0 ? DIM : dim_rt;
+  const int tile = kFcTileDoubles / dim;
+  const int64_t M = seg_pick1(sg.beg, sg.K);
+  const int64_t g = (int64_t)blockIdx.x * kFcBlock + threadIdx.x, gc = g < M ? g : 0;
+  const int k = seg_of(sg.beg, sg.K, gc);
+  const double* a_g = seg_pick(sg.f, k) + (size_t)(gc - seg_pick1(sg.beg, k)) * (size_t)dim;
+  const int64_t t0 = (int64_t)blockIdx.y * chunk, t1 = t0 + chunk < n ? t0 + chunk : n;
+  double a[DIM > 0 ? DIM : 1];
+  if (DIM > 0) {
+#pragma unroll
+    for (int j = 0; j < DIM; ++j) a[j] = a_g[j];
+  }
+  double best = __builtin_huge_val();
+  int32_t bj = -1;
+  for (int64_t tb = t0; tb < t1; tb += tile) {
+    const int nt = (int)(t1 - tb < (int64_t)tile ? t1 - tb : (int64_t)tile);
+    __syncthreads();
+    for (int e = threadIdx.x; e < nt * dim; e += kFcBlock) s_t[e] = src[(size_t)tb * (size_t)dim + (size_t)e];
+    __syncthreads();
+    for (int u = 0; u < nt; ++u) {
+      double d = 0.0;
+      if (DIM > 0) {
+#pragma unroll
+        for (int j = 0; j < DIM; ++j) {
+          const double df = a[j] - s_t[u * DIM + j];
+          d = d + df * df;
+        }
+      } else {
+        for (int j = 0; j < dim; ++j) {
+          const double df = a_g[j] - s_t[u * dim + j];
+          d = d + df * df;
+        }
+      }
+      if (d < best) {
+        best = d;
+        bj = (int32_t)(tb + u);
+      }
+    }
+  }
+  if (g < M) {
+    part_d[(size_t)blockIdx.y * (size_t)M + (size_t)g] = best;
+    part_j[(size_t)blockIdx.y * (size_t)M + (size_t)g] = bj;
+  }
+}
+
+// The head of a place-recognition call, kPlaceHeadWords u32 per target: [0] mutual pairs counted, [1] used_fallback, [2] n_pairs
+constexpr int kPlaceHeadWords = 4;
+// mutual pairs of every target: one integer atomic per wave (the count does not depend on their order)
+__global__ void __launch_bounds__(kFcBlock) k_place_count(const int32_t* __restrict__ ij, const int32_t* __restrict__ ji, int64_t n, FeatSegs sg,
+                                                          uint32_t* __restrict__ head) {
+  const int64_t i = (int64_t)blockIdx.x * kFcBlock + threadIdx.x;
+  const int k = (int)blockIdx.y;
+  bool f = false;
+  if (i < n) {
+    const int32_t j = ij[(size_t)k * (size_t)n + (size_t)i];
+    f = j >= 0 && ji[(size_t)(seg_pick1(sg.beg, k) + j)] == (int32_t)i;
+  }
+  const unsigned long long b = __ballot(f);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(&head[k * kPlaceHeadWords], (uint32_t)__popcll(b));
+}
+// flag[k][i] of the pair (i, ij[k][i]): mutual, or — no mutual filter, or fewer than 3 ransac_n mutual pairs in THIS target —
+// every source column that has a nearest column.  Thread 0 of each target's first block records the decision.
+__global__ void __launch_bounds__(kFcBlock) k_place_flags(const int32_t* __restrict__ ij, const int32_t* __restrict__ ji, int64_t n, FeatSegs sg, int mutual,
+                                                          uint32_t min_mutual, uint32_t* __restrict__ head, uint32_t* __restrict__ flag /*[K * n + 1]*/) {
+  const int64_t i = (int64_t)blockIdx.x * kFcBlock + threadIdx.x;
+  const int k = (int)blockIdx.y;
+  const int64_t b0 = seg_pick1(sg.beg, k), m = seg_pick1(sg.beg, k + 1) - b0;
+  const bool fallback = mutual && m > 0 && head[k * kPlaceHeadWords] < min_mutual;
+  if (i == 0) head[k * kPlaceHeadWords + 1] = fallback ? 1u : 0u;
+  if (i == 0 && k == 0) flag[(size_t)sg.K * (size_t)n] = 0u;  // the scan's last offset is then the number of all pairs
+  if (i >= n) return;
+  const int32_t j = ij[(size_t)k * (size_t)n + (size_t)i];
+  bool f = j >= 0;
+  if (f && mutual && !fallback) f = ji[(size_t)(b0 + j)] == (int32_t)i;
+  flag[(size_t)k * (size_t)n + (size_t)i] = f ? 1u : 0u;
+}
+// order-preserving compaction into target k's slice (n pairs wide) of the pair buffer, and the slice's length
+__global__ void __launch_bounds__(kFcBlock) k_place_scatter(const int32_t* __restrict__ ij, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ off,
+                                                            int64_t n, uint32_t* __restrict__ head, int32_t* __restrict__ pairs /*[K][n][2]*/) {
+  const int64_t i = (int64_t)blockIdx.x * kFcBlock + threadIdx.x;
+  const int k = (int)blockIdx.y;
+  const size_t r0 = (size_t)k * (size_t)n;
+  const uint32_t o0 = off[r0];
+  if (i == 0) head[k * kPlaceHeadWords + 2] = off[r0 + (size_t)n] - o0;
+  if (i >= n || !flag[r0 + (size_t)i]) return;
+  const size_t at = r0 + (size_t)(off[r0 + (size_t)i] - o0);
+  pairs[2 * at] = (int32_t)i;
+  pairs[2 * at + 1] = ij[r0 + (size_t)i];
+}
+
+// Blocks a search launch aims at.  The 33-row search holds 85 VGPRs: 5 waves per SIMD, 5 blocks per CU, 1280 resident blocks on the
+// 256 CUs; a launch of 8 x 1280 blocks of equal work leaves at most an eighth of the last round idle (feat_nn_dev's 2048 blocks are
+// 1.6 rounds, and a one-to-many launch has K times the columns to cut finer).  Measured at closure size, K = 4: 2048 -> 31.2 ms,
+// 5120 -> 26.2, 10240 -> 25.7, 40960 -> 24.9 against 30 ms for the loop of per-pair calls; the partial winners grow with
+// it (12 bytes per source column and chunk).  The hooks build reads it per call, so that one test can run several partitions of the
+// same targets.
+constexpr int kPlaceBlocks = 10240;
+inline int64_t place_blocks() {
+  if (const char* e = O3S_HOOK_ENV("O3S_PLACE_BLOCKS")) {
+    const long v = atol(e);
+    if (v >= 1 && v <= (1 << 20)) return (int64_t)v;
+  }
+  return kPlaceBlocks;
+}
+
+// grow-only work area of a one-to-many call (part of the leased RANSAC area, ransac_impl.h)
+struct PlaceWork {
+  Buf part_d, part_j, ij, ji, flag, off, head, pairs, scan_tmp;
+};
+
+// Correspondences of one source feature array against K targets (device arrays): w.pairs holds K slices of n_src pairs, slice k
+// the pairs of target k in ascending source index; n_out[k], used_fallback[k] come to the host in ONE small copy, behind which the
+// stream is drained.  The arguments were checked by the caller: 1 <= K <= kPlaceMaxTargets, n_src >= 1, K n_src < 2^31, all
+// targets' columns together < 2^31, 1 <= dim <= kFcDimMax, ransac_n >= 0.
+inline int place_correspondences_dev(PlaceWork& w, const double* d_src, int64_t n, const double* const* d_tgt, const int64_t* n_tgt, int K, int dim,
+                                     int mutual_filter, int ransac_n, int64_t* n_out, int32_t* used_fallback, hipStream_t s) {
+  const int64_t tile = kFcTileDoubles / dim;
+  const unsigned bx = (unsigned)((n + kFcBlock - 1) / kFcBlock);
+  FeatSegs sg;
+  memset(&sg, 0, sizeof(sg));
+  sg.K = K;
+  int64_t M = 0;
+  for (int k = 0; k < K; ++k) {
+    sg.f[k] = d_tgt[k];
+    sg.beg[k] = M;
+    M += n_tgt[k];
+  }
+  for (int k = K; k <= kPlaceMaxTargets; ++k) sg.beg[k] = M;
+  // about kPlaceBlocks blocks in all; one chunk size for every target, a whole number of tiles
+  const int64_t blocks = place_blocks();
+  const int64_t want = std::max<int64_t>(1, std::min<int64_t>((M + tile - 1) / tile, blocks / (int64_t)bx));
+  sg.chunk = std::max<int64_t>(tile, ((M + want - 1) / want + tile - 1) / tile * tile);
+  int32_t chunks = 0;
+  for (int k = 0; k < K; ++k) {
+    sg.cbeg[k] = chunks;
+    chunks += (int32_t)((n_tgt[k] + sg.chunk - 1) / sg.chunk);
+  }
+  for (int k = K; k <= kPlaceMaxTargets; ++k) sg.cbeg[k] = chunks;
+  const size_t rows = (size_t)K * (size_t)n;
+  CK(w.ij.alloc(rows * 4));
+  CK(w.flag.alloc((rows + 1) * 4));
+  CK(w.off.alloc((rows + 2) * 4));
+  CK(w.pairs.alloc(rows * 8));
+  CK(w.head.alloc((size_t)kPlaceMaxTargets * kPlaceHeadWords * 4));
+  const size_t scan_bytes = scan_temp_bytes((int64_t)rows + 1);
+  CK(w.scan_tmp.alloc(scan_bytes));
+  // backward chunks over the source
+  const unsigned by = (unsigned)((M + kFcBlock - 1) / kFcBlock);
+  int64_t bchunks = std::max<int64_t>(1, std::min<int64_t>((n + tile - 1) / tile, blocks / (int64_t)std::max(by, 1u)));
+  const int64_t bchunk = ((n + bchunks - 1) / bchunks + tile - 1) / tile * tile;
+  bchunks = (n + bchunk - 1) / bchunk;
+  const bool back = mutual_filter && M > 0;
+  CK(w.part_d.alloc(std::max((size_t)chunks * (size_t)n, back ? (size_t)bchunks * (size_t)M : (size_t)0) * 8));
+  CK(w.part_j.alloc(std::max((size_t)chunks * (size_t)n, back ? (size_t)bchunks * (size_t)M : (size_t)0) * 4));
+  CK(hipMemsetAsync(w.head.p, 0, (size_t)kPlaceMaxTargets * kPlaceHeadWords * 4, s));
+  if (chunks > 0) {
+    if (dim == kFpfhDim)
+      hipLaunchKernelGGL(k_feat_nn_fwd_multi<kFpfhDim>, dim3(bx, (unsigned)chunks), dim3(kFcBlock), 0, s, d_src, n, sg, dim, w.part_d.as<double>(),
+                         w.part_j.as<int32_t>());
+    else
+      hipLaunchKernelGGL(k_feat_nn_fwd_multi<0>, dim3(bx, (unsigned)chunks), dim3(kFcBlock), 0, s, d_src, n, sg, dim, w.part_d.as<double>(),
+                         w.part_j.as<int32_t>());
+  }
+  hipLaunchKernelGGL(k_feat_nn_fwd_fold, dim3(bx, (unsigned)K), dim3(kFcBlock), 0, s, (const double*)w.part_d.as<double>(), (const int32_t*)w.part_j.as<int32_t>(), n,
+                     sg, w.ij.as<int32_t>());
+  if (back) {  // in stream order behind the fold, which was the last reader of the forward partial winners
+    CK(w.ji.alloc((size_t)M * 4));
+    if (dim == kFpfhDim)
+      hipLaunchKernelGGL(k_feat_nn_bwd_multi<kFpfhDim>, dim3(by, (unsigned)bchunks), dim3(kFcBlock), 0, s, sg, d_src, n, dim, bchunk, w.part_d.as<double>(),
+                         w.part_j.as<int32_t>());
+    else
+      hipLaunchKernelGGL(k_feat_nn_bwd_multi<0>, dim3(by, (unsigned)bchunks), dim3(kFcBlock), 0, s, sg, d_src, n, dim, bchunk, w.part_d.as<double>(),
+                         w.part_j.as<int32_t>());
+    hipLaunchKernelGGL(k_feat_nn_fold, dim3(by), dim3(kFcBlock), 0, s, (const double*)w.part_d.as<double>(), (const int32_t*)w.part_j.as<int32_t>(), M, (int)bchunks,
+                       w.ji.as<int32_t>());
+    hipLaunchKernelGGL(k_place_count, dim3(bx, (unsigned)K), dim3(kFcBlock), 0, s, (const int32_t*)w.ij.as<int32_t>(), (const int32_t*)w.ji.as<int32_t>(), n, sg,
+                       w.head.as<uint32_t>());
+  }
+  hipLaunchKernelGGL(k_place_flags, dim3(bx, (unsigned)K), dim3(kFcBlock), 0, s, (const int32_t*)w.ij.as<int32_t>(), (const int32_t*)w.ji.as<int32_t>(), n, sg,
+                     back ? 1 : 0, (uint32_t)std::min<int64_t>((int64_t)3 * ransac_n, (int64_t)0xffffffff), w.head.as<uint32_t>(), w.flag.as<uint32_t>());
+  CK(hipGetLastError());
+  const int rc = scan_flags_dev(w.flag.as<uint32_t>(), w.off.as<uint32_t>(), (int64_t)rows + 1, w.scan_tmp.p, scan_bytes, s);
+  if (rc != O3S_OK) return rc;
+  hipLaunchKernelGGL(k_place_scatter, dim3(bx, (unsigned)K), dim3(kFcBlock), 0, s, (const int32_t*)w.ij.as<int32_t>(), (const uint32_t*)w.flag.as<uint32_t>(),
+                     (const uint32_t*)w.off.as<uint32_t>(), n, w.head.as<uint32_t>(), w.pairs.as<int32_t>());
+  CK(hipGetLastError());
+  uint32_t head[kPlaceMaxTargets * kPlaceHeadWords];
+  CK(hipMemcpyAsync(head, w.head.p, sizeof(head), hipMemcpyDeviceToHost, s));
+  CK(hipStreamSynchronize(s));
+  for (int k = 0; k < K; ++k) {
+    n_out[k] = (int64_t)head[k * kPlaceHeadWords + 2];
+    if (used_fallback) used_fallback[k] = (int32_t)head[k * kPlaceHeadWords + 1];
+  }
   return O3S_OK;
 }
 

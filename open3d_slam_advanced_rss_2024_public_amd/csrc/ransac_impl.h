@@ -18,6 +18,7 @@ struct RansacWork {
   Buf rec, hdr, flag, off, outcome, T, surv, part_n, part_e, sv_n, sv_e, scan_tmp, iflag, ioff, iout, slot_n, slot_e;
   PostBlock<> post;  // kRansacAhead slots of the common layout, one per batch in flight
   FeatNnWork nn;
+  PlaceWork place;  // the one-to-many front end (place_impl.h)
   size_t scan_bytes = 0;
 };
 struct RansacPool {

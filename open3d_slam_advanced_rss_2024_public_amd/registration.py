@@ -536,7 +536,8 @@ def loop_closure_constraint(source_submap, target_submap, ransac_params: RansacP
     feature sets: RANSAC on the feature correspondences, the ransac_min_corresondence_set_size gate, overlap selection at the RANSAC
     pose and refinement with the chosen registration type, the min_refinement_fitness gate, the information matrix.
     overlap_voxel_size: magic::voxelExpansionFactorOverlapComputation x the map voxel size (the caller's; required).
-    isRegistrationConsistent and the choice of candidates are host policy and stay with the caller."""
+    isRegistrationConsistent and the choice of candidates are place_recognition.PlaceRecognition's, which runs a finished submap
+    against all its candidates at once; this call stays the per-pair yardstick."""
     if overlap_voxel_size is None:
         raise ValueError("overlap_voxel_size is required (voxelExpansionFactorOverlapComputation x map voxel size)")
     rr = source_submap.ransacRegistration(target_submap, ransac_params, mutual_filter)

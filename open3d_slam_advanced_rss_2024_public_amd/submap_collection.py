@@ -8,6 +8,9 @@ from .mapper import mul4
 from .submap import AssembledMap, ProcessedScan, Submap, transform_submaps
 
 
+INT_MAX = 2**31 - 1   # std::numeric_limits<int>::max()
+
+
 class SubmapCollection:
     """SubmapCollection::insertScan / updateActiveSubmap (SubmapCollection.cpp:94-247) restated over the Python mirror — the
     same steps as cpp/o3s_submap_collection.hpp, resident scans in a ring of numScansOverlap + 1 objects."""
@@ -30,6 +33,7 @@ class SubmapCollection:
         self.dense_maps = {}           # submap index -> dense map object (transform(T)), where the driver keeps one
         self.active, self.next_id, self.merged, self.force = 0, 0, 0, False
         self.edges = set()
+        self.loop_closure_flags = {}   # AdjacencyMatrix::isLoopClosureSubmap_: submap id -> flag, an entry per id an edge has named
         self.buffer, self.free = [], [scan_factory() for _ in range(overlap + 1)]
         self.finished, self.finished_queue, self.switched = [], [], False
         self.create(np.zeros(3))
@@ -58,6 +62,46 @@ class SubmapCollection:
 
     def adjacent(self, a, b):
         return a == b or (min(a, b), max(a, b)) in self.edges
+
+    def add_edge(self, a, b):
+        """AdjacencyMatrix::addEdge (AdjacencyMatrix.cpp:16-21): the edge, and BOTH ends lose their loop-closure flag."""
+        self.edges.add((min(a, b), max(a, b)))
+        self.loop_closure_flags[a] = False
+        self.loop_closure_flags[b] = False
+
+    def markAsLoopClosureSubmap(self, i):
+        """AdjacencyMatrix::markAsLoopClosureSubmap (:57-59): `.at(id)` — KeyError for an id no edge has named."""
+        if i not in self.loop_closure_flags:
+            raise KeyError(i)
+        self.loop_closure_flags[i] = True
+
+    def getDistanceToNearestLoopClosureSubmap(self, i) -> int:
+        """AdjacencyMatrix::getDistanceToNearestLoopClosureSubmap (:23-55) as written: INT_MAX while no edge has been added; else a
+        breadth-first walk from `i` (neighbours in ascending id, std::set's order) that stops at the first flagged submap it takes
+        from the queue — or, when none is reachable, at the LAST submap it visits — and returns max(0, hops to it - 1)."""
+        if not self.loop_closure_flags:
+            return INT_MAX
+        neighbours = {}
+        for a, b in self.edges:
+            if a != b:
+                neighbours.setdefault(a, set()).add(b)
+                neighbours.setdefault(b, set()).add(a)
+        queue, visited, parents = [i], {i}, {}
+        v = i
+        while queue:
+            v = queue.pop(0)
+            if self.loop_closure_flags.get(v, False):   # (an id only a directly added edge names carries no flag)
+                break
+            for adj in sorted(neighbours.get(v, ())):
+                if adj not in visited:
+                    visited.add(adj)
+                    queue.append(adj)
+                    parents[adj] = v
+        distance = 0
+        while v != i:
+            v = parents[v]
+            distance += 1
+        return max(0, distance - 1)
 
     def update_active(self, p0):
         if self.force:
@@ -99,8 +143,7 @@ class SubmapCollection:
             self.finished.append((prev, stamp))
             self.finished_queue.append((prev, stamp))
             self.merged = 0
-            a, b = self.ids[prev], self.ids[self.active]
-            self.edges.add((min(a, b), max(a, b)))
+            self.add_edge(self.ids[prev], self.ids[self.active])
             while self.buffer:
                 q, Tq, _ = self.buffer.pop(0)
                 self._insert_into(self.active, q, Tq)
@@ -120,10 +163,13 @@ class SubmapCollection:
         return out
 
     def update_adjacency_matrix(self, loop_closure_constraints):
-        """SubmapCollection::updateAdjacencyMatrix (:75-81): a loop-closure constraint makes its two submaps adjacent."""
+        """SubmapCollection::updateAdjacencyMatrix (:75-81): a loop-closure constraint makes its two submaps adjacent and marks
+        both as loop-closure submaps."""
         for c in loop_closure_constraints:
             a, b = c.source_submap_idx, c.target_submap_idx
-            self.edges.add((min(a, b), max(a, b)))
+            self.add_edge(a, b)
+            self.markAsLoopClosureSubmap(a)
+            self.markAsLoopClosureSubmap(b)
 
     def getTotalNumPoints(self) -> int:
         """SubmapCollection::getTotalNumPoints (:69-73): the sum of the submaps' map sizes."""
