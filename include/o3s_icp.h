@@ -312,6 +312,32 @@ int o3s_icp_get_last_step(const o3s_icp* h, float T_step[16]);
  * included (0 unless the last compute ran with error_minimizer 1).  Diagnostics (tools/covariance_bench.py). */
 int o3s_icp_covariance_gpu_us(const o3s_icp* h, double out2[2]);
 
+/* ---- registration fitness (Open3D RegistrationResult::fitness_ / inlier_rmse_; the health gate the reference reads at
+ * O3S/src/Mapper.cpp:424-431 against MapperParameters::minRefinementFitness_) ------------------------------------------------
+ * Stated over the chain's own matcher: a reading point counts when its exact nearest reference point has an fp32 squared
+ * distance d2 <= r2, r = max_correspondence_distance, r2 = r * r in fp32; r = 0 means the chain's max_dist.  Ties and the
+ * inclusion rule (d2 <= maxDist^2) are the matcher's.  A reading point that is not finite (or not finite under the pose) has no
+ * match and never reaches the sum.  MirrorMatcher: every point is matched at distance 0.
+ *   T == NULL  evaluates where the last successful compute on this handle left the reading: T_iter (T0 p), the pose that call
+ *              returned — exactly the points iteration k + 1 would have matched.  O3S_ERR_NOT_INITIALIZED without such a compute
+ *              (none yet, a failed one, or the reading / the reference replaced since).
+ *   T != NULL  matches exactly what iteration 0 of o3s_icp_compute_resident(T_init = T) matches (O3S_ERR_NOT_RIGID as there).
+ * r < 0, NaN or r > max_dist: O3S_ERR_BAD_ARGUMENT; a sharded handle: O3S_ERR_BAD_CONFIG; no reference: O3S_ERR_NOT_INITIALIZED;
+ * no resident reading: O3S_ERR_EMPTY_READING (a new reference retires the resident reading too: set it again).
+ * One matcher launch, one pass over its output (k_fit, csrc/icp_kernels.h: an integer count and an fp64 sum of the promoted fp32
+ * distances per block, folded in block order — run-independent), one host post.  T_out, covariance, last step, trace and stats of
+ * the preceding compute stay readable; o3s_icp_get_error_elements reports nothing afterwards (as after o3s_icp_profile_match); the
+ * next compute returns the bits it would have returned without the evaluation. */
+typedef struct o3s_icp_fitness {
+  int64_t n_points, n_correspondences;
+  double fitness;      /* n_correspondences / n_points                          */
+  double inlier_rmse;  /* sqrt(sum d^2 / n_correspondences); 0 when there is none */
+  float gpu_ms;        /* device time, matcher launch -> the post (wall_clock64 stamps, like o3s_icp_stats::gpu_ms) */
+  int32_t reserved;
+} o3s_icp_fitness;
+int o3s_icp_evaluate_resident(o3s_icp* h, const float T[16] /* nullable */, float max_correspondence_distance,
+                              o3s_icp_fitness* out);
+
 #ifdef __cplusplus
 }
 #endif

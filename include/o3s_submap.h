@@ -247,6 +247,39 @@ int o3s_submap_registration_ransac(const o3s_submap* source, const o3s_submap* t
                                    const o3s_ransac_params* params, o3s_ransac_result* result,
                                    int32_t* inlier_correspondences, int64_t* n_correspondences);
 
+/* ---- occupancy snapshot of the resident map and the overlap fitness: Submap::voxelMap_ (O3S/src/Submap.cpp:260-264) as the
+ * revisit check of SubmapCollection::isSwitchingSubmapsConsistant reads it (O3S/src/SubmapCollection.cpp:392-407, where the body
+ * is commented out; adjacency_based_revisiting_min_fitness, Parameters.hpp:108, is what its result is compared with).
+ * o3s_submap_build_voxel_map: voxelMap_.clear(); voxelMap_.insertCloud(mapCloud_) — the set of getVoxelIdx(p, 1 / voxel_size) keys
+ * (the reciprocal form, fp64, VoxelHashMap.hpp:43-51) of the map's CURRENT points, kept as a key-only open-addressing table in HBM
+ * (the check only asks whether a voxel is occupied).  Completes a pending insert first.  The reference builds it in
+ * Submap::computeFeatures at 2.5 x mapVoxelSize (Submap.cpp:239-240, magic.hpp:16).  voxel_size must be positive and finite.  A map
+ * point whose voxel index does not fit 21 bits per axis (beyond +-2^20 voxels) or is not a number names no voxel.
+ * Lifetime — the reference's: the snapshot describes the map as it was when it was built.  Inserts, carving, o3s_submap_upload and
+ * o3s_submap_transform leave it as built: Submap::transform (Submap.cpp:115-128) moves the map cloud and the feature cloud and does
+ * NOT move voxelMap_ — after a loop-closure correction the snapshot still speaks of the old frame until the next build.  The quirk is
+ * kept on purpose.  o3s_submap_clone copies it; o3s_submap_trim keeps it; o3s_submap_hand_over leaves it with the closed submap; a
+ * fresh submap has none.
+ * Threads: a build is a call that changes the submap — like every such call it may not run while another thread uses the same
+ * submap (the reference holds featureComputationMutex_ around computeFeatures).  Counts against one snapshot may run from several
+ * threads at once: each keeps its total in a word of its own; they are ordered on the submap's stream. */
+int o3s_submap_build_voxel_map(o3s_submap* m, double voxel_size);
+/* occupied voxels of the snapshot; -1: never built */
+int64_t o3s_submap_voxel_map_size(const o3s_submap* m);
+/* The body of isSwitchingSubmapsConsistant: for each of the N scan points (sensor frame, 3 x N host doubles) p' = mapToRangeSensor * p
+ * as an Eigen::Isometry3d product — fp64, no FMA, ((R0 x + R1 y) + R2 z) + t per row; only the rotation block and the translation of
+ * T_map_sensor are read — then its voxel key at the snapshot's voxel size, then a lookup.  *n_overlapping = points whose voxel is
+ * occupied (an integer total: order-free), *fitness = n_overlapping / N in fp64: NaN for N = 0, and 0 while the submap has no
+ * snapshot — what the reference's expression gives in both cases.  A point whose key lies outside the packable range (or is not a
+ * number) counts as not overlapping; it is not an error.  A T_map_sensor that is not finite: O3S_ERR_BAD_ARGUMENT. */
+int o3s_submap_overlap_fitness(const o3s_submap* m, const double* pts, int64_t N, const double T_map_sensor[16],
+                               int64_t* n_overlapping, double* fitness);
+/* The same over a RESIDENT pre-processed scan (o3s_scan.h) of the same device, read where it is; which: 0 = merge cloud — what
+ * SubmapCollection::insertScan passes as preProcessedScan —, 1 = match cloud.  Blocking: the scan may be refilled on return. */
+struct o3s_scan;
+int o3s_submap_overlap_fitness_scan(const o3s_submap* m, const struct o3s_scan* scan, int which, const double T_map_sensor[16],
+                                    int64_t* n_overlapping, double* fitness);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,17 @@ class IcpStatsC(C.Structure):
     ]
 
 
+class IcpFitnessC(C.Structure):   # o3s_icp_fitness
+    _fields_ = [
+        ("n_points", C.c_int64),
+        ("n_correspondences", C.c_int64),
+        ("fitness", C.c_double),
+        ("inlier_rmse", C.c_double),
+        ("gpu_ms", C.c_float),
+        ("reserved", C.c_int32),
+    ]
+
+
 # o3s_allreduce_fn(user, dev_ptr, byte_offset, count, dtype, hip_stream) -> 0 on success
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p)
 XCHG_INT32, XCHG_FLOAT64 = 0, 1
@@ -231,6 +242,7 @@ def load(variant: str | None = None) -> C.CDLL:
     L.o3s_icp_get_error_elements.restype = C.c_int64
     L.o3s_icp_get_last_step.argtypes = [vp, fp]
     L.o3s_icp_covariance_gpu_us.argtypes = [vp, dp]
+    L.o3s_icp_evaluate_resident.argtypes = [vp, fp, C.c_float, C.POINTER(IcpFitnessC)]
     if hasattr(L, "o3s_icp_hook_settled"):  # the hooks build: what its tests read back
         L.o3s_icp_hook_settled.argtypes = [vp, ip, ip, C.c_int32]
         L.o3s_icp_hook_sel_depth.argtypes = [vp, ip, C.c_int32]

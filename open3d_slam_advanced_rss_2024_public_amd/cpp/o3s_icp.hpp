@@ -68,6 +68,15 @@ class IcpHip {
     if (rc != O3S_OK) throw std::runtime_error("o3s_icp_get_covariance: no successful compute on this handle (status " + std::to_string(rc) + ")");
     return c;
   }
+  // Open3D's RegistrationResult (fitness_, inlier_rmse_) of the resident reading over the chain's own matcher
+  // (o3s_icp_evaluate_resident): T == nullptr evaluates where the last successful compute left the reading, a 4x4 column-major T what
+  // iteration 0 of a compute from it matches; maxCorrespondenceDistance 0 = the chain's maxDist.  What the health gate of
+  // Mapper.cpp:424-431 reads as result.fitness_.
+  o3s_icp_fitness evaluate(const float* T = nullptr, float maxCorrespondenceDistance = 0.f) {
+    o3s_icp_fitness f{};
+    raise(o3s_icp_evaluate_resident(h_, T, maxCorrespondenceDistance, &f));
+    return f;
+  }
   o3s_icp* handle() { return h_; }
 
  private:
@@ -163,6 +172,21 @@ class SubmapHip {
   }
   void download(double* points3xN, double* normals3xN) const {
     if (o3s_submap_download(m_, points3xN, normals3xN) != O3S_OK) throw std::runtime_error("o3s_submap_download failed");
+  }
+  // voxelMap_.clear(); voxelMap_.insertCloud(mapCloud_) (Submap.cpp:260-264) as an occupancy snapshot in HBM; returns its size
+  std::int64_t buildVoxelMap(double voxelSize) {
+    if (o3s_submap_build_voxel_map(m_, voxelSize) != O3S_OK) throw std::runtime_error("o3s_submap_build_voxel_map failed");
+    return o3s_submap_voxel_map_size(m_);
+  }
+  std::int64_t voxelMapSize() const { return o3s_submap_voxel_map_size(m_); }  // -1: never built
+  // the share of a resident scan's points (which: 0 merge cloud, 1 match cloud), moved by mapToRangeSensor, that fall into an
+  // occupied voxel of the snapshot (SubmapCollection.cpp:396-402); NaN for an empty scan, 0 without a snapshot
+  double overlapFitness(const o3s_scan* scan, int which, const double* mapToRangeSensor4x4, std::int64_t* nOverlapping = nullptr) const {
+    std::int64_t n = 0;
+    double f = 0.0;
+    if (o3s_submap_overlap_fitness_scan(m_, scan, which, mapToRangeSensor4x4, &n, &f) != O3S_OK) throw std::runtime_error("o3s_submap_overlap_fitness_scan failed");
+    if (nOverlapping) *nOverlapping = n;
+    return f;
   }
   o3s_submap* handle() { return m_; }
 

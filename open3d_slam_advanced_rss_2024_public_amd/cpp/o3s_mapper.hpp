@@ -18,6 +18,9 @@
 //                 icp_.initReference                                             -> o3s_submap_set_reference
 //   :393          icp_.compute(reading, {}, prior, false)                         -> o3s_icp_compute_resident
 //   :420-422      catch (std::runtime_error): keep the prior
+//   :424-431      the health gate (commented out in the reference, whose libpointmatcher result has no fitness_ left to test): when
+//                 isIgnoreMinRefinementFitness is off, a registration whose fitness (o3s_icp_evaluate_resident at the pose it
+//                 returned) is below minRefinementFitness gives the scan up: return false, nothing adopted, pushed or inserted
 //   :435          result cast back to double
 //   :440-455      isNewValueSetMapper_: adopt the GIVEN pose, skip this scan's result and the insert, ignore odometry next time
 //   :465-479      initial-map mode: no merging (or not before mapMergeDelayInSeconds_)
@@ -80,6 +83,11 @@ struct MapperParams {
   bool isMergeScansIntoMap = true;
   double mapMergeDelayInSeconds = 0.0;
   SubmapParams submaps;                              // submaps_ (Parameters.hpp:103-109): radius_, minNumRangeData_, ...
+  double minRefinementFitness = 0.7;                 // scanMatcher_.minRefinementFitness_ (Parameters.hpp:151; min_refinement_fitness)
+  // isIgnoreMinRefinementFitness_ (Parameters.hpp:167).  true = the reference as it runs: its flag defaults to false, but its gate is
+  // commented out (Mapper.cpp:424-431), so "ignore" is what it does
+  bool isIgnoreMinRefinementFitness = true;
+  double fitnessMaxCorrespondenceDistance = 0.0;     // the radius the fitness counts inliers within; 0 = the ICP chain's maxDist
 };
 
 class MapperHip {
@@ -149,6 +157,10 @@ class MapperHip {
   bool lastReferenceReset() const { return lastReferenceReset_; }
   bool lastIcpThrew() const { return lastIcpThrew_; }
   int lastIterations() const { return lastIterations_; }
+  // the fitness the health gate read on the last scan (fitness NaN: the gate is ignored, the scan never reached the registration,
+  // or the ICP threw), and whether it gave the scan up
+  const o3s_icp_fitness& lastFitness() const { return lastFitness_; }
+  bool lastFitnessRejected() const { return lastFitnessRejected_; }
   // covariance of the latest scan-to-map registration (IcpHip::getCovariance: zeros under the plain minimiser); NaN when that
   // registration failed and the prior was kept (Mapper.cpp:420-422), or before the first one
   const std::array<double, 36>& getLatestRegistrationCovariance() const { return lastCovariance_; }
@@ -186,7 +198,10 @@ class MapperHip {
     o3s_scan** ready;  // a scan object the caller has already pre-processed this sweep into
   };
   bool add(const Raw& raw, double timestamp) {
-    lastInserted_ = lastReferenceReset_ = lastIcpThrew_ = false;
+    lastInserted_ = lastReferenceReset_ = lastIcpThrew_ = lastFitnessRejected_ = false;
+    lastFitness_ = o3s_icp_fitness{};
+    lastFitness_.fitness = std::numeric_limits<double>::quiet_NaN();
+    bool haveFitness = false;
     lastTimings_ = MapperTimings{};
     if (!params_.isUseInitialMap && !isCalibrationSet_) return false;  // "Calibration is not set. Returning from mapping." (:169-174)
     scan_ = submaps_.scanForNextMeasurement();  // stays ours until submaps_.insertScan takes it into its overlap buffer
@@ -273,6 +288,10 @@ class MapperHip {
       lastIterations_ = st.iterations;
       if (rc != O3S_OK) throw std::runtime_error(o3s_last_error(icp_.handle()));  // every libpointmatcher exception derives from it
       lastCovariance_ = icp_.getCovariance();
+      if (!params_.isIgnoreMinRefinementFitness) {  // result.fitness_ of :425, inside the registration's stopwatch
+        lastFitness_ = icp_.evaluate(nullptr, (float)params_.fitnessMaxCorrespondenceDistance);
+        haveFitness = true;
+      }
       stamp(t0, lastTimings_.registrationMs, sumTimings_.registrationMs, 2);
     } catch (const std::runtime_error&) {
       // (a scan whose reading could not even be handed over: the reference would have looked at the patch first)
@@ -283,6 +302,11 @@ class MapperHip {
       // a compute that failed before it waited for its stream may leave the asynchronous index build / the reading's hand-over in
       // flight: nothing below may rewrite the buffers they read until the handle's stream has drained
       (void)o3s_icp_synchronize(icp_.handle());
+    }
+    // ---- health gate (:424-431): "Skipping the refinement step" ----
+    if (haveFitness && lastFitness_.fitness < params_.minRefinementFitness) {
+      lastFitnessRejected_ = true;
+      return false;
     }
     Mat4 corrected{};
     for (int k = 0; k < 16; ++k) corrected.m[k] = (double)corrected32[k];  // :435
@@ -377,7 +401,8 @@ class MapperHip {
   double lastMeasurementTimestamp_ = 0.0, lastReferenceInitializationTimestamp_ = 0.0, initTime_ = 0.0;
   bool haveLast_ = false, haveRef_ = false;  // haveLast_: lastMeasurementTimestamp_ holds a stamp (the reference leaves it default-constructed after the first scan, whose lookup would throw: no odometry prior is formed then)
   bool isNewValueSetMapper_ = false, isIgnoreOdometryPrediction_ = false;
-  bool lastInserted_ = false, lastReferenceReset_ = false, lastIcpThrew_ = false;
+  bool lastInserted_ = false, lastReferenceReset_ = false, lastIcpThrew_ = false, lastFitnessRejected_ = false;
+  o3s_icp_fitness lastFitness_{};
   std::array<double, 36> lastCovariance_ = nanCovariance();
   int lastIterations_ = 0;
   Mat4 calibrationInv_ = Mat4::identity();

@@ -6,14 +6,16 @@
 //   :86-92     insertBufferedScans: the buffered (pre-processed) scans go into the new active submap at their own poses
 //   :94-148    updateActiveSubmap: forced creation; minNumRangeData_ gate; localisation mode never switches; closest submap by
 //              centre; maxNumPoints_ forces a new submap at the NEXT scan; another submap within radius_: stay / switch when
-//              adjacent (isSwitchingSubmapsConsistant returns true, :392-407) / create when the active one is left behind;
-//              nobody within radius_: create
+//              adjacent and isSwitchingSubmapsConsistant (:392-407: the reference's body is commented out and returns true — here
+//              it is the written body when SubmapParams::isCheckSwitchingConsistency is on, true otherwise) / create when the
+//              active one is left behind; nobody within radius_: create
 //   :150-162   createNewSubmap (id, parent, origin)
 //   :164-174   findClosestSubmap (first minimum of the centre distances)
 //   :193-247   insertScan: buffer the scan; on a switch the scan
 //              still goes into the PREVIOUS submap, whose centre is then computed (Submap::computeSubmapCenter, Submap.cpp:
 //              282-286), it is queued as finished, an adjacency edge is added, the buffer is replayed into the new one
-//   computeFeatures(idx): Submap::computeFeatures (Submap.cpp:255-275) of a submap on the device (o3s_submap_compute_features);
+//   computeFeatures(idx): Submap::computeFeatures (Submap.cpp:255-275) of a submap on the device (o3s_submap_compute_features),
+//              and with it the occupancy snapshot voxelMap_ (:260-264) at 2.5 x mapVoxelSize (Submap.cpp:239-240, magic.hpp:16);
 //              the caller keeps the reference's timer (minSecondsBetweenFeatureComputation_) and decides when to call it.
 //   :324-375   transform: which increment goes to which submap (planSubmapTransforms, o3s_pose_graph.hpp), applied to all resident
 //              submaps by ONE o3s_submaps_transform call; per submap mapToRangeSensor_ * T, T * submapCenter_, the dense map where the
@@ -53,6 +55,11 @@ struct SubmapParams {            // o3d_slam::SubmapParameters (Parameters.hpp:1
   int minNumRangeData = 5;
   std::int64_t maxNumPoints = 400000;
   int numScansOverlap = 3;
+  // adjacency_based_revisiting_min_fitness (Parameters.hpp:108; 0.5 in the shipped lua files): what the share of scan points inside
+  // occupied voxels of the candidate submap must exceed before the active submap switches back to it
+  double adjacencyBasedRevisitingMinFitness = 0.4;
+  // off = the reference as it runs (isSwitchingSubmapsConsistant returns true); on = the body written at SubmapCollection.cpp:396-404
+  bool isCheckSwitchingConsistency = false;
 };
 
 // o3d_slam::AdjacencyMatrix (AdjacencyMatrix.cpp:16-71): the edges updateActiveSubmap asks about, and the loop-closure flags
@@ -200,8 +207,17 @@ class SubmapCollectionHip {
     o3s_submap_feature_params_default(&p);
     if (params) p = *params;
     if (o3s_submap_compute_features(submaps_.at(idx).map->handle(), &p) != O3S_OK) throw std::runtime_error("o3s_submap_compute_features failed");
+    if (voxel_ > 0.0) submaps_.at(idx).map->buildVoxelMap(kVoxelExpansionFactorAdjacencyBasedRevisiting * voxel_);  // Submap.cpp:260-264
     return o3s_submap_features_size(submaps_.at(idx).map->handle());
   }
+  // SubmapCollection::isSwitchingSubmapsConsistant (:392-407) as written in its commented body, over the resident merge cloud of
+  // `scan` (what insertScan passes as preProcessedScan).  A candidate without a snapshot has fitness 0; an empty scan NaN: both false.
+  bool isSwitchingSubmapsConsistant(const o3s_scan* scan, std::size_t newActiveSubmapCandidate, const double mapToRangeSensor[16]) {
+    lastSwitchFitness_ = submaps_.at(newActiveSubmapCandidate).map->overlapFitness(scan, 0, mapToRangeSensor);
+    return lastSwitchFitness_ > params_.adjacencyBasedRevisitingMinFitness;
+  }
+  // fitness of the last consistency check (NaN: none was made by the last insertScan)
+  double lastSwitchFitness() const { return lastSwitchFitness_; }
   const Entry& submap(std::size_t i) const { return submaps_.at(i); }
   SubmapHip& submapMap(std::size_t i) { return *submaps_.at(i).map; }
   const AdjacencyHip& adjacency() const { return adjacency_; }
@@ -287,12 +303,13 @@ class SubmapCollectionHip {
   // (Mapper.cpp:180-183) goes straight into activeSubmap(): that mode never switches submaps, so the buffer is never replayed.
   bool insertScan(o3s_scan* scan, const double mapToRangeSensor[16], double timestamp) {
     lastSwitched_ = false;
+    lastSwitchFitness_ = std::numeric_limits<double>::quiet_NaN();
     for (int k = 0; k < 16; ++k) mapToRangeSensor_[k] = mapToRangeSensor[k];
     const std::size_t prevActive = activeIdx_;
     // ":201 if (submaps_.empty())" never holds — the constructor has created submap 0 — so the first scan takes the general
     // path like every other: buffered, no switch before minNumRangeData_ scans, inserted into the active submap
     addScanToBuffer(scan, mapToRangeSensor, timestamp);  // :210
-    updateActiveSubmap();                                // :213
+    updateActiveSubmap(scan);                            // :213
     if (prevActive != activeIdx_) {                      // :216-239
       lastSwitched_ = true;
       const auto t0 = std::chrono::steady_clock::now();
@@ -402,7 +419,7 @@ class SubmapCollectionHip {
       if (dist3(p0, submaps_[i].mapToSubmapCenter()) < dist3(p0, submaps_[best].mapToSubmapCenter())) best = i;
     return best;
   }
-  void updateActiveSubmap() {  // :94-148
+  void updateActiveSubmap(const o3s_scan* scan) {  // :94-148
     const double* p0 = mapToRangeSensor_ + 12;
     if (isForceNewSubmapCreation_) {
       createNewSubmap(p0);
@@ -417,7 +434,8 @@ class SubmapCollectionHip {
     const bool isAnotherSubmapWithinRange = dist3(p0, submaps_[closest].mapToSubmapCenter()) < params_.radius;
     if (isAnotherSubmapWithinRange) {
       if (closest == active) return;
-      if (adjacency_.isAdjacent(submaps_[closest].id, submaps_[active].id)) {  // && isSwitchingSubmapsConsistant(...) == true
+      if (adjacency_.isAdjacent(submaps_[closest].id, submaps_[active].id) &&
+          (!params_.isCheckSwitchingConsistency || isSwitchingSubmapsConsistant(scan, closest, mapToRangeSensor_))) {  // :132-133
         activeIdx_ = closest;  // (insertScan retires the previous one once the closing scan is in)
       } else {
         const bool isTraveledSufficientDistance = dist3(p0, submaps_[active].mapToSubmapCenter()) > params_.radius;
@@ -428,6 +446,7 @@ class SubmapCollectionHip {
     }
   }
 
+  static constexpr double kVoxelExpansionFactorAdjacencyBasedRevisiting = 2.5;  // magic.hpp:16
   static constexpr std::int64_t kReserveLimit = 8000000;      // larger limits mean "no limit": the arrays then double as the map grows
   static constexpr std::int64_t kReserveScanPoints = 262144;  // the scan that takes the map over the limit (2 x a 64 x 2048 sweep)
   SubmapParams params_;
@@ -440,6 +459,7 @@ class SubmapCollectionHip {
   int numScansMergedInActiveSubmap_ = 0;
   bool isForceNewSubmapCreation_ = false, lastSwitched_ = false;
   double lastSwitchMs_[5] = {0, 0, 0, 0, 0}, lastCreateMs_ = 0.0;
+  double lastSwitchFitness_ = std::numeric_limits<double>::quiet_NaN();
   double mapToRangeSensor_[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   std::deque<Buffered> buffer_;
   std::vector<o3s_scan*> free_;

@@ -3003,6 +3003,75 @@ __global__ void __launch_bounds__(kBlock) k_cov_post(const double* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// registration fitness (o3s_icp_evaluate_resident): Open3D's fitness_ / inlier_rmse_ over the matcher's own output.  One pass
+// over the `pos` / `d2` streams a matcher launch has just left: a query counts when it has a match (pos != -1: a non-finite
+// query has none) whose fp32 squared distance is <= r2.  Per block an integer count and an fp64 sum of the promoted distances
+// (thread-strided, then BlockSum: a fixed order); k_fit_post folds the blocks in block order and posts.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int kFitPPT = 2;          // points per lane per trip
+constexpr int kFitMaxBlocks = 256;  // one trip of the whole grid covers kFitMaxBlocks x kBlock x kFitPPT = 131 072 points
+__global__ void __launch_bounds__(kBlock) k_fit(const int32_t* __restrict__ pos, const float* __restrict__ d2, int N, float r2,
+                                                double* __restrict__ part_sum /*[grid]*/, unsigned long long* __restrict__ part_cnt /*[grid]*/) {
+  using Sum = BlockSum<1, kBlock>;
+  __shared__ double s_a[Sum::kWordsA];
+  __shared__ double s_b[Sum::kWordsB];
+  __shared__ uint32_t s_cnt[kBlock / 64];
+  double acc[1] = {0.0};
+  uint32_t cnt = 0u;
+  for (int base = blockIdx.x * (kBlock * kFitPPT) + threadIdx.x; base < N; base += gridDim.x * (kBlock * kFitPPT)) {
+    int pe[kFitPPT];
+    float d[kFitPPT];
+#pragma unroll
+    for (int u = 0; u < kFitPPT; ++u) {  // both loads of a trip in flight together
+      const int i = base + u * kBlock;
+      pe[u] = i < N ? pos[i] : -1;
+      d[u] = i < N ? d2[i] : kInfF;
+    }
+#pragma unroll
+    for (int u = 0; u < kFitPPT; ++u)
+      if (pe[u] != -1 && d[u] <= r2) {
+        cnt += 1u;
+        acc[0] += (double)d[u];
+      }
+  }
+  cnt = wave_sum_u32(cnt);
+  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
+  Sum::run(acc, s_a, s_b);  // (its barriers also publish s_cnt)
+  if (threadIdx.x == 0) {
+    unsigned long long c = 0ull;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) c += s_cnt[w];
+    part_cnt[blockIdx.x] = c;
+    part_sum[blockIdx.x] = Sum::total(s_b, 0);
+  }
+}
+// One wave: lane l adds the partials of blocks l, l + 64, ... in order, then the wave's tree — the order is a function of the
+// number of blocks alone.  Lane 0 posts {count, sum, the matcher launch's start stamp, now} (host_post.h) and leaves them in `out`
+// for a host whose posts are switched off.
+__global__ void __launch_bounds__(64) k_fit_post(const double* __restrict__ part_sum, const unsigned long long* __restrict__ part_cnt, int nb,
+                                                 const IcpState* __restrict__ st, double* __restrict__ out /*[4]*/, uint32_t* __restrict__ mailbox,
+                                                 uint32_t seq) {
+  double s = 0.0;
+  unsigned long long c = 0ull;
+  for (int b = threadIdx.x; b < nb; b += 64) {
+    s += part_sum[b];
+    c += part_cnt[b];
+  }
+  s = wave_sum(s);
+  c = wave_sum_u64(c);
+  if (threadIdx.x == 0) {
+    double v[4];  // 8-byte values, the integers as bit patterns
+    v[0] = __longlong_as_double((long long)c);
+    v[1] = s;
+    v[2] = __longlong_as_double((long long)st->t_begin);
+    v[3] = __longlong_as_double((long long)wall_clock64());
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[k] = v[k];
+    host_post::post(mailbox, seq, host_post::kPostVals, v);
+  }
+}
+
 // o3s_icp_get_error_elements: every slot's centred pair of the last iteration and whether it was kept (diagnostics)
 __global__ void __launch_bounds__(kBlock) k_cov_elements(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz, int N,
                                                          const float4* __restrict__ mq, const float4* __restrict__ mn, const int32_t* __restrict__ pos,

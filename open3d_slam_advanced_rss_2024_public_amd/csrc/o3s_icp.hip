@@ -61,6 +61,7 @@ struct DevBuf {
 
 struct HostStage {  // pinned staging block for small H2D / D2H transfers
   IcpState state;
+  IcpState eval_state;  // o3s_icp_evaluate_resident's own: `state` keeps what the last compute left (o3s_icp_host_split reads it)
   float T0[16];
   double ref_part[1024 * 3];  // init_reference: per-block sums and bounds of k_ref_stats (a pageable landing area costs a
   float ref_bb[1024 * 6];     // staged round trip per copy)
@@ -69,6 +70,7 @@ struct HostStage {  // pinned staging block for small H2D / D2H transfers
 
 constexpr int kNumKernels = 5;
 constexpr size_t kCovBufBytes = ((size_t)kMaxPartialBlocks * kCovComps + kCovComps + 3) * sizeof(double);  // k_cov's partials [42][blocks], the 42 totals + 2 stamps, k_cov's start
+static_assert(kCovBufBytes >= (2 * (size_t)kern::kFitMaxBlocks + 4) * sizeof(double), "k_fit's block partials and its four totals fit the covariance pass's area");
 constexpr size_t kHistWords = (size_t)kHistReplicas * kHistBins + 1024;  // level-1 replicas + the level-2 histogram right behind them
 // hooks build: per-iteration traces behind the speculative histograms — the depth k_classify resolved, then the matcher's two
 // counters of settled queries (certificate held | the wave skipped its search) in kHistReplicas copies: one atomic per wave onto
@@ -159,6 +161,11 @@ struct o3s_icp {
   float last_max_out_r2 = 0.f;  // the kept-pair predicate's MaxDist bound of that compute
   float last_step[16] = {0};    // ... and its last iteration's step (IcpState::dT)
   unsigned long long cov_t_start = 0, cov_t_end = 0;  // wall_clock64 stamps of the last covariance pass (k_cov's start, k_cov_post's end)
+  // registration fitness (o3s_icp_evaluate_resident): where the last successful compute left the reading.  pose_valid: that compute's
+  // T_iter is in last_T_iter and nothing has replaced the reading or the reference since; r_is_call: d_r still holds the reading as
+  // that compute prepared it (T0 . p in its processing order) — an evaluation at an explicit pose prepares it anew
+  bool pose_valid = false, r_is_call = false;
+  float last_T_iter[16] = {0};
   HostStage* stage = nullptr;                // pinned
   // mailbox (host_post.h): init_reference's two read-backs without a copy or a stream synchronisation
   host_post::PostBlock<> mb;
@@ -360,7 +367,9 @@ int wait_post(o3s_icp* h, uint32_t seq, hipEvent_t drained, bool* done) {
 int init_reference_impl(o3s_icp* h, const float4* d_xyzw, const float* d_normals, int64_t M, bool wait_end = true, bool center = true,
                         const uint32_t* d_count = nullptr, int64_t* M_out = nullptr) {
   h->ref_ready = false;
-  h->elements_valid = false;
+  // what a compute left speaks of the reference this call replaces: the reading in d_r and T_iter are centred on ITS mean, the
+  // incumbents in d_mq are ITS points (no bound of anything in the new index)
+  h->elements_valid = h->pose_valid = h->r_is_call = false;
   if (M_out) *M_out = 0;
   if (M <= 0) return fail(h, O3S_ERR_EMPTY_REFERENCE, "reference cloud is empty");
   if (M > (int64_t)0x7fffffff) return fail(h, O3S_ERR_BAD_ARGUMENT, "reference larger than 2^31-1 points");
@@ -949,7 +958,7 @@ int issue_segment(o3s_icp* h, Call& c, bool capturing = false) {
 int start_call(o3s_icp* h, const float* T_init) {
   Call& c = h->call;
   c.live = false;
-  h->cov_valid = h->elements_valid = false;
+  h->cov_valid = h->elements_valid = h->pose_valid = false;
 #ifdef O3S_TEST_HOOKS
   h->looks.clear();
 #endif
@@ -1300,6 +1309,8 @@ int compute_finish(o3s_icp* h, float* T_out, o3s_icp_stats* stats) {
     std::memset(h->cov, 0, sizeof(h->cov));  // ErrorMinimizer::getCovariance of the base class (LPM/ErrorMinimizer.cpp:266-270)
   }
   h->cov_valid = h->elements_valid = true;
+  std::memcpy(h->last_T_iter, st.T_iter, sizeof(st.T_iter));
+  h->pose_valid = h->r_is_call = true;
   std::memcpy(T_out, out, sizeof(out));
   return O3S_OK;
 }
@@ -1312,7 +1323,7 @@ int compute_impl(o3s_icp* h, const float* T_init, float* T_out, o3s_icp_stats* s
 
 int upload_reading(o3s_icp* h, const float* xyzw, const float* normals, int64_t N) {
   h->reading_ready = false;
-  h->elements_valid = false;
+  h->elements_valid = h->pose_valid = false;
   h->ext_xyzw = h->ext_n = nullptr;
   if (N <= 0) {
     h->N = 0;
@@ -1626,7 +1637,7 @@ int o3s_icp_set_reading(o3s_icp* h, const float* xyzw, const float* normals, int
 int o3s_icp_set_reading_dev(o3s_icp* h, const void* d_xyzw, const void* d_normals, int64_t N) {
   if (!h) return O3S_ERR_BAD_ARGUMENT;
   h->reading_ready = false;
-  h->elements_valid = false;
+  h->elements_valid = h->pose_valid = false;
   if (N <= 0) {
     h->N = 0;
     return fail(h, O3S_ERR_EMPTY_READING, "the reading point cloud is empty");
@@ -1845,6 +1856,78 @@ int o3s_icp_profile_match(o3s_icp* h, const float T_iter[16], int32_t reps, int3
   *avg_ms = ms / (float)reps;
   HIP_TRY(h, hipMemsetAsync(h->d_hist.p, 0, kHistWords * 4, h->stream));  // the launches left counts behind
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return O3S_OK;
+}
+
+// Open3D's registration result (fitness_, inlier_rmse_) over the chain's own matcher: one matcher launch on a state with done = 0
+// and the evaluation pose, then k_fit + k_fit_post over the pos / d2 streams it left, and one host post.
+// Exactness.  launch_match_any passes no certificate array, so the launch is the kernel without certificates: every finite query is
+// searched; what it reads of earlier launches is the incumbent d_mq[i], a reference POINT, whose distance under the pose of THIS
+// launch only bounds the search from above — true for any pose.  T == NULL keeps the incumbents the last launch of the compute left
+// (or an evaluation since: points of the same reference all the same; a new reference retires the pose, init_reference_impl).  An
+// explicit T prepares the reading anew with the reset a compute makes (incumbents wiped) and matches what iteration 0 of that
+// compute matches — on the main index, where a chain's iteration 0 may search the first-iteration index: both searches are exact.
+int o3s_icp_evaluate_resident(o3s_icp* h, const float T[16], float max_correspondence_distance, o3s_icp_fitness* out) {
+  if (!h || !out) return O3S_ERR_BAD_ARGUMENT;
+  std::memset(out, 0, sizeof(*out));
+  const float r = max_correspondence_distance;
+  if (!(r >= 0.f) || r > h->cfg.max_dist) return fail(h, O3S_ERR_BAD_ARGUMENT, "evaluate: max_correspondence_distance must be in [0, max_dist]");
+  if (h->shard.active) return fail(h, O3S_ERR_BAD_CONFIG, "the registration fitness is not available in the sharded mode");
+  if (!h->ref_ready) return fail(h, O3S_ERR_NOT_INITIALIZED, "evaluate before a successful init_reference");
+  if (h->call.live) return fail(h, O3S_ERR_BAD_ARGUMENT, "evaluate between compute_resident_launch and compute_resident_finish");
+  // (in front of the reading's check: a new reference also retires the resident reading, and T = NULL then asks for a pose that is gone)
+  if (!T && !h->pose_valid) return fail(h, O3S_ERR_NOT_INITIALIZED, "evaluate(T = NULL) needs a successful compute on this reading and reference");
+  if (!h->reading_ready || h->N <= 0) return fail(h, O3S_ERR_EMPTY_READING, "evaluate needs a resident reading");
+  if (h->cfg.matcher == 1 && (int64_t)h->N > h->M) return fail(h, O3S_ERR_BAD_SHAPE, "MirrorMatcher needs reading size <= reference size");
+  HIP_TRY(h, hipSetDevice(h->device));
+  const int N = h->N;
+  int rc = ensure_iteration_buffers(h, N);
+  if (rc != O3S_OK) return rc;
+  HIP_TRY(h, h->d_cov.ensure(kCovBufBytes));  // the block partials share the covariance pass's area (its results are on the host)
+  const ChainParams cp = make_chain(h, h->read_has_normals);
+  const bool sort = h->cfg.sort_queries != 0 && h->cfg.matcher == 0 && !h->reading_presorted;
+  IcpState& st0 = h->stage->eval_state;
+  init_state(st0);
+  const bool fresh = T != nullptr || !h->r_is_call;  // the reading is prepared here: the launch is a first-iteration one
+  if (T) {  // T_refMean_readMean as start_call forms it
+    float TcInv[16], T0[16];
+    hidentity(TcInv);
+    for (int d = 0; d < 3; ++d) HM4(TcInv, d, 3) = -h->mean[d];
+    hmul4(TcInv, T, T0);
+    if (!hrigid(T0)) return fail(h, O3S_ERR_NOT_RIGID, "RigidTransformation: rotation matrix is not orthogonal (evaluation pose)");
+    h->r_is_call = false;
+    rc = prepare_reading(h, T0, sort, /*reset_chain=*/true, false);
+  } else {
+    if (!h->r_is_call) rc = prepare_reading(h, h->call.T0, sort, /*reset_chain=*/true, false);
+    if (rc == O3S_OK) h->r_is_call = true;
+    std::memcpy(st0.T_iter, h->last_T_iter, sizeof(st0.T_iter));
+  }
+  if (rc != O3S_OK) return rc;
+  h->elements_valid = false;  // the state and the match streams are replaced below
+  HIP_TRY(h, hipMemcpyAsync(h->d_state.p, &st0, sizeof(IcpState), hipMemcpyHostToDevice, h->stream));
+  const ChainArgs a = chain_args(h, cp);
+  launch_match_any(h, a, cp, false, h->stream, /*first=*/fresh);
+  const float r2 = r > 0.f ? r * r : h->grid.max_r2;
+  const int nb = std::min(kern::kFitMaxBlocks, nblocks(N, kern::kBlock * kern::kFitPPT));
+  double* part_sum = h->d_cov.as<double>();
+  unsigned long long* part_cnt = reinterpret_cast<unsigned long long*>(part_sum + kern::kFitMaxBlocks);
+  double* totals = part_sum + 2 * kern::kFitMaxBlocks;
+  hipLaunchKernelGGL(kern::k_fit, dim3(nb), dim3(kern::kBlock), 0, h->stream, h->d_pos.as<int32_t>(), h->d_d2.as<float>(), N, r2, part_sum, part_cnt);
+  const uint32_t seq = h->cov_mb.next();
+  hipLaunchKernelGGL(kern::k_fit_post, dim3(1), dim3(64), 0, h->stream, part_sum, part_cnt, nb, h->d_state.as<IcpState>(), totals, h->cov_mb.dev, seq);
+  HIP_TRY(h, hipGetLastError());
+  double v[4];
+  const int w = host_post::fetch_post(h->cov_mb, seq, h->stream, reinterpret_cast<uint32_t*>(v), 8, host_post::kPostVals, totals);
+  if (w == host_post::kPollError) return fail(h, O3S_ERR_HIP, "evaluate: the kernels failed");
+  unsigned long long cnt, t0, t1;
+  std::memcpy(&cnt, &v[0], 8);
+  std::memcpy(&t0, &v[2], 8);
+  std::memcpy(&t1, &v[3], 8);
+  out->n_points = N;
+  out->n_correspondences = (int64_t)cnt;
+  out->fitness = (double)cnt / (double)N;
+  out->inlier_rmse = cnt ? std::sqrt(v[1] / (double)cnt) : 0.0;
+  out->gpu_ms = t1 > t0 ? (float)((double)(t1 - t0) / h->wall_clock_khz) : 0.f;
   return O3S_OK;
 }
 

@@ -531,3 +531,222 @@ int o3s_o3d_registration_icp_submaps_overlap_batch_ex(int32_t n, const o3s_subma
 }
 
 }  // extern "C"
+
+// ---- occupancy snapshot of a resident submap and the overlap fitness (include/o3s_submap.h) ---------------------------------------
+// Submap::voxelMap_ as the revisit check reads it (Submap.cpp:260-264, SubmapCollection.cpp:392-407): only WHETHER a voxel holds a
+// map point matters, so the snapshot is a key-only open-addressing table (packed key + 1, 0 = empty; dm_pack, ov_hash) that stays in
+// HBM with the submap.  Keys are getVoxelIdx in the reciprocal form, the arithmetic of k_ov_keys.
+namespace {
+namespace o3s_cloud {
+
+__device__ __forceinline__ uint64_t vm_key(double x, double y, double z, double inv) {  // kDmEmpty: NaN or beyond the packable range
+  const double fx = floor(x * inv), fy = floor(y * inv), fz = floor(z * inv);
+  return (dm_in_range(fx) && dm_in_range(fy) && dm_in_range(fz)) ? dm_pack((int32_t)fx, (int32_t)fy, (int32_t)fz) : kDmEmpty;
+}
+
+// Inserts the voxel of every point.  The lanes of a wave that share the voxel of its first lane are served by that lane (a map in
+// voxel order: whole waves fall into one voxel and make one compare-and-swap); every other lane inserts its own key, all of them at
+// once (serving one distinct key after the other, as k_ov_count does for its per-voxel counts, was 64 dependent round trips per wave
+// on a map in any other order: 2 ms for 0.4 M points).  cnt[0] += voxels this launch made, cnt[1] = 1 when a key found no slot
+// within max_probe steps (the table is too small: the host repeats the build with room for one voxel per point at half load).
+__global__ void __launch_bounds__(kB) k_vm_insert(const double* __restrict__ pts, int64_t N, double inv, unsigned long long* __restrict__ tab,
+                                                  uint32_t mask, uint32_t max_probe, uint32_t* __restrict__ cnt) {
+  const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63);
+  const uint64_t k = i < N ? vm_key(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], inv) : kDmEmpty;
+  bool pending = k != kDmEmpty;
+  const unsigned long long open = __ballot(pending);
+  if (!open) return;  // (uniform)
+  const int leader = __ffsll((long long)open) - 1;
+  const uint64_t lk = ((uint64_t)(uint32_t)__shfl((int)(k >> 32), leader) << 32) | (uint64_t)(uint32_t)__shfl((int)(k & 0xffffffffu), leader);
+  if (lane != leader && k == lk) pending = false;
+  if (!pending) return;
+  const unsigned long long k1 = k + 1ull;
+  uint32_t h = ov_hash(k1) & mask;
+  for (uint32_t probe = 0; probe < max_probe; ++probe) {
+    const unsigned long long prev = atomicCAS(&tab[h], 0ull, k1);
+    if (prev == 0ull) atomicAdd(&cnt[0], 1u);  // exactly one lane of the whole launch makes a voxel's entry
+    if (prev == 0ull || prev == k1) return;
+    h = (h + 1u) & mask;
+  }
+  cnt[1] = 1u;
+}
+
+// p' = R p + t as an isometry product — fp64, no FMA (the TU is compiled with -ffp-contract=off), ((R0 x + R1 y) + R2 z) + t — then
+// key, then lookup.  One ballot per wave, one integer add per wave: the total does not depend on any order.
+struct Iso3d {
+  double r[9];  // row-major
+  double t[3];
+};
+__global__ void __launch_bounds__(kB) k_vm_count(const double* __restrict__ pts, int64_t N, Iso3d T, double inv,
+                                                 const unsigned long long* __restrict__ tab, uint32_t mask, uint32_t* __restrict__ total) {
+  const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
+  bool hit = false;
+  if (i < N) {
+    const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+    double q[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      double s = T.r[3 * a] * x;
+      s = s + T.r[3 * a + 1] * y;
+      s = s + T.r[3 * a + 2] * z;
+      q[a] = s + T.t[a];
+    }
+    const uint64_t k = vm_key(q[0], q[1], q[2], inv);
+    if (k != kDmEmpty) {
+      const unsigned long long k1 = k + 1ull;
+      uint32_t h = ov_hash(k1) & mask;
+      for (uint32_t probe = 0; probe <= mask; ++probe) {  // (the table is never full: an empty slot ends every miss)
+        const unsigned long long v = tab[h];
+        if (v == k1) hit = true;
+        if (v == k1 || v == 0ull) break;
+        h = (h + 1u) & mask;
+      }
+    }
+  }
+  const unsigned long long b = __ballot(hit);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(total, (uint32_t)__popcll(b));
+}
+// hands `n` counter words to the host (host_post.h)
+__global__ void __launch_bounds__(64) k_vm_post(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ mailbox, uint32_t seq) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const uint32_t v[2] = {cnt[0], cnt[1]};
+  post(mailbox, seq, kPostVals, v);
+}
+inline int vm_fetch(const uint32_t* d_cnt, uint32_t out[2], hipStream_t s) {
+  PinnedArea& pa = pinned_area();
+  const uint32_t seq = mailbox_open(pa);
+  if (seq) {
+    hipLaunchKernelGGL(k_vm_post, dim3(1), dim3(64), 0, s, d_cnt, pa.mb.dev, seq);
+    CK(hipGetLastError());
+  }
+  return fetch_post(pa.mb, seq, s, out, 2, kPostVals, d_cnt, pinned_words()) == kPollError ? O3S_ERR_HIP : O3S_OK;
+}
+// The count's total lives in a word of the CALLING THREAD's own (per device; 16 bytes, made on first use and never freed: a
+// thread_local destructor could run behind the runtime's own exit): the submap is const here, and two threads that count against
+// one snapshot at the same time — the mapping thread's revisit check, a worker's — must not share a counter.
+inline uint32_t* vm_thread_counter(int device) {
+  static thread_local std::vector<uint32_t*> per_device;
+  if ((size_t)device >= per_device.size()) per_device.resize((size_t)device + 1, nullptr);
+  if (!per_device[(size_t)device] && hipMalloc(reinterpret_cast<void**>(&per_device[(size_t)device]), 16) != hipSuccess) per_device[(size_t)device] = nullptr;
+  return per_device[(size_t)device];
+}
+constexpr uint32_t kVmMaxProbe = 256;  // a first-size table that makes a key walk further is given up for the full-size one
+
+// counts the points of a device cloud that fall into an occupied voxel of m's snapshot; everything is enqueued on m's stream
+int vm_count_dev(const o3s_submap* m, const double* d_pts, int64_t N, const double* T, int64_t* n_overlapping) {
+  hipStream_t s = m->stream;
+  Iso3d iso;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) iso.r[3 * r + c] = T[4 * c + r];
+    iso.t[r] = T[12 + r];
+  }
+  uint32_t* d_total = vm_thread_counter(m->device);  // (the device is current: set_dev)
+  if (!d_total) return O3S_ERR_HIP;
+  CK(hipMemsetAsync(d_total, 0, 8, s));
+  hipLaunchKernelGGL(k_vm_count, dim3(nblk(N)), dim3(kB), 0, s, d_pts, N, iso, 1.0 / m->vox_size,
+                     reinterpret_cast<const unsigned long long*>(m->vox_tab.p), m->vox_slots - 1u, d_total);
+  CK(hipGetLastError());
+  uint32_t r[2] = {0, 0};
+  const int rc = vm_fetch(d_total, r, s);
+  if (rc != O3S_OK) return rc;
+  *n_overlapping = (int64_t)r[0];
+  return O3S_OK;
+}
+// the shared front of the two entry points: 1 = answered without the device (no points, or no snapshot), 0 = count, else an error
+int vm_count_front(const o3s_submap* m, int64_t N, const double* T, int64_t* n_overlapping, double* fitness) {
+  if (!m || !T || !n_overlapping || !fitness || N < 0 || N > (int64_t)0x7fffffff) return O3S_ERR_BAD_ARGUMENT;
+  for (int k = 0; k < 16; ++k)
+    if (!std::isfinite(T[k])) return O3S_ERR_BAD_ARGUMENT;
+  *n_overlapping = 0;
+  // static_cast<double>(numOverlappingPoints) / scan.points_.size(): 0 / 0 for an empty scan, 0 / N over an empty voxel map
+  *fitness = N == 0 ? std::numeric_limits<double>::quiet_NaN() : 0.0;
+  return (N == 0 || m->n_vox <= 0) ? 1 : 0;
+}
+
+}  // namespace o3s_cloud
+}  // namespace
+
+extern "C" {
+
+int o3s_submap_build_voxel_map(o3s_submap* m, double voxel_size) {
+  using namespace o3s_cloud;
+  if (const int rs_ = submap_settle(m); rs_ != O3S_OK) return rs_;  // a pending insert is completed first
+  if (!m || !(voxel_size > 0.0) || !std::isfinite(voxel_size)) return O3S_ERR_BAD_ARGUMENT;
+  if (m->n > (int64_t)0x3fffffff) return O3S_ERR_BAD_ARGUMENT;
+  const int rc = set_dev(m);
+  if (rc != O3S_OK) return rc;
+  hipStream_t s = m->stream;
+  const uint32_t full = ov_slots_for(m->n);
+  // the first table: 2^16 slots, or room for one voxel per four points at half load when that is more (a 0.4 M-point map at
+  // 2.5 x its voxel size holds 77 k voxels: a first table they do not fit is filled to its probe limit and thrown away — 0.9 ms)
+  uint32_t slots = std::min(std::max(kOvFirstSlots, ov_slots_for(m->n / 4)), full);
+  m->n_vox = -1;  // (a failed build leaves no snapshot)
+  for (;;) {
+    CK(m->vox_tab.ensure(((size_t)slots + 1) * 8, 0, s));
+    unsigned long long* tab = reinterpret_cast<unsigned long long*>(m->vox_tab.p);
+    uint32_t* cnt = reinterpret_cast<uint32_t*>(tab + slots);
+    CK(hipMemsetAsync(tab, 0, ((size_t)slots + 1) * 8, s));
+    uint32_t r[2] = {0, 0};
+    if (m->n > 0) {
+      // the full-size table holds at most one voxel per point at half load: every key finds a slot
+      hipLaunchKernelGGL(k_vm_insert, dim3(nblk(m->n)), dim3(kB), 0, s, (const double*)m->pts[m->cur].d(), m->n, 1.0 / voxel_size, tab, slots - 1u,
+                         slots == full ? slots : std::min(slots, kVmMaxProbe), cnt);
+      CK(hipGetLastError());
+      if (const int rf = vm_fetch(cnt, r, s); rf != O3S_OK) return rf;
+    }
+    // the first table filled up, or past half load (lookups of absent keys would walk long runs): once more at full size
+    if ((r[1] || 2 * (uint64_t)r[0] > slots) && slots < full) {
+      slots = full;
+      continue;
+    }
+    if (r[1]) return O3S_ERR_HIP;
+    m->vox_slots = slots;
+    m->vox_size = voxel_size;
+    m->n_vox = (int64_t)r[0];
+    return O3S_OK;
+  }
+}
+
+int64_t o3s_submap_voxel_map_size(const o3s_submap* m) { return m ? m->n_vox : -1; }
+
+int o3s_submap_overlap_fitness(const o3s_submap* m, const double* pts, int64_t N, const double T_map_sensor[16], int64_t* n_overlapping,
+                               double* fitness) {
+  using namespace o3s_cloud;
+  const int f = vm_count_front(m, N, T_map_sensor, n_overlapping, fitness);
+  if (f != 0) return f == 1 ? O3S_OK : f;
+  if (!pts) return O3S_ERR_BAD_ARGUMENT;
+  int rc = set_dev(m);
+  if (rc != O3S_OK) return rc;
+  Buf d_p;
+  CK(d_p.alloc((size_t)N * 24));
+  CK(hipMemcpyAsync(d_p.p, pts, (size_t)N * 24, hipMemcpyHostToDevice, m->stream));
+  rc = vm_count_dev(m, d_p.as<double>(), N, T_map_sensor, n_overlapping);
+  if (rc != O3S_OK) return rc;
+  CK(hipStreamSynchronize(m->stream));  // (the post may be ahead of the kernel's retirement: the buffer goes now)
+  *fitness = (double)*n_overlapping / (double)N;
+  return O3S_OK;
+}
+
+int o3s_submap_overlap_fitness_scan(const o3s_submap* m, const o3s_scan* scan, int which, const double T_map_sensor[16], int64_t* n_overlapping,
+                                    double* fitness) {
+  using namespace o3s_cloud;
+  if (!scan || (which != 0 && which != 1)) return O3S_ERR_BAD_ARGUMENT;
+  const int64_t N = which == 0 ? scan->n_wide : scan->n_narrow;
+  const int f = vm_count_front(m, N, T_map_sensor, n_overlapping, fitness);
+  if (f != 0) return f == 1 ? O3S_OK : f;
+  if (m->device != scan->device) return O3S_ERR_BAD_ARGUMENT;
+  int rc = set_dev(m);
+  if (rc != O3S_OK) return rc;
+  if (scan->stream != m->stream) {  // the scan's clouds are complete before the count reads them
+    CK(hipEventRecord(scan->handover, scan->stream));
+    CK(hipStreamWaitEvent(m->stream, scan->handover, 0));
+  }
+  rc = vm_count_dev(m, (which == 0 ? scan->wide_p : scan->narrow_p).d(), N, T_map_sensor, n_overlapping);
+  if (rc != O3S_OK) return rc;
+  CK(hipStreamSynchronize(m->stream));  // the scan may be refilled when this returns
+  *fitness = (double)*n_overlapping / (double)N;
+  return O3S_OK;
+}
+
+}  // extern "C"

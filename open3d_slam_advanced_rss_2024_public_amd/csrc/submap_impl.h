@@ -325,6 +325,13 @@ struct o3s_submap {
   DArr feat_p, feat_n, feat_f;
   int64_t n_feat = -1;
   FpfhWork feat_w;  // grid, neighbour lists and SPFH of the last computation (given back by o3s_submap_trim)
+  // the occupancy snapshot of o3s_submap_build_voxel_map (Submap::voxelMap_): an open-addressing table of packed voxel keys + 1
+  // (0: empty), vox_slots of them (a power of two); n_vox = distinct voxels, -1: never built.  Like the feature set it describes the
+  // map as it was when it was built: inserts, carving and o3s_submap_transform leave it alone (overlap_impl.h)
+  DArr vox_tab;
+  int64_t n_vox = -1;
+  uint32_t vox_slots = 0;
+  double vox_size = 0.0;
 };
 
 namespace {
@@ -471,6 +478,16 @@ int o3s_submap_clone(const o3s_submap* src, int device, o3s_submap** out) {
     if (hipStreamSynchronize(s) != hipSuccess) return fail(O3S_ERR_HIP);
   }
   m->n_feat = src->n_feat;
+  if (src->n_vox >= 0) {  // ... and so does the occupancy snapshot
+    const size_t b = (size_t)src->vox_slots * 8;
+    bool ok = m->vox_tab.ensure(b + 8, 0, s) == hipSuccess;  // (+ the counter word behind the slots)
+    if (ok) ok = (m->device == src->device ? hipMemcpyAsync(m->vox_tab.p, src->vox_tab.p, b, hipMemcpyDeviceToDevice, s)
+                                           : hipMemcpyPeerAsync(m->vox_tab.p, m->device, src->vox_tab.p, src->device, b, s)) == hipSuccess;
+    if (!ok || hipStreamSynchronize(s) != hipSuccess) return fail(O3S_ERR_HIP);
+    m->vox_slots = src->vox_slots;
+    m->vox_size = src->vox_size;
+  }
+  m->n_vox = src->n_vox;
   return O3S_OK;
 }
 
@@ -624,6 +641,7 @@ int64_t o3s_submap_device_bytes(const o3s_submap* m) {
   size_t b = m->arena.cap;
   for (int k = 0; k < 2; ++k) b += m->pts[k].cap + m->nrm[k].cap + m->col[k].cap;
   b += m->scan_p.cap + m->scan_n.cap + m->scan_c.cap + m->carve_scan.cap + m->d_T.cap + m->patch_xyzw.cap + m->patch_n32.cap;
+  b += m->vox_tab.cap;
   b += m->feat_p.cap + m->feat_n.cap + m->feat_f.cap + m->feat_w.grid.arena.cap + m->feat_w.grid.cells_cap + m->feat_w.idx.cap + m->feat_w.d2.cap +
        m->feat_w.spfh.cap;
   return (int64_t)b;

@@ -175,6 +175,16 @@ class IcpConfig:
 
 
 @dataclass
+class IcpFitness:
+    """o3s_icp_fitness: Open3D's RegistrationResult fitness_ / inlier_rmse_ over the chain's own matcher."""
+    n_points: int = 0
+    n_correspondences: int = 0
+    fitness: float = 0.0
+    inlier_rmse: float = 0.0
+    gpu_ms: float = 0.0
+
+
+@dataclass
 class IcpStats:
     iterations: int = 0
     max_iters_reached: bool = False
@@ -401,6 +411,16 @@ class ICP:
             self._check(rc)
             return _from_colmajor(Tout)
         return self._finish(rc, st, Tout)
+
+    def evaluate(self, T=None, max_correspondence_distance: float = 0.0) -> IcpFitness:
+        """o3s_icp_evaluate_resident: the share of the resident reading whose nearest reference point lies within
+        `max_correspondence_distance` (0: the chain's max_dist) and the RMSE of those distances.  T None: where the last successful
+        compute left the reading; a 4x4 T: what iteration 0 of compute_resident(T) matches."""
+        out = _lib.IcpFitnessC()
+        Tin = None if T is None else _colmajor(T)
+        rc = self._L.o3s_icp_evaluate_resident(self._h, _fp(Tin), float(max_correspondence_distance), C.byref(out))
+        self._check(rc)
+        return IcpFitness(int(out.n_points), int(out.n_correspondences), float(out.fitness), float(out.inlier_rmse), float(out.gpu_ms))
 
     def get_covariance(self) -> np.ndarray:
         """icp.errorMinimizer->getCovariance() of the last successful compute (o3s_icp_get_covariance): 6 x 6 float64 in the

@@ -63,6 +63,14 @@ class Mapper:
         self.pose_buffer = TransformBuffer()
         self.motion_compensation = None
         self.last_motion = None
+        # the health gate of Mapper.cpp:424-431 (MapperParams of cpp/o3s_mapper.hpp): ignored by default, which is the reference as it
+        # runs — its gate is commented out.  When it is not ignored, a registration whose fitness (ICP.evaluate at the pose it
+        # returned) is below min_refinement_fitness gives the scan up: nothing is adopted, pushed or inserted
+        self.min_refinement_fitness = 0.7
+        self.ignore_min_refinement_fitness = True
+        self.fitness_max_correspondence_distance = 0.0   # 0 = the ICP chain's max_dist
+        self.last_fitness = None            # IcpFitness the gate read on the last scan; None: ignored, not reached, or the ICP threw
+        self.last_fitness_rejected = False
 
     def set_calibration(self, C_):
         self.calib_inv = inv_iso(np.asarray(C_, np.float64))
@@ -106,6 +114,7 @@ class Mapper:
     def add(self, sp, sn, stamp):
         inserted = refreset = threw = 0
         self.flags = (0, 0, 0)
+        self.last_fitness, self.last_fitness_rejected = None, False
         if not self.use_initial_map and not self.is_calibration_set:
             return False
         self.ps = self.col.scan_for_next()
@@ -150,11 +159,18 @@ class Mapper:
                 self.last_covariance = self.icp.get_covariance()
             if self.check and reset:
                 self.check(self, sp, sn, prior32, corrected32)
+            if not self.ignore_min_refinement_fitness:
+                self.last_fitness = self.icp.evaluate(None, self.fitness_max_correspondence_distance)
         except RuntimeError:
             threw = 1
             corrected32 = prior32.copy()
             self.last_covariance = np.full((6, 6), np.nan)
             self.iters = self.icp.stats.iterations
+            self.last_fitness = None
+        if self.last_fitness is not None and self.last_fitness.fitness < self.min_refinement_fitness:   # Mapper.cpp:425-430
+            self.last_fitness_rejected = True
+            self.flags = (0, refreset, threw)
+            return False
         corrected = corrected32.astype(np.float64)
         if self.new_value:
             self.T_prev = self.T.copy()

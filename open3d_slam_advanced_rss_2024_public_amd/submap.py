@@ -51,6 +51,11 @@ def _L():
         L.o3s_submap_download_features.argtypes = [vp, dp, dp, dp]
         L.o3s_submap_feature_correspondences.argtypes = [vp, vp, C.c_int32, C.c_int32, ip, C.POINTER(C.c_int64), ip]
         L.o3s_submap_transform.argtypes = [vp, dp]
+        L.o3s_submap_build_voxel_map.argtypes = [vp, C.c_double]
+        L.o3s_submap_voxel_map_size.argtypes = [vp]
+        L.o3s_submap_voxel_map_size.restype = C.c_int64
+        L.o3s_submap_overlap_fitness.argtypes = [vp, dp, C.c_int64, dp, C.POINTER(C.c_int64), dp]
+        L.o3s_submap_overlap_fitness_scan.argtypes = [vp, vp, C.c_int, dp, C.POINTER(C.c_int64), dp]
         L.o3s_submaps_transform.argtypes = [C.c_int32, C.POINTER(vp), dp]
         L.o3s_assembled_map_create.argtypes = [C.c_int, C.POINTER(vp)]
         L.o3s_assembled_map_destroy.argtypes = [vp]
@@ -296,6 +301,37 @@ class Submap:
         if rc == _lib.ERR_BAD_ARGUMENT:
             raise ValueError("transform: T must be finite with a last row that is not zero")
         self._check(rc, "o3s_submap_transform")
+
+    def buildVoxelMap(self, voxel_size: float) -> int:
+        """voxelMap_.clear(); voxelMap_.insertCloud(mapCloud_) of Submap::computeFeatures (Submap.cpp:260-264) as an occupancy
+        snapshot in HBM (o3s_submap_build_voxel_map); returns the number of occupied voxels.  Inserts, carving and transform() leave
+        it as built — Submap::transform does not move voxelMap_ either."""
+        rc = self._lib.o3s_submap_build_voxel_map(self._h, float(voxel_size))
+        if rc == _lib.ERR_BAD_ARGUMENT:
+            raise ValueError("buildVoxelMap: voxel_size must be positive and finite")
+        self._check(rc, "o3s_submap_build_voxel_map")
+        return self.voxel_map_size()
+
+    def voxel_map_size(self) -> int:
+        """Occupied voxels of the snapshot; -1 while the submap has none (o3s_submap_voxel_map_size)."""
+        return int(self._lib.o3s_submap_voxel_map_size(self._h))
+
+    def overlapFitness(self, scan, mapToRangeSensor, which: int = 0):
+        """(n_overlapping, fitness): the points of `scan`, moved by mapToRangeSensor, that fall into an occupied voxel of the
+        snapshot, and their share (the body of SubmapCollection::isSwitchingSubmapsConsistant, SubmapCollection.cpp:396-402).
+        `scan`: (N, 3) host points, or a ProcessedScan, whose merge (which = 0) or match (1) cloud is read where it is.
+        fitness is NaN for an empty scan and 0 without a snapshot, as the reference's expression."""
+        k, f = C.c_int64(0), C.c_double(0.0)
+        T = _d(_pose(mapToRangeSensor))
+        if isinstance(scan, ProcessedScan):
+            rc = self._lib.o3s_submap_overlap_fitness_scan(self._h, scan._h, int(which), T, C.byref(k), C.byref(f))
+        else:
+            p = np.ascontiguousarray(scan, np.float64).reshape(-1, 3)
+            rc = self._lib.o3s_submap_overlap_fitness(self._h, _d(p), p.shape[0], T, C.byref(k), C.byref(f))
+        if rc == _lib.ERR_BAD_ARGUMENT:
+            raise ValueError("overlapFitness: bad argument (a pose that is not finite, `which` not 0 / 1, another device)")
+        self._check(rc, "o3s_submap_overlap_fitness")
+        return int(k.value), float(f.value)
 
     def carve(self, rawScan, mapToRangeSensor, voxel_size=0.1, max_raytracing_length=20.0, truncation_distance=0.1,
               min_dot_product_with_normal=0.5) -> int:

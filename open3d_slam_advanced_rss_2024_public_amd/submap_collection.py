@@ -9,6 +9,7 @@ from .submap import AssembledMap, ProcessedScan, Submap, transform_submaps
 
 
 INT_MAX = 2**31 - 1   # std::numeric_limits<int>::max()
+VOXEL_EXPANSION_FACTOR_ADJACENCY_BASED_REVISITING = 2.5   # magic.hpp:16
 
 
 class SubmapCollection:
@@ -36,6 +37,11 @@ class SubmapCollection:
         self.loop_closure_flags = {}   # AdjacencyMatrix::isLoopClosureSubmap_: submap id -> flag, an entry per id an edge has named
         self.buffer, self.free = [], [scan_factory() for _ in range(overlap + 1)]
         self.finished, self.finished_queue, self.switched = [], [], False
+        # SubmapParams of cpp/o3s_submap_collection.hpp: adjacency_based_revisiting_min_fitness, and whether the revisit check of
+        # SubmapCollection.cpp:392-407 runs at all (off = the reference as it runs: its body is commented out and returns true)
+        self.adjacency_min_fitness = 0.4
+        self.check_switching_consistency = False
+        self.last_switch_fitness = float("nan")   # fitness of the last consistency check (NaN: the last insert made none)
         self.create(np.zeros(3))
 
     def create(self, origin):
@@ -103,7 +109,21 @@ class SubmapCollection:
             distance += 1
         return max(0, distance - 1)
 
-    def update_active(self, p0):
+    def computeFeatures(self, i, params=None):
+        """Submap::computeFeatures of submap i (Submap.cpp:255-275): the feature set and, with it, the occupancy snapshot voxelMap_ at
+        2.5 x the map voxel size (:239-240, :260-264).  Returns the number of sparse points."""
+        n = self.maps[i].computeFeatures(params)
+        if self.map_voxel > 0.0:
+            self.maps[i].buildVoxelMap(VOXEL_EXPANSION_FACTOR_ADJACENCY_BASED_REVISITING * self.map_voxel)
+        return n
+
+    def isSwitchingSubmapsConsistant(self, ps, candidate, T) -> bool:
+        """SubmapCollection::isSwitchingSubmapsConsistant (:392-407) as written in its commented body, over the resident merge cloud
+        of `ps`.  A candidate without a snapshot has fitness 0, an empty scan NaN: both False."""
+        _, self.last_switch_fitness = self.maps[candidate].overlapFitness(ps, T, 0)
+        return self.last_switch_fitness > self.adjacency_min_fitness
+
+    def update_active(self, p0, ps=None, T=None):
         if self.force:
             self.create(p0)
             self.force = False
@@ -120,7 +140,8 @@ class SubmapCollection:
         if self.dist(p0, self.centre(closest)) < self.radius:
             if closest == active:
                 return
-            if self.adjacent(self.ids[closest], self.ids[active]):
+            if self.adjacent(self.ids[closest], self.ids[active]) and \
+                    (not self.check_switching_consistency or self.isSwitchingSubmapsConsistant(ps, closest, T)):
                 self.active = closest
             elif self.dist(p0, self.centre(active)) > self.radius:
                 self.create(p0)
@@ -135,7 +156,8 @@ class SubmapCollection:
         self.buffer.append((ps, T.copy(), stamp))
         while len(self.buffer) > self.overlap:
             self.free.append(self.buffer.pop(0)[0])
-        self.update_active(T[:3, 3].copy())
+        self.last_switch_fitness = float("nan")
+        self.update_active(T[:3, 3].copy(), ps, T)
         if prev != self.active:
             self.switched = True
             self._insert_into(prev, ps, T)

@@ -1,0 +1,180 @@
+"""The occupancy snapshot of a resident submap and the overlap fitness (include/o3s_submap.h) on the GPU: snapshot size and
+n_overlapping are integers, compared as such with the numpy restatement (tests/health_ref.py) and with the oracle's getVoxelIdx
+(oracle.voxel_idx) on the same points."""
+import math
+
+import numpy as np
+import pytest
+
+import health_ref as href
+from oracle import oracle as orc
+from open3d_slam_advanced_rss_2024_public_amd import ProcessedScan, Submap
+from open3d_slam_advanced_rss_2024_public_amd import cloud_ops as co
+from open3d_slam_advanced_rss_2024_public_amd import synthetic as syn
+
+pytestmark = pytest.mark.gpu
+
+BIG = co.croppingVolumeFactory("MaxRadius", 1000.0)
+NARROW = co.croppingVolumeFactory("MaxRadius", 4.0)
+VOX = 0.25                                          # 2.5 x a map voxel of 0.1 m
+FIRST_SLOTS = 1 << 16                               # the table's first size (kOvFirstSlots)
+T_ROT = syn.make_T(syn.rot_rpy_deg(3.0, -2.0, 40.0), np.array([1.5, -0.75, 0.2]))
+
+
+def resident(points):
+    m = Submap(0.0, BIG)                            # map voxel size 0: the cloud is what was uploaded
+    m.setMapPointCloud(np.asarray(points, np.float64).reshape(-1, 3), None)
+    return m
+
+
+def oracle_keys(pts, voxel):
+    return {tuple(int(v) for v in row) for row in orc.voxel_idx(pts, voxel)}
+
+
+def room(n, seed, lo=-12.0, hi=12.0):
+    return np.random.default_rng(seed).uniform(lo, hi, (n, 3))
+
+
+def check(m, vmap, scan, T, voxel=VOX):
+    """both references, and the host-points entry"""
+    want = href.overlap_fitness(vmap, scan, T, voxel)
+    moved = href.isometry_apply(T, scan)
+    if len(scan) and vmap is not None:
+        assert want[0] == sum(1 for row in orc.voxel_idx(moved, voxel) if tuple(int(v) for v in row) in vmap)
+    got = m.overlapFitness(scan, T)
+    print(f"N {len(scan)}: {got} (restatement {want})")
+    assert got[0] == want[0]
+    assert got[1] == want[1] or (math.isnan(got[1]) and math.isnan(want[1]))
+    return got
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 5003])
+def test_snapshot_size_and_overlap_equal_the_restatement_and_the_oracle(n):
+    mp = room(n, 10 + n)
+    m = resident(mp)
+    assert m.voxel_map_size() == -1                                  # never built
+    vmap = href.voxel_map(mp, VOX)
+    assert vmap == oracle_keys(mp, VOX)
+    assert m.buildVoxelMap(VOX) == len(vmap) == m.voxel_map_size()
+    scan = np.vstack([mp[: max(1, n // 2)] + 0.01, room(300, 99)])  # points next to map points, and points anywhere in the room
+    n_id, _ = check(m, vmap, scan, np.eye(4))
+    assert n_id >= max(1, n // 2) // 2
+    check(m, vmap, scan, T_ROT)                                      # a rotated pose
+    check(m, vmap, href.isometry_apply(np.linalg.inv(T_ROT), mp), T_ROT)   # ... that brings a cloud back onto the map (up to rounding)
+    # rebuilding at another size replaces the snapshot
+    assert m.buildVoxelMap(1.0) == len(href.voxel_map(mp, 1.0))
+    check(m, href.voxel_map(mp, 1.0), scan, T_ROT, 1.0)
+
+
+def test_more_voxels_than_the_first_table_takes_the_grow_path():
+    g = np.arange(42) * 1.0 + 0.5
+    mp = np.array(np.meshgrid(g, g, g)).reshape(3, -1).T           # 74 088 points, one per 1 m voxel
+    assert len(mp) > FIRST_SLOTS
+    m = resident(mp)
+    assert m.buildVoxelMap(1.0) == len(mp)
+    rng = np.random.default_rng(3)
+    scan = rng.uniform(-5.0, 47.0, (4000, 3))
+    n, f = check(m, href.voxel_map(mp, 1.0), scan, np.eye(4), 1.0)
+    assert 0 < n < len(scan)
+    # past half load of the first table, but not full: also rebuilt at full size, same answers
+    half = mp[: FIRST_SLOTS // 2 + 100]
+    m2 = resident(half)
+    assert m2.buildVoxelMap(1.0) == len(half)
+    check(m2, href.voxel_map(half, 1.0), scan, np.eye(4), 1.0)
+
+
+def test_all_points_in_one_voxel():
+    mp = np.random.default_rng(4).uniform(0.01, 0.24, (3000, 3))   # whole waves with one key
+    m = resident(mp)
+    assert m.buildVoxelMap(VOX) == 1
+    scan = np.vstack([mp[:200], mp[:100] + np.array([0.25, 0.0, 0.0])])
+    assert check(m, {(0, 0, 0)}, scan, np.eye(4)) == (200, 200 / 300)
+
+
+def test_points_exactly_on_voxel_faces():
+    k = np.arange(-40, 41)
+    mp = np.stack([k * VOX, np.zeros_like(k, float) + 0.1, np.zeros_like(k, float) + 0.1], axis=1)   # x exactly on k * voxel
+    vmap = href.voxel_map(mp, VOX)
+    assert vmap == oracle_keys(mp, VOX) == {(int(v), 0, 0) for v in k}
+    m = resident(mp)
+    assert m.buildVoxelMap(VOX) == len(k)
+    scan = np.stack([np.array([-10.25, -10.0, -0.25, -0.0, 0.0, 0.25, 10.0, 10.25, np.nextafter(10.25, 11.0), np.nextafter(-10.0, -11.0)]),
+                     np.full(10, 0.1), np.full(10, 0.1)], axis=1)
+    assert check(m, vmap, scan, np.eye(4))[0] == 6
+    # faces of 0.1 m voxels, where the reciprocal form and a division disagree (0.3 * 10 = 3.0000000000000004)
+    mp = np.stack([k * 0.1, np.zeros(len(k)), np.zeros(len(k))], axis=1)
+    m = resident(mp)
+    assert m.buildVoxelMap(0.1) == len(href.voxel_map(mp, 0.1)) == len(oracle_keys(mp, 0.1))
+    check(m, href.voxel_map(mp, 0.1), mp + np.array([0.0, 0.05, 0.05]), np.eye(4), 0.1)
+
+
+def test_empty_scan_no_snapshot_empty_map_and_out_of_range_keys():
+    mp = room(2000, 5)
+    m = resident(mp)
+    scan = mp[:100] + 0.01
+    assert m.overlapFitness(scan, np.eye(4)) == (0, 0.0)                        # no snapshot: 0 / N
+    n, f = m.overlapFitness(np.zeros((0, 3)), np.eye(4))
+    assert n == 0 and math.isnan(f)                                              # 0 / 0
+    vmap = href.voxel_map(mp, VOX)
+    assert m.buildVoxelMap(VOX) == len(vmap)
+    n, f = check(m, vmap, np.zeros((0, 3)), np.eye(4))
+    assert n == 0 and math.isnan(f)
+    far = (href.PACK_BIAS + 10) * VOX                                           # a voxel index beyond the packed key
+    odd = np.vstack([scan, [[far, 0.0, 0.0], [0.0, -far, 0.0], [np.nan, 0.0, 0.0], [np.inf, 0.0, 0.0]]])
+    n, f = check(m, vmap, odd, np.eye(4))
+    assert n == check(m, vmap, scan, np.eye(4))[0] and f == n / len(odd)        # not overlapping, and not an error
+    empty = Submap(0.0, BIG)
+    assert empty.buildVoxelMap(VOX) == 0                                         # a snapshot of an empty map: nothing overlaps
+    assert empty.overlapFitness(scan, np.eye(4)) == (0, 0.0)
+    with pytest.raises(ValueError):
+        m.buildVoxelMap(0.0)
+    bad = np.eye(4)
+    bad[0, 3] = np.nan
+    with pytest.raises(ValueError):
+        m.overlapFitness(scan, bad)
+
+
+def test_the_snapshot_stays_as_built_and_a_clone_carries_it():
+    mp, extra = room(3000, 6), room(3000, 7, 20.0, 30.0)
+    vmap = href.voxel_map(mp, VOX)
+    scan = np.vstack([mp[:500] + 0.01, extra[:500] + 0.01])
+    m = resident(mp)
+    assert m.buildVoxelMap(VOX) == len(vmap)
+    want = check(m, vmap, scan, T_ROT)
+    size_before = len(m)
+    m.insertScan(extra, None, T_ROT)                                              # a later insert: the map grows, the snapshot does not
+    assert len(m) == size_before + len(extra)
+    assert m.voxel_map_size() == len(vmap) and m.overlapFitness(scan, T_ROT) == want
+    m.transform(T_ROT)                                                            # Submap::transform does not move voxelMap_
+    assert m.voxel_map_size() == len(vmap) and m.overlapFitness(scan, T_ROT) == want
+    c = m.clone()
+    assert c.voxel_map_size() == len(vmap) and c.overlapFitness(scan, T_ROT) == want
+    m.buildVoxelMap(VOX)                                                          # the original moves on, the clone keeps its copy
+    assert m.voxel_map_size() != len(vmap)
+    assert c.overlapFitness(scan, T_ROT) == want
+    fresh = Submap(0.0, BIG)
+    m.hand_over(fresh)                                                            # the buffers change hands, the snapshot stays behind
+    assert fresh.voxel_map_size() == -1 and m.voxel_map_size() >= 0
+    assert Submap(0.0, BIG).voxel_map_size() == -1
+
+
+def test_the_resident_scan_entry_reads_both_clouds_where_they_are():
+    sp = syn.make_scan_pair(6_000, 30_000, 0.1, seed=3)
+    m = resident(sp.map_xyz)
+    vmap = href.voxel_map(sp.map_xyz, VOX)
+    assert m.buildVoxelMap(VOX) == len(vmap) == len(oracle_keys(sp.map_xyz, VOX))
+    sc = ProcessedScan()
+    n_merge, n_match = sc.preprocess(BIG, 0.1, NARROW, sp.scan_xyz, sp.scan_normals)
+    assert 0 < n_match < n_merge
+    for which, cloud in ((0, sc.merge[0]), (1, sc.match[0])):
+        for T in (sp.T_gt, sp.T_init, np.eye(4)):
+            want = href.overlap_fitness(vmap, cloud, T, VOX)
+            got = m.overlapFitness(sc, T, which)
+            print(f"which {which}: {got} (restatement {want})")
+            assert got == want == m.overlapFitness(cloud, T)
+    assert m.overlapFitness(sc, sp.T_gt, 0)[1] > 0.6 > m.overlapFitness(sc, np.eye(4), 0)[1]   # (a sparse map: one point per 0.1 m voxel)
+    with pytest.raises(ValueError):
+        m.overlapFitness(sc, sp.T_gt, 2)
+    empty = ProcessedScan()                                                       # nothing pre-processed: an empty scan
+    n, f = m.overlapFitness(empty, sp.T_gt, 0)
+    assert n == 0 and math.isnan(f)
