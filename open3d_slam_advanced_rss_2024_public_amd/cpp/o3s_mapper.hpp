@@ -8,6 +8,10 @@
 //   :179-195      first scan: pre-process, insert at the given pose, push the pose buffers
 //   :197-235      out-of-order timestamp: propagate the previous pose by the odometry motion, no registration
 //   :237-262      odometry availability (a pose within 100 ms of the buffer's latest counts as available)
+//   :219-224, :268-280   with MapperParams::isInterpolateOdometry the odometry poses of both stamps come from getTransform over an
+//                 interpolating buffer (clamped before it, extrapolated after it), as in the reference; without it (the default)
+//                 they are read at exact stamps only
+//   :106-115      getMapToOdom / getMapToRangeSensor: getTransform over the registered poses and the odometry
 //   :265-281      prior = mapToRangeSensorPrev_ * ((odomPrev * C^-1)^-1 * (odomNow * C^-1)), C = calibration_ (:221-222, :270-273),
 //                 unless isNewValueSetMapper_ / isIgnoreOdometryPrediction_
 //   :305-318, :359-376, :382-411, :481-501   the four stage stopwatches (o3d_slam::Timer): lastTimings() / meanTimings()
@@ -49,7 +53,8 @@
 namespace o3s {
 
 // o3d_slam::TransformInterpolationBuffer restricted to what the Mapper asks of it when the odometry is sampled at the
-// scan stamps: has(t), latest_time(), lookup(t) (exact stamp; the interpolation itself is a host utility, out of scope)
+// scan stamps: has(t), latest_time(), lookup(t) of an exact stamp.  It is the odometry buffer while
+// MapperParams::isInterpolateOdometry is off; the interpolating one is o3s_odometry.hpp's TransformInterpolationBuffer
 class PoseBuffer {
  public:
   void push(double t, const Mat4& T) { poses_[t] = T; }
@@ -88,6 +93,9 @@ struct MapperParams {
   // commented out (Mapper.cpp:424-431), so "ignore" is what it does
   bool isIgnoreMinRefinementFitness = true;
   double fitnessMaxCorrespondenceDistance = 0.0;     // the radius the fitness counts inliers within; 0 = the ICP chain's maxDist
+  // The odometry prior at ANY stamp (Mapper.cpp:219-224, 237-261, 268-280): getTransform over an interpolating buffer, which is what
+  // an external odometry source needs (its poses never carry the LiDAR's stamps).  false = exact stamps only, as before
+  bool isInterpolateOdometry = false;
 };
 
 class MapperHip {
@@ -110,10 +118,20 @@ class MapperHip {
     mapToRangeSensor_ = mul(loopClosureCorrection, mapToRangeSensor_);
     mapToRangeSensorPrev_ = mul(loopClosureCorrection, mapToRangeSensorPrev_);
   }
-  void addOdometryPose(double t, const Mat4& odomToRangeSensor) { odomToRangeSensorBuffer_.push(t, odomToRangeSensor); }
+  void addOdometryPose(double t, const Mat4& odomToRangeSensor) {
+    odomToRangeSensorBuffer_.push(t, odomToRangeSensor);
+    odomInterpolationBuffer_.push(t, odomToRangeSensor);
+  }
+  const TransformInterpolationBuffer& getOdomToRangeSensorBuffer() const { return odomInterpolationBuffer_; }
+  // Mapper::getMapToRangeSensor / getMapToOdom (Mapper.cpp:106-115)
+  Mat4 getMapToRangeSensor(double t) const { return getTransform(t, mapToRangeSensorBuffer_); }
+  Mat4 getMapToOdom(double t) const {
+    return mul(getTransform(t, mapToRangeSensorBuffer_), inverse_isometry(getTransform(t, odomInterpolationBuffer_)));
+  }
   // Mapper::setExternalOdometryFrameToCloudFrameCalibration (Mapper.cpp:66-85): the odometry poses are those of ANOTHER frame
   // (the tracking camera / IMU); every lookup is multiplied by calibration^-1 before the motion is formed (:221-222, :270-273)
   void setCalibration(const Mat4& odometryFrameToCloudFrame) {
+    calibration_ = odometryFrameToCloudFrame;
     calibrationInv_ = inverse_isometry(odometryFrameToCloudFrame);
     isCalibrationSet_ = true;
   }
@@ -123,6 +141,7 @@ class MapperHip {
   // the staged copy.  A sweep the caller has staged itself is de-skewed with undistort(staged, stamp) before it is handed over, as
   // SlamWrapper.cpp:671 does before the mapper sees the cloud; a sweep that arrives pre-processed was de-skewed before that.
   void enableMotionCompensation(double scanDuration = 0.1, bool isSpinningClockwise = true, int numPosesVelocityEstimation = 3) {
+    if (trajectoryCompensation_) throw std::runtime_error("the trajectory motion compensation is already enabled");
     motionCompensation_.reset(new ConstantVelocityMotionCompensation(mapToRangeSensorBuffer_, scanDuration, isSpinningClockwise,
                                                                      numPosesVelocityEstimation));
   }
@@ -133,6 +152,20 @@ class MapperHip {
     return lastMotion_;
   }
   const o3s_motion& lastMotion() const { return lastMotion_; }
+  // The de-skew along the odometry's trajectory (off by default), the twin of the two above: every sweep handed over as host arrays
+  // is staged, de-skewed along the poses addOdometryPose was given (whatever isInterpolateOdometry says) and pre-processed from the
+  // staged copy; a sweep the caller has staged itself — with o3s_raw_scan_set_point_times where the driver provides point times —
+  // is de-skewed with undistortAlongOdometry(staged, stamp) before it is handed over.  Host arrays carry no point times: their
+  // points are timed by azimuth.
+  void enableTrajectoryMotionCompensation(double scanDuration = 0.1, bool isSpinningClockwise = true) {
+    if (motionCompensation_) throw std::runtime_error("the constant-velocity motion compensation is already enabled");
+    trajectoryCompensation_.reset(new TrajectoryMotionCompensation(odomInterpolationBuffer_, scanDuration, isSpinningClockwise));
+  }
+  bool isTrajectoryMotionCompensationEnabled() const { return (bool)trajectoryCompensation_; }
+  void undistortAlongOdometry(o3s_raw_scan* staged, double timestamp) {
+    if (!trajectoryCompensation_) throw std::runtime_error("undistortAlongOdometry: trajectory motion compensation is not enabled");
+    trajectoryCompensation_->undistort(staged, timestamp, calibration_);
+  }
   const TransformBuffer& getMapToRangeSensorBuffer() const { return mapToRangeSensorBuffer_; }
   const MapperTimings& lastTimings() const { return lastTimings_; }
   MapperTimings meanTimings() const {  // Timer::getAvgMeasurementMsec over the scans that ran the stage
@@ -221,7 +254,7 @@ class MapperHip {
     }
     // ---- out-of-order stamp (:197-235): propagate by the odometry motion, no registration ----
     if (haveLast_ && timestamp <= lastMeasurementTimestamp_) {
-      const double latest = odomToRangeSensorBuffer_.latest_time();
+      const double latest = params_.isInterpolateOdometry ? odomInterpolationBuffer_.latest_time() : odomToRangeSensorBuffer_.latest_time();
       const Mat4 motion = mul(inverse_isometry(odomInCloudFrame(lastMeasurementTimestamp_)), odomInCloudFrame(latest));
       mapToRangeSensor_ = mul(mapToRangeSensorPrev_, motion);
       mapToRangeSensorBuffer_.push(latest, mapToRangeSensor_);
@@ -229,11 +262,18 @@ class MapperHip {
       return true;
     }
     // ---- odometry prior (:237-281) ----
-    bool isOdomOkay = odomToRangeSensorBuffer_.has(timestamp);
-    if (!odomToRangeSensorBuffer_.empty() && (timestamp - odomToRangeSensorBuffer_.latest_time()) * 1e3 < 100.0) isOdomOkay = true;
+    bool isOdomOkay, havePoses;
+    if (params_.isInterpolateOdometry) {  // both poses come from getTransform: no further condition (:268-273)
+      const TransformInterpolationBuffer& b = odomInterpolationBuffer_;
+      isOdomOkay = b.has(timestamp) || (!b.empty() && (timestamp - b.latest_time()) * 1e3 < 100.0);
+      havePoses = true;
+    } else {
+      isOdomOkay = odomToRangeSensorBuffer_.has(timestamp);
+      if (!odomToRangeSensorBuffer_.empty() && (timestamp - odomToRangeSensorBuffer_.latest_time()) * 1e3 < 100.0) isOdomOkay = true;
+      havePoses = odomToRangeSensorBuffer_.has(timestamp) && odomToRangeSensorBuffer_.has(lastMeasurementTimestamp_);
+    }
     Mat4 estimate = mapToRangeSensorPrev_;
-    if (isOdomOkay && haveLast_ && !isNewValueSetMapper_ && !isIgnoreOdometryPrediction_ && odomToRangeSensorBuffer_.has(timestamp) &&
-        odomToRangeSensorBuffer_.has(lastMeasurementTimestamp_)) {
+    if (isOdomOkay && haveLast_ && !isNewValueSetMapper_ && !isIgnoreOdometryPrediction_ && havePoses) {
       const Mat4 motion = mul(inverse_isometry(odomInCloudFrame(lastMeasurementTimestamp_)), odomInCloudFrame(timestamp));
       estimate = mul(mapToRangeSensorPrev_, motion);
     }
@@ -353,13 +393,19 @@ class MapperHip {
     nTimed_[which] += 1;
   }
   // getTransform(t, odomToRangeSensorBuffer_) * calibration_.inverse()   (:221-222, :270-273)
-  Mat4 odomInCloudFrame(double t) const { return mul(odomToRangeSensorBuffer_.lookup(t), calibrationInv_); }
+  Mat4 odomInCloudFrame(double t) const {
+    if (params_.isInterpolateOdometry) return mul(getTransform(t, odomInterpolationBuffer_), calibrationInv_);
+    return mul(odomToRangeSensorBuffer_.lookup(t), calibrationInv_);
+  }
   void preprocess(const Raw& raw, double timestamp) {
     std::int64_t nMerge = 0, nMatch = 0;
-    if (motionCompensation_ && !raw.ready && !raw.staged) {  // host arrays: stage, de-skew, pre-process from the staged copy
+    if ((motionCompensation_ || trajectoryCompensation_) && !raw.ready && !raw.staged) {  // host arrays: stage, de-skew, pre-process from the staged copy
       if (!deskewStage_) check(o3s_raw_scan_create(device_, &deskewStage_), "o3s_raw_scan_create");
       check(o3s_raw_scan_upload(deskewStage_, raw.pts, raw.normals, raw.N), "o3s_raw_scan_upload");
-      lastMotion_ = motionCompensation_->undistort(deskewStage_, timestamp);
+      if (motionCompensation_)
+        lastMotion_ = motionCompensation_->undistort(deskewStage_, timestamp);
+      else
+        trajectoryCompensation_->undistort(deskewStage_, timestamp, calibration_);
       check(o3s_scan_preprocess_staged(scan_, &params_.mapBuilderCropper, params_.scanVoxelSize, &params_.scanMatcherCropper, deskewStage_, &nMerge,
                                        &nMatch),
             "o3s_scan_preprocess_staged");
@@ -390,7 +436,9 @@ class MapperHip {
   IcpHip icp_;
   SubmapCollectionHip submaps_;
   o3s_scan* scan_ = nullptr;  // owned by submaps_ (its ring of resident scans)
-  PoseBuffer odomToRangeSensorBuffer_;
+  PoseBuffer odomToRangeSensorBuffer_;                     // the odometry at exact stamps (isInterpolateOdometry off)
+  TransformInterpolationBuffer odomInterpolationBuffer_;  // the odometry at any stamp (isInterpolateOdometry on; the trajectory de-skew)
+  std::unique_ptr<TrajectoryMotionCompensation> trajectoryCompensation_;  // null: off
   TransformBuffer mapToRangeSensorBuffer_;  // the registered poses (Mapper::getMapToRangeSensorBuffer)
   std::unique_ptr<ConstantVelocityMotionCompensation> motionCompensation_;  // motionCompensationMap_; null: off
   o3s_raw_scan* deskewStage_ = nullptr;     // where a sweep handed over as host arrays is de-skewed
@@ -405,7 +453,7 @@ class MapperHip {
   o3s_icp_fitness lastFitness_{};
   std::array<double, 36> lastCovariance_ = nanCovariance();
   int lastIterations_ = 0;
-  Mat4 calibrationInv_ = Mat4::identity();
+  Mat4 calibration_ = Mat4::identity(), calibrationInv_ = Mat4::identity();
   bool isCalibrationSet_ = false;
   MapperTimings lastTimings_, sumTimings_;
   long long nTimed_[4] = {0, 0, 0, 0};

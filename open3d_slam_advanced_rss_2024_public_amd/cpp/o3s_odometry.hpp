@@ -3,7 +3,11 @@
 //
 //   TransformBuffer                      TransformInterpolationBuffer.cpp: the push rules (:22-46), the size limit (:151-155,
 //                                        default 2000), size / latest_time / latest_measurement / latest_offseted_measurement /
-//                                        has, and the lookup of an exact stamp (interpolation is a host utility, out of scope)
+//                                        has, and the lookup of an exact stamp
+//   TransformInterpolationBuffer         the same buffer with the lookup of ANY stamp it covers (:100-149: interpolation between the
+//                                        two neighbouring poses) and getTransform (:189-220: clamp before, extrapolation after);
+//                                        the arithmetic is the library's (include/trajectory/o3s_trajectory.h)
+//   TrajectoryMotionCompensation         the de-skew of a staged sweep along such a buffer (o3s_raw_scan_undistort_trajectory)
 //   ConstantVelocityMotionCompensation   MotionCompensation.cpp:32-127: velocities from the buffer (o3s_motion_from_poses),
 //                                        the de-skew on the staged sweep (o3s_raw_scan_undistort)
 //   LidarOdometry                        Odometry.cpp:22-134: two o3s_scan objects that are swapped, never copied; the registration
@@ -17,10 +21,12 @@
 #include <stdexcept>
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "o3s_pose.hpp"
 #include "o3s_registration.h"
 #include "o3s_scan.h"
+#include "trajectory/o3s_trajectory.h"
 
 namespace o3s {
 
@@ -52,6 +58,14 @@ class TransformBuffer {
       if (p.time == t) return p.transform;
     throw std::runtime_error("TransformBuffer: no pose at the requested stamp");
   }
+  std::vector<o3s_stamped_pose> table() const {  // the buffer as the library's functions take it
+    std::vector<o3s_stamped_pose> tab(poses_.size());
+    for (std::size_t k = 0; k < poses_.size(); ++k) {
+      tab[k].t = poses_[k].time;
+      for (int i = 0; i < 16; ++i) tab[k].T[i] = poses_[k].transform.m[i];
+    }
+    return tab;
+  }
 
  private:
   const std::deque<TimestampedPose>& need() const {
@@ -60,6 +74,91 @@ class TransformBuffer {
   }
   std::deque<TimestampedPose> poses_;
   std::size_t limit_;
+};
+
+// getTransform over a table of stamped poses (o3s_trajectory_get_transform)
+inline Mat4 getTransform(double t, const o3s_stamped_pose* table, std::size_t K) {
+  Mat4 out{};
+  if (K == 0) throw std::runtime_error("getTransform: empty buffer");
+  const int rc = o3s_trajectory_get_transform(table, (std::int64_t)K, t, out.m);
+  if (rc != O3S_OK) throw std::runtime_error("o3s_trajectory_get_transform failed (status " + std::to_string(rc) + ")");
+  return out;
+}
+inline Mat4 getTransform(double t, const TransformBuffer& buffer) {
+  const std::vector<o3s_stamped_pose> tab = buffer.table();
+  return getTransform(t, tab.data(), tab.size());
+}
+
+// The buffer kept as one table in memory, so that every lookup and every de-skew reads it in place
+class TransformInterpolationBuffer {
+ public:
+  explicit TransformInterpolationBuffer(std::size_t sizeLimit = 2000) : limit_(sizeLimit) {}
+  void push(double t, const Mat4& T) {
+    if (!empty() && (t < earliest_time() || t < latest_time())) return;  // earlier than the earliest / out of order
+    o3s_stamped_pose p;
+    p.t = t;
+    for (int i = 0; i < 16; ++i) p.T[i] = T.m[i];
+    poses_.push_back(p);
+    while (size() > limit_) ++head_;
+    if (head_ > limit_) {  // drop the retired front now and then, not on every push
+      poses_.erase(poses_.begin(), poses_.begin() + (std::ptrdiff_t)head_);
+      head_ = 0;
+    }
+  }
+  std::size_t size() const { return poses_.size() - head_; }
+  bool empty() const { return size() == 0; }
+  const o3s_stamped_pose* table() const { return poses_.data() + head_; }
+  double earliest_time() const { return need()[0].t; }
+  double latest_time() const { return need()[size() - 1].t; }
+  const o3s_stamped_pose& latest_measurement() const { return need()[size() - 1]; }
+  const o3s_stamped_pose& latest_offseted_measurement(int offset) const {
+    if (offset < 0 || (std::size_t)offset >= size()) throw std::runtime_error("TransformInterpolationBuffer: offset beyond the buffer");
+    return need()[size() - 1 - (std::size_t)offset];
+  }
+  bool has(double t) const { return o3s_trajectory_has(table(), (std::int64_t)size(), t) != 0; }
+  Mat4 lookup(double t) const {
+    Mat4 out{};
+    const int rc = o3s_trajectory_lookup(table(), (std::int64_t)size(), t, out.m);
+    if (rc == O3S_ERR_BAD_ARGUMENT) throw std::runtime_error("TransformInterpolationBuffer: missing transform for the requested stamp");
+    if (rc != O3S_OK) throw std::runtime_error("o3s_trajectory_lookup failed (status " + std::to_string(rc) + ")");
+    return out;
+  }
+
+ private:
+  const o3s_stamped_pose* need() const {
+    if (empty()) throw std::runtime_error("TransformInterpolationBuffer: empty buffer");
+    return table();
+  }
+  std::vector<o3s_stamped_pose> poses_;
+  std::size_t head_ = 0, limit_;
+};
+
+inline Mat4 getTransform(double t, const TransformInterpolationBuffer& buffer) { return getTransform(t, buffer.table(), buffer.size()); }
+
+// The de-skew of a staged sweep along the trajectory the buffer holds: every point is expressed in the sensor frame at the
+// sweep's stamp.  Point times come from the driver (o3s_raw_scan_set_point_times on the staged sweep), else from the azimuth as
+// in ConstantVelocityMotionCompensation.  With an empty buffer the sweep stays as it came.
+class TrajectoryMotionCompensation {
+ public:
+  TrajectoryMotionCompensation(const TransformInterpolationBuffer& buffer, double scanDuration = 0.1, bool isSpinningClockwise = true)
+      : buffer_(buffer), scanDuration_(scanDuration), clockwise_(isSpinningClockwise) {
+    if (!(scanDuration > 0.0)) throw std::runtime_error("lidar scanDuration_ must be > 0");
+  }
+  void undistort(o3s_raw_scan* staged, double stamp, const Mat4& calibration) const {
+    if (buffer_.empty()) return;
+    o3s_trajectory_deskew p{};
+    p.stamp = stamp;
+    p.scan_duration = scanDuration_;
+    for (int i = 0; i < 16; ++i) p.calibration[i] = calibration.m[i];
+    p.is_spinning_clockwise = clockwise_ ? 1 : 0;
+    const int rc = o3s_raw_scan_undistort_trajectory(staged, buffer_.table(), (std::int64_t)buffer_.size(), &p);
+    if (rc != O3S_OK) throw std::runtime_error("o3s_raw_scan_undistort_trajectory failed (status " + std::to_string(rc) + ")");
+  }
+
+ private:
+  const TransformInterpolationBuffer& buffer_;
+  double scanDuration_;
+  bool clockwise_;
 };
 
 class ConstantVelocityMotionCompensation {

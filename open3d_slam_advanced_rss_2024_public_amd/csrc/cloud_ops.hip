@@ -1,8 +1,11 @@
 // cloud_ops.hip — open3d_slam-side point-cloud operators on HOST buffers (C ABI: include/o3s_cloud_ops.h), gfx950 only.
 // The kernels and the device-level pipelines live in cloud_dev.h (shared with the device-resident submap, submap.hip);
 // this file stages the caller's buffers through HBM.
+#include <chrono>
+
 #include "cloud_dev.h"
 #include "undistort_dev.h"
+#include "trajectory_dev.h"
 
 using namespace o3s_cloud;
 
@@ -234,6 +237,61 @@ int o3s_motion_from_poses(const double T_start[16], double t_start, const double
   return O3S_OK;
 }
 
+// ---- include/trajectory/o3s_trajectory.h: the host arithmetic (no device call) ----
+int o3s_transform_interpolate(const o3s_stamped_pose* start, const o3s_stamped_pose* end, double t, o3s_stamped_pose* out) {
+  if (!start || !end || !out) return O3S_ERR_BAD_ARGUMENT;
+  return transform_interpolate(start, end, t, out);
+}
+
+int o3s_transform_extrapolate(const o3s_stamped_pose* start, const o3s_stamped_pose* end, double t, o3s_stamped_pose* out) {
+  if (!start || !end || !out) return O3S_ERR_BAD_ARGUMENT;
+  return transform_extrapolate(start, end, t, out);
+}
+
+int o3s_trajectory_has(const o3s_stamped_pose* poses, int64_t K, double t) { return trajectory_has(poses, K, t) ? 1 : 0; }
+
+int o3s_trajectory_lookup(const o3s_stamped_pose* poses, int64_t K, double t, double out_T[16]) {
+  if (!out_T) return O3S_ERR_BAD_ARGUMENT;
+  return trajectory_lookup(poses, K, t, out_T);
+}
+
+int o3s_trajectory_get_transform(const o3s_stamped_pose* poses, int64_t K, double t, double out_T[16]) {
+  if (!out_T) return O3S_ERR_BAD_ARGUMENT;
+  return trajectory_get_transform(poses, K, t, out_T);
+}
+
+// the de-skew along a trajectory on host buffers (out may alias pts)
+int o3s_undistort_cloud_trajectory(int device, const o3s_stamped_pose* poses, int64_t K, const o3s_trajectory_deskew* params, const double* pts,
+                                   const double* dt, int64_t N, double* out) {
+  if (!trajectory_call_valid(poses, K, params, dt != nullptr) || N < 0 || (N > 0 && (!pts || !out))) return O3S_ERR_BAD_ARGUMENT;
+  if (N == 0) return O3S_OK;
+  if (K == 1) {  // G is the same pose at every stamp: A * G * C^-1 is the identity
+    if (out != pts) std::memmove(out, pts, (size_t)N * 24);
+    return O3S_OK;
+  }
+  TrajectoryArgs a;
+  std::vector<double> tab;
+  int rc = trajectory_prepare(poses, K, *params, &a, &tab);
+  if (rc != O3S_OK) return rc;
+  rc = pick_device(device);
+  if (rc != O3S_OK) return rc;
+  hipStream_t s = nullptr;
+  Buf d, d_dt, d_tab;
+  CK(d.alloc((size_t)N * 24));
+  CK(d_tab.alloc(tab.size() * 8));
+  CK(hipMemcpyAsync(d.p, pts, (size_t)N * 24, hipMemcpyHostToDevice, s));
+  CK(hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
+  if (dt) {
+    CK(d_dt.alloc((size_t)N * 8));
+    CK(hipMemcpyAsync(d_dt.p, dt, (size_t)N * 8, hipMemcpyHostToDevice, s));
+  }
+  rc = undistort_trajectory_dev(d.as<double>(), dt ? d_dt.as<double>() : nullptr, N, d_tab.as<double>(), a, s);
+  if (rc != O3S_OK) return rc;
+  CK(hipMemcpyAsync(out, d.p, (size_t)N * 24, hipMemcpyDeviceToHost, s));
+  CK(hipStreamSynchronize(s));
+  return O3S_OK;
+}
+
 }  // extern "C"
 
 #include "o3d_icp_impl.h"
@@ -246,6 +304,58 @@ int o3s_motion_from_poses(const double T_start[16], double t_start, const double
 #include "overlap_impl.h"
 
 #ifdef O3S_TEST_HOOKS
+// hooks build only (tools/trajectory_deskew_bench.py): the host's share of one trajectory de-skew — A, C^-1, the extrapolation and
+// the table of K knots — `reps` times; *ms_per_call is the mean wall time of one
+extern "C" int o3s_test_trajectory_prepare(const o3s_stamped_pose* poses, int64_t K, const o3s_trajectory_deskew* params, int reps, double* ms_per_call) {
+  using namespace o3s_cloud;
+  if (!trajectory_call_valid(poses, K, params, false) || reps < 1 || !ms_per_call) return O3S_ERR_BAD_ARGUMENT;
+  TrajectoryArgs a;
+  std::vector<double> tab;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int k = 0; k < reps; ++k) {
+    const int rc = trajectory_prepare(poses, K, *params, &a, &tab);
+    if (rc != O3S_OK) return rc;
+  }
+  *ms_per_call = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / reps;
+  return O3S_OK;
+}
+
+// hooks build only (tools/trajectory_deskew_bench.py): the device time of ONE de-skew kernel on the staged sweep, between two HIP
+// events on its stream — k_undistort when a motion is given, else k_undistort_trajectory (its table is uploaded before the first
+// event).  The sweep is rewritten in place, as by the product entries
+extern "C" int o3s_test_deskew_kernel_ms(o3s_raw_scan* r, const o3s_motion* m, const o3s_stamped_pose* poses, int64_t K,
+                                         const o3s_trajectory_deskew* params, float* ms) {
+  using namespace o3s_cloud;
+  if (!r || r->N == 0 || !ms) return O3S_ERR_BAD_ARGUMENT;
+  if (m ? !motion_valid(m) : (K < 2 || !trajectory_call_valid(poses, K, params, r->has_times != 0))) return O3S_ERR_BAD_ARGUMENT;
+  if (hipSetDevice(r->device) != hipSuccess) return O3S_ERR_HIP;
+  TrajectoryArgs a;
+  if (!m) {
+    std::vector<double> tab;
+    const int rc = trajectory_prepare(poses, K, *params, &a, &tab);
+    if (rc != O3S_OK) return rc;
+    CK(r->traj.ensure(tab.size() * 8, 0, r->stream));
+    CK(hipMemcpyAsync(r->traj.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, r->stream));
+    CK(hipStreamSynchronize(r->stream));
+  }
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  CK(hipEventCreate(&e0));
+  if (hipEventCreate(&e1) != hipSuccess) {
+    (void)hipEventDestroy(e0);
+    return O3S_ERR_HIP;
+  }
+  int rc = hipEventRecord(e0, r->stream) == hipSuccess ? O3S_OK : O3S_ERR_HIP;
+  if (rc == O3S_OK)
+    rc = m ? undistort_dev(r->p.d(), r->N, *m, r->stream)
+           : undistort_trajectory_dev(r->p.d(), r->has_times ? r->dt.d() : nullptr, r->N, r->traj.d(), a, r->stream);
+  if (rc == O3S_OK && (hipEventRecord(e1, r->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                       hipEventElapsedTime(ms, e0, e1) != hipSuccess))
+    rc = O3S_ERR_HIP;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  return rc;
+}
+
 // hooks build only (tests/test_gpu_cloud_ops.py): the pair sort of the work areas (cloud_dev.h sort_pairs) on host arrays
 extern "C" int o3s_test_sort_pairs(int device, const uint64_t* keys, const uint32_t* vals, int64_t n, int end_bit, uint64_t* keys_out, uint32_t* vals_out) {
   using namespace o3s_cloud;

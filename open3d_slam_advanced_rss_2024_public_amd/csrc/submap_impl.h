@@ -1246,6 +1246,8 @@ struct o3s_raw_scan {
   DArr p, n;
   int64_t N = 0;
   int has_normals = 0;
+  DArr dt, traj;      // per-point time offsets of this sweep (o3s_raw_scan_set_point_times); the table of the last trajectory de-skew
+  int has_times = 0;  // dropped by the next upload
 };
 
 extern "C" {
@@ -1278,6 +1280,7 @@ void o3s_raw_scan_destroy(o3s_raw_scan* r) {
 int o3s_raw_scan_upload(o3s_raw_scan* r, const double* pts, const double* normals, int64_t N) {
   if (!r || N < 0 || (N > 0 && !pts) || N > (int64_t)0x7fffffff) return O3S_ERR_BAD_ARGUMENT;
   r->N = 0;
+  r->has_times = 0;
   if (N == 0) return O3S_OK;
   if (hipSetDevice(r->device) != hipSuccess) return O3S_ERR_HIP;
   hipStream_t s = r->stream;
@@ -1303,6 +1306,36 @@ int o3s_raw_scan_undistort(o3s_raw_scan* r, const o3s_motion* m) {
   const int rc = undistort_dev(r->p.d(), r->N, *m, r->stream);
   if (rc != O3S_OK) return rc;
   CK(hipStreamSynchronize(r->stream));  // the pre-process reads the staged copy from another stream
+  return O3S_OK;
+}
+
+// include/trajectory/o3s_trajectory.h: the driver's per-point time offsets of the staged sweep
+int o3s_raw_scan_set_point_times(o3s_raw_scan* r, const double* dt, int64_t N) {
+  if (!r || N != r->N || (N > 0 && !dt)) return O3S_ERR_BAD_ARGUMENT;
+  if (N == 0) return O3S_OK;
+  if (hipSetDevice(r->device) != hipSuccess) return O3S_ERR_HIP;
+  r->has_times = 0;
+  CK(r->dt.ensure((size_t)N * 8, 0, r->stream));
+  CK(hipMemcpyAsync(r->dt.p, dt, (size_t)N * 8, hipMemcpyHostToDevice, r->stream));
+  CK(hipStreamSynchronize(r->stream));
+  r->has_times = 1;
+  return O3S_OK;
+}
+
+// the de-skew along a trajectory on the staged sweep, in place (trajectory_dev.h): points only, the staged normals stay as they are
+int o3s_raw_scan_undistort_trajectory(o3s_raw_scan* r, const o3s_stamped_pose* poses, int64_t K, const o3s_trajectory_deskew* params) {
+  if (!r || !trajectory_call_valid(poses, K, params, r->N > 0 && r->has_times)) return O3S_ERR_BAD_ARGUMENT;
+  if (r->N == 0 || K == 1) return O3S_OK;
+  TrajectoryArgs a;
+  std::vector<double> tab;
+  int rc = trajectory_prepare(poses, K, *params, &a, &tab);
+  if (rc != O3S_OK) return rc;
+  if (hipSetDevice(r->device) != hipSuccess) return O3S_ERR_HIP;
+  CK(r->traj.ensure(tab.size() * 8, 0, r->stream));
+  CK(hipMemcpyAsync(r->traj.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, r->stream));
+  rc = undistort_trajectory_dev(r->p.d(), r->has_times ? r->dt.d() : nullptr, r->N, r->traj.d(), a, r->stream);
+  if (rc != O3S_OK) return rc;
+  CK(hipStreamSynchronize(r->stream));  // the pre-process reads the staged copy from another stream; `tab` is free again
   return O3S_OK;
 }
 

@@ -85,27 +85,9 @@ inline int undistort_dev(double* d_pts, int64_t N, const o3s_motion& m, hipStrea
   return O3S_OK;
 }
 
-// estimateLinearAndAngularVelocity for start / finish already taken from the buffer (4x4 column-major isometries)
-inline void motion_from_poses(const double A[16], double ta, const double B[16], double tb, o3s_motion* m) {
-  for (int k = 0; k < 3; ++k) m->linear_velocity[k] = m->angular_velocity_rpy[k] = 0.0;
-  const double dt = tb - ta;
-  if (!(dt > 0.0)) return;
-  // dT = start^-1 * finish: R = Ra^T Rb, t = Ra^T (tb - ta)
-  double R[3][3], t[3];
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) {
-      double v = A[r * 4 + 0] * B[c * 4 + 0];
-      v = v + A[r * 4 + 1] * B[c * 4 + 1];
-      v = v + A[r * 4 + 2] * B[c * 4 + 2];
-      R[r][c] = v;
-    }
-    double v = A[r * 4 + 0] * (B[12] - A[12]);
-    v = v + A[r * 4 + 1] * (B[13] - A[13]);
-    v = v + A[r * 4 + 2] * (B[14] - A[14]);
-    t[r] = v;
-  }
-  // Eigen::Quaterniond(R): the branch on the trace and the largest diagonal element
-  double q[4];  // w, x, y, z
+// Eigen::Quaterniond(Matrix3d): the branch on the trace and the largest diagonal element; q = (w, x, y, z), not normalised
+// (shared with trajectory_dev.h)
+inline void quat_from_rotation(const double R[3][3], double q[4]) {
   const double tr = R[0][0] + R[1][1] + R[2][2];
   if (tr > 0.0) {
     double u = std::sqrt(tr + 1.0);
@@ -126,6 +108,29 @@ inline void motion_from_poses(const double A[16], double ta, const double B[16],
     q[1 + j] = (R[j][i] + R[i][j]) * u;
     q[1 + k] = (R[k][i] + R[i][k]) * u;
   }
+}
+
+// estimateLinearAndAngularVelocity for start / finish already taken from the buffer (4x4 column-major isometries)
+inline void motion_from_poses(const double A[16], double ta, const double B[16], double tb, o3s_motion* m) {
+  for (int k = 0; k < 3; ++k) m->linear_velocity[k] = m->angular_velocity_rpy[k] = 0.0;
+  const double dt = tb - ta;
+  if (!(dt > 0.0)) return;
+  // dT = start^-1 * finish: R = Ra^T Rb, t = Ra^T (tb - ta)
+  double R[3][3], t[3];
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) {
+      double v = A[r * 4 + 0] * B[c * 4 + 0];
+      v = v + A[r * 4 + 1] * B[c * 4 + 1];
+      v = v + A[r * 4 + 2] * B[c * 4 + 2];
+      R[r][c] = v;
+    }
+    double v = A[r * 4 + 0] * (B[12] - A[12]);
+    v = v + A[r * 4 + 1] * (B[13] - A[13]);
+    v = v + A[r * 4 + 2] * (B[14] - A[14]);
+    t[r] = v;
+  }
+  double q[4];  // w, x, y, z
+  quat_from_rotation(R, q);
   const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
   const double w = q[0] / n, x = q[1] / n, y = q[2] / n, z = q[3] / n;
   const double d = dt + 1e-6;

@@ -71,17 +71,62 @@ class Mapper:
         self.fitness_max_correspondence_distance = 0.0   # 0 = the ICP chain's max_dist
         self.last_fitness = None            # IcpFitness the gate read on the last scan; None: ignored, not reached, or the ICP threw
         self.last_fitness_rejected = False
+        # MapperParams::isInterpolateOdometry.  Off: the odometry is the dict `odom`, read at exact stamps only.  On: the odometry
+        # is odomToRangeSensorBuffer_ as the reference has it — add_odometry_pose feeds odom_buffer, and the prior is formed at
+        # any stamp by getTransform (Mapper.cpp:219-224, 237-261, 268-280)
+        from .odometry import TransformInterpolationBuffer
+        self.interpolate_odometry = False
+        self.odom_buffer = TransformInterpolationBuffer()
+        self.calibration = np.eye(4)
+        self.trajectory_compensation = None   # enable_trajectory_motion_compensation
+        self.last_deskewed = None             # the sweep as the last trajectory de-skew handed it to the pre-processing
 
     def set_calibration(self, C_):
-        self.calib_inv = inv_iso(np.asarray(C_, np.float64))
+        self.calibration = np.array(C_, np.float64).reshape(4, 4)
+        self.calib_inv = inv_iso(self.calibration)
         self.is_calibration_set = True
+
+    def add_odometry_pose(self, stamp, T):
+        """Mapper::addOdometryPose: into the dict of exact stamps and into the interpolating buffer (the one in use is chosen by
+        interpolate_odometry)."""
+        T = np.array(T, np.float64).reshape(4, 4)
+        self.odom[float(stamp)] = T
+        self.odom_buffer.push(stamp, T)
 
     def enable_motion_compensation(self, scan_duration=0.1, is_spinning_clockwise=True, num_poses_vel_estimation=3):
         """motion_compensation.is_undistort_scan: every sweep is de-skewed with the velocities of the registered poses before the
         pre-processing sees it (ConstantVelocityMotionCompensation over getMapToRangeSensorBuffer())."""
         from .odometry import ConstantVelocityMotionCompensation
+        if self.trajectory_compensation is not None:
+            raise ValueError("the trajectory motion compensation is already enabled")
         self.motion_compensation = ConstantVelocityMotionCompensation(self.pose_buffer, scan_duration, is_spinning_clockwise,
                                                                       num_poses_vel_estimation)
+
+    def enable_trajectory_motion_compensation(self, scan_duration=0.1, is_spinning_clockwise=True):
+        """Every sweep is de-skewed along the odometry's trajectory (odom_buffer, whatever interpolate_odometry says) before the
+        pre-processing sees it: each point is expressed in the sensor frame at the sweep's stamp.  Point times come from
+        add(..., point_times=), else from the azimuth.  While the buffer is empty the sweep passes as it came."""
+        from .odometry import TrajectoryMotionCompensation
+        if self.motion_compensation is not None:
+            raise ValueError("the constant-velocity motion compensation is already enabled")
+        self.trajectory_compensation = TrajectoryMotionCompensation(self.odom_buffer, scan_duration, is_spinning_clockwise)
+
+    def getMapToRangeSensor(self, stamp):
+        """Mapper::getMapToRangeSensor (Mapper.cpp:113-115): getTransform over the registered poses."""
+        from .odometry import get_transform
+        return get_transform(stamp, self._registered())
+
+    def getMapToOdom(self, stamp):
+        """Mapper::getMapToOdom (Mapper.cpp:106-111): mapToRangeSensor(t) * odomToRangeSensor(t)^-1."""
+        from .odometry import get_transform
+        return mul4(get_transform(stamp, self._registered()), inv_iso(get_transform(stamp, self.odom_buffer)))
+
+    def _registered(self):
+        """pose_buffer as an interpolating buffer (the same pushes: the push rules are the same)."""
+        from .odometry import TransformInterpolationBuffer
+        b = TransformInterpolationBuffer(self.pose_buffer.size_limit)
+        b._t, b._T = self.pose_buffer._t, self.pose_buffer._T
+        return b
 
     def loopClosureUpdate(self, loopClosureCorrection):
         """Mapper::loopClosureUpdate (Mapper.cpp:92-95).  The ICP reference is NOT renewed: until the next renewal the matcher still
@@ -98,20 +143,28 @@ class Mapper:
 
     def _odom(self, stamp):
         """getTransform(t, odomToRangeSensorBuffer_) * calibration_.inverse()   (Mapper.cpp:221-222, 270-273)"""
+        if self.interpolate_odometry:
+            from .odometry import get_transform
+            return mul4(get_transform(stamp, self.odom_buffer), self.calib_inv)
         return mul4(self.odom[stamp], self.calib_inv)
 
     @property
     def sm(self):
         return self.col.maps[self.col.active]
 
-    def preprocess(self, sp, sn, stamp=None):
+    def preprocess(self, sp, sn, stamp=None, point_times=None):
+        if self.trajectory_compensation is not None and stamp is not None:
+            self.trajectory_compensation.calibration = self.calibration
+            sp = self.trajectory_compensation.undistort_cloud(sp, stamp, point_times, getattr(self.icp, "device", 0))
+            self.last_deskewed = sp
         if self.motion_compensation is not None and stamp is not None:   # SlamWrapper.cpp:671: undistortInputPointCloud(raw.cloud_, raw.time_)
             self.last_motion = self.motion_compensation.motion(stamp)
             from .odometry import undistort_cloud
             sp = undistort_cloud(sp, self.last_motion, getattr(self.icp, "device", 0))
         self.ps.preprocess(self.wide, self.scan_voxel, self.narrow, sp, sn)
 
-    def add(self, sp, sn, stamp):
+    def add(self, sp, sn, stamp, point_times=None):
+        """point_times: the driver's per-point time offsets (seconds after `stamp`), read by the trajectory motion compensation."""
         inserted = refreset = threw = 0
         self.flags = (0, 0, 0)
         self.last_fitness, self.last_fitness_rejected = None, False
@@ -120,23 +173,28 @@ class Mapper:
         self.ps = self.col.scan_for_next()
         if len(self.sm) == 0:
             self.T_prev = self.T.copy()
-            self.preprocess(sp, sn, stamp)
+            self.preprocess(sp, sn, stamp, point_times)
             self.col.insert(self.ps, self.T, stamp)
             self.pose_buffer.push(stamp, self.T)
             self.flags = (1, 0, 0)
             return True
         if self.last_stamp is not None and stamp <= self.last_stamp:
-            latest = max(self.odom)
+            latest = self.odom_buffer.latest_time() if self.interpolate_odometry else max(self.odom)
             self.T = mul4(self.T_prev, mul4(inv_iso(self._odom(self.last_stamp)), self._odom(latest)))
             self.pose_buffer.push(latest, self.T)
             self.T_prev = self.T.copy()
             return True
         est = self.T_prev.copy()
-        if stamp in self.odom and self.last_stamp is not None and not self.new_value and not self.ignore_odom:
+        if self.interpolate_odometry:   # isOdomOkay (Mapper.cpp:237-261); both poses come from getTransform, no further condition
+            b = self.odom_buffer
+            have = b.has(stamp) or (not b.empty() and (stamp - b.latest_time()) * 1e3 < 100.0)
+        else:
+            have = stamp in self.odom
+        if have and self.last_stamp is not None and not self.new_value and not self.ignore_odom:
             est = mul4(self.T_prev, mul4(inv_iso(self._odom(self.last_stamp)), self._odom(stamp)))
         self.ignore_odom = False
         self.prior = est
-        self.preprocess(sp, sn, stamp)
+        self.preprocess(sp, sn, stamp, point_times)
         prior32 = est.astype(np.float32)
         corrected32 = prior32.copy()
         reset = self.new_value or self.last_ref is None or (stamp - self.last_ref) >= self.ref_period

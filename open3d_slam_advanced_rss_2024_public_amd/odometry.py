@@ -4,9 +4,12 @@ cpp/o3s_odometry.hpp.  Restates, with every cloud operation on the device:
   LidarOdometry                       O3S/src/Odometry.cpp:22-134
   ConstantVelocityMotionCompensation  O3S/src/MotionCompensation.cpp:32-127
   TransformBuffer                     O3S/src/TransformInterpolationBuffer.cpp (push rules, size limit, accessors, exact lookup)
+  TransformInterpolationBuffer        ... with the range-based has and the interpolating lookup (:100-149); get_transform (:189-220)
+  TrajectoryMotionCompensation        the de-skew of a sweep along the odometry's trajectory (include/trajectory/o3s_trajectory.h)
 
 Timestamps are double seconds.  No arithmetic on clouds happens here; the velocity estimate is one host function of the library
-(o3s_motion_from_poses) so that C++ and Python share one implementation."""
+(o3s_motion_from_poses), and so are the interpolation and extrapolation of poses (o3s_transform_* / o3s_trajectory_*), so that
+C++ and Python share one implementation."""
 from __future__ import annotations
 
 import ctypes as C
@@ -29,6 +32,20 @@ class MotionC(C.Structure):
                 ("is_spinning_clockwise", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class StampedPoseC(C.Structure):
+    """o3s_stamped_pose"""
+    _fields_ = [("t", C.c_double), ("T", C.c_double * 16)]
+
+
+class TrajectoryDeskewC(C.Structure):
+    """o3s_trajectory_deskew"""
+    _fields_ = [("stamp", C.c_double), ("scan_duration", C.c_double), ("calibration", C.c_double * 16), ("is_spinning_clockwise", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+TRAJECTORY_MAX_POSES = 2000   # O3S_TRAJECTORY_MAX_POSES
+
+
 def _L():
     sm._L(), reg._L()
     L = _lib.lib()
@@ -43,6 +60,15 @@ def _L():
         L.o3s_raw_scan_undistort.argtypes = [vp, C.POINTER(MotionC)]
         L.o3s_undistort_cloud.argtypes = [C.c_int, C.POINTER(MotionC), dp, C.c_int64, dp]
         L.o3s_motion_from_poses.argtypes = [dp, C.c_double, dp, C.c_double, C.POINTER(MotionC)]
+        sp, td = C.POINTER(StampedPoseC), C.POINTER(TrajectoryDeskewC)
+        L.o3s_transform_interpolate.argtypes = [sp, sp, C.c_double, sp]
+        L.o3s_transform_extrapolate.argtypes = [sp, sp, C.c_double, sp]
+        L.o3s_trajectory_has.argtypes = [sp, C.c_int64, C.c_double]
+        L.o3s_trajectory_lookup.argtypes = [sp, C.c_int64, C.c_double, dp]
+        L.o3s_trajectory_get_transform.argtypes = [sp, C.c_int64, C.c_double, dp]
+        L.o3s_raw_scan_set_point_times.argtypes = [vp, dp, C.c_int64]
+        L.o3s_raw_scan_undistort_trajectory.argtypes = [vp, sp, C.c_int64, td]
+        L.o3s_undistort_cloud_trajectory.argtypes = [C.c_int, sp, C.c_int64, td, dp, dp, C.c_int64, dp]
         L.o3s_scan_preprocess_staged.argtypes = [vp, C.POINTER(CropperC), C.c_double, C.POINTER(CropperC), vp, C.POINTER(C.c_int64),
                                                  C.POINTER(C.c_int64)]
         L.o3s_scan_registration_icp.argtypes = [vp, C.c_int, vp, C.c_int, C.c_double, dp, C.POINTER(reg._Estimation), C.POINTER(reg._Criteria),
@@ -80,6 +106,77 @@ def undistort_cloud(points, motion: MotionC, device: int = 0, in_place: bool = F
         raise ValueError("scan_duration must be > 0")
     if rc != _lib.OK:
         raise RuntimeError(f"o3s_undistort_cloud failed with o3s_status {rc}")
+    return out
+
+
+def stamped_pose(t, T) -> StampedPoseC:
+    p = StampedPoseC()
+    p.t = float(t)
+    p.T[:] = np.asarray(T, np.float64).reshape(4, 4).T.reshape(16)
+    return p
+
+
+def pose_table(stamps, poses):
+    """A table of o3s_stamped_pose in buffer order (a ctypes array; empty tables are one unused entry long)."""
+    tab = (StampedPoseC * max(len(stamps), 1))()
+    for k, (t, T) in enumerate(zip(stamps, poses)):
+        tab[k].t = float(t)
+        tab[k].T[:] = np.asarray(T, np.float64).reshape(4, 4).T.reshape(16)
+    return tab
+
+
+def _mat(T16) -> np.ndarray:
+    return np.array(T16[:], np.float64).reshape(4, 4).T.copy()
+
+
+def _two_pose_call(fn, name, start, end, t):
+    out = StampedPoseC()
+    rc = fn(C.byref(stamped_pose(*start)), C.byref(stamped_pose(*end)), float(t), C.byref(out))
+    if rc == _lib.ERR_BAD_ARGUMENT:
+        raise ValueError(f"{name}: the stamps do not allow it")
+    if rc != _lib.OK:
+        raise RuntimeError(f"{name} failed with o3s_status {rc}")
+    return out.t, _mat(out.T)
+
+
+def transform_interpolate(start, end, t):
+    """interpolate (Transform.cpp:16-67) between two (stamp, pose) pairs: (t, pose).  ValueError where the reference throws."""
+    return _two_pose_call(_L().o3s_transform_interpolate, "o3s_transform_interpolate", start, end, t)
+
+
+def transform_extrapolate(start, end, t):
+    """extrapolate (Transform.cpp:69-110) beyond `end`: (stamp, pose).  ValueError where the reference throws."""
+    return _two_pose_call(_L().o3s_transform_extrapolate, "o3s_transform_extrapolate", start, end, t)
+
+
+def make_trajectory_deskew(stamp, scan_duration=0.1, is_spinning_clockwise=True, calibration=None) -> TrajectoryDeskewC:
+    p = TrajectoryDeskewC()
+    p.stamp, p.scan_duration = float(stamp), float(scan_duration)
+    p.calibration[:] = np.asarray(np.eye(4) if calibration is None else calibration, np.float64).reshape(4, 4).T.reshape(16)
+    p.is_spinning_clockwise = int(bool(is_spinning_clockwise))
+    return p
+
+
+def _trajectory_status(rc, what):
+    if rc == _lib.ERR_BAD_ARGUMENT:
+        raise ValueError(f"{what}: 1 .. {TRAJECTORY_MAX_POSES} poses with stamps in order, point times for every point or a scan_duration > 0")
+    if rc != _lib.OK:
+        raise RuntimeError(f"{what} failed with o3s_status {rc}")
+
+
+def undistort_cloud_trajectory(points, table, K, params: TrajectoryDeskewC, point_times=None, device: int = 0, in_place: bool = False) -> np.ndarray:
+    """The de-skew along a trajectory on a host cloud (o3s_undistort_cloud_trajectory); table: pose_table(...) of K poses."""
+    p = np.ascontiguousarray(points, np.float64)
+    if in_place and p is not points:
+        raise ValueError("in_place needs a contiguous float64 array")
+    dt = None
+    if point_times is not None:
+        dt = np.ascontiguousarray(point_times, np.float64)
+        if dt.shape != (p.shape[0],):
+            raise ValueError("point_times: one offset per point")
+    out = p if in_place else np.empty_like(p)
+    _trajectory_status(_L().o3s_undistort_cloud_trajectory(device, table, int(K), C.byref(params), _d(p), _d(dt), p.shape[0], _d(out)),
+                       "o3s_undistort_cloud_trajectory")
     return out
 
 
@@ -123,6 +220,18 @@ class RawScan:
             raise ValueError("scan_duration must be > 0")
         if rc != _lib.OK:
             raise RuntimeError(f"o3s_raw_scan_undistort failed with o3s_status {rc}")
+
+    def set_point_times(self, point_times):
+        """The driver's per-point time offsets (seconds after the sweep's stamp) of the staged sweep; the next upload drops them."""
+        dt = np.ascontiguousarray(point_times, np.float64).reshape(-1)
+        rc = self._lib.o3s_raw_scan_set_point_times(self._h, _d(dt), dt.shape[0])
+        if rc == _lib.ERR_BAD_ARGUMENT:
+            raise ValueError("point_times: one offset per staged point")
+        if rc != _lib.OK:
+            raise RuntimeError(f"o3s_raw_scan_set_point_times failed with o3s_status {rc}")
+
+    def undistort_trajectory(self, table, K, params: TrajectoryDeskewC):
+        _trajectory_status(self._lib.o3s_raw_scan_undistort_trajectory(self._h, table, int(K), C.byref(params)), "o3s_raw_scan_undistort_trajectory")
 
 
 def preprocess_staged(scan: sm.ProcessedScan, map_builder_cropper: CropperC, voxel_size: float, scan_matcher_cropper: CropperC, raw: RawScan):
@@ -219,6 +328,76 @@ class TransformBuffer:
             if tk == t:
                 return self._T[k]
         raise RuntimeError("TransformBuffer: no pose at the requested stamp")
+
+
+class TransformInterpolationBuffer(TransformBuffer):
+    """TransformInterpolationBuffer as the reference has it: the push rules and accessors of TransformBuffer, has(t) over the range
+    of the buffer and the lookup that interpolates between the two neighbouring poses (:100-149).  The arithmetic is the
+    library's (o3s_trajectory_lookup): C++ and Python share one implementation."""
+
+    def __init__(self, size_limit: int = 2000):
+        super().__init__(size_limit)
+        self._table = None
+
+    def push(self, t, T):
+        super().push(t, T)
+        self._table = None
+
+    def table(self):
+        """The buffer as a table of o3s_stamped_pose (built once per change of the buffer)."""
+        if self._table is None:
+            self._table = pose_table(self._t, self._T)
+        return self._table
+
+    def lookup(self, t):
+        out = (C.c_double * 16)()
+        rc = _L().o3s_trajectory_lookup(self.table(), len(self._t), float(t), out)
+        if rc == _lib.ERR_BAD_ARGUMENT:
+            raise RuntimeError(f"TransformInterpolationBuffer: missing transform for {t!r}")
+        if rc != _lib.OK:
+            raise RuntimeError(f"o3s_trajectory_lookup failed with o3s_status {rc}")
+        return _mat(out)
+
+
+def get_transform(t, buffer: TransformInterpolationBuffer):
+    """getTransform(time, buffer) (:189-220): the earliest pose before the buffer, the extrapolation from the third pose from the
+    end after it (the latest pose while it holds fewer than three), else the lookup."""
+    buffer._need()
+    out = (C.c_double * 16)()
+    rc = _L().o3s_trajectory_get_transform(buffer.table(), buffer.size(), float(t), out)
+    if rc != _lib.OK:
+        raise RuntimeError(f"o3s_trajectory_get_transform failed with o3s_status {rc}")
+    return _mat(out)
+
+
+class TrajectoryMotionCompensation:
+    """The de-skew of a sweep along the trajectory an interpolating buffer holds (o3s_*_undistort_trajectory): every point is
+    expressed in the sensor frame at the sweep's stamp.  Point times come from the driver (point_times), else from the azimuth as
+    in ConstantVelocityMotionCompensation (scan_duration, is_spinning_clockwise)."""
+
+    def __init__(self, buffer: TransformInterpolationBuffer, scan_duration: float = 0.1, is_spinning_clockwise: bool = True, calibration=None):
+        if not scan_duration > 0.0:
+            raise ValueError("scan_duration must be > 0")
+        self.buffer = buffer
+        self.scan_duration = float(scan_duration)
+        self.is_spinning_clockwise = bool(is_spinning_clockwise)
+        self.calibration = np.eye(4) if calibration is None else np.array(calibration, np.float64).reshape(4, 4)
+
+    def params(self, stamp) -> TrajectoryDeskewC:
+        return make_trajectory_deskew(stamp, self.scan_duration, self.is_spinning_clockwise, self.calibration)
+
+    def undistort_cloud(self, points, stamp, point_times=None, device: int = 0):
+        """A host cloud de-skewed; with an empty buffer the cloud as it came."""
+        if self.buffer.empty():
+            return np.ascontiguousarray(points, np.float64)
+        return undistort_cloud_trajectory(points, self.buffer.table(), self.buffer.size(), self.params(stamp), point_times, device)
+
+    def undistort(self, raw_scan: RawScan, stamp, point_times=None):
+        """The staged sweep de-skewed in place; with an empty buffer nothing happens."""
+        if point_times is not None:
+            raw_scan.set_point_times(point_times)
+        if not self.buffer.empty():
+            raw_scan.undistort_trajectory(self.buffer.table(), self.buffer.size(), self.params(stamp))
 
 
 class ConstantVelocityMotionCompensation:
