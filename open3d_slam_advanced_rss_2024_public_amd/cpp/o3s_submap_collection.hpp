@@ -17,6 +17,9 @@
 //   computeFeatures(idx): Submap::computeFeatures (Submap.cpp:255-275) of a submap on the device (o3s_submap_compute_features),
 //              and with it the occupancy snapshot voxelMap_ (:260-264) at 2.5 x mapVoxelSize (Submap.cpp:239-240, magic.hpp:16);
 //              the caller keeps the reference's timer (minSecondsBetweenFeatureComputation_) and decides when to call it.
+//   :257-289   computeFeatures(finishedSubmapIds): the features of every finished submap, each pushed to the loop-closure candidates,
+//              and the odometry constraints (parent -> finished) of all of them in ONE device call into odometryConstraints_
+//              (o3s_constraint_builders.hpp), one after the other on the caller; getOdometryConstraints, popLoopClosureCandidates
 //   :324-375   transform: which increment goes to which submap (planSubmapTransforms, o3s_pose_graph.hpp), applied to all resident
 //              submaps by ONE o3s_submaps_transform call; per submap mapToRangeSensor_ * T, T * submapCenter_, the dense map where the
 //              driver keeps one (Submap.cpp:115-128); the overlap buffer is flushed
@@ -44,6 +47,7 @@
 #include <vector>
 
 #include "assembled_map/o3s_assembled_map.h"
+#include "o3s_constraint_builders.hpp"
 #include "o3s_icp.hpp"
 #include "o3s_pose_graph.hpp"
 #include "o3s_scan.h"
@@ -210,6 +214,27 @@ class SubmapCollectionHip {
     if (voxel_ > 0.0) submaps_.at(idx).map->buildVoxelMap(kVoxelExpansionFactorAdjacencyBasedRevisiting * voxel_);  // Submap.cpp:260-264
     return o3s_submap_features_size(submaps_.at(idx).map->handle());
   }
+  // SubmapCollection::computeFeatures(finishedSubmapIds) (:257-281): the features of every finished submap, each pushed to the
+  // loop-closure candidates, and the odometry constraints of the finished submaps into the collection's own list (one device call:
+  // o3s_constraint_builders.hpp).  The reference runs the features on a second thread; here the two steps run one after the other on
+  // the caller (both settle and use the streams of the same submaps).
+  void computeFeatures(const std::vector<std::pair<std::size_t, double>>& finishedSubmapIds, const o3s_submap_feature_params* params = nullptr) {
+    for (const auto& id : finishedSubmapIds) {
+      computeFeatures(id.first, params);
+      loopClosureCandidates_.push_back(id);
+    }
+    computeOdometryConstraints(*this, finishedSubmapIds, &odometryConstraints_);
+  }
+  const Constraints& getOdometryConstraints() const { return odometryConstraints_; }  // :287-289
+  std::vector<std::pair<std::size_t, double>> popLoopClosureCandidates() {                // loopClosureCandidatesIdxs_.popAllElements()
+    std::vector<std::pair<std::size_t, double>> out;
+    out.swap(loopClosureCandidates_);
+    return out;
+  }
+  const o3s_submap* submapHandle(std::size_t i) { return submaps_.at(i).map->handle(); }
+  double mapVoxelSize() const { return voxel_; }
+  bool isRefineOdometryConstraintsBetweenSubmaps() const { return isRefineOdometryConstraints_; }  // Parameters.hpp:177; every parameter file: false
+  void setRefineOdometryConstraintsBetweenSubmaps(bool on) { isRefineOdometryConstraints_ = on; }
   // SubmapCollection::isSwitchingSubmapsConsistant (:392-407) as written in its commented body, over the resident merge cloud of
   // `scan` (what insertScan passes as preProcessedScan).  A candidate without a snapshot has fitness 0; an empty scan NaN: both false.
   bool isSwitchingSubmapsConsistant(const o3s_scan* scan, std::size_t newActiveSubmapCandidate, const double mapToRangeSensor[16]) {
@@ -464,6 +489,9 @@ class SubmapCollectionHip {
   std::deque<Buffered> buffer_;
   std::vector<o3s_scan*> free_;
   std::deque<std::pair<std::size_t, double>> finished_;
+  std::vector<std::pair<std::size_t, double>> loopClosureCandidates_;  // loopClosureCandidatesIdxs_
+  Constraints odometryConstraints_;
+  bool isRefineOdometryConstraints_ = false;
   AdjacencyHip adjacency_;
   std::map<std::size_t, DenseMapHip*> denseMaps_;
 };

@@ -1251,6 +1251,12 @@ struct RegArea {
   Buf ov_src, ov_tgt, ov_tgtn;   // the two selected clouds of o3s_o3d_registration_icp_submaps_overlap
   Buf ov_srcn;                   // ... and the source's selected normals (Generalized ICP)
   O3dIcpWork reg;
+  PostBlock<> oc_res;            // what o3s_submaps_odometry_constraints reads back: every pair's sums and counts (constraints_impl.h)
+  size_t oc_res_bytes = 0;
+  RegArea() = default;
+  RegArea(const RegArea&) = delete;
+  RegArea& operator=(const RegArea&) = delete;
+  ~RegArea() { oc_res.release(); }  // only ever runs through o3s_o3d_registration_release, like ~O3dIcpWork
 };
 struct RegPool {
   std::mutex m;

@@ -292,3 +292,28 @@ def update_submaps_and_trajectory(problem: OptimizationProblem, collection, mapp
         cs[i] = c
     collection.update_adjacency_matrix(cs)
     return increments
+
+
+def loop_closure_step(collection, place_recognition, problem: OptimizationProblem, candidates, device_call=None, refine_call=None):
+    """The body of SlamWrapper::loopClosureWorker (SlamWrapper.cpp:1068-1099), once: the loop-closure constraints of the candidates
+    ((submap id, time stamp), SubmapCollection::buildLoopClosureConstraints :291-299); none: return [] and leave the problem alone;
+    else a COPY of the collection's odometry constraints completed with the all-submaps overload of computeOdometryConstraints,
+    the problem's odometry constraints cleared, both kinds inserted, the problem built and solved.  Returns the loop-closure
+    constraints: what update_submaps_and_trajectory then takes as last_constraints."""
+    from .constraint_builders import compute_odometry_constraints
+
+    loop_closure_constraints = []
+    for submap_id, stamp in candidates:
+        loop_closure_constraints.extend(place_recognition.buildLoopClosureConstraints(
+            collection.range_sensor_poses[collection.active], collection, int(submap_id), collection.active, stamp))
+    if not loop_closure_constraints:
+        return []
+    odometry_constraints = list(collection.getOdometryConstraints())
+    compute_odometry_constraints(collection, odometry_constraints, None, device_call or getattr(collection, "_odometry_call", None),
+                                 refine_call or getattr(collection, "_refine_call", None))
+    problem.clear_odometry_constraints()
+    problem.insert_loop_closure_constraints(loop_closure_constraints)
+    problem.insert_odometry_constraints(odometry_constraints)
+    problem.build_optimization_problem()
+    problem.solve()
+    return loop_closure_constraints

@@ -17,12 +17,18 @@ class SubmapCollection:
     same steps as cpp/o3s_submap_collection.hpp, resident scans in a ring of numScansOverlap + 1 objects."""
 
     def __init__(self, radius, min_num, max_points, overlap, map_voxel, map_builder_cropper, submap_factory=None, scan_factory=None,
-                 transform_maps=None, assemble_maps=None):
+                 transform_maps=None, assemble_maps=None, odometry_constraints_call=None, refine_call=None):
         """map_builder_cropper: (kind, p0[, p1, p2]) as for cloud_ops.croppingVolumeFactory.  submap_factory / scan_factory:
         stand-ins for the device-resident objects (insertProcessed / __len__ / computeSubmapCenter) — the CPU tests of the
         switching rules use them; the default is the real thing.  transform_maps(maps, Ts): the one batched device call of
         transform() (submap.transform_submaps unless a stand-in is given).  assemble_maps(out, maps, voxel_size, normals, colors):
-        the one device call of assembleMap() (AssembledMap.build unless a stand-in is given)."""
+        the one device call of assembleMap() (AssembledMap.build unless a stand-in is given).  odometry_constraints_call / refine_call:
+        the device calls of the odometry constraints (constraint_builders.submaps_odometry_constraints and the refinement unless
+        stand-ins are given)."""
+        self._odometry_call, self._refine_call = odometry_constraints_call, refine_call
+        self.refine_odometry_constraints = False   # isRefineOdometryConstraintsBetweenSubmaps_ (Parameters.hpp:177; every parameter file: false)
+        self.odometry_constraints = []             # SubmapCollection::odometryConstraints_
+        self.loop_closure_candidates = []          # loopClosureCandidatesIdxs_: (submap id, time stamp)
         self._transform_maps = transform_maps or transform_submaps
         self._assemble_maps = assemble_maps or AssembledMap.build
         self.radius, self.min_num, self.max_points, self.overlap = radius, min_num, max_points, overlap
@@ -111,7 +117,22 @@ class SubmapCollection:
 
     def computeFeatures(self, i, params=None):
         """Submap::computeFeatures of submap i (Submap.cpp:255-275): the feature set and, with it, the occupancy snapshot voxelMap_ at
-        2.5 x the map voxel size (:239-240, :260-264).  Returns the number of sparse points."""
+        2.5 x the map voxel size (:239-240, :260-264).  Returns the number of sparse points.
+        With a list of finished (submap id, time stamp) instead of an index: SubmapCollection::computeFeatures(finishedSubmapIds)
+        (SubmapCollection.cpp:257-281) — the features of every finished submap, each pushed to the loop-closure candidates, and the
+        odometry constraints of the finished submaps into the collection's own list (one device call).  The reference runs the
+        features on a second thread; here the two steps run one after the other on the caller (both settle and use the streams of
+        the same submaps).  Returns the list of sparse-point counts."""
+        if not isinstance(i, (int, np.integer)):
+            from .constraint_builders import compute_odometry_constraints
+
+            finished = [(int(f[0]), f[1]) for f in i]
+            counts = []
+            for f in finished:
+                counts.append(self.computeFeatures(f[0], params))
+                self.loop_closure_candidates.append(f)
+            compute_odometry_constraints(self, self.odometry_constraints, finished, self._odometry_call, self._refine_call)
+            return counts
         n = self.maps[i].computeFeatures(params)
         if self.map_voxel > 0.0:
             self.maps[i].buildVoxelMap(VOXEL_EXPANSION_FACTOR_ADJACENCY_BASED_REVISITING * self.map_voxel)
@@ -178,6 +199,15 @@ class SubmapCollection:
     def _insert_into(self, i, ps, T):
         self.range_sensor_poses[i] = np.array(T, np.float64)   # Submap.cpp:45
         self.maps[i].insertProcessed(ps, T)
+
+    def getOdometryConstraints(self):
+        """SubmapCollection::getOdometryConstraints (:287-289)"""
+        return self.odometry_constraints
+
+    def popLoopClosureCandidates(self):
+        """loopClosureCandidatesIdxs_.popAllElements(), as SlamWrapper's workers take them"""
+        out, self.loop_closure_candidates = self.loop_closure_candidates, []
+        return out
 
     def pop_finished(self):
         """SubmapCollection::popFinishedSubmapIds (:53-55)."""
