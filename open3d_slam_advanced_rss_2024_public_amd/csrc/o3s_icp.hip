@@ -1768,6 +1768,9 @@ int64_t o3s_icp_hook_export_matches(o3s_icp* h, int32_t* ids, float* dists2, int
   if (hipStreamSynchronize(h->stream) != hipSuccess) return 0;
   return N;
 }
+// hooks build only: the way the solver went in the last iteration of the last minimize / compute — IcpState::solve_branch as that
+// call fetched it (0 LLT: the fast path or the general path at rank 6, 1 minimum norm or rank 0, 2 fp64 fallback); -1 without a handle
+int o3s_test_last_solve_branch(const o3s_icp* h) { return h ? (int)h->stage->state.solve_branch : -1; }
 #endif
 
 int64_t o3s_icp_get_reading_order(const o3s_icp* h, int32_t* order, int64_t cap) {
