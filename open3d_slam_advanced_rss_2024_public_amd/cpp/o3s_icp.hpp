@@ -19,6 +19,7 @@
 #include "o3s_icp.h"
 #include "o3s_dense_map.h"
 #include "o3s_submap.h"
+#include "localizability/o3s_localizability.h"
 
 namespace o3s {
 
@@ -76,6 +77,14 @@ class IcpHip {
     o3s_icp_fitness f{};
     raise(o3s_icp_evaluate_resident(h_, T, maxCorrespondenceDistance, &f));
     return f;
+  }
+  // Which directions of the pose the kept pairs of the last successful compute constrained (o3s_icp_localizability: four launches
+  // behind the chain, one round trip).  params: the three sums have no default (o3s_localizability_default_params leaves them NaN).
+  // Call it before evaluate(): the fitness replaces the match streams the analysis reads.
+  o3s_localizability localizability(const o3s_localizability_params& params) {
+    o3s_localizability out{};
+    raise(o3s_icp_localizability(h_, &params, &out));
+    return out;
   }
   o3s_icp* handle() { return h_; }
 

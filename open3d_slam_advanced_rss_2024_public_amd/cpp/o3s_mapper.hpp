@@ -26,6 +26,9 @@
 //                 isIgnoreMinRefinementFitness is off, a registration whose fitness (o3s_icp_evaluate_resident at the pose it
 //                 returned) is below minRefinementFitness gives the scan up: return false, nothing adopted, pushed or inserted
 //   :435          result cast back to double
+//   (no counterpart) degeneracyPolicy: the localizability analysis of that registration (o3s_localizability.h) behind the compute;
+//                 Report keeps it for getLatestLocalizability(), Remap also replaces the pose by o3s_localizability_remap(prior, result):
+//                 the ICP's correction in the directions the scan constrained, the prior in the others.  Off (the default): no call
 //   :440-455      isNewValueSetMapper_: adopt the GIVEN pose, skip this scan's result and the insert, ignore odometry next time
 //   :465-479      initial-map mode: no merging (or not before mapMergeDelayInSeconds_)
 //   :483-489      insert the merge cloud if the sensor moved at least minMovementBetweenMappingSteps_
@@ -96,12 +99,33 @@ struct MapperParams {
   // The odometry prior at ANY stamp (Mapper.cpp:219-224, 237-261, 268-280): getTransform over an interpolating buffer, which is what
   // an external odometry source needs (its poses never carry the LiDAR's stamps).  false = exact stamps only, as before
   bool isInterpolateOdometry = false;
+  // What to do about a registration whose scan left directions of the pose unconstrained (a corridor, a tunnel, an open field).
+  // Off: nothing, not even the analysis.  Report: run it, keep the result.  Remap: also keep the prior in the directions whose
+  // category is below remapMinCategory.  `localizability`: the thresholds — its three sums have no default and must be calibrated
+  // (run Report on a well-constrained recording and read sum_all / sum_strong); unset, Report and Remap throw at construction.
+  enum class DegeneracyPolicy { Off, Report, Remap };
+  DegeneracyPolicy degeneracyPolicy = DegeneracyPolicy::Off;
+  o3s_localizability_params localizability = defaultLocalizability();
+  std::int32_t remapMinCategory = 1;
+  static o3s_localizability_params defaultLocalizability() {
+    o3s_localizability_params p;
+    o3s_localizability_default_params(&p);
+    return p;
+  }
 };
 
 class MapperHip {
  public:
   MapperHip(const MapperParams& p, const o3s_icp_config& icpCfg, int device = 0)
-      : params_(p), icp_(icpCfg, device), submaps_(p.submaps, p.mapVoxelSize, p.mapBuilderCropper, p.isUseInitialMap, device), device_(device) {}
+      : params_(p), icp_(icpCfg, device), submaps_(p.submaps, p.mapVoxelSize, p.mapBuilderCropper, p.isUseInitialMap, device), device_(device) {
+    if (p.degeneracyPolicy != MapperParams::DegeneracyPolicy::Off) {
+      o3s_localizability unused;  // (a NULL handle: the parameters are checked first, nothing else is)
+      if (o3s_icp_localizability(nullptr, &p.localizability, &unused) == O3S_ERR_BAD_CONFIG)
+        throw std::runtime_error("MapperParams::localizability: the thresholds are unset or out of order");
+      if (p.remapMinCategory != 1 && p.remapMinCategory != 2) throw std::runtime_error("MapperParams::remapMinCategory must be 1 or 2");
+    }
+    lastLocalizability_.kept = -1;
+  }
   ~MapperHip() { o3s_raw_scan_destroy(deskewStage_); }
   MapperHip(const MapperHip&) = delete;
   MapperHip& operator=(const MapperHip&) = delete;
@@ -197,6 +221,13 @@ class MapperHip {
   // covariance of the latest scan-to-map registration (IcpHip::getCovariance: zeros under the plain minimiser); NaN when that
   // registration failed and the prior was kept (Mapper.cpp:420-422), or before the first one
   const std::array<double, 36>& getLatestRegistrationCovariance() const { return lastCovariance_; }
+  // the localizability analysis of the latest scan-to-map registration (degeneracyPolicy Report / Remap); kept = -1 when there is
+  // none: the policy is Off, that registration failed, or before the first one.  lastRemapReplaced(): the directions in which
+  // Remap kept the prior on the last scan (0 under Off / Report)
+  const o3s_localizability& getLatestLocalizability() const { return lastLocalizability_; }
+  int lastRemapReplaced() const { return lastRemapReplaced_; }
+  // the pose the ICP itself returned on the last scan, before any remap (the prior when it threw)
+  const Mat4& lastRegistrationPose() const { return lastRegistrationPose_; }
 
   // rawScan in the sensor frame (3 x N doubles, normals nullable when normal estimation is configured on the scan object)
   bool addRangeMeasurement(const double* rawPts, const double* rawNormals, std::int64_t N, double timestamp) {
@@ -234,7 +265,10 @@ class MapperHip {
     lastInserted_ = lastReferenceReset_ = lastIcpThrew_ = lastFitnessRejected_ = false;
     lastFitness_ = o3s_icp_fitness{};
     lastFitness_.fitness = std::numeric_limits<double>::quiet_NaN();
-    bool haveFitness = false;
+    bool haveFitness = false, haveLocalizability = false;
+    lastLocalizability_ = o3s_localizability{};
+    lastLocalizability_.kept = -1;
+    lastRemapReplaced_ = 0;
     lastTimings_ = MapperTimings{};
     if (!params_.isUseInitialMap && !isCalibrationSet_) return false;  // "Calibration is not set. Returning from mapping." (:169-174)
     scan_ = submaps_.scanForNextMeasurement();  // stays ours until submaps_.insertScan takes it into its overlap buffer
@@ -328,6 +362,10 @@ class MapperHip {
       lastIterations_ = st.iterations;
       if (rc != O3S_OK) throw std::runtime_error(o3s_last_error(icp_.handle()));  // every libpointmatcher exception derives from it
       lastCovariance_ = icp_.getCovariance();
+      if (params_.degeneracyPolicy != MapperParams::DegeneracyPolicy::Off) {  // before the fitness: that replaces the match streams
+        lastLocalizability_ = icp_.localizability(params_.localizability);
+        haveLocalizability = true;
+      }
       if (!params_.isIgnoreMinRefinementFitness) {  // result.fitness_ of :425, inside the registration's stopwatch
         lastFitness_ = icp_.evaluate(nullptr, (float)params_.fitnessMaxCorrespondenceDistance);
         haveFitness = true;
@@ -338,6 +376,9 @@ class MapperHip {
       if (!resetRef && nPatchNow < 0 && submaps_.activeSubmap().patchCount(patch, mapToRangeSensor_.m) == 0) return false;
       lastIcpThrew_ = true;  // :420-422: the prior stays (corrected32 must not hold a half-written result)
       lastCovariance_.fill(std::numeric_limits<double>::quiet_NaN());
+      haveLocalizability = false;
+      lastLocalizability_ = o3s_localizability{};
+      lastLocalizability_.kept = -1;
       for (int k = 0; k < 16; ++k) corrected32[k] = prior32[k];
       // a compute that failed before it waited for its stream may leave the asynchronous index build / the reading's hand-over in
       // flight: nothing below may rewrite the buffers they read until the handle's stream has drained
@@ -350,6 +391,17 @@ class MapperHip {
     }
     Mat4 corrected{};
     for (int k = 0; k < 16; ++k) corrected.m[k] = (double)corrected32[k];  // :435
+    lastRegistrationPose_ = corrected;
+    if (haveLocalizability && params_.degeneracyPolicy == MapperParams::DegeneracyPolicy::Remap) {
+      // the prior is the initial guess the chain was handed (fp32, :323); with every direction kept the result is copied bit for bit
+      Mat4 prior{}, remapped{};
+      for (int k = 0; k < 16; ++k) prior.m[k] = (double)prior32[k];
+      std::int32_t replaced = 0;
+      if (o3s_localizability_remap(&lastLocalizability_, params_.remapMinCategory, prior.m, corrected.m, remapped.m, &replaced) == O3S_OK) {
+        corrected = remapped;
+        lastRemapReplaced_ = (int)replaced;
+      }  // (refused: a correction of pi / 2 or more is not one to linearise — the ICP's pose stays)
+    }
     // ---- pose reset (:440-455) ----
     if (isNewValueSetMapper_) {  // the GIVEN pose is adopted; lastMeasurementTimestamp_ is left as it was (:440-455)
       initTime_ = timestamp;
@@ -445,12 +497,14 @@ class MapperHip {
   o3s_motion lastMotion_{};
   int device_ = 0;
   Mat4 mapToRangeSensor_ = Mat4::identity(), mapToRangeSensorPrev_ = Mat4::identity(), lastPrior_ = Mat4::identity();
-  Mat4 mapToRangeSensorLastScanInsertion_ = Mat4::identity();
+  Mat4 mapToRangeSensorLastScanInsertion_ = Mat4::identity(), lastRegistrationPose_ = Mat4::identity();
   double lastMeasurementTimestamp_ = 0.0, lastReferenceInitializationTimestamp_ = 0.0, initTime_ = 0.0;
   bool haveLast_ = false, haveRef_ = false;  // haveLast_: lastMeasurementTimestamp_ holds a stamp (the reference leaves it default-constructed after the first scan, whose lookup would throw: no odometry prior is formed then)
   bool isNewValueSetMapper_ = false, isIgnoreOdometryPrediction_ = false;
   bool lastInserted_ = false, lastReferenceReset_ = false, lastIcpThrew_ = false, lastFitnessRejected_ = false;
   o3s_icp_fitness lastFitness_{};
+  o3s_localizability lastLocalizability_{};
+  int lastRemapReplaced_ = 0;
   std::array<double, 36> lastCovariance_ = nanCovariance();
   int lastIterations_ = 0;
   Mat4 calibration_ = Mat4::identity(), calibrationInv_ = Mat4::identity();

@@ -18,6 +18,7 @@
 #include "icp_kernels.h"
 #include "icp_shard_kernels.h"
 #include "icp_types.h"
+#include "localizability_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -161,6 +162,9 @@ struct o3s_icp {
   float last_max_out_r2 = 0.f;  // the kept-pair predicate's MaxDist bound of that compute
   float last_step[16] = {0};    // ... and its last iteration's step (IcpState::dT)
   unsigned long long cov_t_start = 0, cov_t_end = 0;  // wall_clock64 stamps of the last covariance pass (k_cov's start, k_cov_post's end)
+  // localizability analysis (localizability_impl.h): the work area of its four kernels, allocated by the first call.  No captured
+  // kernel points into it, so it stays out of all_bufs() and a first call leaves the chain's graph alone
+  DevBuf d_loc;
   // registration fitness (o3s_icp_evaluate_resident): where the last successful compute left the reading.  pose_valid: that compute's
   // T_iter is in last_T_iter and nothing has replaced the reading or the reference since; r_is_call: d_r still holds the reading as
   // that compute prepared it (T0 . p in its processing order) — an evaluation at an explicit pose prepares it anew
@@ -1415,7 +1419,7 @@ int o3s_icp_create(const o3s_icp_config* cfg, int device, o3s_icp** out) {
   if (e == hipSuccess) e = hipHostMalloc((void**)&h->stage, sizeof(HostStage), hipHostMallocDefault);
   if (e == hipSuccess) e = h->mb.alloc(64);
   if (e == hipSuccess) e = h->post.alloc();
-  if (e == hipSuccess) e = h->cov_mb.alloc((size_t)(host_post::kPostVals + 2 * (kCovComps + 2)) * 4);
+  if (e == hipSuccess) e = h->cov_mb.alloc((size_t)(host_post::kPostVals + 2 * std::max(kCovComps + 2, kern::kLocPostVals)) * 4);  // its largest post
   if (e == hipSuccess) {
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) h->wall_clock_khz = (double)khz;
@@ -1441,6 +1445,7 @@ void o3s_icp_destroy(o3s_icp* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
   for (DevBuf* b : h->all_bufs()) b->release();
+  h->d_loc.release();
   for (hipEvent_t e : h->prof_events) (void)hipEventDestroy(e);
   if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
   if (h->ev_end) (void)hipEventDestroy(h->ev_end);
@@ -2162,3 +2167,5 @@ int64_t o3s_icp_get_error_elements(o3s_icp* h, float* reading_c, float* referenc
 }
 
 }  // extern "C"
+
+#include "localizability_impl.h"

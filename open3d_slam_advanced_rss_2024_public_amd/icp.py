@@ -478,6 +478,31 @@ class ICP:
         self._check(self._L.o3s_icp_covariance_gpu_us(self._h, out))
         return float(out[0]), float(out[1])
 
+    def localizability(self, params):
+        """The localizability analysis of the last successful compute (o3s_icp_localizability): which directions of the pose its
+        kept pairs constrained.  params: localizability.LocalizabilityParams with the three sums set."""
+        from . import localizability as loc
+
+        out = loc.LocalizabilityC()
+        p = params.to_c()
+        loc._bind(self._L)
+        self._check_cov(self._L.o3s_icp_localizability(self._h, C.byref(p), C.byref(out)))
+        return loc.Localizability.from_c(out)
+
+    def estimate_localizability(self, reading_c, normals, params):
+        """The same kernels on (K, 3) arrays of ALREADY centred pairs (o3s_localizability_estimate)."""
+        from . import localizability as loc
+
+        p = np.ascontiguousarray(reading_c, np.float32).reshape(-1, 3)
+        n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if p.shape != n.shape:
+            raise ValueError("reading_c and normals must have the same shape (K, 3)")
+        out = loc.LocalizabilityC()
+        pc = params.to_c()
+        loc._bind(self._L)
+        self._check(self._L.o3s_localizability_estimate(self._h, _fp(p), _fp(n), p.shape[0], C.byref(pc), C.byref(out)))
+        return loc.Localizability.from_c(out)
+
     def get_max_num_iterations_reached(self) -> bool:
         """ICP::getMaxNumIterationsReached (PointMatcher.h:786)."""
         return self.stats.max_iters_reached

@@ -80,6 +80,16 @@ class Mapper:
         self.calibration = np.eye(4)
         self.trajectory_compensation = None   # enable_trajectory_motion_compensation
         self.last_deskewed = None             # the sweep as the last trajectory de-skew handed it to the pre-processing
+        # MapperParams::degeneracyPolicy (localizability.OFF / REPORT / REMAP): what to do about a registration whose scan left
+        # directions of the pose unconstrained.  Off: no call at all.  Report: ICP.localizability behind the compute, kept in
+        # last_localizability.  Remap: also the prior instead of the ICP's correction in the directions below remap_min_category.
+        # localizability_params: localizability.LocalizabilityParams — its three sums have no default
+        self.degeneracy_policy = "Off"
+        self.localizability_params = None
+        self.remap_min_category = 1
+        self.last_localizability = None       # None: the policy is Off, that registration failed, or before the first one
+        self.last_remap_replaced = 0
+        self.last_registration_pose = np.eye(4)
 
     def set_calibration(self, C_):
         self.calibration = np.array(C_, np.float64).reshape(4, 4)
@@ -168,6 +178,9 @@ class Mapper:
         inserted = refreset = threw = 0
         self.flags = (0, 0, 0)
         self.last_fitness, self.last_fitness_rejected = None, False
+        self.last_localizability, self.last_remap_replaced = None, 0
+        if self.degeneracy_policy not in ("Off", "Report", "Remap"):
+            raise ValueError("degeneracy_policy must be 'Off', 'Report' or 'Remap'")
         if not self.use_initial_map and not self.is_calibration_set:
             return False
         self.ps = self.col.scan_for_next()
@@ -215,6 +228,8 @@ class Mapper:
             self.iters = self.icp.stats.iterations
             if hasattr(self.icp, "get_covariance"):   # (the CPU tests' stand-in handles register nothing and have none)
                 self.last_covariance = self.icp.get_covariance()
+            if self.degeneracy_policy != "Off":   # before the fitness: that replaces the match streams
+                self.last_localizability = self.icp.localizability(self.localizability_params)
             if self.check and reset:
                 self.check(self, sp, sn, prior32, corrected32)
             if not self.ignore_min_refinement_fitness:
@@ -225,11 +240,20 @@ class Mapper:
             self.last_covariance = np.full((6, 6), np.nan)
             self.iters = self.icp.stats.iterations
             self.last_fitness = None
+            self.last_localizability = None
         if self.last_fitness is not None and self.last_fitness.fitness < self.min_refinement_fitness:   # Mapper.cpp:425-430
             self.last_fitness_rejected = True
             self.flags = (0, refreset, threw)
             return False
         corrected = corrected32.astype(np.float64)
+        self.last_registration_pose = corrected.copy()   # the ICP's own result, before any remap (the prior when it threw)
+        if self.last_localizability is not None and self.degeneracy_policy == "Remap":
+            from .localizability import remap_pose
+            try:   # the prior is the initial guess the chain was handed (fp32); nothing replaced: the ICP's pose bit for bit
+                corrected, self.last_remap_replaced = remap_pose(self.last_localizability, prior32.astype(np.float64), corrected,
+                                                                 self.remap_min_category)
+            except ValueError:   # a correction of pi / 2 or more is not one to linearise: the ICP's pose stays
+                pass
         if self.new_value:
             self.T_prev = self.T.copy()
             self.pose_buffer.push(stamp, self.T)
