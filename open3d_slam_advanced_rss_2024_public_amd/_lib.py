@@ -291,3 +291,34 @@ def forked_copy(obj) -> bool:
     otherwise abort the worker)."""
     import os
     return getattr(obj, "_pid", None) not in (None, os.getpid())
+
+
+class Handle:
+    """Base of the wrappers that own one device handle (ICP, RawScan, DenseMap, Submap, AssembledMap, ProcessedScan): the library
+    the handle belongs to (_lib), the process that made it (_pid), the handle (_h), and the one way it is made and destroyed.  A
+    subclass names its C destroy function in `_destroy` and makes its handle with _create()."""
+
+    _destroy = None
+
+    def _create(self, L, create: str, *args) -> int:
+        """Calls L.<create>(*args, &handle) and adopts the result; returns the o3s_status.  After a failure the wrapper holds no
+        handle: close() and __del__ have nothing to do.  Also the way in for objects built through __new__ (Submap.clone)."""
+        self._lib = L             # every later call goes through the library the handle was made by (product or a hooks build)
+        self._pid = os.getpid()   # forked_copy: a forked child must not destroy the handle
+        self._h = C.c_void_p()
+        rc = getattr(L, create)(*args, C.byref(self._h))
+        if rc != OK:
+            self._h = C.c_void_p()
+        return rc
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            if not forked_copy(self):   # a forked child drops its copy of the wrapper, the handle is the parent's
+                getattr(self._lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -140,11 +140,11 @@ inline size_t assemble_arena_bytes(int64_t N) {
 
 struct o3s_assembled_map {
   int device = 0;
-  DArr pts, nrm, col;  // the result
+  DevMem pts, nrm, col;  // the result
   int64_t n = 0;
   int has_normals = 0, has_colors = 0;
   Arena arena;         // work area of the voxelising build
-  DArr table;          // the segment table
+  DevMem table;          // the segment table
 };
 
 extern "C" {
@@ -170,7 +170,7 @@ int64_t o3s_assembled_map_size(const o3s_assembled_map* a) { return a ? a->n : 0
 int o3s_assembled_map_has_normals(const o3s_assembled_map* a) { return a && a->n > 0 && a->has_normals ? 1 : 0; }
 int o3s_assembled_map_has_colors(const o3s_assembled_map* a) { return a && a->n > 0 && a->has_colors ? 1 : 0; }
 int64_t o3s_assembled_map_device_bytes(const o3s_assembled_map* a) {
-  return a ? (int64_t)(a->pts.cap + a->nrm.cap + a->col.cap + a->arena.cap + a->table.cap) : 0;
+  return a ? (int64_t)(a->pts.cap + a->nrm.cap + a->col.cap + a->arena.mem.cap + a->table.cap) : 0;
 }
 
 int o3s_assembled_map_build(o3s_assembled_map* a, int32_t n, o3s_submap* const* maps, double voxel_size, int32_t attrs, int64_t* n_out) {
@@ -253,7 +253,7 @@ int o3s_assembled_map_build(o3s_assembled_map* a, int32_t n, o3s_submap* const* 
     CK(a->pts.ensure(bytes, 0, s));
     if (hn) CK(a->nrm.ensure(bytes, 0, s));
     if (hc) CK(a->col.ensure(bytes, 0, s));
-    hipLaunchKernelGGL(k_asm_concat, dim3(nblk(3 * total)), dim3(kB), 0, s, t, total, a->pts.d(), hn ? a->nrm.d() : nullptr, hc ? a->col.d() : nullptr);
+    hipLaunchKernelGGL(k_asm_concat, dim3(nblk(3 * total)), dim3(kB), 0, s, t, total, a->pts.as<double>(), hn ? a->nrm.as<double>() : nullptr, hc ? a->col.as<double>() : nullptr);
     CK(hipGetLastError());
     CK(hipStreamSynchronize(s));
     a->n = total;
@@ -312,8 +312,8 @@ int o3s_assembled_map_build(o3s_assembled_map* a, int32_t n, o3s_submap* const* 
   CK(a->pts.ensure(bytes, 0, s));
   if (hn) CK(a->nrm.ensure(bytes, 0, s));
   if (hc) CK(a->col.ensure(bytes, 0, s));
-  hipLaunchKernelGGL(k_asm_reduce, dim3(nb), dim3(kB), 0, s, t, keys2, vals2, head, ord, N, a->pts.d(), hn ? a->nrm.d() : nullptr,
-                     hc ? a->col.d() : nullptr);
+  hipLaunchKernelGGL(k_asm_reduce, dim3(nb), dim3(kB), 0, s, t, keys2, vals2, head, ord, N, a->pts.as<double>(), hn ? a->nrm.as<double>() : nullptr,
+                     hc ? a->col.as<double>() : nullptr);
   CK(hipGetLastError());
   CK(hipStreamSynchronize(s));
   a->n = n_vox;

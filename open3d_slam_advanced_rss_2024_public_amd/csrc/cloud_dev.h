@@ -9,6 +9,8 @@
 #include "../../include/o3s_icp.h"
 #include "icp_types.h"  // O3S_HOOK_ENV
 #include "host_post.h"
+#include "dev_mem.h"
+#include "lease_pool.h"
 
 #include <string.h>
 
@@ -21,12 +23,16 @@
 #include <cstdint>
 #include <limits>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <vector>
 
 #pragma clang fp contract(off)
 
 namespace {  // internal linkage
+using o3s::Arena;
+using o3s::DevMem;
+using o3s::LeasePool;
 namespace o3s_cloud {
 using namespace o3s::host_post;
 
@@ -67,27 +73,6 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
   return v;
 }
 
-struct Buf {  // grow-only: a second alloc() that fits re-uses the memory (contents are not kept when it has to grow)
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t alloc(size_t bytes) {
-    if (p && bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-    if (e == hipSuccess) cap = bytes ? bytes : 16;
-    return e;
-  }
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-  template <typename T>
-  T* as() const {
-    return reinterpret_cast<T*>(p);
-  }
-};
-
 #define CK(expr)                               \
   do {                                         \
     if ((expr) != hipSuccess) return O3S_ERR_HIP; \
@@ -113,32 +98,9 @@ struct PinnedArea {
   // thread_local / static destructor can run after the HIP runtime has been unloaded (exit-time crashes), and the worker
   // threads of o3s_o3d_registration_icp_batch would otherwise allocate and free two pinned buffers per call.
 };
-struct PinnedPool {
-  std::mutex mu;
-  std::vector<PinnedArea*> idle;
-};
-inline PinnedPool& pinned_pool() {
-  static PinnedPool* pool = new PinnedPool();  // leaked deliberately (see PinnedArea)
-  return *pool;
-}
-struct PinnedLease {  // one per host thread; hands the area back to the pool when the thread ends
-  PinnedArea* a = nullptr;
-  PinnedLease() {
-    PinnedPool& pool = pinned_pool();
-    {
-      std::lock_guard<std::mutex> lk(pool.mu);
-      if (!pool.idle.empty()) {
-        a = pool.idle.back();
-        pool.idle.pop_back();
-      }
-    }
-    if (!a) a = new PinnedArea();
-  }
-  ~PinnedLease() {
-    PinnedPool& pool = pinned_pool();
-    std::lock_guard<std::mutex> lk(pool.mu);
-    pool.idle.push_back(a);
-  }
+struct PinnedLease {  // one per host thread; hands the area back to the pool (one key: the areas are all alike) when the thread ends
+  std::unique_ptr<PinnedArea> a = LeasePool<PinnedArea>::get().take(0);
+  ~PinnedLease() { LeasePool<PinnedArea>::get().give(0, std::move(a)); }
 };
 inline PinnedArea& pinned_area() {
   static thread_local PinnedLease lease;
@@ -148,6 +110,71 @@ inline uint32_t* pinned_words() { return pinned_area().p; }
 inline bool mailbox_enabled(const PinnedArea& pa) { return posts_enabled() && pa.mb; }
 // the sequence number of the post a call is about to issue; 0 (no post: fetch_post copies) with the mailbox off
 inline uint32_t mailbox_open(PinnedArea& pa) { return mailbox_enabled(pa) ? pa.mb.next() : 0u; }
+
+// The calling thread's work area of type T for the duration of a call (the device is current), leased from the device's pool.
+// Every early error return (a failed launch, O3S_ERR_HIP from a post wait, an empty selection behind enqueued compactions) can
+// leave kernels in flight that still read or write the area's buffers: the area goes back to the pool — where a call on another
+// stream or thread may lease it at once — only behind a drained stream.  kAlwaysDrain false: a call that ended through
+// end(O3S_OK) has waited for its stream itself and is not made to wait again; true: every exit drains.
+template <typename T, bool kAlwaysDrain>
+struct AreaLease {
+  const int device;
+  std::unique_ptr<T> a;
+  hipStream_t s = nullptr;  // the stream the call enqueues on
+  bool ok = false;          // the call ended through end(O3S_OK)
+  int end(int rc) {
+    ok = rc == O3S_OK;
+    return rc;
+  }
+  explicit AreaLease(int device_, hipStream_t stream = nullptr) : device(device_), a(LeasePool<T>::get().take(device_)), s(stream) {}
+  AreaLease(const AreaLease&) = delete;
+  AreaLease& operator=(const AreaLease&) = delete;
+  ~AreaLease() {
+    if (kAlwaysDrain || !ok) (void)hipStreamSynchronize(s);
+    LeasePool<T>::get().give(device, std::move(a));
+  }
+  T* operator->() { return a.get(); }
+  T& operator*() { return *a; }
+};
+// what the two *_release entry points do: the idle areas of the device go back to the allocator behind an idle device
+template <typename T>
+inline int release_idle_areas(int device) {
+  const int rc = pick_device(device);
+  if (rc != O3S_OK) return rc;
+  CK(hipDeviceSynchronize());
+  LeasePool<T>::get().drop_idle(device);
+  return O3S_OK;
+}
+
+// Creating a HIP stream makes a hardware queue: 2.6 - 3.5 ms on the calling thread.  Callers that want a few streams per device
+// (the submaps' shared streams, the lanes of the batch registrations) keep one table each: kPerDevice non-blocking streams per
+// device, all made on the first get() for that device (the device is current) and kept for the life of the process — a table
+// is never destroyed: its streams must not be torn down behind the runtime's own exit.
+template <int kPerDevice>
+struct DeviceStreams {
+  struct Set {
+    hipStream_t s[kPerDevice];
+    int n;  // streams made: fewer than kPerDevice only when a hipStreamCreateWithFlags failed (what that means is the caller's call)
+  };
+  Set get(int device) {
+    std::lock_guard<std::mutex> g(m_);
+    if ((size_t)device >= per_device_.size()) per_device_.resize((size_t)device + 1);
+    std::vector<hipStream_t>& v = per_device_[(size_t)device];
+    while (v.size() < (size_t)kPerDevice) {
+      hipStream_t s = nullptr;
+      if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) break;
+      v.push_back(s);
+    }
+    Set out{};
+    out.n = (int)v.size();
+    for (int k = 0; k < out.n; ++k) out.s[k] = v[(size_t)k];
+    return out;
+  }
+
+ private:
+  std::mutex m_;
+  std::vector<std::vector<hipStream_t>> per_device_;
+};
 
 // ---- kernels ---------------------------------------------------------------------------------------------------
 // getVoxelIdx(p, InverseVoxelSize): int(std::floor(p * inv))  (VoxelHashMap.hpp:48-51)
@@ -656,35 +683,6 @@ inline int ext_i32_fetch(const int32_t* d, int32_t out[6], hipStream_t s) {
     for (int a = 0; a < 6; ++a) out[a] = a < 3 ? std::min(out[a], h[k * 6 + a]) : std::max(out[a], h[k * 6 + a]);
   return O3S_OK;
 }
-
-// ---- grow-only device arena: one allocation per pipeline call at most, none once it has seen the largest input -----
-struct Arena {
-  void* base = nullptr;
-  size_t cap = 0, used = 0;
-  ~Arena() {
-    if (base) (void)hipFree(base);
-  }
-  hipError_t reserve(size_t bytes) {
-    used = 0;
-    if (bytes <= cap) return hipSuccess;
-    const size_t had = cap;
-    if (base) (void)hipFree(base);
-    base = nullptr;
-    cap = 0;
-    size_t want = bytes + bytes / 4 + 4096;
-    if (had && want < 2 * had) want = 2 * had;  // growing again: the cloud behind it grows (a map); hipFree / hipMalloc stall the device for milliseconds
-    const hipError_t e = hipMalloc(&base, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  static size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-  template <typename T>
-  T* take(size_t count) {
-    T* p = reinterpret_cast<T*>(reinterpret_cast<char*>(base) + used);
-    used += pad(count * sizeof(T));
-    return p;
-  }
-};
 
 // grow-only work area of the overlap selection (overlap_impl.h); owned by the target submap or by the host-buffer entry
 struct OverlapWork {

@@ -19,7 +19,7 @@ int voxel_pipeline(int mode, const o3s_cropper* crop, double voxel, const double
   if (N == 0) return O3S_OK;
   if (N > (int64_t)0x7fffffff) return O3S_ERR_BAD_ARGUMENT;
   hipStream_t s = nullptr;
-  Buf d_pts, d_nrm, d_opts, d_on, d_oidx, d_col, d_cov, d_ocol, d_ocov;
+  DevMem d_pts, d_nrm, d_opts, d_on, d_oidx, d_col, d_cov, d_ocol, d_ocov;
   Arena ar;
   CK(d_pts.alloc((size_t)N * 24));
   CK(hipMemcpyAsync(d_pts.p, pts, (size_t)N * 24, hipMemcpyHostToDevice, s));
@@ -68,7 +68,7 @@ int o3s_voxel_idx(int device, const double* pts, int64_t N, double voxel_size, i
   if (N == 0) return O3S_OK;
   int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
-  Buf a, b;
+  DevMem a, b;
   CK(a.alloc((size_t)N * 24));
   CK(b.alloc((size_t)N * 12));
   CK(hipMemcpy(a.p, pts, (size_t)N * 24, hipMemcpyHostToDevice));
@@ -83,7 +83,7 @@ int o3s_voxel_hash(int device, const int32_t* idx, int64_t N, uint64_t* hash) {
   if (N == 0) return O3S_OK;
   int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
-  Buf a, b;
+  DevMem a, b;
   CK(a.alloc((size_t)N * 12));
   CK(b.alloc((size_t)N * 8));
   CK(hipMemcpy(a.p, idx, (size_t)N * 12, hipMemcpyHostToDevice));
@@ -98,7 +98,7 @@ int o3s_o3d_to_pm(int device, const double* pts, const double* normals, int64_t 
   if (N == 0) return O3S_OK;
   int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
-  Buf a, b, c, d;
+  DevMem a, b, c, d;
   CK(a.alloc((size_t)N * 24));
   CK(c.alloc((size_t)N * 16));
   CK(hipMemcpy(a.p, pts, (size_t)N * 24, hipMemcpyHostToDevice));
@@ -125,7 +125,7 @@ int o3s_crop_attr(int device, const o3s_cropper* c, const double* pts, const dou
   int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
   hipStream_t s = nullptr;
-  Buf d_pts, d_nrm, d_opts, d_on, d_col, d_cov, d_ocol, d_ocov;
+  DevMem d_pts, d_nrm, d_opts, d_on, d_col, d_cov, d_ocol, d_ocov;
   Arena ar;
   CK(d_pts.alloc((size_t)N * 24));
   CK(hipMemcpyAsync(d_pts.p, pts, (size_t)N * 24, hipMemcpyHostToDevice, s));
@@ -221,7 +221,7 @@ int o3s_undistort_cloud(int device, const o3s_motion* m, const double* pts, int6
   int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
   hipStream_t s = nullptr;
-  Buf d;
+  DevMem d;
   CK(d.alloc((size_t)N * 24));
   CK(hipMemcpyAsync(d.p, pts, (size_t)N * 24, hipMemcpyHostToDevice, s));
   rc = undistort_dev(d.as<double>(), N, *m, s);
@@ -276,7 +276,7 @@ int o3s_undistort_cloud_trajectory(int device, const o3s_stamped_pose* poses, in
   rc = pick_device(device);
   if (rc != O3S_OK) return rc;
   hipStream_t s = nullptr;
-  Buf d, d_dt, d_tab;
+  DevMem d, d_dt, d_tab;
   CK(d.alloc((size_t)N * 24));
   CK(d_tab.alloc(tab.size() * 8));
   CK(hipMemcpyAsync(d.p, pts, (size_t)N * 24, hipMemcpyHostToDevice, s));
@@ -347,8 +347,8 @@ extern "C" int o3s_test_deskew_kernel_ms(o3s_raw_scan* r, const o3s_motion* m, c
   }
   int rc = hipEventRecord(e0, r->stream) == hipSuccess ? O3S_OK : O3S_ERR_HIP;
   if (rc == O3S_OK)
-    rc = m ? undistort_dev(r->p.d(), r->N, *m, r->stream)
-           : undistort_trajectory_dev(r->p.d(), r->has_times ? r->dt.d() : nullptr, r->N, r->traj.d(), a, r->stream);
+    rc = m ? undistort_dev(r->p.as<double>(), r->N, *m, r->stream)
+           : undistort_trajectory_dev(r->p.as<double>(), r->has_times ? r->dt.as<double>() : nullptr, r->N, r->traj.as<double>(), a, r->stream);
   if (rc == O3S_OK && (hipEventRecord(e1, r->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
                        hipEventElapsedTime(ms, e0, e1) != hipSuccess))
     rc = O3S_ERR_HIP;
@@ -363,7 +363,7 @@ extern "C" int o3s_test_sort_pairs(int device, const uint64_t* keys, const uint3
   if (n <= 0 || !keys || !vals || !keys_out || !vals_out) return O3S_ERR_BAD_ARGUMENT;
   const int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
-  Buf k1, k2, v1, v2, tmp;
+  DevMem k1, k2, v1, v2, tmp;
   size_t tb = sort_temp_bytes(n);
   CK(k1.alloc((size_t)n * 8));
   CK(k2.alloc((size_t)n * 8));
@@ -384,7 +384,7 @@ extern "C" int o3s_test_cloud_bounds(int device, const double* pts, int64_t n, d
   if (n <= 0 || !pts || !out6) return O3S_ERR_BAD_ARGUMENT;
   const int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
-  Buf d_pts, d_bb;
+  DevMem d_pts, d_bb;
   CK(d_pts.alloc((size_t)n * 24));
   CK(d_bb.alloc((size_t)kBoundsWords * 8));
   CK(hipMemcpy(d_pts.p, pts, (size_t)n * 24, hipMemcpyHostToDevice));

@@ -40,8 +40,8 @@ int oc_run_chunk(RegArea& area, const std::vector<int32_t>& idx, const o3s_subma
     for (int k = 0; k < m; ++k) {
       const o3s_submap *src = sources[idx[(size_t)k]], *tgt = targets[idx[(size_t)k]];
       OcPair& P = pairs[(size_t)k];
-      P.sp = src->pts[src->cur].d();
-      P.tp = tgt->pts[tgt->cur].d();
+      P.sp = src->pts[src->cur].as<double>();
+      P.tp = tgt->pts[tgt->cur].as<double>();
       P.ns = src->n;
       P.nt = tgt->n;
       P.has_T = Ts ? 1 : 0;
@@ -196,7 +196,7 @@ int o3s_submaps_odometry_constraints(int32_t n, const o3s_submap* const* sources
   int64_t chunk_points = 0;
   auto flush = [&]() -> int {
     if (chunk.empty()) return O3S_OK;
-    const int rc = oc_run_chunk(*area.a, chunk, sources, targets, Ts, overlap_voxel_size, min_points_per_voxel, max_correspondence_distance, infos, n_overlaps,
+    const int rc = oc_run_chunk(*area, chunk, sources, targets, Ts, overlap_voxel_size, min_points_per_voxel, max_correspondence_distance, infos, n_overlaps,
                                 n_correspondences, statuses, s);
     chunk.clear();
     chunk_points = 0;

@@ -404,26 +404,18 @@ struct o3s_dense_map {
   int device = 0;
   double voxel = 0.0, inv = 0.0;
   hipStream_t stream = nullptr;
-  void *keys = nullptr, *cnt = nullptr, *sum = nullptr;  // the table
+  DevMem keys, cnt, sum;  // the table
   int64_t cap = 0, live = 0, tomb = 0;
   int has_normals = 0;
   int64_t n_scans_inserted = 0;  // nScansInsertedDenseMap_
-  mutable DArr in_p, in_n, crop_p, crop_n, tf_p, tf_n, d_T, d_ctr, out;
+  mutable DevMem in_p, in_n, crop_p, crop_n, tf_p, tf_n, d_T, d_ctr, out;
   mutable Arena arena;
-  uint64_t* K() const { return reinterpret_cast<uint64_t*>(keys); }
-  int32_t* C() const { return reinterpret_cast<int32_t*>(cnt); }
-  double* S() const { return reinterpret_cast<double*>(sum); }
+  uint64_t* K() const { return keys.as<uint64_t>(); }
+  int32_t* C() const { return cnt.as<int32_t>(); }
+  double* S() const { return sum.as<double>(); }
 };
 
 namespace {
-
-void dm_free_table(o3s_dense_map* m) {
-  if (m->keys) (void)hipFree(m->keys);
-  if (m->cnt) (void)hipFree(m->cnt);
-  if (m->sum) (void)hipFree(m->sum);
-  m->keys = m->cnt = m->sum = nullptr;
-  m->cap = m->live = m->tomb = 0;
-}
 
 // makes room for `add` more voxels at load <= 1/2, re-hashing into a larger (or tombstone-free) table when needed
 int dm_reserve(o3s_dense_map* m, int64_t add) {
@@ -431,7 +423,7 @@ int dm_reserve(o3s_dense_map* m, int64_t add) {
   if (m->cap > 0 && 2 * (m->live + m->tomb + add) <= m->cap) return O3S_OK;
   int64_t ncap = 1 << 16;
   while (ncap < 4 * (m->live + add)) ncap <<= 1;
-  Buf nk, nc, ns;  // released on every early return; handed to the map at the end
+  DevMem nk, nc, ns;  // released on every early return; handed to the map at the end
   CK(nk.alloc((size_t)ncap * 8));
   CK(nc.alloc((size_t)ncap * 4));
   CK(ns.alloc((size_t)ncap * 48));
@@ -442,14 +434,11 @@ int dm_reserve(o3s_dense_map* m, int64_t add) {
     CK(hipGetLastError());
   }
   CK(hipStreamSynchronize(s));
-  const int64_t live = m->live;
-  dm_free_table(m);
-  m->keys = nk.p;
-  m->cnt = nc.p;
-  m->sum = ns.p;
-  nk.p = nc.p = ns.p = nullptr;
+  m->keys = std::move(nk);  // the old table is freed as the new one moves in
+  m->cnt = std::move(nc);
+  m->sum = std::move(ns);
   m->cap = ncap;
-  m->live = live;
+  m->tomb = 0;
   return O3S_OK;
 }
 
@@ -635,7 +624,6 @@ void o3s_dense_map_destroy(o3s_dense_map* m) {
     (void)hipStreamSynchronize(m->stream);
     (void)hipStreamDestroy(m->stream);
   }
-  dm_free_table(m);
   delete m;
 }
 
@@ -646,7 +634,10 @@ void o3s_dense_map_clear(o3s_dense_map* m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
   (void)hipStreamSynchronize(m->stream);
-  dm_free_table(m);
+  m->keys.release();
+  m->cnt.release();
+  m->sum.release();
+  m->cap = m->live = m->tomb = 0;
 }
 
 int o3s_dense_map_insert(o3s_dense_map* m, const double* pts, const double* normals, int64_t N) {
@@ -656,7 +647,7 @@ int o3s_dense_map_insert(o3s_dense_map* m, const double* pts, const double* norm
   if (rc != O3S_OK) return rc;
   rc = dm_upload(m, pts, normals, N);
   if (rc != O3S_OK) return rc;
-  return dm_insert_dev(m, m->in_p.d(), normals ? m->in_n.d() : nullptr, N);
+  return dm_insert_dev(m, m->in_p.as<double>(), normals ? m->in_n.as<double>() : nullptr, N);
 }
 
 int o3s_dense_map_carve(o3s_dense_map* m, const o3s_dense_carving_params* p, const double* scan_pts, int64_t N, const double sensor_position[3],
@@ -668,7 +659,7 @@ int o3s_dense_map_carve(o3s_dense_map* m, const o3s_dense_carving_params* p, con
   if (rc != O3S_OK) return rc;
   rc = dm_upload(m, scan_pts, nullptr, N);
   if (rc != O3S_OK) return rc;
-  return dm_carve_dev(m, p, m->in_p.d(), N, sensor_position, n_removed);
+  return dm_carve_dev(m, p, m->in_p.as<double>(), N, sensor_position, n_removed);
 }
 
 }  // extern "C"
@@ -687,7 +678,7 @@ int dm_insert_scan_dev(o3s_dense_map* m, const o3s_cropper* dense_map_cropper, c
     CK(m->crop_p.ensure((size_t)N * 24, 0, s));
     CK(m->crop_n.ensure((size_t)N * 24, 0, s));
     int64_t kept = 0;
-    rc = crop_dev(m->arena, c, d_raw_p, d_raw_n, N, m->crop_p.d(), m->crop_n.d(), &kept, s);
+    rc = crop_dev(m->arena, c, d_raw_p, d_raw_n, N, m->crop_p.as<double>(), m->crop_n.as<double>(), &kept, s);
     if (rc != O3S_OK) return rc;
     if (kept > 0) {
       // o3d_slam::transform (helpers.cpp:283-318): a near-identity pose emits the cloud twice (copy + transformed)
@@ -700,18 +691,18 @@ int dm_insert_scan_dev(o3s_dense_map* m, const o3s_cropper* dense_map_cropper, c
       CK(m->tf_n.ensure((size_t)n_tf * 24, 0, s));
       CK(m->d_T.ensure(128, 0, s));
       CK(hipMemcpyAsync(m->d_T.p, T, 128, hipMemcpyHostToDevice, s));
-      double* dp = m->tf_p.d();
-      double* dn = m->tf_n.d();
+      double* dp = m->tf_p.as<double>();
+      double* dn = m->tf_n.as<double>();
       if (doubled) {
         CK(hipMemcpyAsync(dp, m->crop_p.p, (size_t)kept * 24, hipMemcpyDeviceToDevice, s));
         if (hn) CK(hipMemcpyAsync(dn, m->crop_n.p, (size_t)kept * 24, hipMemcpyDeviceToDevice, s));
         dp += 3 * kept;
         dn += 3 * kept;
       }
-      hipLaunchKernelGGL(k_transform_append, dim3(nblk(kept)), dim3(kB), 0, s, m->crop_p.d(), hn ? m->crop_n.d() : nullptr, kept, m->d_T.d(), dp,
+      hipLaunchKernelGGL(k_transform_append, dim3(nblk(kept)), dim3(kB), 0, s, m->crop_p.as<double>(), hn ? m->crop_n.as<double>() : nullptr, kept, m->d_T.as<double>(), dp,
                          hn ? dn : nullptr);
       CK(hipGetLastError());
-      rc = dm_insert_dev(m, m->tf_p.d(), hn ? m->tf_n.d() : nullptr, n_tf);
+      rc = dm_insert_dev(m, m->tf_p.as<double>(), hn ? m->tf_n.as<double>() : nullptr, n_tf);
       if (rc != O3S_OK) return rc;
     }
   }
@@ -739,7 +730,7 @@ int o3s_dense_map_insert_scan(o3s_dense_map* m, const o3s_cropper* dense_map_cro
     rc = dm_upload(m, raw_pts, raw_normals, N);
     if (rc != O3S_OK) return rc;
   }
-  return dm_insert_scan_dev(m, dense_map_cropper, m->in_p.d(), raw_normals ? m->in_n.d() : nullptr, N, T, carving, n_removed);
+  return dm_insert_scan_dev(m, dense_map_cropper, m->in_p.as<double>(), raw_normals ? m->in_n.as<double>() : nullptr, N, T, carving, n_removed);
 }
 
 int o3s_dense_map_insert_resident_scan(o3s_dense_map* m, const o3s_cropper* dense_map_cropper, const o3s_scan* sc, const double T[16],
@@ -751,7 +742,7 @@ int o3s_dense_map_insert_resident_scan(o3s_dense_map* m, const o3s_cropper* dens
   const int rc = dm_set_dev(m);
   if (rc != O3S_OK) return rc;
   CK(hipStreamSynchronize(sc->stream));  // the scan's own work is complete (its calls end synchronised); this map's stream takes over
-  return dm_insert_scan_dev(m, dense_map_cropper, sc->raw_p.d(), sc->raw_has_normals ? sc->raw_n.d() : nullptr, sc->n_raw, T, carving, n_removed);
+  return dm_insert_scan_dev(m, dense_map_cropper, sc->raw_p.as<double>(), sc->raw_has_normals ? sc->raw_n.as<double>() : nullptr, sc->n_raw, T, carving, n_removed);
 }
 
 int o3s_dense_map_to_point_cloud(const o3s_dense_map* m, double* pts, double* normals, int32_t* keys, int32_t* counts, int64_t* n_out) {
@@ -805,7 +796,7 @@ int o3s_dense_map_transform(o3s_dense_map* m, const double T[16]) {
   hipStream_t s = m->stream;
   CK(m->d_T.ensure(128, 0, s));
   CK(hipMemcpyAsync(m->d_T.p, T, 128, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_dm_transform, dim3(nblk(m->cap)), dim3(kB), 0, s, m->K(), m->C(), m->S(), m->cap, m->d_T.d());
+  hipLaunchKernelGGL(k_dm_transform, dim3(nblk(m->cap)), dim3(kB), 0, s, m->K(), m->C(), m->S(), m->cap, m->d_T.as<double>());
   CK(hipGetLastError());
   CK(hipStreamSynchronize(s));
   return O3S_OK;

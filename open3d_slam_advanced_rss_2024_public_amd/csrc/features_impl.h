@@ -15,7 +15,7 @@ int o3s_compute_fpfh(int device, const double* pts, const double* normals, int64
   int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
   hipStream_t s = nullptr;
-  Buf d_p, d_n, d_f;
+  DevMem d_p, d_n, d_f;
   FpfhWork w;
   CK(d_p.alloc((size_t)N * 24));
   CK(d_n.alloc((size_t)N * 24));
@@ -41,7 +41,7 @@ int o3s_feature_correspondences(int device, const double* src_feat, int64_t n_sr
   const int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
   hipStream_t s = nullptr;
-  Buf d_a, d_b;
+  DevMem d_a, d_b;
   FeatNnWork w;
   CK(d_a.alloc((size_t)n_src * (size_t)dim * 8));
   CK(d_b.alloc((size_t)n_tgt * (size_t)dim * 8));
@@ -81,16 +81,16 @@ int o3s_submap_compute_features(o3s_submap* m, const o3s_submap_feature_params* 
   CK(m->feat_p.ensure((size_t)N * 24, 0, s));
   CK(m->feat_n.ensure((size_t)N * 24, 0, s));
   int64_t n_sparse = 0;
-  rc = voxel_pipeline_dev(m->feat_w.grid.arena, 1, nullptr, params->feature_voxel_size, m->pts[m->cur].d(), nullptr, N, m->feat_p.d(), m->feat_n.d(),
+  rc = voxel_pipeline_dev(m->feat_w.grid.arena, 1, nullptr, params->feature_voxel_size, m->pts[m->cur].as<double>(), nullptr, N, m->feat_p.as<double>(), m->feat_n.as<double>(),
                           nullptr, &n_sparse, s);
   if (rc != O3S_OK) return rc;
   if (n_sparse > 0) {
     // EstimateNormals(Hybrid(normalEstimationRadius_, normalKnn_)) + NormalizeNormals + OrientNormalsTowardsCameraLocation(0)
-    rc = estimate_normals_dev(m->feat_w.grid, m->feat_p.d(), n_sparse, params->normal_radius, params->normal_knn, m->feat_n.d(), nullptr, s);
+    rc = estimate_normals_dev(m->feat_w.grid, m->feat_p.as<double>(), n_sparse, params->normal_radius, params->normal_knn, m->feat_n.as<double>(), nullptr, s);
     if (rc != O3S_OK) return rc;
     // feature_ = ComputeFPFHFeature(sparseMapCloud_, Hybrid(featureRadius_, featureKnn_))
     CK(m->feat_f.ensure((size_t)n_sparse * kFpfhDim * 8, 0, s));
-    rc = fpfh_dev(m->feat_w, m->feat_p.d(), m->feat_n.d(), n_sparse, params->feature_radius, params->feature_knn, m->feat_f.d(), s);
+    rc = fpfh_dev(m->feat_w, m->feat_p.as<double>(), m->feat_n.as<double>(), n_sparse, params->feature_radius, params->feature_knn, m->feat_f.as<double>(), s);
     if (rc != O3S_OK) return rc;
   }
   CK(hipStreamSynchronize(s));
@@ -127,7 +127,7 @@ int o3s_submap_feature_correspondences(const o3s_submap* source, const o3s_subma
   CK(hipStreamSynchronize(target->stream));
   FeatNnWork w;
   int fb = 0;
-  const int rf = feature_correspondences_dev(w, source->feat_f.d(), source->n_feat, target->feat_f.d(), target->n_feat, kFpfhDim, mutual_filter, ransac_n,
+  const int rf = feature_correspondences_dev(w, source->feat_f.as<double>(), source->n_feat, target->feat_f.as<double>(), target->n_feat, kFpfhDim, mutual_filter, ransac_n,
                                              out_pairs, n_out, &fb, source->stream);
   if (used_fallback) *used_fallback = fb;
   return rf;

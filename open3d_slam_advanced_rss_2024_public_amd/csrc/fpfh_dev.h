@@ -302,21 +302,14 @@ __global__ void __launch_bounds__(64) k_fpfh(const double* __restrict__ spfh, in
 
 struct FpfhWork {  // grow-only buffers of the feature computation (owned by the caller's object)
   NormalsWork grid;
-  Buf idx, d2, spfh;  // neighbour lists (N x max_nn int32 + d2) and SPFH (33 x N): in HBM between the stages
+  DevMem idx, d2, spfh;  // neighbour lists (N x max_nn int32 + d2) and SPFH (33 x N): in HBM between the stages
+  void release() {
+    grid.release();
+    idx.release();
+    d2.release();
+    spfh.release();
+  }
 };
-inline void drop_buf(Buf& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-}
-inline void drop_normals_work(NormalsWork& w) {
-  if (w.arena.base) (void)hipFree(w.arena.base);
-  w.arena.base = nullptr;
-  w.arena.cap = w.arena.used = 0;
-  if (w.cells) (void)hipFree(w.cells);
-  w.cells = nullptr;
-  w.cells_cap = 0;
-}
 
 // d_pts, d_nrm (3 x N doubles, device) -> d_fpfh (33 x N doubles); the lists and the SPFH stay in w (w.idx, w.d2, w.spfh)
 inline int fpfh_dev(FpfhWork& w, const double* d_pts, const double* d_nrm, int64_t N, double radius, int max_nn, double* d_fpfh, hipStream_t s) {
@@ -412,11 +405,11 @@ __global__ void __launch_bounds__(kFcBlock) k_feat_nn_fold(const double* __restr
 }
 
 struct FeatNnWork {
-  Buf part_d, part_j, ij, ji;
+  DevMem part_d, part_j, ij, ji;
 };
 
 // out_j[i] = the column of b nearest to column i of a (device arrays, dim x n / dim x m)
-inline int feat_nn_dev(Buf& part_d, Buf& part_j, const double* d_a, int64_t n, const double* d_b, int64_t m, int dim, int32_t* d_out_j, hipStream_t s) {
+inline int feat_nn_dev(DevMem& part_d, DevMem& part_j, const double* d_a, int64_t n, const double* d_b, int64_t m, int dim, int32_t* d_out_j, hipStream_t s) {
   const unsigned bx = (unsigned)((n + kFcBlock - 1) / kFcBlock);
   const int64_t tile = kFcTileDoubles / dim;
   // about 2048 blocks in all (8 per CU), chunks a whole number of tiles
@@ -709,7 +702,7 @@ inline int64_t place_blocks() {
 
 // grow-only work area of a one-to-many call (part of the leased RANSAC area, ransac_impl.h)
 struct PlaceWork {
-  Buf part_d, part_j, ij, ji, flag, off, head, pairs, scan_tmp;
+  DevMem part_d, part_j, ij, ji, flag, off, head, pairs, scan_tmp;
 };
 
 // Correspondences of one source feature array against K targets (device arrays): w.pairs holds K slices of n_src pairs, slice k

@@ -418,10 +418,11 @@ __global__ void __launch_bounds__(kB) k_normals(const double* __restrict__ sp /*
 
 struct NormalsWork {  // grow-only buffers of the estimator (owned by the caller's object)
   Arena arena;
-  void* cells = nullptr;  // begin[ncells] | end[ncells]
-  size_t cells_cap = 0;
-  ~NormalsWork() {
-    if (cells) (void)hipFree(cells);
+  DevMem cells;  // begin[ncells] | end[ncells]
+  hipError_t reserve_cells(size_t ncells) { return cells.fit(ncells * 8, 4096); }
+  void release() {
+    arena.release();
+    cells.release();
   }
 };
 
@@ -557,16 +558,10 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
   g.ny = (int32_t)dims[1];
   g.nz = (int32_t)dims[2];
   const size_t ncells = (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2];
-  if (ncells * 8 > w.cells_cap) {
-    if (w.cells) (void)hipFree(w.cells);
-    w.cells = nullptr;
-    w.cells_cap = 0;
-    CK(hipMalloc(&w.cells, ncells * 8 + 4096));
-    w.cells_cap = ncells * 8 + 4096;
-  }
-  uint32_t* cbeg = reinterpret_cast<uint32_t*>(w.cells);
+  CK(w.reserve_cells(ncells));
+  uint32_t* cbeg = w.cells.as<uint32_t>();
   uint32_t* cend = cbeg + ncells;
-  CK(hipMemsetAsync(w.cells, 0, ncells * 8, s));
+  CK(hipMemsetAsync(w.cells.p, 0, ncells * 8, s));
   hipLaunchKernelGGL(k_cell_ranges, dim3(nblk(N)), dim3(kB), 0, s, keys2, N, cbeg, cend);
   hipLaunchKernelGGL(k_gather_sorted, dim3(nblk(N)), dim3(kB), 0, s, d_pts, vals2, N, sp);
   CK(hipGetLastError());

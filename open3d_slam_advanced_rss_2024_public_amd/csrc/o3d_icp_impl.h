@@ -1211,7 +1211,7 @@ inline void h_umeyama(const double* v, const double* c, double* T) {
 
 struct O3dIcpWork {
   NormalsWork grid;  // index over the target
-  Buf d_src, d_tgt, d_tn, d_corr, d_part, d_sum, d_rec, d_far, d_far_count, d_cert, d_list;
+  DevMem d_src, d_tgt, d_tn, d_corr, d_part, d_sum, d_rec, d_far, d_far_count, d_cert, d_list;
   const double* tgt = nullptr;  // the target cloud the kernels read: d_tgt / d_tn, or arrays that already live in HBM
   const double* tn = nullptr;
   Arena sort_arena;
@@ -1220,7 +1220,7 @@ struct O3dIcpWork {
   int pass_no = 0;               // passes since the source was placed (o3d_place_source): the first two search nearly every point
   bool corr_valid = false;  // d_corr holds the correspondences of an earlier pass over the same source order: bounds for the next search
   // what a registration leaves behind for the information matrix of the same pair (o3d_info_after_icp)
-  Buf d_orig;                    // the source as given, when it came from the host
+  DevMem d_orig;                 // the source as given, when it came from the host
   const double* orig = nullptr;  // the source as given, on the device (d_orig or the caller's resident array)
   const uint32_t* order = nullptr;  // search order -> index into the source (lives in sort_arena)
   GridIndex gi{};
@@ -1229,8 +1229,8 @@ struct O3dIcpWork {
   // the estimation of the running registration (o3d_icp_run): what the passes' k_o3d_corr sums
   int est = kEstPlane;
   O3dEstArgs ea{};
-  Buf d_scov, d_tcov;  // GICP: 6 doubles per point, source in search order / target in index order (k_o3d_cov)
-  Buf d_sraw, d_traw;  // GICP from the host: the normals / covariances as uploaded
+  DevMem d_scov, d_tcov;  // GICP: 6 doubles per point, source in search order / target in index order (k_o3d_cov)
+  DevMem d_sraw, d_traw;  // GICP from the host: the normals / covariances as uploaded
   O3dIcpWork() = default;
   O3dIcpWork(const O3dIcpWork&) = delete;
   O3dIcpWork& operator=(const O3dIcpWork&) = delete;
@@ -1246,10 +1246,9 @@ size_t reg_overlap_arena_bytes(int64_t Ns, int64_t Nt);  // overlap_impl.h
 void reg_warm_lane_streams(int device);                   // overlap_impl.h
 
 struct RegArea {
-  int device = -1;
   OverlapWork ov;                // overlap selection (overlap_impl.h)
-  Buf ov_src, ov_tgt, ov_tgtn;   // the two selected clouds of o3s_o3d_registration_icp_submaps_overlap
-  Buf ov_srcn;                   // ... and the source's selected normals (Generalized ICP)
+  DevMem ov_src, ov_tgt, ov_tgtn;  // the two selected clouds of o3s_o3d_registration_icp_submaps_overlap
+  DevMem ov_srcn;                  // ... and the source's selected normals (Generalized ICP)
   O3dIcpWork reg;
   PostBlock<> oc_res;            // what o3s_submaps_odometry_constraints reads back: every pair's sums and counts (constraints_impl.h)
   size_t oc_res_bytes = 0;
@@ -1258,49 +1257,7 @@ struct RegArea {
   RegArea& operator=(const RegArea&) = delete;
   ~RegArea() { oc_res.release(); }  // only ever runs through o3s_o3d_registration_release, like ~O3dIcpWork
 };
-struct RegPool {
-  std::mutex m;
-  std::vector<std::unique_ptr<RegArea>> idle;
-};
-inline RegPool& reg_pool() {
-  static RegPool* p = new RegPool;  // never destroyed: its buffers must not be freed behind the runtime's own teardown
-  return *p;
-}
-struct RegLease {  // the calling thread's area for the duration of a call (the device is current)
-  std::unique_ptr<RegArea> a;
-  hipStream_t s = nullptr;  // the stream the call enqueues on
-  bool ok = false;          // the call ended through end(O3S_OK): it has waited for its stream itself
-  // Every early error return (a failed launch, O3S_ERR_HIP from a post wait, an empty selection behind enqueued compactions) can
-  // leave kernels in flight that still read or write the area's buffers: the area goes back to the pool — where a registration
-  // on another stream or thread may lease it at once — only behind a drained stream.  Successful calls have drained it already.
-  int end(int rc) {
-    ok = rc == O3S_OK;
-    return rc;
-  }
-  explicit RegLease(int device, hipStream_t stream = nullptr) : s(stream) {
-    RegPool& p = reg_pool();
-    {
-      std::lock_guard<std::mutex> g(p.m);
-      for (size_t k = 0; k < p.idle.size(); ++k)
-        if (p.idle[k]->device == device) {
-          a = std::move(p.idle[k]);
-          p.idle.erase(p.idle.begin() + (long)k);
-          break;
-        }
-    }
-    if (!a) {
-      a.reset(new RegArea);
-      a->device = device;
-    }
-  }
-  ~RegLease() {
-    if (!ok) (void)hipStreamSynchronize(s);
-    RegPool& p = reg_pool();
-    std::lock_guard<std::mutex> g(p.m);
-    p.idle.push_back(std::move(a));
-  }
-  RegArea* operator->() { return a.get(); }
-};
+using RegLease = AreaLease<RegArea, /*kAlwaysDrain=*/false>;  // successful calls have drained their stream already
 
 // the pinned post of the sums: allocated once per work area (a pinned allocation takes milliseconds: o3s_o3d_registration_reserve
 // makes it ahead of time) and never freed (the areas live in a pool that is never torn down); without it the sums are copied back
@@ -1490,13 +1447,7 @@ inline int reg_reserve_area(RegLease& area, int64_t max_source_points, int64_t m
   o3d_ensure_post(w);
   CK(w.d_far_count.alloc(256));
   CK(w.grid.arena.reserve(grid_index_arena_bytes(max_target_points)));
-  if (w.grid.cells_cap < kGridMaxCells * 8 + 4096) {
-    if (w.grid.cells) (void)hipFree(w.grid.cells);
-    w.grid.cells = nullptr;
-    w.grid.cells_cap = 0;
-    CK(hipMalloc(&w.grid.cells, kGridMaxCells * 8 + 4096));
-    w.grid.cells_cap = kGridMaxCells * 8 + 4096;
-  }
+  CK(w.grid.reserve_cells(kGridMaxCells));
   CK(w.sort_arena.reserve(2 * Arena::pad(ns * 8) + 2 * Arena::pad(ns * 4) + Arena::pad(sort_temp_bytes(max_source_points)) + 4096));
   CK(area->ov_src.alloc(ns * 24));
   CK(area->ov_tgt.alloc(nt * 24));
@@ -1531,18 +1482,7 @@ int o3s_o3d_registration_reserve(int device, int64_t max_source_points, int64_t 
   return o3s_o3d_registration_reserve_n(device, max_source_points, max_target_points, 1);
 }
 
-int o3s_o3d_registration_release(int device) {
-  using namespace o3s_cloud;
-  const int rc = pick_device(device);
-  if (rc != O3S_OK) return rc;
-  if (hipDeviceSynchronize() != hipSuccess) return O3S_ERR_HIP;
-  RegPool& p = reg_pool();
-  std::lock_guard<std::mutex> g(p.m);
-  for (size_t k = 0; k < p.idle.size();)
-    if (p.idle[k]->device == device) p.idle.erase(p.idle.begin() + (long)k);
-    else ++k;
-  return O3S_OK;
-}
+int o3s_o3d_registration_release(int device) { return o3s_cloud::release_idle_areas<o3s_cloud::RegArea>(device); }
 
 void o3s_o3d_icp_default_criteria(o3s_o3d_icp_criteria* c) {
   if (!c) return;

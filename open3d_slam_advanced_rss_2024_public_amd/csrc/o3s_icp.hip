@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_mem.h"
 #include "icp_kernels.h"
 #include "icp_shard_kernels.h"
 #include "icp_types.h"
@@ -27,38 +28,6 @@ using namespace o3s;
 namespace {
 
 thread_local std::string g_create_error;
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  uint64_t* gen = nullptr;  // the owning handle's allocation generation: bumped whenever this buffer moves, which
-                            // invalidates every captured graph that has the old address baked in
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (gen) ++*gen;
-    // the first allocation is tight (a 20 M-point map is allocated once); a buffer that has to grow AGAIN belongs to a growing
-    // map patch, and every move costs a device-wide synchronisation plus a re-capture of the chain's graph: double it
-    const size_t had = cap;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = bytes + bytes / 8 + 256;
-    if (had && want < 2 * had) want = 2 * had;
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (gen) ++*gen;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <typename T>
-  T* as() const {
-    return reinterpret_cast<T*>(p);
-  }
-};
 
 struct HostStage {  // pinned staging block for small H2D / D2H transfers
   IcpState state;
@@ -114,6 +83,9 @@ struct o3s_icp {
   int device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
   std::string err;
+  // Every DevBuf of the handle but d_loc reports its moves here; the graph key carries the value, so a graph is never replayed
+  // after ANY buffer a captured kernel points at has moved (the key's pointer list alone missed d_cand & co.).
+  uint64_t alloc_gen = 0;
 
   // reference (matcher index)
   bool ref_ready = false;
@@ -124,12 +96,13 @@ struct o3s_icp {
   size_t ncells = 0;
   int qf = 1, qnx = 1, qny = 1, qnz = 1;  // coarsened grid the reading is sorted on
   size_t qcells = 1;
-  DevBuf d_ref_in, d_refn_in;  // staging for host-supplied references
-  DevBuf d_ref, d_refn, d_cell_start, d_cell_tmp, d_qstart, d_orig_to_sorted, d_cell_of, d_scan_sums, d_ref_part, d_ref_bb;
+  DevBuf d_ref_in{&alloc_gen}, d_refn_in{&alloc_gen};  // staging for host-supplied references
+  DevBuf d_ref{&alloc_gen}, d_refn{&alloc_gen}, d_cell_start{&alloc_gen}, d_cell_tmp{&alloc_gen}, d_qstart{&alloc_gen}, d_orig_to_sorted{&alloc_gen},
+      d_cell_of{&alloc_gen}, d_scan_sums{&alloc_gen}, d_ref_part{&alloc_gen}, d_ref_bb{&alloc_gen};
   // the first-iteration index (dense maps only, init_reference_impl step 4): the same points sorted on a grid of 1.5 x the cell edge
   bool have_grid1 = false;
   GridParams grid1{};
-  DevBuf d_ref1, d_refn1, d_cell_start1;
+  DevBuf d_ref1{&alloc_gen}, d_refn1{&alloc_gen}, d_cell_start1{&alloc_gen};
   bool far_rows = false;  // the matcher's far search is the row-disc search (finite maxDist), else the ring search
 
   // reading
@@ -140,21 +113,22 @@ struct o3s_icp {
   int prepared_N = 0;  // points of the last prepare_reading (d_perm holds their processing order)
   const void* ext_xyzw = nullptr;  // device pointers supplied by set_reading_dev (not owned)
   const void* ext_n = nullptr;
-  DevBuf d_in_xyzw, d_in_n, d_t, d_r, d_perm, d_qcell;
-  DevBuf d_qcount;  // per-bin counts of the reading's sort [qcells] + tile totals behind them: ALL ZEROS between calls
+  DevBuf d_in_xyzw{&alloc_gen}, d_in_n{&alloc_gen}, d_t{&alloc_gen}, d_r{&alloc_gen}, d_perm{&alloc_gen}, d_qcell{&alloc_gen};
+  DevBuf d_qcount{&alloc_gen};  // per-bin counts of the reading's sort [qcells] + tile totals behind them: ALL ZEROS between calls
   size_t qcount_words = 0;
 
   // iteration chain
-  DevBuf d_mn;  // matched reference normal of every query (written by k_classify, streamed by k_normal_eq)
-  DevBuf d_mq;  // matched reference point of every query (k_match2: this iteration's output, the next one's pruning bound)
-  DevBuf d_cert;  // ... and its certificate: a lower bound of the squared distance to every OTHER reference point (0: none)
-  DevBuf d_cand_cnt;
-  DevBuf d_sel_part2, d_park;  // k_sel_partial (large readings): block partials [7][blocks]; parked records [kParkRecs] + their order keys
-  DevBuf d_pos, d_d2, d_hist, d_cand, d_sel, d_cent, d_ne, d_state, d_T0, d_trace_T, d_trace_limit, d_trace_kept;
-  DevBuf d_mod_a, d_mod_b, d_mod_c, d_mod_d;  // module-level scratch
+  DevBuf d_mn{&alloc_gen};  // matched reference normal of every query (written by k_classify, streamed by k_normal_eq)
+  DevBuf d_mq{&alloc_gen};  // matched reference point of every query (k_match2: this iteration's output, the next one's pruning bound)
+  DevBuf d_cert{&alloc_gen};  // ... and its certificate: a lower bound of the squared distance to every OTHER reference point (0: none)
+  DevBuf d_cand_cnt{&alloc_gen};
+  DevBuf d_sel_part2{&alloc_gen}, d_park{&alloc_gen};  // k_sel_partial (large readings): block partials [7][blocks]; parked records [kParkRecs] + their order keys
+  DevBuf d_pos{&alloc_gen}, d_d2{&alloc_gen}, d_hist{&alloc_gen}, d_cand{&alloc_gen}, d_sel{&alloc_gen}, d_cent{&alloc_gen}, d_ne{&alloc_gen},
+      d_state{&alloc_gen}, d_T0{&alloc_gen}, d_trace_T{&alloc_gen}, d_trace_limit{&alloc_gen}, d_trace_kept{&alloc_gen};
+  DevBuf d_mod_a{&alloc_gen}, d_mod_b{&alloc_gen}, d_mod_c{&alloc_gen}, d_mod_d{&alloc_gen};  // module-level scratch
   // pose covariance (error_minimizer 1, o3s_icp_estimate_covariance): k_cov's block partials [42][blocks] with the 42 totals behind
   // them, and the mailbox k_cov_post posts the totals to
-  DevBuf d_cov;
+  DevBuf d_cov{&alloc_gen};
   host_post::PostBlock<> cov_mb;
   double cov[36] = {0};
   bool cov_valid = false;       // the last compute succeeded: o3s_icp_get_covariance has something to return
@@ -163,7 +137,7 @@ struct o3s_icp {
   float last_step[16] = {0};    // ... and its last iteration's step (IcpState::dT)
   unsigned long long cov_t_start = 0, cov_t_end = 0;  // wall_clock64 stamps of the last covariance pass (k_cov's start, k_cov_post's end)
   // localizability analysis (localizability_impl.h): the work area of its four kernels, allocated by the first call.  No captured
-  // kernel points into it, so it stays out of all_bufs() and a first call leaves the chain's graph alone
+  // kernel points into it, so it is not wired to alloc_gen and a first call leaves the chain's graph alone
   DevBuf d_loc;
   // registration fitness (o3s_icp_evaluate_resident): where the last successful compute left the reading.  pose_valid: that compute's
   // T_iter is in last_T_iter and nothing has replaced the reading or the reference since; r_is_call: d_r still holds the reading as
@@ -196,15 +170,6 @@ struct o3s_icp {
   std::vector<int> looks;  // hooks build (O3S_PRINT_CHAIN): iterations issued at each look at the post of the call in flight
 #endif
 
-  // Every DevBuf of the handle reports (re)allocations here; the graph key carries the value, so a graph is never
-  // replayed after ANY buffer a captured kernel points at has moved (the key's pointer list alone missed d_cand & co.).
-  uint64_t alloc_gen = 0;
-  std::vector<DevBuf*> all_bufs() {
-    return {&d_ref_in, &d_refn_in, &d_ref, &d_refn, &d_cell_start, &d_cell_tmp, &d_qstart, &d_orig_to_sorted, &d_cell_of, &d_scan_sums,
-            &d_ref_part, &d_ref_bb, &d_ref1, &d_refn1, &d_cell_start1, &d_in_xyzw, &d_in_n, &d_t, &d_r, &d_perm, &d_qcell, &d_qcount, &d_pos, &d_d2, &d_hist, &d_cand, &d_cand_cnt, &d_sel_part2, &d_park, &d_sel, &d_cent,
-            &d_ne, &d_state, &d_T0, &d_mq, &d_cert, &d_mn, &d_trace_T, &d_trace_limit, &d_trace_kept, &d_mod_a, &d_mod_b, &d_mod_c, &d_mod_d, &d_cov, &shard.own};
-  }
-
   // graph cache
   hipGraphExec_t graph_exec = nullptr;
   struct GraphKey {
@@ -228,7 +193,8 @@ struct o3s_icp {
     bool capturable = false;  // fn only enqueues stream work (ncclAllReduce): the sharded chain may be captured in a hipGraph
     uint8_t* xbuf = nullptr;  // exchange buffer (kXchgBytes), caller's or `own`
     DevBuf own;
-  } shard;
+    explicit Shard(uint64_t* gen) : own(gen) {}
+  } shard{&alloc_gen};
 
   int eager_hint = 4;  // iterations the last call needed: where the eager (un-graphed) chain first looks at the `done` flag
 
@@ -1411,7 +1377,6 @@ int o3s_icp_create(const o3s_icp_config* cfg, int device, o3s_icp** out) {
     return O3S_ERR_HIP;
   }
   o3s_icp* h = new o3s_icp();
-  for (DevBuf* b : h->all_bufs()) b->gen = &h->alloc_gen;
   h->cfg = *cfg;
   h->device = device;
   hipError_t e = hipSetDevice(device);
@@ -1444,8 +1409,6 @@ void o3s_icp_destroy(o3s_icp* h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-  for (DevBuf* b : h->all_bufs()) b->release();
-  h->d_loc.release();
   for (hipEvent_t e : h->prof_events) (void)hipEventDestroy(e);
   if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
   if (h->ev_end) (void)hipEventDestroy(h->ev_end);
@@ -1454,7 +1417,7 @@ void o3s_icp_destroy(o3s_icp* h) {
   h->post.release();
   h->cov_mb.release();
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
+  delete h;  // the device buffers go with their members
 }
 
 const char* o3s_last_error(const o3s_icp* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
@@ -1488,11 +1451,12 @@ int o3s_stream_copy_gbs(int device, int64_t bytes, int32_t reps, double* gbs) {
   if (hipSetDevice(device) != hipSuccess) return O3S_ERR_HIP;
   const size_t n = (size_t)bytes / 16;
   if (n > (size_t)0x7fffffff * 256) return O3S_ERR_BAD_ARGUMENT;
-  void *a = nullptr, *b = nullptr;
+  DevMem ma, mb;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int rc = O3S_ERR_HIP;
-  if (hipMalloc(&a, n * 16) == hipSuccess && hipMalloc(&b, n * 16) == hipSuccess && hipEventCreate(&e0) == hipSuccess &&
-      hipEventCreate(&e1) == hipSuccess && hipMemset(a, 1, n * 16) == hipSuccess && hipMemset(b, 0, n * 16) == hipSuccess) {
+  if (ma.reset(n * 16) == hipSuccess && mb.reset(n * 16) == hipSuccess && hipEventCreate(&e0) == hipSuccess &&
+      hipEventCreate(&e1) == hipSuccess && hipMemset(ma.p, 1, n * 16) == hipSuccess && hipMemset(mb.p, 0, n * 16) == hipSuccess) {
+    void *a = ma.p, *b = mb.p;
     const unsigned grid = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_stream_copy, dim3(grid), dim3(256), 0, nullptr, (const v4f*)a, (v4f*)b, n);  // warm-up
     (void)hipEventRecord(e0, nullptr);
@@ -1506,8 +1470,6 @@ int o3s_stream_copy_gbs(int device, int64_t bytes, int32_t reps, double* gbs) {
   }
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  if (a) (void)hipFree(a);
-  if (b) (void)hipFree(b);
   return rc;
 }
 

@@ -309,7 +309,7 @@ int o3s_overlap_indices(int device, const double* source, int64_t Ns, const doub
   int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
   hipStream_t s = nullptr;
-  Buf d_s, d_t, d_is, d_it;
+  DevMem d_s, d_t, d_is, d_it;
   CK(d_s.alloc((size_t)Ns * 24));
   CK(d_t.alloc((size_t)Nt * 24));
   CK(hipMemcpyAsync(d_s.p, source, (size_t)Ns * 24, hipMemcpyHostToDevice, s));
@@ -344,10 +344,10 @@ int refine_overlap_on(const o3s_submap* source, const o3s_submap* target, double
   using namespace o3s_cloud;
   int rc = O3S_OK;
   const bool gicp = est_type == kEstGicp;
-  const double* sp = source->pts[source->cur].d();
-  const double* tp = target->pts[target->cur].d();
-  const double* tn = target->has_normals == 1 ? target->nrm[target->cur].d() : nullptr;
-  const double* sn = gicp ? source->nrm[source->cur].d() : nullptr;
+  const double* sp = source->pts[source->cur].as<double>();
+  const double* tp = target->pts[target->cur].as<double>();
+  const double* tn = target->has_normals == 1 ? target->nrm[target->cur].as<double>() : nullptr;
+  const double* sn = gicp ? source->nrm[source->cur].as<double>() : nullptr;
   uint32_t *fs, *os, *ft, *ot;
   int64_t ns = 0, nt = 0;
   RegLease area(target->device, s);
@@ -395,28 +395,17 @@ int refine_overlap_on(const o3s_submap* source, const o3s_submap* target, double
 }
 
 // streams of the batch entry's lanes: made once per device, kept for the life of the process (a stream costs ~3 ms to create)
-struct RefineStreams {
-  static constexpr int kLanes = 4;
-  std::mutex m;
-  std::vector<std::vector<hipStream_t>> per_device;
-  hipStream_t get(int device, int lane) {  // the device is current
-    std::lock_guard<std::mutex> g(m);
-    if ((size_t)device >= per_device.size()) per_device.resize((size_t)device + 1);
-    std::vector<hipStream_t>& v = per_device[(size_t)device];
-    while (v.size() < (size_t)kLanes) {
-      hipStream_t s = nullptr;
-      if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return nullptr;
-      v.push_back(s);
-    }
-    return v[(size_t)lane % v.size()];
-  }
-};
-inline RefineStreams& refine_streams() {
-  static RefineStreams* p = new RefineStreams;  // never destroyed (see RegPool)
+constexpr int kLanes = 4;
+inline o3s_cloud::DeviceStreams<kLanes>& lane_streams() {
+  static auto* p = new o3s_cloud::DeviceStreams<kLanes>;  // never destroyed (see DeviceStreams)
   return *p;
 }
+inline hipStream_t lane_stream(int device, int lane) {  // the device is current; a device that could not make every lane's stream has none
+  const auto set = lane_streams().get(device);
+  return set.n == kLanes ? set.s[lane % kLanes] : nullptr;
+}
 namespace o3s_cloud {
-void reg_warm_lane_streams(int device) { (void)refine_streams().get(device, 0); }  // o3s_o3d_registration_reserve_n with count > 1
+void reg_warm_lane_streams(int device) { (void)lane_streams().get(device); }  // o3s_o3d_registration_reserve_n with count > 1
 }  // namespace o3s_cloud
 }  // namespace
 
@@ -465,12 +454,12 @@ int refine_overlap_batch(int32_t n, const o3s_submap* const* sources, const o3s_
     CK(hipStreamSynchronize(sources[k]->stream));
     CK(hipStreamSynchronize(targets[k]->stream));
   }
-  const int lanes = std::min<int>(RefineStreams::kLanes, n);
+  const int lanes = std::min<int>(kLanes, n);
   std::vector<hipStream_t> streams((size_t)lanes);
   for (int l = 0; l < lanes; ++l) {
     // one pair: the target's own stream, like the single call (no lane stream is needed — or made: the first use of the lanes'
     // streams creates them, ~3 ms each, unless o3s_o3d_registration_reserve_n has done so ahead of time)
-    streams[(size_t)l] = lanes == 1 ? targets[0]->stream : refine_streams().get(device, l);
+    streams[(size_t)l] = lanes == 1 ? targets[0]->stream : lane_stream(device, l);
     if (!streams[(size_t)l]) return O3S_ERR_HIP;
   }
   auto one = [&](int32_t k, hipStream_t s) {
@@ -690,7 +679,7 @@ int o3s_submap_build_voxel_map(o3s_submap* m, double voxel_size) {
     uint32_t r[2] = {0, 0};
     if (m->n > 0) {
       // the full-size table holds at most one voxel per point at half load: every key finds a slot
-      hipLaunchKernelGGL(k_vm_insert, dim3(nblk(m->n)), dim3(kB), 0, s, (const double*)m->pts[m->cur].d(), m->n, 1.0 / voxel_size, tab, slots - 1u,
+      hipLaunchKernelGGL(k_vm_insert, dim3(nblk(m->n)), dim3(kB), 0, s, (const double*)m->pts[m->cur].as<double>(), m->n, 1.0 / voxel_size, tab, slots - 1u,
                          slots == full ? slots : std::min(slots, kVmMaxProbe), cnt);
       CK(hipGetLastError());
       if (const int rf = vm_fetch(cnt, r, s); rf != O3S_OK) return rf;
@@ -718,7 +707,7 @@ int o3s_submap_overlap_fitness(const o3s_submap* m, const double* pts, int64_t N
   if (!pts) return O3S_ERR_BAD_ARGUMENT;
   int rc = set_dev(m);
   if (rc != O3S_OK) return rc;
-  Buf d_p;
+  DevMem d_p;
   CK(d_p.alloc((size_t)N * 24));
   CK(hipMemcpyAsync(d_p.p, pts, (size_t)N * 24, hipMemcpyHostToDevice, m->stream));
   rc = vm_count_dev(m, d_p.as<double>(), N, T_map_sensor, n_overlapping);
@@ -742,7 +731,7 @@ int o3s_submap_overlap_fitness_scan(const o3s_submap* m, const o3s_scan* scan, i
     CK(hipEventRecord(scan->handover, scan->stream));
     CK(hipStreamWaitEvent(m->stream, scan->handover, 0));
   }
-  rc = vm_count_dev(m, (which == 0 ? scan->wide_p : scan->narrow_p).d(), N, T_map_sensor, n_overlapping);
+  rc = vm_count_dev(m, (which == 0 ? scan->wide_p : scan->narrow_p).as<double>(), N, T_map_sensor, n_overlapping);
   if (rc != O3S_OK) return rc;
   CK(hipStreamSynchronize(m->stream));  // the scan may be refilled when this returns
   *fitness = (double)*n_overlapping / (double)N;

@@ -31,7 +31,7 @@ inline int place_check_submaps(const o3s_submap* source, const o3s_submap* const
     if (targets[k]->n_feat < 0) return O3S_ERR_NOT_INITIALIZED;
   for (int k = 0; k < K; ++k) {
     n_tgt[k] = targets[k]->n_feat;
-    f[k] = n_tgt[k] > 0 ? targets[k]->feat_f.d() : nullptr;
+    f[k] = n_tgt[k] > 0 ? targets[k]->feat_f.as<double>() : nullptr;
   }
   return place_sizes_ok(source->n_feat, n_tgt, K) ? O3S_OK : O3S_ERR_BAD_ARGUMENT;
 }
@@ -61,7 +61,7 @@ int o3s_feature_correspondences_multi(int device, const double* src_feat, int64_
   const int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
   hipStream_t s = nullptr;
-  Buf d_a, d_b[kPlaceMaxTargets];
+  DevMem d_a, d_b[kPlaceMaxTargets];
   PlaceWork w;
   const double* d_t[kPlaceMaxTargets];
   CK(d_a.alloc((size_t)n_src * (size_t)dim * 8));
@@ -104,7 +104,7 @@ int o3s_submaps_feature_correspondences(const o3s_submap* source, const o3s_subm
   rc = place_drain_targets(source, targets, K);
   if (rc != O3S_OK) return rc;
   RansacLease w(source->device, s);
-  rc = place_correspondences_dev(w->place, source->feat_f.d(), n, f, n_tgt, K, kFpfhDim, mutual_filter, ransac_n, n_out, used_fallback, s);
+  rc = place_correspondences_dev(w->place, source->feat_f.as<double>(), n, f, n_tgt, K, kFpfhDim, mutual_filter, ransac_n, n_out, used_fallback, s);
   if (rc != O3S_OK) return rc;
   for (int k = 0; k < K; ++k)
     if (n_out[k] > 0)
@@ -133,12 +133,12 @@ int o3s_submaps_registration_ransac(const o3s_submap* source, const o3s_submap* 
   rc = place_drain_targets(source, targets, K);
   if (rc != O3S_OK) return rc;
   RansacLease w(source->device, s);
-  rc = place_correspondences_dev(w->place, source->feat_f.d(), n, f, n_tgt, K, kFpfhDim, mutual_filter, std::max(params->ransac_n, 0), n_pairs, nullptr, s);
+  rc = place_correspondences_dev(w->place, source->feat_f.as<double>(), n, f, n_tgt, K, kFpfhDim, mutual_filter, std::max(params->ransac_n, 0), n_pairs, nullptr, s);
   if (rc != O3S_OK) return rc;
   for (int k = 0; k < K; ++k) {  // one target after the other, each from its slice of the device pair buffer
     if (n_correspondences) n_correspondences[k] = n_pairs[k];
     if (n_tgt[k] == 0 || ransac_trivial(params, n_pairs[k])) continue;
-    rc = ransac_run_dev(*w.w, source->feat_p.d(), n, targets[k]->feat_p.d(), n_tgt[k], w->place.pairs.as<int32_t>() + 2 * (size_t)n * (size_t)k, n_pairs[k], params,
+    rc = ransac_run_dev(*w, source->feat_p.as<double>(), n, targets[k]->feat_p.as<double>(), n_tgt[k], w->place.pairs.as<int32_t>() + 2 * (size_t)n * (size_t)k, n_pairs[k], params,
                         nullptr, 0, &results[k], inlier_correspondences ? inlier_correspondences + 2 * (size_t)n * (size_t)k : nullptr, s);
     if (rc != O3S_OK) return rc;
   }

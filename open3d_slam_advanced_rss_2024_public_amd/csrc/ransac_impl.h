@@ -13,49 +13,18 @@ namespace o3s_cloud {
 // Grow-only work area of one RANSAC call: sized by the number of correspondences and the batch size, leased per call from a pool
 // per device (o3s_ransac_reserve sizes one ahead of time), so that repeated closures do not allocate.
 struct RansacWork {
-  int device = -1;
-  Buf src, tgt, pairs, table, feat_pairs;  // staging of the host-buffer entries
-  Buf rec, hdr, flag, off, outcome, T, surv, part_n, part_e, sv_n, sv_e, scan_tmp, iflag, ioff, iout, slot_n, slot_e;
+  DevMem src, tgt, pairs, table, feat_pairs;  // staging of the host-buffer entries
+  DevMem rec, hdr, flag, off, outcome, T, surv, part_n, part_e, sv_n, sv_e, scan_tmp, iflag, ioff, iout, slot_n, slot_e;
   PostBlock<> post;  // kRansacAhead slots of the common layout, one per batch in flight
   FeatNnWork nn;
   PlaceWork place;  // the one-to-many front end (place_impl.h)
   size_t scan_bytes = 0;
+  RansacWork() = default;
+  RansacWork(const RansacWork&) = delete;
+  RansacWork& operator=(const RansacWork&) = delete;
+  ~RansacWork() { post.release(); }  // only ever runs through o3s_ransac_release (the pool itself is never torn down)
 };
-struct RansacPool {
-  std::mutex m;
-  std::vector<std::unique_ptr<RansacWork>> idle;
-};
-inline RansacPool& ransac_pool() {
-  static RansacPool* p = new RansacPool;  // never destroyed: its buffers must not be freed behind the runtime's own teardown
-  return *p;
-}
-struct RansacLease {
-  std::unique_ptr<RansacWork> w;
-  hipStream_t s;
-  explicit RansacLease(int device, hipStream_t stream = nullptr) : s(stream) {
-    RansacPool& p = ransac_pool();
-    {
-      std::lock_guard<std::mutex> g(p.m);
-      for (size_t k = 0; k < p.idle.size(); ++k)
-        if (p.idle[k]->device == device) {
-          w = std::move(p.idle[k]);
-          p.idle.erase(p.idle.begin() + (long)k);
-          break;
-        }
-    }
-    if (!w) {
-      w.reset(new RansacWork);
-      w->device = device;
-    }
-  }
-  ~RansacLease() {  // every exit, an early error included, hands the area back behind a drained stream
-    (void)hipStreamSynchronize(s);
-    RansacPool& p = ransac_pool();
-    std::lock_guard<std::mutex> g(p.m);
-    p.idle.push_back(std::move(w));
-  }
-  RansacWork* operator->() { return w.get(); }
-};
+using RansacLease = AreaLease<RansacWork, /*kAlwaysDrain=*/true>;  // every exit, an early error included, hands the area back behind a drained stream
 
 inline int ransac_batch() {  // a constant in the product; the hooks build reads it per call (one test, several batch sizes)
   if (const char* e = O3S_HOOK_ENV("O3S_RANSAC_BATCH")) {
@@ -266,24 +235,10 @@ int o3s_ransac_reserve(int device, int64_t max_correspondences) {
   const int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
   RansacLease w(device);
-  return ransac_size_work(*w.w, max_correspondences, ransac_batch());
+  return ransac_size_work(*w, max_correspondences, ransac_batch());
 }
 
-int o3s_ransac_release(int device) {
-  const int rc = pick_device(device);
-  if (rc != O3S_OK) return rc;
-  CK(hipDeviceSynchronize());
-  RansacPool& p = ransac_pool();
-  std::lock_guard<std::mutex> g(p.m);
-  for (size_t k = 0; k < p.idle.size();)
-    if (p.idle[k]->device == device) {
-      p.idle[k]->post.release();
-      p.idle.erase(p.idle.begin() + (long)k);
-    } else {
-      ++k;
-    }
-  return O3S_OK;
-}
+int o3s_ransac_release(int device) { return release_idle_areas<RansacWork>(device); }
 
 int o3s_registration_ransac_correspondence(int device, const double* source, int64_t Ns, const double* target, int64_t Nt,
                                            const int32_t* correspondences, int64_t K, const o3s_ransac_params* params, const int32_t* samples,
@@ -301,13 +256,13 @@ int o3s_registration_ransac_correspondence(int device, const double* source, int
   int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
   RansacLease w(device);
-  rc = ransac_upload_clouds(*w.w, source, Ns, target, Nt, correspondences, K, w.s);
+  rc = ransac_upload_clouds(*w, source, Ns, target, Nt, correspondences, K, w.s);
   if (rc != O3S_OK) return rc;
   if (samples && n_iter > 0) {
     CK(w->table.alloc((size_t)n_iter * params->ransac_n * 4));
     CK(hipMemcpyAsync(w->table.p, samples, (size_t)n_iter * params->ransac_n * 4, hipMemcpyHostToDevice, w.s));
   }
-  return ransac_run_dev(*w.w, w->src.as<double>(), Ns, w->tgt.as<double>(), Nt, w->pairs.as<int32_t>(), K, params,
+  return ransac_run_dev(*w, w->src.as<double>(), Ns, w->tgt.as<double>(), Nt, w->pairs.as<int32_t>(), K, params,
                         samples ? w->table.as<int32_t>() : nullptr, n_iter, result, inlier_correspondences, w.s);
 }
 
@@ -345,17 +300,17 @@ int o3s_ransac_evaluate_samples(int device, const double* source, int64_t Ns, co
   RansacLease w(device);
   hipStream_t s = w.s;
   const int batch = ransac_batch();
-  rc = ransac_size_work(*w.w, K, batch);
+  rc = ransac_size_work(*w, K, batch);
   if (rc != O3S_OK) return rc;
   CK(w->slot_n.alloc((size_t)batch * 8));
   CK(w->slot_e.alloc((size_t)batch * 8));
-  rc = ransac_upload_clouds(*w.w, source, Ns, target, Nt, correspondences, K, s);
+  rc = ransac_upload_clouds(*w, source, Ns, target, Nt, correspondences, K, s);
   if (rc != O3S_OK) return rc;
   if (samples) {
     CK(w->table.alloc((size_t)H * params->ransac_n * 4));
     CK(hipMemcpyAsync(w->table.p, samples, (size_t)H * params->ransac_n * 4, hipMemcpyHostToDevice, s));
   }
-  rc = ransac_prepare(*w.w, w->src.as<double>(), Ns, w->tgt.as<double>(), Nt, w->pairs.as<int32_t>(), K, H, s);
+  rc = ransac_prepare(*w, w->src.as<double>(), Ns, w->tgt.as<double>(), Nt, w->pairs.as<int32_t>(), K, H, s);
   if (rc != O3S_OK) return rc;
   const RansacArgs a = ransac_args(params, K);
   std::vector<double> T12((size_t)batch * 12);
@@ -363,7 +318,7 @@ int o3s_ransac_evaluate_samples(int device, const double* source, int64_t Ns, co
     const int count = (int)std::min<int64_t>(batch, H - done);
     CK(hipMemsetAsync(w->slot_n.p, 0, (size_t)count * 8, s));
     CK(hipMemsetAsync(w->slot_e.p, 0, (size_t)count * 8, s));
-    rc = ransac_issue_batch(*w.w, a, samples ? w->table.as<int32_t>() : nullptr, first_iteration + done, count, batch, nullptr,
+    rc = ransac_issue_batch(*w, a, samples ? w->table.as<int32_t>() : nullptr, first_iteration + done, count, batch, nullptr,
                             w->slot_n.as<long long>(), w->slot_e.as<double>(), s);
     if (rc != O3S_OK) return rc;
     CK(hipMemcpyAsync(outcome + done, w->outcome.p, (size_t)count * 4, hipMemcpyDeviceToHost, s));
@@ -398,14 +353,14 @@ int o3s_submap_registration_ransac(const o3s_submap* source, const o3s_submap* t
   // the mutual filter of the two index arrays runs on the host (feature_correspondences_dev): 4 (n + m) bytes come down, the pairs go up
   std::vector<int32_t> pairs((size_t)source->n_feat * 2);
   int64_t K = 0;
-  rc = feature_correspondences_dev(w->nn, source->feat_f.d(), source->n_feat, target->feat_f.d(), target->n_feat, kFpfhDim, mutual_filter,
+  rc = feature_correspondences_dev(w->nn, source->feat_f.as<double>(), source->n_feat, target->feat_f.as<double>(), target->n_feat, kFpfhDim, mutual_filter,
                                    std::max(params->ransac_n, 0), pairs.data(), &K, nullptr, s);
   if (rc != O3S_OK) return rc;
   if (n_correspondences) *n_correspondences = K;
   if (ransac_trivial(params, K)) return O3S_OK;
   CK(w->feat_pairs.alloc((size_t)K * 8));
   CK(hipMemcpyAsync(w->feat_pairs.p, pairs.data(), (size_t)K * 8, hipMemcpyHostToDevice, s));
-  rc = ransac_run_dev(*w.w, source->feat_p.d(), source->n_feat, target->feat_p.d(), target->n_feat, w->feat_pairs.as<int32_t>(), K, params, nullptr, 0,
+  rc = ransac_run_dev(*w, source->feat_p.as<double>(), source->n_feat, target->feat_p.as<double>(), target->n_feat, w->feat_pairs.as<int32_t>(), K, params, nullptr, 0,
                       result, inlier_correspondences, s);
   return rc;
 }

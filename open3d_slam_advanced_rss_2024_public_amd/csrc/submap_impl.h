@@ -10,33 +10,6 @@
 
 namespace {
 
-// grow-only device array
-struct DArr {
-  void* p = nullptr;
-  size_t cap = 0;
-  ~DArr() {
-    if (p) (void)hipFree(p);
-  }
-  // keeps the first `keep` bytes when it has to move
-  hipError_t ensure(size_t bytes, size_t keep, hipStream_t s) {
-    if (bytes <= cap) return hipSuccess;
-    size_t want = bytes + bytes / 2 + 4096;
-    if (cap && want < 2 * cap) want = 2 * cap;  // a map that grows: each move is a device-wide stall of several milliseconds
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, want);
-    if (e != hipSuccess) return e;
-    if (p && keep) {
-      e = hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    if (p) (void)hipFree(p);
-    p = q;
-    cap = want;
-    return e;
-  }
-  double* d() const { return reinterpret_cast<double*>(p); }
-};
-
 // o3d_slam::transform (helpers.cpp:283-318): p' = (T [p 1]).head<3>() / w, n' = (T [n 0]).head<3>(); the 4-term
 // products are accumulated k = 0..3 in fp64 without contraction
 struct Mat4d {  // a pose as a kernel argument: no 128-byte host-to-device copy in front of the launch
@@ -289,9 +262,9 @@ struct o3s_submap {
   double voxel = 0.0;
   o3s_cropper cropper{};
   hipStream_t stream = nullptr;
-  bool owns_stream = true;        // false: `stream` is one of the device's shared submap streams (submap_stream_pool)
+  bool owns_stream = true;        // false: `stream` is one of the device's shared submap streams (submap_streams)
   hipEvent_t handover = nullptr;  // recorded on `stream`, waited for by the ICP handle's stream (o3s_icp_wait_event)
-  DArr pts[2], nrm[2];  // ping-pong: voxelisation reads [cur] and writes [1 - cur]
+  DevMem pts[2], nrm[2];  // ping-pong: voxelisation reads [cur] and writes [1 - cur]
   int cur = 0;
   int64_t n = 0;
   // layout of the map array after a voxelisation: [n_pt pass-through points | one point per voxel in key order]; valid only while
@@ -301,10 +274,10 @@ struct o3s_submap {
   int merge_backoff = 0;              // inserts left before the merge path is tried again after it had to give way to the sort
   int64_t n_merged = 0, n_sorted = 0, n_fell_back = 0;  // how the voxelising inserts ran (o3s_submap_insert_stats)
   int has_normals = -1;  // -1: undecided (empty map)
-  DArr col[2];           // colours of the map cloud (open3d PointCloud::colors_), ping-pong like the points
+  DevMem col[2];           // colours of the map cloud (open3d PointCloud::colors_), ping-pong like the points
   int has_colors = 0;    // 1 while the map carries one colour per point (PointCloud::HasColors())
-  DArr scan_c;
-  DArr scan_p, scan_n, carve_scan, d_T, patch_xyzw, patch_n32;
+  DevMem scan_c;
+  DevMem scan_p, scan_n, carve_scan, d_T, patch_xyzw, patch_n32;
   Arena arena;
   // An insert whose completion is looked at later (o3s_submap_insert_processed): everything is enqueued, the merge path's counts and
   // verdict are on their way to a mailbox slot, and `n`, `cur`, `n_pt` still describe the map BEFORE the insert.  submap_settle() —
@@ -318,17 +291,17 @@ struct o3s_submap {
     bool hn = false;
     VoxHint vh{};
   } pend;
-  DArr d_post;                      // 4 words the pending insert's counts also go to (lazy_post_fetch's fallback)
+  DevMem d_post;                      // 4 words the pending insert's counts also go to (lazy_post_fetch's fallback)
   hipEvent_t scan_read = nullptr;   // recorded when an insert has read its device scan: the scan's stream waits for it before the object is rewritten
   // the feature set of o3s_submap_compute_features: sparse cloud, its normals, FPFH (33 x n_feat); -1: none.  It describes the map
   // as it was when it was computed; inserts leave it alone
-  DArr feat_p, feat_n, feat_f;
+  DevMem feat_p, feat_n, feat_f;
   int64_t n_feat = -1;
   FpfhWork feat_w;  // grid, neighbour lists and SPFH of the last computation (given back by o3s_submap_trim)
   // the occupancy snapshot of o3s_submap_build_voxel_map (Submap::voxelMap_): an open-addressing table of packed voxel keys + 1
   // (0: empty), vox_slots of them (a power of two); n_vox = distinct voxels, -1: never built.  Like the feature set it describes the
   // map as it was when it was built: inserts, carving and o3s_submap_transform leave it alone (overlap_impl.h)
-  DArr vox_tab;
+  DevMem vox_tab;
   int64_t n_vox = -1;
   uint32_t vox_slots = 0;
   double vox_size = 0.0;
@@ -345,32 +318,20 @@ inline int submap_settle(const o3s_submap* m) { return submap_settle(const_cast<
 // the process, dealt round-robin: two submaps on one stream only ever order their work behind each other (the mapper works on one
 // submap at a time), which no call's semantics depends on.  Snapshots made for a worker thread (o3s_submap_clone) get a stream of
 // their own: they are there to run beside the mapper.
-struct SubmapStreamPool {
-  static constexpr int kPerDevice = 4;
-  std::mutex m;
-  std::vector<std::vector<hipStream_t>> streams;  // [device][k]
-  std::vector<unsigned> next;
-  hipStream_t get(int device) {  // the device is current
-    std::lock_guard<std::mutex> g(m);
-    if ((size_t)device >= streams.size()) {
-      streams.resize((size_t)device + 1);
-      next.resize((size_t)device + 1, 0u);
-    }
-    std::vector<hipStream_t>& v = streams[(size_t)device];
-    const unsigned k = next[(size_t)device]++ % (unsigned)kPerDevice;
-    // all of a device's streams are made with its first submap (a collection's constructor), not one per switch of submaps later
-    while (v.size() < (size_t)kPerDevice) {
-      hipStream_t s = nullptr;
-      if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) break;
-      v.push_back(s);
-    }
-    if (v.empty()) return nullptr;
-    return v[k % (unsigned)v.size()];
-  }
-};
-inline SubmapStreamPool& submap_stream_pool() {
-  static SubmapStreamPool* p = new SubmapStreamPool;  // never destroyed: its streams must not be torn down behind the runtime's own exit
+inline DeviceStreams<4>& submap_streams() {
+  static DeviceStreams<4>* p = new DeviceStreams<4>;  // never destroyed (see DeviceStreams)
   return *p;
+}
+// all of a device's streams are made with its first submap (a collection's constructor), not one per switch of submaps later;
+// a device that could not make all four deals what it got, and has no stream only if it got none
+inline hipStream_t next_submap_stream(int device) {  // the device is current
+  static std::mutex m;
+  static std::vector<unsigned> next;  // [device]: the round-robin turn
+  const auto set = submap_streams().get(device);
+  std::lock_guard<std::mutex> g(m);
+  if ((size_t)device >= next.size()) next.resize((size_t)device + 1, 0u);
+  const unsigned k = next[(size_t)device]++ % 4u;
+  return set.n ? set.s[k % (unsigned)set.n] : nullptr;
 }
 }  // namespace
 
@@ -389,7 +350,7 @@ static int submap_create_impl(int device, double map_voxel_size, const o3s_cropp
   if (own_stream) {
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) m->stream = nullptr;
   } else {
-    m->stream = submap_stream_pool().get(device);
+    m->stream = next_submap_stream(device);
   }
   if (!m->stream || hipEventCreateWithFlags(&m->handover, hipEventDisableTiming) != hipSuccess) {
     if (m->stream && m->owns_stream) (void)hipStreamDestroy(m->stream);
@@ -449,7 +410,7 @@ int o3s_submap_clone(const o3s_submap* src, int device, o3s_submap** out) {
   if (hipSetDevice(m->device) != hipSuccess) return fail(O3S_ERR_HIP);
   const size_t bytes = (size_t)src->n * 24;
   hipStream_t s = m->stream;
-  auto copy = [&](DArr& dst, const DArr& from) -> bool {
+  auto copy = [&](DevMem& dst, const DevMem& from) -> bool {
     if (dst.ensure(bytes, 0, s) != hipSuccess) return false;
     if (m->device == src->device) return hipMemcpyAsync(dst.p, from.p, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess;
     return hipMemcpyPeerAsync(dst.p, m->device, from.p, src->device, bytes, s) == hipSuccess;  // over xGMI when the devices are peers
@@ -468,7 +429,7 @@ int o3s_submap_clone(const o3s_submap* src, int device, o3s_submap** out) {
   m->layout_valid = src->layout_valid;
   if (src->n_feat > 0) {  // the feature set travels with the snapshot
     const size_t nf = (size_t)src->n_feat;
-    auto copy_n = [&](DArr& dst, const DArr& from, size_t b) -> bool {
+    auto copy_n = [&](DevMem& dst, const DevMem& from, size_t b) -> bool {
       if (dst.ensure(b, 0, s) != hipSuccess) return false;
       if (m->device == src->device) return hipMemcpyAsync(dst.p, from.p, b, hipMemcpyDeviceToDevice, s) == hipSuccess;
       return hipMemcpyPeerAsync(dst.p, m->device, from.p, src->device, b, s) == hipSuccess;
@@ -513,7 +474,7 @@ int o3s_submap_reserve(o3s_submap* m, int64_t n_points) {
   }
   // the work area of either insert pipeline at that size (the merge takes the map plus a scan of up to 2 x 64 x 2048 points)
   const size_t work = std::max(voxel_arena_bytes(n_points), insert_merge_arena_bytes(n_points, n_points, std::min<int64_t>(n_points, 262144)));
-  if (m->arena.cap < work) CK(m->arena.reserve(work));
+  if (m->arena.mem.cap < work) CK(m->arena.reserve(work));
   return O3S_OK;
 }
 
@@ -526,51 +487,28 @@ int o3s_submap_trim(o3s_submap* m) {
   // a submap that is no longer inserted into keeps its map cloud ([cur]) and nothing else: the spare ping-pong arrays, the
   // sort / scan work area and the scan staging go back to the allocator (they come back on the next reserve / insert); the patch
   // buffers stay: an ICP handle may still be indexing the last patch on its own stream
-  auto drop = [](DArr& a) {
-    if (a.p) (void)hipFree(a.p);
-    a.p = nullptr;
-    a.cap = 0;
-  };
   const int spare = 1 - m->cur;
-  drop(m->pts[spare]);
-  drop(m->nrm[spare]);
-  drop(m->col[spare]);
-  drop(m->scan_p);
-  drop(m->scan_n);
-  drop(m->scan_c);
-  drop(m->carve_scan);
-  if (m->arena.base) (void)hipFree(m->arena.base);
-  m->arena.base = nullptr;
-  m->arena.cap = m->arena.used = 0;
+  for (DevMem* a : {&m->pts[spare], &m->nrm[spare], &m->col[spare], &m->scan_p, &m->scan_n, &m->scan_c, &m->carve_scan}) a->release();
+  m->arena.release();
   // the feature set stays (a closed submap is what place recognition matches against); its work areas go
-  drop_normals_work(m->feat_w.grid);
-  drop_buf(m->feat_w.idx);
-  drop_buf(m->feat_w.d2);
-  drop_buf(m->feat_w.spfh);
+  m->feat_w.release();
   // shrink the map arrays themselves to what the map holds (a submap closed by radius at a fraction of the reserved size)
   const size_t need = (size_t)m->n * 24;
-  auto shrink = [&](DArr& a, bool used) -> hipError_t {
-    if (!a.p || !used || a.cap <= need + need / 8 + 4096) return hipSuccess;
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, need + 4096);
-    if (e != hipSuccess) return hipSuccess;  // no room for the copy: keep the large array
-    e = hipMemcpyAsync(q, a.p, need, hipMemcpyDeviceToDevice, m->stream);
+  auto shrink = [&](DevMem& a) -> hipError_t {
+    if (!a.p || a.cap <= need + need / 8 + 4096) return hipSuccess;
+    DevMem q;
+    if (q.reset(need + 4096) != hipSuccess) return hipSuccess;  // no room for the copy: keep the large array
+    hipError_t e = hipMemcpyAsync(q.p, a.p, need, hipMemcpyDeviceToDevice, m->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    if (e != hipSuccess) {
-      (void)hipFree(q);
-      return e;
-    }
-    (void)hipFree(a.p);
-    a.p = q;
-    a.cap = need + 4096;
-    return hipSuccess;
+    if (e == hipSuccess) a = std::move(q);
+    return e;
   };
-  CK(shrink(m->pts[m->cur], true));
+  CK(shrink(m->pts[m->cur]));
   // a map without normals / colours keeps none of the reserved room for them (the arrays come back with the next reserve / insert)
-  if (m->has_normals == 1) CK(shrink(m->nrm[m->cur], true));
-  else drop(m->nrm[m->cur]);
-  if (m->has_colors == 1) CK(shrink(m->col[m->cur], true));
-  else drop(m->col[m->cur]);
+  if (m->has_normals == 1) CK(shrink(m->nrm[m->cur]));
+  else m->nrm[m->cur].release();
+  if (m->has_colors == 1) CK(shrink(m->col[m->cur]));
+  else m->col[m->cur].release();
   return O3S_OK;
 }
 
@@ -585,64 +523,46 @@ int o3s_submap_hand_over(o3s_submap* from, o3s_submap* to) {
   hipStream_t s = from->stream;
   const int c = from->cur;
   const size_t need = (size_t)from->n * 24;
-  DArr* ff[3] = {from->pts, from->nrm, from->col};
-  DArr* tf[3] = {to->pts, to->nrm, to->col};
+  DevMem* ff[3] = {from->pts, from->nrm, from->col};
+  DevMem* tf[3] = {to->pts, to->nrm, to->col};
   const bool used[3] = {true, from->has_normals == 1, from->has_colors == 1};
   // 1. the closed submap's map into arrays of its own size (the only allocations: a few MB each; nothing has moved if one fails)
-  void* tight[3] = {nullptr, nullptr, nullptr};
+  DevMem tight[3];  // (an early return frees them)
   hipError_t e = hipSuccess;
   for (int f = 0; f < 3 && e == hipSuccess; ++f)
     if (used[f] && need > 0 && ff[f][c].p) {
-      e = hipMalloc(&tight[f], need + 4096);
-      if (e == hipSuccess) e = hipMemcpyAsync(tight[f], ff[f][c].p, need, hipMemcpyDeviceToDevice, s);
+      e = tight[f].reset(need + 4096);
+      if (e == hipSuccess) e = hipMemcpyAsync(tight[f].p, ff[f][c].p, need, hipMemcpyDeviceToDevice, s);
     }
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) {
-    for (void* q : tight)
-      if (q) (void)hipFree(q);
-    return O3S_ERR_HIP;
-  }
-  // 2. everything else changes hands
-  auto give = [](DArr& dst, DArr& src) {
-    if (dst.p) (void)hipFree(dst.p);  // a fresh submap holds nothing; one that was reserved gives that back
-    dst.p = src.p;
-    dst.cap = src.cap;
-    src.p = nullptr;
-    src.cap = 0;
-  };
+  if (e != hipSuccess) return O3S_ERR_HIP;
+  // 2. everything else changes hands (a fresh submap holds nothing; one that was reserved gives that back)
   for (int f = 0; f < 3; ++f) {
-    give(tf[f][0], ff[f][c]);
-    give(tf[f][1], ff[f][1 - c]);
-    if (tight[f]) {
-      ff[f][c].p = tight[f];
-      ff[f][c].cap = need + 4096;
-    }
+    tf[f][0] = std::move(ff[f][c]);
+    tf[f][1] = std::move(ff[f][1 - c]);
+    if (tight[f].p) ff[f][c] = std::move(tight[f]);
   }
   to->cur = 0;
-  give(to->scan_p, from->scan_p);
-  give(to->scan_n, from->scan_n);
-  give(to->scan_c, from->scan_c);
-  give(to->carve_scan, from->carve_scan);
-  give(to->patch_xyzw, from->patch_xyzw);
-  give(to->patch_n32, from->patch_n32);
-  give(to->d_post, from->d_post);
-  if (to->arena.base) (void)hipFree(to->arena.base);
-  to->arena.base = from->arena.base;
-  to->arena.cap = from->arena.cap;
-  to->arena.used = 0;
-  from->arena.base = nullptr;
-  from->arena.cap = from->arena.used = 0;
+  to->scan_p = std::move(from->scan_p);
+  to->scan_n = std::move(from->scan_n);
+  to->scan_c = std::move(from->scan_c);
+  to->carve_scan = std::move(from->carve_scan);
+  to->patch_xyzw = std::move(from->patch_xyzw);
+  to->patch_n32 = std::move(from->patch_n32);
+  to->d_post = std::move(from->d_post);
+  to->arena.mem = std::move(from->arena.mem);
+  to->arena.used = from->arena.used = 0;
   return O3S_OK;
 }
 
 int64_t o3s_submap_device_bytes(const o3s_submap* m) {
   (void)submap_settle(m);
   if (!m) return 0;
-  size_t b = m->arena.cap;
+  size_t b = m->arena.mem.cap;
   for (int k = 0; k < 2; ++k) b += m->pts[k].cap + m->nrm[k].cap + m->col[k].cap;
   b += m->scan_p.cap + m->scan_n.cap + m->scan_c.cap + m->carve_scan.cap + m->d_T.cap + m->patch_xyzw.cap + m->patch_n32.cap;
   b += m->vox_tab.cap;
-  b += m->feat_p.cap + m->feat_n.cap + m->feat_f.cap + m->feat_w.grid.arena.cap + m->feat_w.grid.cells_cap + m->feat_w.idx.cap + m->feat_w.d2.cap +
+  b += m->feat_p.cap + m->feat_n.cap + m->feat_f.cap + m->feat_w.grid.arena.mem.cap + m->feat_w.grid.cells.cap + m->feat_w.idx.cap + m->feat_w.d2.cap +
        m->feat_w.spfh.cap;
   return (int64_t)b;
 }
@@ -656,9 +576,9 @@ int o3s_submap_center(const o3s_submap* m, double center[3]) {
   if (rc != O3S_OK) return rc;
   hipStream_t s = m->stream;
   const int G = (int)std::min<int64_t>(256, (m->n + kB - 1) / kB);
-  Buf part;
+  DevMem part;
   CK(part.alloc((size_t)G * 24));
-  hipLaunchKernelGGL(k_center_part, dim3(G), dim3(kB), 0, s, (const double*)m->pts[m->cur].d(), m->n, part.as<double>());
+  hipLaunchKernelGGL(k_center_part, dim3(G), dim3(kB), 0, s, (const double*)m->pts[m->cur].as<double>(), m->n, part.as<double>());
   CK(hipGetLastError());
   double h[256 * 3];
   CK(hipMemcpyAsync(h, part.p, (size_t)G * 24, hipMemcpyDeviceToHost, s));
@@ -683,7 +603,7 @@ int o3s_transform_cloud(int device, const double T[16], const double* pts, const
     for (int c = 0; c < 4; ++c) dev = std::max(dev, std::fabs(T[c * 4 + r] - (r == c ? 1.0 : 0.0)));
   const int64_t lead = dev < 1e-4 ? N : 0;  // "*out = cloud" first (helpers.cpp:285-288), the loop below appends regardless
   hipStream_t s = nullptr;
-  Buf a, b, c, d, e, f, t;
+  DevMem a, b, c, d, e, f, t;
   CK(a.alloc((size_t)N * 24));
   CK(d.alloc((size_t)N * 24));
   CK(t.alloc(128));
@@ -767,8 +687,8 @@ int submap_transform_enqueue(o3s_submap* m, const double* T) {
   for (int k = 0; k < 16; ++k) Tv.m[k] = T[k];
   const int c = m->cur;  // whichever ping-pong array is current (a closed submap's tight copy)
   const int64_t nf = m->n_feat > 0 ? m->n_feat : 0;
-  hipLaunchKernelGGL(k_submap_transform, dim3(nblk(m->n + nf)), dim3(kB), 0, m->stream, m->pts[c].d(), m->has_normals == 1 ? m->nrm[c].d() : nullptr,
-                     m->n, nf ? m->feat_p.d() : nullptr, nf ? m->feat_n.d() : nullptr, nf, Tv);
+  hipLaunchKernelGGL(k_submap_transform, dim3(nblk(m->n + nf)), dim3(kB), 0, m->stream, m->pts[c].as<double>(), m->has_normals == 1 ? m->nrm[c].as<double>() : nullptr,
+                     m->n, nf ? m->feat_p.as<double>() : nullptr, nf ? m->feat_n.as<double>() : nullptr, nf, Tv);
   CK(hipGetLastError());
   // The voxel order of the map array is the order of the OLD coordinates: the next insert sorts, and tries the merge right after
   // (a back-off counted revisits of the old frame).  The patch buffers and the feature work area (grid, lists, SPFH) carry no
@@ -821,16 +741,16 @@ int insert_finish(o3s_submap* m, int c, int64_t n_tmp, bool hn, bool have_vh, co
   hipStream_t s = m->stream;
   Attrs at;
   if (m->has_colors == 1) {
-    at.col = m->col[c].d();
-    at.out_col = m->col[1 - c].d();
+    at.col = m->col[c].as<double>();
+    at.out_col = m->col[1 - c].as<double>();
   }
   int rc = O3S_OK;
   bool hinted = merged;
   int64_t n_out = merged ? cnt_m[0] + cnt_m[1] : 0, n_pt_new = merged ? cnt_m[0] : 0;
   if (!hinted && have_vh) {
     int64_t cnt[3];
-    rc = voxel_pipeline_hint_dev(m->arena, 0, &m->cropper, vh, m->voxel, m->pts[c].d(), hn ? m->nrm[c].d() : nullptr, n_tmp, m->pts[1 - c].d(),
-                                 m->nrm[1 - c].d(), nullptr, &at, nullptr, nullptr, nullptr, cnt, &hinted, s);
+    rc = voxel_pipeline_hint_dev(m->arena, 0, &m->cropper, vh, m->voxel, m->pts[c].as<double>(), hn ? m->nrm[c].as<double>() : nullptr, n_tmp, m->pts[1 - c].as<double>(),
+                                 m->nrm[1 - c].as<double>(), nullptr, &at, nullptr, nullptr, nullptr, cnt, &hinted, s);
     if (rc == O3S_OK && hinted) {
       n_out = cnt[0] + cnt[1];
       n_pt_new = cnt[0];
@@ -839,8 +759,8 @@ int insert_finish(o3s_submap* m, int c, int64_t n_tmp, bool hn, bool have_vh, co
   }
   m->layout_valid = false;
   if (rc == O3S_OK && !hinted)
-    rc = voxel_pipeline_dev(m->arena, 0, &m->cropper, m->voxel, m->pts[c].d(), hn ? m->nrm[c].d() : nullptr, n_tmp, m->pts[1 - c].d(),
-                            m->nrm[1 - c].d(), nullptr, &n_out, s, &at);
+    rc = voxel_pipeline_dev(m->arena, 0, &m->cropper, m->voxel, m->pts[c].as<double>(), hn ? m->nrm[c].as<double>() : nullptr, n_tmp, m->pts[1 - c].as<double>(),
+                            m->nrm[1 - c].as<double>(), nullptr, &n_out, s, &at);
   if (rc != O3S_OK) {
     m->n = n_tmp;  // the appended cloud is still a valid map
     return rc;
@@ -898,8 +818,8 @@ int insert_dev(o3s_submap* m, const double* d_pts, const double* d_nrm, int64_t 
   CK(m->pts[c].ensure((size_t)n_tmp * 24, (size_t)m->n * 24, s));
   if (hn) CK(m->nrm[c].ensure((size_t)n_tmp * 24, (size_t)m->n * 24, s));
   // mapCloud_ += *transformedCloud (Submap.cpp:85)
-  double* dst_p = m->pts[c].d() + 3 * m->n;
-  double* dst_n = hn ? m->nrm[c].d() + 3 * m->n : nullptr;
+  double* dst_p = m->pts[c].as<double>() + 3 * m->n;
+  double* dst_n = hn ? m->nrm[c].as<double>() + 3 * m->n : nullptr;
   if (doubled) {
     CK(hipMemcpyAsync(dst_p, d_pts, (size_t)N * 24, hipMemcpyDeviceToDevice, s));
     if (hn) CK(hipMemcpyAsync(dst_n, d_nrm, (size_t)N * 24, hipMemcpyDeviceToDevice, s));
@@ -918,7 +838,7 @@ int insert_dev(o3s_submap* m, const double* d_pts, const double* d_nrm, int64_t 
     const bool keep_colors = (m->n == 0 || m->has_colors == 1) && scan_has;
     if (keep_colors) {
       CK(m->col[c].ensure((size_t)n_tmp * 24, (size_t)m->n * 24, s));
-      CK(hipMemcpyAsync(m->col[c].d() + 3 * m->n, d_col, (size_t)N * 24, hipMemcpyDeviceToDevice, s));
+      CK(hipMemcpyAsync(m->col[c].as<double>() + 3 * m->n, d_col, (size_t)N * 24, hipMemcpyDeviceToDevice, s));
     }
     m->has_colors = keep_colors ? 1 : 0;
   }
@@ -953,10 +873,10 @@ int insert_dev(o3s_submap* m, const double* d_pts, const double* d_nrm, int64_t 
         bool can_lazy = lazy && O3S_HOOK_ENV("O3S_INSERT_EAGER") == nullptr;
         if (can_lazy) {
           CK(m->d_post.ensure(64, 0, s));
-          can_lazy = lazy_post_open(pinned_area(), reinterpret_cast<uint32_t*>(m->d_post.d()), s, &lp);
+          can_lazy = lazy_post_open(pinned_area(), reinterpret_cast<uint32_t*>(m->d_post.as<double>()), s, &lp);
         }
-        rc = voxel_insert_merge_dev(m->arena, m->cropper, vh, m->voxel, m->pts[c].d(), hn ? m->nrm[c].d() : nullptr, m->n_pt, n_old, n_tmp,
-                                    m->pts[1 - c].d(), m->nrm[1 - c].d(), cnt_m, &merged, s, can_lazy ? &lp : nullptr, &issued);
+        rc = voxel_insert_merge_dev(m->arena, m->cropper, vh, m->voxel, m->pts[c].as<double>(), hn ? m->nrm[c].as<double>() : nullptr, m->n_pt, n_old, n_tmp,
+                                    m->pts[1 - c].as<double>(), m->nrm[1 - c].as<double>(), cnt_m, &merged, s, can_lazy ? &lp : nullptr, &issued);
         if (rc == O3S_OK && issued) {  // the answer is on its way: submap_settle() takes it from here
           m->layout_valid = false;
           m->pend.active = true;
@@ -998,7 +918,7 @@ int o3s_submap_insert_scan(o3s_submap* m, const double* pts, const double* norma
     CK(m->scan_n.ensure((size_t)N * 24, 0, s));
     CK(hipMemcpyAsync(m->scan_n.p, normals, (size_t)N * 24, hipMemcpyHostToDevice, s));
   }
-  return insert_dev(m, m->scan_p.d(), normals ? m->scan_n.d() : nullptr, N, T_map_sensor);
+  return insert_dev(m, m->scan_p.as<double>(), normals ? m->scan_n.as<double>() : nullptr, N, T_map_sensor);
 }
 
 int o3s_submap_insert_scan_colored(o3s_submap* m, const double* pts, const double* normals, const double* colors, int64_t N,
@@ -1019,7 +939,7 @@ int o3s_submap_insert_scan_colored(o3s_submap* m, const double* pts, const doubl
   }
   CK(m->scan_c.ensure((size_t)N * 24, 0, s));
   CK(hipMemcpyAsync(m->scan_c.p, colors, (size_t)N * 24, hipMemcpyHostToDevice, s));
-  return insert_dev(m, m->scan_p.d(), normals ? m->scan_n.d() : nullptr, N, T_map_sensor, m->scan_c.d());
+  return insert_dev(m, m->scan_p.as<double>(), normals ? m->scan_n.as<double>() : nullptr, N, T_map_sensor, m->scan_c.as<double>());
 }
 
 int o3s_submap_has_colors(const o3s_submap* m) {
@@ -1055,7 +975,7 @@ int o3s_submap_carve(o3s_submap* m, const o3s_carving_params* cp, const double* 
   CK(m->d_T.ensure(128, 0, s));
   CK(hipMemcpyAsync(m->scan_p.p, raw_pts, (size_t)N * 24, hipMemcpyHostToDevice, s));
   CK(hipMemcpyAsync(m->d_T.p, T_map_sensor, 128, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_transform_append, dim3(nblk(N)), dim3(kB), 0, s, m->scan_p.d(), (const double*)nullptr, N, m->d_T.d(), m->carve_scan.d(),
+  hipLaunchKernelGGL(k_transform_append, dim3(nblk(N)), dim3(kB), 0, s, m->scan_p.as<double>(), (const double*)nullptr, N, m->d_T.as<double>(), m->carve_scan.as<double>(),
                      (double*)nullptr);
   // wideCroppedIdxs = cropper.getIndicesWithinVolume(*map): the map-builder cropper at the pose of the previous insert
   const size_t nm = (size_t)Nm;
@@ -1074,7 +994,7 @@ int o3s_submap_carve(o3s_submap* m, const o3s_carving_params* cp, const double* 
   int32_t* d_mm = ar.take<int32_t>(kExtSlots * 6);
   const size_t tb_scan = scan_temp_bytes(Nm), tb_sort = sort_temp_bytes(Nm);
   void* tmp = ar.take<char>(std::max(tb_scan, tb_sort));
-  hipLaunchKernelGGL(k_mask, dim3(nblk(Nm)), dim3(kB), 0, s, m->cropper, m->pts[c].d(), Nm, 1, inflag);
+  hipLaunchKernelGGL(k_mask, dim3(nblk(Nm)), dim3(kB), 0, s, m->cropper, m->pts[c].as<double>(), Nm, 1, inflag);
   int64_t n_in = 0;
   rc = scan_flags(inflag, off, Nm, tmp, tb_scan, &n_in, s);
   if (rc != O3S_OK) return rc;
@@ -1082,7 +1002,7 @@ int o3s_submap_carve(o3s_submap* m, const o3s_carving_params* cp, const double* 
   const double inv = 1.0 / cp->voxel_size;
   rc = ext_i32_init(d_mm, s);
   if (rc != O3S_OK) return rc;
-  hipLaunchKernelGGL(k_carve_box, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].d(), Nm, inflag, inv, d_mm);
+  hipLaunchKernelGGL(k_carve_box, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].as<double>(), Nm, inflag, inv, d_mm);
   int32_t mm[6];
   rc = ext_i32_fetch(d_mm, mm, s);
   if (rc != O3S_OK) return rc;
@@ -1093,14 +1013,14 @@ int o3s_submap_carve(o3s_submap* m, const o3s_carving_params* cp, const double* 
   // with all 64 bits, three or four with the range that is known here)
   const int kb = key_bits((uint64_t)ex * (uint64_t)ey * (uint64_t)ez);
   const uint64_t out_key = kb < 63 ? (1ull << kb) : ~0ull;
-  hipLaunchKernelGGL(k_carve_keys, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].d(), Nm, inflag, inv, mm[0], mm[1], mm[2], (uint64_t)ex, (uint64_t)ey, out_key,
+  hipLaunchKernelGGL(k_carve_keys, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].as<double>(), Nm, inflag, inv, mm[0], mm[1], mm[2], (uint64_t)ex, (uint64_t)ey, out_key,
                      keys, vals);
   size_t tb = tb_sort;
   CK(sort_pairs(tmp, tb, keys, keys2, vals, vals2, nm, kb < 63 ? kb + 1 : 64, s));
   CK(hipMemsetAsync(remove, 0, nm * 4, s));
-  hipLaunchKernelGGL(k_carve_rays, dim3(nblk(N)), dim3(kB), 0, s, m->carve_scan.d(), N, T_map_sensor[12], T_map_sensor[13], T_map_sensor[14],
+  hipLaunchKernelGGL(k_carve_rays, dim3(nblk(N)), dim3(kB), 0, s, m->carve_scan.as<double>(), N, T_map_sensor[12], T_map_sensor[13], T_map_sensor[14],
                      cp->voxel_size, inv, cp->max_raytracing_length, cp->truncation_distance, cp->min_dot_product_with_normal, keys2, vals2, n_in, mm[0],
-                     mm[1], mm[2], ex, ey, ez, hn ? m->nrm[c].d() : nullptr, remove);
+                     mm[1], mm[2], ex, ey, ez, hn ? m->nrm[c].as<double>() : nullptr, remove);
   // removeByIds: SelectByIndex(ids, invert) keeps the survivors in their order
   hipLaunchKernelGGL(k_invert_flags, dim3(nblk(Nm)), dim3(kB), 0, s, remove, Nm, keep);
   int64_t n_keep = 0;
@@ -1109,12 +1029,12 @@ int o3s_submap_carve(o3s_submap* m, const o3s_carving_params* cp, const double* 
   if (n_keep < Nm) {
     CK(m->pts[1 - c].ensure((size_t)Nm * 24, 0, s));
     CK(m->nrm[1 - c].ensure((size_t)Nm * 24, 0, s));
-    hipLaunchKernelGGL(k_compact, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].d(), hn ? m->nrm[c].d() : nullptr, Nm, keep, off, m->pts[1 - c].d(),
-                       m->nrm[1 - c].d(), (int32_t*)nullptr);
+    hipLaunchKernelGGL(k_compact, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].as<double>(), hn ? m->nrm[c].as<double>() : nullptr, Nm, keep, off, m->pts[1 - c].as<double>(),
+                       m->nrm[1 - c].as<double>(), (int32_t*)nullptr);
     if (m->has_colors == 1) {  // SelectByIndex carries the colours along
       CK(m->col[1 - c].ensure((size_t)Nm * 24, 0, s));
-      hipLaunchKernelGGL(k_compact_attr, dim3(nblk(Nm)), dim3(kB), 0, s, (const double*)m->col[c].d(), (const double*)nullptr, Nm, keep, off,
-                         m->col[1 - c].d(), (double*)nullptr);
+      hipLaunchKernelGGL(k_compact_attr, dim3(nblk(Nm)), dim3(kB), 0, s, (const double*)m->col[c].as<double>(), (const double*)nullptr, Nm, keep, off,
+                         m->col[1 - c].as<double>(), (double*)nullptr);
     }
     CK(hipGetLastError());
     CK(hipStreamSynchronize(s));
@@ -1143,7 +1063,7 @@ int o3s_submap_patch_count(o3s_submap* m, const o3s_cropper* scan_matcher_croppe
   const size_t tb = scan_temp_bytes(N);
   void* tmp = m->arena.take<char>(tb);
   uint32_t* blk = reinterpret_cast<uint32_t*>(tmp);
-  hipLaunchKernelGGL(k_mask, dim3(nblk(N)), dim3(kB), 0, s, c, (const double*)m->pts[m->cur].d(), N, 1, flag, (uint32_t*)nullptr, blk);
+  hipLaunchKernelGGL(k_mask, dim3(nblk(N)), dim3(kB), 0, s, c, (const double*)m->pts[m->cur].as<double>(), N, 1, flag, (uint32_t*)nullptr, blk);
   return scan_flags(flag, off, N, tmp, tb, n_patch, s, blk);
 }
 
@@ -1178,13 +1098,13 @@ int o3s_submap_set_reference(o3s_submap* m, const o3s_cropper* scan_matcher_crop
     const size_t tb = scan_temp_bytes(N);
     void* tmp = m->arena.take<char>(tb);
     uint32_t* blk = reinterpret_cast<uint32_t*>(tmp);  // the mask's per-block counts: the scan is one launch (cloud_dev.h k_scan_flags_blk)
-    hipLaunchKernelGGL(k_mask, dim3(nblk(N)), dim3(kB), 0, s, c, (const double*)m->pts[m->cur].d(), N, 1, flag, (uint32_t*)nullptr, blk);
+    hipLaunchKernelGGL(k_mask, dim3(nblk(N)), dim3(kB), 0, s, c, (const double*)m->pts[m->cur].as<double>(), N, 1, flag, (uint32_t*)nullptr, blk);
     rc = scan_flags_dev(flag, off, N, tmp, tb, s, blk);
     if (rc != O3S_OK) return rc;
     CK(m->patch_xyzw.ensure((size_t)N * 16, 0, s));
     CK(m->patch_n32.ensure((size_t)N * 12, 0, s));
     d_count = off + N;
-    hipLaunchKernelGGL(k_compact_pm, dim3(nblk(N)), dim3(kB), 0, s, (const double*)m->pts[m->cur].d(), hn ? (const double*)m->nrm[m->cur].d() : nullptr, N,
+    hipLaunchKernelGGL(k_compact_pm, dim3(nblk(N)), dim3(kB), 0, s, (const double*)m->pts[m->cur].as<double>(), hn ? (const double*)m->nrm[m->cur].as<double>() : nullptr, N,
                        flag, off, reinterpret_cast<float4*>(m->patch_xyzw.p), reinterpret_cast<float*>(m->patch_n32.p), d_count);
     CK(hipGetLastError());
   }
@@ -1215,7 +1135,7 @@ int o3s_o3d_registration_icp_submaps(const o3s_submap* source, const o3s_submap*
   CK(hipStreamSynchronize(target->stream));
   hipStream_t s = target->stream;
   o3s_cloud::RegLease area(target->device, s);
-  rc = o3d_icp_run(area->reg, source->pts[source->cur].d(), source->n, target->pts[target->cur].d(), target->nrm[target->cur].d(), target->n,
+  rc = o3d_icp_run(area->reg, source->pts[source->cur].as<double>(), source->n, target->pts[target->cur].as<double>(), target->nrm[target->cur].as<double>(), target->n,
                    max_dist, init, criteria, result, s, /*on_device=*/true);
   if (rc == O3S_OK && info36) rc = o3d_info_after_icp(area->reg, max_dist, result->transformation, info36, s);
   return area.end(rc);
@@ -1228,7 +1148,7 @@ struct o3s_scan {
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t handover = nullptr;  // recorded on `stream`, waited for by the ICP handle's stream
-  DArr raw_p, raw_n, tmp_p, tmp_n, wide_p, wide_n, narrow_p, narrow_n, xyzw, n32;
+  DevMem raw_p, raw_n, tmp_p, tmp_n, wide_p, wide_n, narrow_p, narrow_n, xyzw, n32;
   int64_t n_wide = 0, n_narrow = 0, n_raw = 0;  // n_raw: the raw scan of the last preprocess, still in raw_p (/ raw_n)
   int raw_has_normals = 0;
   double normal_radius = 0.0;
@@ -1243,10 +1163,10 @@ struct o3s_scan {
 struct o3s_raw_scan {
   int device = 0;
   hipStream_t stream = nullptr;
-  DArr p, n;
+  DevMem p, n;
   int64_t N = 0;
   int has_normals = 0;
-  DArr dt, traj;      // per-point time offsets of this sweep (o3s_raw_scan_set_point_times); the table of the last trajectory de-skew
+  DevMem dt, traj;      // per-point time offsets of this sweep (o3s_raw_scan_set_point_times); the table of the last trajectory de-skew
   int has_times = 0;  // dropped by the next upload
 };
 
@@ -1303,7 +1223,7 @@ int o3s_raw_scan_undistort(o3s_raw_scan* r, const o3s_motion* m) {
   if (!r || !motion_valid(m)) return O3S_ERR_BAD_ARGUMENT;
   if (r->N == 0 || motion_is_zero(*m)) return O3S_OK;
   if (hipSetDevice(r->device) != hipSuccess) return O3S_ERR_HIP;
-  const int rc = undistort_dev(r->p.d(), r->N, *m, r->stream);
+  const int rc = undistort_dev(r->p.as<double>(), r->N, *m, r->stream);
   if (rc != O3S_OK) return rc;
   CK(hipStreamSynchronize(r->stream));  // the pre-process reads the staged copy from another stream
   return O3S_OK;
@@ -1333,7 +1253,7 @@ int o3s_raw_scan_undistort_trajectory(o3s_raw_scan* r, const o3s_stamped_pose* p
   if (hipSetDevice(r->device) != hipSuccess) return O3S_ERR_HIP;
   CK(r->traj.ensure(tab.size() * 8, 0, r->stream));
   CK(hipMemcpyAsync(r->traj.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, r->stream));
-  rc = undistort_trajectory_dev(r->p.d(), r->has_times ? r->dt.d() : nullptr, r->N, r->traj.d(), a, r->stream);
+  rc = undistort_trajectory_dev(r->p.as<double>(), r->has_times ? r->dt.as<double>() : nullptr, r->N, r->traj.as<double>(), a, r->stream);
   if (rc != O3S_OK) return rc;
   CK(hipStreamSynchronize(r->stream));  // the pre-process reads the staged copy from another stream; `tab` is free again
   return O3S_OK;
@@ -1410,7 +1330,7 @@ static int scan_preprocess_impl(o3s_scan* sc, const o3s_cropper* map_builder_cro
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   CK(hipMemcpyAsync(sc->raw_p.p, pts, (size_t)N * 24, kind, s));
   if (!estimate) CK(hipMemcpyAsync(sc->raw_n.p, normals, (size_t)N * 24, kind, s));
-  for (DArr* a : {&sc->tmp_p, &sc->tmp_n, &sc->wide_p, &sc->wide_n, &sc->narrow_p, &sc->narrow_n}) CK(a->ensure((size_t)N * 24, 0, s));
+  for (DevMem* a : {&sc->tmp_p, &sc->tmp_n, &sc->wide_p, &sc->wide_n, &sc->narrow_p, &sc->narrow_n}) CK(a->ensure((size_t)N * 24, 0, s));
   int rc = O3S_OK;
   {  // bounded wide volume: crop, down-sample and narrow crop as one pipeline with a single read-back (cloud_dev.h, "hinted")
     double lo[3], hi[3];
@@ -1422,19 +1342,19 @@ static int scan_preprocess_impl(o3s_scan* sc, const o3s_cropper* map_builder_cro
         CK(sc->xyzw.ensure((size_t)N * 16, 0, s));
         CK(sc->n32.ensure((size_t)N * 12, 0, s));
       }
-      rc = voxel_pipeline_hint_dev(sc->arena, 1, map_builder_cropper, vh, voxel_size, sc->raw_p.d(), estimate ? nullptr : sc->raw_n.d(), N,
-                                   sc->wide_p.d(), sc->wide_n.d(), nullptr, nullptr, estimate ? nullptr : scan_matcher_cropper, sc->narrow_p.d(),
-                                   sc->narrow_n.d(), cnt, &ok, s, estimate ? nullptr : reinterpret_cast<float4*>(sc->xyzw.p),
+      rc = voxel_pipeline_hint_dev(sc->arena, 1, map_builder_cropper, vh, voxel_size, sc->raw_p.as<double>(), estimate ? nullptr : sc->raw_n.as<double>(), N,
+                                   sc->wide_p.as<double>(), sc->wide_n.as<double>(), nullptr, nullptr, estimate ? nullptr : scan_matcher_cropper, sc->narrow_p.as<double>(),
+                                   sc->narrow_n.as<double>(), cnt, &ok, s, estimate ? nullptr : reinterpret_cast<float4*>(sc->xyzw.p),
                                    estimate ? nullptr : reinterpret_cast<float*>(sc->n32.p));
       if (rc != O3S_OK) return rc;
       if (ok) {
         int64_t n_wide = cnt[1], n_narrow = cnt[2];
         if (estimate) {
           if (n_wide > 0) {
-            rc = estimate_normals_dev(sc->nwork, sc->wide_p.d(), n_wide, sc->normal_radius, sc->normal_knn, sc->wide_n.d(), nullptr, s);
+            rc = estimate_normals_dev(sc->nwork, sc->wide_p.as<double>(), n_wide, sc->normal_radius, sc->normal_knn, sc->wide_n.as<double>(), nullptr, s);
             if (rc != O3S_OK) return rc;
           }
-          rc = crop_dev(sc->arena, *scan_matcher_cropper, sc->wide_p.d(), sc->wide_n.d(), n_wide, sc->narrow_p.d(), sc->narrow_n.d(), &n_narrow, s);
+          rc = crop_dev(sc->arena, *scan_matcher_cropper, sc->wide_p.as<double>(), sc->wide_n.as<double>(), n_wide, sc->narrow_p.as<double>(), sc->narrow_n.as<double>(), &n_narrow, s);
           if (rc != O3S_OK) return rc;
         }
         CK(hipStreamSynchronize(s));
@@ -1452,12 +1372,12 @@ static int scan_preprocess_impl(o3s_scan* sc, const o3s_cropper* map_builder_cro
   }
   // preprocess(): croppedCloud = mapBuilderCropper_->crop(in)
   int64_t n_crop = 0;
-  rc = crop_dev(sc->arena, *map_builder_cropper, sc->raw_p.d(), estimate ? nullptr : sc->raw_n.d(), N, sc->tmp_p.d(), sc->tmp_n.d(), &n_crop, s);
+  rc = crop_dev(sc->arena, *map_builder_cropper, sc->raw_p.as<double>(), estimate ? nullptr : sc->raw_n.as<double>(), N, sc->tmp_p.as<double>(), sc->tmp_n.as<double>(), &n_crop, s);
   if (rc != O3S_OK) return rc;
   // o3d_slam::voxelize(voxelSize, croppedCloud): Open3D VoxelDownSample, or nothing for voxelSize <= 0
   int64_t n_wide = 0;
   if (voxel_size > 0.0 && n_crop > 0) {
-    rc = voxel_pipeline_dev(sc->arena, 1, nullptr, voxel_size, sc->tmp_p.d(), estimate ? nullptr : sc->tmp_n.d(), n_crop, sc->wide_p.d(), sc->wide_n.d(),
+    rc = voxel_pipeline_dev(sc->arena, 1, nullptr, voxel_size, sc->tmp_p.as<double>(), estimate ? nullptr : sc->tmp_n.as<double>(), n_crop, sc->wide_p.as<double>(), sc->wide_n.as<double>(),
                             nullptr, &n_wide, s);
     if (rc != O3S_OK) return rc;
   } else {
@@ -1469,12 +1389,12 @@ static int scan_preprocess_impl(o3s_scan* sc, const o3s_cropper* map_builder_cro
   }
   // cloudRegistration->estimateNormalsOrCovariancesIfNeeded(croppedCloud): only for clouds that came without normals
   if (estimate && n_wide > 0) {
-    rc = estimate_normals_dev(sc->nwork, sc->wide_p.d(), n_wide, sc->normal_radius, sc->normal_knn, sc->wide_n.d(), nullptr, s);
+    rc = estimate_normals_dev(sc->nwork, sc->wide_p.as<double>(), n_wide, sc->normal_radius, sc->normal_knn, sc->wide_n.as<double>(), nullptr, s);
     if (rc != O3S_OK) return rc;
   }
   // narrowCropped = scanMatcherCropper_->crop(*wideCropped)
   int64_t n_narrow = 0;
-  rc = crop_dev(sc->arena, *scan_matcher_cropper, sc->wide_p.d(), sc->wide_n.d(), n_wide, sc->narrow_p.d(), sc->narrow_n.d(), &n_narrow, s);
+  rc = crop_dev(sc->arena, *scan_matcher_cropper, sc->wide_p.as<double>(), sc->wide_n.as<double>(), n_wide, sc->narrow_p.as<double>(), sc->narrow_n.as<double>(), &n_narrow, s);
   if (rc != O3S_OK) return rc;
   CK(hipStreamSynchronize(s));
   sc->n_wide = n_wide;
@@ -1498,7 +1418,7 @@ int o3s_scan_preprocess(o3s_scan* sc, const o3s_cropper* map_builder_cropper, do
 int o3s_scan_preprocess_staged(o3s_scan* sc, const o3s_cropper* map_builder_cropper, double voxel_size, const o3s_cropper* scan_matcher_cropper,
                                const o3s_raw_scan* raw, int64_t* n_merge, int64_t* n_match) {
   if (!raw || !sc || raw->device != sc->device) return O3S_ERR_BAD_ARGUMENT;
-  return scan_preprocess_impl(sc, map_builder_cropper, voxel_size, scan_matcher_cropper, raw->p.d(), raw->has_normals ? raw->n.d() : nullptr, raw->N,
+  return scan_preprocess_impl(sc, map_builder_cropper, voxel_size, scan_matcher_cropper, raw->p.as<double>(), raw->has_normals ? raw->n.as<double>() : nullptr, raw->N,
                               n_merge, n_match, true);
 }
 
@@ -1507,8 +1427,8 @@ int64_t o3s_scan_get(const o3s_scan* sc, int which, double* pts, double* normals
   const int64_t n = which == 0 ? sc->n_wide : sc->n_narrow;
   if (!pts || n == 0) return n;
   if (hipSetDevice(sc->device) != hipSuccess) return -1;
-  const DArr& p = which == 0 ? sc->wide_p : sc->narrow_p;
-  const DArr& q = which == 0 ? sc->wide_n : sc->narrow_n;
+  const DevMem& p = which == 0 ? sc->wide_p : sc->narrow_p;
+  const DevMem& q = which == 0 ? sc->wide_n : sc->narrow_n;
   if (hipStreamSynchronize(sc->stream) != hipSuccess) return -1;
   if (hipMemcpy(pts, p.p, (size_t)n * 24, hipMemcpyDeviceToHost) != hipSuccess) return -1;
   if (normals && hipMemcpy(normals, q.p, (size_t)n * 24, hipMemcpyDeviceToHost) != hipSuccess) return -1;
@@ -1528,10 +1448,10 @@ int o3s_scan_registration_icp(const o3s_scan* source, int source_which, const o3
   const int64_t Nt = target_which == 0 ? target->n_wide : target->n_narrow;
   if (Ns == 0 || Nt == 0) return O3S_ERR_EMPTY_REFERENCE;
   if (hipSetDevice(target->device) != hipSuccess) return O3S_ERR_HIP;
-  const double* sp = (source_which == 0 ? source->wide_p : source->narrow_p).d();
-  const double* sn = (source_which == 0 ? source->wide_n : source->narrow_n).d();
-  const double* tp = (target_which == 0 ? target->wide_p : target->narrow_p).d();
-  const double* tn = (target_which == 0 ? target->wide_n : target->narrow_n).d();
+  const double* sp = (source_which == 0 ? source->wide_p : source->narrow_p).as<double>();
+  const double* sn = (source_which == 0 ? source->wide_n : source->narrow_n).as<double>();
+  const double* tp = (target_which == 0 ? target->wide_p : target->narrow_p).as<double>();
+  const double* tn = (target_which == 0 ? target->wide_n : target->narrow_n).as<double>();
   hipStream_t s = target->stream;
   if (source->stream != s) {
     CK(hipEventRecord(source->handover, source->stream));
@@ -1554,7 +1474,7 @@ int o3s_scan_set_reading(o3s_scan* sc, o3s_icp* icp) {
   if (!sc->pm_ready) {
     CK(sc->xyzw.ensure((size_t)n * 16, 0, s));
     CK(sc->n32.ensure((size_t)n * 12, 0, s));
-    hipLaunchKernelGGL(k_o3d_to_pm, dim3(nblk(n)), dim3(kB), 0, s, sc->narrow_p.d(), sc->narrow_n.d(), n, reinterpret_cast<float4*>(sc->xyzw.p),
+    hipLaunchKernelGGL(k_o3d_to_pm, dim3(nblk(n)), dim3(kB), 0, s, sc->narrow_p.as<double>(), sc->narrow_n.as<double>(), n, reinterpret_cast<float4*>(sc->xyzw.p),
                        reinterpret_cast<float*>(sc->n32.p));
     CK(hipGetLastError());
   }
@@ -1578,7 +1498,7 @@ int o3s_submap_insert_processed(o3s_submap* m, const o3s_scan* sc, const double 
   // the insert may come back with its completion pending (submap_settle): every later call on the submap completes it first.  The
   // scan object may be refilled as soon as this returns, so its stream is ordered behind the kernels that read it here.
   if (!m->scan_read) CK(hipEventCreateWithFlags(&m->scan_read, hipEventDisableTiming));
-  const int ri = insert_dev(m, sc->wide_p.d(), sc->wide_n.d(), sc->n_wide, T_map_sensor, nullptr, /*lazy=*/true, m->scan_read);
+  const int ri = insert_dev(m, sc->wide_p.as<double>(), sc->wide_n.as<double>(), sc->n_wide, T_map_sensor, nullptr, /*lazy=*/true, m->scan_read);
   if (m->pend.active) CK(hipStreamWaitEvent(sc->stream, m->scan_read, 0));
   return ri;
 }
@@ -1589,7 +1509,7 @@ int o3s_estimate_normals(int device, const double* pts, int64_t N, double radius
   int rc = pick_device(device);
   if (rc != O3S_OK) return rc;
   hipStream_t s = nullptr;
-  Buf d_p, d_n, d_i;
+  DevMem d_p, d_n, d_i;
   NormalsWork w;
   CK(d_p.alloc((size_t)N * 24));
   CK(d_n.alloc((size_t)N * 24));

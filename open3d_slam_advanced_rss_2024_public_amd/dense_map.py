@@ -3,7 +3,6 @@
 open3d_slam/src/Submap.cpp:97-113,146-157); the voxel table stays in HBM."""
 from __future__ import annotations
 
-import os
 import ctypes as C
 
 import numpy as np
@@ -51,30 +50,16 @@ def _pose(T) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(T, np.float64).T).reshape(16)
 
 
-class DenseMap:
+class DenseMap(_lib.Handle):
     """VoxelizedPointCloud resident on one MI355X."""
 
+    _destroy = "o3s_dense_map_destroy"
+
     def __init__(self, voxel_size: float, device: int = 0):
-        self._lib = _L()   # the library this handle belongs to (product or a hooks build): every later call goes through it
-        self._pid = os.getpid()   # _lib.forked_copy: a forked child must not destroy the handle
-        self._h = C.c_void_p()
         self.voxel_size = float(voxel_size)
-        rc = self._lib.o3s_dense_map_create(device, self.voxel_size, C.byref(self._h))
+        rc = self._create(_L(), "o3s_dense_map_create", device, self.voxel_size)
         if rc != _lib.OK:
-            self._h = C.c_void_p()
             raise RuntimeError(f"o3s_dense_map_create failed with o3s_status {rc} (no CPU fallback)")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            if not _lib.forked_copy(self):   # a forked child drops its copy of the wrapper, the handle is the parent's
-                self._lib.o3s_dense_map_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def _check(rc, what):

@@ -8,7 +8,6 @@ happens in libo3dslam_icp_hip.so on the GPU; this file only marshals numpy array
 """
 from __future__ import annotations
 
-import os
 import ctypes as C
 import math
 from dataclasses import dataclass, field
@@ -227,35 +226,21 @@ def _from_colmajor(t) -> np.ndarray:
     return np.asarray(t, dtype=np.float32).reshape(4, 4).T.copy()
 
 
-class ICP:
+class ICP(_lib.Handle):
     """PM::ICP for the scan-to-map chain, running on one MI355X."""
+
+    _destroy = "o3s_icp_destroy"
 
     def __init__(self, config: IcpConfig | None = None, device: int = 0):
         self.config = config or IcpConfig()
-        self._L = _lib.lib()
-        self._pid = os.getpid()   # _lib.forked_copy: a forked child must not destroy the handle
-        self._h = C.c_void_p()
+        self._L = _lib.lib()   # (the same library as _lib: the name this class's calls go through)
         c = self.config.to_c()
-        rc = self._L.o3s_icp_create(C.byref(c), device, C.byref(self._h))
+        rc = self._create(self._L, "o3s_icp_create", C.byref(c), device)
         if rc != _lib.OK:
             msg = self._L.o3s_last_error(None).decode()
-            self._h = C.c_void_p()
             raise _RAISE.get(rc, RuntimeError)(f"o3s_icp_create failed ({rc}): {msg}")
         self.stats = IcpStats()
         self.device = device
-
-    # -- lifetime ----------------------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            if not _lib.forked_copy(self):   # a forked child drops its copy of the wrapper, the handle is the parent's
-                self._L.o3s_icp_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _check(self, rc):
         if rc == _lib.OK:

@@ -13,7 +13,6 @@ C++ and Python share one implementation."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 import time
 from dataclasses import dataclass, field
 
@@ -180,29 +179,15 @@ def undistort_cloud_trajectory(points, table, K, params: TrajectoryDeskewC, poin
     return out
 
 
-class RawScan:
+class RawScan(_lib.Handle):
     """o3s_raw_scan: a sweep staged in HBM ahead of the pre-processing (and the thing a de-skew acts on)."""
 
+    _destroy = "o3s_raw_scan_destroy"
+
     def __init__(self, device: int = 0):
-        self._lib = _L()
-        self._pid = os.getpid()   # _lib.forked_copy: a forked child must not destroy the handle
-        self._h = C.c_void_p()
-        rc = self._lib.o3s_raw_scan_create(device, C.byref(self._h))
+        rc = self._create(_L(), "o3s_raw_scan_create", device)
         if rc != _lib.OK:
-            self._h = C.c_void_p()
             raise RuntimeError(f"o3s_raw_scan_create failed with o3s_status {rc} (no CPU fallback)")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            if not _lib.forked_copy(self):
-                self._lib.o3s_raw_scan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __len__(self) -> int:
         return int(self._lib.o3s_raw_scan_size(self._h))

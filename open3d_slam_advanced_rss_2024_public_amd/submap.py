@@ -2,7 +2,6 @@
 Method names follow the reference (open3d_slam/src/Submap.cpp, ScanToMapRegistration.cpp); the map cloud stays in HBM."""
 from __future__ import annotations
 
-import os
 import ctypes as C
 
 import numpy as np
@@ -92,31 +91,17 @@ def featureParams(feature_voxel_size=0.5, normal_radius=2.0, normal_knn=20, feat
     return FeatureParamsC(float(feature_voxel_size), float(normal_radius), int(normal_knn), float(feature_radius), int(feature_knn))
 
 
-class Submap:
+class Submap(_lib.Handle):
     """The active submap's sparse map cloud, resident on one MI355X."""
 
+    _destroy = "o3s_submap_destroy"
+
     def __init__(self, map_voxel_size: float, map_builder_cropper: CropperC, device: int = 0):
-        self._lib = _L()   # the library this handle belongs to (product or a hooks build): every later call goes through it
-        self._pid = os.getpid()   # _lib.forked_copy: a forked child must not destroy the handle
-        self._h = C.c_void_p()
-        rc = self._lib.o3s_submap_create(device, float(map_voxel_size), C.byref(map_builder_cropper), C.byref(self._h))
+        rc = self._create(_L(), "o3s_submap_create", device, float(map_voxel_size), C.byref(map_builder_cropper))
         if rc != _lib.OK:
-            self._h = C.c_void_p()
             raise RuntimeError(f"o3s_submap_create failed with o3s_status {rc} (no CPU fallback)")
         self.has_normals = None
         self.device = int(device)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            if not _lib.forked_copy(self):   # a forked child drops its copy of the wrapper, the handle is the parent's
-                self._lib.o3s_submap_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _check(self, rc, what):
         if rc != _lib.OK:
@@ -171,14 +156,10 @@ class Submap:
         L = self._lib
         L.o3s_submap_clone.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         other = object.__new__(Submap)
-        other._lib = L
-        other._pid = os.getpid()
-        other._h = C.c_void_p()
         other.has_normals = self.has_normals
         dev = int(getattr(self, "device", 0) if device is None else device)
-        rc = L.o3s_submap_clone(self._h, dev, C.byref(other._h))
+        rc = other._create(L, "o3s_submap_clone", self._h, dev)
         if rc != _lib.OK:
-            other._h = C.c_void_p()
             raise RuntimeError(f"o3s_submap_clone failed with o3s_status {rc}")
         other.device = dev
         return other
@@ -390,35 +371,20 @@ def transform_submaps(maps, Ts):
         raise RuntimeError(f"o3s_submaps_transform failed with o3s_status {rc}")
 
 
-class AssembledMap:
+class AssembledMap(_lib.Handle):
     """The map clouds of several resident submaps assembled into one cloud on the device (include/assembled_map/o3s_assembled_map.h):
     Mapper::getAssembledMapPointCloud (Mapper.cpp:506-538) and, with a voxel size, Open3D's VoxelDownSample of it — what
     SlamWrapper::saveMap writes and SlamWrapperRos::publishMaps publishes.  The result and the work area stay resident and only
     grow; nothing but the result ever crosses the bus, and only when getPointCloud() asks for it."""
 
     NORMALS, COLORS = 1, 2   # bits of the C call's `attrs`
+    _destroy = "o3s_assembled_map_destroy"
 
     def __init__(self, device: int = 0):
-        self._lib = _L()   # the library this handle belongs to (product or a hooks build): every later call goes through it
-        self._pid = os.getpid()   # _lib.forked_copy: a forked child must not destroy the handle
-        self._h = C.c_void_p()
-        rc = self._lib.o3s_assembled_map_create(device, C.byref(self._h))
+        rc = self._create(_L(), "o3s_assembled_map_create", device)
         if rc != _lib.OK:
-            self._h = C.c_void_p()
             raise RuntimeError(f"o3s_assembled_map_create failed with o3s_status {rc} (no CPU fallback)")
         self.device = int(device)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            if not _lib.forked_copy(self):   # a forked child drops its copy of the wrapper, the handle is the parent's
-                self._lib.o3s_assembled_map_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def build(self, maps, voxel_size: float = 0.0, normals: bool = True, colors: bool = True) -> int:
         """Assembles `maps` (Submap objects, or None for a NULL pointer) in the order given; voxel_size <= 0: the plain concatenation,
@@ -475,31 +441,17 @@ class AssembledMap:
         return int(self._lib.o3s_assembled_map_device_bytes(self._h))
 
 
-class ProcessedScan:
+class ProcessedScan(_lib.Handle):
     """ScanToMapIcp::processForScanMatchingAndMerging (ScanToMapRegistration.cpp:36-69) with both result clouds resident
     in HBM: ``merge`` (wide crop, voxelised) feeds Submap.insertProcessed, ``match`` (narrow crop) feeds the ICP."""
 
+    _destroy = "o3s_scan_destroy"
+
     def __init__(self, device: int = 0):
-        self._lib = _L()   # the library this handle belongs to (product or a hooks build): every later call goes through it
-        self._pid = os.getpid()   # _lib.forked_copy: a forked child must not destroy the handle
-        self._h = C.c_void_p()
-        rc = self._lib.o3s_scan_create(device, C.byref(self._h))
+        rc = self._create(_L(), "o3s_scan_create", device)
         if rc != _lib.OK:
-            self._h = C.c_void_p()
             raise RuntimeError(f"o3s_scan_create failed with o3s_status {rc} (no CPU fallback)")
         self.n_merge = self.n_match = 0
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            if not _lib.forked_copy(self):   # a forked child drops its copy of the wrapper, the handle is the parent's
-                self._lib.o3s_scan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_normal_estimation(self, max_radius: float, knn: int):
         """icp.max_distance_knn / icp.knn of the parameter files: used only for scans that arrive without normals."""
