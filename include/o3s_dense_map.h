@@ -18,7 +18,8 @@
  * bits), point count, fp64 sums of positions and normals.  Voxel keys are getVoxelIdx(p, 1 / voxel) in fp64
  * (VoxelHashMap.hpp:48-51,127); the sums of a voxel are accumulated in the order the points were inserted, so means are
  * bit-identical to the reference's sequential loop.  Voxel indices outside [-2^20, 2^20) per axis are refused with
- * O3S_ERR_BAD_ARGUMENT (at 5 cm voxels: beyond +-52 km).  Colours are not carried (nothing on this path has them).
+ * O3S_ERR_BAD_ARGUMENT (at 5 cm voxels: beyond +-52 km).  The entries below take clouds without colours; the colour
+ * crop and the per-voxel colour sums are in dense_map/o3s_dense_map_color.h (same handle).
  *
  * Conventions as in o3s_submap.h: points / normals are 3 x N doubles (point-major), poses 4x4 column-major doubles.
  * One handle = one device + one stream; calls on a handle are serialised by the caller (the reference holds

@@ -177,6 +177,17 @@ def crop_attr(cropper: CropperC, points, normals=None, colors=None, covariances=
     return _attr_call("o3s_crop_attr", [C.byref(cropper)], points, normals, colors, covariances, False, device)
 
 
+def _rgb(v):
+    return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (3,)))
+
+
+def color_range_crop(points, normals=None, colors=None, covariances=None, rgb_min=None, rgb_max=None, device: int = 0):
+    """ColorRangeCropper::crop (croppers.cpp:178-244) -> (points, normals, colors, covariances): the points whose colour lies in
+    [rgb_min, rgb_max] (inclusive; None: the reference's 0 / 1), in order; a cloud without colours comes back whole."""
+    lo, hi = _rgb(rgb_min), _rgb(rgb_max)
+    return _attr_call("o3s_color_range_crop", [_d(lo), _d(hi)], points, normals, colors, covariances, False, device)
+
+
 def voxelizeWithinCroppingVolume_attr(voxel_size: float, cropper: CropperC, points, normals=None, colors=None, covariances=None, device: int = 0):
     """voxelizeWithinCroppingVolume with colours (last colour of the voxel) and covariances (mean) -> (p, n, col, cov, voxel_idx)."""
     return _attr_call("o3s_voxelize_within_crop_attr", [C.byref(cropper), C.c_double(float(voxel_size))], points, normals, colors, covariances, True, device)

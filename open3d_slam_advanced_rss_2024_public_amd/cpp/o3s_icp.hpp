@@ -18,6 +18,7 @@
 
 #include "o3s_icp.h"
 #include "o3s_dense_map.h"
+#include "dense_map/o3s_dense_map_color.h"
 #include "o3s_submap.h"
 #include "localizability/o3s_localizability.h"
 
@@ -228,6 +229,32 @@ class DenseMapHip {
           "o3s_dense_map_insert_scan");
     return removed;
   }
+  // The coloured forms (include/dense_map/o3s_dense_map_color.h).  colors3xN == nullptr: the calls above.  rgbMin3 / rgbMax3 are the
+  // bounds of the reference's colorCropper_ (nullptr: its defaults 0 / 1)
+  void insert(const double* points3xN, const double* normals3xN, const double* colors3xN, std::int64_t N) {
+    check(o3s_dense_map_insert_colored(m_, points3xN, normals3xN, colors3xN, N), "o3s_dense_map_insert_colored");
+  }
+  std::int64_t insertScanDenseMap(const o3s_cropper& denseMapCropper, const double* rawPoints3xN, const double* rawNormals3xN,
+                                  const double* rawColors3xN, std::int64_t N, const double* mapToRangeSensor4x4,
+                                  const o3s_dense_carving_params* carving = nullptr, const double* rgbMin3 = nullptr,
+                                  const double* rgbMax3 = nullptr) {
+    std::int64_t removed = 0;
+    check(o3s_dense_map_insert_scan_colored(m_, &denseMapCropper, rgbMin3, rgbMax3, rawPoints3xN, rawNormals3xN, rawColors3xN, N,
+                                            mapToRangeSensor4x4, carving, &removed),
+          "o3s_dense_map_insert_scan_colored");
+    return removed;
+  }
+  // points and normals from the scan o3s_scan_preprocess left in HBM; one colour per raw point of it, from the host
+  std::int64_t insertResidentScanDenseMap(const o3s_cropper& denseMapCropper, const o3s_scan* scan, const double* rawColors3xN,
+                                          std::int64_t nColors, const double* mapToRangeSensor4x4,
+                                          const o3s_dense_carving_params* carving = nullptr, const double* rgbMin3 = nullptr,
+                                          const double* rgbMax3 = nullptr) {
+    std::int64_t removed = 0;
+    check(o3s_dense_map_insert_resident_scan_colored(m_, &denseMapCropper, rgbMin3, rgbMax3, scan, rawColors3xN, nColors, mapToRangeSensor4x4,
+                                                     carving, &removed),
+          "o3s_dense_map_insert_resident_scan_colored");
+    return removed;
+  }
   std::int64_t carve(const o3s_dense_carving_params& p, const double* scanPoints3xN, std::int64_t N, const double* sensorPosition3) {
     std::int64_t removed = 0;
     check(o3s_dense_map_carve(m_, &p, scanPoints3xN, N, sensorPosition3, &removed), "o3s_dense_map_carve");
@@ -237,10 +264,17 @@ class DenseMapHip {
   std::int64_t size() const { return o3s_dense_map_size(m_); }
   bool empty() const { return size() == 0; }
   bool hasNormals() const { return o3s_dense_map_has_normals(m_) != 0; }
+  bool hasColors() const { return o3s_dense_map_has_colors(m_) != 0; }
   // buffers sized by size(); returns the number of voxels written
   std::int64_t toPointCloud(double* points3xV, double* normals3xV) const {
     std::int64_t n = 0;
     check(o3s_dense_map_to_point_cloud(m_, points3xV, normals3xV, nullptr, nullptr, &n), "o3s_dense_map_to_point_cloud");
+    return n;
+  }
+  // colors3xV: only while hasColors() (sum / count of every voxel; the sum starts at (1, 1, 1), see the header)
+  std::int64_t toPointCloud(double* points3xV, double* normals3xV, double* colors3xV) const {
+    std::int64_t n = 0;
+    check(o3s_dense_map_to_point_cloud_colored(m_, points3xV, normals3xV, colors3xV, nullptr, nullptr, &n), "o3s_dense_map_to_point_cloud_colored");
     return n;
   }
   o3s_dense_map* handle() { return m_; }

@@ -3,7 +3,8 @@
 //
 // The reference's VoxelizedPointCloud is an unordered_map<Vector3i, AggregatedVoxel> filled point by point
 // (O3S/src/Voxel.cpp:66-88).  Here it is an open-addressing table in HBM (linear probing, load <= 1/2, tombstones):
-//   keys[cap] u64 | cnt[cap] i32 | sum[cap][6] f64 (position xyz, normal xyz)
+//   keys[cap] u64 | cnt[cap] i32 | sum[cap][6] f64 (position xyz, normal xyz) | csum[cap][3] f64 (colour; only once a
+//   coloured cloud has been aggregated, include/dense_map/o3s_dense_map_color.h)
 // An insert sorts the new points by packed voxel key (stable, so a voxel's points stay in input order), and ONE lane per
 // distinct key claims / finds the slot (64-bit CAS) and adds its points one after the other — the same additions in the
 // same order as the reference's loop, hence bit-identical sums, and no two lanes ever touch the same slot.
@@ -11,6 +12,7 @@
 // hits flagged per slot, and a second kernel turns the flagged slots into tombstones.
 #pragma once
 #include "../../include/o3s_dense_map.h"
+#include "../../include/dense_map/o3s_dense_map_color.h"
 
 #include "cloud_dev.h"
 
@@ -82,10 +84,15 @@ __global__ void __launch_bounds__(kB) k_dm_keys(const double* __restrict__ pts, 
 
 // VoxelizedPointCloud::insert (Voxel.cpp:66-88) on key-sorted points: one lane per distinct key.
 // counters: [0] slots newly occupied, [1] of those, how many re-used a tombstone
+// kCol: the map holds colour sums (csum).  A slot claimed here starts its colour sum at (1, 1, 1) — AggregatedVoxel's initialiser
+// (Voxel.hpp:50), restated as it is — whether or not this cloud has colours (col nullable), so a re-used tombstone never shows the
+// sum of the voxel that was carved away; aggregateColor (Voxel.cpp:34-36) then adds in input order like the other two sums.
+// kCol == false is the kernel as it was before colours: no further load, store or register.
+template <bool kCol>
 __global__ void __launch_bounds__(kB) k_dm_insert(const uint64_t* __restrict__ skeys, const uint32_t* __restrict__ svals, int64_t N,
-                                                  const double* __restrict__ pts, const double* __restrict__ nrm, uint64_t* __restrict__ keys,
-                                                  int32_t* __restrict__ cnt, double* __restrict__ sum, uint64_t mask,
-                                                  uint32_t* __restrict__ counters) {
+                                                  const double* __restrict__ pts, const double* __restrict__ nrm, const double* __restrict__ col,
+                                                  uint64_t* __restrict__ keys, int32_t* __restrict__ cnt, double* __restrict__ sum,
+                                                  double* __restrict__ csum, uint64_t mask, uint32_t* __restrict__ counters) {
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
   bool is_new = false, from_tomb = false;
   if (i < N) {
@@ -119,11 +126,18 @@ __global__ void __launch_bounds__(kB) k_dm_insert(const uint64_t* __restrict__ s
         h = (h + 1) & mask;
       }
       double s[6] = {0, 0, 0, 0, 0, 0};
+      [[maybe_unused]] double cs[3] = {1.0, 1.0, 1.0};
       int32_t c = 0;
       if (!is_new) {
         c = cnt[slot];
 #pragma unroll
         for (int a = 0; a < 6; ++a) s[a] = sum[6 * slot + a];
+        if constexpr (kCol) {
+          if (col) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) cs[a] = csum[3 * slot + a];
+          }
+        }
       }
       for (int64_t j = i; j < N && skeys[j] == key; ++j) {  // aggregatePoint, aggregateNormal (Voxel.cpp:27-33), input order
         const int64_t p = svals[j];
@@ -136,20 +150,33 @@ __global__ void __launch_bounds__(kB) k_dm_insert(const uint64_t* __restrict__ s
           s[4] += nrm[3 * p + 1];
           s[5] += nrm[3 * p + 2];
         }
+        if constexpr (kCol) {
+          if (col) {
+            cs[0] += col[3 * p];
+            cs[1] += col[3 * p + 1];
+            cs[2] += col[3 * p + 2];
+          }
+        }
       }
       cnt[slot] = c;
 #pragma unroll
       for (int a = 0; a < 6; ++a) sum[6 * slot + a] = s[a];
+      if constexpr (kCol) {
+        if (is_new || col) {
+#pragma unroll
+          for (int a = 0; a < 3; ++a) csum[3 * slot + a] = cs[a];
+        }
+      }
     }
   }
   wave_count(is_new, counters);
   wave_count(from_tomb, counters + 1);
 }
 
-// moves every live slot into a fresh (all-empty) table
+// moves every live slot into a fresh (all-empty) table; ocsum / csum: the colour sums, both null while the map has none
 __global__ void __launch_bounds__(kB) k_dm_rehash(const uint64_t* __restrict__ okeys, const int32_t* __restrict__ ocnt, const double* __restrict__ osum,
-                                                  int64_t ocap, uint64_t* __restrict__ keys, int32_t* __restrict__ cnt, double* __restrict__ sum,
-                                                  uint64_t mask) {
+                                                  const double* __restrict__ ocsum, int64_t ocap, uint64_t* __restrict__ keys,
+                                                  int32_t* __restrict__ cnt, double* __restrict__ sum, double* __restrict__ csum, uint64_t mask) {
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
   if (i >= ocap) return;
   const uint64_t key = okeys[i];
@@ -164,6 +191,16 @@ __global__ void __launch_bounds__(kB) k_dm_rehash(const uint64_t* __restrict__ o
   cnt[h] = ocnt[i];
 #pragma unroll
   for (int a = 0; a < 6; ++a) sum[6 * h + a] = osum[6 * i + a];
+  if (ocsum) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) csum[3 * h + a] = ocsum[3 * i + a];
+  }
+}
+
+// the colour sums of a map that meets its first colour: every voxel, alive or yet to come, has held (1, 1, 1) all along
+__global__ void __launch_bounds__(kB) k_dm_fill_ones(double* __restrict__ v, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
+  if (i < n) v[i] = 1.0;
 }
 
 // toPointCloud (Voxel.cpp:90-114): voxels with numAggregatedPoints_ > 0
@@ -182,8 +219,9 @@ __global__ void __launch_bounds__(kB) k_dm_collect(const uint64_t* __restrict__ 
   oslots[off[i]] = (uint32_t)i;
 }
 __global__ void __launch_bounds__(kB) k_dm_emit(const uint64_t* __restrict__ skeys, const uint32_t* __restrict__ sslots, int64_t V,
-                                                const int32_t* __restrict__ cnt, const double* __restrict__ sum, double* __restrict__ out_p,
-                                                double* __restrict__ out_n, int32_t* __restrict__ out_k, int32_t* __restrict__ out_c) {
+                                                const int32_t* __restrict__ cnt, const double* __restrict__ sum, const double* __restrict__ csum,
+                                                double* __restrict__ out_p, double* __restrict__ out_n, double* __restrict__ out_col /*with csum*/,
+                                                int32_t* __restrict__ out_k, int32_t* __restrict__ out_c) {
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
   if (i >= V) return;
   const uint64_t key = skeys[i];
@@ -195,13 +233,18 @@ __global__ void __launch_bounds__(kB) k_dm_emit(const uint64_t* __restrict__ ske
     out_p[3 * i + a] = sum[6 * s + a] / d;
     out_n[3 * i + a] = sum[6 * s + 3 + a] / d;
   }
+  if (csum) {  // getAggregatedColor (Voxel.cpp:24-26): the sum that began at (1, 1, 1), over ALL points of the voxel
+#pragma unroll
+    for (int a = 0; a < 3; ++a) out_col[3 * i + a] = csum[3 * s + a] / d;
+  }
   out_k[3 * i] = (int32_t)(key & 0x1fffffull) - kDmBias;
   out_k[3 * i + 1] = (int32_t)((key >> 21) & 0x1fffffull) - kDmBias;
   out_k[3 * i + 2] = (int32_t)((key >> 42) & 0x1fffffull) - kDmBias;
   out_c[i] = c;
 }
 
-// VoxelizedPointCloud::transform (Voxel.cpp:49-64): Isometry3d * Vector3d = translation + linear * v on both sums
+// VoxelizedPointCloud::transform (Voxel.cpp:49-64): Isometry3d * Vector3d = translation + linear * v on both sums; the voxel is
+// copied, so its colour sum stays
 __global__ void __launch_bounds__(kB) k_dm_transform(const uint64_t* __restrict__ keys, const int32_t* __restrict__ cnt, double* __restrict__ sum,
                                                      int64_t cap, const double* __restrict__ Tm) {
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
@@ -230,6 +273,40 @@ __global__ void __launch_bounds__(kB) k_dm_first(const uint32_t* __restrict__ sv
                                                  int64_t N, uint32_t* __restrict__ first) {
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
   if (i < N && head[i]) first[off[i]] = svals[i];
+}
+
+// ColorRangeCropper::isValidColor (croppers.cpp:178-180): min <= c && c <= max in every component, so a NaN fails
+struct DmRgb {
+  double lo[3], hi[3];
+};
+// flag[i] = 1 for a point with a valid colour that, with use_volume, also lies inside the cropping volume: denseMapCropper_->crop
+// followed by colorCropper_.crop (Submap.cpp:100-101) are two order-preserving filters, hence one predicate
+__global__ void __launch_bounds__(kB) k_dm_color_mask(o3s_cropper c, int use_volume, const double* __restrict__ pts, const double* __restrict__ col,
+                                                      int64_t N, DmRgb b, uint32_t* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
+  if (i >= N) return;
+  bool ok = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double v = col[3 * i + a];
+    ok = ok && b.lo[a] <= v && v <= b.hi[a];
+  }
+  if (ok && use_volume) ok = within(c, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
+  flag[i] = ok ? 1u : 0u;
+}
+// the scatter of that crop: points, normals (nullable) and colours in one pass
+__global__ void __launch_bounds__(kB) k_dm_compact_col(const double* __restrict__ pts, const double* __restrict__ nrm, const double* __restrict__ col,
+                                                       int64_t N, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ off,
+                                                       double* __restrict__ out_p, double* __restrict__ out_n, double* __restrict__ out_c) {
+  const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
+  if (i >= N || !flag[i]) return;
+  const int64_t o = (int64_t)off[i];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    out_p[3 * o + a] = pts[3 * i + a];
+    if (nrm) out_n[3 * o + a] = nrm[3 * i + a];
+    out_c[3 * o + a] = col[3 * i + a];
+  }
 }
 
 __global__ void __launch_bounds__(kB) k_dm_build_filter(const uint64_t* __restrict__ keys, int64_t cap, unsigned long long* __restrict__ words,
@@ -405,14 +482,16 @@ struct o3s_dense_map {
   double voxel = 0.0, inv = 0.0;
   hipStream_t stream = nullptr;
   DevMem keys, cnt, sum;  // the table
+  DevMem csum;            // its colour sums: empty until a coloured cloud is aggregated (dm_ensure_colors)
   int64_t cap = 0, live = 0, tomb = 0;
-  int has_normals = 0;
+  int has_normals = 0, has_colors = 0;
   int64_t n_scans_inserted = 0;  // nScansInsertedDenseMap_
-  mutable DevMem in_p, in_n, crop_p, crop_n, tf_p, tf_n, d_T, d_ctr, out;
+  mutable DevMem in_p, in_n, in_c, crop_p, crop_n, crop_c, tf_p, tf_n, d_T, d_ctr, out;
   mutable Arena arena;
   uint64_t* K() const { return keys.as<uint64_t>(); }
   int32_t* C() const { return cnt.as<int32_t>(); }
   double* S() const { return sum.as<double>(); }
+  double* CS() const { return csum.as<double>(); }  // null while the map holds no colour sums
 };
 
 namespace {
@@ -423,20 +502,23 @@ int dm_reserve(o3s_dense_map* m, int64_t add) {
   if (m->cap > 0 && 2 * (m->live + m->tomb + add) <= m->cap) return O3S_OK;
   int64_t ncap = 1 << 16;
   while (ncap < 4 * (m->live + add)) ncap <<= 1;
-  DevMem nk, nc, ns;  // released on every early return; handed to the map at the end
+  DevMem nk, nc, ns, ncs;  // released on every early return; handed to the map at the end
   CK(nk.alloc((size_t)ncap * 8));
   CK(nc.alloc((size_t)ncap * 4));
   CK(ns.alloc((size_t)ncap * 48));
+  const bool colors = m->csum.p != nullptr;  // slots nobody holds need no value: k_dm_insert<true> writes a colour sum as it claims
+  if (colors) CK(ncs.alloc((size_t)ncap * 24));
   CK(hipMemsetAsync(nk.p, 0xff, (size_t)ncap * 8, s));
   if (m->cap > 0 && m->live > 0) {
-    hipLaunchKernelGGL(k_dm_rehash, dim3(nblk(m->cap)), dim3(kB), 0, s, m->K(), m->C(), m->S(), m->cap, nk.as<uint64_t>(), nc.as<int32_t>(),
-                       ns.as<double>(), (uint64_t)(ncap - 1));
+    hipLaunchKernelGGL(k_dm_rehash, dim3(nblk(m->cap)), dim3(kB), 0, s, m->K(), m->C(), m->S(), m->CS(), m->cap, nk.as<uint64_t>(),
+                       nc.as<int32_t>(), ns.as<double>(), ncs.as<double>(), (uint64_t)(ncap - 1));
     CK(hipGetLastError());
   }
   CK(hipStreamSynchronize(s));
   m->keys = std::move(nk);  // the old table is freed as the new one moves in
   m->cnt = std::move(nc);
   m->sum = std::move(ns);
+  if (colors) m->csum = std::move(ncs);
   m->cap = ncap;
   m->tomb = 0;
   return O3S_OK;
@@ -472,8 +554,20 @@ int dm_read_counters(o3s_dense_map* m, uint32_t out[16]) {
   return O3S_OK;
 }
 
-// VoxelizedPointCloud::insert on a device cloud
-int dm_insert_dev(o3s_dense_map* m, const double* d_pts, const double* d_nrm, int64_t N) {
+// The colour sums come into being with the first insert that needs them: a coloured cloud, or any cloud into a map whose
+// isHasColors_ outlived a clear().  All of them 1.0: that is what every voxel of the reference has held since it was made.
+int dm_ensure_colors(o3s_dense_map* m) {
+  if (m->csum.p) return O3S_OK;
+  DevMem cs;
+  CK(cs.alloc((size_t)m->cap * 24));
+  hipLaunchKernelGGL(k_dm_fill_ones, dim3(nblk(3 * m->cap)), dim3(kB), 0, m->stream, cs.as<double>(), 3 * m->cap);
+  CK(hipGetLastError());
+  m->csum = std::move(cs);
+  return O3S_OK;
+}
+
+// VoxelizedPointCloud::insert on a device cloud; d_nrm, d_col: nullable
+int dm_insert_dev(o3s_dense_map* m, const double* d_pts, const double* d_nrm, const double* d_col, int64_t N) {
   if (N == 0) return O3S_OK;
   if (N > (int64_t)0x7fffffff) return O3S_ERR_BAD_ARGUMENT;
   hipStream_t s = m->stream;
@@ -489,18 +583,35 @@ int dm_insert_dev(o3s_dense_map* m, const double* d_pts, const double* d_nrm, in
   rc = dm_read_counters(m, ctr);  // the range check has to be known before the table is touched
   if (rc != O3S_OK) return rc;
   if (ctr[8]) return O3S_ERR_BAD_ARGUMENT;
-  hipLaunchKernelGGL(k_dm_insert, dim3(nblk(N)), dim3(kB), 0, s, sk, sv, N, d_pts, d_nrm, m->K(), m->C(), m->S(), (uint64_t)(m->cap - 1),
-                     reinterpret_cast<uint32_t*>(m->d_ctr.p));
+  if (d_col || m->has_colors) {
+    rc = dm_ensure_colors(m);
+    if (rc != O3S_OK) return rc;
+  }
+  if (m->csum.p) {
+    hipLaunchKernelGGL(k_dm_insert<true>, dim3(nblk(N)), dim3(kB), 0, s, sk, sv, N, d_pts, d_nrm, d_col, m->K(), m->C(), m->S(), m->CS(),
+                       (uint64_t)(m->cap - 1), reinterpret_cast<uint32_t*>(m->d_ctr.p));
+  } else {
+    hipLaunchKernelGGL(k_dm_insert<false>, dim3(nblk(N)), dim3(kB), 0, s, sk, sv, N, d_pts, d_nrm, (const double*)nullptr, m->K(), m->C(),
+                       m->S(), (double*)nullptr, (uint64_t)(m->cap - 1), reinterpret_cast<uint32_t*>(m->d_ctr.p));
+  }
   CK(hipGetLastError());
   rc = dm_read_counters(m, ctr);
   if (rc != O3S_OK) return rc;
   m->live += ctr[0];
   m->tomb -= ctr[1];
   if (d_nrm) m->has_normals = 1;  // isHasNormals_ (Voxel.cpp:80-82)
+  if (d_col) m->has_colors = 1;   // isHasColors_ (Voxel.cpp:83-86)
   return O3S_OK;
 }
 
-int dm_upload(o3s_dense_map* m, const double* pts, const double* normals, int64_t N) {
+int dm_upload_colors(o3s_dense_map* m, const double* colors, int64_t N) {
+  hipStream_t s = m->stream;
+  CK(m->in_c.ensure((size_t)N * 24, 0, s));
+  CK(hipMemcpyAsync(m->in_c.p, colors, (size_t)N * 24, hipMemcpyHostToDevice, s));
+  return O3S_OK;
+}
+
+int dm_upload(o3s_dense_map* m, const double* pts, const double* normals, int64_t N, const double* colors = nullptr) {
   hipStream_t s = m->stream;
   CK(m->in_p.ensure((size_t)N * 24, 0, s));
   CK(hipMemcpyAsync(m->in_p.p, pts, (size_t)N * 24, hipMemcpyHostToDevice, s));
@@ -508,7 +619,7 @@ int dm_upload(o3s_dense_map* m, const double* pts, const double* normals, int64_
     CK(m->in_n.ensure((size_t)N * 24, 0, s));
     CK(hipMemcpyAsync(m->in_n.p, normals, (size_t)N * 24, hipMemcpyHostToDevice, s));
   }
-  return O3S_OK;
+  return colors ? dm_upload_colors(m, colors, N) : O3S_OK;
 }
 
 // Submap::carve on the dense map, scan already on the device
@@ -629,6 +740,8 @@ void o3s_dense_map_destroy(o3s_dense_map* m) {
 
 int64_t o3s_dense_map_size(const o3s_dense_map* m) { return m ? m->live : 0; }
 int o3s_dense_map_has_normals(const o3s_dense_map* m) { return m ? m->has_normals : 0; }
+int o3s_dense_map_has_colors(const o3s_dense_map* m) { return m ? m->has_colors : 0; }
+int64_t o3s_dense_map_capacity(const o3s_dense_map* m) { return m ? m->cap : 0; }
 
 void o3s_dense_map_clear(o3s_dense_map* m) {
   if (!m) return;
@@ -637,17 +750,22 @@ void o3s_dense_map_clear(o3s_dense_map* m) {
   m->keys.release();
   m->cnt.release();
   m->sum.release();
+  m->csum.release();  // (has_colors stays, like has_normals: VoxelHashMap::clear empties voxels_ alone, VoxelHashMap.hpp:125)
   m->cap = m->live = m->tomb = 0;
 }
 
-int o3s_dense_map_insert(o3s_dense_map* m, const double* pts, const double* normals, int64_t N) {
+int o3s_dense_map_insert_colored(o3s_dense_map* m, const double* pts, const double* normals, const double* colors, int64_t N) {
   if (!m || N < 0 || (N > 0 && !pts)) return O3S_ERR_BAD_ARGUMENT;
   if (N == 0) return O3S_OK;
   int rc = dm_set_dev(m);
   if (rc != O3S_OK) return rc;
-  rc = dm_upload(m, pts, normals, N);
+  rc = dm_upload(m, pts, normals, N, colors);
   if (rc != O3S_OK) return rc;
-  return dm_insert_dev(m, m->in_p.as<double>(), normals ? m->in_n.as<double>() : nullptr, N);
+  return dm_insert_dev(m, m->in_p.as<double>(), normals ? m->in_n.as<double>() : nullptr, colors ? m->in_c.as<double>() : nullptr, N);
+}
+
+int o3s_dense_map_insert(o3s_dense_map* m, const double* pts, const double* normals, int64_t N) {
+  return o3s_dense_map_insert_colored(m, pts, normals, nullptr, N);
 }
 
 int o3s_dense_map_carve(o3s_dense_map* m, const o3s_dense_carving_params* p, const double* scan_pts, int64_t N, const double sensor_position[3],
@@ -666,20 +784,36 @@ int o3s_dense_map_carve(o3s_dense_map* m, const o3s_dense_carving_params* p, con
 
 namespace {
 // Submap::insertScanDenseMap (Submap.cpp:97-113) on a raw scan that is already in HBM
-int dm_insert_scan_dev(o3s_dense_map* m, const o3s_cropper* dense_map_cropper, const double* d_raw_p, const double* d_raw_n, int64_t N,
-                       const double T[16], const o3s_dense_carving_params* carving, int64_t* n_removed) {
+// d_raw_c: the scan's colours (nullable); rgb: the bounds of colorCropper_
+int dm_insert_scan_dev(o3s_dense_map* m, const o3s_cropper* dense_map_cropper, const double* d_raw_p, const double* d_raw_n, const double* d_raw_c,
+                       const DmRgb& rgb, int64_t N, const double T[16], const o3s_dense_carving_params* carving, int64_t* n_removed) {
   hipStream_t s = m->stream;
   const bool hn = d_raw_n != nullptr;
   int rc = O3S_OK;
   if (N > 0) {
-    // denseMapCropper_->setPose(Identity); crop(rawScan) (Submap.cpp:99-100); no colours: colorCropper_ passes all
+    // denseMapCropper_->setPose(Identity); crop(rawScan) (Submap.cpp:99-100)
     o3s_cropper c = *dense_map_cropper;
     c.centre[0] = c.centre[1] = c.centre[2] = 0.0;
     CK(m->crop_p.ensure((size_t)N * 24, 0, s));
     CK(m->crop_n.ensure((size_t)N * 24, 0, s));
     int64_t kept = 0;
-    rc = crop_dev(m->arena, c, d_raw_p, d_raw_n, N, m->crop_p.as<double>(), m->crop_n.as<double>(), &kept, s);
-    if (rc != O3S_OK) return rc;
+    if (!d_raw_c) {  // a cloud without colours passes colorCropper_.crop whole (croppers.cpp:209-214)
+      rc = crop_dev(m->arena, c, d_raw_p, d_raw_n, N, m->crop_p.as<double>(), m->crop_n.as<double>(), &kept, s);
+      if (rc != O3S_OK) return rc;
+    } else {  // the volume crop and colorCropper_.crop (Submap.cpp:101) as one flag pass, one scan, one scatter
+      CK(m->crop_c.ensure((size_t)N * 24, 0, s));
+      CK(m->arena.reserve(crop_arena_bytes(N)));
+      uint32_t* flag = m->arena.take<uint32_t>((size_t)N);
+      uint32_t* off = m->arena.take<uint32_t>((size_t)N + 1);
+      const size_t tb = scan_temp_bytes(N);
+      void* tmp = m->arena.take<char>(tb);
+      hipLaunchKernelGGL(k_dm_color_mask, dim3(nblk(N)), dim3(kB), 0, s, c, 1, d_raw_p, d_raw_c, N, rgb, flag);
+      rc = scan_flags(flag, off, N, tmp, tb, &kept, s);
+      if (rc != O3S_OK) return rc;
+      hipLaunchKernelGGL(k_dm_compact_col, dim3(nblk(N)), dim3(kB), 0, s, d_raw_p, d_raw_n, d_raw_c, N, flag, off, m->crop_p.as<double>(),
+                         m->crop_n.as<double>(), m->crop_c.as<double>());
+      CK(hipGetLastError());
+    }
     if (kept > 0) {
       // o3d_slam::transform (helpers.cpp:283-318): a near-identity pose emits the cloud twice (copy + transformed)
       double dev = 0.0;
@@ -702,7 +836,10 @@ int dm_insert_scan_dev(o3s_dense_map* m, const o3s_cropper* dense_map_cropper, c
       hipLaunchKernelGGL(k_transform_append, dim3(nblk(kept)), dim3(kB), 0, s, m->crop_p.as<double>(), hn ? m->crop_n.as<double>() : nullptr, kept, m->d_T.as<double>(), dp,
                          hn ? dn : nullptr);
       CK(hipGetLastError());
-      rc = dm_insert_dev(m, m->tf_p.as<double>(), hn ? m->tf_n.as<double>() : nullptr, n_tf);
+      // out->colors_ = cloud.colors_ (helpers.cpp:291): the colours ride along as they are — `kept` of them also beside the 2 * kept
+      // points of the doubled cloud, which therefore no longer HasColors(): that scan adds no colour and does not set isHasColors_
+      const double* d_col = (d_raw_c && !doubled) ? m->crop_c.as<double>() : nullptr;
+      rc = dm_insert_dev(m, m->tf_p.as<double>(), hn ? m->tf_n.as<double>() : nullptr, d_col, n_tf);
       if (rc != O3S_OK) return rc;
     }
   }
@@ -715,40 +852,73 @@ int dm_insert_scan_dev(o3s_dense_map* m, const o3s_cropper* dense_map_cropper, c
   ++m->n_scans_inserted;
   return O3S_OK;
 }
+
+// ColorRangeCropper's bounds: rgbMin_ = 0, rgbMax_ = 1 unless given (croppers.hpp; nothing in the reference sets them)
+DmRgb dm_rgb(const double rgb_min[3], const double rgb_max[3]) {
+  DmRgb b;
+  for (int a = 0; a < 3; ++a) {
+    b.lo[a] = rgb_min ? rgb_min[a] : 0.0;
+    b.hi[a] = rgb_max ? rgb_max[a] : 1.0;
+  }
+  return b;
+}
 }  // namespace
 
 extern "C" {
 
-int o3s_dense_map_insert_scan(o3s_dense_map* m, const o3s_cropper* dense_map_cropper, const double* raw_pts, const double* raw_normals, int64_t N,
-                              const double T[16], const o3s_dense_carving_params* carving, int64_t* n_removed) {
+int o3s_dense_map_insert_scan_colored(o3s_dense_map* m, const o3s_cropper* dense_map_cropper, const double rgb_min[3], const double rgb_max[3],
+                                      const double* raw_pts, const double* raw_normals, const double* raw_colors, int64_t N, const double T[16],
+                                      const o3s_dense_carving_params* carving, int64_t* n_removed) {
   if (n_removed) *n_removed = 0;
   if (!m || !dense_map_cropper || !T || N < 0 || (N > 0 && !raw_pts)) return O3S_ERR_BAD_ARGUMENT;
   if (carving && carving->carve_space_every_n_scans <= 0) return O3S_ERR_BAD_ARGUMENT;  // the reference divides by it
   int rc = dm_set_dev(m);
   if (rc != O3S_OK) return rc;
   if (N > 0) {
-    rc = dm_upload(m, raw_pts, raw_normals, N);
+    rc = dm_upload(m, raw_pts, raw_normals, N, raw_colors);
     if (rc != O3S_OK) return rc;
   }
-  return dm_insert_scan_dev(m, dense_map_cropper, m->in_p.as<double>(), raw_normals ? m->in_n.as<double>() : nullptr, N, T, carving, n_removed);
+  return dm_insert_scan_dev(m, dense_map_cropper, m->in_p.as<double>(), raw_normals ? m->in_n.as<double>() : nullptr,
+                            raw_colors ? m->in_c.as<double>() : nullptr, dm_rgb(rgb_min, rgb_max), N, T, carving, n_removed);
+}
+
+int o3s_dense_map_insert_scan(o3s_dense_map* m, const o3s_cropper* dense_map_cropper, const double* raw_pts, const double* raw_normals, int64_t N,
+                              const double T[16], const o3s_dense_carving_params* carving, int64_t* n_removed) {
+  return o3s_dense_map_insert_scan_colored(m, dense_map_cropper, nullptr, nullptr, raw_pts, raw_normals, nullptr, N, T, carving, n_removed);
+}
+
+int o3s_dense_map_insert_resident_scan_colored(o3s_dense_map* m, const o3s_cropper* dense_map_cropper, const double rgb_min[3],
+                                               const double rgb_max[3], const o3s_scan* sc, const double* raw_colors, int64_t n_colors,
+                                               const double T[16], const o3s_dense_carving_params* carving, int64_t* n_removed) {
+  if (n_removed) *n_removed = 0;
+  if (!m || !dense_map_cropper || !sc || !T || (raw_colors && n_colors < 0)) return O3S_ERR_BAD_ARGUMENT;
+  if (carving && carving->carve_space_every_n_scans <= 0) return O3S_ERR_BAD_ARGUMENT;
+  if (sc->device != m->device) return O3S_ERR_BAD_ARGUMENT;
+  if (raw_colors && n_colors != sc->n_raw) return O3S_ERR_BAD_SHAPE;  // one colour per raw point
+  int rc = dm_set_dev(m);
+  if (rc != O3S_OK) return rc;
+  CK(hipStreamSynchronize(sc->stream));  // the scan's own work is complete (its calls end synchronised); this map's stream takes over
+  const bool hc = raw_colors && sc->n_raw > 0;
+  if (hc) {
+    rc = dm_upload_colors(m, raw_colors, sc->n_raw);
+    if (rc != O3S_OK) return rc;
+  }
+  return dm_insert_scan_dev(m, dense_map_cropper, sc->raw_p.as<double>(), sc->raw_has_normals ? sc->raw_n.as<double>() : nullptr,
+                            hc ? m->in_c.as<double>() : nullptr, dm_rgb(rgb_min, rgb_max), sc->n_raw, T, carving, n_removed);
 }
 
 int o3s_dense_map_insert_resident_scan(o3s_dense_map* m, const o3s_cropper* dense_map_cropper, const o3s_scan* sc, const double T[16],
                                        const o3s_dense_carving_params* carving, int64_t* n_removed) {
-  if (n_removed) *n_removed = 0;
-  if (!m || !dense_map_cropper || !sc || !T) return O3S_ERR_BAD_ARGUMENT;
-  if (carving && carving->carve_space_every_n_scans <= 0) return O3S_ERR_BAD_ARGUMENT;
-  if (sc->device != m->device) return O3S_ERR_BAD_ARGUMENT;
-  const int rc = dm_set_dev(m);
-  if (rc != O3S_OK) return rc;
-  CK(hipStreamSynchronize(sc->stream));  // the scan's own work is complete (its calls end synchronised); this map's stream takes over
-  return dm_insert_scan_dev(m, dense_map_cropper, sc->raw_p.as<double>(), sc->raw_has_normals ? sc->raw_n.as<double>() : nullptr, sc->n_raw, T, carving, n_removed);
+  return o3s_dense_map_insert_resident_scan_colored(m, dense_map_cropper, nullptr, nullptr, sc, nullptr, 0, T, carving, n_removed);
 }
 
-int o3s_dense_map_to_point_cloud(const o3s_dense_map* m, double* pts, double* normals, int32_t* keys, int32_t* counts, int64_t* n_out) {
+int o3s_dense_map_to_point_cloud_colored(const o3s_dense_map* m, double* pts, double* normals, double* colors, int32_t* keys, int32_t* counts,
+                                         int64_t* n_out) {
   if (n_out) *n_out = 0;
   if (!m) return O3S_ERR_BAD_ARGUMENT;
+  if (colors && !m->has_colors) return O3S_ERR_BAD_SHAPE;  // as o3s_submap_download_colors refuses a map without colours
   if (m->live == 0) return O3S_OK;
+  if (colors && !m->csum.p) return O3S_ERR_HIP;  // cannot happen: has_colors is set by, and a live voxel after it made by, an insert that holds them
   if (!pts) return O3S_ERR_BAD_ARGUMENT;
   int rc = dm_set_dev(m);
   if (rc != O3S_OK) return rc;
@@ -756,7 +926,7 @@ int o3s_dense_map_to_point_cloud(const o3s_dense_map* m, double* pts, double* no
   const size_t cap = (size_t)m->cap, v = (size_t)m->live;
   const size_t tb = std::max(scan_temp_bytes(m->cap), sort_temp_bytes(m->live));
   CK(m->arena.reserve(Arena::pad(cap * 4) + Arena::pad((cap + 1) * 4) + 2 * Arena::pad(v * 8) + 2 * Arena::pad(v * 4) + Arena::pad(tb) +
-                      2 * Arena::pad(v * 24) + Arena::pad(v * 12) + Arena::pad(v * 4) + 4096));
+                      (colors ? 3 : 2) * Arena::pad(v * 24) + Arena::pad(v * 12) + Arena::pad(v * 4) + 4096));
   uint32_t* flag = m->arena.take<uint32_t>(cap);
   uint32_t* off = m->arena.take<uint32_t>(cap + 1);
   uint64_t* k1 = m->arena.take<uint64_t>(v);
@@ -768,6 +938,7 @@ int o3s_dense_map_to_point_cloud(const o3s_dense_map* m, double* pts, double* no
   double* on = m->arena.take<double>(v * 3);
   int32_t* ok = m->arena.take<int32_t>(v * 3);
   int32_t* oc = m->arena.take<int32_t>(v);
+  double* ocol = colors ? m->arena.take<double>(v * 3) : nullptr;
   hipLaunchKernelGGL(k_dm_live, dim3(nblk(m->cap)), dim3(kB), 0, s, m->K(), m->C(), m->cap, flag);
   int64_t V = 0;
   rc = scan_flags(flag, off, m->cap, tmp, tb, &V, s);
@@ -777,14 +948,82 @@ int o3s_dense_map_to_point_cloud(const o3s_dense_map* m, double* pts, double* no
   hipLaunchKernelGGL(k_dm_collect, dim3(nblk(m->cap)), dim3(kB), 0, s, m->K(), flag, off, m->cap, k1, s1);
   size_t stb = tb;
   CK(rocprim::radix_sort_pairs(tmp, stb, k1, k2, s1, s2, (size_t)V, 0, 64, s));
-  hipLaunchKernelGGL(k_dm_emit, dim3(nblk(V)), dim3(kB), 0, s, k2, s2, V, m->C(), m->S(), op, on, ok, oc);
+  hipLaunchKernelGGL(k_dm_emit, dim3(nblk(V)), dim3(kB), 0, s, k2, s2, V, m->C(), m->S(), colors ? m->CS() : (const double*)nullptr, op, on, ocol, ok,
+                     oc);
   CK(hipGetLastError());
   CK(hipMemcpyAsync(pts, op, (size_t)V * 24, hipMemcpyDeviceToHost, s));
   if (normals) CK(hipMemcpyAsync(normals, on, (size_t)V * 24, hipMemcpyDeviceToHost, s));
+  if (colors) CK(hipMemcpyAsync(colors, ocol, (size_t)V * 24, hipMemcpyDeviceToHost, s));
   if (keys) CK(hipMemcpyAsync(keys, ok, (size_t)V * 12, hipMemcpyDeviceToHost, s));
   if (counts) CK(hipMemcpyAsync(counts, oc, (size_t)V * 4, hipMemcpyDeviceToHost, s));
   CK(hipStreamSynchronize(s));
   if (n_out) *n_out = V;
+  return O3S_OK;
+}
+
+int o3s_dense_map_to_point_cloud(const o3s_dense_map* m, double* pts, double* normals, int32_t* keys, int32_t* counts, int64_t* n_out) {
+  return o3s_dense_map_to_point_cloud_colored(m, pts, normals, nullptr, keys, counts, n_out);
+}
+
+// ColorRangeCropper::crop (croppers.cpp:205-239) on host buffers
+int o3s_color_range_crop(int device, const double rgb_min[3], const double rgb_max[3], const double* pts, const double* normals, const double* colors,
+                         const double* covariances, int64_t N, double* out_pts, double* out_normals, double* out_colors, double* out_covariances,
+                         int64_t* n_out) {
+  if (!pts || !out_pts || !n_out || N < 0 || (normals && !out_normals) || (colors && !out_colors) || (covariances && !out_covariances))
+    return O3S_ERR_BAD_ARGUMENT;
+  *n_out = 0;
+  if (N == 0) return O3S_OK;
+  if (N > (int64_t)0x7fffffff) return O3S_ERR_BAD_ARGUMENT;
+  if (!colors) {  // "*cropped = cloud" (croppers.cpp:211-214): nothing to decide, nothing for the device to do
+    std::memcpy(out_pts, pts, (size_t)N * 24);
+    if (normals) std::memcpy(out_normals, normals, (size_t)N * 24);
+    if (covariances) std::memcpy(out_covariances, covariances, (size_t)N * 72);
+    *n_out = N;
+    return O3S_OK;
+  }
+  int rc = pick_device(device);
+  if (rc != O3S_OK) return rc;
+  hipStream_t s = nullptr;
+  DevMem d_pts, d_nrm, d_col, d_cov, d_opts, d_on, d_ocol, d_ocov;
+  Arena ar;
+  CK(d_pts.alloc((size_t)N * 24));
+  CK(d_col.alloc((size_t)N * 24));
+  CK(d_opts.alloc((size_t)N * 24));
+  CK(d_ocol.alloc((size_t)N * 24));
+  CK(hipMemcpyAsync(d_pts.p, pts, (size_t)N * 24, hipMemcpyHostToDevice, s));
+  CK(hipMemcpyAsync(d_col.p, colors, (size_t)N * 24, hipMemcpyHostToDevice, s));
+  if (normals) {
+    CK(d_nrm.alloc((size_t)N * 24));
+    CK(d_on.alloc((size_t)N * 24));
+    CK(hipMemcpyAsync(d_nrm.p, normals, (size_t)N * 24, hipMemcpyHostToDevice, s));
+  }
+  if (covariances) {
+    CK(d_cov.alloc((size_t)N * 72));
+    CK(d_ocov.alloc((size_t)N * 72));
+    CK(hipMemcpyAsync(d_cov.p, covariances, (size_t)N * 72, hipMemcpyHostToDevice, s));
+  }
+  CK(ar.reserve(crop_arena_bytes(N)));
+  uint32_t* flag = ar.take<uint32_t>((size_t)N);
+  uint32_t* off = ar.take<uint32_t>((size_t)N + 1);
+  const size_t tb = scan_temp_bytes(N);
+  void* tmp = ar.take<char>(tb);
+  hipLaunchKernelGGL(k_dm_color_mask, dim3(nblk(N)), dim3(kB), 0, s, o3s_cropper{}, 0, d_pts.as<double>(), d_col.as<double>(), N,
+                     dm_rgb(rgb_min, rgb_max), flag);
+  int64_t kept = 0;
+  rc = scan_flags(flag, off, N, tmp, tb, &kept, s);
+  if (rc != O3S_OK) return rc;
+  hipLaunchKernelGGL(k_dm_compact_col, dim3(nblk(N)), dim3(kB), 0, s, d_pts.as<double>(), normals ? d_nrm.as<double>() : nullptr, d_col.as<double>(), N,
+                     flag, off, d_opts.as<double>(), d_on.as<double>(), d_ocol.as<double>());
+  if (covariances)
+    hipLaunchKernelGGL(k_compact_attr, dim3(nblk(N)), dim3(kB), 0, s, (const double*)nullptr, d_cov.as<double>(), N, flag, off, (double*)nullptr,
+                       d_ocov.as<double>());
+  CK(hipGetLastError());
+  CK(hipStreamSynchronize(s));
+  CK(hipMemcpy(out_pts, d_opts.p, (size_t)kept * 24, hipMemcpyDeviceToHost));
+  if (normals) CK(hipMemcpy(out_normals, d_on.p, (size_t)kept * 24, hipMemcpyDeviceToHost));
+  CK(hipMemcpy(out_colors, d_ocol.p, (size_t)kept * 24, hipMemcpyDeviceToHost));
+  if (covariances) CK(hipMemcpy(out_covariances, d_ocov.p, (size_t)kept * 72, hipMemcpyDeviceToHost));
+  *n_out = kept;
   return O3S_OK;
 }
 

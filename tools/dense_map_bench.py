@@ -1,6 +1,8 @@
 """Timing of the device-resident dense map (include/o3s_dense_map.h) on a 64-beam style scan sequence: insert, carve,
-toPointCloud; the CPU oracle (sequential, like the reference's loops) timed beside it on a smaller sample.
-Usage: python tools/dense_map_bench.py [--scans 30] [--points 120000] [--voxel 0.05] [--out FILE]"""
+toPointCloud; the CPU oracle (sequential, like the reference's loops) timed beside it on a smaller sample.  --colors adds a
+second leg: the same sweeps with a colour per point into a map of its own (include/dense_map/o3s_dense_map_color.h), reported
+beside the colourless leg and as a ratio to it.
+Usage: python tools/dense_map_bench.py [--scans 30] [--points 120000] [--voxel 0.05] [--colors] [--out FILE]"""
 import argparse
 import json
 import os
@@ -23,6 +25,7 @@ def main():
     ap.add_argument("--voxel", type=float, default=0.05)
     ap.add_argument("--radius", type=float, default=0.1)
     ap.add_argument("--cpu-rays", type=int, default=2000)
+    ap.add_argument("--colors", action="store_true", help="also time the coloured leg")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     world = syn.make_world(20000.0, seed=7)
@@ -62,11 +65,35 @@ def main():
     t0 = time.perf_counter()
     om.carve(tp[: a.cpu_rays], T[:3, 3] + np.array([0.3, 0.2, 0.1]), a.radius, 20.0, 0.1)
     cpu_carve = time.perf_counter() - t0
+    colored = {}
+    if a.colors:
+        rng = np.random.default_rng(11)
+        cols = [rng.uniform(0.0, 1.0, sp.shape) for sp, _, _ in scans]   # inside the default colour range: every point is kept
+        cm = DenseMap(a.voxel)
+        cm.insertScanDenseMap(scans[0][0], scans[0][2], crop, raw_normals=scans[0][1], raw_colors=cols[0])  # warm-up, as above
+        cm.clear()
+        t_col = []
+        for (sp, sn, T), sc in zip(scans, cols):
+            t0 = time.perf_counter()
+            cm.insertScanDenseMap(sp, T, crop, raw_normals=sn, raw_colors=sc)
+            t_col.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        cm.toPointCloud(with_colors=True)
+        t_cout = time.perf_counter() - t0
+        assert cm.size() == sizes[-1] and cm.hasColors()
+        colored = {
+            "colored_insert_scan_ms_median": 1e3 * float(np.median(t_col)),
+            "colored_insert_scan_ms_all": [round(1e3 * t, 4) for t in t_col],
+            "colored_over_colorless_insert": float(np.median(t_col) / np.median(t_ins)),
+            "colored_to_point_cloud_ms": 1e3 * t_cout,
+        }
     res = {
         "workload": f"{a.scans} scans x {a.points} pts, dense voxel {a.voxel} m, carve radius {a.radius} m",
         "voxels_final": sizes[-1],
         "insert_scan_ms_median": 1e3 * float(np.median(t_ins)),
         "insert_scan_ms_last": 1e3 * t_ins[-1],
+        "insert_scan_ms_min_max": [1e3 * min(t_ins), 1e3 * max(t_ins)],
+        "insert_scan_ms_all": [round(1e3 * t, 4) for t in t_ins],
         "carve_ms_median": 1e3 * float(np.median(t_carve)),
         "carve_rays": a.points,
         "carve_removed": removed,
@@ -75,6 +102,7 @@ def main():
         "cpu_oracle_carve_ms_per_1000_rays": 1e3 * cpu_carve / (a.cpu_rays / 1000.0),
         "note": "host-to-device copies of the scan included; CPU oracle is single-threaded with an ordered map",
     }
+    res.update(colored)
     line = json.dumps(res)
     print(line)
     if a.out:
