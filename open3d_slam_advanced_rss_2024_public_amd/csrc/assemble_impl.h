@@ -128,13 +128,25 @@ __global__ void __launch_bounds__(kB) k_asm_reduce(AsmTable t, const uint64_t* _
   }
 }
 
-inline size_t assemble_arena_bytes(int64_t N) {
-  const size_t n = (size_t)N;
-  return Arena::pad(kBoundsWords * 8)                              // bounds block
-         + 2 * Arena::pad(n * 8) + 2 * Arena::pad(n * 4)           // keys x2, vals x2
-         + Arena::pad(n * 4) + Arena::pad((n + 1) * 4)             // head, ord
-         + Arena::pad(std::max(scan_temp_bytes(N), sort_temp_bytes(N))) + 4096;
-}
+// work area of the voxelising build over n points in all
+struct AssembleArea {
+  static constexpr size_t kSlack = 4096;
+  unsigned long long* d_bb;  // bounds block
+  uint64_t *keys, *keys2;
+  uint32_t *vals, *vals2, *head, *ord;
+  char* tmp;  // also k_heads' per-block counts `blk` (room: scan_temp_bytes), consumed by the scan right behind
+  template <class A>
+  void lay(A& a, size_t n, size_t tb_scan, size_t tb_sort) {
+    take(a, d_bb, kBoundsWords);
+    take(a, keys, n);
+    take(a, keys2, n);
+    take(a, vals, n);
+    take(a, vals2, n);
+    take(a, head, n);
+    take(a, ord, n + 1);
+    take(a, tmp, std::max(tb_scan, tb_sort));
+  }
+};
 
 }  // namespace
 
@@ -265,23 +277,15 @@ int o3s_assembled_map_build(o3s_assembled_map* a, int32_t n, o3s_submap* const* 
 
   // ---- Open3D VoxelDownSample of the concatenation
   const int64_t N = total;
-  CK(a->arena.reserve(assemble_arena_bytes(N)));
-  Arena& ar = a->arena;
-  unsigned long long* d_bb = ar.take<unsigned long long>(kBoundsWords);
-  uint64_t* keys = ar.take<uint64_t>((size_t)N);
-  uint64_t* keys2 = ar.take<uint64_t>((size_t)N);
-  uint32_t* vals = ar.take<uint32_t>((size_t)N);
-  uint32_t* vals2 = ar.take<uint32_t>((size_t)N);
-  uint32_t* head = ar.take<uint32_t>((size_t)N);
-  uint32_t* ord = ar.take<uint32_t>((size_t)N + 1);
   const size_t tb_scan = scan_temp_bytes(N), tb_sort = sort_temp_bytes(N);
-  void* tmp = ar.take<char>(std::max(tb_scan, tb_sort));
-  uint32_t* blk = reinterpret_cast<uint32_t*>(tmp);  // k_heads' per-block counts (room: scan_temp_bytes), consumed by the scan right behind
+  AssembleArea ar;
+  CK(lay_out(a->arena, ar, (size_t)N, tb_scan, tb_sort));
+  uint32_t* blk = reinterpret_cast<uint32_t*>(ar.tmp);  // k_heads' per-block counts (room: scan_temp_bytes), consumed by the scan right behind
   const unsigned nb = nblk(N);
   // 1. exact min and max bound over all segments, read back once
   const AsmPoints cloud{t};
   unsigned long long bnd[6];
-  if (const int rc = cloud_bounds(cloud, N, d_bb, s, bnd); rc != O3S_OK) return rc;
+  if (const int rc = cloud_bounds(cloud, N, ar.d_bb, s, bnd); rc != O3S_OK) return rc;
   // anchor = min_bound - voxel / 2; extents from the max bound with the kernel's own expression (IEEE fp64 on both sides)
   double anchor[3];
   uint64_t ext[3];
@@ -296,13 +300,13 @@ int o3s_assembled_map_build(o3s_assembled_map* a, int32_t n, o3s_submap* const* 
   const int bits = key_bits((uint64_t)prod);
   // 2. - 4. keys from the segments (Open3D's voxel index floor((p - anchor) / voxel), packed (z, y, x); the value is the global
   // ordinal; floor((x - a) / v) is monotone in x, so every index is inside the extents), stable sort, heads, flag scan
-  hipLaunchKernelGGL(k_grid_keys<AsmPoints>, dim3(nb), dim3(kB), 0, s, cloud, N, voxel_size, anchor[0], anchor[1], anchor[2], ext[0], ext[1], keys, vals);
+  hipLaunchKernelGGL(k_grid_keys<AsmPoints>, dim3(nb), dim3(kB), 0, s, cloud, N, voxel_size, anchor[0], anchor[1], anchor[2], ext[0], ext[1], ar.keys, ar.vals);
   size_t tb = tb_sort;
-  CK(sort_pairs(tmp, tb, keys, keys2, vals, vals2, (size_t)N, bits, s));
-  hipLaunchKernelGGL(k_heads, dim3(nb), dim3(kB), 0, s, keys2, N, ~0ull /*no key is excluded*/, head, 0, blk);
+  CK(sort_pairs(ar.tmp, tb, ar.keys, ar.keys2, ar.vals, ar.vals2, (size_t)N, bits, s));
+  hipLaunchKernelGGL(k_heads, dim3(nb), dim3(kB), 0, s, ar.keys2, N, ~0ull /*no key is excluded*/, ar.head, 0, blk);
   int64_t n_vox = 0;
   {
-    const int rc = scan_flags(head, ord, N, tmp, tb_scan, &n_vox, s, blk);
+    const int rc = scan_flags(ar.head, ar.ord, N, ar.tmp, tb_scan, &n_vox, s, blk);
     if (rc != O3S_OK) return rc;
   }
   if (n_vox <= 0 || n_vox > N) return O3S_ERR_HIP;
@@ -312,7 +316,7 @@ int o3s_assembled_map_build(o3s_assembled_map* a, int32_t n, o3s_submap* const* 
   CK(a->pts.ensure(bytes, 0, s));
   if (hn) CK(a->nrm.ensure(bytes, 0, s));
   if (hc) CK(a->col.ensure(bytes, 0, s));
-  hipLaunchKernelGGL(k_asm_reduce, dim3(nb), dim3(kB), 0, s, t, keys2, vals2, head, ord, N, a->pts.as<double>(), hn ? a->nrm.as<double>() : nullptr,
+  hipLaunchKernelGGL(k_asm_reduce, dim3(nb), dim3(kB), 0, s, t, ar.keys2, ar.vals2, ar.head, ar.ord, N, a->pts.as<double>(), hn ? a->nrm.as<double>() : nullptr,
                      hc ? a->col.as<double>() : nullptr);
   CK(hipGetLastError());
   CK(hipStreamSynchronize(s));

@@ -33,6 +33,9 @@ namespace {  // internal linkage
 using o3s::Arena;
 using o3s::DevMem;
 using o3s::LeasePool;
+using o3s::lay_out;
+using o3s::lay_out_in;
+using o3s::layout_bytes;
 namespace o3s_cloud {
 using namespace o3s::host_post;
 
@@ -764,35 +767,61 @@ inline int scan_flags(const uint32_t* flag, uint32_t* off, int64_t n, void* tmp,
   return O3S_OK;
 }
 
-inline size_t crop_arena_bytes(int64_t N) { return Arena::pad((size_t)N * 4) + Arena::pad((size_t)(N + 1) * 4) + Arena::pad(scan_temp_bytes(N)) + 1024; }
+// work area of a crop (and of every other mask - scan - compact of n items): flags, their offsets, the scan's temp
+struct CropArea {
+  static constexpr size_t kSlack = 1024;
+  uint32_t *flag, *off;
+  char* tmp;
+  template <class A>
+  void lay(A& a, size_t n, size_t tb_scan) {
+    take(a, flag, n);
+    take(a, off, n + 1);
+    take(a, tmp, tb_scan);
+  }
+};
 
 // CroppingVolume::crop (croppers.cpp:76-106) on device arrays: order-preserving compaction of the points inside
 inline int crop_dev(Arena& ar, const o3s_cropper& c, const double* d_pts, const double* d_nrm, int64_t N, double* d_opts, double* d_on,
                     int64_t* kept, hipStream_t s, const Attrs* at = nullptr) {
   *kept = 0;
   if (N == 0) return O3S_OK;
-  CK(ar.reserve(crop_arena_bytes(N)));
-  uint32_t* flag = ar.take<uint32_t>((size_t)N);
-  uint32_t* off = ar.take<uint32_t>((size_t)N + 1);
   const size_t tb = scan_temp_bytes(N);
-  void* tmp = ar.take<char>(tb);
-  hipLaunchKernelGGL(k_mask, dim3(nblk(N)), dim3(kB), 0, s, c, d_pts, N, 1, flag);
-  const int rc = scan_flags(flag, off, N, tmp, tb, kept, s);
+  CropArea w;
+  CK(lay_out(ar, w, (size_t)N, tb));
+  hipLaunchKernelGGL(k_mask, dim3(nblk(N)), dim3(kB), 0, s, c, d_pts, N, 1, w.flag);
+  const int rc = scan_flags(w.flag, w.off, N, w.tmp, tb, kept, s);
   if (rc != O3S_OK) return rc;
-  hipLaunchKernelGGL(k_compact, dim3(nblk(N)), dim3(kB), 0, s, d_pts, d_nrm, N, flag, off, d_opts, d_on, (int32_t*)nullptr);
-  if (at && at->any()) hipLaunchKernelGGL(k_compact_attr, dim3(nblk(N)), dim3(kB), 0, s, at->col, at->cov, N, flag, off, at->out_col, at->out_cov);
+  hipLaunchKernelGGL(k_compact, dim3(nblk(N)), dim3(kB), 0, s, d_pts, d_nrm, N, w.flag, w.off, d_opts, d_on, (int32_t*)nullptr);
+  if (at && at->any()) hipLaunchKernelGGL(k_compact_attr, dim3(nblk(N)), dim3(kB), 0, s, at->col, at->cov, N, w.flag, w.off, at->out_col, at->out_cov);
   CK(hipGetLastError());
   return O3S_OK;
 }
 
-inline size_t voxel_arena_bytes(int64_t N) {
-  const size_t n = (size_t)N;
-  return Arena::pad(n * 4) + Arena::pad((n + 1) * 4)                 // flag, off
-         + Arena::pad(n * 12) + Arena::pad(kExtSlots * 6 * 4) + Arena::pad(kBoundsWords * 8)  // vidx, mm, bounds block
-         + 2 * Arena::pad(n * 8) + 2 * Arena::pad(n * 4)             // keys x2, vals x2
-         + Arena::pad(n * 4) + Arena::pad((n + 1) * 4)               // head, ord
-         + Arena::pad(std::max(scan_temp_bytes(N), sort_temp_bytes(N))) + 4096;
-}
+// work area of the measuring voxeliser
+struct VoxelArea {
+  static constexpr size_t kSlack = 4096;
+  uint32_t *flag, *off;
+  int32_t *vidx, *d_mm;
+  unsigned long long* d_bb;  // bounds block
+  uint64_t *keys, *keys2;
+  uint32_t *vals, *vals2, *head, *ord;
+  char* tmp;
+  template <class A>
+  void lay(A& a, size_t n, size_t tb_scan, size_t tb_sort) {
+    take(a, flag, n);
+    take(a, off, n + 1);
+    take(a, vidx, n * 3);
+    take(a, d_mm, kExtSlots * 6);
+    take(a, d_bb, kBoundsWords);
+    take(a, keys, n);
+    take(a, keys2, n);
+    take(a, vals, n);
+    take(a, vals2, n);
+    take(a, head, n);
+    take(a, ord, n + 1);
+    take(a, tmp, std::max(tb_scan, tb_sort));
+  }
+};
 
 // Shared body of the two voxelisers on device arrays: pass-through compaction, sort of the voxelised points by packed
 // voxel key, per-voxel reduction.  d_opts / d_on / d_oidx hold up to N points.
@@ -801,34 +830,23 @@ inline int voxel_pipeline_dev(Arena& ar, int mode, const o3s_cropper* crop, doub
   *n_out = 0;
   if (N == 0) return O3S_OK;
   if (N > (int64_t)0x7fffffff) return O3S_ERR_BAD_ARGUMENT;
-  CK(ar.reserve(voxel_arena_bytes(N)));
-  uint32_t* flag = ar.take<uint32_t>((size_t)N);
-  uint32_t* off = ar.take<uint32_t>((size_t)N + 1);
-  int32_t* vidx = ar.take<int32_t>((size_t)N * 3);
-  int32_t* d_mm = ar.take<int32_t>(kExtSlots * 6);
-  unsigned long long* d_bb = ar.take<unsigned long long>(kBoundsWords);
-  uint64_t* keys = ar.take<uint64_t>((size_t)N);
-  uint64_t* keys2 = ar.take<uint64_t>((size_t)N);
-  uint32_t* vals = ar.take<uint32_t>((size_t)N);
-  uint32_t* vals2 = ar.take<uint32_t>((size_t)N);
-  uint32_t* head = ar.take<uint32_t>((size_t)N);
-  uint32_t* ord = ar.take<uint32_t>((size_t)N + 1);
   const size_t tb_scan = scan_temp_bytes(N), tb_sort = sort_temp_bytes(N);
-  void* tmp = ar.take<char>(std::max(tb_scan, tb_sort));
+  VoxelArea w;
+  CK(lay_out(ar, w, (size_t)N, tb_scan, tb_sort));
   int64_t n_pass = 0;
   const uint32_t* passflag = nullptr;
   if (crop) {  // pass-through points: outside the volume, emitted first in input order (helpers.cpp:162-176)
-    hipLaunchKernelGGL(k_mask, dim3(nblk(N)), dim3(kB), 0, s, *crop, d_pts, N, 0, flag);
-    const int rc = scan_flags(flag, off, N, tmp, tb_scan, &n_pass, s);
+    hipLaunchKernelGGL(k_mask, dim3(nblk(N)), dim3(kB), 0, s, *crop, d_pts, N, 0, w.flag);
+    const int rc = scan_flags(w.flag, w.off, N, w.tmp, tb_scan, &n_pass, s);
     if (rc != O3S_OK) return rc;
-    hipLaunchKernelGGL(k_compact, dim3(nblk(N)), dim3(kB), 0, s, d_pts, d_nrm, N, flag, off, d_opts, d_on, d_oidx);
-    if (at && at->any()) hipLaunchKernelGGL(k_compact_attr, dim3(nblk(N)), dim3(kB), 0, s, at->col, at->cov, N, flag, off, at->out_col, at->out_cov);
-    passflag = flag;
+    hipLaunchKernelGGL(k_compact, dim3(nblk(N)), dim3(kB), 0, s, d_pts, d_nrm, N, w.flag, w.off, d_opts, d_on, d_oidx);
+    if (at && at->any()) hipLaunchKernelGGL(k_compact_attr, dim3(nblk(N)), dim3(kB), 0, s, at->col, at->cov, N, w.flag, w.off, at->out_col, at->out_cov);
+    passflag = w.flag;
   }
   double ax = 0, ay = 0, az = 0;
   if (mode == 1) {  // Open3D: anchor = min_bound - voxel/2
     unsigned long long bb[6];
-    const int rc = cloud_bounds<false>(FlatPoints{d_pts}, N, d_bb, s, bb);  // the minima only: the anchor
+    const int rc = cloud_bounds<false>(FlatPoints{d_pts}, N, w.d_bb, s, bb);  // the minima only: the anchor
     if (rc != O3S_OK) return rc;
     const double m[3] = {from_ordered_bits(bb[0]), from_ordered_bits(bb[1]), from_ordered_bits(bb[2])};
     ax = m[0] - voxel * 0.5;
@@ -836,13 +854,13 @@ inline int voxel_pipeline_dev(Arena& ar, int mode, const o3s_cropper* crop, doub
     az = m[2] - voxel * 0.5;
   }
   {
-    const int rc0 = ext_i32_init(d_mm, s);
+    const int rc0 = ext_i32_init(w.d_mm, s);
     if (rc0 != O3S_OK) return rc0;
   }
-  hipLaunchKernelGGL(k_vox_keys_idx, dim3(nblk(N)), dim3(kB), 0, s, d_pts, N, passflag, mode, 1.0 / voxel, voxel, ax, ay, az, vidx, d_mm);
+  hipLaunchKernelGGL(k_vox_keys_idx, dim3(nblk(N)), dim3(kB), 0, s, d_pts, N, passflag, mode, 1.0 / voxel, voxel, ax, ay, az, w.vidx, w.d_mm);
   int32_t mm[6];
   {
-    const int rc0 = ext_i32_fetch(d_mm, mm, s);
+    const int rc0 = ext_i32_fetch(w.d_mm, mm, s);
     if (rc0 != O3S_OK) return rc0;
   }
   int64_t n_vox = 0;
@@ -857,16 +875,16 @@ inline int voxel_pipeline_dev(Arena& ar, int mode, const o3s_cropper* crop, doub
     while (bits < 63 && ((long double)(1ull << bits)) <= prod) ++bits;
     const uint64_t pass_key = bits < 63 ? (1ull << bits) : ~0ull;
     const int end_bit = passflag ? (bits < 63 ? bits + 1 : 64) : bits;
-    hipLaunchKernelGGL(k_vox_pack, dim3(nblk(N)), dim3(kB), 0, s, N, passflag, vidx, mm[0], mm[1], mm[2], ex, ey, pass_key, keys, vals);
+    hipLaunchKernelGGL(k_vox_pack, dim3(nblk(N)), dim3(kB), 0, s, N, passflag, w.vidx, mm[0], mm[1], mm[2], ex, ey, pass_key, w.keys, w.vals);
     size_t tb = tb_sort;
-    CK(sort_pairs(tmp, tb, keys, keys2, vals, vals2, (size_t)N, end_bit, s));
-    hipLaunchKernelGGL(k_heads, dim3(nblk(N)), dim3(kB), 0, s, keys2, N, pass_key, head);
-    const int rc = scan_flags(head, ord, N, tmp, tb_scan, &n_vox, s);
+    CK(sort_pairs(w.tmp, tb, w.keys, w.keys2, w.vals, w.vals2, (size_t)N, end_bit, s));
+    hipLaunchKernelGGL(k_heads, dim3(nblk(N)), dim3(kB), 0, s, w.keys2, N, pass_key, w.head);
+    const int rc = scan_flags(w.head, w.ord, N, w.tmp, tb_scan, &n_vox, s);
     if (rc != O3S_OK) return rc;
-    hipLaunchKernelGGL(k_vox_reduce, dim3(nblk(N)), dim3(kB), 0, s, keys2, vals2, head, ord, N, d_pts, d_nrm, vidx, mode == 0 ? 1 : 0,
+    hipLaunchKernelGGL(k_vox_reduce, dim3(nblk(N)), dim3(kB), 0, s, w.keys2, w.vals2, w.head, w.ord, N, d_pts, d_nrm, w.vidx, mode == 0 ? 1 : 0,
                        mode == 0 ? 1 : 0, n_pass, d_opts, d_on, d_oidx);
     if (at && at->any())
-      hipLaunchKernelGGL(k_vox_reduce_attr, dim3(nblk(N)), dim3(kB), 0, s, keys2, vals2, head, ord, N, at->col, at->cov, mode == 1 ? 1 : 0, n_pass,
+      hipLaunchKernelGGL(k_vox_reduce_attr, dim3(nblk(N)), dim3(kB), 0, s, w.keys2, w.vals2, w.head, w.ord, N, at->col, at->cov, mode == 1 ? 1 : 0, n_pass,
                          at->out_col, at->out_cov);
   }
   CK(hipGetLastError());
@@ -974,6 +992,32 @@ inline int scan_flags_dev(const uint32_t* flag, uint32_t* off, int64_t n, void* 
 // post_crop (nullable): CroppingVolume::crop of the voxelised output into d_ppts / d_pn (the narrow crop).
 // counts[0..2] = pass-through points, voxels, points kept by post_crop.  *ok = false: an index fell outside the hint (or
 // the mailbox is off) and nothing was produced — the caller repeats on the measuring path.
+// work area of the hinted voxelisers.  It is RESERVED as a VoxelArea of the same size (the measuring path a miss falls back
+// to then finds its area in place), which is never smaller: status and part fill at most the slots of d_mm and d_bb
+struct VoxelHintArea {
+  uint32_t *flag, *off;
+  int32_t* vidx;
+  uint32_t* status;          // 16 words used
+  unsigned long long* part;  // mode 1 needs nblk(n) * 3: it borrows `head` when that is large enough (voxel_pipeline_hint_dev)
+  uint64_t *keys, *keys2;
+  uint32_t *vals, *vals2, *head, *ord;
+  char* tmp;  // also the flag producers' per-block counts `blk` (scan_temp_bytes has room for them): written and consumed between two uses by the sort
+  template <class A>
+  void lay(A& a, size_t n, size_t tb_scan, size_t tb_sort) {
+    take(a, flag, n);
+    take(a, off, n + 1);
+    take(a, vidx, n * 3);
+    take(a, status, kExtSlots * 6);
+    take(a, part, kExtSlots * 3);
+    take(a, keys, n);
+    take(a, keys2, n);
+    take(a, vals, n);
+    take(a, vals2, n);
+    take(a, head, n);
+    take(a, ord, n + 1);
+    take(a, tmp, std::max(tb_scan, tb_sort));
+  }
+};
 inline int voxel_pipeline_hint_dev(Arena& ar, int mode, const o3s_cropper* crop, const VoxHint& h, double voxel, const double* d_pts,
                                    const double* d_nrm, int64_t N, double* d_opts, double* d_on, int32_t* d_oidx, const Attrs* at,
                                    const o3s_cropper* post_crop, double* d_ppts, double* d_pn, int64_t counts[3], bool* ok, hipStream_t s,
@@ -982,71 +1026,60 @@ inline int voxel_pipeline_hint_dev(Arena& ar, int mode, const o3s_cropper* crop,
   *ok = false;
   PinnedArea& pa = pinned_area();
   if (N <= 0 || N > (int64_t)0x7fffffff || !mailbox_enabled(pa)) return O3S_OK;
-  CK(ar.reserve(voxel_arena_bytes(N)));
-  uint32_t* flag = ar.take<uint32_t>((size_t)N);
-  uint32_t* off = ar.take<uint32_t>((size_t)N + 1);
-  int32_t* vidx = ar.take<int32_t>((size_t)N * 3);
-  uint32_t* status = reinterpret_cast<uint32_t*>(ar.take<int32_t>(kExtSlots * 6));  // 16 words used
-  unsigned long long* part = ar.take<unsigned long long>(kExtSlots * 3);           // mode 1 needs nblk(N) * 3: taken from vidx when it is free
-  uint64_t* keys = ar.take<uint64_t>((size_t)N);
-  uint64_t* keys2 = ar.take<uint64_t>((size_t)N);
-  uint32_t* vals = ar.take<uint32_t>((size_t)N);
-  uint32_t* vals2 = ar.take<uint32_t>((size_t)N);
-  uint32_t* head = ar.take<uint32_t>((size_t)N);
-  uint32_t* ord = ar.take<uint32_t>((size_t)N + 1);
   const size_t tb_scan = scan_temp_bytes(N), tb_sort = sort_temp_bytes(N);
-  void* tmp = ar.take<char>(std::max(tb_scan, tb_sort));
-  uint32_t* blk = reinterpret_cast<uint32_t*>(tmp);  // the flag producers' per-block counts (scan_temp_bytes has room for them): written and
+  VoxelHintArea w;
+  CK(lay_out_in(ar, layout_bytes<VoxelArea>((size_t)N, tb_scan, tb_sort), w, (size_t)N, tb_scan, tb_sort));
+  uint32_t* blk = reinterpret_cast<uint32_t*>(w.tmp);  // the flag producers' per-block counts (scan_temp_bytes has room for them): written and
                                                      // consumed between two uses of tmp by the sort
   const unsigned nb = nblk(N);
   const bool pass = mode == 0 && crop != nullptr;
   const o3s_cropper none{};
   if (mode == 1) {
     // nblk(N) * 24 bytes of minima: `head` (4 N bytes) is free until k_heads and large enough for N >= 2 blocks of input
-    part = (size_t)nb * 24 <= (size_t)N * 4 ? reinterpret_cast<unsigned long long*>(head) : part;
+    w.part = (size_t)nb * 24 <= (size_t)N * 4 ? reinterpret_cast<unsigned long long*>(w.head) : w.part;
     if ((size_t)nb * 24 > (size_t)N * 4 && nb > (unsigned)kExtSlots) return O3S_OK;
-    hipLaunchKernelGGL(k_min_part, dim3(nb), dim3(kB), 0, s, crop ? *crop : none, crop ? 1 : 0, d_pts, N, part, status);
+    hipLaunchKernelGGL(k_min_part, dim3(nb), dim3(kB), 0, s, crop ? *crop : none, crop ? 1 : 0, d_pts, N, w.part, w.status);
   } else {
-    if (!pass) CK(hipMemsetAsync(status, 0, 64, s));
+    if (!pass) CK(hipMemsetAsync(w.status, 0, 64, s));
     if (pass) {
-      hipLaunchKernelGGL(k_mask, dim3(nb), dim3(kB), 0, s, *crop, d_pts, N, 0, flag, status, blk);
-      const int rc = scan_flags_dev(flag, off, N, tmp, tb_scan, s, blk);
+      hipLaunchKernelGGL(k_mask, dim3(nb), dim3(kB), 0, s, *crop, d_pts, N, 0, w.flag, w.status, blk);
+      const int rc = scan_flags_dev(w.flag, w.off, N, w.tmp, tb_scan, s, blk);
       if (rc != O3S_OK) return rc;
-      hipLaunchKernelGGL(k_compact, dim3(nb), dim3(kB), 0, s, d_pts, d_nrm, N, flag, off, d_opts, d_on, d_oidx);
-      if (at && at->any()) hipLaunchKernelGGL(k_compact_attr, dim3(nb), dim3(kB), 0, s, at->col, at->cov, N, flag, off, at->out_col, at->out_cov);
+      hipLaunchKernelGGL(k_compact, dim3(nb), dim3(kB), 0, s, d_pts, d_nrm, N, w.flag, w.off, d_opts, d_on, d_oidx);
+      if (at && at->any()) hipLaunchKernelGGL(k_compact_attr, dim3(nb), dim3(kB), 0, s, at->col, at->cov, N, w.flag, w.off, at->out_col, at->out_cov);
     }
   }
   const uint64_t pass_key = 1ull << h.bits;
-  hipLaunchKernelGGL(k_vox_key_direct, dim3(nb), dim3(kB), 0, s, d_pts, N, pass ? flag : nullptr, (mode == 1 && crop) ? *crop : none,
-                     (mode == 1 && crop) ? 1 : 0, mode, 1.0 / voxel, voxel, part, (int)nb, h, pass_key, d_oidx ? vidx : nullptr, keys, vals, status);
+  hipLaunchKernelGGL(k_vox_key_direct, dim3(nb), dim3(kB), 0, s, d_pts, N, pass ? w.flag : nullptr, (mode == 1 && crop) ? *crop : none,
+                     (mode == 1 && crop) ? 1 : 0, mode, 1.0 / voxel, voxel, w.part, (int)nb, h, pass_key, d_oidx ? w.vidx : nullptr, w.keys, w.vals, w.status);
   size_t tb = tb_sort;
-  CK(sort_pairs(tmp, tb, keys, keys2, vals, vals2, (size_t)N, h.bits + 1, s));
-  hipLaunchKernelGGL(k_heads, dim3(nb), dim3(kB), 0, s, keys2, N, pass_key, head, 0, blk);
+  CK(sort_pairs(w.tmp, tb, w.keys, w.keys2, w.vals, w.vals2, (size_t)N, h.bits + 1, s));
+  hipLaunchKernelGGL(k_heads, dim3(nb), dim3(kB), 0, s, w.keys2, N, pass_key, w.head, 0, blk);
   {
-    const int rc = scan_flags_dev(head, ord, N, tmp, tb_scan, s, blk);
+    const int rc = scan_flags_dev(w.head, w.ord, N, w.tmp, tb_scan, s, blk);
     if (rc != O3S_OK) return rc;
   }
-  hipLaunchKernelGGL(k_vox_reduce, dim3(nb), dim3(kB), 0, s, keys2, vals2, head, ord, N, d_pts, d_nrm, vidx, mode == 0 ? 1 : 0, mode == 0 ? 1 : 0,
-                     (int64_t)0, d_opts, d_on, d_oidx, pass ? flag : nullptr, pass ? off : nullptr, N);
+  hipLaunchKernelGGL(k_vox_reduce, dim3(nb), dim3(kB), 0, s, w.keys2, w.vals2, w.head, w.ord, N, d_pts, d_nrm, w.vidx, mode == 0 ? 1 : 0, mode == 0 ? 1 : 0,
+                     (int64_t)0, d_opts, d_on, d_oidx, pass ? w.flag : nullptr, pass ? w.off : nullptr, N);
   if (at && at->any())
-    hipLaunchKernelGGL(k_vox_reduce_attr, dim3(nb), dim3(kB), 0, s, keys2, vals2, head, ord, N, at->col, at->cov, mode == 1 ? 1 : 0, (int64_t)0,
-                       at->out_col, at->out_cov, pass ? flag : nullptr, pass ? off : nullptr, N);
+    hipLaunchKernelGGL(k_vox_reduce_attr, dim3(nb), dim3(kB), 0, s, w.keys2, w.vals2, w.head, w.ord, N, at->col, at->cov, mode == 1 ? 1 : 0, (int64_t)0,
+                       at->out_col, at->out_cov, pass ? w.flag : nullptr, pass ? w.off : nullptr, N);
   const bool post = post_crop != nullptr && !pass;  // flag / off are free when nothing passes through
   if (post) {
-    hipLaunchKernelGGL(k_mask_cnt, dim3(nb), dim3(kB), 0, s, *post_crop, d_opts, head, ord, N, N, 1, flag, blk);
-    const int rc = scan_flags_dev(flag, off, N, tmp, tb_scan, s, blk);
+    hipLaunchKernelGGL(k_mask_cnt, dim3(nb), dim3(kB), 0, s, *post_crop, d_opts, w.head, w.ord, N, N, 1, w.flag, blk);
+    const int rc = scan_flags_dev(w.flag, w.off, N, w.tmp, tb_scan, s, blk);
     if (rc != O3S_OK) return rc;
-    if (pm_xyzw) hipLaunchKernelGGL(k_compact_dual, dim3(nb), dim3(kB), 0, s, d_opts, d_on, N, flag, off, d_ppts, d_pn, pm_xyzw, pm_n);
-    else hipLaunchKernelGGL(k_compact, dim3(nb), dim3(kB), 0, s, d_opts, d_on, N, flag, off, d_ppts, d_pn, (int32_t*)nullptr);
+    if (pm_xyzw) hipLaunchKernelGGL(k_compact_dual, dim3(nb), dim3(kB), 0, s, d_opts, d_on, N, w.flag, w.off, d_ppts, d_pn, pm_xyzw, pm_n);
+    else hipLaunchKernelGGL(k_compact, dim3(nb), dim3(kB), 0, s, d_opts, d_on, N, w.flag, w.off, d_ppts, d_pn, (int32_t*)nullptr);
   } else if (post_crop) {
     return O3S_ERR_BAD_ARGUMENT;
   }
   const uint32_t seq = pa.mb.next();
-  hipLaunchKernelGGL(k_post_counts<false>, dim3(1), dim3(64), 0, s, status, pass ? flag : nullptr, pass ? off : nullptr, N, head, ord, N,
-                     post ? flag : nullptr, post ? off : nullptr, N, status + 4, pa.mb.dev, seq);
+  hipLaunchKernelGGL(k_post_counts<false>, dim3(1), dim3(64), 0, s, w.status, pass ? w.flag : nullptr, pass ? w.off : nullptr, N, w.head, w.ord, N,
+                     post ? w.flag : nullptr, post ? w.off : nullptr, N, w.status + 4, pa.mb.dev, seq);
   CK(hipGetLastError());
   uint32_t r[4];
-  if (fetch_post(pa.mb, seq, s, r, 4, kPostVals, status + 4, pa.p) == kPollError) return O3S_ERR_HIP;
+  if (fetch_post(pa.mb, seq, s, r, 4, kPostVals, w.status + 4, pa.p) == kPollError) return O3S_ERR_HIP;
   if (r[0] != 0u) return O3S_OK;  // *ok stays false
   counts[0] = (int64_t)r[1];
   counts[1] = (int64_t)r[2];
@@ -1125,13 +1158,38 @@ inline size_t merge_temp_bytes(int64_t n1, int64_t n2) {
                        (const uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n1, (size_t)n2, rocprim::less<uint64_t>(), nullptr);
   return bytes;
 }
-inline size_t insert_merge_arena_bytes(int64_t n_tmp, int64_t n_v, int64_t n_s) {
-  const size_t nt = (size_t)n_tmp, nv = (size_t)std::max<int64_t>(n_v, 1), ns = (size_t)std::max<int64_t>(n_s, 1), nm = nv + ns;
-  return Arena::pad(nt * 4) + Arena::pad((nt + 1) * 4) + Arena::pad(256)                      // flag, off, status
-         + Arena::pad(nv * 8) + Arena::pad(nv * 4) + 2 * Arena::pad(ns * 8) + 2 * Arena::pad(ns * 4)  // A, U, U sorted
-         + Arena::pad(nm * 8) + Arena::pad(nm * 4) + Arena::pad(nm * 4) + Arena::pad((nm + 1) * 4)   // merged keys / vals, head, ord
-         + Arena::pad(std::max(std::max(scan_temp_bytes(n_tmp), sort_temp_bytes(n_s)), merge_temp_bytes(n_v, n_s))) + 4096;
-}
+// work area of the insert by merge: n_tmp points in all, n_v old voxel points (A), n_s scan points (U), both merged (M)
+struct InsertMergeArea {
+  static constexpr size_t kSlack = 4096;
+  uint32_t *flag, *off, *status;
+  uint64_t* keysA;
+  uint32_t* valsA;
+  uint64_t *keysU, *keysU2;
+  uint32_t *valsU, *valsU2;
+  uint64_t* keysM;
+  uint32_t *valsM, *head, *ord;
+  char* tmp;  // also the flag producers' per-block counts `blk` (room: scan_temp_bytes), consumed by the scan right behind
+  template <class A>
+  void lay(A& a, size_t n_tmp, size_t n_v, size_t n_s, size_t tb_scan, size_t tb_sort, size_t tb_merge) {
+    // at least one element each: the pipeline never runs with less, and a reservation ahead of the first insert
+    // (o3s_submap_reserve(0)) has always been sized so
+    const size_t nv = std::max<size_t>(n_v, 1), ns = std::max<size_t>(n_s, 1), nm = nv + ns;
+    take(a, flag, n_tmp);
+    take(a, off, n_tmp + 1);
+    take(a, status, 64);
+    take(a, keysA, nv);
+    take(a, valsA, nv);
+    take(a, keysU, ns);
+    take(a, keysU2, ns);
+    take(a, valsU, ns);
+    take(a, valsU2, ns);
+    take(a, keysM, nm);
+    take(a, valsM, nm);
+    take(a, head, nm);
+    take(a, ord, nm + 1);
+    take(a, tmp, std::max(std::max(tb_scan, tb_sort), tb_merge));
+  }
+};
 
 // d_pts / d_nrm: [PT_old (n_pt) | V_old (n_old - n_pt) | appended scan (n_tmp - n_old)].  counts[0..1] = pass-through points,
 // voxels.  *ok = false: a condition above failed (or an index fell outside the hint, or the mailbox is off) — nothing usable
@@ -1158,61 +1216,48 @@ inline int voxel_insert_merge_dev(Arena& ar, const o3s_cropper& crop, const VoxH
   PinnedArea& pa = pinned_area();
   const int64_t n_v = n_old - n_pt, n_s = n_tmp - n_old;
   if (n_v <= 0 || n_s <= 0 || n_pt < 0 || n_tmp > (int64_t)0x7fffffff || h.bits > 58 || !mailbox_enabled(pa)) return O3S_OK;
-  CK(ar.reserve(insert_merge_arena_bytes(n_tmp, n_v, n_s)));
   const int64_t n_m = n_v + n_s;
-  uint32_t* flag = ar.take<uint32_t>((size_t)n_tmp);
-  uint32_t* off = ar.take<uint32_t>((size_t)n_tmp + 1);
-  uint32_t* status = ar.take<uint32_t>(64);
-  uint64_t* keysA = ar.take<uint64_t>((size_t)n_v);
-  uint32_t* valsA = ar.take<uint32_t>((size_t)n_v);
-  uint64_t* keysU = ar.take<uint64_t>((size_t)n_s);
-  uint64_t* keysU2 = ar.take<uint64_t>((size_t)n_s);
-  uint32_t* valsU = ar.take<uint32_t>((size_t)n_s);
-  uint32_t* valsU2 = ar.take<uint32_t>((size_t)n_s);
-  uint64_t* keysM = ar.take<uint64_t>((size_t)n_m);
-  uint32_t* valsM = ar.take<uint32_t>((size_t)n_m);
-  uint32_t* head = ar.take<uint32_t>((size_t)n_m);
-  uint32_t* ord = ar.take<uint32_t>((size_t)n_m + 1);
   const size_t tb_scan = scan_temp_bytes(n_tmp), tb_sort = sort_temp_bytes(n_s), tb_merge = merge_temp_bytes(n_v, n_s);
-  void* tmp = ar.take<char>(std::max(std::max(tb_scan, tb_sort), tb_merge));
+  InsertMergeArea w;
+  CK(lay_out(ar, w, (size_t)n_tmp, (size_t)n_v, (size_t)n_s, tb_scan, tb_sort, tb_merge));
   const unsigned nb = nblk(n_tmp);
   const uint64_t sentinel = 1ull << (h.bits + 2);
   // pass-through points: outside the volume, emitted first in input order (helpers.cpp:162-176)
-  uint32_t* blk = reinterpret_cast<uint32_t*>(tmp);  // per-block counts of the flag producers (room: scan_temp_bytes), consumed by the scan right behind
-  hipLaunchKernelGGL(k_mask, dim3(nb), dim3(kB), 0, s, crop, d_pts, n_tmp, 0, flag, status, blk);
+  uint32_t* blk = reinterpret_cast<uint32_t*>(w.tmp);  // per-block counts of the flag producers (room: scan_temp_bytes), consumed by the scan right behind
+  hipLaunchKernelGGL(k_mask, dim3(nb), dim3(kB), 0, s, crop, d_pts, n_tmp, 0, w.flag, w.status, blk);
   {
-    const int rc = scan_flags_dev(flag, off, n_tmp, tmp, tb_scan, s, blk);
+    const int rc = scan_flags_dev(w.flag, w.off, n_tmp, w.tmp, tb_scan, s, blk);
     if (rc != O3S_OK) return rc;
   }
-  hipLaunchKernelGGL(k_insert_split, dim3(nb), dim3(kB), 0, s, d_pts, d_nrm, n_pt, n_old, n_tmp, flag, off, 1.0 / voxel, h, sentinel, keysA, valsA, keysU,
-                     valsU, status, d_opts, d_on);
-  hipLaunchKernelGGL(k_check_increasing, dim3(nblk(n_v)), dim3(kB), 0, s, keysA, n_v, sentinel, status);
+  hipLaunchKernelGGL(k_insert_split, dim3(nb), dim3(kB), 0, s, d_pts, d_nrm, n_pt, n_old, n_tmp, w.flag, w.off, 1.0 / voxel, h, sentinel, w.keysA, w.valsA, w.keysU,
+                     w.valsU, w.status, d_opts, d_on);
+  hipLaunchKernelGGL(k_check_increasing, dim3(nblk(n_v)), dim3(kB), 0, s, w.keysA, n_v, sentinel, w.status);
   {
     size_t tb = tb_sort;
-    CK(sort_pairs(tmp, tb, keysU, keysU2, valsU, valsU2, (size_t)n_s, h.bits + 3, s));
+    CK(sort_pairs(w.tmp, tb, w.keysU, w.keysU2, w.valsU, w.valsU2, (size_t)n_s, h.bits + 3, s));
     size_t tm = tb_merge;
-    CK(rocprim::merge(tmp, tm, keysA, keysU2, keysM, valsA, valsU2, valsM, (size_t)n_v, (size_t)n_s, rocprim::less<uint64_t>(), s));
+    CK(rocprim::merge(w.tmp, tm, w.keysA, w.keysU2, w.keysM, w.valsA, w.valsU2, w.valsM, (size_t)n_v, (size_t)n_s, rocprim::less<uint64_t>(), s));
   }
-  hipLaunchKernelGGL(k_heads, dim3(nblk(n_m)), dim3(kB), 0, s, keysM, n_m, sentinel, head, 2, blk);
+  hipLaunchKernelGGL(k_heads, dim3(nblk(n_m)), dim3(kB), 0, s, w.keysM, n_m, sentinel, w.head, 2, blk);
   {
-    const int rc = scan_flags_dev(head, ord, n_m, tmp, tb_scan, s, blk);
+    const int rc = scan_flags_dev(w.head, w.ord, n_m, w.tmp, tb_scan, s, blk);
     if (rc != O3S_OK) return rc;
   }
-  hipLaunchKernelGGL(k_vox_reduce, dim3(nblk(n_m)), dim3(kB), 0, s, keysM, valsM, head, ord, n_m, d_pts, d_nrm, (const int32_t*)nullptr, 1, 1, (int64_t)0,
-                     d_opts, d_on, (int32_t*)nullptr, flag, off, n_tmp, 2);
+  hipLaunchKernelGGL(k_vox_reduce, dim3(nblk(n_m)), dim3(kB), 0, s, w.keysM, w.valsM, w.head, w.ord, n_m, d_pts, d_nrm, (const int32_t*)nullptr, 1, 1, (int64_t)0,
+                     d_opts, d_on, (int32_t*)nullptr, w.flag, w.off, n_tmp, 2);
   if (lazy) {
-    hipLaunchKernelGGL(k_post_counts<true>, dim3(1), dim3(64), 0, s, status, flag, off, n_tmp, head, ord, n_m, (const uint32_t*)nullptr,
+    hipLaunchKernelGGL(k_post_counts<true>, dim3(1), dim3(64), 0, s, w.status, w.flag, w.off, n_tmp, w.head, w.ord, n_m, (const uint32_t*)nullptr,
                        (const uint32_t*)nullptr, (int64_t)0, lazy->dev_out, lazy->mb_dev, lazy->seq);
     CK(hipGetLastError());
     if (issued) *issued = true;
     return O3S_OK;
   }
   const uint32_t seq = pa.mb.next();
-  hipLaunchKernelGGL(k_post_counts<false>, dim3(1), dim3(64), 0, s, status, flag, off, n_tmp, head, ord, n_m, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
-                     (int64_t)0, status + 4, pa.mb.dev, seq);
+  hipLaunchKernelGGL(k_post_counts<false>, dim3(1), dim3(64), 0, s, w.status, w.flag, w.off, n_tmp, w.head, w.ord, n_m, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
+                     (int64_t)0, w.status + 4, pa.mb.dev, seq);
   CK(hipGetLastError());
   uint32_t r[4];
-  if (fetch_post(pa.mb, seq, s, r, 4, kPostVals, status + 4, pa.p) == kPollError) return O3S_ERR_HIP;
+  if (fetch_post(pa.mb, seq, s, r, 4, kPostVals, w.status + 4, pa.p) == kPollError) return O3S_ERR_HIP;
   if (r[0] != 0u) return O3S_OK;  // *ok stays false
   counts[0] = (int64_t)r[1];
   counts[1] = (int64_t)r[2];

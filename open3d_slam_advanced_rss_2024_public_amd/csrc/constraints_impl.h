@@ -17,15 +17,43 @@ namespace o3s_cloud {
 
 constexpr int64_t kOcChunkPoints = (int64_t)1 << 29;  // points of one sequence of launches: 32-bit bases, table offsets and block numbers
 
-struct OcLayout {  // sizes of one chunk, from the host's view of its pairs
+struct OcSizes {  // sizes of one chunk, from the host's view of its pairs
   uint32_t slots = 0, n_buckets = 0, blocks_all = 0, blocks_src = 0;
   int64_t G = 0, Mt = 0;
   size_t tb_sort = 0;
-  size_t bytes(int m) const {
-    return Arena::pad((size_t)m * sizeof(OcPair)) + Arena::pad((size_t)slots * sizeof(OvSlot)) + 2 * Arena::pad((size_t)G * 4) +
-           Arena::pad((size_t)(3 * m + 1) * 4) + Arena::pad((size_t)blocks_all * 4) + 2 * Arena::pad((size_t)Mt * 8) + 2 * Arena::pad((size_t)Mt * 4) + Arena::pad(tb_sort) +
-           Arena::pad((size_t)n_buckets * 8) + Arena::pad((size_t)Mt * sizeof(OcRec)) + Arena::pad((size_t)kOcComps * blocks_src * 8) +
-           Arena::pad((size_t)m * kOcComps * 8) + 4096;
+};
+// work area of one chunk of m pairs
+struct OcArea {
+  static constexpr size_t kSlack = 4096;
+  OcPair* d_pairs;
+  OvSlot* tab;
+  uint32_t *slot_of, *flag;
+  uint32_t* err;  // a bad coordinate per pair [m], a table slice is full [1], the selection sizes [2 m]
+  uint32_t* cnt(int m) const { return err + (m + 1); }  // ... the selection sizes
+  uint32_t* blk_cnt;
+  uint64_t *k1, *k2;
+  uint32_t *v1, *v2;
+  char* tmp;
+  uint2* range;
+  OcRec* rec;
+  double *part, *sums;
+  template <class A>
+  void lay(A& a, int m, const OcSizes& L) {
+    take(a, d_pairs, (size_t)m);
+    take(a, tab, (size_t)L.slots);
+    take(a, slot_of, (size_t)L.G);
+    take(a, flag, (size_t)L.G);
+    take(a, err, (size_t)(3 * m + 1));
+    take(a, blk_cnt, (size_t)L.blocks_all);
+    take(a, k1, (size_t)L.Mt);
+    take(a, k2, (size_t)L.Mt);
+    take(a, v1, (size_t)L.Mt);
+    take(a, v2, (size_t)L.Mt);
+    take(a, tmp, L.tb_sort);
+    take(a, range, (size_t)L.n_buckets);
+    take(a, rec, (size_t)L.Mt);
+    take(a, part, (size_t)kOcComps * L.blocks_src);
+    take(a, sums, (size_t)m * kOcComps);
   }
 };
 
@@ -35,7 +63,7 @@ int oc_run_chunk(RegArea& area, const std::vector<int32_t>& idx, const o3s_subma
   const int m = (int)idx.size();
   std::vector<OcPair> pairs((size_t)m);
   for (int attempt = 0;; ++attempt) {
-    OcLayout L;
+    OcSizes L;
     bool all_full_size = true;
     for (int k = 0; k < m; ++k) {
       const o3s_submap *src = sources[idx[(size_t)k]], *tgt = targets[idx[(size_t)k]];
@@ -68,24 +96,8 @@ int oc_run_chunk(RegArea& area, const std::vector<int32_t>& idx, const o3s_subma
     while ((int64_t)L.n_buckets < L.Mt && L.n_buckets < (1u << 31)) L.n_buckets <<= 1;
     L.tb_sort = sort_temp_bytes(L.Mt);
 
-    CK(area.ov.arena.reserve(L.bytes(m)));
-    Arena& ar = area.ov.arena;
-    OcPair* d_pairs = ar.take<OcPair>((size_t)m);
-    OvSlot* tab = ar.take<OvSlot>((size_t)L.slots);
-    uint32_t* slot_of = ar.take<uint32_t>((size_t)L.G);
-    uint32_t* flag = ar.take<uint32_t>((size_t)L.G);
-    uint32_t* err = ar.take<uint32_t>((size_t)(3 * m + 1));  // a bad coordinate per pair [m], a table slice is full [1], the selection sizes [2 m]
-    uint32_t* cnt = err + (m + 1);
-    uint32_t* blk_cnt = ar.take<uint32_t>((size_t)L.blocks_all);
-    uint64_t* k1 = ar.take<uint64_t>((size_t)L.Mt);
-    uint64_t* k2 = ar.take<uint64_t>((size_t)L.Mt);
-    uint32_t* v1 = ar.take<uint32_t>((size_t)L.Mt);
-    uint32_t* v2 = ar.take<uint32_t>((size_t)L.Mt);
-    void* tmp = ar.take<char>(L.tb_sort);
-    uint2* range = ar.take<uint2>((size_t)L.n_buckets);
-    OcRec* rec = ar.take<OcRec>((size_t)L.Mt);
-    double* part = ar.take<double>((size_t)kOcComps * L.blocks_src);
-    double* sums = ar.take<double>((size_t)m * kOcComps);
+    OcArea w;
+    CK(lay_out(area.ov.arena, w, m, L));
     // the host's block: pinned, mapped, grow-only (a pinned allocation takes milliseconds: once per size)
     const size_t res_bytes = (size_t)m * kOcRes * 8;
     if (!area.oc_res || area.oc_res_bytes < res_bytes) {
@@ -95,25 +107,25 @@ int oc_run_chunk(RegArea& area, const std::vector<int32_t>& idx, const o3s_subma
       area.oc_res_bytes = res_bytes + res_bytes / 2;
     }
 
-    CK(hipMemcpyAsync(d_pairs, pairs.data(), (size_t)m * sizeof(OcPair), hipMemcpyHostToDevice, s));  // pageable source: staged before the call returns
-    CK(hipMemsetAsync(tab, 0, (size_t)L.slots * sizeof(OvSlot), s));
-    CK(hipMemsetAsync(err, 0, (size_t)(3 * m + 1) * 4, s));
-    CK(hipMemsetAsync(range, 0, (size_t)L.n_buckets * 8, s));
-    hipLaunchKernelGGL(k_oc_count, dim3(L.blocks_all), dim3(kB), 0, s, (const OcPair*)d_pairs, m, 1.0 / voxel, tab, slot_of, err);
-    hipLaunchKernelGGL(k_oc_flag, dim3(L.blocks_all), dim3(kB), 0, s, (const OcPair*)d_pairs, m, (const OvSlot*)tab, (const uint32_t*)slot_of, min_pts, max_dist,
-                       L.n_buckets, flag, blk_cnt, k1, v1);
+    CK(hipMemcpyAsync(w.d_pairs, pairs.data(), (size_t)m * sizeof(OcPair), hipMemcpyHostToDevice, s));  // pageable source: staged before the call returns
+    CK(hipMemsetAsync(w.tab, 0, (size_t)L.slots * sizeof(OvSlot), s));
+    CK(hipMemsetAsync(w.err, 0, (size_t)(3 * m + 1) * 4, s));
+    CK(hipMemsetAsync(w.range, 0, (size_t)L.n_buckets * 8, s));
+    hipLaunchKernelGGL(k_oc_count, dim3(L.blocks_all), dim3(kB), 0, s, (const OcPair*)w.d_pairs, m, 1.0 / voxel, w.tab, w.slot_of, w.err);
+    hipLaunchKernelGGL(k_oc_flag, dim3(L.blocks_all), dim3(kB), 0, s, (const OcPair*)w.d_pairs, m, (const OvSlot*)w.tab, (const uint32_t*)w.slot_of, min_pts, max_dist,
+                       L.n_buckets, w.flag, w.blk_cnt, w.k1, w.v1);
     CK(hipGetLastError());
     size_t stb = L.tb_sort;
-    CK(sort_pairs(tmp, stb, k1, k2, v1, v2, (size_t)L.Mt, key_bits((uint64_t)L.n_buckets + 1u), s));
-    hipLaunchKernelGGL(k_oc_heads, dim3(nblk(L.Mt)), dim3(kB), 0, s, (const uint64_t*)k2, (const uint32_t*)v2, L.Mt, L.n_buckets, (const OcPair*)d_pairs, m, range,
-                       rec);
-    hipLaunchKernelGGL(k_oc_search, dim3(L.blocks_src), dim3(kB), 0, s, (const OcPair*)d_pairs, m, (const uint32_t*)flag, (const uint2*)range, (const OcRec*)rec,
-                       L.n_buckets - 1u, max_dist, max_dist * max_dist, part);
-    hipLaunchKernelGGL(k_oc_fold, dim3((unsigned)(m * kOcFolds)), dim3(64), 0, s, (const OcPair*)d_pairs, (const double*)part, L.blocks_src, (const uint32_t*)blk_cnt, sums,
-                       cnt);
+    CK(sort_pairs(w.tmp, stb, w.k1, w.k2, w.v1, w.v2, (size_t)L.Mt, key_bits((uint64_t)L.n_buckets + 1u), s));
+    hipLaunchKernelGGL(k_oc_heads, dim3(nblk(L.Mt)), dim3(kB), 0, s, (const uint64_t*)w.k2, (const uint32_t*)w.v2, L.Mt, L.n_buckets, (const OcPair*)w.d_pairs, m, w.range,
+                       w.rec);
+    hipLaunchKernelGGL(k_oc_search, dim3(L.blocks_src), dim3(kB), 0, s, (const OcPair*)w.d_pairs, m, (const uint32_t*)w.flag, (const uint2*)w.range, (const OcRec*)w.rec,
+                       L.n_buckets - 1u, max_dist, max_dist * max_dist, w.part);
+    hipLaunchKernelGGL(k_oc_fold, dim3((unsigned)(m * kOcFolds)), dim3(64), 0, s, (const OcPair*)w.d_pairs, (const double*)w.part, L.blocks_src, (const uint32_t*)w.blk_cnt, w.sums,
+                       w.cnt(m));
     PinnedArea& pa = pinned_area();
     const uint32_t seq = mailbox_open(pa);
-    hipLaunchKernelGGL(k_oc_post, dim3(1), dim3(64), 0, s, m, (const double*)sums, (const uint32_t*)cnt, (const uint32_t*)err,
+    hipLaunchKernelGGL(k_oc_post, dim3(1), dim3(64), 0, s, m, (const double*)w.sums, (const uint32_t*)w.cnt(m), (const uint32_t*)w.err,
                        reinterpret_cast<unsigned long long*>(area.oc_res.dev), seq ? pa.mb.dev : (uint32_t*)nullptr, seq);
     CK(hipGetLastError());
     uint32_t full_word = 0;

@@ -524,27 +524,75 @@ int dm_reserve(o3s_dense_map* m, int64_t add) {
   return O3S_OK;
 }
 
-// keys of a device cloud, stably sorted; returns the sorted keys / values inside the arena
-int dm_sorted_keys(o3s_dense_map* m, const double* d_pts, int64_t N, size_t extra_bytes, uint64_t** skeys, uint32_t** svals, void** tmp,
-                   size_t* tmp_bytes) {
+// work area of an insert: the keys of n points and their stable sort (tb: room for the sort and for a scan of n flags)
+struct DmSortArea {
+  static constexpr size_t kSlack = 4096;
+  uint64_t *keys, *skeys;  // s...: sorted
+  uint32_t *vals, *svals;
+  char* tmp;
+  template <class A>
+  void lay(A& a, size_t n, size_t tb) {
+    take(a, keys, n);
+    take(a, skeys, n);
+    take(a, vals, n);
+    take(a, svals, n);
+    take(a, tmp, tb);
+  }
+};
+// work area of carving: the sorted scan keys, then the first point of each scan voxel, the removal marks of a table of
+// `cap` slots and the two arrays of the occupancy filter
+struct DmCarveArea {
+  static constexpr size_t kSlack = DmSortArea::kSlack;
+  DmSortArea sort;
+  uint32_t *head, *ord, *first;
+  uint8_t* rm;
+  unsigned long long* words;  // two arrays of nwords
+  template <class A>
+  void lay(A& a, size_t n, size_t tb, size_t cap, size_t nwords) {
+    sort.lay(a, n, tb);
+    take(a, head, n);
+    take(a, ord, n + 1);
+    take(a, first, n);
+    take(a, rm, cap);
+    take(a, words, nwords * 2);
+  }
+};
+// work area of the export: the live slots of a table of `cap`, the sort of the v live voxels by key, and what is emitted
+struct DmExportArea {
+  static constexpr size_t kSlack = 4096;
+  uint32_t *flag, *off;
+  uint64_t *k1, *k2;
+  uint32_t *s1, *s2;
+  char* tmp;
+  double *op, *on;
+  int32_t *ok, *oc;
+  double* ocol = nullptr;  // only when colours are asked for
+  template <class A>
+  void lay(A& a, size_t cap, size_t v, size_t tb, bool colors) {
+    take(a, flag, cap);
+    take(a, off, cap + 1);
+    take(a, k1, v);
+    take(a, k2, v);
+    take(a, s1, v);
+    take(a, s2, v);
+    take(a, tmp, tb);
+    take(a, op, v * 3);
+    take(a, on, v * 3);
+    take(a, ok, v * 3);
+    take(a, oc, v);
+    if (colors) take(a, ocol, v * 3);
+  }
+};
+inline size_t dm_sort_temp_bytes(int64_t N) { return std::max(sort_temp_bytes(N), scan_temp_bytes(N)); }
+
+// keys of a device cloud, stably sorted, in a work area laid out for N points and tb = dm_sort_temp_bytes(N)
+int dm_sorted_keys(o3s_dense_map* m, const double* d_pts, int64_t N, const DmSortArea& w, size_t tb) {
   hipStream_t s = m->stream;
-  const size_t n = (size_t)N;
-  const size_t tb = std::max(sort_temp_bytes(N), scan_temp_bytes(N));
-  CK(m->arena.reserve(2 * Arena::pad(n * 8) + 2 * Arena::pad(n * 4) + Arena::pad(tb) + extra_bytes + 4096));
-  uint64_t* k1 = m->arena.take<uint64_t>(n);
-  uint64_t* k2 = m->arena.take<uint64_t>(n);
-  uint32_t* v1 = m->arena.take<uint32_t>(n);
-  uint32_t* v2 = m->arena.take<uint32_t>(n);
-  *tmp = m->arena.take<char>(tb);
-  *tmp_bytes = tb;
   CK(m->d_ctr.ensure(64, 0, s));
   CK(hipMemsetAsync(m->d_ctr.p, 0, 64, s));
   uint32_t* ctr = reinterpret_cast<uint32_t*>(m->d_ctr.p);
-  hipLaunchKernelGGL(k_dm_keys, dim3(nblk(N)), dim3(kB), 0, s, d_pts, N, m->inv, k1, v1, ctr + 8);
-  size_t stb = tb;
-  CK(rocprim::radix_sort_pairs(*tmp, stb, k1, k2, v1, v2, n, 0, 64, s));
-  *skeys = k2;
-  *svals = v2;
+  hipLaunchKernelGGL(k_dm_keys, dim3(nblk(N)), dim3(kB), 0, s, d_pts, N, m->inv, w.keys, w.vals, ctr + 8);
+  CK(rocprim::radix_sort_pairs(w.tmp, tb, w.keys, w.skeys, w.vals, w.svals, (size_t)N, 0, 64, s));
   return O3S_OK;
 }
 
@@ -573,11 +621,10 @@ int dm_insert_dev(o3s_dense_map* m, const double* d_pts, const double* d_nrm, co
   hipStream_t s = m->stream;
   int rc = dm_reserve(m, N);
   if (rc != O3S_OK) return rc;
-  uint64_t* sk = nullptr;
-  uint32_t* sv = nullptr;
-  void* tmp = nullptr;
-  size_t tb = 0;
-  rc = dm_sorted_keys(m, d_pts, N, 0, &sk, &sv, &tmp, &tb);
+  const size_t tb = dm_sort_temp_bytes(N);
+  DmSortArea w;
+  CK(lay_out(m->arena, w, (size_t)N, tb));
+  rc = dm_sorted_keys(m, d_pts, N, w, tb);
   if (rc != O3S_OK) return rc;
   uint32_t ctr[16];
   rc = dm_read_counters(m, ctr);  // the range check has to be known before the table is touched
@@ -588,10 +635,10 @@ int dm_insert_dev(o3s_dense_map* m, const double* d_pts, const double* d_nrm, co
     if (rc != O3S_OK) return rc;
   }
   if (m->csum.p) {
-    hipLaunchKernelGGL(k_dm_insert<true>, dim3(nblk(N)), dim3(kB), 0, s, sk, sv, N, d_pts, d_nrm, d_col, m->K(), m->C(), m->S(), m->CS(),
+    hipLaunchKernelGGL(k_dm_insert<true>, dim3(nblk(N)), dim3(kB), 0, s, w.skeys, w.svals, N, d_pts, d_nrm, d_col, m->K(), m->C(), m->S(), m->CS(),
                        (uint64_t)(m->cap - 1), reinterpret_cast<uint32_t*>(m->d_ctr.p));
   } else {
-    hipLaunchKernelGGL(k_dm_insert<false>, dim3(nblk(N)), dim3(kB), 0, s, sk, sv, N, d_pts, d_nrm, (const double*)nullptr, m->K(), m->C(),
+    hipLaunchKernelGGL(k_dm_insert<false>, dim3(nblk(N)), dim3(kB), 0, s, w.skeys, w.svals, N, d_pts, d_nrm, (const double*)nullptr, m->K(), m->C(),
                        m->S(), (double*)nullptr, (uint64_t)(m->cap - 1), reinterpret_cast<uint32_t*>(m->d_ctr.p));
   }
   CK(hipGetLastError());
@@ -638,42 +685,35 @@ int dm_carve_dev(o3s_dense_map* m, const o3s_dense_carving_params* p, const doub
     off.d[off.n++] = d;
   }
   hipStream_t s = m->stream;
-  const size_t n = (size_t)N, cap = (size_t)m->cap;
-  uint64_t* sk = nullptr;
-  uint32_t* sv = nullptr;
-  void* tmp = nullptr;
-  size_t tb = 0;
+  const size_t cap = (size_t)m->cap;
   int64_t nwords = 4096;  // about one word per four voxels: a few MB, L2 / Infinity-Cache resident
   while (nwords * 4 < m->live) nwords <<= 1;
-  int rc = dm_sorted_keys(m, d_scan, N, 2 * Arena::pad(n * 4) + Arena::pad((n + 1) * 4) + Arena::pad(cap) + Arena::pad((size_t)nwords * 16), &sk, &sv,
-                          &tmp, &tb);
+  const size_t tb = dm_sort_temp_bytes(N);
+  DmCarveArea w;
+  CK(lay_out(m->arena, w, (size_t)N, tb, cap, (size_t)nwords));
+  int rc = dm_sorted_keys(m, d_scan, N, w.sort, tb);
   if (rc != O3S_OK) return rc;
-  uint32_t* head = m->arena.take<uint32_t>(n);
-  uint32_t* ord = m->arena.take<uint32_t>(n + 1);
-  uint32_t* first = m->arena.take<uint32_t>(n);
-  uint8_t* rm = m->arena.take<uint8_t>(cap);
-  unsigned long long* words = m->arena.take<unsigned long long>((size_t)nwords * 2);  // two arrays of nwords
-  CK(hipMemsetAsync(words, 0, (size_t)nwords * 16, s));
-  hipLaunchKernelGGL(k_dm_build_filter, dim3(nblk(m->cap)), dim3(kB), 0, s, m->K(), m->cap, words, (uint64_t)(nwords - 1));
-  hipLaunchKernelGGL(k_dm_heads, dim3(nblk(N)), dim3(kB), 0, s, sk, N, head);
+  CK(hipMemsetAsync(w.words, 0, (size_t)nwords * 16, s));
+  hipLaunchKernelGGL(k_dm_build_filter, dim3(nblk(m->cap)), dim3(kB), 0, s, m->K(), m->cap, w.words, (uint64_t)(nwords - 1));
+  hipLaunchKernelGGL(k_dm_heads, dim3(nblk(N)), dim3(kB), 0, s, w.sort.skeys, N, w.head);
   int64_t n_first = 0;
-  rc = scan_flags(head, ord, N, tmp, tb, &n_first, s);
+  rc = scan_flags(w.head, w.ord, N, w.sort.tmp, tb, &n_first, s);
   if (rc != O3S_OK) return rc;
   uint32_t ctr[16];
   rc = dm_read_counters(m, ctr);
   if (rc != O3S_OK) return rc;
   if (ctr[8]) return O3S_ERR_BAD_ARGUMENT;  // a NaN / out-of-range scan point has no voxel key
   if (n_first == 0) return O3S_OK;
-  hipLaunchKernelGGL(k_dm_first, dim3(nblk(N)), dim3(kB), 0, s, sv, head, ord, N, first);
-  CK(hipMemsetAsync(rm, 0, cap, s));
+  hipLaunchKernelGGL(k_dm_first, dim3(nblk(N)), dim3(kB), 0, s, w.sort.svals, w.head, w.ord, N, w.first);
+  CK(hipMemsetAsync(w.rm, 0, cap, s));
   {
     // sqrt(v) <= radius is certain below r2lo and impossible above r2hi (sqrt is monotone and correctly rounded)
     const double r2 = radius * radius, r2lo = r2 * (1.0 - 1.0e-14), r2hi = r2 * (1.0 + 1.0e-14);
     const dim3 grid(nblk(n_first * kDmRayLanes)), block(kB);
 #define O3S_DM_CARVE(NX)                                                                                                                     \
-  hipLaunchKernelGGL(k_dm_carve_rays<NX>, grid, block, 0, s, d_scan, first, n_first, sensor[0], sensor[1], sensor[2], m->voxel, radius, r2lo, r2hi, \
+  hipLaunchKernelGGL(k_dm_carve_rays<NX>, grid, block, 0, s, d_scan, w.first, n_first, sensor[0], sensor[1], sensor[2], m->voxel, radius, r2lo, r2hi, \
                      step, p->max_raytracing_length, p->truncation_distance, off, m->K(), (uint64_t)(m->cap - 1),                            \
-                     reinterpret_cast<const uint64_t*>(words), (uint64_t)(nwords - 1), rm)
+                     reinterpret_cast<const uint64_t*>(w.words), (uint64_t)(nwords - 1), w.rm)
     switch (off.n) {
       case 1: O3S_DM_CARVE(1); break;
       case 2: O3S_DM_CARVE(2); break;
@@ -693,7 +733,7 @@ int dm_carve_dev(o3s_dense_map* m, const o3s_dense_carving_params* p, const doub
 #endif
   }
   CK(hipMemsetAsync(m->d_ctr.p, 0, 64, s));
-  hipLaunchKernelGGL(k_dm_apply_remove, dim3(nblk(m->cap / 8)), dim3(kB), 0, s, rm, m->K(), m->cap, reinterpret_cast<uint32_t*>(m->d_ctr.p));
+  hipLaunchKernelGGL(k_dm_apply_remove, dim3(nblk(m->cap / 8)), dim3(kB), 0, s, w.rm, m->K(), m->cap, reinterpret_cast<uint32_t*>(m->d_ctr.p));
   CK(hipGetLastError());
   rc = dm_read_counters(m, ctr);
   if (rc != O3S_OK) return rc;
@@ -802,15 +842,13 @@ int dm_insert_scan_dev(o3s_dense_map* m, const o3s_cropper* dense_map_cropper, c
       if (rc != O3S_OK) return rc;
     } else {  // the volume crop and colorCropper_.crop (Submap.cpp:101) as one flag pass, one scan, one scatter
       CK(m->crop_c.ensure((size_t)N * 24, 0, s));
-      CK(m->arena.reserve(crop_arena_bytes(N)));
-      uint32_t* flag = m->arena.take<uint32_t>((size_t)N);
-      uint32_t* off = m->arena.take<uint32_t>((size_t)N + 1);
       const size_t tb = scan_temp_bytes(N);
-      void* tmp = m->arena.take<char>(tb);
-      hipLaunchKernelGGL(k_dm_color_mask, dim3(nblk(N)), dim3(kB), 0, s, c, 1, d_raw_p, d_raw_c, N, rgb, flag);
-      rc = scan_flags(flag, off, N, tmp, tb, &kept, s);
+      CropArea w;
+      CK(lay_out(m->arena, w, (size_t)N, tb));
+      hipLaunchKernelGGL(k_dm_color_mask, dim3(nblk(N)), dim3(kB), 0, s, c, 1, d_raw_p, d_raw_c, N, rgb, w.flag);
+      rc = scan_flags(w.flag, w.off, N, w.tmp, tb, &kept, s);
       if (rc != O3S_OK) return rc;
-      hipLaunchKernelGGL(k_dm_compact_col, dim3(nblk(N)), dim3(kB), 0, s, d_raw_p, d_raw_n, d_raw_c, N, flag, off, m->crop_p.as<double>(),
+      hipLaunchKernelGGL(k_dm_compact_col, dim3(nblk(N)), dim3(kB), 0, s, d_raw_p, d_raw_n, d_raw_c, N, w.flag, w.off, m->crop_p.as<double>(),
                          m->crop_n.as<double>(), m->crop_c.as<double>());
       CK(hipGetLastError());
     }
@@ -925,37 +963,25 @@ int o3s_dense_map_to_point_cloud_colored(const o3s_dense_map* m, double* pts, do
   hipStream_t s = m->stream;
   const size_t cap = (size_t)m->cap, v = (size_t)m->live;
   const size_t tb = std::max(scan_temp_bytes(m->cap), sort_temp_bytes(m->live));
-  CK(m->arena.reserve(Arena::pad(cap * 4) + Arena::pad((cap + 1) * 4) + 2 * Arena::pad(v * 8) + 2 * Arena::pad(v * 4) + Arena::pad(tb) +
-                      (colors ? 3 : 2) * Arena::pad(v * 24) + Arena::pad(v * 12) + Arena::pad(v * 4) + 4096));
-  uint32_t* flag = m->arena.take<uint32_t>(cap);
-  uint32_t* off = m->arena.take<uint32_t>(cap + 1);
-  uint64_t* k1 = m->arena.take<uint64_t>(v);
-  uint64_t* k2 = m->arena.take<uint64_t>(v);
-  uint32_t* s1 = m->arena.take<uint32_t>(v);
-  uint32_t* s2 = m->arena.take<uint32_t>(v);
-  void* tmp = m->arena.take<char>(tb);
-  double* op = m->arena.take<double>(v * 3);
-  double* on = m->arena.take<double>(v * 3);
-  int32_t* ok = m->arena.take<int32_t>(v * 3);
-  int32_t* oc = m->arena.take<int32_t>(v);
-  double* ocol = colors ? m->arena.take<double>(v * 3) : nullptr;
-  hipLaunchKernelGGL(k_dm_live, dim3(nblk(m->cap)), dim3(kB), 0, s, m->K(), m->C(), m->cap, flag);
+  DmExportArea w;
+  CK(lay_out(m->arena, w, cap, v, tb, colors != nullptr));
+  hipLaunchKernelGGL(k_dm_live, dim3(nblk(m->cap)), dim3(kB), 0, s, m->K(), m->C(), m->cap, w.flag);
   int64_t V = 0;
-  rc = scan_flags(flag, off, m->cap, tmp, tb, &V, s);
+  rc = scan_flags(w.flag, w.off, m->cap, w.tmp, tb, &V, s);
   if (rc != O3S_OK) return rc;
   if (V > m->live) return O3S_ERR_HIP;  // cannot happen: the host count tracks every claim and removal
   if (V == 0) return O3S_OK;
-  hipLaunchKernelGGL(k_dm_collect, dim3(nblk(m->cap)), dim3(kB), 0, s, m->K(), flag, off, m->cap, k1, s1);
+  hipLaunchKernelGGL(k_dm_collect, dim3(nblk(m->cap)), dim3(kB), 0, s, m->K(), w.flag, w.off, m->cap, w.k1, w.s1);
   size_t stb = tb;
-  CK(rocprim::radix_sort_pairs(tmp, stb, k1, k2, s1, s2, (size_t)V, 0, 64, s));
-  hipLaunchKernelGGL(k_dm_emit, dim3(nblk(V)), dim3(kB), 0, s, k2, s2, V, m->C(), m->S(), colors ? m->CS() : (const double*)nullptr, op, on, ocol, ok,
-                     oc);
+  CK(rocprim::radix_sort_pairs(w.tmp, stb, w.k1, w.k2, w.s1, w.s2, (size_t)V, 0, 64, s));
+  hipLaunchKernelGGL(k_dm_emit, dim3(nblk(V)), dim3(kB), 0, s, w.k2, w.s2, V, m->C(), m->S(), colors ? m->CS() : (const double*)nullptr, w.op, w.on, w.ocol, w.ok,
+                     w.oc);
   CK(hipGetLastError());
-  CK(hipMemcpyAsync(pts, op, (size_t)V * 24, hipMemcpyDeviceToHost, s));
-  if (normals) CK(hipMemcpyAsync(normals, on, (size_t)V * 24, hipMemcpyDeviceToHost, s));
-  if (colors) CK(hipMemcpyAsync(colors, ocol, (size_t)V * 24, hipMemcpyDeviceToHost, s));
-  if (keys) CK(hipMemcpyAsync(keys, ok, (size_t)V * 12, hipMemcpyDeviceToHost, s));
-  if (counts) CK(hipMemcpyAsync(counts, oc, (size_t)V * 4, hipMemcpyDeviceToHost, s));
+  CK(hipMemcpyAsync(pts, w.op, (size_t)V * 24, hipMemcpyDeviceToHost, s));
+  if (normals) CK(hipMemcpyAsync(normals, w.on, (size_t)V * 24, hipMemcpyDeviceToHost, s));
+  if (colors) CK(hipMemcpyAsync(colors, w.ocol, (size_t)V * 24, hipMemcpyDeviceToHost, s));
+  if (keys) CK(hipMemcpyAsync(keys, w.ok, (size_t)V * 12, hipMemcpyDeviceToHost, s));
+  if (counts) CK(hipMemcpyAsync(counts, w.oc, (size_t)V * 4, hipMemcpyDeviceToHost, s));
   CK(hipStreamSynchronize(s));
   if (n_out) *n_out = V;
   return O3S_OK;
@@ -1002,20 +1028,18 @@ int o3s_color_range_crop(int device, const double rgb_min[3], const double rgb_m
     CK(d_ocov.alloc((size_t)N * 72));
     CK(hipMemcpyAsync(d_cov.p, covariances, (size_t)N * 72, hipMemcpyHostToDevice, s));
   }
-  CK(ar.reserve(crop_arena_bytes(N)));
-  uint32_t* flag = ar.take<uint32_t>((size_t)N);
-  uint32_t* off = ar.take<uint32_t>((size_t)N + 1);
   const size_t tb = scan_temp_bytes(N);
-  void* tmp = ar.take<char>(tb);
+  CropArea w;
+  CK(lay_out(ar, w, (size_t)N, tb));
   hipLaunchKernelGGL(k_dm_color_mask, dim3(nblk(N)), dim3(kB), 0, s, o3s_cropper{}, 0, d_pts.as<double>(), d_col.as<double>(), N,
-                     dm_rgb(rgb_min, rgb_max), flag);
+                     dm_rgb(rgb_min, rgb_max), w.flag);
   int64_t kept = 0;
-  rc = scan_flags(flag, off, N, tmp, tb, &kept, s);
+  rc = scan_flags(w.flag, w.off, N, w.tmp, tb, &kept, s);
   if (rc != O3S_OK) return rc;
   hipLaunchKernelGGL(k_dm_compact_col, dim3(nblk(N)), dim3(kB), 0, s, d_pts.as<double>(), normals ? d_nrm.as<double>() : nullptr, d_col.as<double>(), N,
-                     flag, off, d_opts.as<double>(), d_on.as<double>(), d_ocol.as<double>());
+                     w.flag, w.off, d_opts.as<double>(), d_on.as<double>(), d_ocol.as<double>());
   if (covariances)
-    hipLaunchKernelGGL(k_compact_attr, dim3(nblk(N)), dim3(kB), 0, s, (const double*)nullptr, d_cov.as<double>(), N, flag, off, (double*)nullptr,
+    hipLaunchKernelGGL(k_compact_attr, dim3(nblk(N)), dim3(kB), 0, s, (const double*)nullptr, d_cov.as<double>(), N, w.flag, w.off, (double*)nullptr,
                        d_ocov.as<double>());
   CK(hipGetLastError());
   CK(hipStreamSynchronize(s));

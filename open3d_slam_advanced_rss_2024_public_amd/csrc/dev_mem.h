@@ -2,9 +2,13 @@
 // runtime header and the standard library: tests/cpp/dev_mem_cases.cpp compiles it against a stub of the four calls it makes.
 //
 // DevMem frees what it holds when it dies, is overwritten by a move, or is told to release(); it cannot be copied.  WHEN a block
-// grows and by how much is the caller's policy, spelled out by the three members below and by the types built on them (Arena in
-// cloud_dev.h, DevBuf in o3s_icp.hip): the capacities are visible through *_device_bytes and decide when the device stalls in a
+// grows and by how much is the caller's policy, spelled out by the members below and by the types built on them (Arena and DevBuf
+// further down): the capacities are visible through *_device_bytes and decide when the device stalls in a
 // hipFree / hipMalloc, so each policy is kept to the byte.
+//
+// HOW a block is carved up is said once per work area, by a layout (below, at Arena): the same description is measured on a
+// counting arena and laid out on the real one, so no size formula stands apart from the takes it sizes, and a take that does
+// not fit is refused instead of handing out an address past the block.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -93,11 +97,17 @@ struct DevMem {
 };
 
 // ---- grow-only device arena: one allocation per pipeline call at most, none once it has seen the largest input -----
+// A work area is described ONCE, by a layout: a struct of the pointers with `template <class A> void lay(A& a, sizes...)`
+// taking each array in turn, and `kSlack`, the bytes it reserves beyond them.  The same lay() runs on an ArenaCount, which
+// only adds the padded sizes up, and on the Arena, which hands out the addresses: what is reserved is what is taken, by
+// construction (layout_bytes, lay_out).  Sizes rocPRIM reports are arguments of a layout, so a layout is plain arithmetic.
 struct Arena {
   DevMem mem;
   size_t used = 0;
+  bool refused = false;               // a take did not fit: the layout is unusable (lay_out reports it before anything is launched)
   hipError_t reserve(size_t bytes) {  // (growing again: the cloud behind it grows (a map); hipFree / hipMalloc stall the device for milliseconds)
     used = 0;
+    refused = false;
     return mem.grow(bytes, 4, 4096);
   }
   void release() {
@@ -107,11 +117,52 @@ struct Arena {
   static size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
   template <typename T>
   T* take(size_t count) {
+    const size_t bytes = pad(count * sizeof(T));
+    if (bytes > mem.cap - used) {  // used <= cap always: nothing is handed out past the block
+      refused = true;
+      return nullptr;
+    }
     T* p = reinterpret_cast<T*>(mem.as<char>() + used);
-    used += pad(count * sizeof(T));
+    used += bytes;
     return p;
   }
 };
+struct ArenaCount {  // the arena without memory: the same padding, no addresses
+  size_t used = 0;
+  template <typename T>
+  T* take(size_t count) {
+    used += Arena::pad(count * sizeof(T));
+    return nullptr;
+  }
+};
+template <class A, typename T>
+void take(A& a, T*& p, size_t count) {  // the element type is the pointer's
+  p = a.template take<T>(count);
+}
+// what layout L takes for these sizes, padded; and what it reserves: that plus its slack
+template <class L, class... S>
+size_t measure(S... sizes) {
+  L l{};
+  ArenaCount c;
+  l.lay(c, sizes...);
+  return c.used;
+}
+template <class L, class... S>
+size_t layout_bytes(S... sizes) {
+  return measure<L>(sizes...) + L::kSlack;
+}
+// lay `l` out in a fresh reservation of `bytes` (a sibling's layout_bytes where the area is deliberately sized by it)
+template <class L, class... S>
+hipError_t lay_out_in(Arena& ar, size_t bytes, L& l, S... sizes) {
+  const hipError_t e = ar.reserve(bytes);
+  if (e != hipSuccess) return e;
+  l.lay(ar, sizes...);
+  return ar.refused ? hipErrorOutOfMemory : hipSuccess;
+}
+template <class L, class... S>
+hipError_t lay_out(Arena& ar, L& l, S... sizes) {
+  return lay_out_in(ar, layout_bytes<L>(sizes...), l, sizes...);
+}
 
 // A device buffer of an ICP handle (o3s_icp.hip): DevMem's block plus the owning handle's allocation generation, bumped whenever
 // the buffer moves or a held block is released — which invalidates every captured graph that has the old address baked in.

@@ -450,11 +450,28 @@ __global__ void __launch_bounds__(kB) k_grid_keys(Src src, int64_t N, double cel
   vals[i] = (uint32_t)i;
 }
 
-inline size_t grid_index_arena_bytes(int64_t N) {
-  const size_t n = (size_t)N;
-  return Arena::pad(kBoundsWords * 8) + 2 * Arena::pad(n * 8) + 2 * Arena::pad(n * 4) + Arena::pad(n * 4) + Arena::pad((n + 1) * 4) +
-         Arena::pad(n * 24) + Arena::pad(std::max(scan_temp_bytes(N), sort_temp_bytes(N))) + 8192;
-}
+// work area of the grid index of n points: what the build sorts and scans, and the cell-sorted copy `sp` that the searches read
+struct GridIndexArea {
+  static constexpr size_t kSlack = 8192;  // twice the usual page: what the index has always reserved
+  unsigned long long* d_bb;
+  uint64_t *keys, *keys2;
+  uint32_t *vals, *vals2, *head, *ord;
+  double* sp;
+  char* tmp;
+  template <class A>
+  void lay(A& a, size_t n, size_t tb_scan, size_t tb_sort) {
+    take(a, d_bb, kBoundsWords);
+    take(a, keys, n);
+    take(a, keys2, n);
+    take(a, vals, n);
+    take(a, vals2, n);
+    take(a, head, n);
+    take(a, ord, n + 1);
+    take(a, sp, n * 3);
+    take(a, tmp, std::max(tb_scan, tb_sort));
+  }
+};
+inline size_t grid_index_arena_bytes(int64_t N) { return layout_bytes<GridIndexArea>((size_t)N, scan_temp_bytes(N), sort_temp_bytes(N)); }
 constexpr size_t kGridMaxCells = (size_t)1 << 24;
 
 // hooks build: what the O3S_PRINT_NGRID line of build_grid_index reports (the product compiles none of it)
@@ -472,25 +489,16 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
                             hipStream_t s, const unsigned long long* known_bb = nullptr) {
   if (N <= 0 || N > (int64_t)0x7fffffff) return O3S_ERR_BAD_ARGUMENT;
   const size_t n = (size_t)N;
-  CK(w.arena.reserve(grid_index_arena_bytes(N)));
-  Arena& ar = w.arena;
-  unsigned long long* d_bb = ar.take<unsigned long long>(kBoundsWords);
-  uint64_t* keys = ar.take<uint64_t>(n);
-  uint64_t* keys2 = ar.take<uint64_t>(n);
-  uint32_t* vals = ar.take<uint32_t>(n);
-  uint32_t* vals2 = ar.take<uint32_t>(n);
-  uint32_t* head = ar.take<uint32_t>(n);
-  uint32_t* ord = ar.take<uint32_t>(n + 1);
-  double* sp = ar.take<double>(n * 3);
   const size_t tb_scan = scan_temp_bytes(N), tb_sort = sort_temp_bytes(N);
-  void* tmp = ar.take<char>(std::max(tb_scan, tb_sort));
+  GridIndexArea ar;
+  CK(lay_out(w.arena, ar, n, tb_scan, tb_sort));
   // bounds: folded on the device and posted into the mailbox the host polls (the copy of the replicas into pageable memory plus a
   // stream synchronisation was 25-40 us of every build)
   unsigned long long bb[6];
   if (known_bb) {
     for (int a = 0; a < 6; ++a) bb[a] = known_bb[a];
   } else {
-    const int rc = cloud_bounds(FlatPoints{d_pts}, N, d_bb, s, bb);
+    const int rc = cloud_bounds(FlatPoints{d_pts}, N, ar.d_bb, s, bb);
     if (rc != O3S_OK) return rc;
   }
   double lo[3], hi[3];
@@ -533,13 +541,13 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
   // ~130 us of the key + sort + count pass it replaces — bits of one word set from eight L2s.)
   for (int attempt = 0; attempt < 2; ++attempt) {
     size_grid();
-    hipLaunchKernelGGL(k_grid_keys<FlatPoints>, dim3(nblk(N)), dim3(kB), 0, s, FlatPoints{d_pts}, N, cell, lo[0], lo[1], lo[2], (uint64_t)dims[0], (uint64_t)dims[1], keys, vals);
+    hipLaunchKernelGGL(k_grid_keys<FlatPoints>, dim3(nblk(N)), dim3(kB), 0, s, FlatPoints{d_pts}, N, cell, lo[0], lo[1], lo[2], (uint64_t)dims[0], (uint64_t)dims[1], ar.keys, ar.vals);
     size_t tb = tb_sort;
-    CK(sort_pairs(tmp, tb, keys, keys2, vals, vals2, n, key_bits((uint64_t)dims[0] * (uint64_t)dims[1] * (uint64_t)dims[2]), s));  // keys are cell indices of the grid just sized
+    CK(sort_pairs(ar.tmp, tb, ar.keys, ar.keys2, ar.vals, ar.vals2, n, key_bits((uint64_t)dims[0] * (uint64_t)dims[1] * (uint64_t)dims[2]), s));  // keys are cell indices of the grid just sized
     if (attempt == 0) {
-      hipLaunchKernelGGL(k_heads, dim3(nblk(N)), dim3(kB), 0, s, keys2, N, ~0ull, head);
+      hipLaunchKernelGGL(k_heads, dim3(nblk(N)), dim3(kB), 0, s, ar.keys2, N, ~0ull, ar.head);
       int64_t n_occ = 0;
-      const int rc = scan_flags(head, ord, N, tmp, tb_scan, &n_occ, s);
+      const int rc = scan_flags(ar.head, ar.ord, N, ar.tmp, tb_scan, &n_occ, s);
       if (rc != O3S_OK) return rc;
       O3S_NGRID_NOTE(occ_first = n_occ);
       if (resize_for(n_occ)) {
@@ -562,15 +570,15 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
   uint32_t* cbeg = w.cells.as<uint32_t>();
   uint32_t* cend = cbeg + ncells;
   CK(hipMemsetAsync(w.cells.p, 0, ncells * 8, s));
-  hipLaunchKernelGGL(k_cell_ranges, dim3(nblk(N)), dim3(kB), 0, s, keys2, N, cbeg, cend);
-  hipLaunchKernelGGL(k_gather_sorted, dim3(nblk(N)), dim3(kB), 0, s, d_pts, vals2, N, sp);
+  hipLaunchKernelGGL(k_cell_ranges, dim3(nblk(N)), dim3(kB), 0, s, ar.keys2, N, cbeg, cend);
+  hipLaunchKernelGGL(k_gather_sorted, dim3(nblk(N)), dim3(kB), 0, s, d_pts, ar.vals2, N, ar.sp);
   CK(hipGetLastError());
 #ifdef O3S_TEST_HOOKS
   if (O3S_HOOK_ENV("O3S_PRINT_NGRID")) {  // hooks build: the sizing path this build took (tests/test_gpu_normals_scale.py)
     int64_t occ = occ_first;  // the occupied cells of the final grid: counted again when the re-size moved the cell
     if (resized) {
-      hipLaunchKernelGGL(k_heads, dim3(nblk(N)), dim3(kB), 0, s, keys2, N, ~0ull, head);
-      const int rc = scan_flags(head, ord, N, tmp, tb_scan, &occ, s);
+      hipLaunchKernelGGL(k_heads, dim3(nblk(N)), dim3(kB), 0, s, ar.keys2, N, ~0ull, ar.head);
+      const int rc = scan_flags(ar.head, ar.ord, N, ar.tmp, tb_scan, &occ, s);
       if (rc != O3S_OK) return rc;
     }
     std::fprintf(stderr,
@@ -583,8 +591,8 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
   out->g = g;
   out->cbeg = cbeg;
   out->cend = cend;
-  out->sp = sp;
-  out->vals = vals2;
+  out->sp = ar.sp;
+  out->vals = ar.vals2;
   return O3S_OK;
 }
 

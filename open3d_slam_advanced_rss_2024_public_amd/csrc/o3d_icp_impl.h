@@ -1323,24 +1323,34 @@ inline int o3d_prepare(O3dIcpWork& w, const double* source, int64_t Ns, const do
 // d_src = T . source in the order of the target grid's cells under T (T nullptr / identity: the points as they are).  One key
 // pass over the source where it lies, the sort, one gather that applies T on the way (round 3: copy, transform in place, keys,
 // sort, copy, gather).
+struct O3dSortArea {  // the sort of n source points by target cell (O3dIcpWork::sort_arena)
+  static constexpr size_t kSlack = 4096;
+  uint64_t *keys, *keys2;
+  uint32_t *vals, *vals2;
+  char* tmp;
+  template <class A>
+  void lay(A& a, size_t n, size_t tb_sort) {
+    take(a, keys, n);
+    take(a, keys2, n);
+    take(a, vals, n);
+    take(a, vals2, n);
+    take(a, tmp, tb_sort);
+  }
+};
 inline int o3d_place_source(O3dIcpWork& w, int64_t Ns, const GridIndex& gi, const double* T, hipStream_t s) {
   const size_t n = (size_t)Ns;
   const size_t tb = sort_temp_bytes(Ns);
-  CK(w.sort_arena.reserve(2 * Arena::pad(n * 8) + 2 * Arena::pad(n * 4) + Arena::pad(tb) + 4096));
-  uint64_t* keys = w.sort_arena.take<uint64_t>(n);
-  uint64_t* keys2 = w.sort_arena.take<uint64_t>(n);
-  uint32_t* vals = w.sort_arena.take<uint32_t>(n);
-  uint32_t* vals2 = w.sort_arena.take<uint32_t>(n);
-  void* tmp = w.sort_arena.take<char>(tb);
+  O3dSortArea a;
+  CK(lay_out(w.sort_arena, a, n, tb));
   const int apply = (T && !h_is_identity(T)) ? 1 : 0;
   O3dPose Tp{};
   if (apply) std::memcpy(Tp.m, T, sizeof(Tp.m));
-  hipLaunchKernelGGL(k_src_cell_keys, dim3(nblk(Ns)), dim3(kB), 0, s, w.orig, Ns, Tp, apply, gi.g, keys, vals);
+  hipLaunchKernelGGL(k_src_cell_keys, dim3(nblk(Ns)), dim3(kB), 0, s, w.orig, Ns, Tp, apply, gi.g, a.keys, a.vals);
   size_t tbb = tb;
-  CK(sort_pairs(tmp, tbb, keys, keys2, vals, vals2, n, key_bits((uint64_t)gi.g.nx * (uint64_t)gi.g.ny * (uint64_t)gi.g.nz), s));  // cell indices of the target grid
-  hipLaunchKernelGGL(k_o3d_place, dim3(nblk(Ns)), dim3(kB), 0, s, w.orig, vals2, Ns, Tp, apply, w.d_src.as<double>());
+  CK(sort_pairs(a.tmp, tbb, a.keys, a.keys2, a.vals, a.vals2, n, key_bits((uint64_t)gi.g.nx * (uint64_t)gi.g.ny * (uint64_t)gi.g.nz), s));  // cell indices of the target grid
+  hipLaunchKernelGGL(k_o3d_place, dim3(nblk(Ns)), dim3(kB), 0, s, w.orig, a.vals2, Ns, Tp, apply, w.d_src.as<double>());
   CK(hipGetLastError());
-  w.order = vals2;
+  w.order = a.vals2;
   w.gi = gi;
   w.n_src = Ns;
   w.corr_valid = false;
@@ -1448,7 +1458,7 @@ inline int reg_reserve_area(RegLease& area, int64_t max_source_points, int64_t m
   CK(w.d_far_count.alloc(256));
   CK(w.grid.arena.reserve(grid_index_arena_bytes(max_target_points)));
   CK(w.grid.reserve_cells(kGridMaxCells));
-  CK(w.sort_arena.reserve(2 * Arena::pad(ns * 8) + 2 * Arena::pad(ns * 4) + Arena::pad(sort_temp_bytes(max_source_points)) + 4096));
+  CK(w.sort_arena.reserve(layout_bytes<O3dSortArea>(ns, sort_temp_bytes(max_source_points))));
   CK(area->ov_src.alloc(ns * 24));
   CK(area->ov_tgt.alloc(nt * 24));
   CK(area->ov_tgtn.alloc(nt * 24));

@@ -187,14 +187,36 @@ inline uint32_t ov_slots_for(int64_t n_points) {  // room for one voxel per poin
   while ((int64_t)c < 2 * n_points && c < (1u << 31)) c <<= 1;
   return c;
 }
-inline size_t overlap_arena_bytes(int64_t Ns, int64_t Nt, uint32_t slots) {
-  const size_t ns = (size_t)Ns, nt = (size_t)Nt, nmax = std::max(ns, nt);
-  return Arena::pad(ns * 8) + Arena::pad(nt * 8) + Arena::pad(ns * 4) + Arena::pad(nt * 4) + Arena::pad((ns + 1) * 4) + Arena::pad((nt + 1) * 4) +
-         Arena::pad(scan_temp_bytes((int64_t)nmax)) + Arena::pad((size_t)slots * sizeof(OvSlot)) + Arena::pad(64) + Arena::pad(128) +
-         Arena::pad(kBoundsReplicaWords * 8) + 4096;
-}
+// work area of the overlap selection of a source of ns and a target of nt points (tb_scan: a scan of max(ns, nt) flags)
+struct OverlapArea {
+  static constexpr size_t kSlack = 4096;
+  uint64_t *ks, *kt;
+  uint32_t *fs, *ft;
+  uint32_t *os, *ot;  // first each point's slot (k_ov_count), then the offsets: the scans overwrite the slots once the flags are made
+  char* tmp;
+  OvSlot* tab;
+  uint32_t* err;
+  double* d_T;
+  unsigned long long* bb;  // folded by k_ov_post, with the counts
+  template <class A>
+  void lay(A& a, size_t ns, size_t nt, size_t slots, size_t tb_scan) {
+    take(a, ks, ns);
+    take(a, kt, nt);
+    take(a, fs, ns);
+    take(a, ft, nt);
+    take(a, os, ns + 1);
+    take(a, ot, nt + 1);
+    take(a, tmp, tb_scan);
+    take(a, tab, slots);
+    take(a, err, 16);
+    take(a, d_T, 16);
+    take(a, bb, kBoundsReplicaWords);
+  }
+};
 
-size_t reg_overlap_arena_bytes(int64_t Ns, int64_t Nt) { return overlap_arena_bytes(Ns, Nt, ov_slots_for(Ns + Nt)); }
+size_t reg_overlap_arena_bytes(int64_t Ns, int64_t Nt) {  // with the table at its largest
+  return layout_bytes<OverlapArea>((size_t)Ns, (size_t)Nt, (size_t)ov_slots_for(Ns + Nt), scan_temp_bytes(std::max(Ns, Nt)));
+}
 
 // flags + exclusive offsets of both layers on the device; counts on the host.  d_T: 16 doubles on the device.
 inline int overlap_dev(OverlapWork& w, const double* d_src, int64_t Ns, const double* d_tgt, int64_t Nt, const double T[16], double voxel,
@@ -204,41 +226,28 @@ inline int overlap_dev(OverlapWork& w, const double* d_src, int64_t Ns, const do
   if (sel) sel->have_bounds = false;
   if (Ns > (int64_t)0x7fffffff || Nt > (int64_t)0x7fffffff) return O3S_ERR_BAD_ARGUMENT;
   uint32_t slots = std::min(kOvFirstSlots, ov_slots_for(Ns + Nt));
-  uint32_t *fs = nullptr, *ft = nullptr, *os = nullptr, *ot = nullptr, *err = nullptr;
-  void* tmp = nullptr;
+  OverlapArea a;
   const size_t tb_scan = scan_temp_bytes(std::max(Ns, Nt));
   for (int attempt = 0;; ++attempt) {
     if (sel) sel->have_bounds = false;  // an attempt whose table filled up has posted the bounds of an INCOMPLETE selection: never carried over
-    CK(w.arena.reserve(overlap_arena_bytes(Ns, Nt, slots)));
-    Arena& ar = w.arena;
-    uint64_t* ks = ar.take<uint64_t>((size_t)Ns);
-    uint64_t* kt = ar.take<uint64_t>((size_t)Nt);
-    fs = ar.take<uint32_t>((size_t)Ns);
-    ft = ar.take<uint32_t>((size_t)Nt);
-    os = ar.take<uint32_t>((size_t)Ns + 1);
-    ot = ar.take<uint32_t>((size_t)Nt + 1);
-    tmp = ar.take<char>(tb_scan);
-    OvSlot* tab = ar.take<OvSlot>((size_t)slots);
-    err = ar.take<uint32_t>(16);
-    double* d_T = ar.take<double>(16);
-    unsigned long long* bb = ar.take<unsigned long long>(kBoundsReplicaWords);  // folded by k_ov_post, with the counts
-    CK(hipMemsetAsync(err, 0, 8, s));
-    CK(hipMemsetAsync(tab, 0, (size_t)slots * sizeof(OvSlot), s));
-    CK(hipMemcpyAsync(d_T, T, 16 * sizeof(double), hipMemcpyHostToDevice, s));  // pageable source: staged before the call returns
+    CK(lay_out(w.arena, a, (size_t)Ns, (size_t)Nt, (size_t)slots, tb_scan));
+    CK(hipMemsetAsync(a.err, 0, 8, s));
+    CK(hipMemsetAsync(a.tab, 0, (size_t)slots * sizeof(OvSlot), s));
+    CK(hipMemcpyAsync(a.d_T, T, 16 * sizeof(double), hipMemcpyHostToDevice, s));  // pageable source: staged before the call returns
     const double inv = 1.0 / voxel;
-    hipLaunchKernelGGL(k_ov_keys, dim3(nblk(Ns)), dim3(kB), 0, s, d_src, Ns, (const double*)d_T, inv, ks, err);
-    hipLaunchKernelGGL(k_ov_keys, dim3(nblk(Nt)), dim3(kB), 0, s, d_tgt, Nt, (const double*)nullptr, inv, kt, err);
+    hipLaunchKernelGGL(k_ov_keys, dim3(nblk(Ns)), dim3(kB), 0, s, d_src, Ns, (const double*)a.d_T, inv, a.ks, a.err);
+    hipLaunchKernelGGL(k_ov_keys, dim3(nblk(Nt)), dim3(kB), 0, s, d_tgt, Nt, (const double*)nullptr, inv, a.kt, a.err);
     // the slots land in the offset arrays, which the scans below overwrite once the flags are made
-    hipLaunchKernelGGL(k_ov_count, dim3(nblk(Ns)), dim3(kB), 0, s, ks, Ns, tab, slots - 1u, 0, os, err);
-    hipLaunchKernelGGL(k_ov_count, dim3(nblk(Nt)), dim3(kB), 0, s, kt, Nt, tab, slots - 1u, 1, ot, err);
-    hipLaunchKernelGGL(k_ov_flag, dim3(nblk(Ns)), dim3(kB), 0, s, (const uint32_t*)os, Ns, tab, 0, min_pts, fs);
-    hipLaunchKernelGGL(k_ov_flag, dim3(nblk(Nt)), dim3(kB), 0, s, (const uint32_t*)ot, Nt, tab, 1, min_pts, ft);
+    hipLaunchKernelGGL(k_ov_count, dim3(nblk(Ns)), dim3(kB), 0, s, a.ks, Ns, a.tab, slots - 1u, 0, a.os, a.err);
+    hipLaunchKernelGGL(k_ov_count, dim3(nblk(Nt)), dim3(kB), 0, s, a.kt, Nt, a.tab, slots - 1u, 1, a.ot, a.err);
+    hipLaunchKernelGGL(k_ov_flag, dim3(nblk(Ns)), dim3(kB), 0, s, (const uint32_t*)a.os, Ns, a.tab, 0, min_pts, a.fs);
+    hipLaunchKernelGGL(k_ov_flag, dim3(nblk(Nt)), dim3(kB), 0, s, (const uint32_t*)a.ot, Nt, a.tab, 1, min_pts, a.ft);
     CK(hipGetLastError());
     // both scans, then ONE hand-over of the two counts and the error words (three separate waits — two counts and a copied-back error
     // word — were 40-50 us of a refinement)
-    int rc = scan_flags_dev(fs, os, Ns, tmp, tb_scan, s);
+    int rc = scan_flags_dev(a.fs, a.os, Ns, a.tmp, tb_scan, s);
     if (rc != O3S_OK) return rc;
-    rc = scan_flags_dev(ft, ot, Nt, tmp, tb_scan, s);
+    rc = scan_flags_dev(a.ft, a.ot, Nt, a.tmp, tb_scan, s);
     if (rc != O3S_OK) return rc;
     uint32_t herr[2] = {0, 0};
     {
@@ -246,14 +255,14 @@ inline int overlap_dev(OverlapWork& w, const double* d_src, int64_t Ns, const do
       const uint32_t seq = mailbox_open(pa);
       const bool with_sel = sel && seq;
       if (with_sel) {  // the two selections, enqueued before their sizes are known (the buffers hold either cloud whole)
-        if (const int rb = bounds_begin(bb, s); rb != O3S_OK) return rb;
-        hipLaunchKernelGGL(k_compact, dim3(nblk(Ns)), dim3(kB), 0, s, d_src, sel->src_normals, Ns, (const uint32_t*)fs, (const uint32_t*)os, sel->out_src,
+        if (const int rb = bounds_begin(a.bb, s); rb != O3S_OK) return rb;
+        hipLaunchKernelGGL(k_compact, dim3(nblk(Ns)), dim3(kB), 0, s, d_src, sel->src_normals, Ns, (const uint32_t*)a.fs, (const uint32_t*)a.os, sel->out_src,
                            sel->out_src_n, (int32_t*)nullptr);
-        hipLaunchKernelGGL(k_compact_bounds, dim3(std::min(nblk(Nt), 1024u)), dim3(kB), 0, s, d_tgt, sel->tgt_normals, Nt, (const uint32_t*)ft,
-                           (const uint32_t*)ot, sel->out_tgt, sel->out_tgt_n, bb);
+        hipLaunchKernelGGL(k_compact_bounds, dim3(std::min(nblk(Nt), 1024u)), dim3(kB), 0, s, d_tgt, sel->tgt_normals, Nt, (const uint32_t*)a.ft,
+                           (const uint32_t*)a.ot, sel->out_tgt, sel->out_tgt_n, a.bb);
       }
-      hipLaunchKernelGGL(k_ov_post, dim3(1), dim3(64), 0, s, (const uint32_t*)fs, os, Ns, (const uint32_t*)ft, ot, Nt, (const uint32_t*)err,
-                         with_sel ? (const unsigned long long*)bb : (const unsigned long long*)nullptr, seq ? pa.mb.dev : (uint32_t*)nullptr, seq);
+      hipLaunchKernelGGL(k_ov_post, dim3(1), dim3(64), 0, s, (const uint32_t*)a.fs, a.os, Ns, (const uint32_t*)a.ft, a.ot, Nt, (const uint32_t*)a.err,
+                         with_sel ? (const unsigned long long*)a.bb : (const unsigned long long*)nullptr, seq ? pa.mb.dev : (uint32_t*)nullptr, seq);
       CK(hipGetLastError());
       uint32_t r[4 + 12];
       const int posted = fetch_post(pa.mb, seq, s, r, with_sel ? 16 : 4, kOvCounts, nullptr);
@@ -270,9 +279,9 @@ inline int overlap_dev(OverlapWork& w, const double* d_src, int64_t Ns, const do
       } else {
         if (sel) sel->have_bounds = false;  // the caller falls back to its own compaction and bounds pass
         uint32_t cnt[2] = {0, 0};
-        CK(hipMemcpyAsync(&cnt[0], os + Ns, 4, hipMemcpyDeviceToHost, s));
-        CK(hipMemcpyAsync(&cnt[1], ot + Nt, 4, hipMemcpyDeviceToHost, s));
-        CK(hipMemcpyAsync(herr, err, 8, hipMemcpyDeviceToHost, s));
+        CK(hipMemcpyAsync(&cnt[0], a.os + Ns, 4, hipMemcpyDeviceToHost, s));
+        CK(hipMemcpyAsync(&cnt[1], a.ot + Nt, 4, hipMemcpyDeviceToHost, s));
+        CK(hipMemcpyAsync(herr, a.err, 8, hipMemcpyDeviceToHost, s));
         CK(hipStreamSynchronize(s));
         *n_s = (int64_t)cnt[0];
         *n_t = (int64_t)cnt[1];
@@ -285,10 +294,10 @@ inline int overlap_dev(OverlapWork& w, const double* d_src, int64_t Ns, const do
     slots = ov_slots_for(Ns + Nt);
     *n_s = *n_t = 0;
   }
-  *flag_s = fs;
-  *off_s = os;
-  *flag_t = ft;
-  *off_t = ot;
+  *flag_s = a.fs;
+  *off_s = a.os;
+  *flag_t = a.ft;
+  *off_t = a.ot;
   return O3S_OK;
 }
 

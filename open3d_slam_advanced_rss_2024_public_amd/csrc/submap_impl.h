@@ -333,6 +333,29 @@ inline hipStream_t next_submap_stream(int device) {  // the device is current
   const unsigned k = next[(size_t)device]++ % 4u;
   return set.n ? set.s[k % (unsigned)set.n] : nullptr;
 }
+
+// work area of space carving on a map of nm points
+struct CarveArea {
+  static constexpr size_t kSlack = 8192;  // twice the usual page: what carving has always reserved
+  uint32_t *inflag, *remove, *keep, *off;
+  uint64_t *keys, *keys2;
+  uint32_t *vals, *vals2;
+  int32_t* d_mm;
+  char* tmp;
+  template <class A>
+  void lay(A& a, size_t nm, size_t tb_scan, size_t tb_sort) {
+    take(a, inflag, nm);
+    take(a, remove, nm);
+    take(a, keep, nm);
+    take(a, off, nm + 1);
+    take(a, keys, nm);
+    take(a, keys2, nm);
+    take(a, vals, nm);
+    take(a, vals2, nm);
+    take(a, d_mm, kExtSlots * 6);
+    take(a, tmp, std::max(tb_scan, tb_sort));
+  }
+};
 }  // namespace
 
 extern "C" {
@@ -473,7 +496,10 @@ int o3s_submap_reserve(o3s_submap* m, int64_t n_points) {
     CK(m->nrm[k].ensure(bytes, (k == m->cur && m->has_normals == 1) ? (size_t)m->n * 24 : 0, s));
   }
   // the work area of either insert pipeline at that size (the merge takes the map plus a scan of up to 2 x 64 x 2048 points)
-  const size_t work = std::max(voxel_arena_bytes(n_points), insert_merge_arena_bytes(n_points, n_points, std::min<int64_t>(n_points, 262144)));
+  const size_t n = (size_t)n_points, n_s = std::min<size_t>(n, 262144);
+  const size_t work = std::max(layout_bytes<VoxelArea>(n, scan_temp_bytes(n_points), sort_temp_bytes(n_points)),
+                               layout_bytes<InsertMergeArea>(n, n, n_s, scan_temp_bytes(n_points), sort_temp_bytes((int64_t)n_s),
+                                                             merge_temp_bytes(n_points, (int64_t)n_s)));
   if (m->arena.mem.cap < work) CK(m->arena.reserve(work));
   return O3S_OK;
 }
@@ -979,32 +1005,20 @@ int o3s_submap_carve(o3s_submap* m, const o3s_carving_params* cp, const double* 
                      (double*)nullptr);
   // wideCroppedIdxs = cropper.getIndicesWithinVolume(*map): the map-builder cropper at the pose of the previous insert
   const size_t nm = (size_t)Nm;
-  const size_t need = 3 * Arena::pad(nm * 4) + Arena::pad((nm + 1) * 4) + 2 * Arena::pad(nm * 8) + 2 * Arena::pad(nm * 4) + Arena::pad(kExtSlots * 6 * 4) +
-                      Arena::pad(std::max(scan_temp_bytes(Nm), sort_temp_bytes(Nm))) + 8192;
-  CK(m->arena.reserve(need));
-  Arena& ar = m->arena;
-  uint32_t* inflag = ar.take<uint32_t>(nm);
-  uint32_t* remove = ar.take<uint32_t>(nm);
-  uint32_t* keep = ar.take<uint32_t>(nm);
-  uint32_t* off = ar.take<uint32_t>(nm + 1);
-  uint64_t* keys = ar.take<uint64_t>(nm);
-  uint64_t* keys2 = ar.take<uint64_t>(nm);
-  uint32_t* vals = ar.take<uint32_t>(nm);
-  uint32_t* vals2 = ar.take<uint32_t>(nm);
-  int32_t* d_mm = ar.take<int32_t>(kExtSlots * 6);
   const size_t tb_scan = scan_temp_bytes(Nm), tb_sort = sort_temp_bytes(Nm);
-  void* tmp = ar.take<char>(std::max(tb_scan, tb_sort));
-  hipLaunchKernelGGL(k_mask, dim3(nblk(Nm)), dim3(kB), 0, s, m->cropper, m->pts[c].as<double>(), Nm, 1, inflag);
+  CarveArea w;
+  CK(lay_out(m->arena, w, nm, tb_scan, tb_sort));
+  hipLaunchKernelGGL(k_mask, dim3(nblk(Nm)), dim3(kB), 0, s, m->cropper, m->pts[c].as<double>(), Nm, 1, w.inflag);
   int64_t n_in = 0;
-  rc = scan_flags(inflag, off, Nm, tmp, tb_scan, &n_in, s);
+  rc = scan_flags(w.inflag, w.off, Nm, w.tmp, tb_scan, &n_in, s);
   if (rc != O3S_OK) return rc;
   if (n_in == 0) return O3S_OK;
   const double inv = 1.0 / cp->voxel_size;
-  rc = ext_i32_init(d_mm, s);
+  rc = ext_i32_init(w.d_mm, s);
   if (rc != O3S_OK) return rc;
-  hipLaunchKernelGGL(k_carve_box, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].as<double>(), Nm, inflag, inv, d_mm);
+  hipLaunchKernelGGL(k_carve_box, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].as<double>(), Nm, w.inflag, inv, w.d_mm);
   int32_t mm[6];
-  rc = ext_i32_fetch(d_mm, mm, s);
+  rc = ext_i32_fetch(w.d_mm, mm, s);
   if (rc != O3S_OK) return rc;
   if (mm[0] > mm[3]) return O3S_OK;  // no point of the subset is in a voxel (all of them non-finite): nothing can be carved
   const int64_t ex = (int64_t)mm[3] - mm[0] + 1, ey = (int64_t)mm[4] - mm[1] + 1, ez = (int64_t)mm[5] - mm[2] + 1;
@@ -1013,27 +1027,27 @@ int o3s_submap_carve(o3s_submap* m, const o3s_carving_params* cp, const double* 
   // with all 64 bits, three or four with the range that is known here)
   const int kb = key_bits((uint64_t)ex * (uint64_t)ey * (uint64_t)ez);
   const uint64_t out_key = kb < 63 ? (1ull << kb) : ~0ull;
-  hipLaunchKernelGGL(k_carve_keys, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].as<double>(), Nm, inflag, inv, mm[0], mm[1], mm[2], (uint64_t)ex, (uint64_t)ey, out_key,
-                     keys, vals);
+  hipLaunchKernelGGL(k_carve_keys, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].as<double>(), Nm, w.inflag, inv, mm[0], mm[1], mm[2], (uint64_t)ex, (uint64_t)ey, out_key,
+                     w.keys, w.vals);
   size_t tb = tb_sort;
-  CK(sort_pairs(tmp, tb, keys, keys2, vals, vals2, nm, kb < 63 ? kb + 1 : 64, s));
-  CK(hipMemsetAsync(remove, 0, nm * 4, s));
+  CK(sort_pairs(w.tmp, tb, w.keys, w.keys2, w.vals, w.vals2, nm, kb < 63 ? kb + 1 : 64, s));
+  CK(hipMemsetAsync(w.remove, 0, nm * 4, s));
   hipLaunchKernelGGL(k_carve_rays, dim3(nblk(N)), dim3(kB), 0, s, m->carve_scan.as<double>(), N, T_map_sensor[12], T_map_sensor[13], T_map_sensor[14],
-                     cp->voxel_size, inv, cp->max_raytracing_length, cp->truncation_distance, cp->min_dot_product_with_normal, keys2, vals2, n_in, mm[0],
-                     mm[1], mm[2], ex, ey, ez, hn ? m->nrm[c].as<double>() : nullptr, remove);
+                     cp->voxel_size, inv, cp->max_raytracing_length, cp->truncation_distance, cp->min_dot_product_with_normal, w.keys2, w.vals2, n_in, mm[0],
+                     mm[1], mm[2], ex, ey, ez, hn ? m->nrm[c].as<double>() : nullptr, w.remove);
   // removeByIds: SelectByIndex(ids, invert) keeps the survivors in their order
-  hipLaunchKernelGGL(k_invert_flags, dim3(nblk(Nm)), dim3(kB), 0, s, remove, Nm, keep);
+  hipLaunchKernelGGL(k_invert_flags, dim3(nblk(Nm)), dim3(kB), 0, s, w.remove, Nm, w.keep);
   int64_t n_keep = 0;
-  rc = scan_flags(keep, off, Nm, tmp, tb_scan, &n_keep, s);
+  rc = scan_flags(w.keep, w.off, Nm, w.tmp, tb_scan, &n_keep, s);
   if (rc != O3S_OK) return rc;
   if (n_keep < Nm) {
     CK(m->pts[1 - c].ensure((size_t)Nm * 24, 0, s));
     CK(m->nrm[1 - c].ensure((size_t)Nm * 24, 0, s));
-    hipLaunchKernelGGL(k_compact, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].as<double>(), hn ? m->nrm[c].as<double>() : nullptr, Nm, keep, off, m->pts[1 - c].as<double>(),
+    hipLaunchKernelGGL(k_compact, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].as<double>(), hn ? m->nrm[c].as<double>() : nullptr, Nm, w.keep, w.off, m->pts[1 - c].as<double>(),
                        m->nrm[1 - c].as<double>(), (int32_t*)nullptr);
     if (m->has_colors == 1) {  // SelectByIndex carries the colours along
       CK(m->col[1 - c].ensure((size_t)Nm * 24, 0, s));
-      hipLaunchKernelGGL(k_compact_attr, dim3(nblk(Nm)), dim3(kB), 0, s, (const double*)m->col[c].as<double>(), (const double*)nullptr, Nm, keep, off,
+      hipLaunchKernelGGL(k_compact_attr, dim3(nblk(Nm)), dim3(kB), 0, s, (const double*)m->col[c].as<double>(), (const double*)nullptr, Nm, w.keep, w.off,
                          m->col[1 - c].as<double>(), (double*)nullptr);
     }
     CK(hipGetLastError());
@@ -1057,14 +1071,12 @@ int o3s_submap_patch_count(o3s_submap* m, const o3s_cropper* scan_matcher_croppe
   o3s_cropper c = *scan_matcher_cropper;  // scanMatcherCropper_->setPose(mapToRangeSensor)
   for (int d = 0; d < 3; ++d) c.centre[d] = T_map_sensor[12 + d];
   const int64_t N = m->n;
-  CK(m->arena.reserve(crop_arena_bytes(N)));
-  uint32_t* flag = m->arena.take<uint32_t>((size_t)N);
-  uint32_t* off = m->arena.take<uint32_t>((size_t)N + 1);
   const size_t tb = scan_temp_bytes(N);
-  void* tmp = m->arena.take<char>(tb);
-  uint32_t* blk = reinterpret_cast<uint32_t*>(tmp);
-  hipLaunchKernelGGL(k_mask, dim3(nblk(N)), dim3(kB), 0, s, c, (const double*)m->pts[m->cur].as<double>(), N, 1, flag, (uint32_t*)nullptr, blk);
-  return scan_flags(flag, off, N, tmp, tb, n_patch, s, blk);
+  CropArea w;
+  CK(lay_out(m->arena, w, (size_t)N, tb));
+  uint32_t* blk = reinterpret_cast<uint32_t*>(w.tmp);
+  hipLaunchKernelGGL(k_mask, dim3(nblk(N)), dim3(kB), 0, s, c, (const double*)m->pts[m->cur].as<double>(), N, 1, w.flag, (uint32_t*)nullptr, blk);
+  return scan_flags(w.flag, w.off, N, w.tmp, tb, n_patch, s, blk);
 }
 
 int o3s_submap_set_reference(o3s_submap* m, const o3s_cropper* scan_matcher_cropper, const double T_map_sensor[16], o3s_icp* icp,
@@ -1092,20 +1104,18 @@ int o3s_submap_set_reference(o3s_submap* m, const o3s_cropper* scan_matcher_crop
   uint32_t* d_count = nullptr;
   const int64_t N = m->n;
   {
-    CK(m->arena.reserve(crop_arena_bytes(N)));
-    uint32_t* flag = m->arena.take<uint32_t>((size_t)N);
-    uint32_t* off = m->arena.take<uint32_t>((size_t)N + 1);
     const size_t tb = scan_temp_bytes(N);
-    void* tmp = m->arena.take<char>(tb);
-    uint32_t* blk = reinterpret_cast<uint32_t*>(tmp);  // the mask's per-block counts: the scan is one launch (cloud_dev.h k_scan_flags_blk)
-    hipLaunchKernelGGL(k_mask, dim3(nblk(N)), dim3(kB), 0, s, c, (const double*)m->pts[m->cur].as<double>(), N, 1, flag, (uint32_t*)nullptr, blk);
-    rc = scan_flags_dev(flag, off, N, tmp, tb, s, blk);
+    CropArea w;
+    CK(lay_out(m->arena, w, (size_t)N, tb));
+    uint32_t* blk = reinterpret_cast<uint32_t*>(w.tmp);  // the mask's per-block counts: the scan is one launch (cloud_dev.h k_scan_flags_blk)
+    hipLaunchKernelGGL(k_mask, dim3(nblk(N)), dim3(kB), 0, s, c, (const double*)m->pts[m->cur].as<double>(), N, 1, w.flag, (uint32_t*)nullptr, blk);
+    rc = scan_flags_dev(w.flag, w.off, N, w.tmp, tb, s, blk);
     if (rc != O3S_OK) return rc;
     CK(m->patch_xyzw.ensure((size_t)N * 16, 0, s));
     CK(m->patch_n32.ensure((size_t)N * 12, 0, s));
-    d_count = off + N;
+    d_count = w.off + N;
     hipLaunchKernelGGL(k_compact_pm, dim3(nblk(N)), dim3(kB), 0, s, (const double*)m->pts[m->cur].as<double>(), hn ? (const double*)m->nrm[m->cur].as<double>() : nullptr, N,
-                       flag, off, reinterpret_cast<float4*>(m->patch_xyzw.p), reinterpret_cast<float*>(m->patch_n32.p), d_count);
+                       w.flag, w.off, reinterpret_cast<float4*>(m->patch_xyzw.p), reinterpret_cast<float*>(m->patch_n32.p), d_count);
     CK(hipGetLastError());
   }
   // the ICP handle works on its own stream: it waits for the patch on the device, and reads it asynchronously — the patch

@@ -1,5 +1,5 @@
 // csrc/dev_mem.h against the stand-in HIP of tests/cpp/fake_hip: ownership (moves, release, no leak at exit) and every growth
-// policy to the byte.  Built with -fsanitize=address,undefined by tests/test_ownership_cpp.py; exits 0 and prints "ok" when all hold.
+// policy to the byte; the counting arena against the real one, and the take that does not fit.  Built with -fsanitize=address,undefined by tests/test_ownership_cpp.py; exits 0 and prints "ok" when all hold.
 #include "dev_mem.h"
 
 #include <cstdio>
@@ -121,6 +121,78 @@ static void policy_arena() {  // Arena::reserve: grows when bytes > cap; bytes +
   CHECK(asked() == (V{14096, 28192, 129096}));
 }
 
+// a layout over every element size the work areas use (1, 4, 8, 12 bytes), all of one count
+struct Twelve {
+  uint32_t w[3];
+};
+struct ToyArea {
+  static constexpr size_t kSlack = 512;
+  char* c;
+  uint32_t* u;
+  double* d;
+  Twelve* t;
+  template <class A>
+  void lay(A& a, size_t count) {
+    take(a, c, count);
+    take(a, u, count);
+    take(a, d, count);
+    take(a, t, count);
+  }
+};
+
+static void layouts() {  // the counting arena adds up what Arena::take hands out, to the byte
+  Arena a;
+  for (size_t count : {(size_t)0, (size_t)1, (size_t)63, (size_t)64, (size_t)65, ((size_t)1 << 20) + 1}) {
+    const size_t bytes = measure<ToyArea>(count);
+    CHECK(bytes == Arena::pad(count) + Arena::pad(count * 4) + Arena::pad(count * 8) + Arena::pad(count * 12));
+    CHECK(layout_bytes<ToyArea>(count) == bytes + 512);
+    ToyArea w{};
+    CHECK(lay_out(a, w, count) == hipSuccess && !a.refused);
+    CHECK(a.used == bytes && a.mem.cap >= bytes + 512);
+    char* base = a.mem.as<char>();
+    CHECK(w.c == base && reinterpret_cast<char*>(w.u) == base + Arena::pad(count));
+    CHECK(reinterpret_cast<char*>(w.t) + Arena::pad(count * 12) == base + bytes);
+    if (count) w.t[count - 1].w[2] = 7u;  // the last word of the last array is inside the block (the sanitizer watches)
+  }
+  for (size_t size : {(size_t)1, (size_t)4, (size_t)8, (size_t)12})  // each element size alone, across a padding boundary
+    for (size_t count : {(size_t)0, (size_t)1, (size_t)63, (size_t)64, (size_t)65, ((size_t)1 << 20) + 1}) {
+      ArenaCount c;
+      CHECK(a.reserve(count * size + 256) == hipSuccess);
+      if (size == 1) c.take<char>(count), a.take<char>(count);
+      if (size == 4) c.take<uint32_t>(count), a.take<uint32_t>(count);
+      if (size == 8) c.take<double>(count), a.take<double>(count);
+      if (size == 12) c.take<Twelve>(count), a.take<Twelve>(count);
+      CHECK(c.used == a.used && c.used == ((count * size + 255) / 256) * 256 && !a.refused);
+    }
+  // a layout laid into a reservation that is too small is reported, and nothing points anywhere
+  Arena small;
+  ToyArea w{};
+  CHECK(lay_out_in(small, 0, w, 1) != hipSuccess && small.refused && small.used == 0);
+  CHECK(w.c == nullptr && w.u == nullptr && w.d == nullptr && w.t == nullptr);
+  CHECK(lay_out_in(small, 0, w, 0) == hipSuccess && !small.refused);  // nothing asked, nothing refused
+  asked();
+}
+
+static void checked_take() {  // a take that does not fit: nullptr, the flag latched, `used` as it was; reserve clears the flag
+  Arena a;
+  CHECK(a.reserve(4096) == hipSuccess && a.mem.cap == 4096 + 1024 + 4096);  // 9216 = 36 * 256
+  const size_t cap = a.mem.cap;
+  char* base = a.mem.as<char>();
+  CHECK(a.take<char>(cap) == base && a.used == cap && !a.refused);  // fits exactly
+  CHECK(a.take<char>(0) == base + cap && a.used == cap && !a.refused);  // nothing more asked: nothing refused
+  CHECK(a.take<char>(1) == nullptr && a.refused && a.used == cap);
+  CHECK(a.reserve(cap) == hipSuccess && a.mem.as<char>() == base && !a.refused && a.used == 0);
+  CHECK(a.take<char>(cap + 1) == nullptr && a.refused && a.used == 0);  // one byte more than there is
+  CHECK(a.reserve(cap) == hipSuccess && !a.refused);
+  CHECK(a.take<double>(32) == reinterpret_cast<double*>(base) && a.used == 256);
+  CHECK(a.take<uint32_t>((cap - 256) / 4 + 1) == nullptr && a.refused && a.used == 256);  // one element past the rest
+  CHECK(a.take<uint32_t>((cap - 256) / 4) == reinterpret_cast<uint32_t*>(base + 256) && a.used == cap);  // the rest exactly
+  CHECK(a.refused);  // latched until the next reserve
+  CHECK(a.reserve(1) == hipSuccess && !a.refused && a.used == 0);
+  base[cap - 1] = 1;  // the block is all there
+  asked();
+}
+
 static void policy_cells() {  // NormalsWork::cells: grows when ncells * 8 > cap; ncells * 8 + 4096; contents lost
   DevMem c;
   CHECK(c.fit(0, 4096) == hipSuccess && c.p == nullptr);
@@ -162,6 +234,8 @@ int main() {
   policy_ensure();
   policy_ensure_keep();
   policy_arena();
+  layouts();
+  checked_take();
   policy_cells();
   policy_devbuf();
   CHECK(mallocs == frees);  // at program end, frees equal allocations
