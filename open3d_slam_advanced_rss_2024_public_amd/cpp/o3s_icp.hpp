@@ -15,11 +15,13 @@
 #include <limits>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "o3s_icp.h"
 #include "o3s_dense_map.h"
 #include "dense_map/o3s_dense_map_color.h"
 #include "o3s_submap.h"
+#include "degeneracy/o3s_degeneracy.h"
 #include "localizability/o3s_localizability.h"
 
 namespace o3s {
@@ -86,6 +88,19 @@ class IcpHip {
     o3s_localizability out{};
     raise(o3s_icp_localizability(h_, &params, &out));
     return out;
+  }
+  // How the later computes treat directions the scan does not constrain (o3s_icp_set_degeneracy): O3S_DEGENERACY_OFF, _FIXED with
+  // `fixedSet` (the same set in every iteration) or _ANALYSE with `params` (every iteration analyses its own kept pairs and
+  // constrains the directions of category < minCategory).  One launch more per iteration (FIXED) or four (ANALYSE); none when OFF.
+  void setDegeneracy(std::int32_t mode, const o3s_degeneracy_set* fixedSet = nullptr, const o3s_localizability_params* params = nullptr,
+                     std::int32_t minCategory = 2) {
+    raise(o3s_icp_set_degeneracy(h_, mode, fixedSet, params, minCategory));
+  }
+  // One 6-bit mask per iteration of the last successful compute: the directions that iteration constrained (o3s_icp_degeneracy_trace)
+  std::vector<std::int32_t> degeneracyTrace() {
+    std::vector<std::int32_t> masks(4096);
+    masks.resize((size_t)o3s_icp_degeneracy_trace(h_, masks.data(), (std::int32_t)masks.size()));
+    return masks;
   }
   o3s_icp* handle() { return h_; }
 

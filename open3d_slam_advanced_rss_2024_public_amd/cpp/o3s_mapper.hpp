@@ -103,7 +103,9 @@ struct MapperParams {
   // Off: nothing, not even the analysis.  Report: run it, keep the result.  Remap: also keep the prior in the directions whose
   // category is below remapMinCategory.  `localizability`: the thresholds — its three sums have no default and must be calibrated
   // (run Report on a well-constrained recording and read sum_all / sum_strong); unset, Report and Remap throw at construction.
-  enum class DegeneracyPolicy { Off, Report, Remap };
+  // Constrain: every ICP iteration solves its step with no component along the directions whose category is below remapMinCategory
+  // (IcpHip::setDegeneracy, mode ANALYSE, include/degeneracy/o3s_degeneracy.h); the analysis behind the compute is kept as for Report.
+  enum class DegeneracyPolicy { Off, Report, Remap, Constrain };
   DegeneracyPolicy degeneracyPolicy = DegeneracyPolicy::Off;
   o3s_localizability_params localizability = defaultLocalizability();
   std::int32_t remapMinCategory = 1;
@@ -123,6 +125,8 @@ class MapperHip {
       if (o3s_icp_localizability(nullptr, &p.localizability, &unused) == O3S_ERR_BAD_CONFIG)
         throw std::runtime_error("MapperParams::localizability: the thresholds are unset or out of order");
       if (p.remapMinCategory != 1 && p.remapMinCategory != 2) throw std::runtime_error("MapperParams::remapMinCategory must be 1 or 2");
+      if (p.degeneracyPolicy == MapperParams::DegeneracyPolicy::Constrain)
+        icp_.setDegeneracy(O3S_DEGENERACY_ANALYSE, nullptr, &p.localizability, p.remapMinCategory);
     }
     lastLocalizability_.kept = -1;
   }

@@ -1,0 +1,148 @@
+// degeneracy_dev.h — k_constrain, the one kernel of the degeneracy-aware step (include/degeneracy/o3s_degeneracy.h holds the
+// arithmetic contract): it stands between the normal equations (k_sel_ne / k_normal_eq) and k_solve and rewrites the [27][nb] block
+// partials in d_ne into the system constrained to C x = 0, so that k_solve runs unchanged on it.
+//   FIXED    the set arrives by value with the launch
+//   ANALYSE  k_loc_hessian, k_loc_eig and k_loc_contrib (localizability_dev.h, live) have run on this iteration's kept pairs; the
+//            kernel folds pass 2 as k_loc_post does, applies the categories (k_loc_decide, fused in here: one launch less per
+//            iteration) and takes the directions of category < min_category
+// One block of kBlock threads.  Every small matrix lives in LDS and is indexed there (a run-time subscript into registers would put
+// it into scratch, see the note at the top of solve_device.h); the 36 entries are formed by 36 lanes side by side, each a serial
+// left-to-right fp64 sum, so the order of operations is the header's whatever the lane count.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "icp_kernels.h"
+#include "localizability_dev.h"
+
+#pragma clang fp contract(off)
+
+namespace o3s {
+namespace kern {
+
+// what the last constrained iteration used, for o3s_icp_get_degeneracy: dirs in the mask's order (translation 0..2, rotation 3..5)
+struct DegLast {
+  double dir[6][3];
+  uint32_t mask;
+  uint32_t pad;
+};
+struct DegFixed {  // the caller's set, by value: rows in the mask's order (translation 0..2, rotation 3..5), mask of the rows present
+  double dir[6][3];
+  uint32_t mask;
+};
+struct DegLds {
+  double s_a[BlockSum<kNeComps, kBlock>::kWordsA];
+  double s_b[BlockSum<kNeComps, kBlock>::kWordsB];
+  double s_sum[kNeComps];
+  double loc[kLocSums];  // ANALYSE: pass 2's folded sums
+  double C[6][6];        // the rows of C: rotation directions first, then translation
+  double A[6][6], P[6][6], M[6][6], F[2][6][6];
+  double mu[2];
+  int n_rot, n_rows;
+  uint32_t mask;
+};
+
+__global__ void __launch_bounds__(kBlock) k_constrain(double* __restrict__ part /*[27][nb]*/, int nb, const IcpState* __restrict__ st, DegFixed fixed,
+                                                      const double* __restrict__ loc_part /*null: FIXED; [12][nbl] of k_loc_contrib*/, int nbl,
+                                                      const double* __restrict__ loc_dirs, LocThresholds th, int min_category,
+                                                      DegLast* __restrict__ last, uint32_t* __restrict__ masks /*nullable*/, int mask_cap) {
+  __shared__ DegLds L;
+  const float hv = hdr_load(st);
+  if (hdr_i(hv, H_DONE) || hdr_i(hv, H_STATUS)) return;  // the chain has ended (or this iteration has failed: k_solve closes it)
+  const int t = threadIdx.x;
+  const int it = hdr_i(hv, H_ITER);
+  const bool analyse = loc_part != nullptr;  // uniform
+  if (analyse) {  // k_loc_post's fold: component c by wave c % 4, lane l adds the partials of blocks l, l + 64, ..., then the wave's tree
+    const int w = t >> 6, l = t & 63;
+    for (int c = w; c < kLocSums; c += kBlock / 64) {
+      double s = 0.0;
+      for (int b = l; b < nbl; b += 64) s += loc_part[(size_t)c * nbl + b];
+      s = wave_sum(s);
+      if (l == 0) L.loc[c] = s;
+    }
+  }
+  if (t < 36) L.C[t / 6][t % 6] = 0.0;
+  __syncthreads();
+  if (t == 0) {  // the set: mask, and the rows of C (rotation first)
+    uint32_t mask = 0u;
+    if (analyse) {
+      for (int j = 0; j < 6; ++j) {
+        const double all = L.loc[j], strong = L.loc[6 + j];
+        const int cat = (all >= th.sum_all_min || strong >= th.sum_strong_min) ? 2 : (strong >= th.sum_partial_min ? 1 : 0);
+        if (cat < min_category) mask |= 1u << j;
+      }
+    } else {
+      mask = fixed.mask;
+    }
+    int row = 0;
+    for (int j = 3; j < 6; ++j)
+      if (mask & (1u << j)) {
+        for (int c = 0; c < 3; ++c) L.C[row][c] = analyse ? loc_dirs[6 + 3 * j + c] : fixed.dir[j][c];
+        ++row;
+      }
+    L.n_rot = row;
+    for (int j = 0; j < 3; ++j)
+      if (mask & (1u << j)) {
+        for (int c = 0; c < 3; ++c) L.C[row][3 + c] = analyse ? loc_dirs[6 + 3 * j + c] : fixed.dir[j][c];
+        ++row;
+      }
+    L.n_rows = row;
+    L.mask = mask;
+    if (masks && it < mask_cap) masks[it] = mask;
+  }
+  __syncthreads();
+  const uint32_t mask = L.mask;
+  if (mask == 0u) return;  // uniform.  The empty set: the partials stay as they are, bit for bit
+  if (t < 18) {  // the set this iteration used, in the mask's order
+    const int j = t / 3, c = t % 3;
+    double v = 0.0;
+    if (mask & (1u << j)) v = analyse ? loc_dirs[6 + 3 * j + c] : fixed.dir[j][c];
+    last->dir[j][c] = v;
+  } else if (t == 18) {
+    last->mask = mask;
+  }
+  ne_fold(part, nb, L.s_a, L.s_b, L.s_sum);
+  __syncthreads();
+  const int n_rot = L.n_rot, n_rows = L.n_rows;
+  const int a = t / 6, c = t % 6;  // (t < 36)
+  if (t < 36) {
+    const int lo = a < c ? a : c, hi = a < c ? c : a;
+    L.A[a][c] = L.s_sum[lo * 6 - (lo * (lo - 1)) / 2 + (hi - lo)];  // the row-major upper triangle, mirrored
+    double d = 0.0, fr = 0.0, ft = 0.0;
+    for (int j = 0; j < n_rows; ++j) d += L.C[j][a] * L.C[j][c];
+    for (int j = 0; j < n_rot; ++j) fr += L.C[j][a] * L.C[j][c];
+    for (int j = n_rot; j < n_rows; ++j) ft += L.C[j][a] * L.C[j][c];
+    L.P[a][c] = (a == c ? 1.0 : 0.0) - d;
+    L.F[0][a][c] = fr;
+    L.F[1][a][c] = ft;
+  } else if (t == 64 || t == 65) {  // mu_r, mu_t: the next wave, beside the 36 lanes
+    const int o = t == 64 ? 0 : 3;
+    const double d0 = L.s_sum[o * 6 - (o * (o - 1)) / 2], d1 = L.s_sum[(o + 1) * 6 - ((o + 1) * o) / 2], d2 = L.s_sum[(o + 2) * 6 - ((o + 2) * (o + 1)) / 2];
+    double mu = ((d0 + d1) + d2) / 3.0;
+    if (!(fabs(mu) < __builtin_huge_val()) || mu == 0.0) mu = 1.0;  // zero or not finite (a NaN fails the comparison)
+    L.mu[t - 64] = mu;
+  }
+  __syncthreads();
+  if (t < 36) {
+    double m = 0.0;
+    for (int k = 0; k < 6; ++k) m += L.A[a][k] * L.P[k][c];
+    L.M[a][c] = m;
+  }
+  __syncthreads();
+  if (t < 36 && a <= c) {
+    double v = 0.0;
+    for (int k = 0; k < 6; ++k) v += L.P[a][k] * L.M[k][c];
+    v = (v + L.mu[0] * L.F[0][a][c]) + L.mu[1] * L.F[1][a][c];
+    part[(size_t)(a * 6 - (a * (a - 1)) / 2 + (c - a)) * nb] = v;
+  } else if (t >= 64 && t < 70) {
+    const int r = t - 64;
+    double g = 0.0;
+    for (int k = 0; k < 6; ++k) g += L.P[r][k] * L.s_sum[21 + k];
+    part[(size_t)(21 + r) * nb] = g;
+  }
+  // the other nb - 1 columns: +0.0, whose fold is exact (every thread read its share of them in ne_fold, in front of two barriers)
+  for (int k = t; k < kNeComps * (nb - 1); k += kBlock) part[(size_t)(k / (nb - 1)) * nb + 1 + k % (nb - 1)] = 0.0;
+}
+
+}  // namespace kern
+}  // namespace o3s

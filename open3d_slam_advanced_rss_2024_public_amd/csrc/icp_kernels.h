@@ -2590,10 +2590,38 @@ __device__ __forceinline__ void post_state(const IcpState* S /*LDS*/, const IcpS
   }
 }
 
+// The fold of the [27][nb] block partials of the normal equations, block-wide (kBlock threads, all of them call it; the caller's
+// next barrier publishes s_sum): the one order in which the 27 sums are ever formed — solve_body's, and k_constrain's
+// (degeneracy_dev.h), which has to see the very A and b that k_solve would have seen.
+__device__ __forceinline__ void ne_fold(const double* __restrict__ part, int nb, double* __restrict__ s_a, double* __restrict__ s_b,
+                                        double* __restrict__ s_sum) {
+  using Sum = BlockSum<kNeComps, kBlock>;
+  static_assert(kMaxPartialBlocks <= 2 * kBlock, "two partial blocks per thread at most");
+  const int nbm1 = nb > 0 ? nb - 1 : 0;
+  const int t = threadIdx.x;
+  double v[kNeComps];
+#pragma unroll
+  for (int c = 0; c < kNeComps; ++c) v[c] = 0.0;
+  if (t < kBlock) {
+#pragma unroll
+    for (int c = 0; c < kNeComps; ++c) v[c] = part[c * nb + min(t, nbm1)];
+#pragma unroll
+    for (int c = 0; c < kNeComps; ++c) v[c] = t < nb ? v[c] : 0.0;
+    if (nb > kBlock) {  // uniform
+      double u[kNeComps];
+#pragma unroll
+      for (int c = 0; c < kNeComps; ++c) u[c] = part[c * nb + min(t + kBlock, nbm1)];
+#pragma unroll
+      for (int c = 0; c < kNeComps; ++c) v[c] += (t + kBlock < nb) ? u[c] : 0.0;
+    }
+  }
+  Sum::run(v, s_a, s_b);
+  if (t < kNeComps) s_sum[t] = Sum::total(s_b, t);
+}
+
 __device__ __forceinline__ void solve_body(const double* __restrict__ part, int nb, int N, const ChainParams& cp, IcpState* __restrict__ st,
                                            float* __restrict__ trace_T, float* __restrict__ trace_limit, int64_t* __restrict__ trace_kept,
                                            int trace_cap, int update_pose, HostPost* __restrict__ post, SolveLds& L, const SolveOverride* ov /*LDS or null*/) {
-  using Sum = BlockSum<kNeComps, kBlock>;
   constexpr int kWords = kStateWords;
   IcpState& s_st = L.st;
   for (int k = threadIdx.x; k < kWords; k += kBlock) reinterpret_cast<uint32_t*>(&s_st)[k] = reinterpret_cast<const uint32_t*>(st)[k];
@@ -2602,29 +2630,7 @@ __device__ __forceinline__ void solve_body(const double* __restrict__ part, int 
   // s_waitcnt, i.e. one memory round trip per component) and coalesced along the block index; the 27 x 256 values are
   // then summed through LDS in a fixed order.
   const bool sums_formed = part == nullptr;  // the sharded chain's front has put the 27 sums into L.s_sum (and says so through `ov`)
-  if (!sums_formed) {
-    static_assert(kMaxPartialBlocks <= 2 * kBlock, "two partial blocks per thread at most");
-    const int nbm1 = nb > 0 ? nb - 1 : 0;
-    const int t = threadIdx.x;
-    double v[kNeComps];
-#pragma unroll
-    for (int c = 0; c < kNeComps; ++c) v[c] = 0.0;
-    if (t < kBlock) {
-#pragma unroll
-      for (int c = 0; c < kNeComps; ++c) v[c] = part[c * nb + min(t, nbm1)];
-#pragma unroll
-      for (int c = 0; c < kNeComps; ++c) v[c] = t < nb ? v[c] : 0.0;
-      if (nb > kBlock) {  // uniform
-        double u[kNeComps];
-#pragma unroll
-        for (int c = 0; c < kNeComps; ++c) u[c] = part[c * nb + min(t + kBlock, nbm1)];
-#pragma unroll
-        for (int c = 0; c < kNeComps; ++c) v[c] += (t + kBlock < nb) ? u[c] : 0.0;
-      }
-    }
-    Sum::run(v, L.s_a, L.s_b);
-    if (t < kNeComps) L.s_sum[t] = Sum::total(L.s_b, t);
-  }
+  if (!sums_formed) ne_fold(part, nb, L.s_a, L.s_b, L.s_sum);
   if (ov && threadIdx.x == 0) {  // what this launch formed: the state's copy is a launch old (barrier above: the staging is complete)
     if (ov->has_limit) s_st.limit = ov->limit;
     s_st.kept = ov->kept;

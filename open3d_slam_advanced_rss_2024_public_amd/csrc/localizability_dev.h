@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "icp_kernels.h"
 
 #pragma clang fp contract(off)
@@ -60,33 +62,44 @@ __device__ __forceinline__ void loc_cross(const float (&p)[3], const float (&n)[
   c[1] = p[2] * n[0] - p[0] * n[2];
   c[2] = p[0] * n[1] - p[1] * n[0];
 }
-// the chain's state as k_cov reads it
-__device__ __forceinline__ void loc_chain_state(bool chain, const IcpState* __restrict__ st, float (&T)[16], float& limit, float& mpx, float& mpy,
-                                                float& mpz) {
+// the chain's state as k_cov reads it.  live (the degeneracy-aware chain, degeneracy_dev.h): the kernel runs INSIDE an iteration, in
+// front of k_solve, so the pose its pairs were formed under is still T_iter (the header) — k_solve moves those very words to
+// T_prev, which is what the pass behind the chain reads: the same bits either way.  false: the chain has ended, or an earlier
+// kernel of this iteration failed it, and the caller returns at once
+__device__ __forceinline__ bool loc_chain_state(bool chain, int live, const IcpState* __restrict__ st, float (&T)[16], float& limit, float& mpx,
+                                                float& mpy, float& mpz) {
 #pragma unroll
   for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.f : 0.f;
   limit = kInfF, mpx = mpy = mpz = 0.f;
   if (chain) {
     const float hv = hdr_load(st);
+    if (live) {  // uniform
+      if (hdr_i(hv, H_DONE) || hdr_i(hv, H_STATUS)) return false;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) T[k] = st->T_prev[k];
+      for (int k = 0; k < 16; ++k) T[k] = hdr_f(hv, k);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) T[k] = st->T_prev[k];
+    }
     limit = hdr_f(hv, H_LIMIT);
     mpx = hdr_f(hv, H_MP), mpy = hdr_f(hv, H_MP + 1), mpz = hdr_f(hv, H_MP + 2);
   }
+  return true;
 }
 
 __global__ void __launch_bounds__(kBlock) k_loc_hessian(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz, int N,
                                                         const float4* __restrict__ mn, const int32_t* __restrict__ pos, const float* __restrict__ d2,
                                                         float max_out_r2, const IcpState* __restrict__ st, const float* __restrict__ ext_p,
                                                         const float* __restrict__ ext_n, double* __restrict__ part /*[12][grid]*/,
-                                                        unsigned long long* __restrict__ t_start /*wall_clock64 of block 0's start*/) {
+                                                        unsigned long long* __restrict__ t_start /*wall_clock64 of block 0's start*/,
+                                                        int live /*inside an iteration: loc_chain_state*/) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *t_start = wall_clock64();
   using Sum = BlockSum<kLocTri, kBlock>;  // two passes of six
   __shared__ double s_a[Sum::kWordsA];
   __shared__ double s_b[Sum::kWordsB];
   const bool chain = ext_p == nullptr;  // uniform
   float T[16], limit, mpx, mpy, mpz;
-  loc_chain_state(chain, st, T, limit, mpx, mpy, mpz);
+  if (!loc_chain_state(chain, live, st, T, limit, mpx, mpy, mpz)) return;
   double accT[kLocTri], accR[kLocTri];
 #pragma unroll
   for (int c = 0; c < kLocTri; ++c) accT[c] = accR[c] = 0.0;
@@ -196,8 +209,13 @@ __device__ __forceinline__ void loc_eig3(const double* __restrict__ tri, double*
 
 // One block: component c is folded by wave c % 4 — lane l adds the partials of blocks l, l + 64, ... in order, then the wave's DPP
 // tree — so the order is a function of the number of blocks alone (k_cov_post).
-__global__ void __launch_bounds__(kBlock) k_loc_eig(const double* __restrict__ part /*[12][nb]*/, int nb, double* __restrict__ dirs /*eval[6], evec[6][3]*/) {
+__global__ void __launch_bounds__(kBlock) k_loc_eig(const double* __restrict__ part /*[12][nb]*/, int nb, double* __restrict__ dirs /*eval[6], evec[6][3]*/,
+                                                    const IcpState* __restrict__ st_live /*non-null: inside an iteration*/) {
   __shared__ double s_sum[kLocSums];
+  if (st_live) {  // uniform
+    const float hv = hdr_load(st_live);
+    if (hdr_i(hv, H_DONE) || hdr_i(hv, H_STATUS)) return;
+  }
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   for (int c = w; c < kLocSums; c += kBlock / 64) {
     double s = 0.0;
@@ -216,14 +234,14 @@ __global__ void __launch_bounds__(kBlock) k_loc_contrib(const float* __restrict_
                                                         float max_out_r2, const IcpState* __restrict__ st, const float* __restrict__ ext_p,
                                                         const float* __restrict__ ext_n, const double* __restrict__ dirs, double filter_min,
                                                         double strong_min, double* __restrict__ part /*[12][grid]*/,
-                                                        unsigned long long* __restrict__ part_cnt /*[7][grid]*/) {
+                                                        unsigned long long* __restrict__ part_cnt /*[7][grid]*/, int live) {
   using Sum = BlockSum<kLocTri, kBlock>;
   __shared__ double s_a[Sum::kWordsA];
   __shared__ double s_b[Sum::kWordsB];
   __shared__ uint32_t s_cnt[kLocCounts][kBlock / 64];
   const bool chain = ext_p == nullptr;  // uniform
   float T[16], limit, mpx, mpy, mpz;
-  loc_chain_state(chain, st, T, limit, mpx, mpy, mpz);
+  if (!loc_chain_state(chain, live, st, T, limit, mpx, mpy, mpz)) return;
   double dir[6][3];  // uniform: fully unrolled subscripts below, so registers
 #pragma unroll
   for (int j = 0; j < 6; ++j)
@@ -326,4 +344,16 @@ __global__ void __launch_bounds__(kBlock) k_loc_post(const double* __restrict__ 
 }
 
 }  // namespace kern
+
+// the work area, in doubles: pass 1's partials [12][blocks], the six directions, pass 2's partials [12][blocks] and counts
+// [7][blocks], what k_loc_post posts, k_loc_hessian's start stamp.  (Here, not in localizability_impl.h: the degeneracy-aware chain
+// launches the first three kernels from the issue loop, which stands in front of that header.)
+constexpr size_t kLocOffDirs = (size_t)kMaxPartialBlocks * kern::kLocSums;
+constexpr size_t kLocOffPart2 = kLocOffDirs + kern::kLocDirs;
+constexpr size_t kLocOffCnt = kLocOffPart2 + (size_t)kMaxPartialBlocks * kern::kLocSums;
+constexpr size_t kLocOffOut = kLocOffCnt + (size_t)kMaxPartialBlocks * kern::kLocCounts;
+constexpr size_t kLocOffStart = kLocOffOut + kern::kLocPostVals;
+constexpr size_t kLocBufBytes = (kLocOffStart + 1) * sizeof(double);
+// the grid of both passes (k_cov's)
+inline int loc_blocks(int n) { return std::max(1, std::min(kMaxPartialBlocks, (n + kern::kBlock * kern::kNePPT - 1) / (kern::kBlock * kern::kNePPT))); }
 }  // namespace o3s

@@ -5,15 +5,6 @@
 
 namespace {
 
-// the work area, in doubles: pass 1's partials [12][blocks], the six directions, pass 2's partials [12][blocks] and counts
-// [7][blocks], what k_loc_post posts, k_loc_hessian's start stamp
-constexpr size_t kLocOffDirs = (size_t)kMaxPartialBlocks * kern::kLocSums;
-constexpr size_t kLocOffPart2 = kLocOffDirs + kern::kLocDirs;
-constexpr size_t kLocOffCnt = kLocOffPart2 + (size_t)kMaxPartialBlocks * kern::kLocSums;
-constexpr size_t kLocOffOut = kLocOffCnt + (size_t)kMaxPartialBlocks * kern::kLocCounts;
-constexpr size_t kLocOffStart = kLocOffOut + kern::kLocPostVals;
-constexpr size_t kLocBufBytes = (kLocOffStart + 1) * sizeof(double);
-
 const char* loc_params_error(const o3s_localizability_params& p) {
   if (!(p.filter_min >= 0.0 && p.filter_min <= p.strong_min && p.strong_min <= 1.0)) return "localizability: 0 <= filter_min <= strong_min <= 1 does not hold";
   if (!(std::isfinite(p.sum_all_min) && std::isfinite(p.sum_strong_min) && std::isfinite(p.sum_partial_min)))
@@ -26,7 +17,7 @@ const char* loc_params_error(const o3s_localizability_params& p) {
 // the four launches on the handle's stream and the wait for k_loc_post's values.  ext_*: the module-level source (device, 3 x n AoS)
 int loc_run(o3s_icp* h, int n, const float* rx, const float* ry, const float* rz, float max_out_r2, const float* ext_p, const float* ext_n,
             const o3s_localizability_params& p, o3s_localizability* out) {
-  const int nb = std::max(1, std::min(kMaxPartialBlocks, nblocks(n, kern::kBlock * kern::kNePPT)));  // k_cov's grid
+  const int nb = loc_blocks(n);
   HIP_TRY(h, h->d_loc.ensure(kLocBufBytes));
   double* base = h->d_loc.as<double>();
   double *part1 = base, *dirs = base + kLocOffDirs, *part2 = base + kLocOffPart2, *vals = base + kLocOffOut;
@@ -35,10 +26,10 @@ int loc_run(o3s_icp* h, int n, const float* rx, const float* ry, const float* rz
   const IcpState* st = ext_p ? nullptr : h->d_state.as<IcpState>();
   const kern::LocThresholds th{p.filter_min, p.strong_min, p.sum_all_min, p.sum_strong_min, p.sum_partial_min};
   hipLaunchKernelGGL(kern::k_loc_hessian, dim3(nb), dim3(kern::kBlock), 0, h->stream, rx, ry, rz, n, h->d_mn.as<float4>(), h->d_pos.as<int32_t>(),
-                     h->d_d2.as<float>(), max_out_r2, h->d_state.as<IcpState>(), ext_p, ext_n, part1, t_start);
-  hipLaunchKernelGGL(kern::k_loc_eig, dim3(1), dim3(kern::kBlock), 0, h->stream, part1, nb, dirs);
+                     h->d_d2.as<float>(), max_out_r2, h->d_state.as<IcpState>(), ext_p, ext_n, part1, t_start, 0);
+  hipLaunchKernelGGL(kern::k_loc_eig, dim3(1), dim3(kern::kBlock), 0, h->stream, part1, nb, dirs, (const IcpState*)nullptr);
   hipLaunchKernelGGL(kern::k_loc_contrib, dim3(nb), dim3(kern::kBlock), 0, h->stream, rx, ry, rz, n, h->d_mn.as<float4>(), h->d_pos.as<int32_t>(),
-                     h->d_d2.as<float>(), max_out_r2, h->d_state.as<IcpState>(), ext_p, ext_n, dirs, p.filter_min, p.strong_min, part2, cnt);
+                     h->d_d2.as<float>(), max_out_r2, h->d_state.as<IcpState>(), ext_p, ext_n, dirs, p.filter_min, p.strong_min, part2, cnt, 0);
   const uint32_t seq = h->cov_mb.next();
   hipLaunchKernelGGL(kern::k_loc_post, dim3(1), dim3(kern::kBlock), 0, h->stream, part2, cnt, nb, dirs, th, st, t_start, vals, h->cov_mb.dev, seq);
   HIP_TRY(h, hipGetLastError());

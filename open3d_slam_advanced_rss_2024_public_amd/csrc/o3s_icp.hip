@@ -20,6 +20,8 @@
 #include "icp_shard_kernels.h"
 #include "icp_types.h"
 #include "localizability_dev.h"
+#include "degeneracy_dev.h"
+#include "../../include/degeneracy/o3s_degeneracy.h"
 
 #pragma clang fp contract(off)
 
@@ -83,8 +85,8 @@ struct o3s_icp {
   int device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
   std::string err;
-  // Every DevBuf of the handle but d_loc reports its moves here; the graph key carries the value, so a graph is never replayed
-  // after ANY buffer a captured kernel points at has moved (the key's pointer list alone missed d_cand & co.).
+  // Every DevBuf of the handle but d_loc (which has loc_gen, below) reports its moves here; the graph key carries the value, so a
+  // graph is never replayed after ANY buffer a captured kernel points at has moved (the key's pointer list alone missed d_cand & co.).
   uint64_t alloc_gen = 0;
 
   // reference (matcher index)
@@ -136,9 +138,18 @@ struct o3s_icp {
   float last_max_out_r2 = 0.f;  // the kept-pair predicate's MaxDist bound of that compute
   float last_step[16] = {0};    // ... and its last iteration's step (IcpState::dT)
   unsigned long long cov_t_start = 0, cov_t_end = 0;  // wall_clock64 stamps of the last covariance pass (k_cov's start, k_cov_post's end)
-  // localizability analysis (localizability_impl.h): the work area of its four kernels, allocated by the first call.  No captured
-  // kernel points into it, so it is not wired to alloc_gen and a first call leaves the chain's graph alone
-  DevBuf d_loc;
+  // localizability analysis (localizability_impl.h): the work area of its four kernels, allocated by the first call or when the
+  // degeneracy mode ANALYSE is set.  Only that mode's captured kernels point into it, so its moves are counted apart and the graph
+  // key carries the count in that mode alone: a first analysis behind an unconstrained compute leaves the chain's graph alone
+  uint64_t loc_gen = 0;
+  DevBuf d_loc{&loc_gen};
+  // degeneracy-aware step (degeneracy_impl.h): the mode of the later computes; the device area (the set the last constrained
+  // iteration used, then one mask per iteration) exists only once a mode other than OFF has been set
+  o3s_degeneracy_config deg{};          // (mode 0 = OFF)
+  kern::DegFixed deg_fixed{};           // FIXED: the caller's set as k_constrain takes it
+  uint64_t deg_gen = 0;                 // moves with every change of mode, set or parameters: part of the graph key
+  bool deg_trace_valid = false;         // the last successful compute ran with a mode other than OFF
+  DevBuf d_deg{&alloc_gen};
   // registration fitness (o3s_icp_evaluate_resident): where the last successful compute left the reading.  pose_valid: that compute's
   // T_iter is in last_T_iter and nothing has replaced the reading or the reference since; r_is_call: d_r still holds the reading as
   // that compute prepared it (T0 . p in its processing order) — an evaluation at an explicit pose prepares it anew
@@ -175,6 +186,8 @@ struct o3s_icp {
   struct GraphKey {
     int N = -1, iters = -1, nb = -1, has_n = -1;
     uint64_t gen = 0;
+    uint64_t deg = 0;  // 0: the degeneracy mode is OFF; else deg_gen
+    uint64_t loc = 0;  // mode ANALYSE: loc_gen (the captured analysis kernels point into d_loc); else 0
     const void* ptrs[8] = {nullptr};
     ChainParams cp{};
     GridParams g{};
@@ -725,6 +738,36 @@ inline bool sel_partial(const ChainArgs& a) {
   return a.nb_cls > kern::kFinThreads && !(pe && std::atoi(pe) == 0);
 }
 
+// the degeneracy-aware step's launches between the normal equations and k_solve (degeneracy_dev.h): k_constrain, in ANALYSE mode
+// behind the three analysis kernels on this iteration's kept pairs.  `set`: the module-level minimiser's own set (no trace)
+constexpr int kDegMaskCap = 4096;  // ensure_trace's bound
+constexpr size_t kDegBufBytes = sizeof(kern::DegLast) + (size_t)kDegMaskCap * 4;
+void launch_constrain(o3s_icp* h, const ChainArgs& a, int nb, hipStream_t s, const kern::DegFixed* set = nullptr) {
+  IcpState* st = h->d_state.as<IcpState>();
+  kern::DegLast* last = h->d_deg.as<kern::DegLast>();
+  uint32_t* masks = set ? nullptr : reinterpret_cast<uint32_t*>(h->d_deg.as<char>() + sizeof(kern::DegLast));
+  kern::LocThresholds th{};
+  if (set || h->deg.mode == O3S_DEGENERACY_FIXED) {
+    hipLaunchKernelGGL(kern::k_constrain, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), nb, st, set ? *set : h->deg_fixed,
+                       (const double*)nullptr, 0, (const double*)nullptr, th, 0, last, masks, kDegMaskCap);
+    return;
+  }
+  const o3s_localizability_params& p = h->deg.loc_params;
+  th = kern::LocThresholds{p.filter_min, p.strong_min, p.sum_all_min, p.sum_strong_min, p.sum_partial_min};
+  const int nbl = loc_blocks(a.N);
+  double* base = h->d_loc.as<double>();
+  double *part1 = base, *dirs = base + kLocOffDirs, *part2 = base + kLocOffPart2;
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(base + kLocOffCnt);
+  unsigned long long* t_start = reinterpret_cast<unsigned long long*>(base + kLocOffStart);
+  hipLaunchKernelGGL(kern::k_loc_hessian, dim3(nbl), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, h->d_mn.as<float4>(), h->d_pos.as<int32_t>(),
+                     h->d_d2.as<float>(), a.cp.max_out_r2, st, (const float*)nullptr, (const float*)nullptr, part1, t_start, 1);
+  hipLaunchKernelGGL(kern::k_loc_eig, dim3(1), dim3(kern::kBlock), 0, s, part1, nbl, dirs, (const IcpState*)st);
+  hipLaunchKernelGGL(kern::k_loc_contrib, dim3(nbl), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, h->d_mn.as<float4>(), h->d_pos.as<int32_t>(),
+                     h->d_d2.as<float>(), a.cp.max_out_r2, st, (const float*)nullptr, (const float*)nullptr, dirs, p.filter_min, p.strong_min, part2, cnt, 1);
+  hipLaunchKernelGGL(kern::k_constrain, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), nb, st, kern::DegFixed{}, part2, nbl, dirs, th,
+                     (int)h->deg.min_category, last, masks, kDegMaskCap);
+}
+
 void launch_iteration(o3s_icp* h, const ChainArgs& a, bool stats, hipEvent_t* ev /*6 events or null*/, int it) {
   IcpState* st = h->d_state.as<IcpState>();
   hipStream_t s = h->stream;
@@ -746,6 +789,7 @@ void launch_iteration(o3s_icp* h, const ChainArgs& a, bool stats, hipEvent_t* ev
                        h->d_d2.as<float>(), h->d_ne.as<double>(), h->d_hist.as<uint32_t>());
     if (ev) (void)hipEventRecord(ev[3], s);
     if (ev) (void)hipEventRecord(ev[4], s);
+    if (h->deg.mode != O3S_DEGENERACY_OFF) launch_constrain(h, a, a.nb_fused, s);  // (a profiled call times it with k_solve)
     hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), a.nb_fused, a.N, a.cp, st, h->d_trace_T.as<float>(),
                        h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 1, h->post.dev);
     if (ev) (void)hipEventRecord(ev[5], s);
@@ -768,6 +812,7 @@ void launch_iteration(o3s_icp* h, const ChainArgs& a, bool stats, hipEvent_t* ev
   hipLaunchKernelGGL(kern::k_normal_eq, dim3(a.nb_part), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, h->d_mq.as<float4>(),
                      h->d_mn.as<float4>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), a.cp, st, h->d_ne.as<double>(), h->d_hist.as<uint32_t>());
   if (ev) (void)hipEventRecord(ev[4], s);
+  if (h->deg.mode != O3S_DEGENERACY_OFF) launch_constrain(h, a, a.nb_part, s);
   hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), a.nb_part, a.N, a.cp, st, h->d_trace_T.as<float>(),
                      h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 1, h->post.dev);
   if (ev) (void)hipEventRecord(ev[5], s);
@@ -820,7 +865,7 @@ void init_state(IcpState& st) {
 }
 
 bool graph_key_equal(const o3s_icp::GraphKey& a, const o3s_icp::GraphKey& b) {
-  return a.N == b.N && a.iters == b.iters && a.nb == b.nb && a.has_n == b.has_n && a.gen == b.gen && std::memcmp(a.ptrs, b.ptrs, sizeof(a.ptrs)) == 0 &&
+  return a.N == b.N && a.iters == b.iters && a.nb == b.nb && a.has_n == b.has_n && a.gen == b.gen && a.deg == b.deg && a.loc == b.loc && std::memcmp(a.ptrs, b.ptrs, sizeof(a.ptrs)) == 0 &&
          std::memcmp(&a.cp, &b.cp, sizeof(ChainParams)) == 0 && std::memcmp(&a.g, &b.g, sizeof(GridParams)) == 0 && a.have_grid1 == b.have_grid1 &&
          std::memcmp(&a.g1, &b.g1, sizeof(GridParams)) == 0;
 }
@@ -929,9 +974,12 @@ int start_call(o3s_icp* h, const float* T_init) {
   Call& c = h->call;
   c.live = false;
   h->cov_valid = h->elements_valid = h->pose_valid = false;
+  h->deg_trace_valid = false;
 #ifdef O3S_TEST_HOOKS
   h->looks.clear();
 #endif
+  if (h->shard.active && h->deg.mode != O3S_DEGENERACY_OFF)
+    return fail(h, O3S_ERR_BAD_CONFIG, "the degeneracy-aware step is not available in the sharded mode");
   if (!h->ref_ready) return fail(h, O3S_ERR_NOT_INITIALIZED, "compute before a successful init_reference");
   if (!h->reading_ready || h->N <= 0) return fail(h, O3S_ERR_EMPTY_READING, "the reading point cloud is empty");
   if (!h->ref_has_normals) return fail(h, O3S_ERR_BAD_SHAPE, "point-to-plane needs reference normals");
@@ -958,6 +1006,8 @@ int start_call(o3s_icp* h, const float* T_init) {
 
   if (++h->call_seq == 0) ++h->call_seq;  // what this call's posts carry (k_read_prep writes it into the state)
   c.issued = 0;
+  // the degeneracy area starts a call empty: no set used yet, every mask 0 (o3s_icp_set_degeneracy allocated it)
+  if (h->deg.mode != O3S_DEGENERACY_OFF) HIP_TRY(h, hipMemsetAsync(h->d_deg.p, 0, kDegBufBytes, h->stream));
   rc = prepare_reading(h, c.T0, h->cfg.sort_queries != 0 && h->cfg.matcher == 0 && !h->reading_presorted, /*reset_chain=*/true, cp.use_differential != 0);
   if (rc != O3S_OK) return rc;
   c.a = chain_args(h, cp);
@@ -986,6 +1036,8 @@ int start_call(o3s_icp* h, const float* T_init) {
     key.iters = chunk;
     key.nb = c.a.nb_fused > 0 ? -c.a.nb_fused : c.a.nb_part;  // the fused and the two-kernel chain are different graphs
     key.has_n = c.a.has_n ? 1 : 0;
+    key.deg = h->deg.mode != O3S_DEGENERACY_OFF ? h->deg_gen : 0;
+    key.loc = h->deg.mode == O3S_DEGENERACY_ANALYSE ? h->loc_gen : 0;
     key.gen = h->alloc_gen;  // every ensure() of this call has already run (ensure_iteration_buffers / ensure_trace / prepare)
     key.ptrs[0] = h->d_r.p;
     key.ptrs[1] = h->d_pos.p;
@@ -1279,6 +1331,7 @@ int compute_finish(o3s_icp* h, float* T_out, o3s_icp_stats* stats) {
     std::memset(h->cov, 0, sizeof(h->cov));  // ErrorMinimizer::getCovariance of the base class (LPM/ErrorMinimizer.cpp:266-270)
   }
   h->cov_valid = h->elements_valid = true;
+  h->deg_trace_valid = h->deg.mode != O3S_DEGENERACY_OFF;
   std::memcpy(h->last_T_iter, st.T_iter, sizeof(st.T_iter));
   h->pose_valid = h->r_is_call = true;
   std::memcpy(T_out, out, sizeof(out));
@@ -1998,8 +2051,9 @@ int o3s_icp_outlier_weights(o3s_icp* h, const float* reading_normals, const int3
   return O3S_OK;
 }
 
-int o3s_icp_minimize(o3s_icp* h, const float* reading_xyzw, const int32_t* ids, const float* dists2, const float* weights, int64_t N,
-                     float T_out[16], float A_out[36], float b_out[6], float x_out[6]) {
+// o3s_icp_minimize, and o3s_icp_minimize_degeneracy (degeneracy_impl.h) with `set`: k_constrain in front of k_solve
+static int minimize_impl(o3s_icp* h, const float* reading_xyzw, const int32_t* ids, const float* dists2, const float* weights, int64_t N,
+                         const kern::DegFixed* set, float T_out[16], float A_out[36], float b_out[6], float x_out[6]) {
   if (!h || !reading_xyzw || !ids || !dists2 || !weights || !T_out) return O3S_ERR_BAD_ARGUMENT;
   if (!h->ref_ready) return fail(h, O3S_ERR_NOT_INITIALIZED, "minimize before a successful init_reference");
   if (!h->ref_has_normals) return fail(h, O3S_ERR_BAD_SHAPE, "point-to-plane needs reference normals");
@@ -2037,6 +2091,7 @@ int o3s_icp_minimize(o3s_icp* h, const float* reading_xyzw, const int32_t* ids, 
                      (const CandRec*)nullptr, (const uint32_t*)nullptr);
   hipLaunchKernelGGL(kern::k_normal_eq, dim3(a.nb_part), dim3(kern::kBlock), 0, h->stream, a.rx, a.ry, a.rz, a.N, h->d_mq.as<float4>(),
                      h->d_mn.as<float4>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), cp, st, h->d_ne.as<double>(), (uint32_t*)nullptr);
+  if (set) launch_constrain(h, a, a.nb_part, h->stream, set);
   hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, h->stream, h->d_ne.as<double>(), a.nb_part, a.N, cp, st,
                      h->d_trace_T.as<float>(), h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 0, (HostPost*)nullptr);
   HIP_TRY(h, hipGetLastError());
@@ -2049,6 +2104,11 @@ int o3s_icp_minimize(o3s_icp* h, const float* reading_xyzw, const int32_t* ids, 
   if (b_out) std::memcpy(b_out, s.b, sizeof(s.b));
   if (x_out) std::memcpy(x_out, s.x, sizeof(s.x));
   return O3S_OK;
+}
+
+int o3s_icp_minimize(o3s_icp* h, const float* reading_xyzw, const int32_t* ids, const float* dists2, const float* weights, int64_t N,
+                     float T_out[16], float A_out[36], float b_out[6], float x_out[6]) {
+  return minimize_impl(h, reading_xyzw, ids, dists2, weights, N, nullptr, T_out, A_out, b_out, x_out);
 }
 
 int o3s_icp_get_covariance(const o3s_icp* h, double cov36[36]) {
@@ -2131,3 +2191,4 @@ int64_t o3s_icp_get_error_elements(o3s_icp* h, float* reading_c, float* referenc
 }  // extern "C"
 
 #include "localizability_impl.h"
+#include "degeneracy_impl.h"

@@ -488,6 +488,56 @@ class ICP(_lib.Handle):
         self._check(self._L.o3s_localizability_estimate(self._h, _fp(p), _fp(n), p.shape[0], C.byref(pc), C.byref(out)))
         return loc.Localizability.from_c(out)
 
+    def set_degeneracy(self, mode, fixed_set=None, params=None, min_category: int = 2):
+        """o3s_icp_set_degeneracy: how the later computes on this handle treat directions the scan does not constrain.
+        mode: localizability.DEGENERACY_OFF / DEGENERACY_FIXED (fixed_set: a DegeneracySet, the same in every iteration) /
+        DEGENERACY_ANALYSE (params: LocalizabilityParams with the three sums set; every iteration analyses its own kept pairs and
+        constrains the directions of category < min_category)."""
+        from . import localizability as loc
+
+        loc._bind(self._L)
+        fs = None if fixed_set is None else C.byref(fixed_set.to_c())
+        pc = None if params is None else C.byref(params.to_c())
+        self._check(self._L.o3s_icp_set_degeneracy(self._h, int(mode), fs, pc, int(min_category)))
+
+    def degeneracy_trace(self) -> np.ndarray:
+        """o3s_icp_degeneracy_trace: one 6-bit mask per iteration of the last successful compute (bit j < 3 translation direction j,
+        bit 3 + j rotation direction j); empty when the mode was OFF."""
+        from . import localizability as loc
+
+        loc._bind(self._L)
+        masks = np.zeros(4096, np.int32)
+        n = int(self._L.o3s_icp_degeneracy_trace(self._h, _ip(masks), masks.shape[0]))
+        return masks[:n].copy()
+
+    def last_degeneracy_set(self):
+        """The set the last constrained iteration of the last successful compute used (o3s_icp_get_degeneracy), as a
+        localizability.DegeneracySet in the mask's order."""
+        from . import localizability as loc
+
+        loc._bind(self._L)
+        out = loc.DegeneracySetC()
+        self._check(self._L.o3s_icp_get_degeneracy(self._h, None, C.byref(out)))
+        return loc.DegeneracySet.from_c(out)
+
+    def minimize_degeneracy(self, reading_xyz, ids, dists2, weights, dset):
+        """minimize() under C x = 0 for the directions of `dset` (o3s_icp_minimize_degeneracy) -> (T 4x4, A' 6x6, b', x)."""
+        from . import localizability as loc
+
+        loc._bind(self._L)
+        q = as_xyzw(reading_xyz)
+        ids = np.ascontiguousarray(ids, np.int32)
+        d2 = np.ascontiguousarray(dists2, np.float32)
+        w = np.ascontiguousarray(weights, np.float32)
+        T = np.zeros(16, np.float32)
+        A = np.zeros(36, np.float32)
+        b = np.zeros(6, np.float32)
+        x = np.zeros(6, np.float32)
+        sc = dset.to_c()
+        self._check(self._L.o3s_icp_minimize_degeneracy(self._h, _fp(q), _ip(ids), _fp(d2), _fp(w), q.shape[0], C.byref(sc), _fp(T), _fp(A),
+                                                        _fp(b), _fp(x)))
+        return _from_colmajor(T), A.reshape(6, 6).T.copy(), b, x
+
     def get_max_num_iterations_reached(self) -> bool:
         """ICP::getMaxNumIterationsReached (PointMatcher.h:786)."""
         return self.stats.max_iters_reached

@@ -21,8 +21,11 @@ from . import _lib
 LOCALIZABLE, PARTIALLY, NOT_LOCALIZABLE = 2, 1, 0
 
 # the mapper's degeneracyPolicy (cpp/o3s_mapper.hpp, DegeneracyPolicy)
-OFF, REPORT, REMAP = "Off", "Report", "Remap"
-POLICIES = (OFF, REPORT, REMAP)
+OFF, REPORT, REMAP, CONSTRAIN = "Off", "Report", "Remap", "Constrain"
+POLICIES = (OFF, REPORT, REMAP, CONSTRAIN)
+
+# o3s_icp_set_degeneracy's modes (include/degeneracy/o3s_degeneracy.h)
+DEGENERACY_OFF, DEGENERACY_FIXED, DEGENERACY_ANALYSE = 0, 1, 2
 
 
 class LocalizabilityParamsC(C.Structure):   # o3s_localizability_params
@@ -34,6 +37,40 @@ class LocalizabilityC(C.Structure):   # o3s_localizability
     _fields_ = [("eval", C.c_double * 6), ("evec", (C.c_double * 3) * 6), ("sum_all", C.c_double * 6), ("sum_strong", C.c_double * 6),
                 ("n_strong", C.c_int64 * 6), ("category", C.c_int32 * 6), ("kept", C.c_int64), ("centre", C.c_double * 3), ("gpu_ms", C.c_float),
                 ("reserved", C.c_int32)]
+
+
+class DegeneracySetC(C.Structure):   # o3s_degeneracy_set
+    _fields_ = [("n_rot", C.c_int32), ("n_trans", C.c_int32), ("rot", (C.c_double * 3) * 3), ("trans", (C.c_double * 3) * 3)]
+
+
+class DegeneracyConfigC(C.Structure):   # o3s_degeneracy_config
+    _fields_ = [("mode", C.c_int32), ("min_category", C.c_int32), ("fixed_set", DegeneracySetC), ("loc_params", LocalizabilityParamsC)]
+
+
+@dataclass
+class DegeneracySet:
+    """o3s_degeneracy_set: up to three unit rotation directions and up to three unit translation directions, (n, 3) float64 each,
+    mutually orthogonal inside a group.  The ICP step is solved with no component along any of them."""
+    rot: np.ndarray = field(default_factory=lambda: np.zeros((0, 3)))
+    trans: np.ndarray = field(default_factory=lambda: np.zeros((0, 3)))
+
+    def to_c(self) -> DegeneracySetC:
+        r = np.asarray(self.rot, np.float64).reshape(-1, 3)
+        t = np.asarray(self.trans, np.float64).reshape(-1, 3)
+        c = DegeneracySetC()
+        c.n_rot, c.n_trans = r.shape[0], t.shape[0]   # (the library refuses a count outside 0..3)
+        for j in range(min(r.shape[0], 3)):
+            for k in range(3):
+                c.rot[j][k] = float(r[j, k])
+        for j in range(min(t.shape[0], 3)):
+            for k in range(3):
+                c.trans[j][k] = float(t[j, k])
+        return c
+
+    @classmethod
+    def from_c(cls, c: DegeneracySetC) -> "DegeneracySet":
+        return cls(np.array([list(c.rot[j]) for j in range(c.n_rot)], np.float64).reshape(-1, 3),
+                   np.array([list(c.trans[j]) for j in range(c.n_trans)], np.float64).reshape(-1, 3))
 
 
 @dataclass
@@ -84,7 +121,7 @@ class Localizability:
 
 
 def _bind(L):
-    """Declares the argtypes of the four calls on library `L`, once."""
+    """Declares the argtypes of the localizability and degeneracy calls on library `L`, once."""
     if _lib.needs_binding(L, __name__):
         pp, op, dp = C.POINTER(LocalizabilityParamsC), C.POINTER(LocalizabilityC), C.POINTER(C.c_double)
         fp = C.POINTER(C.c_float)
@@ -93,6 +130,14 @@ def _bind(L):
         L.o3s_icp_localizability.argtypes = [C.c_void_p, pp, op]
         L.o3s_localizability_estimate.argtypes = [C.c_void_p, fp, fp, C.c_int64, pp, op]
         L.o3s_localizability_remap.argtypes = [op, C.c_int32, dp, dp, dp, C.POINTER(C.c_int32)]
+        sp, cp, ip = C.POINTER(DegeneracySetC), C.POINTER(DegeneracyConfigC), C.POINTER(C.c_int32)
+        L.o3s_degeneracy_default_config.argtypes = [cp]
+        L.o3s_degeneracy_default_config.restype = None
+        L.o3s_icp_set_degeneracy.argtypes = [C.c_void_p, C.c_int32, sp, pp, C.c_int32]
+        L.o3s_icp_get_degeneracy.argtypes = [C.c_void_p, cp, sp]
+        L.o3s_icp_degeneracy_trace.argtypes = [C.c_void_p, ip, C.c_int32]
+        L.o3s_icp_degeneracy_trace.restype = C.c_int32
+        L.o3s_icp_minimize_degeneracy.argtypes = [C.c_void_p, fp, ip, fp, fp, C.c_int64, sp, fp, fp, fp, fp]
     return L
 
 
@@ -121,3 +166,9 @@ def remap_pose(loc: Localizability, T_prior, T_icp, min_category: int = PARTIALL
     if rc != _lib.OK:
         raise ValueError(f"[{rc}] o3s_localizability_remap refused its arguments")
     return out.reshape(4, 4).T.copy(), int(n.value)
+
+
+def minimize_degeneracy(icp, reading_xyz, ids, dists2, weights, dset: DegeneracySet):
+    """o3s_icp_minimize_degeneracy: ICP.minimize with the step constrained to have no component along the directions of `dset`
+    -> (T 4x4, A' 6x6, b', x): the constrained system as the solver took it."""
+    return icp.minimize_degeneracy(reading_xyz, ids, dists2, weights, dset)

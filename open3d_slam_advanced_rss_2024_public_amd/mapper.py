@@ -83,6 +83,8 @@ class Mapper:
         # MapperParams::degeneracyPolicy (localizability.OFF / REPORT / REMAP): what to do about a registration whose scan left
         # directions of the pose unconstrained.  Off: no call at all.  Report: ICP.localizability behind the compute, kept in
         # last_localizability.  Remap: also the prior instead of the ICP's correction in the directions below remap_min_category.
+        # Constrain: every ICP iteration solves its step with no component along the directions below remap_min_category
+        # (ICP.set_degeneracy, mode ANALYSE, with localizability_params); the Report-style analysis still fills last_localizability.
         # localizability_params: localizability.LocalizabilityParams — its three sums have no default
         self.degeneracy_policy = "Off"
         self.localizability_params = None
@@ -90,6 +92,7 @@ class Mapper:
         self.last_localizability = None       # None: the policy is Off, that registration failed, or before the first one
         self.last_remap_replaced = 0
         self.last_registration_pose = np.eye(4)
+        self._degeneracy_armed = None         # what the ICP handle was last told (Constrain): (params, min_category)
 
     def set_calibration(self, C_):
         self.calibration = np.array(C_, np.float64).reshape(4, 4)
@@ -173,14 +176,32 @@ class Mapper:
             sp = undistort_cloud(sp, self.last_motion, getattr(self.icp, "device", 0))
         self.ps.preprocess(self.wide, self.scan_voxel, self.narrow, sp, sn)
 
+    def _arm_degeneracy(self):
+        """Constrain: the handle's degeneracy mode follows the policy (set again only when the policy or its parameters change)."""
+        from . import localizability as loc
+
+        want = None
+        if self.degeneracy_policy == "Constrain":
+            p = self.localizability_params
+            want = (None if p is None else (p.filter_min, p.strong_min, p.sum_all_min, p.sum_strong_min, p.sum_partial_min), self.remap_min_category)
+        if want == self._degeneracy_armed:
+            return
+        if want is None:
+            self.icp.set_degeneracy(loc.DEGENERACY_OFF)
+        else:
+            self.icp.set_degeneracy(loc.DEGENERACY_ANALYSE, params=self.localizability_params or loc.LocalizabilityParams(),
+                                    min_category=self.remap_min_category)
+        self._degeneracy_armed = want
+
     def add(self, sp, sn, stamp, point_times=None):
         """point_times: the driver's per-point time offsets (seconds after `stamp`), read by the trajectory motion compensation."""
         inserted = refreset = threw = 0
         self.flags = (0, 0, 0)
         self.last_fitness, self.last_fitness_rejected = None, False
         self.last_localizability, self.last_remap_replaced = None, 0
-        if self.degeneracy_policy not in ("Off", "Report", "Remap"):
-            raise ValueError("degeneracy_policy must be 'Off', 'Report' or 'Remap'")
+        if self.degeneracy_policy not in ("Off", "Report", "Remap", "Constrain"):
+            raise ValueError("degeneracy_policy must be 'Off', 'Report', 'Remap' or 'Constrain'")
+        self._arm_degeneracy()
         if not self.use_initial_map and not self.is_calibration_set:
             return False
         self.ps = self.col.scan_for_next()

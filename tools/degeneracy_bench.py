@@ -1,0 +1,157 @@
+"""GPU-box helper: what the degeneracy-aware step (o3s_icp_set_degeneracy, include/degeneracy/o3s_degeneracy.h) costs.
+
+The icp.yaml chain (it stops by itself) per registration on the resident reading (o3s_icp_compute_resident), on the C2 pair — a
+100 000-point reading against a 2 M-point voxel map —, median of CALLS (default 11) calls after WARM (3):
+
+  off       the product library, the mode never set: what the chain launches is what the parent launches
+  fixed     mode FIXED with the empty set: k_constrain runs in every iteration and writes nothing, so the iterations and the pose
+            are those of `off` and the difference is the cost of the one launch more per iteration
+  analyse   mode ANALYSE with thresholds of 0 (every direction localizable): k_loc_hessian, k_loc_eig, k_loc_contrib and
+            k_constrain run in every iteration on that iteration's kept pairs and constrain nothing: again the iterations and the
+            pose of `off`, and the difference is the cost of the four launches more per iteration
+  parent    the same chain on the library of the parent commit, TWICE, when PARENT=<path to its libo3dslam_icp_hip.so> is given
+            (default: libo3dslam_icp_hip_parent.so beside the product library, if it is there).  The difference of its two runs is
+            the spread a difference between `off` and `parent` has to be read against.
+
+Every library is driven through the same few C ABI calls from here (ctypes), so the parent needs none of the newer symbols.  The
+runs alternate (parent, off, parent, off, fixed, analyse); a run is a fresh handle.  wall = host time around the call; gpu =
+o3s_icp_stats::gpu_ms (the chain's own stamps: first matcher launch -> the k_solve that posts the final state, so the added
+launches are inside it).  CONFIGS=C2 (or C4, or C2,C4) picks the pairs; OUT=<path> also writes the JSON there
+(profiles/degeneracy/).  TRACE=1: no parent, five `analyse` calls and five `fixed` calls — the run to put under
+`rocprofv3 --kernel-trace --stats` for the kernels' own times."""
+import ctypes as C
+import gc
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+
+from open3d_slam_advanced_rss_2024_public_amd import _lib, localizability as loc, synthetic as syn  # noqa: E402
+from open3d_slam_advanced_rss_2024_public_amd.icp import IcpConfig, as_xyzw  # noqa: E402
+
+TRACE = os.environ.get("TRACE") == "1"
+CALLS = int(os.environ.get("CALLS", "5" if TRACE else "11"))
+WARM = int(os.environ.get("WARM", "3"))
+CONFIGS = {"C2": (100_000, 2_000_000, 0.1), "C4": (500_000, 20_000_000, 0.02)}
+WHICH = [c for c in os.environ.get("CONFIGS", "C2").split(",") if c]
+PARENT = os.environ.get("PARENT") or _lib.variant_path("parent")
+
+
+def fp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def open_library(path):
+    _lib._preload_torch_runtime(["libamdhip64.so"])
+    L = C.CDLL(path)
+    vp, f = C.c_void_p, C.POINTER(C.c_float)
+    L.o3s_icp_create.argtypes = [C.POINTER(_lib.IcpConfigC), C.c_int, C.POINTER(vp)]
+    L.o3s_icp_destroy.argtypes = [vp]
+    L.o3s_icp_destroy.restype = None
+    L.o3s_icp_init_reference.argtypes = [vp, f, f, C.c_int64]
+    L.o3s_icp_set_reading.argtypes = [vp, f, f, C.c_int64]
+    L.o3s_icp_compute_resident.argtypes = [vp, f, f, C.POINTER(_lib.IcpStatsC)]
+    if hasattr(L, "o3s_icp_set_degeneracy"):
+        L.o3s_icp_set_degeneracy.argtypes = [vp, C.c_int32, C.POINTER(loc.DegeneracySetC), C.POINTER(loc.LocalizabilityParamsC), C.c_int32]
+        L.o3s_icp_degeneracy_trace.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32]
+    return L
+
+
+def median(v):
+    return float(np.median(np.asarray(v, np.float64)))
+
+
+def run(L, sp, mode):
+    cfg = IcpConfig().to_c()
+    h = C.c_void_p()
+    assert L.o3s_icp_create(C.byref(cfg), 0, C.byref(h)) == 0
+    ref, refn = as_xyzw(sp.map_xyz), np.ascontiguousarray(sp.map_normals, np.float32)
+    scan, scann = as_xyzw(sp.scan_xyz), np.ascontiguousarray(sp.scan_normals, np.float32)
+    assert L.o3s_icp_init_reference(h, fp(ref), fp(refn), len(ref)) == 0
+    assert L.o3s_icp_set_reading(h, fp(scan), fp(scann), len(scan)) == 0
+    if mode == "fixed":
+        empty = loc.DegeneracySet().to_c()
+        assert L.o3s_icp_set_degeneracy(h, loc.DEGENERACY_FIXED, C.byref(empty), None, 2) == 0
+    elif mode == "analyse":
+        params = loc.LocalizabilityParams(sum_all_min=0.0, sum_strong_min=0.0, sum_partial_min=0.0).to_c()
+        assert L.o3s_icp_set_degeneracy(h, loc.DEGENERACY_ANALYSE, None, C.byref(params), 2) == 0
+    Tin = np.ascontiguousarray(sp.T_init.astype(np.float32).T).reshape(16)
+    Tout = np.zeros(16, np.float32)
+    st = _lib.IcpStatsC()
+    wall, gpu = [], []
+    gc.disable()
+    for k in range(WARM + CALLS):
+        t0 = time.perf_counter()
+        rc = L.o3s_icp_compute_resident(h, fp(Tin), fp(Tout), C.byref(st))
+        dt = (time.perf_counter() - t0) * 1e6
+        assert rc == 0
+        if k < WARM:
+            continue
+        wall.append(dt)
+        gpu.append(st.gpu_ms * 1e3)
+    gc.enable()
+    r = {"wall_us_median": median(wall), "wall_us_min": float(min(wall)), "chain_gpu_us_median": median(gpu), "chain_gpu_us_min": float(min(gpu)),
+         "iterations": int(st.iterations), "kept_pairs": int(st.kept_pairs), "pose": [float(x) for x in Tout]}
+    if mode in ("fixed", "analyse"):
+        masks = np.full(64, -1, np.int32)
+        n = L.o3s_icp_degeneracy_trace(h, masks.ctypes.data_as(C.POINTER(C.c_int32)), 64)
+        r["masks"] = masks[:n].tolist()
+    L.o3s_icp_destroy(h)
+    return r
+
+
+def one_config(name, product, parent):
+    N, M, voxel = CONFIGS[name]
+    sp = syn.make_scan_pair(N, M, voxel)
+    res = {"workload": f"{name}: icp.yaml chain, {N}-point reading vs {M}-point map, resident reading, median of {CALLS} calls after {WARM}"}
+    if TRACE:
+        for mode in ("analyse", "fixed"):
+            res[mode] = run(product, sp, mode)
+            res[mode].pop("pose")
+        return res
+    if parent:
+        res["parent_a"] = run(parent, sp, "off")
+    res["off_a"] = run(product, sp, "off")
+    if parent:
+        res["parent_b"] = run(parent, sp, "off")
+    res["off_b"] = run(product, sp, "off")
+    res["fixed"] = run(product, sp, "fixed")
+    res["analyse"] = run(product, sp, "analyse")
+    off_wall = min(res["off_a"]["wall_us_median"], res["off_b"]["wall_us_median"])
+    off_gpu = min(res["off_a"]["chain_gpu_us_median"], res["off_b"]["chain_gpu_us_median"])
+    for mode in ("fixed", "analyse"):
+        it = res[mode]["iterations"]
+        res[f"same_pose_{mode}_and_off"] = res[mode]["pose"] == res["off_a"]["pose"] and it == res["off_a"]["iterations"]
+        res[f"{mode}_minus_off_per_registration_us"] = {"wall": res[mode]["wall_us_median"] - off_wall, "gpu": res[mode]["chain_gpu_us_median"] - off_gpu}
+        res[f"{mode}_minus_off_per_iteration_us"] = {"wall": (res[mode]["wall_us_median"] - off_wall) / it, "gpu": (res[mode]["chain_gpu_us_median"] - off_gpu) / it}
+    if parent:
+        res["same_pose_as_parent"] = res["parent_a"]["pose"] == res["off_a"]["pose"]
+        for key in ("wall_us_median", "chain_gpu_us_median"):
+            pa, pb = res["parent_a"][key], res["parent_b"][key]
+            res[f"{key}_parent_spread"] = abs(pa - pb)
+            res[f"{key}_off_minus_parent"] = min(res["off_a"][key], res["off_b"][key]) - min(pa, pb)
+    for k in ("parent_a", "parent_b", "off_a", "off_b", "fixed", "analyse"):
+        if k in res:
+            res[k].pop("pose")
+    return res
+
+
+def main():
+    product = open_library(_lib.variant_path(None))
+    parent = open_library(PARENT) if (os.path.exists(PARENT) and not TRACE) else None
+    res = {name: one_config(name, product, parent) for name in WHICH}
+    line = json.dumps(res)
+    print(line)
+    out = os.environ.get("OUT")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
