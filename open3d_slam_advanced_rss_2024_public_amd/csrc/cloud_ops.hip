@@ -377,6 +377,33 @@ extern "C" int o3s_test_sort_pairs(int device, const uint64_t* keys, const uint3
   CK(hipMemcpy(vals_out, v2.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   return O3S_OK;
 }
+// hooks build only (tests/test_gpu_cloud_edges.py): the run heads of `n` sorted keys and their exclusive scan, as the voxelisers chain them —
+// k_heads, then scan_flags.  with_blk: k_heads leaves its per-block counts in the scan's temp (put_block_count), as the hinted
+// pipelines do, and the scan is k_scan_flags_blk; otherwise rocPRIM's scan.  head_out: n words, off_out: n + 1, *count: the total
+// as the host receives it (posted, or copied under O3S_NO_MAILBOX)
+extern "C" int o3s_test_scan_flags(int device, const uint64_t* keys, int64_t n, uint64_t pass_key, int key_shift, int with_blk, uint32_t* head_out,
+                                   uint32_t* off_out, int64_t* count) {
+  using namespace o3s_cloud;
+  if (n <= 0 || n > (int64_t)0x7fffffff || !keys || !head_out || !off_out || !count || key_shift < 0 || key_shift > 63) return O3S_ERR_BAD_ARGUMENT;
+  const int rc = pick_device(device);
+  if (rc != O3S_OK) return rc;
+  DevMem d_keys, d_head, d_off, d_tmp;
+  const size_t tb = scan_temp_bytes(n);
+  CK(d_keys.alloc((size_t)n * 8));
+  CK(d_head.alloc((size_t)n * 4));
+  CK(d_off.alloc((size_t)(n + 1) * 4));
+  CK(d_tmp.alloc(tb));
+  CK(hipMemcpy(d_keys.p, keys, (size_t)n * 8, hipMemcpyHostToDevice));
+  CK(hipMemset(d_off.p, 0xff, (size_t)(n + 1) * 4));
+  uint32_t* blk = with_blk ? reinterpret_cast<uint32_t*>(d_tmp.p) : nullptr;
+  hipLaunchKernelGGL(k_heads, dim3(nblk(n)), dim3(kB), 0, nullptr, d_keys.as<uint64_t>(), n, pass_key, d_head.as<uint32_t>(), key_shift, blk);
+  CK(hipGetLastError());
+  const int rs = scan_flags(d_head.as<uint32_t>(), d_off.as<uint32_t>(), n, d_tmp.p, tb, count, nullptr, blk);
+  if (rs != O3S_OK) return rs;
+  CK(hipMemcpy(head_out, d_head.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  CK(hipMemcpy(off_out, d_off.p, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost));
+  return O3S_OK;
+}
 // hooks build only (tests/test_gpu_cloud_ops.py): the bounds of a host cloud through the shared reduction (cloud_bounds.h) — fill,
 // k_bounds over the flat source on the production grid, fold and fetch; out6 = min x, y, z, max x, y, z
 extern "C" int o3s_test_cloud_bounds(int device, const double* pts, int64_t n, double* out6) {

@@ -171,20 +171,42 @@ def test_transform_with_covariances_and_identity_doubling():
 
 @pytest.mark.parametrize("n", [1, 7, 2047, 2048, 2049, 5000, 13337, 16384, 16385, 20481, 40000, 53211, 65536, 131071, 131072, 131073, 200000, 262143, 262144, 300000])
 def test_pair_sort_of_the_work_areas_is_a_stable_sort(hooks_lib, n):
-    """csrc/cloud_dev.h sort_pairs (rocPRIM's merge path below 262 144 pairs, Onesweep above; the library's own small sort was measured
-    slower in round 5 and removed): the stable order of the keys, with many ties and a key of all ones among them."""
-    import ctypes as C
+    """csrc/cloud_dev.h sort_pairs with end_bit = 64, which is rocPRIM's default configuration at EVERY size (its merge path below a
+    million pairs): the Onesweep configuration is taken only for n >= 262 144 AND end_bit <= 40 — the short-key test below.  (The library's
+    own small sort was measured slower in round 5 and removed.)  The stable order of the keys, with many ties and a key of all ones among them."""
     rng = np.random.default_rng(n)
     keys = rng.integers(0, max(2, n // 3), n).astype(np.uint64) << np.uint64(17)
     keys[rng.integers(0, n, max(1, n // 50))] = np.uint64(0xFFFFFFFFFFFFFFFF)
-    vals = rng.permutation(n).astype(np.uint32)
+    _check_pair_sort(hooks_lib, keys, rng.permutation(n).astype(np.uint32), 64)
+
+
+def _check_pair_sort(hooks_lib, keys, vals, end_bit):
+    import ctypes as C
+    n = len(keys)
     ko, vo = np.empty_like(keys), np.empty_like(vals)
     f = hooks_lib.o3s_test_sort_pairs
     f.restype = C.c_int
     f.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
-    assert f(0, keys.ctypes.data, vals.ctypes.data, n, 64, ko.ctypes.data, vo.ctypes.data) == 0
+    assert f(0, keys.ctypes.data, vals.ctypes.data, n, end_bit, ko.ctypes.data, vo.ctypes.data) == 0
     order = np.argsort(keys, kind="stable")
     assert np.array_equal(ko, keys[order]) and np.array_equal(vo, vals[order])
+
+
+@pytest.mark.parametrize("end_bit", [1, 8, 9, 20, 32, 33, 40, 41])
+@pytest.mark.parametrize("n", [262143, 262144, 262145, 300000, 1048577])
+def test_pair_sort_with_short_keys_is_a_stable_sort(hooks_lib, n, end_bit):
+    """sort_pairs around its switch to the Onesweep configuration (n >= 262 144 and end_bit <= 40; 262 143 pairs or 41 bits stay on
+    rocPRIM's default): keys below 2^end_bit with many ties, 0 and 2^end_bit - 1 among them — whole and partial radix passes (8 bits
+    each), one bit, and both sides of the 40-bit limit."""
+    rng = np.random.default_rng(1000 * end_bit + n % 1000)
+    top = (1 << end_bit) - 1
+    distinct = rng.integers(0, top + 1, max(2, n // 3), dtype=np.uint64)      # about three pairs per key where the range allows
+    keys = distinct[rng.integers(0, len(distinct), n)]
+    where = rng.choice(n, 40, replace=False)
+    keys[where[:20]] = 0
+    keys[where[20:]] = top
+    assert int(keys.max()) == top and int(keys.min()) == 0
+    _check_pair_sort(hooks_lib, keys, rng.permutation(n).astype(np.uint32), end_bit)
 
 
 def _bounds_cloud(n):
