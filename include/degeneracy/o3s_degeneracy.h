@@ -35,7 +35,7 @@
  *                          contract of o3s_localizability.h, on the kept pairs of THAT iteration under the pose they were formed at) in
  *                          front of k_constrain, which folds pass 2 as k_loc_post does, applies the categories and constrains every
  *                          direction whose category < min_category.  Four launches more per iteration.  Partially localizable
- *                          directions get no treatment of their own.
+ *                          directions get no treatment of their own unless o3s_degeneracy_partial.h's flag is set.
  *  Mask of an iteration (o3s_icp_degeneracy_trace): bit j < 3 translation direction j, bit 3 + j rotation direction j; in ANALYSE
  *  mode j is the analysis' index (eval ascending), in FIXED mode the index in the caller's set.
  *  After a constrained compute in ANALYSE mode, o3s_icp_localizability with the same parameters reports for the last iteration the

@@ -105,6 +105,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "pose_graph", "o3s_pose_graph.h"))
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "localizability", "o3s_localizability.h"))
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "degeneracy", "o3s_degeneracy.h"))
+    srcs.append(os.path.join(os.path.dirname(_HERE), "include", "degeneracy", "o3s_degeneracy_partial.h"))
     stale = (not os.path.exists(LIB_PATH)) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s"] + (["-B"] if force else []))

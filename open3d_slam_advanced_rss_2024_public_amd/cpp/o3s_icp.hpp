@@ -22,6 +22,7 @@
 #include "dense_map/o3s_dense_map_color.h"
 #include "o3s_submap.h"
 #include "degeneracy/o3s_degeneracy.h"
+#include "degeneracy/o3s_degeneracy_partial.h"
 #include "localizability/o3s_localizability.h"
 
 namespace o3s {
@@ -101,6 +102,24 @@ class IcpHip {
     std::vector<std::int32_t> masks(4096);
     masks.resize((size_t)o3s_icp_degeneracy_trace(h_, masks.data(), (std::int32_t)masks.size()));
     return masks;
+  }
+  // With the flag set, the ANALYSE chain constrains a partially localizable direction (category 1) to the step its strong pairs
+  // alone ask for, instead of to zero or not at all (o3s_icp_set_degeneracy_partial).  No launch more; FIXED and OFF ignore it.
+  void setDegeneracyPartial(bool enable) { raise(o3s_icp_set_degeneracy_partial(h_, enable ? 1 : 0)); }
+  // One record per iteration of the last successful compute: the directions of category 1 and the six values the rows carried
+  // (o3s_icp_degeneracy_partial_trace); empty when the flag is off
+  struct DegeneracyPartialTrace {
+    std::vector<std::int32_t> partialMasks;
+    std::vector<double> values;  // [n][6]
+  };
+  DegeneracyPartialTrace degeneracyPartialTrace() {
+    DegeneracyPartialTrace t;
+    t.partialMasks.resize(4096);
+    t.values.resize(4096 * 6);
+    const size_t n = (size_t)o3s_icp_degeneracy_partial_trace(h_, t.partialMasks.data(), t.values.data(), (std::int32_t)t.partialMasks.size());
+    t.partialMasks.resize(n);
+    t.values.resize(n * 6);
+    return t;
   }
   o3s_icp* handle() { return h_; }
 

@@ -109,6 +109,10 @@ struct MapperParams {
   DegeneracyPolicy degeneracyPolicy = DegeneracyPolicy::Off;
   o3s_localizability_params localizability = defaultLocalizability();
   std::int32_t remapMinCategory = 1;
+  // Constrain only: a partially localizable direction (category 1) is constrained to the step its strong pairs alone ask for
+  // (IcpHip::setDegeneracyPartial, include/degeneracy/o3s_degeneracy_partial.h) instead of to zero (remapMinCategory 2) or not
+  // at all (remapMinCategory 1)
+  bool degeneracyPartial = false;
   static o3s_localizability_params defaultLocalizability() {
     o3s_localizability_params p;
     o3s_localizability_default_params(&p);
@@ -125,8 +129,10 @@ class MapperHip {
       if (o3s_icp_localizability(nullptr, &p.localizability, &unused) == O3S_ERR_BAD_CONFIG)
         throw std::runtime_error("MapperParams::localizability: the thresholds are unset or out of order");
       if (p.remapMinCategory != 1 && p.remapMinCategory != 2) throw std::runtime_error("MapperParams::remapMinCategory must be 1 or 2");
-      if (p.degeneracyPolicy == MapperParams::DegeneracyPolicy::Constrain)
+      if (p.degeneracyPolicy == MapperParams::DegeneracyPolicy::Constrain) {
         icp_.setDegeneracy(O3S_DEGENERACY_ANALYSE, nullptr, &p.localizability, p.remapMinCategory);
+        if (p.degeneracyPartial) icp_.setDegeneracyPartial(true);
+      }
     }
     lastLocalizability_.kept = -1;
   }

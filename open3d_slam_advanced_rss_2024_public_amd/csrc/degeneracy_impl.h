@@ -69,7 +69,7 @@ int o3s_icp_set_degeneracy(o3s_icp* h, int32_t mode, const o3s_degeneracy_set* f
   if (std::memcmp(&next, &h->deg, sizeof(next)) != 0) ++h->deg_gen;  // another chain: its graph is another graph
   h->deg = next;
   h->deg_fixed = fixed;
-  h->deg_trace_valid = false;
+  h->deg_trace_valid = h->deg_partial_valid = false;
   return O3S_OK;
 }
 
@@ -113,7 +113,7 @@ int o3s_icp_minimize_degeneracy(o3s_icp* h, const float* reading_xyzw, const int
   HIP_TRY(h, hipSetDevice(h->device));
   HIP_TRY(h, h->d_deg.ensure(kDegBufBytes));
   h->deg_trace_valid = false;  // k_constrain leaves this call's set where a compute leaves its last one
-  return minimize_impl(h, reading_xyzw, ids, dists2, weights, N, &fixed, T_out, A_out, b_out, x_out);
+  return minimize_impl(h, reading_xyzw, ids, dists2, weights, N, &fixed, nullptr, T_out, A_out, b_out, x_out);
 }
 
 }  // extern "C"

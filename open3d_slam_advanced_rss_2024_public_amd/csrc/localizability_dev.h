@@ -6,7 +6,8 @@
 //   k_loc_hessian   12 fp64 partial sums per block: the upper triangles of A_t = sum n n^T and A_r = sum c c^T
 //   k_loc_eig       one block: folds them, two lanes (one per 3 x 3 block, in two waves) run the Jacobis and leave the six directions in
 //                   device memory
-//   k_loc_contrib   the second pass: 12 fp64 sums and 7 counts per block (six n_strong, the pairs taken)
+//   k_loc_contrib   the second pass: 12 fp64 sums and 7 counts per block (six n_strong, the pairs taken); k_loc_contrib_partial is
+//                   the same body with the strong-pair sums of include/degeneracy/o3s_degeneracy_partial.h beside them
 //   k_loc_post      one block: folds them, applies the categories, stamps the clock and posts (host_post.h)
 // Nothing per pair is stored: pass 2 forms the centred pair again exactly as pass 1 did.
 #pragma once
@@ -229,12 +230,24 @@ __global__ void __launch_bounds__(kBlock) k_loc_eig(const double* __restrict__ p
   if (threadIdx.x == 64) loc_eig3(s_sum + kLocTri, dirs + 3, dirs + 6 + 9);
 }
 
-__global__ void __launch_bounds__(kBlock) k_loc_contrib(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz, int N,
-                                                        const float4* __restrict__ mn, const int32_t* __restrict__ pos, const float* __restrict__ d2,
-                                                        float max_out_r2, const IcpState* __restrict__ st, const float* __restrict__ ext_p,
-                                                        const float* __restrict__ ext_n, const double* __restrict__ dirs, double filter_min,
-                                                        double strong_min, double* __restrict__ part /*[12][grid]*/,
-                                                        unsigned long long* __restrict__ part_cnt /*[7][grid]*/, int live) {
+// What the flagged instantiation of pass 2 reads and writes on top (include/degeneracy/o3s_degeneracy_partial.h): the matched points
+// (chain: the matcher's stream and the centroid mq of the header; module: a third 3 x K array) and a partial region of its own.
+struct LocNoPartialIo {};  // the unflagged instantiation carries nothing
+struct LocPartialIo {
+  const float4* mq;      // chain
+  const float* ext_q;    // module
+  double* part;          // [12][grid]: num[6] then den[6]
+};
+// kPartial: the strong-pair sums num_j, den_j of the partially localizable directions, twelve accumulators beside pass 2's own
+// (which keep their accumulators, their order and their partial region: the unflagged instantiation is the source it was and gives
+// the bits it gave).  Chain sources are live only: the centroid mq is read where k_normal_eq reads it.
+template <bool kPartial, class Pio>
+__device__ __forceinline__ void loc_contrib_body(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz, int N,
+                                                 const float4* __restrict__ mn, const int32_t* __restrict__ pos, const float* __restrict__ d2,
+                                                 float max_out_r2, const IcpState* __restrict__ st, const float* __restrict__ ext_p,
+                                                 const float* __restrict__ ext_n, const double* __restrict__ dirs, double filter_min,
+                                                 double strong_min, double* __restrict__ part /*[12][grid]*/,
+                                                 unsigned long long* __restrict__ part_cnt /*[7][grid]*/, int live, const Pio pio) {
   using Sum = BlockSum<kLocTri, kBlock>;
   __shared__ double s_a[Sum::kWordsA];
   __shared__ double s_b[Sum::kWordsB];
@@ -251,6 +264,16 @@ __global__ void __launch_bounds__(kBlock) k_loc_contrib(const float* __restrict_
   uint32_t cnt[kLocCounts];
 #pragma unroll
   for (int j = 0; j < 6; ++j) accA[j] = accS[j] = 0.0;
+  double accN[kPartial ? 6 : 1], accD[kPartial ? 6 : 1];
+  float mqx = 0.f, mqy = 0.f, mqz = 0.f;
+  if constexpr (kPartial) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) accN[j] = accD[j] = 0.0;
+    if (chain) {  // uniform
+      const float hv = hdr_load(st);
+      mqx = hdr_f(hv, H_MQ), mqy = hdr_f(hv, H_MQ + 1), mqz = hdr_f(hv, H_MQ + 2);
+    }
+  }
 #pragma unroll
   for (int j = 0; j < kLocCounts; ++j) cnt[j] = 0u;
   for (int base = blockIdx.x * (kBlock * kNePPT) + threadIdx.x; base < N; base += gridDim.x * (kBlock * kNePPT)) {
@@ -266,6 +289,21 @@ __global__ void __launch_bounds__(kBlock) k_loc_contrib(const float* __restrict_
 #pragma unroll
       for (int k = 0; k < 3; ++k) tau[k] = r > 0.f ? c[k] / r : 0.f;
       cnt[6] += 1u;
+      float h = 0.f;  // kPartial: the pair's residual as k_normal_eq forms it
+      if constexpr (kPartial) {
+        float q[3];
+        if (chain) {
+          const float4 qq = pio.mq[i];
+          q[0] = qq.x - mqx, q[1] = qq.y - mqy, q[2] = qq.z - mqz;
+        } else {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) q[k] = pio.ext_q[3 * (size_t)i + k];
+        }
+        const float ex = p[0] - q[0], ey = p[1] - q[1], ez = p[2] - q[2];
+        h = h + ex * n[0];
+        h = h + ey * n[1];
+        h = h + ez * n[2];
+      }
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
         const float* g = j < 3 ? n : tau;
@@ -274,6 +312,14 @@ __global__ void __launch_bounds__(kBlock) k_loc_contrib(const float* __restrict_
         if (a >= strong_min) {
           accS[j] += a;
           cnt[j] += 1u;
+        }
+        if constexpr (kPartial) {
+          const float* gr = j < 3 ? n : c;  // the minimiser's own row: the rotation part unnormalised
+          const double s = ((double)gr[0] * dir[j][0] + (double)gr[1] * dir[j][1]) + (double)gr[2] * dir[j][2];
+          if (a >= strong_min) {
+            accN[j] += s * (double)h;
+            accD[j] += s * s;
+          }
         }
       }
     }
@@ -293,6 +339,30 @@ __global__ void __launch_bounds__(kBlock) k_loc_contrib(const float* __restrict_
   }
   Sum::run(accS, s_a, s_b);
   if (threadIdx.x < 6) part[(6 + threadIdx.x) * gridDim.x + blockIdx.x] = Sum::total(s_b, threadIdx.x);
+  if constexpr (kPartial) {
+    Sum::run(accN, s_a, s_b);  // (its first barrier stands between the totals above and the new segment sums)
+    if (threadIdx.x < 6) pio.part[threadIdx.x * gridDim.x + blockIdx.x] = Sum::total(s_b, threadIdx.x);
+    Sum::run(accD, s_a, s_b);
+    if (threadIdx.x < 6) pio.part[(6 + threadIdx.x) * gridDim.x + blockIdx.x] = Sum::total(s_b, threadIdx.x);
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_loc_contrib(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz, int N,
+                                                        const float4* __restrict__ mn, const int32_t* __restrict__ pos, const float* __restrict__ d2,
+                                                        float max_out_r2, const IcpState* __restrict__ st, const float* __restrict__ ext_p,
+                                                        const float* __restrict__ ext_n, const double* __restrict__ dirs, double filter_min,
+                                                        double strong_min, double* __restrict__ part /*[12][grid]*/,
+                                                        unsigned long long* __restrict__ part_cnt /*[7][grid]*/, int live) {
+  loc_contrib_body<false>(rx, ry, rz, N, mn, pos, d2, max_out_r2, st, ext_p, ext_n, dirs, filter_min, strong_min, part, part_cnt, live, LocNoPartialIo{});
+}
+__global__ void __launch_bounds__(kBlock) k_loc_contrib_partial(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz,
+                                                                int N, const float4* __restrict__ mn, const int32_t* __restrict__ pos,
+                                                                const float* __restrict__ d2, float max_out_r2, const IcpState* __restrict__ st,
+                                                                const float* __restrict__ ext_p, const float* __restrict__ ext_n,
+                                                                const double* __restrict__ dirs, double filter_min, double strong_min,
+                                                                double* __restrict__ part /*[12][grid]*/,
+                                                                unsigned long long* __restrict__ part_cnt /*[7][grid]*/, int live, LocPartialIo pio) {
+  loc_contrib_body<true>(rx, ry, rz, N, mn, pos, d2, max_out_r2, st, ext_p, ext_n, dirs, filter_min, strong_min, part, part_cnt, live, pio);
 }
 
 // One block: the 12 sums folded as in k_loc_eig, the 7 counts by waves 0..3 in turn (lane l adds blocks l, l + 64, ...: integers,

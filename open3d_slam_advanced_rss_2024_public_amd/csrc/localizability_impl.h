@@ -16,7 +16,7 @@ const char* loc_params_error(const o3s_localizability_params& p) {
 
 // the four launches on the handle's stream and the wait for k_loc_post's values.  ext_*: the module-level source (device, 3 x n AoS)
 int loc_run(o3s_icp* h, int n, const float* rx, const float* ry, const float* rz, float max_out_r2, const float* ext_p, const float* ext_n,
-            const o3s_localizability_params& p, o3s_localizability* out) {
+            const o3s_localizability_params& p, o3s_localizability* out, const float* ext_q = nullptr, kern::DegPartialLast* partial = nullptr) {
   const int nb = loc_blocks(n);
   HIP_TRY(h, h->d_loc.ensure(kLocBufBytes));
   double* base = h->d_loc.as<double>();
@@ -28,10 +28,24 @@ int loc_run(o3s_icp* h, int n, const float* rx, const float* ry, const float* rz
   hipLaunchKernelGGL(kern::k_loc_hessian, dim3(nb), dim3(kern::kBlock), 0, h->stream, rx, ry, rz, n, h->d_mn.as<float4>(), h->d_pos.as<int32_t>(),
                      h->d_d2.as<float>(), max_out_r2, h->d_state.as<IcpState>(), ext_p, ext_n, part1, t_start, 0);
   hipLaunchKernelGGL(kern::k_loc_eig, dim3(1), dim3(kern::kBlock), 0, h->stream, part1, nb, dirs, (const IcpState*)nullptr);
-  hipLaunchKernelGGL(kern::k_loc_contrib, dim3(nb), dim3(kern::kBlock), 0, h->stream, rx, ry, rz, n, h->d_mn.as<float4>(), h->d_pos.as<int32_t>(),
-                     h->d_d2.as<float>(), max_out_r2, h->d_state.as<IcpState>(), ext_p, ext_n, dirs, p.filter_min, p.strong_min, part2, cnt, 0);
+  if (partial) {  // the module-level source with its matched points (degeneracy_partial_impl.h): pass 2 flagged, the caller has sized d_degp
+    const kern::LocPartialIo pio{nullptr, ext_q, h->d_degp.as<double>()};
+    hipLaunchKernelGGL(kern::k_loc_contrib_partial, dim3(nb), dim3(kern::kBlock), 0, h->stream, rx, ry, rz, n, h->d_mn.as<float4>(),
+                       h->d_pos.as<int32_t>(), h->d_d2.as<float>(), max_out_r2, h->d_state.as<IcpState>(), ext_p, ext_n, dirs, p.filter_min,
+                       p.strong_min, part2, cnt, 0, pio);
+  } else {
+    hipLaunchKernelGGL(kern::k_loc_contrib, dim3(nb), dim3(kern::kBlock), 0, h->stream, rx, ry, rz, n, h->d_mn.as<float4>(), h->d_pos.as<int32_t>(),
+                       h->d_d2.as<float>(), max_out_r2, h->d_state.as<IcpState>(), ext_p, ext_n, dirs, p.filter_min, p.strong_min, part2, cnt, 0);
+  }
   const uint32_t seq = h->cov_mb.next();
   hipLaunchKernelGGL(kern::k_loc_post, dim3(1), dim3(kern::kBlock), 0, h->stream, part2, cnt, nb, dirs, th, st, t_start, vals, h->cov_mb.dev, seq);
+  if (partial) {
+    kern::DegPartialLast* rec = reinterpret_cast<kern::DegPartialLast*>(h->d_degp.as<char>() + kDegpOffLast);
+    hipLaunchKernelGGL(kern::k_deg_partial_post, dim3(1), dim3(kern::kBlock), 0, h->stream, h->d_degp.as<double>(), nb, vals, rec);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(partial, rec, sizeof(*partial), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+  }
   HIP_TRY(h, hipGetLastError());
   double v[kern::kLocPostVals];
   const int w = host_post::fetch_post(h->cov_mb, seq, h->stream, reinterpret_cast<uint32_t*>(v), 2 * kern::kLocPostVals, host_post::kPostVals, vals);

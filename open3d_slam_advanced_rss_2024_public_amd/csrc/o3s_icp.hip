@@ -150,6 +150,11 @@ struct o3s_icp {
   uint64_t deg_gen = 0;                 // moves with every change of mode, set or parameters: part of the graph key
   bool deg_trace_valid = false;         // the last successful compute ran with a mode other than OFF
   DevBuf d_deg{&alloc_gen};
+  // values for the partially localizable directions (degeneracy_partial_impl.h): the flag of the later computes; the device area
+  // (the strong-pair partials, the last record, one trace record per iteration) exists only once the flag has been set
+  bool deg_partial = false;
+  bool deg_partial_valid = false;       // the last successful compute ran in ANALYSE mode with the flag set
+  DevBuf d_degp{&alloc_gen};
   // registration fitness (o3s_icp_evaluate_resident): where the last successful compute left the reading.  pose_valid: that compute's
   // T_iter is in last_T_iter and nothing has replaced the reading or the reference since; r_is_call: d_r still holds the reading as
   // that compute prepared it (T0 . p in its processing order) — an evaluation at an explicit pose prepares it anew
@@ -742,11 +747,27 @@ inline bool sel_partial(const ChainArgs& a) {
 // behind the three analysis kernels on this iteration's kept pairs.  `set`: the module-level minimiser's own set (no trace)
 constexpr int kDegMaskCap = 4096;  // ensure_trace's bound
 constexpr size_t kDegBufBytes = sizeof(kern::DegLast) + (size_t)kDegMaskCap * 4;
-void launch_constrain(o3s_icp* h, const ChainArgs& a, int nb, hipStream_t s, const kern::DegFixed* set = nullptr) {
+// the area of the values (o3s_degeneracy_partial.h), in bytes: the strong-pair partials [12][blocks], the last record, the trace
+// (one partial mask and six values per iteration)
+constexpr size_t kDegpOffLast = (size_t)kMaxPartialBlocks * kern::kLocSums * sizeof(double);
+constexpr size_t kDegpOffMasks = kDegpOffLast + sizeof(kern::DegPartialLast);
+constexpr size_t kDegpOffValues = kDegpOffMasks + (size_t)kDegMaskCap * 4;
+constexpr size_t kDegpBufBytes = kDegpOffValues + (size_t)kDegMaskCap * 6 * sizeof(double);
+static_assert(kDegpOffLast % 8 == 0 && kDegpOffValues % 8 == 0, "doubles on 8-byte boundaries");
+inline bool deg_partial_live(const o3s_icp* h) { return h->deg_partial && h->deg.mode == O3S_DEGENERACY_ANALYSE; }
+// `vals`: the module-level minimiser's values for the rows of `set`, in the mask's order (k_constrain_values)
+void launch_constrain(o3s_icp* h, const ChainArgs& a, int nb, hipStream_t s, const kern::DegFixed* set = nullptr, const double* vals = nullptr) {
   IcpState* st = h->d_state.as<IcpState>();
   kern::DegLast* last = h->d_deg.as<kern::DegLast>();
   uint32_t* masks = set ? nullptr : reinterpret_cast<uint32_t*>(h->d_deg.as<char>() + sizeof(kern::DegLast));
   kern::LocThresholds th{};
+  if (set && vals) {
+    kern::DegValuesIo io{};
+    for (int j = 0; j < 6; ++j) io.fixed_vals[j] = vals[j];
+    hipLaunchKernelGGL(kern::k_constrain_values, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), nb, st, *set, (const double*)nullptr, 0,
+                       (const double*)nullptr, th, 0, last, masks, kDegMaskCap, io);
+    return;
+  }
   if (set || h->deg.mode == O3S_DEGENERACY_FIXED) {
     hipLaunchKernelGGL(kern::k_constrain, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), nb, st, set ? *set : h->deg_fixed,
                        (const double*)nullptr, 0, (const double*)nullptr, th, 0, last, masks, kDegMaskCap);
@@ -762,6 +783,22 @@ void launch_constrain(o3s_icp* h, const ChainArgs& a, int nb, hipStream_t s, con
   hipLaunchKernelGGL(kern::k_loc_hessian, dim3(nbl), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, h->d_mn.as<float4>(), h->d_pos.as<int32_t>(),
                      h->d_d2.as<float>(), a.cp.max_out_r2, st, (const float*)nullptr, (const float*)nullptr, part1, t_start, 1);
   hipLaunchKernelGGL(kern::k_loc_eig, dim3(1), dim3(kern::kBlock), 0, s, part1, nbl, dirs, (const IcpState*)st);
+  if (h->deg_partial) {  // the same launches, the flagged instantiations: the strong-pair sums ride on pass 2, k_constrain_values applies them
+    char* pb = h->d_degp.as<char>();
+    double* pp = reinterpret_cast<double*>(pb);
+    const kern::LocPartialIo pio{h->d_mq.as<float4>(), nullptr, pp};
+    hipLaunchKernelGGL(kern::k_loc_contrib_partial, dim3(nbl), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, h->d_mn.as<float4>(),
+                       h->d_pos.as<int32_t>(), h->d_d2.as<float>(), a.cp.max_out_r2, st, (const float*)nullptr, (const float*)nullptr, dirs, p.filter_min,
+                       p.strong_min, part2, cnt, 1, pio);
+    kern::DegValuesIo io{};
+    io.pp_part = pp;
+    io.last = reinterpret_cast<kern::DegPartialLast*>(pb + kDegpOffLast);
+    io.pmasks = reinterpret_cast<uint32_t*>(pb + kDegpOffMasks);
+    io.values = reinterpret_cast<double*>(pb + kDegpOffValues);
+    hipLaunchKernelGGL(kern::k_constrain_values, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), nb, st, kern::DegFixed{}, part2, nbl, dirs, th,
+                       (int)h->deg.min_category, last, masks, kDegMaskCap, io);
+    return;
+  }
   hipLaunchKernelGGL(kern::k_loc_contrib, dim3(nbl), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, h->d_mn.as<float4>(), h->d_pos.as<int32_t>(),
                      h->d_d2.as<float>(), a.cp.max_out_r2, st, (const float*)nullptr, (const float*)nullptr, dirs, p.filter_min, p.strong_min, part2, cnt, 1);
   hipLaunchKernelGGL(kern::k_constrain, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), nb, st, kern::DegFixed{}, part2, nbl, dirs, th,
@@ -974,7 +1011,7 @@ int start_call(o3s_icp* h, const float* T_init) {
   Call& c = h->call;
   c.live = false;
   h->cov_valid = h->elements_valid = h->pose_valid = false;
-  h->deg_trace_valid = false;
+  h->deg_trace_valid = h->deg_partial_valid = false;
 #ifdef O3S_TEST_HOOKS
   h->looks.clear();
 #endif
@@ -1008,6 +1045,11 @@ int start_call(o3s_icp* h, const float* T_init) {
   c.issued = 0;
   // the degeneracy area starts a call empty: no set used yet, every mask 0 (o3s_icp_set_degeneracy allocated it)
   if (h->deg.mode != O3S_DEGENERACY_OFF) HIP_TRY(h, hipMemsetAsync(h->d_deg.p, 0, kDegBufBytes, h->stream));
+  if (deg_partial_live(h)) {  // ... and so does the area of the values: the last record and the records this call's iterations can reach
+    const size_t n = (size_t)std::min(c.iters_cap, kDegMaskCap);
+    HIP_TRY(h, hipMemsetAsync(h->d_degp.as<char>() + kDegpOffLast, 0, sizeof(kern::DegPartialLast) + n * 4, h->stream));  // (the masks follow the record)
+    HIP_TRY(h, hipMemsetAsync(h->d_degp.as<char>() + kDegpOffValues, 0, n * 6 * sizeof(double), h->stream));
+  }
   rc = prepare_reading(h, c.T0, h->cfg.sort_queries != 0 && h->cfg.matcher == 0 && !h->reading_presorted, /*reset_chain=*/true, cp.use_differential != 0);
   if (rc != O3S_OK) return rc;
   c.a = chain_args(h, cp);
@@ -1332,6 +1374,7 @@ int compute_finish(o3s_icp* h, float* T_out, o3s_icp_stats* stats) {
   }
   h->cov_valid = h->elements_valid = true;
   h->deg_trace_valid = h->deg.mode != O3S_DEGENERACY_OFF;
+  h->deg_partial_valid = deg_partial_live(h);
   std::memcpy(h->last_T_iter, st.T_iter, sizeof(st.T_iter));
   h->pose_valid = h->r_is_call = true;
   std::memcpy(T_out, out, sizeof(out));
@@ -2051,9 +2094,11 @@ int o3s_icp_outlier_weights(o3s_icp* h, const float* reading_normals, const int3
   return O3S_OK;
 }
 
-// o3s_icp_minimize, and o3s_icp_minimize_degeneracy (degeneracy_impl.h) with `set`: k_constrain in front of k_solve
+// o3s_icp_minimize, and o3s_icp_minimize_degeneracy (degeneracy_impl.h) with `set`: k_constrain in front of k_solve (with `vals`,
+// o3s_icp_minimize_degen_values of degeneracy_partial_impl.h: k_constrain_values)
 static int minimize_impl(o3s_icp* h, const float* reading_xyzw, const int32_t* ids, const float* dists2, const float* weights, int64_t N,
-                         const kern::DegFixed* set, float T_out[16], float A_out[36], float b_out[6], float x_out[6]) {
+                         const kern::DegFixed* set, const double* vals /*nullable: k_constrain_values*/, float T_out[16], float A_out[36],
+                         float b_out[6], float x_out[6]) {
   if (!h || !reading_xyzw || !ids || !dists2 || !weights || !T_out) return O3S_ERR_BAD_ARGUMENT;
   if (!h->ref_ready) return fail(h, O3S_ERR_NOT_INITIALIZED, "minimize before a successful init_reference");
   if (!h->ref_has_normals) return fail(h, O3S_ERR_BAD_SHAPE, "point-to-plane needs reference normals");
@@ -2091,7 +2136,7 @@ static int minimize_impl(o3s_icp* h, const float* reading_xyzw, const int32_t* i
                      (const CandRec*)nullptr, (const uint32_t*)nullptr);
   hipLaunchKernelGGL(kern::k_normal_eq, dim3(a.nb_part), dim3(kern::kBlock), 0, h->stream, a.rx, a.ry, a.rz, a.N, h->d_mq.as<float4>(),
                      h->d_mn.as<float4>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), cp, st, h->d_ne.as<double>(), (uint32_t*)nullptr);
-  if (set) launch_constrain(h, a, a.nb_part, h->stream, set);
+  if (set) launch_constrain(h, a, a.nb_part, h->stream, set, vals);
   hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, h->stream, h->d_ne.as<double>(), a.nb_part, a.N, cp, st,
                      h->d_trace_T.as<float>(), h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 0, (HostPost*)nullptr);
   HIP_TRY(h, hipGetLastError());
@@ -2108,7 +2153,7 @@ static int minimize_impl(o3s_icp* h, const float* reading_xyzw, const int32_t* i
 
 int o3s_icp_minimize(o3s_icp* h, const float* reading_xyzw, const int32_t* ids, const float* dists2, const float* weights, int64_t N,
                      float T_out[16], float A_out[36], float b_out[6], float x_out[6]) {
-  return minimize_impl(h, reading_xyzw, ids, dists2, weights, N, nullptr, T_out, A_out, b_out, x_out);
+  return minimize_impl(h, reading_xyzw, ids, dists2, weights, N, nullptr, nullptr, T_out, A_out, b_out, x_out);
 }
 
 int o3s_icp_get_covariance(const o3s_icp* h, double cov36[36]) {
@@ -2192,3 +2237,4 @@ int64_t o3s_icp_get_error_elements(o3s_icp* h, float* reading_c, float* referenc
 
 #include "localizability_impl.h"
 #include "degeneracy_impl.h"
+#include "degeneracy_partial_impl.h"

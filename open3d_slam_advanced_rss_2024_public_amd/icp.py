@@ -520,8 +520,40 @@ class ICP(_lib.Handle):
         self._check(self._L.o3s_icp_get_degeneracy(self._h, None, C.byref(out)))
         return loc.DegeneracySet.from_c(out)
 
-    def minimize_degeneracy(self, reading_xyz, ids, dists2, weights, dset):
-        """minimize() under C x = 0 for the directions of `dset` (o3s_icp_minimize_degeneracy) -> (T 4x4, A' 6x6, b', x)."""
+    def set_degeneracy_partial(self, enable: bool = True):
+        """o3s_icp_set_degeneracy_partial: with the flag set, every iteration of the ANALYSE chain constrains a partially localizable
+        direction (category 1) to the step its strong pairs alone ask for, instead of to zero or not at all
+        (include/degeneracy/o3s_degeneracy_partial.h).  Off by default."""
+        from . import localizability as loc
+
+        loc._bind(self._L)
+        self._check(self._L.o3s_icp_set_degen_partial(self._h, int(bool(enable))))
+
+    def degeneracy_partial_trace(self):
+        """o3s_icp_degeneracy_partial_trace: (partial masks (n,) int32, values (n, 6) float64), one record per iteration of the last
+        successful compute: the directions of category 1 and what their rows carried.  Empty when the flag is off."""
+        from . import localizability as loc
+
+        loc._bind(self._L)
+        masks = np.zeros(4096, np.int32)
+        values = np.zeros((4096, 6), np.float64)
+        n = int(self._L.o3s_icp_degen_partial_trace(self._h, _ip(masks), values.ctypes.data_as(C.POINTER(C.c_double)), masks.shape[0]))
+        return masks[:n].copy(), values[:n].copy()
+
+    def last_degeneracy_partial(self):
+        """(flag, localizability.DegeneracyPartial of the last constrained iteration of the last successful compute)
+        (o3s_icp_get_degeneracy_partial)."""
+        from . import localizability as loc
+
+        loc._bind(self._L)
+        on, out = C.c_int32(0), loc.DegeneracyPartialC()
+        self._check(self._L.o3s_icp_get_degen_partial(self._h, C.byref(on), C.byref(out)))
+        return bool(on.value), loc.DegeneracyPartial.from_c(out)
+
+    def minimize_degeneracy(self, reading_xyz, ids, dists2, weights, dset, values=None):
+        """minimize() under C x = 0 for the directions of `dset` (o3s_icp_minimize_degeneracy) -> (T 4x4, A' 6x6, b', x).
+        values = (rot_values, trans_values), one number per direction of `dset`: the step under C x = d instead
+        (o3s_icp_minimize_degeneracy_values); either of the two may be None (a NULL array: zeros)."""
         from . import localizability as loc
 
         loc._bind(self._L)
@@ -534,8 +566,23 @@ class ICP(_lib.Handle):
         b = np.zeros(6, np.float32)
         x = np.zeros(6, np.float32)
         sc = dset.to_c()
-        self._check(self._L.o3s_icp_minimize_degeneracy(self._h, _fp(q), _ip(ids), _fp(d2), _fp(w), q.shape[0], C.byref(sc), _fp(T), _fp(A),
-                                                        _fp(b), _fp(x)))
+        if values is None:
+            self._check(self._L.o3s_icp_minimize_degeneracy(self._h, _fp(q), _ip(ids), _fp(d2), _fp(w), q.shape[0], C.byref(sc), _fp(T), _fp(A),
+                                                            _fp(b), _fp(x)))
+        else:
+            dp = C.POINTER(C.c_double)
+            keep, ptrs = [], []
+            for v in values:                                  # None: a NULL array (zeros; both NULL: o3s_icp_minimize_degeneracy's bits)
+                if v is None:
+                    ptrs.append(None)
+                    continue
+                v_in = np.asarray(v, np.float64).reshape(-1)
+                buf = np.zeros(3)
+                buf[:min(3, len(v_in))] = v_in[:3]
+                keep.append(buf)
+                ptrs.append(buf.ctypes.data_as(dp))
+            self._check(self._L.o3s_icp_minimize_degen_values(self._h, _fp(q), _ip(ids), _fp(d2), _fp(w), q.shape[0], C.byref(sc), ptrs[0], ptrs[1],
+                                                              _fp(T), _fp(A), _fp(b), _fp(x)))
         return _from_colmajor(T), A.reshape(6, 6).T.copy(), b, x
 
     def get_max_num_iterations_reached(self) -> bool:

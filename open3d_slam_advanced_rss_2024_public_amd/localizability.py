@@ -47,6 +47,28 @@ class DegeneracyConfigC(C.Structure):   # o3s_degeneracy_config
     _fields_ = [("mode", C.c_int32), ("min_category", C.c_int32), ("fixed_set", DegeneracySetC), ("loc_params", LocalizabilityParamsC)]
 
 
+class DegeneracyPartialC(C.Structure):   # o3s_degeneracy_partial (include/degeneracy/o3s_degeneracy_partial.h)
+    _fields_ = [("num", C.c_double * 6), ("den", C.c_double * 6), ("value", C.c_double * 6), ("category", C.c_int32 * 6),
+                ("partial_mask", C.c_int32), ("constrained_mask", C.c_int32)]
+
+
+@dataclass
+class DegeneracyPartial:
+    """o3s_degeneracy_partial: the strong-pair sums of the six directions (the mask's order: translation 0..2, rotation 3..5),
+    value = -num / den, the categories, the directions of category 1 and the whole constrained set."""
+    num: np.ndarray = field(default_factory=lambda: np.zeros(6))
+    den: np.ndarray = field(default_factory=lambda: np.zeros(6))
+    value: np.ndarray = field(default_factory=lambda: np.zeros(6))
+    category: np.ndarray = field(default_factory=lambda: np.zeros(6, np.int32))
+    partial_mask: int = 0
+    constrained_mask: int = 0
+
+    @classmethod
+    def from_c(cls, c: DegeneracyPartialC) -> "DegeneracyPartial":
+        return cls(np.array(c.num[:], np.float64), np.array(c.den[:], np.float64), np.array(c.value[:], np.float64),
+                   np.array(c.category[:], np.int32), int(c.partial_mask), int(c.constrained_mask))
+
+
 @dataclass
 class DegeneracySet:
     """o3s_degeneracy_set: up to three unit rotation directions and up to three unit translation directions, (n, 3) float64 each,
@@ -138,6 +160,13 @@ def _bind(L):
         L.o3s_icp_degeneracy_trace.argtypes = [C.c_void_p, ip, C.c_int32]
         L.o3s_icp_degeneracy_trace.restype = C.c_int32
         L.o3s_icp_minimize_degeneracy.argtypes = [C.c_void_p, fp, ip, fp, fp, C.c_int64, sp, fp, fp, fp, fp]
+        qp = C.POINTER(DegeneracyPartialC)   # o3s_degeneracy_partial.h (the link names abbreviate "degeneracy")
+        L.o3s_icp_set_degen_partial.argtypes = [C.c_void_p, C.c_int32]
+        L.o3s_icp_get_degen_partial.argtypes = [C.c_void_p, ip, qp]
+        L.o3s_icp_degen_partial_trace.argtypes = [C.c_void_p, ip, dp, C.c_int32]
+        L.o3s_icp_degen_partial_trace.restype = C.c_int32
+        L.o3s_degen_partial_estimate.argtypes = [C.c_void_p, fp, fp, fp, C.c_int64, pp, op, qp]
+        L.o3s_icp_minimize_degen_values.argtypes = [C.c_void_p, fp, ip, fp, fp, C.c_int64, sp, dp, dp, fp, fp, fp, fp]
     return L
 
 
@@ -168,7 +197,24 @@ def remap_pose(loc: Localizability, T_prior, T_icp, min_category: int = PARTIALL
     return out.reshape(4, 4).T.copy(), int(n.value)
 
 
-def minimize_degeneracy(icp, reading_xyz, ids, dists2, weights, dset: DegeneracySet):
+def minimize_degeneracy(icp, reading_xyz, ids, dists2, weights, dset: DegeneracySet, values=None):
     """o3s_icp_minimize_degeneracy: ICP.minimize with the step constrained to have no component along the directions of `dset`
-    -> (T 4x4, A' 6x6, b', x): the constrained system as the solver took it."""
-    return icp.minimize_degeneracy(reading_xyz, ids, dists2, weights, dset)
+    -> (T 4x4, A' 6x6, b', x): the constrained system as the solver took it.  values = (rot_values, trans_values): the step's
+    components along the directions instead of zero (o3s_icp_minimize_degeneracy_values)."""
+    return icp.minimize_degeneracy(reading_xyz, ids, dists2, weights, dset, values=values)
+
+
+def partial_estimate(icp, reading_c, reference_c, normals, params: LocalizabilityParams):
+    """o3s_degeneracy_partial_estimate: the analysis and the strong-pair sums of (K, 3) arrays of ALREADY centred pairs
+    -> (Localizability, DegeneracyPartial); the first is o3s_localizability_estimate's result bit for bit."""
+    fp = C.POINTER(C.c_float)
+    p = np.ascontiguousarray(reading_c, np.float32).reshape(-1, 3)
+    q = np.ascontiguousarray(reference_c, np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if not (p.shape == q.shape == n.shape):
+        raise ValueError("reading_c, reference_c and normals must have the same shape (K, 3)")
+    L = _bind(icp._L)
+    lc, pc, out = LocalizabilityC(), params.to_c(), DegeneracyPartialC()
+    icp._check(L.o3s_degen_partial_estimate(icp._h, p.ctypes.data_as(fp), q.ctypes.data_as(fp), n.ctypes.data_as(fp), p.shape[0], C.byref(pc),
+                                            C.byref(lc), C.byref(out)))
+    return Localizability.from_c(lc), DegeneracyPartial.from_c(out)

@@ -89,7 +89,10 @@ class Mapper:
         self.degeneracy_policy = "Off"
         self.localizability_params = None
         self.remap_min_category = 1
-        self.last_localizability = None       # None: the policy is Off, that registration failed, or before the first one
+        # MapperParams::degeneracyPartial (Constrain only): a partially localizable direction (category 1) is constrained to the
+        # step its strong pairs alone ask for (ICP.set_degeneracy_partial) instead of to zero or not at all
+        self.degeneracy_partial = False
+        self.last_localizability = None      # None: the policy is Off, that registration failed, or before the first one
         self.last_remap_replaced = 0
         self.last_registration_pose = np.eye(4)
         self._degeneracy_armed = None         # what the ICP handle was last told (Constrain): (params, min_category)
@@ -183,14 +186,19 @@ class Mapper:
         want = None
         if self.degeneracy_policy == "Constrain":
             p = self.localizability_params
-            want = (None if p is None else (p.filter_min, p.strong_min, p.sum_all_min, p.sum_strong_min, p.sum_partial_min), self.remap_min_category)
+            want = (None if p is None else (p.filter_min, p.strong_min, p.sum_all_min, p.sum_strong_min, p.sum_partial_min), self.remap_min_category,
+                    bool(self.degeneracy_partial))
         if want == self._degeneracy_armed:
             return
         if want is None:
             self.icp.set_degeneracy(loc.DEGENERACY_OFF)
+            if self._degeneracy_armed is not None and self._degeneracy_armed[2]:
+                self.icp.set_degeneracy_partial(False)
         else:
             self.icp.set_degeneracy(loc.DEGENERACY_ANALYSE, params=self.localizability_params or loc.LocalizabilityParams(),
                                     min_category=self.remap_min_category)
+            if want[2] or (self._degeneracy_armed is not None and self._degeneracy_armed[2]):   # (a mapper that never asks makes no call)
+                self.icp.set_degeneracy_partial(want[2])
         self._degeneracy_armed = want
 
     def add(self, sp, sn, stamp, point_times=None):

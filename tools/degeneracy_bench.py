@@ -18,7 +18,13 @@ runs alternate (parent, off, parent, off, fixed, analyse); a run is a fresh hand
 o3s_icp_stats::gpu_ms (the chain's own stamps: first matcher launch -> the k_solve that posts the final state, so the added
 launches are inside it).  CONFIGS=C2 (or C4, or C2,C4) picks the pairs; OUT=<path> also writes the JSON there
 (profiles/degeneracy/).  TRACE=1: no parent, five `analyse` calls and five `fixed` calls — the run to put under
-`rocprofv3 --kernel-trace --stats` for the kernels' own times."""
+`rocprofv3 --kernel-trace --stats` for the kernels' own times.
+
+--partial: also what o3s_icp_set_degeneracy_partial (include/degeneracy/o3s_degeneracy_partial.h) costs: `analyse_partial` is
+`analyse` with the flag set — the flagged pass 2 forms the strong-pair sums in every iteration, and with thresholds of 0 nothing
+is constrained, so the iterations and the pose are again those of `off` — against a second `analyse` run of the same process
+(flag off) and, when the parent library is given, against the parent's own `analyse`.  Nothing is constrained in these runs, so
+k_constrain_values returns behind its fold: the value algebra of a constrained iteration is not in the difference."""
 import ctypes as C
 import gc
 import json
@@ -39,6 +45,7 @@ WARM = int(os.environ.get("WARM", "3"))
 CONFIGS = {"C2": (100_000, 2_000_000, 0.1), "C4": (500_000, 20_000_000, 0.02)}
 WHICH = [c for c in os.environ.get("CONFIGS", "C2").split(",") if c]
 PARENT = os.environ.get("PARENT") or _lib.variant_path("parent")
+PARTIAL = "--partial" in sys.argv[1:]
 
 
 def fp(a):
@@ -58,6 +65,8 @@ def open_library(path):
     if hasattr(L, "o3s_icp_set_degeneracy"):
         L.o3s_icp_set_degeneracy.argtypes = [vp, C.c_int32, C.POINTER(loc.DegeneracySetC), C.POINTER(loc.LocalizabilityParamsC), C.c_int32]
         L.o3s_icp_degeneracy_trace.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32]
+    if hasattr(L, "o3s_icp_set_degen_partial"):
+        L.o3s_icp_set_degen_partial.argtypes = [vp, C.c_int32]
     return L
 
 
@@ -76,9 +85,11 @@ def run(L, sp, mode):
     if mode == "fixed":
         empty = loc.DegeneracySet().to_c()
         assert L.o3s_icp_set_degeneracy(h, loc.DEGENERACY_FIXED, C.byref(empty), None, 2) == 0
-    elif mode == "analyse":
+    elif mode in ("analyse", "analyse_partial"):
         params = loc.LocalizabilityParams(sum_all_min=0.0, sum_strong_min=0.0, sum_partial_min=0.0).to_c()
         assert L.o3s_icp_set_degeneracy(h, loc.DEGENERACY_ANALYSE, None, C.byref(params), 2) == 0
+        if mode == "analyse_partial":
+            assert L.o3s_icp_set_degen_partial(h, 1) == 0
     Tin = np.ascontiguousarray(sp.T_init.astype(np.float32).T).reshape(16)
     Tout = np.zeros(16, np.float32)
     st = _lib.IcpStatsC()
@@ -96,7 +107,7 @@ def run(L, sp, mode):
     gc.enable()
     r = {"wall_us_median": median(wall), "wall_us_min": float(min(wall)), "chain_gpu_us_median": median(gpu), "chain_gpu_us_min": float(min(gpu)),
          "iterations": int(st.iterations), "kept_pairs": int(st.kept_pairs), "pose": [float(x) for x in Tout]}
-    if mode in ("fixed", "analyse"):
+    if mode in ("fixed", "analyse", "analyse_partial"):
         masks = np.full(64, -1, np.int32)
         n = L.o3s_icp_degeneracy_trace(h, masks.ctypes.data_as(C.POINTER(C.c_int32)), 64)
         r["masks"] = masks[:n].tolist()
@@ -128,13 +139,29 @@ def one_config(name, product, parent):
         res[f"same_pose_{mode}_and_off"] = res[mode]["pose"] == res["off_a"]["pose"] and it == res["off_a"]["iterations"]
         res[f"{mode}_minus_off_per_registration_us"] = {"wall": res[mode]["wall_us_median"] - off_wall, "gpu": res[mode]["chain_gpu_us_median"] - off_gpu}
         res[f"{mode}_minus_off_per_iteration_us"] = {"wall": (res[mode]["wall_us_median"] - off_wall) / it, "gpu": (res[mode]["chain_gpu_us_median"] - off_gpu) / it}
+    if PARTIAL:
+        if parent:
+            res["parent_analyse"] = run(parent, sp, "analyse")
+        res["analyse_partial"] = run(product, sp, "analyse_partial")
+        res["analyse_b"] = run(product, sp, "analyse")
+        it = res["analyse_partial"]["iterations"]
+        res["same_pose_analyse_partial_and_off"] = res["analyse_partial"]["pose"] == res["off_a"]["pose"] and it == res["off_a"]["iterations"]
+        base = {key: min(res["analyse"][key], res["analyse_b"][key]) for key in ("wall_us_median", "chain_gpu_us_median")}
+        res["analyse_partial_minus_analyse_per_iteration_us"] = {"wall": (res["analyse_partial"]["wall_us_median"] - base["wall_us_median"]) / it,
+                                                                 "gpu": (res["analyse_partial"]["chain_gpu_us_median"] - base["chain_gpu_us_median"]) / it}
+        res["analyse_spread_per_iteration_us"] = {"gpu": abs(res["analyse"]["chain_gpu_us_median"] - res["analyse_b"]["chain_gpu_us_median"]) / it}
+        if parent:
+            res["analyse_minus_parent_analyse_per_iteration_us"] = {
+                "gpu": (base["chain_gpu_us_median"] - res["parent_analyse"]["chain_gpu_us_median"]) / it}
+            res["analyse_partial_minus_parent_analyse_per_iteration_us"] = {
+                "gpu": (res["analyse_partial"]["chain_gpu_us_median"] - res["parent_analyse"]["chain_gpu_us_median"]) / it}
     if parent:
         res["same_pose_as_parent"] = res["parent_a"]["pose"] == res["off_a"]["pose"]
         for key in ("wall_us_median", "chain_gpu_us_median"):
             pa, pb = res["parent_a"][key], res["parent_b"][key]
             res[f"{key}_parent_spread"] = abs(pa - pb)
             res[f"{key}_off_minus_parent"] = min(res["off_a"][key], res["off_b"][key]) - min(pa, pb)
-    for k in ("parent_a", "parent_b", "off_a", "off_b", "fixed", "analyse"):
+    for k in ("parent_a", "parent_b", "off_a", "off_b", "fixed", "analyse", "parent_analyse", "analyse_partial", "analyse_b"):
         if k in res:
             res[k].pop("pose")
     return res
