@@ -909,22 +909,95 @@ constexpr int kFarQ = 6;      // ranges per batch of the row-disc search (4: 53.
 // CERT: the launch reads and leaves certificates (`cert` is not null).  Without it the kernel is the one it was before there were
 // certificates — nothing of their book-keeping is compiled in: the first iteration of a call, whose far search is bound by
 // instruction issue and has nothing to settle, and every path that keeps none (module-level entry points, sharded chain).
+// FRONT (with CERT only): the settle front of a converged launch.  Phase A holds ONE lane per query
+// (kBlock queries per block, half / a quarter of the waves): the first trip and the settle decision are the CERT head's own, and a
+// valid query that does not settle goes onto the block's list in LDS.  Phase B, behind a barrier, deals the list to G lanes per
+// entry and runs the same search body on it.  Outputs are per query and every count is an integer: the same bits as without it.
+
+// A found match is counted where it is written: the level-1 bin of its d2 in the block's histogram (the first toucher of a bin
+// flushes it at the end of the launch) and, under a finite previous limit, the next digit of the pairs that share its leading
+// 11 / 21 bits.  ... and the two bin counters: the lanes that counted a match, and those of them whose level-1 bin lies below the
+// previous limit's.  Tallied per wave (ballot + popcount into two scalars, no register per lane: the kernel is at its limit) at the
+// convergent point behind each place that calls count_match.
+// MULTI: a lane may count more than one match in a launch (the settle front: its own query, then list entries).  `mybin` holds one
+// bin, so a lane that becomes the first toucher of a second bin flushes the first and hands it back: the next lane that touches it
+// finds 0 and owns it.  Integer sums, whatever the order.
+template <bool MULTI>
+struct MatchCount {
+  uint32_t* s_hist;    // the block's level-1 histogram (LDS)
+  uint32_t* rep;       // the level-1 replica this block flushes to
+  uint32_t* spec_cur;  // this iteration's speculative digit histograms (null unless spec_on)
+  uint32_t hint;       // bits of the previous limit
+  bool spec_on;        // uniform
+  int dbg;             // hooks build: O3S_DBG's switches (0 in the product)
+  int mybin = -1;
+  uint32_t n_found = 0u, n_below = 0u;  // uniform
+  __device__ __forceinline__ void count_match(float d) {
+    const int bin = (int)((__float_as_uint(d) >> 20) & (kHistBins - 1));
+    if (!O3S_DBG(1) && atomicAdd(&s_hist[bin], 1u) == 0u) {
+      if (MULTI && mybin >= 0) {
+        const uint32_t v = atomicExch(&s_hist[mybin], 0u);
+        if (v) atomicAdd(&rep[mybin], v);
+      }
+      mybin = bin;
+    }
+    if (spec_on && !O3S_DBG(1)) {  // ~2 % of the lanes: plain global atomics
+      const uint32_t key = __float_as_uint(d) & 0x7fffffffu;
+      if ((key >> 20) == (hint >> 20)) atomicAdd(&spec_cur[(key >> 10) & 1023u], 1u);
+      if ((key >> 10) == (hint >> 10)) atomicAdd(&spec_cur[1024 + (key & 1023u)], 1u);
+    }
+  }
+  __device__ __forceinline__ void tally(bool counted, float d) {
+    if (spec_on && !O3S_DBG(1)) {  // uniform
+      const bool below = counted && ((__float_as_uint(d) & 0x7fffffffu) >> 20) < (hint >> 20);
+      n_found += (uint32_t)__popcll(__ballot(counted));
+      n_below += (uint32_t)__popcll(__ballot(below));
+    }
+  }
+};
+
+// the search of one query by the G lanes that hold it (lane `sub` of the group), from the pruning bound to the outputs: defined
+// behind the kernel, which calls it for its own query or, in the settle front, for the entries of the block's list
+template <bool STATS, int G, int UN, int RCB, bool FAR, bool CERT, class Count>
+__device__ __forceinline__ void match_search(const int i, const int sub, const bool valid, const bool settled, const bool wave_settled, bool active,
+                                             const float sx, const float sy, const float sz, const float4 inc, const float (&T)[16],
+                                             const float4* __restrict__ ref, const uint32_t* __restrict__ cell_start, const GridParams& g,
+                                             int32_t* __restrict__ pos_out, float* __restrict__ d2_out, float4* __restrict__ mq,
+                                             const float4* __restrict__ refn, float4* __restrict__ mn, const float* __restrict__ rnx,
+                                             const float* __restrict__ rny, const float* __restrict__ rnz, float* __restrict__ cert, Count& cnt,
+                                             unsigned long long& n_cand, unsigned long long& n_rows O3S_DBG_PARAM);
+
+constexpr int kFrontWaves = 4;  // waves per SIMD the settle front is compiled for: it has half / a quarter of the waves, and the list's loop keeps more alive
+// the kernel's parameters, shared by its two entry points below (the launch without the front keeps its six template arguments
+// and so its symbol, which the trace tools and tools/isa_round_trips.py know it by; the front is the overload with a seventh)
+#define O3S_MATCH2_PARAMS                                                                                                          \
+  const float *__restrict__ rx, const float *__restrict__ ry, const float *__restrict__ rz, int N, const float4 *__restrict__ ref,  \
+      const uint32_t *__restrict__ cell_start, GridParams g, IcpState *__restrict__ st, int32_t *__restrict__ pos_out,               \
+      float *__restrict__ d2_out, float4 *__restrict__ mq, uint32_t *__restrict__ hist_rep,                                          \
+      const float4 *__restrict__ refn /*reference normals in slot order (nullable)*/,                                               \
+      float4 *__restrict__ mn /*out (nullable): the matched normal of every query*/, const float *__restrict__ rnx,                  \
+      const float *__restrict__ rny, const float *__restrict__ rnz /*FAR: the reading's normals (nullable): the seed probe's direction*/, \
+      int rep_mask /*level-1 replicas - 1 (15; fewer in the sharded mode, where they travel)*/,                                     \
+      uint32_t *__restrict__ spec /*nullable: speculative digit histograms [kSpecWords]*/,                                          \
+      float *__restrict__ cert /*CERT: the queries' certificates [N], read and rewritten; else null*/                               \
+      O3S_DBG_PARAM /*hooks build only: timing experiments (o3s_icp_profile_match)*/                                                \
+      O3S_HOOK_PARAM(uint32_t *__restrict__ settled_cnt /*nullable: [kHistReplicas][2][kSpecTrace] per iteration: queries whose      \
+                     certificate held, queries of the waves in which every valid query settled*/)
+#define O3S_MATCH2_ARGS                                                                                                             \
+  rx, ry, rz, N, ref, cell_start, g, st, pos_out, d2_out, mq, hist_rep, refn, mn, rnx, rny, rnz, rep_mask, spec, cert O3S_DBG_ARG(dbg) \
+      O3S_DBG_ARG(settled_cnt)
+template <bool STATS, int G, int UN, int RCB, bool FAR, bool CERT, bool FRONT>
+__device__ __forceinline__ void match2_body(O3S_MATCH2_PARAMS);
 template <bool STATS, int G, int UN, int RCB, bool FAR, bool CERT>
-__global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz,
-                                                      int N, const float4* __restrict__ ref, const uint32_t* __restrict__ cell_start,
-                                                      GridParams g, IcpState* __restrict__ st,
-                                                      int32_t* __restrict__ pos_out, float* __restrict__ d2_out, float4* __restrict__ mq,
-                                                      uint32_t* __restrict__ hist_rep,
-                                                      const float4* __restrict__ refn /*reference normals in slot order (nullable)*/,
-                                                      float4* __restrict__ mn /*out (nullable): the matched normal of every query*/,
-                                                      const float* __restrict__ rnx, const float* __restrict__ rny,
-                                                      const float* __restrict__ rnz /*FAR: the reading's normals (nullable): the seed probe's direction*/,
-                                                      int rep_mask /*level-1 replicas - 1 (15; fewer in the sharded mode, where they travel)*/,
-                                                      uint32_t* __restrict__ spec /*nullable: speculative digit histograms [kSpecWords]*/,
-                                                      float* __restrict__ cert /*CERT: the queries' certificates [N], read and rewritten; else null*/
-                                                      O3S_DBG_PARAM /*hooks build only: timing experiments (o3s_icp_profile_match)*/
-                                                      O3S_HOOK_PARAM(uint32_t* __restrict__ settled_cnt /*nullable: [kHistReplicas][2][kSpecTrace]
-                                                      per iteration: queries whose certificate held, queries of the waves that skipped the search*/)) {
+__global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(O3S_MATCH2_PARAMS) {
+  match2_body<STATS, G, UN, RCB, FAR, CERT, false>(O3S_MATCH2_ARGS);
+}
+template <bool STATS, int G, int UN, int RCB, bool FAR, bool CERT, bool FRONT>
+__global__ void __launch_bounds__(kBlock, FRONT ? kFrontWaves : FAR ? kFarWaves : 7) k_match2(O3S_MATCH2_PARAMS) {
+  match2_body<STATS, G, UN, RCB, FAR, CERT, FRONT>(O3S_MATCH2_ARGS);
+}
+template <bool STATS, int G, int UN, int RCB, bool FAR, bool CERT, bool FRONT>
+__device__ __forceinline__ void match2_body(O3S_MATCH2_PARAMS) {
   __shared__ uint32_t s_hist[kHistBins];
   __shared__ uint32_t s_cnt[2];  // the block's bin counters {F, Bl}: one LDS add per wave, one global atomic per block and counter
   if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
@@ -932,10 +1005,15 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
   __shared__ uint32_t s_set[2];  // the block's settled queries: one global atomic per block and counter, spread over the replicas
   if (threadIdx.x < 2) s_set[threadIdx.x] = 0u;
 #endif
-  constexpr int TQ = kBlock / G;        // queries per block: ONE tile per block (straight-line code, nothing kept alive across tiles)
-  constexpr int NK = (9 + G - 1) / G;   // rows of the 3x3x3 block a lane owns: t = sub, sub + G, ...
-  const int sub = threadIdx.x & (G - 1);
-  const int qib = threadIdx.x / G;
+  static_assert(CERT || !FRONT, "the settle front is a launch that carries certificates");
+  __shared__ int s_open[FRONT ? kBlock : 1];  // FRONT: the block's open queries, in any order
+  __shared__ float s_oq[7][FRONT ? kBlock : 1];  // ... and what their search starts from: sx sy sz, the incumbent (x y z w)
+  __shared__ uint32_t s_nopen;
+  if (FRONT && threadIdx.x == 0) s_nopen = 0u;
+  constexpr int GA = FRONT ? 1 : G;      // lanes per query up to the settle decision
+  constexpr int TQ = kBlock / GA;        // queries per block: ONE tile per block (straight-line code, nothing kept alive across tiles)
+  const int sub = threadIdx.x & (GA - 1);
+  const int qib = threadIdx.x / GA;
   // XCD-aware: gridDim.x is a multiple of 8; blocks b, b + 8, ... (one XCD) walk a contiguous range of the sorted reading
   const int tile = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
   const int i = tile * TQ + qib;
@@ -986,37 +1064,17 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
   unsigned long long n_cand = 0, n_rows = 0;
 
   const float sx = xf_row(T, 0, px, py, pz), sy = xf_row(T, 1, px, py, pz), sz = xf_row(T, 2, px, py, pz);
-  Own b{kInfF, 0x7fffffff, -1, 0.f, 0.f, 0.f};
-  float gd = kInfF;  // the group's best so far
-  int gi = 0x7fffffff;
   // a NaN or infinite query (a NaN in the reading, an overflow under the pose) has no neighbour — every distance test fails, in
   // libnabo's walk as in the brute force — and is settled here: its cell and offsets are not numbers, and with an unbounded
   // maxDist the ring search would walk every ring of the grid for it
   bool active = valid && ((fabsf(sx) + fabsf(sy)) + fabsf(sz) < kInfF);
-  float bound = lim;
-  // a found match is counted where it is written: the level-1 bin of its d2 in the block's histogram (the first toucher of a bin
-  // flushes it at the end) and, under a finite previous limit, the next digit of the pairs that share its leading 11 / 21 bits
-  int mybin = -1;
-  auto count_match = [&](float d) {
-    const int bin = (int)((__float_as_uint(d) >> 20) & (kHistBins - 1));
-    if (!O3S_DBG(1) && atomicAdd(&s_hist[bin], 1u) == 0u) mybin = bin;
-    if (spec_on && !O3S_DBG(1)) {  // ~2 % of the lanes: plain global atomics
-      const uint32_t key = __float_as_uint(d) & 0x7fffffffu;
-      if ((key >> 20) == (hint >> 20)) atomicAdd(&spec_cur[(key >> 10) & 1023u], 1u);
-      if ((key >> 10) == (hint >> 10)) atomicAdd(&spec_cur[1024 + (key & 1023u)], 1u);
-    }
-  };
-  // ... and the two bin counters: the lanes that counted a match, and those of them whose level-1 bin lies below the previous limit's.
-  // Tallied per wave (ballot + popcount into two scalars, no register per lane: the kernel is at its limit) at the convergent point
-  // behind each of the two places that call count_match; a lane counts a match in at most one of them.
-  uint32_t n_found = 0u, n_below = 0u;  // uniform
-  auto tally = [&](bool counted, float d) {
-    if (spec_on && !O3S_DBG(1)) {  // uniform
-      const bool below = counted && ((__float_as_uint(d) & 0x7fffffffu) >> 20) < (hint >> 20);
-      n_found += (uint32_t)__popcll(__ballot(counted));
-      n_below += (uint32_t)__popcll(__ballot(below));
-    }
-  };
+  // the launch's counts of found matches (the level-1 histogram, the speculative digits, the two bin counters)
+#ifdef O3S_TEST_HOOKS
+  const int cnt_dbg = dbg;
+#else
+  const int cnt_dbg = 0;
+#endif
+  MatchCount<FRONT> cnt{s_hist, hist_rep + (size_t)(blockIdx.x & (unsigned)rep_mask) * kHistBins, spec_cur, hint, spec_on, cnt_dbg};
   // ---- the certificate's fast path: a query that moved by less than its certificate leaves room for keeps its match (or stays
   //      unmatched) without a search; a wave of such queries writes its outputs here and is done ----
   bool wave_settled = false;  // uniform: every valid query of the wave is settled (the seed probe's condition, the hooks' counter)
@@ -1058,14 +1116,94 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
         if (inc.w != 0.f) {  // mq and mn keep the match they hold
           pos_out[i] = pe >= 0 ? pe : -2 - pe;
           d2_out[i] = dn;
-          count_match(dn);
+          cnt.count_match(dn);
         }
         cert[i] = cn;
       }
     }
-    tally(settled && !O3S_DBG(8) && sub == 0 && inc.w != 0.f, dn);
+    cnt.tally(settled && !O3S_DBG(8) && sub == 0 && inc.w != 0.f, dn);
     active = active && !settled;
   }
+  if (!FRONT) {
+    match_search<STATS, G, UN, RCB, FAR, CERT>(i, sub, valid, settled, wave_settled, active, sx, sy, sz, inc, T, ref, cell_start, g, pos_out, d2_out,
+                                               mq, refn, mn, rnx, rny, rnz, cert, cnt, n_cand, n_rows O3S_DBG_ARG(dbg));
+  } else {
+    // ---- phase A ends: the valid queries that did not settle (a stale or zero certificate and a query that is not a number
+    //      included) go onto the block's list — one ballot, one popcount and one LDS add per wave ----
+    {
+      const bool open = valid && !settled;
+      const unsigned long long om = __ballot(open);
+      if (om) {  // uniform
+        uint32_t base = 0u;
+        if ((threadIdx.x & 63) == 0) base = atomicAdd(&s_nopen, (uint32_t)__popcll(om));
+        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        if (open) {  // at most kBlock entries: one per thread
+          const uint32_t e = base + (uint32_t)__popcll(om & ((1ull << (threadIdx.x & 63)) - 1ull));
+          s_open[e] = i;
+          s_oq[0][e] = sx;
+          s_oq[1][e] = sy;
+          s_oq[2][e] = sz;
+          s_oq[3][e] = inc.x;
+          s_oq[4][e] = inc.y;
+          s_oq[5][e] = inc.z;
+          s_oq[6][e] = inc.w;
+        }
+      }
+    }
+    __syncthreads();
+    // ---- phase B: the list in chunks of kBlock / G entries, G lanes per entry.  An entry carries what the search starts from (the
+    //      query under this launch's pose, its incumbent: the very values phase A held, so no first trip is repeated) and its search
+    //      is the one every other launch runs.  Block-uniform bounds, nothing waits on another block. ----
+    const int n_open = (int)s_nopen;
+    for (int e0 = 0; e0 < n_open; e0 += kBlock / G) {
+      if (e0 + (int)(threadIdx.x & ~63u) / G >= n_open) continue;  // a wave with no entry in this chunk (uniform per wave)
+      const int e = e0 + (int)threadIdx.x / G;
+      const bool ev = e < n_open;
+      const int el = ev ? e : 0;
+      const int q = ev ? s_open[el] : 0;
+      const float tx = s_oq[0][el], ty = s_oq[1][el], tz = s_oq[2][el];
+      const float4 qinc = ev ? make_float4(s_oq[3][el], s_oq[4][el], s_oq[5][el], s_oq[6][el]) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const bool qact = ev && ((fabsf(tx) + fabsf(ty)) + fabsf(tz) < kInfF);
+      match_search<STATS, G, UN, RCB, FAR, CERT>(q, (int)(threadIdx.x & (G - 1)), ev, false, false, qact, tx, ty, tz, qinc, T, ref, cell_start, g, pos_out,
+                                                 d2_out, mq, refn, mn, rnx, rny, rnz, cert, cnt, n_cand, n_rows O3S_DBG_ARG(dbg));
+    }
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (cnt.n_found) atomicAdd(&s_cnt[0], cnt.n_found);
+    if (cnt.n_below) atomicAdd(&s_cnt[1], cnt.n_below);
+  }
+  __syncthreads();
+  if (spec_on && threadIdx.x < 2 && s_cnt[threadIdx.x])
+    atomicAdd(&spec_cur[kSpecHist + 2 * (blockIdx.x & (kSpecCntCopies - 1)) + threadIdx.x], s_cnt[threadIdx.x]);
+#ifdef O3S_TEST_HOOKS
+  if (CERT && settled_cnt && threadIdx.x < 2 && s_set[threadIdx.x] && hdr_i(hv, H_ITER) < kSpecTrace)
+    atomicAdd(&settled_cnt[((blockIdx.x & (kHistReplicas - 1)) * 2 + threadIdx.x) * kSpecTrace + hdr_i(hv, H_ITER)], s_set[threadIdx.x]);
+#endif
+  if (cnt.mybin >= 0) atomicAdd(&cnt.rep[cnt.mybin], s_hist[cnt.mybin]);
+  if (STATS) {
+    n_cand = wave_sum_u64(n_cand);
+    n_rows = wave_sum_u64(n_rows);
+    if ((threadIdx.x & 63) == 0) {
+      atomicAdd(&st->cand_count, n_cand);
+      atomicAdd(&st->row_count, n_rows);
+    }
+  }
+}
+
+template <bool STATS, int G, int UN, int RCB, bool FAR, bool CERT, class Count>
+__device__ __forceinline__ void match_search(const int i, const int sub, const bool valid, const bool settled, const bool wave_settled, bool active,
+                                             const float sx, const float sy, const float sz, const float4 inc, const float (&T)[16],
+                                             const float4* __restrict__ ref, const uint32_t* __restrict__ cell_start, const GridParams& g,
+                                             int32_t* __restrict__ pos_out, float* __restrict__ d2_out, float4* __restrict__ mq,
+                                             const float4* __restrict__ refn, float4* __restrict__ mn, const float* __restrict__ rnx,
+                                             const float* __restrict__ rny, const float* __restrict__ rnz, float* __restrict__ cert, Count& cnt,
+                                             unsigned long long& n_cand, unsigned long long& n_rows O3S_DBG_PARAM) {
+  constexpr int NK = (9 + G - 1) / G;   // rows of the 3x3x3 block a lane owns: t = sub, sub + G, ...
+  const float lim = g.max_r2;
+  Own b{kInfF, 0x7fffffff, -1, 0.f, 0.f, 0.f};
+  float gd = kInfF;  // the group's best so far
+  int gi = 0x7fffffff;
+  float bound = lim;
   if (active) {
     // ---- pruning bound: the previous correspondence under the new pose (any reference point is an upper bound) ----
     const float di = dist2(sx, sy, sz, inc.x, inc.y, inc.z);
@@ -1491,7 +1629,7 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
       mq[i] = make_float4(b.qx, b.qy, b.qz, 1.f);
       if (mn) mn[i] = nq;
       if (FAR && CERT) cert[i] = cn;
-      count_match(b.d);
+      cnt.count_match(b.d);
       counted = true;
     } else if (!found && sub == 0) {
       pos_out[i] = -1;
@@ -1501,27 +1639,7 @@ __global__ void __launch_bounds__(kBlock, FAR ? kFarWaves : 7) k_match2(const fl
       if (FAR && CERT) cert[i] = cn;
     }
   }
-  tally(counted, b.d);
-  if ((threadIdx.x & 63) == 0) {
-    if (n_found) atomicAdd(&s_cnt[0], n_found);
-    if (n_below) atomicAdd(&s_cnt[1], n_below);
-  }
-  __syncthreads();
-  if (spec_on && threadIdx.x < 2 && s_cnt[threadIdx.x])
-    atomicAdd(&spec_cur[kSpecHist + 2 * (blockIdx.x & (kSpecCntCopies - 1)) + threadIdx.x], s_cnt[threadIdx.x]);
-#ifdef O3S_TEST_HOOKS
-  if (CERT && settled_cnt && threadIdx.x < 2 && s_set[threadIdx.x] && hdr_i(hv, H_ITER) < kSpecTrace)
-    atomicAdd(&settled_cnt[((blockIdx.x & (kHistReplicas - 1)) * 2 + threadIdx.x) * kSpecTrace + hdr_i(hv, H_ITER)], s_set[threadIdx.x]);
-#endif
-  if (mybin >= 0) atomicAdd(&hist_rep[(size_t)(blockIdx.x & (unsigned)rep_mask) * kHistBins + mybin], s_hist[mybin]);
-  if (STATS) {
-    n_cand = wave_sum_u64(n_cand);
-    n_rows = wave_sum_u64(n_rows);
-    if ((threadIdx.x & 63) == 0) {
-      atomicAdd(&st->cand_count, n_cand);
-      atomicAdd(&st->row_count, n_rows);
-    }
-  }
+  cnt.tally(counted, b.d);
 }
 
 // MirrorMatcher (LPM/MatchersImpl.cpp:58-85): id = i, dist = 0 for every reading point; same outputs as the matcher

@@ -49,9 +49,15 @@ constexpr size_t kHistWords = (size_t)kHistReplicas * kHistBins + 1024;  // leve
 // one word made the hooks build's converged launch 39 us
 constexpr size_t kHookTraceWords = (1 + 2 * (size_t)kHistReplicas) * kSpecTrace;
 
+// Lanes per open query of k_match2's settle front.  Four whatever the reading's size: the open queries' search is what the launch
+// ends on, and four lanes take their candidates in one round (converged k_match2, hooks build, us: C2 without the front 8.58, two
+// lanes 8.13, four 7.50;  C4 24.1, 18.4, 17.0: profiles/r10/NOTES.md)
+constexpr int kFrontLanes = 4;
+
 struct ChainArgs {
   int N;
   int match_g;  // lanes per query of k_match2
+  int front_g;  // lanes per open query of k_match2's settle front (launches 2.. of a chain that keeps certificates); 0: no front
   int nb_match, nb_part, nb_cls;
   int nb_fused;  // blocks of the fused selection + normal-equation kernel (0: the two kernels are launched separately)
   bool has_n;
@@ -633,6 +639,9 @@ ChainArgs chain_args(o3s_icp* h, const ChainParams& cp) {
     const char* nc = O3S_HOOK_ENV("O3S_NO_CERT");  // read per call: the tests run both in one process
     const bool on = !cp.mirror && !h->shard.active && !(nc && std::atoi(nc) != 0) && !O3S_CP_DBG(cp, ~0);
     a.cert = on ? h->d_cert.as<float>() : nullptr;
+    // the settle front of launches 2.. (O3S_NO_SETTLE_FRONT=1: the kernel of launch 1 everywhere)
+    const char* nf = O3S_HOOK_ENV("O3S_NO_SETTLE_FRONT");  // read per call: the tests run both in one process
+    a.front_g = (on && !(nf && std::atoi(nf) != 0)) ? kFrontLanes : 0;
   }
   float* r = h->d_r.as<float>();
   a.rx = r;
@@ -678,19 +687,26 @@ inline RefIndex chain_index(o3s_icp* h, const ChainParams& cp, int it) {
     return RefIndex{h->d_ref1.as<float4>(), h->ref_has_normals ? h->d_refn1.as<float4>() : h->d_refn.as<float4>(), h->d_cell_start1.as<uint32_t>(), h->grid1};
   return main_index(h);
 }
-template <bool STATS, int G, bool CERT>
+// the entry point of k_match2 for a launch: the overload with the seventh template argument is the settle front
+template <bool STATS, int G, int UN, int RCB, bool FAR, bool CERT, bool FRONT>
+constexpr auto match2_kernel() {
+  if constexpr (FRONT) return &kern::k_match2<STATS, G, UN, RCB, FAR, CERT, true>;
+  else return &kern::k_match2<STATS, G, UN, RCB, FAR, CERT>;
+}
+// FRONT: the settle front (kernels: k_match2) — one lane per query up to the settle decision, G lanes per open query behind it
+template <bool STATS, int G, bool CERT, bool FRONT = false>
 void launch_match2(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, const RefIndex& ix, uint32_t* spec, float* cert, hipStream_t s) {
 #ifdef O3S_TEST_HOOKS
   uint32_t* const settled = CERT ? h->d_hist.as<uint32_t>() + kHistWords + kSpecWords + kSpecTrace : nullptr;
 #endif
-  const int nb = round_up8(nblocks(a.N, kern::kBlock / G));  // one tile of kBlock / G queries per block
+  const int nb = round_up8(nblocks(a.N, kern::kBlock / (FRONT ? 1 : G)));  // one tile of kBlock / G queries per block (FRONT: kBlock)
   if (h->far_rows)
-    hipLaunchKernelGGL((kern::k_match2<STATS, G, 2, 4, true, CERT>), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, ix.ref, ix.cell_start, ix.g,
+    hipLaunchKernelGGL((match2_kernel<STATS, G, 2, 4, true, CERT, FRONT>()), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, ix.ref, ix.cell_start, ix.g,
                        h->d_state.as<IcpState>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_mq.as<float4>(), chain_hist(h), ix.refn,
                        normals_from_matcher(a) ? h->d_mn.as<float4>() : (float4*)nullptr, a.has_n ? a.rnx : (const float*)nullptr, a.rny, a.rnz,
                        chain_replicas(h) - 1, spec, CERT ? cert : (float*)nullptr O3S_DBG_ARG(cp.dbg) O3S_DBG_ARG(settled));
   else
-    hipLaunchKernelGGL((kern::k_match2<STATS, G, 2, 2, false, CERT>), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, ix.ref, ix.cell_start, ix.g,
+    hipLaunchKernelGGL((match2_kernel<STATS, G, 2, 2, false, CERT, FRONT>()), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, ix.ref, ix.cell_start, ix.g,
                        h->d_state.as<IcpState>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_mq.as<float4>(), chain_hist(h), ix.refn,
                        normals_from_matcher(a) ? h->d_mn.as<float4>() : (float4*)nullptr, a.has_n ? a.rnx : (const float*)nullptr, a.rny, a.rnz,
                        chain_replicas(h) - 1, spec, CERT ? cert : (float*)nullptr O3S_DBG_ARG(cp.dbg) O3S_DBG_ARG(settled));
@@ -703,16 +719,18 @@ inline int match_lanes(const o3s_icp* h, const ChainArgs& a, bool first) {
   return (first && h->far_rows && a.N < 200000) ? 4 : a.match_g;
 }
 void launch_match2_any(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, bool stats, bool first, const RefIndex& ix, uint32_t* spec, float* cert,
-                       hipStream_t s) {
+                       hipStream_t s, int front_g = 0 /*lanes per open query of the settle front; 0: the launch has none*/) {
   if (cp.mirror) {
     hipLaunchKernelGGL(kern::k_match_mirror, dim3(nblocks(a.N)), dim3(kern::kBlock), 0, s, a.N, h->d_ref.as<float4>(), h->d_orig_to_sorted.as<int32_t>(),
                        h->d_perm.as<int32_t>(), h->d_state.as<IcpState>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_mq.as<float4>(),
                        chain_hist(h));
     return;
   }
+  const bool front = cert != nullptr && front_g != 0;
   const int G = match_lanes(h, a, first);
   auto go = [&](auto st_, auto g_) {
-    if (cert) launch_match2<decltype(st_)::value, decltype(g_)::value, true>(h, a, cp, ix, spec, cert, s);
+    if (front) launch_match2<decltype(st_)::value, kFrontLanes, true, true>(h, a, cp, ix, spec, cert, s);
+    else if (cert) launch_match2<decltype(st_)::value, decltype(g_)::value, true>(h, a, cp, ix, spec, cert, s);
     else launch_match2<decltype(st_)::value, decltype(g_)::value, false>(h, a, cp, ix, spec, cert, s);
   };
   using std::integral_constant;
@@ -733,7 +751,9 @@ void launch_match_chain(o3s_icp* h, const ChainArgs& a, bool stats, hipStream_t 
   // 6 us at C2), the pose still moves by millimetres behind it, and on the first-iteration index its slots are in THAT index's
   // order, which nothing may carry on.  They stay 0, as k_read_prep left them: iteration 1 searches every query and leaves them.
   float* const cert = it == 0 ? nullptr : a.cert;
-  launch_match2_any(h, a, a.cp, stats, it == 0, ix, a.spec, cert, s);
+  // from the third launch of an issued chain or replayed chunk on, most queries settle: the settle front.
+  // Launch 1 meets certificates that are all zero or stale and searches every query: it keeps the lanes it has.
+  launch_match2_any(h, a, a.cp, stats, it == 0, ix, a.spec, cert, s, it >= 2 ? a.front_g : 0);
 }
 
 // large readings (more classify blocks than the finishing block has threads): the candidate sweep of the two-kernel chain runs on many
@@ -1282,10 +1302,10 @@ void print_chain(o3s_icp* h) {
   std::string looks;
   for (int n : h->looks) looks += (looks.empty() ? "" : ",") + std::to_string(n);
   std::fprintf(stderr,
-               "o3s chain: N %d matcher %s far %s it0_index %s match_g %d first_g %d normals_from_matcher %d nb_fused %d partial %d spec %d "
-               "has_n %d issued %s looks %s\n",
+               "o3s chain: N %d matcher %s far %s it0_index %s match_g %d first_g %d front_g %d normals_from_matcher %d nb_fused %d partial %d "
+               "spec %d has_n %d issued %s looks %s\n",
                a.N, cp.mirror ? "mirror" : "kdtree", h->far_rows ? "rows" : "ring", first_index_used(h, cp) ? "first" : "main",
-               cp.mirror ? 0 : a.match_g, cp.mirror ? 0 : match_lanes(h, a, true), normals_from_matcher(a) ? 1 : 0, a.nb_fused,
+               cp.mirror ? 0 : a.match_g, cp.mirror ? 0 : match_lanes(h, a, true), a.cert ? a.front_g : 0, normals_from_matcher(a) ? 1 : 0, a.nb_fused,
                (!h->shard.active && a.nb_fused == 0 && sel_partial(a)) ? 1 : 0, a.spec ? 1 : 0, a.has_n ? 1 : 0,
                h->profiling ? "profiled" : issued[h->issue_mode], looks.c_str());
 }
