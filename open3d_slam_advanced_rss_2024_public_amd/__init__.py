@@ -8,7 +8,9 @@ from .odometry import ConstantVelocityMotionCompensation, LidarOdometry, RawScan
 from .pose_graph import Constraint, OptimizationProblem, loop_closure_step, update_submaps_and_trajectory  # noqa: F401
 from .constraint_builders import build_odometry_constraint, compute_odometry_constraints  # noqa: F401
 from .place_recognition import PlaceRecognition, PlaceRecognitionParameters  # noqa: F401
+from .pose_search import PoseSearchParams, PoseSearchResult, LocalizeResult, localize  # noqa: F401
+from . import pose_search  # noqa: F401  (pose_search.search / pose_search.pose)
 
 __all__ = ["ICP", "IcpConfig", "IcpStats", "ConvergenceError", "TransformationError", "InvalidModuleType", "HipError", "compute_batch", "Submap", "AssembledMap", "ProcessedScan", "SubmapCollection", "DenseMap", "LidarOdometry",
            "ConstantVelocityMotionCompensation", "TransformBuffer", "RawScan", "Constraint", "OptimizationProblem", "update_submaps_and_trajectory", "loop_closure_step", "build_odometry_constraint", "compute_odometry_constraints",
-           "PlaceRecognition", "PlaceRecognitionParameters"]
+           "PlaceRecognition", "PlaceRecognitionParameters", "PoseSearchParams", "PoseSearchResult", "LocalizeResult", "localize", "pose_search"]

@@ -93,6 +93,38 @@ class IcpFitnessC(C.Structure):   # o3s_icp_fitness
     ]
 
 
+class PoseSearchParamsC(C.Structure):   # o3s_pose_search_params (include/pose_search/o3s_pose_search.h)
+    _fields_ = [
+        ("center", C.c_double * 16),
+        ("step_xy", C.c_double),
+        ("step_z", C.c_double),
+        ("step_yaw", C.c_double),
+        ("yaw0", C.c_double),
+        ("n_x", C.c_int32),
+        ("n_y", C.c_int32),
+        ("n_z", C.c_int32),
+        ("n_yaw", C.c_int32),
+        ("yaw_ring", C.c_int32),
+        ("point_stride", C.c_int32),
+        ("local_maxima", C.c_int32),
+        ("top_k", C.c_int32),
+        ("min_score", C.c_int64),
+    ]
+
+
+class PoseSearchResultC(C.Structure):   # o3s_pose_search_result
+    _fields_ = [
+        ("n_poses", C.c_int64),
+        ("n_found", C.c_int32),
+        ("reserved", C.c_int32),
+        ("index", C.c_int64 * 64),
+        ("score", C.c_int64 * 64),
+        ("n_points_counted", C.c_int64),
+        ("gpu_ms", C.c_float),
+        ("reserved2", C.c_int32),
+    ]
+
+
 # o3s_allreduce_fn(user, dev_ptr, byte_offset, count, dtype, hip_stream) -> 0 on success
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p)
 XCHG_INT32, XCHG_FLOAT64 = 0, 1
@@ -106,6 +138,7 @@ def build(force: bool = False) -> str:
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "localizability", "o3s_localizability.h"))
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "degeneracy", "o3s_degeneracy.h"))
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "degeneracy", "o3s_degeneracy_partial.h"))
+    srcs.append(os.path.join(os.path.dirname(_HERE), "include", "pose_search", "o3s_pose_search.h"))
     stale = (not os.path.exists(LIB_PATH)) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s"] + (["-B"] if force else []))
@@ -246,6 +279,14 @@ def load(variant: str | None = None) -> C.CDLL:
     L.o3s_icp_get_last_step.argtypes = [vp, fp]
     L.o3s_icp_covariance_gpu_us.argtypes = [vp, dp]
     L.o3s_icp_evaluate_resident.argtypes = [vp, fp, C.c_float, C.POINTER(IcpFitnessC)]
+    pp, rp = C.POINTER(PoseSearchParamsC), C.POINTER(PoseSearchResultC)
+    L.o3s_pose_search_default_params.argtypes = [pp]
+    L.o3s_pose_search_default_params.restype = None
+    L.o3s_pose_search_count.argtypes = [pp]
+    L.o3s_pose_search_count.restype = C.c_int64
+    L.o3s_pose_search_pose.argtypes = [pp, C.c_int64, dp]
+    L.o3s_submap_pose_search.argtypes = [vp, dp, C.c_int64, pp, rp, C.POINTER(C.c_uint32)]
+    L.o3s_submap_pose_search_scan.argtypes = [vp, vp, C.c_int, pp, rp, C.POINTER(C.c_uint32)]
     if hasattr(L, "o3s_icp_hook_settled"):  # the hooks build: what its tests read back
         L.o3s_icp_hook_settled.argtypes = [vp, ip, ip, C.c_int32]
         L.o3s_icp_hook_sel_depth.argtypes = [vp, ip, C.c_int32]

@@ -50,6 +50,7 @@
 #include "o3s_icp.hpp"
 #include "o3s_odometry.hpp"
 #include "o3s_pose.hpp"
+#include "o3s_pose_search.hpp"
 #include "o3s_scan.h"
 #include "o3s_submap_collection.hpp"
 
@@ -147,6 +148,22 @@ class MapperHip {
     isNewValueSetMapper_ = true;
   }
   void setMapToRangeSensor(const Mat4& T) { mapToRangeSensor_ = T; }  // first-scan pose (no flag: Mapper.cpp:179-195)
+  // The start pose of the localisation mode, FOUND instead of dragged (SlamMapInitializer's interactive marker): the sweep is
+  // pre-processed as addRangeMeasurement would, o3s::localize searches `search`'s grid in the active submap's occupancy snapshot —
+  // which the caller has built: activeSubmap().buildVoxelMap — and refines the winners, and an accepted pose goes through
+  // setMapToRangeSensorInitial.  Valid only with isUseInitialMap, once the map is in and before the first measurement: otherwise,
+  // and when no candidate reaches minFitness, nothing of the mapper's state changes and the answer is false.  Never called
+  // implicitly: a mapper that does not call it launches and allocates what it always did.
+  bool localizeInitialPose(const double* rawPts, const double* rawNormals, std::int64_t N, const o3s_pose_search_params& search, double minFitness) {
+    if (!params_.isUseInitialMap || submaps_.activeSubmap().empty() || haveLast_ || !mapToRangeSensorBuffer_.empty()) return false;
+    scan_ = submaps_.scanForNextMeasurement();
+    preprocess(Raw{rawPts, rawNormals, N, nullptr, nullptr}, 0.0);
+    lastLocalize_ = localize(submaps_.activeSubmap(), scan_, icp_, params_.scanMatcherCropper, search, minFitness, params_.fitnessMaxCorrespondenceDistance);
+    if (!lastLocalize_.ok) return false;
+    setMapToRangeSensorInitial(lastLocalize_.T);
+    return true;
+  }
+  const LocalizeResult& lastLocalize() const { return lastLocalize_; }  // of the last localizeInitialPose that searched
   // Mapper::loopClosureUpdate (Mapper.cpp:93-96)
   void loopClosureUpdate(const Mat4& loopClosureCorrection) {
     mapToRangeSensor_ = mul(loopClosureCorrection, mapToRangeSensor_);
@@ -513,6 +530,7 @@ class MapperHip {
   bool isNewValueSetMapper_ = false, isIgnoreOdometryPrediction_ = false;
   bool lastInserted_ = false, lastReferenceReset_ = false, lastIcpThrew_ = false, lastFitnessRejected_ = false;
   o3s_icp_fitness lastFitness_{};
+  LocalizeResult lastLocalize_;
   o3s_localizability lastLocalizability_{};
   int lastRemapReplaced_ = 0;
   std::array<double, 36> lastCovariance_ = nanCovariance();

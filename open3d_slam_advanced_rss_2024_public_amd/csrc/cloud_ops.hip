@@ -302,6 +302,7 @@ int o3s_undistort_cloud_trajectory(int device, const o3s_stamped_pose* poses, in
 #include "place_impl.h"
 #include "dense_map_impl.h"
 #include "overlap_impl.h"
+#include "pose_search_impl.h"  // (includes pose_search_dev.h, the kernels)
 #include "constraints_impl.h"
 
 #ifdef O3S_TEST_HOOKS

@@ -57,6 +57,7 @@ class Mapper:
         self.calib_inv = np.eye(4)          # calibration_.inverse(); identity until set, as in the reference (Mapper.hpp) and MapperHip
         self.is_calibration_set = False     # isCalibrationSet_ (Mapper.cpp:66-85): until it is, every scan is refused (:169-174)
         self.use_initial_map = False
+        self.last_localize = None           # pose_search.LocalizeResult of the last localize_initial_pose that searched
         # mapToRangeSensorBuffer_ (Mapper.cpp:190, 228, 450, 460): the registered poses; motionCompensationMap_ works over it
         # (SlamWrapper.cpp:445-447, 671).  Off by default: the sweep then reaches the pre-processing as it came.
         from .odometry import TransformBuffer
@@ -143,6 +144,31 @@ class Mapper:
         b = TransformInterpolationBuffer(self.pose_buffer.size_limit)
         b._t, b._T = self.pose_buffer._t, self.pose_buffer._T
         return b
+
+    def setMapToRangeSensorInitial(self, T):
+        """Mapper::setMapToRangeSensorInitial (Mapper.cpp:96-118): the next scan adopts T."""
+        self.T = np.array(T, np.float64).reshape(4, 4)
+        self.T_prev = self.T.copy()
+        self.new_value = True
+
+    def localize_initial_pose(self, points, normals, params, min_fitness):
+        """The start pose of the localisation mode, found instead of dragged (SlamMapInitializer's interactive marker): the sweep
+        is pre-processed as add() would, pose_search.localize searches params' grid in the active submap's occupancy snapshot
+        (the caller has built it: Submap.buildVoxelMap) and refines the winners, and an accepted pose goes through
+        setMapToRangeSensorInitial.  Valid only with use_initial_map, once the map is in the active submap (Submap.setMapPointCloud:
+        the initial map goes straight into it, as in cpp/o3s_mapper.hpp) and before the first measurement — no pose has been
+        registered yet: otherwise, and when no candidate reaches min_fitness, nothing changes and the answer is False.  Never
+        called implicitly; last_localize keeps the LocalizeResult of the last call that searched."""
+        from .pose_search import localize
+        if not self.use_initial_map or len(self.sm) == 0 or self.last_stamp is not None or not self.pose_buffer.empty():
+            return False
+        self.ps = self.col.scan_for_next()
+        self.preprocess(points, normals)
+        self.last_localize = localize(self.sm, self.ps, self.icp, self.narrow, params, min_fitness, self.fitness_max_correspondence_distance)
+        if not self.last_localize.ok:
+            return False
+        self.setMapToRangeSensorInitial(self.last_localize.T)
+        return True
 
     def loopClosureUpdate(self, loopClosureCorrection):
         """Mapper::loopClosureUpdate (Mapper.cpp:92-95).  The ICP reference is NOT renewed: until the next renewal the matcher still
