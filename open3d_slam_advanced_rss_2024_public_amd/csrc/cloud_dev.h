@@ -11,6 +11,7 @@
 #include "host_post.h"
 #include "dev_mem.h"
 #include "lease_pool.h"
+#include "wave_ops.h"
 
 #include <string.h>
 
@@ -38,6 +39,7 @@ using o3s::lay_out_in;
 using o3s::layout_bytes;
 namespace o3s_cloud {
 using namespace o3s::host_post;
+using namespace o3s::devfn;  // wave_ops.h, and voxel_table.h where a module includes it
 
 
 constexpr int kB = 256;
@@ -47,33 +49,36 @@ inline unsigned nblk(int64_t n) { return (unsigned)((n + kB - 1) / kB); }
 // together with the wave reduction and the look-before-atomic below this keeps same-address atomics off the critical path.
 constexpr int kExtSlots = 64;
 
-// Wave-wide min / max before touching a global extremum: one atomic per wave instead of one per point (same-address
-// atomics serialise at ~11 ns each — per-point atomics made the bound kernels the largest item of the mapping loop).
-__device__ __forceinline__ int32_t wave_min_i32(int32_t v) {
+// A 4x4 pose (column-major) as a kernel argument: no 128-byte host-to-device copy in front of the launch
+struct Pose4d {
+  double m[16];
+};
+// Open3D PointCloud::Transform (TransformPoints) / o3d_slam::transform (helpers.cpp:283-318) of one point, in place:
+// p' = (T [p 1]).head<3>() / w; the 4-term products are accumulated k = 0..3 in fp64 without contraction
+__device__ __forceinline__ void o3d_transform_point(const double* T, double& x, double& y, double& z) {
+  double v[4];
 #pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v = min(v, __shfl_xor(v, m, 64));
-  return v;
-}
-__device__ __forceinline__ int32_t wave_max_i32(int32_t v) {
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v = max(v, __shfl_xor(v, m, 64));
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) {
-    const unsigned long long o = __shfl_xor(v, m, 64);
-    v = o < v ? o : v;
+  for (int r = 0; r < 4; ++r) {
+    double s = T[r] * x;
+    s = s + T[4 + r] * y;
+    s = s + T[8 + r] * z;
+    s = s + T[12 + r] * 1.0;
+    v[r] = s;
   }
-  return v;
+  x = v[0] / v[3];
+  y = v[1] / v[3];
+  z = v[2] / v[3];
 }
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+// ... of one direction (a normal): n' = (T [n 0]).head<3>().  The last term stays: it is NaN for a T that is not finite
+__device__ __forceinline__ void o3d_transform_dir(const double* T, double a, double b, double c, double out[3]) {
 #pragma unroll
-  for (int m = 32; m > 0; m >>= 1) {
-    const unsigned long long o = __shfl_xor(v, m, 64);
-    v = o > v ? o : v;
+  for (int r = 0; r < 3; ++r) {
+    double s = T[r] * a;
+    s = s + T[4 + r] * b;
+    s = s + T[8 + r] * c;
+    s = s + T[12 + r] * 0.0;
+    out[r] = s;
   }
-  return v;
 }
 
 #define CK(expr)                               \
@@ -961,7 +966,7 @@ __global__ void __launch_bounds__(kB) k_scan_flags_blk(const uint32_t* __restric
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   uint32_t acc = 0u;
   for (int k = threadIdx.x; k < (int)blockIdx.x; k += kB) acc += blk_cnt[k];
-  for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
+  acc = wave_sum_u32(acc);
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
   const uint32_t f = i < n ? (flag[i] != 0u ? 1u : 0u) : 0u;
   const unsigned long long m = __ballot(f != 0u);

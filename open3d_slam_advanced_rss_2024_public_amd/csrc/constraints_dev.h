@@ -1,7 +1,7 @@
 // constraints_dev.h — kernels of o3s_submaps_odometry_constraints (include/constraints/o3s_constraints.h): the overlap selection and
 // Open3D's information matrix for MANY pairs of resident submaps in one sequence of launches; gfx950 only.  Included from
-// constraints_impl.h at the end of cloud_ops.hip (one TU: OvSlot / ov_hash / vm_key of overlap_impl.h, o3d_apply and
-// wave_sum_f64 of o3d_icp_impl.h, the sort of cloud_dev.h).
+// constraints_impl.h at the end of cloud_ops.hip (one TU: the key and the OvSlot table of voxel_table.h, wave_sum of wave_ops.h,
+// o3d_transform_point and the sort of cloud_dev.h; nothing of overlap_impl.h).
 //
 // Every launch covers all pairs.  A pair table on the device (OcPair) says which blocks belong to which pair: a block never straddles
 // two clouds, so the wave-wide step of the selection and the per-block partial sums see one pair only, and a pair's
@@ -23,7 +23,8 @@
 // in 64 bits; the cells probed for a point are those of [x - r', x + r'] per axis with r' a hair above max_dist, so a neighbour whose
 // quotient rounds across a cell border is still met (three cells per axis, four when the interval straddles one more border).
 #pragma once
-#include "overlap_impl.h"
+#include "cloud_dev.h"
+#include "voxel_table.h"
 
 namespace {
 namespace o3s_cloud {
@@ -57,14 +58,6 @@ __device__ __forceinline__ int oc_find(const OcPair* __restrict__ pairs, int m, 
   return lo;
 }
 
-__device__ __forceinline__ uint64_t oc_mix(uint64_t k) {  // splitmix64 finaliser
-  k ^= k >> 30;
-  k *= 0xbf58476d1ce4e5b9ull;
-  k ^= k >> 27;
-  k *= 0x94d049bb133111ebull;
-  k ^= k >> 31;
-  return k;
-}
 // cell number along one axis; clamped where a 64-bit integer ends (coordinates are bounded by the selection's voxel range and
 // max_dist >= voxel 2^-20, so the clamp is never reached: it keeps the conversion defined)
 __device__ __forceinline__ long long oc_cell(double x, double h) {
@@ -77,22 +70,6 @@ __device__ __forceinline__ void oc_cell_range(double x, double h, long long* lo,
   const double r = h * (1.0 + 0x1p-20) + fabs(x) * 0x1p-50;
   *lo = oc_cell(x - r, h);
   *hi = oc_cell(x + r, h);
-}
-
-// key's entry in the table, made if need be, with `add` more points of `layer`; 0xffffffff (and *full = 1) when the table is full
-__device__ __forceinline__ uint32_t oc_count_key(uint64_t key, OvSlot* __restrict__ tab, uint32_t mask, int layer, uint32_t add, uint32_t* __restrict__ full) {
-  const unsigned long long k1 = key + 1ull;
-  uint32_t h = ov_hash(k1) & mask;
-  for (uint32_t probe = 0; probe <= mask; ++probe) {
-    const unsigned long long prev = atomicCAS(&tab[h].key1, 0ull, k1);
-    if (prev == 0ull || prev == k1) {
-      atomicAdd(&tab[h].n[layer], add);
-      return h;
-    }
-    h = (h + 1u) & mask;
-  }
-  *full = 1u;
-  return 0xffffffffu;
 }
 
 // err[k] = 1: pair k has a coordinate that is not finite or a voxel index beyond +-2^20; err[m] = 1: a pair's table slice is full.
@@ -112,7 +89,7 @@ __global__ void __launch_bounds__(kB) k_oc_count(const OcPair* __restrict__ pair
   if (i < N) {
     const double* __restrict__ pts = layer ? P.tp : P.sp;
     double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    if (!layer && P.has_T) o3d_apply(P.T, x, y, z);
+    if (!layer && P.has_T) o3d_transform_point(P.T, x, y, z);
     key = vm_key(x, y, z, inv);
     if (key == kDmEmpty) err[k] = 1u;
   }
@@ -122,14 +99,14 @@ __global__ void __launch_bounds__(kB) k_oc_count(const OcPair* __restrict__ pair
   const unsigned long long open = __ballot(pending);
   if (open) {  // (uniform)
     const int leader = __ffsll((long long)open) - 1;
-    const uint64_t lk = ((uint64_t)(uint32_t)__shfl((int)(key >> 32), leader) << 32) | (uint64_t)(uint32_t)__shfl((int)(key & 0xffffffffu), leader);
+    const uint64_t lk = wave_bcast_u64(key, leader);
     const bool same = pending && key == lk;
     const unsigned long long grp = __ballot(same);
     uint32_t h = 0xffffffffu;
-    if (lane == leader) h = oc_count_key(lk, slice, P.tab_mask, layer, (uint32_t)__popcll(grp), err + m);
+    if (lane == leader) h = ov_count_key(lk, slice, P.tab_mask, layer, (uint32_t)__popcll(grp), err + m);
     h = (uint32_t)__shfl((int)h, leader);
     if (same) my_slot = h;
-    else if (pending) my_slot = oc_count_key(key, slice, P.tab_mask, layer, 1u, err + m);
+    else if (pending) my_slot = ov_count_key(key, slice, P.tab_mask, layer, 1u, err + m);
   }
   if (i < N) slot_of[(size_t)(layer ? P.g_t : P.g_s) + (size_t)i] = my_slot;
 }
@@ -159,7 +136,7 @@ __global__ void __launch_bounds__(kB) k_oc_flag(const OcPair* __restrict__ pairs
       if (in) {
         const double* __restrict__ tp = P.tp;
         const long long cx = oc_cell(tp[3 * i], cell), cy = oc_cell(tp[3 * i + 1], cell), cz = oc_cell(tp[3 * i + 2], cell);
-        b = oc_mix((uint64_t)cx + oc_mix((uint64_t)cy + oc_mix((uint64_t)cz + (uint64_t)k))) & (uint64_t)(n_buckets - 1u);
+        b = splitmix64((uint64_t)cx + splitmix64((uint64_t)cy + splitmix64((uint64_t)cz + (uint64_t)k))) & (uint64_t)(n_buckets - 1u);
       }
       bkey[(size_t)P.t_base + (size_t)i] = b;
       bval[(size_t)P.t_base + (size_t)i] = P.t_base + (uint32_t)i;
@@ -210,7 +187,7 @@ __global__ void __launch_bounds__(kB) k_oc_search(const OcPair* __restrict__ pai
   for (int c = 0; c < kOcComps; ++c) acc[c] = 0.0;
   if (i < P.ns && flag[(size_t)P.g_s + (size_t)i]) {
     double qx = P.sp[3 * i], qy = P.sp[3 * i + 1], qz = P.sp[3 * i + 2];
-    if (P.apply_search) o3d_apply(P.T, qx, qy, qz);
+    if (P.apply_search) o3d_transform_point(P.T, qx, qy, qz);
     long long x0, x1, y0, y1, z0, z1;
     oc_cell_range(qx, cell, &x0, &x1);
     oc_cell_range(qy, cell, &y0, &y1);
@@ -218,11 +195,11 @@ __global__ void __launch_bounds__(kB) k_oc_search(const OcPair* __restrict__ pai
     double best = __builtin_huge_val(), tx = 0.0, ty = 0.0, tz = 0.0;
     uint32_t bj = 0xffffffffu;
     for (long long cz = z0; cz <= z1; ++cz) {
-      const uint64_t hz = oc_mix((uint64_t)cz + (uint64_t)k);
+      const uint64_t hz = splitmix64((uint64_t)cz + (uint64_t)k);
       for (long long cy = y0; cy <= y1; ++cy) {
-        const uint64_t hy = oc_mix((uint64_t)cy + hz);
+        const uint64_t hy = splitmix64((uint64_t)cy + hz);
         for (long long cx = x0; cx <= x1; ++cx) {
-          const uint2 rg = range[(uint32_t)oc_mix((uint64_t)cx + hy) & bucket_mask];
+          const uint2 rg = range[(uint32_t)splitmix64((uint64_t)cx + hy) & bucket_mask];
           for (uint32_t a = rg.x; a < rg.y; ++a) {
             const OcRec c = rec[a];
             if (c.pair != (uint32_t)k) continue;
@@ -259,7 +236,7 @@ __global__ void __launch_bounds__(kB) k_oc_search(const OcPair* __restrict__ pai
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
 #pragma unroll
   for (int c = 0; c < kOcComps; ++c) {
-    const double v = wave_sum_f64(acc[c]);
+    const double v = wave_sum(acc[c]);
     if (l == 0) sh[w][c] = v;
   }
   __syncthreads();
@@ -280,8 +257,7 @@ __global__ void __launch_bounds__(64) k_oc_fold(const OcPair* __restrict__ pairs
     const int nb = (int)(((layer ? P.nt : P.ns) + kB - 1) / kB);
     uint32_t s = 0;
     for (int b = l; b < nb; b += 64) s += p[b];
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) s += (uint32_t)__shfl_xor((int)s, w, 64);
+    s = wave_sum_u32(s);
     if (l == 0) cnt[2 * k + layer] = s;
     return;
   }
@@ -289,7 +265,7 @@ __global__ void __launch_bounds__(64) k_oc_fold(const OcPair* __restrict__ pairs
   const int nb = (int)((P.ns + kB - 1) / kB);
   double s = 0;
   for (int b = l; b < nb; b += 64) s += p[b];
-  s = wave_sum_f64(s);
+  s = wave_sum(s);
   if (l == 0) sums[(size_t)k * kOcComps + c] = s;
 }
 

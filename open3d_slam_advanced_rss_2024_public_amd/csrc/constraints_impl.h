@@ -1,5 +1,5 @@
 // constraints_impl.h — host side of o3s_submaps_odometry_constraints (include/constraints/o3s_constraints.h); the kernels are in
-// constraints_dev.h.  Included at the end of cloud_ops.hip after overlap_impl.h.
+// constraints_dev.h.  Included at the end of cloud_ops.hip after o3d_icp_impl.h (its work area lives in RegArea) and submap_impl.h.
 //
 // One call = one sequence of launches over ALL its pairs on one stream and one wait: the pair table goes up, six kernels and a
 // sort run, k_oc_post writes every pair's sums, counts and error word into the work area's pinned block and publishes through the
@@ -11,6 +11,8 @@
 
 #include "../../include/constraints/o3s_constraints.h"
 #include "constraints_dev.h"
+#include "o3d_icp_impl.h"
+#include "submap_impl.h"
 
 namespace {
 namespace o3s_cloud {

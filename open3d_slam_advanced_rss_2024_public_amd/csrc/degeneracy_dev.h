@@ -74,16 +74,6 @@ __device__ __forceinline__ double deg_quotient(double num, double den) {
   const double q = -num / den;
   return fabs(q) < __builtin_huge_val() ? q : 0.0;  // (a NaN fails the comparison)
 }
-// k_loc_post's fold of twelve sums: component c by wave c % 4, lane l adds the partials of blocks l, l + 64, ..., then the wave's tree
-__device__ __forceinline__ void loc_fold12(const double* __restrict__ part, int nbl, double* __restrict__ out /*LDS*/) {
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  for (int c = w; c < kLocSums; c += kBlock / 64) {
-    double s = 0.0;
-    for (int b = l; b < nbl; b += 64) s += part[(size_t)c * nbl + b];
-    s = wave_sum(s);
-    if (l == 0) out[c] = s;
-  }
-}
 
 template <bool kValues>
 __device__ __forceinline__ void constrain_body(double* __restrict__ part /*[27][nb]*/, int nb, const IcpState* __restrict__ st, const DegFixed& fixed,
@@ -98,14 +88,8 @@ __device__ __forceinline__ void constrain_body(double* __restrict__ part /*[27][
   const int t = threadIdx.x;
   const int it = hdr_i(hv, H_ITER);
   const bool analyse = loc_part != nullptr;  // uniform
-  if (analyse) {  // k_loc_post's fold: component c by wave c % 4, lane l adds the partials of blocks l, l + 64, ..., then the wave's tree
-    const int w = t >> 6, l = t & 63;
-    for (int c = w; c < kLocSums; c += kBlock / 64) {
-      double s = 0.0;
-      for (int b = l; b < nbl; b += 64) s += loc_part[(size_t)c * nbl + b];
-      s = wave_sum(s);
-      if (l == 0) L.loc[c] = s;
-    }
+  if (analyse) {  // k_loc_post's fold (loc_fold12, localizability_dev.h)
+    loc_fold12(loc_part, nbl, L.loc);
     if constexpr (kValues) loc_fold12(io.pp_part, nbl, V.pp);
   }
   if (t < 36) L.C[t / 6][t % 6] = 0.0;

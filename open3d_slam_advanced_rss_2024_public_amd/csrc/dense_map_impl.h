@@ -15,17 +15,14 @@
 #include "../../include/dense_map/o3s_dense_map_color.h"
 
 #include "cloud_dev.h"
+#include "voxel_table.h"
 
 namespace {
 
-constexpr uint64_t kDmEmpty = ~0ull, kDmTomb = ~0ull - 1ull;
-constexpr int32_t kDmBias = 1 << 20;
+// the packed key (kDmEmpty, dm_pack, dm_field, dm_in_range, vm_key) is voxel_table.h's; the table here is this map's own
+constexpr uint64_t kDmTomb = ~0ull - 1ull;
 constexpr int kDmMaxOff = 16;  // neighbourhood offsets per axis: radius / voxel <= 7.5
 
-__device__ __forceinline__ uint64_t dm_pack(int32_t x, int32_t y, int32_t z) {
-  return ((uint64_t)(uint32_t)(z + kDmBias) << 42) | ((uint64_t)(uint32_t)(y + kDmBias) << 21) | (uint64_t)(uint32_t)(x + kDmBias);
-}
-__device__ __forceinline__ bool dm_in_range(double f) { return f >= -(double)kDmBias && f < (double)kDmBias; }  // false for NaN
 __device__ __forceinline__ uint64_t dm_hash(uint64_t k) {
   k ^= k >> 33;
   k *= 0xff51afd7ed558ccdull;
@@ -72,14 +69,10 @@ __global__ void __launch_bounds__(kB) k_dm_keys(const double* __restrict__ pts, 
                                                 uint32_t* __restrict__ vals, uint32_t* __restrict__ err) {
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
   if (i >= N) return;
-  const double fx = floor(pts[3 * i] * inv), fy = floor(pts[3 * i + 1] * inv), fz = floor(pts[3 * i + 2] * inv);
+  const uint64_t k = vm_key(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], inv);
   vals[i] = (uint32_t)i;
-  if (dm_in_range(fx) && dm_in_range(fy) && dm_in_range(fz)) {
-    keys[i] = dm_pack((int32_t)fx, (int32_t)fy, (int32_t)fz);
-  } else {
-    keys[i] = kDmEmpty;
-    *err = 1u;
-  }
+  keys[i] = k;
+  if (k == kDmEmpty) *err = 1u;
 }
 
 // VoxelizedPointCloud::insert (Voxel.cpp:66-88) on key-sorted points: one lane per distinct key.
@@ -237,14 +230,14 @@ __global__ void __launch_bounds__(kB) k_dm_emit(const uint64_t* __restrict__ ske
 #pragma unroll
     for (int a = 0; a < 3; ++a) out_col[3 * i + a] = csum[3 * s + a] / d;
   }
-  out_k[3 * i] = (int32_t)(key & 0x1fffffull) - kDmBias;
-  out_k[3 * i + 1] = (int32_t)((key >> 21) & 0x1fffffull) - kDmBias;
-  out_k[3 * i + 2] = (int32_t)((key >> 42) & 0x1fffffull) - kDmBias;
+  out_k[3 * i] = dm_index(key, 0);
+  out_k[3 * i + 1] = dm_index(key, 1);
+  out_k[3 * i + 2] = dm_index(key, 2);
   out_c[i] = c;
 }
 
 // VoxelizedPointCloud::transform (Voxel.cpp:49-64): Isometry3d * Vector3d = translation + linear * v on both sums; the voxel is
-// copied, so its colour sum stays
+// copied, so its colour sum stays.  t + ((T0 x + T1 y) + T2 z), no division: another order than o3d_transform_point's, so it stays
 __global__ void __launch_bounds__(kB) k_dm_transform(const uint64_t* __restrict__ keys, const int32_t* __restrict__ cnt, double* __restrict__ sum,
                                                      int64_t cap, const double* __restrict__ Tm) {
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
@@ -392,11 +385,11 @@ __global__ void __launch_bounds__(kB) k_dm_carve_rays(const double* __restrict__
     if (s >= 0) rm[s] = 1;
   };
   // key part and squared centre offset of one test coordinate
-  auto axis = [&](double tq, int shift, uint64_t& part, double& e2) {
+  auto axis = [&](double tq, int ax, uint64_t& part, double& e2) {
     const double f = floor(tq / voxel);                          // getVoxelIdx(p, voxelSize): the dividing form
     const double e = tq - ((double)(int32_t)f * voxel + half);   // getVoxelCenter = key * voxel + voxel * 0.5
     e2 = e * e;
-    part = dm_in_range(f) ? (uint64_t)(uint32_t)((int32_t)f + kDmBias) << shift : kDmBad;
+    part = dm_in_range(f) ? dm_field((int32_t)f, ax) : kDmBad;
   };
   double distance = 0.0;
   for (int k = 0; k < sub && distance < max_path; ++k) distance += step;  // this lane's first stop
@@ -411,16 +404,16 @@ __global__ void __launch_bounds__(kB) k_dm_carve_rays(const double* __restrict__
       for (int q = 0; q < n; ++q) axis(cx + off.d[q], 0, px[q], ex2[q]);
     }
     for (int q = 0; q < n; ++q) {
-      axis(cy + off.d[q], 21, py[q], ey2[q]);
-      axis(cz + off.d[q], 42, pz[q], ez2[q]);
+      axis(cy + off.d[q], 1, py[q], ey2[q]);
+      axis(cz + off.d[q], 2, pz[q], ez2[q]);
     }
     uint64_t ckey;
     {
       uint64_t a, b, c;
       double unused;
       axis(cx, 0, a, unused);
-      axis(cy, 21, b, unused);
-      axis(cz, 42, c, unused);
+      axis(cy, 1, b, unused);
+      axis(cz, 2, c, unused);
       ckey = a | b | c;
     }
     bool centre_added = false;

@@ -21,11 +21,13 @@
 #include "host_post.h"
 #include "icp_types.h"
 #include "solve_device.h"
+#include "wave_ops.h"
 
 #pragma clang fp contract(off)
 
 namespace o3s {
 namespace kern {
+using namespace o3s::devfn;  // wave_ops.h: wave_sum and its kin
 
 constexpr int kBlock = 256;
 
@@ -34,43 +36,6 @@ constexpr float kInfF = __builtin_huge_valf();
 // ------------------------------------------------------------------------------------------------------------------
 // small device helpers
 // ------------------------------------------------------------------------------------------------------------------
-// Wave-wide sums.  The in-row steps use DPP lane permutes (VALU speed, no LDS crossbar round trip: a ds_bpermute-based
-// __shfl tree of a double costs ~12 dependent LDS operations, which dominated the small kernels); the four 16-lane row
-// sums are then combined through v_readlane.  Every lane returns the total.
-//   quad_perm [1,0,3,2] = 0xB1, quad_perm [2,3,0,1] = 0x4E, row_half_mirror = 0x141, row_mirror = 0x140
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v) {
-  return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false);
-}
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-  const int lo = dpp_i32<CTRL>(__double2loint(v)), hi = dpp_i32<CTRL>(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-__device__ __forceinline__ double wave_sum(double v) {
-  v += dpp_f64<0xB1>(v);   // pairs
-  v += dpp_f64<0x4E>(v);   // quads
-  v += dpp_f64<0x141>(v);  // 8 lanes
-  v += dpp_f64<0x140>(v);  // 16-lane rows
-  return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-  v += (uint32_t)dpp_i32<0xB1>((int)v);
-  v += (uint32_t)dpp_i32<0x4E>((int)v);
-  v += (uint32_t)dpp_i32<0x141>((int)v);
-  v += (uint32_t)dpp_i32<0x140>((int)v);
-  return ((uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16)) +
-         ((uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48));
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 // Blocks are dealt round-robin over the 8 XCDs (b and b+8 share an L2).  Remap so that each XCD walks a contiguous
 // slice of the (spatially sorted) reading: its L2 then sees one compact region of the reference grid.
 __device__ __forceinline__ int xcd_remap(int b, int nblocks) {

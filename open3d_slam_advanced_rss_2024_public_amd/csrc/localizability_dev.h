@@ -208,8 +208,19 @@ __device__ __forceinline__ void loc_eig3(const double* __restrict__ tri, double*
   evec[6] = V.v02, evec[7] = V.v12, evec[8] = V.v22;
 }
 
-// One block: component c is folded by wave c % 4 — lane l adds the partials of blocks l, l + 64, ... in order, then the wave's DPP
-// tree — so the order is a function of the number of blocks alone (k_cov_post).
+// The fold of twelve sums (k_loc_eig, k_loc_post, degeneracy_dev.h): component c is folded by wave c % 4 — lane l adds the partials
+// of blocks l, l + 64, ... in order, then the wave's DPP tree — so the order is a function of the number of blocks alone (k_cov_post).
+__device__ __forceinline__ void loc_fold12(const double* __restrict__ part /*[12][nb]*/, int nb, double* __restrict__ out /*LDS*/) {
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  for (int c = w; c < kLocSums; c += kBlock / 64) {
+    double s = 0.0;
+    for (int b = l; b < nb; b += 64) s += part[(size_t)c * nb + b];
+    s = wave_sum(s);
+    if (l == 0) out[c] = s;
+  }
+}
+
+// One block: loc_fold12, then the two eigen-decompositions.
 __global__ void __launch_bounds__(kBlock) k_loc_eig(const double* __restrict__ part /*[12][nb]*/, int nb, double* __restrict__ dirs /*eval[6], evec[6][3]*/,
                                                     const IcpState* __restrict__ st_live /*non-null: inside an iteration*/) {
   __shared__ double s_sum[kLocSums];
@@ -217,13 +228,7 @@ __global__ void __launch_bounds__(kBlock) k_loc_eig(const double* __restrict__ p
     const float hv = hdr_load(st_live);
     if (hdr_i(hv, H_DONE) || hdr_i(hv, H_STATUS)) return;
   }
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  for (int c = w; c < kLocSums; c += kBlock / 64) {
-    double s = 0.0;
-    for (int b = l; b < nb; b += 64) s += part[(size_t)c * nb + b];
-    s = wave_sum(s);
-    if (l == 0) s_sum[c] = s;
-  }
+  loc_fold12(part, nb, s_sum);
   __syncthreads();
   // the two blocks are independent serial chains of fp64 divisions and square roots: one lane each, in two waves, side by side
   if (threadIdx.x == 0) loc_eig3(s_sum, dirs, dirs + 6);
@@ -374,13 +379,8 @@ __global__ void __launch_bounds__(kBlock) k_loc_post(const double* __restrict__ 
                                                      uint32_t* __restrict__ mailbox, uint32_t seq) {
   __shared__ double s_sum[kLocSums];
   __shared__ unsigned long long s_cnt[kLocCounts];
+  loc_fold12(part, nb, s_sum);
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  for (int c = w; c < kLocSums; c += kBlock / 64) {
-    double s = 0.0;
-    for (int b = l; b < nb; b += 64) s += part[(size_t)c * nb + b];
-    s = wave_sum(s);
-    if (l == 0) s_sum[c] = s;
-  }
   for (int c = w; c < kLocCounts; c += kBlock / 64) {
     unsigned long long s = 0ull;
     for (int b = l; b < nb; b += 64) s += part_cnt[(size_t)c * nb + b];

@@ -18,54 +18,17 @@ namespace o3s_cloud {
 constexpr int kO3dFarBlocks = 2048;  // k_o3d_search_far: 8192 waves stride over the work list
 constexpr int kAccComps = 30;  // [0..20] upper triangle of J^T J (or G^T G), [21..26] J^T r, [27] sum r^2, [28] sum d2, [29] count
 
-// wave-wide fp64 sum through DPP lane permutes + readlane (see csrc/icp_kernels.h wave_sum)
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64c(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double readlane_f64c(double v, int lane) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  v += dpp_f64c<0xB1>(v);
-  v += dpp_f64c<0x4E>(v);
-  v += dpp_f64c<0x141>(v);
-  v += dpp_f64c<0x140>(v);
-  return (readlane_f64c(v, 0) + readlane_f64c(v, 16)) + (readlane_f64c(v, 32) + readlane_f64c(v, 48));
-}
-
-// PointCloud::Transform (TransformPoints) of one point: p = (T [p 1]).head<3>() / w
-struct O3dPose {  // a 4x4 (column-major) as a kernel argument: no 128-byte host-to-device copy in front of the launch
-  double m[16];
-};
-__device__ __forceinline__ void o3d_apply(const double* Tm, double& x, double& y, double& z) {
-  double v[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    double s = Tm[r] * x;
-    s = s + Tm[4 + r] * y;
-    s = s + Tm[8 + r] * z;
-    s = s + Tm[12 + r] * 1.0;
-    v[r] = s;
-  }
-  x = v[0] / v[3];
-  y = v[1] / v[3];
-  z = v[2] / v[3];
-}
-
 // Source points are visited in the order of the TARGET grid's cells (sorted once, under the initial guess): lanes of a
 // wave then walk the same few cells, so the cell ranges and target points they read are shared cache lines instead of
 // one DRAM miss per lane.  The correspondences themselves never leave the device, so their order is free.
 // Keys of the points as the transformation Tm places them (apply = 0: as they are — Open3D skips an identity); the source itself
 // is left where it lies (a resident submap's array) and is only ever read.
-__global__ void __launch_bounds__(kB) k_src_cell_keys(const double* __restrict__ p, int64_t N, O3dPose Tm, int apply, NGrid g,
+__global__ void __launch_bounds__(kB) k_src_cell_keys(const double* __restrict__ p, int64_t N, Pose4d Tm, int apply, NGrid g,
                                                       uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
   if (i >= N) return;
   double px = p[3 * i], py = p[3 * i + 1], pz = p[3 * i + 2];
-  if (apply) o3d_apply(Tm.m, px, py, pz);
+  if (apply) o3d_transform_point(Tm.m, px, py, pz);
   const double big = 1.0e9;
   const double fx = fmin(fmax(floor((px - g.ox) / g.cell), -big), big), fy = fmin(fmax(floor((py - g.oy) / g.cell), -big), big),
                fz = fmin(fmax(floor((pz - g.oz) / g.cell), -big), big);
@@ -76,12 +39,12 @@ __global__ void __launch_bounds__(kB) k_src_cell_keys(const double* __restrict__
 }
 // out[i] = Tm . p[order[i]]: the working copy of the source, placed and in search order, in one pass
 __global__ void __launch_bounds__(kB) k_o3d_place(const double* __restrict__ p, const uint32_t* __restrict__ order, int64_t N,
-                                                  O3dPose Tm, int apply, double* __restrict__ out) {
+                                                  Pose4d Tm, int apply, double* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
   if (i >= N) return;
   const size_t j = order[i];
   double px = p[3 * j], py = p[3 * j + 1], pz = p[3 * j + 2];
-  if (apply) o3d_apply(Tm.m, px, py, pz);
+  if (apply) o3d_transform_point(Tm.m, px, py, pz);
   out[3 * i] = px;
   out[3 * i + 1] = py;
   out[3 * i + 2] = pz;
@@ -379,7 +342,7 @@ __device__ __forceinline__ void o3d_rows_wave(const O3dQuery& q, const GridIndex
       ib[j] = -1;
     }
     for (int ix = 0; ix < side; ++ix) {  // uniform within the group; the gap term along x is the same for every lane of it
-      const double gx = W == 64 ? readlane_f64c(tx, ix) : __shfl(tx, ix, W);
+      const double gx = W == 64 ? readlane_f64(tx, ix) : __shfl(tx, ix, W);
       const int dx = ix - r, x = q.cx + dx;
       const bool xin = (unsigned)x < (unsigned)g.nx, xcore = abs(dx) < r_lo;
 #pragma unroll
@@ -626,7 +589,7 @@ __device__ __forceinline__ uint32_t o3d_block_slot(bool flag, uint32_t* __restri
 
 // counts[0] = points on the search list, counts[1] = points on the far list (both cleared behind the pass by k_o3d_fold)
 constexpr int kKeepThreads = 1024;  // one atomic per block onto the list counter: 0.6 k of them at 0.6 M points instead of 2.3 k
-__global__ void __launch_bounds__(kKeepThreads) k_o3d_keep(double* __restrict__ pcd, int64_t Ns, O3dPose Tm, int apply,
+__global__ void __launch_bounds__(kKeepThreads) k_o3d_keep(double* __restrict__ pcd, int64_t Ns, Pose4d Tm, int apply,
                                                  const double* __restrict__ tgt, double r2, int32_t* __restrict__ corr, O3dCert* __restrict__ cert,
                                                  uint32_t* __restrict__ list, uint32_t* __restrict__ counts O3S_DBG_PARAM) {
   const int64_t i = (int64_t)blockIdx.x * kKeepThreads + threadIdx.x;
@@ -634,7 +597,7 @@ __global__ void __launch_bounds__(kKeepThreads) k_o3d_keep(double* __restrict__ 
   if (i < Ns) {
     double px = pcd[3 * i], py = pcd[3 * i + 1], pz = pcd[3 * i + 2];
     if (apply) {  // PointCloud::Transform(update)
-      o3d_apply(Tm.m, px, py, pz);
+      o3d_transform_point(Tm.m, px, py, pz);
       pcd[3 * i] = px;
       pcd[3 * i + 1] = py;
       pcd[3 * i + 2] = pz;
@@ -937,7 +900,7 @@ __global__ void __launch_bounds__(kB) k_o3d_corr(const double* __restrict__ pcd,
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
 #pragma unroll
   for (int c = 0; c < kAccComps; ++c) {
-    const double v = wave_sum_f64(acc[c]);
+    const double v = wave_sum(acc[c]);
     if (l == 0) sh[w][c] = v;
   }
   __syncthreads();
@@ -966,7 +929,7 @@ __global__ void __launch_bounds__(64) k_o3d_fold(const double* __restrict__ part
     for (int k = 0; k < 8; ++k) s += v[k];
   }
   for (; b < nb; b += 64) s += p[b];
-  s = wave_sum_f64(s);
+  s = wave_sum(s);
   if (!post) {
     if (l == 0) out[c] = s;
     return;
@@ -1343,7 +1306,7 @@ inline int o3d_place_source(O3dIcpWork& w, int64_t Ns, const GridIndex& gi, cons
   O3dSortArea a;
   CK(lay_out(w.sort_arena, a, n, tb));
   const int apply = (T && !h_is_identity(T)) ? 1 : 0;
-  O3dPose Tp{};
+  Pose4d Tp{};
   if (apply) std::memcpy(Tp.m, T, sizeof(Tp.m));
   hipLaunchKernelGGL(k_src_cell_keys, dim3(nblk(Ns)), dim3(kB), 0, s, w.orig, Ns, Tp, apply, gi.g, a.keys, a.vals);
   size_t tbb = tb;
@@ -1380,7 +1343,7 @@ inline int o3d_corr_pass(O3dIcpWork& w, int64_t Ns, const GridIndex& gi, double 
   }
   rc.pad = 0.02 * r;  // closed-loop run, ms per refinement with pads of 0 / 1.5 / 3 / 6 / 10 %: 1.72 / 1.58 / 1.61 / 1.70 / 1.70 (the 8-pass one)
   if (w.corr_valid) {  // every pass but the first: most points keep their neighbour without a search
-    O3dPose Tp{};
+    Pose4d Tp{};
     if (update) std::memcpy(Tp.m, update, sizeof(Tp.m));
     hipLaunchKernelGGL(k_o3d_keep, dim3((unsigned)((Ns + kKeepThreads - 1) / kKeepThreads)), dim3(kKeepThreads), 0, s, w.d_src.as<double>(), Ns, Tp, update ? 1 : 0, w.tgt, r2,
                        w.d_corr.as<int32_t>(), w.d_cert.as<O3dCert>(), w.d_list.as<uint32_t>(), counts O3S_DBG_ARG(kdbg));
@@ -1648,7 +1611,7 @@ int o3d_info_after_icp(O3dIcpWork& w, double max_dist, const double T[16], doubl
   if (!w.pair_ready || !T || !info || !(max_dist > 0.0)) return O3S_ERR_BAD_ARGUMENT;
   const int64_t Ns = w.n_src;
   const int apply = h_is_identity(T) ? 0 : 1;
-  O3dPose Tp{};
+  Pose4d Tp{};
   if (apply) std::memcpy(Tp.m, T, sizeof(Tp.m));
   hipLaunchKernelGGL(k_o3d_place, dim3(nblk(Ns)), dim3(kB), 0, s, w.orig, w.order, Ns, Tp, apply, w.d_src.as<double>());
   CK(hipGetLastError());

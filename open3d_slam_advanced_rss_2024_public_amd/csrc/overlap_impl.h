@@ -1,7 +1,7 @@
 // overlap_impl.h — computeIndicesOfOverlappingPoints (O3S/src/helpers.cpp:319-345) and the loop-closure refinement that
 // uses it (O3S/src/PlaceRecognition.cpp:97-150) on the device; gfx950 only.  Included at the end of cloud_ops.hip after
-// dense_map_impl.h (one TU: it shares the voxel-key packing of the dense map, the rocPRIM sort / scan instantiations and
-// the Open3D-semantics ICP of o3d_icp_impl.h).
+// submap_impl.h (one TU: the voxel key and table of voxel_table.h, the rocPRIM sort / scan instantiations and the
+// Open3D-semantics ICP of o3d_icp_impl.h).
 //
 // The reference fills a VoxelMap (unordered_map voxel key -> per-layer index lists) with the target cloud and with the
 // source cloud moved by sourceToTarget, then walks the map and keeps the indices of every voxel that holds at least
@@ -14,7 +14,9 @@
 // The reference's output order is its hash map's iteration order (unspecified); ascending index order is used here, on the
 // device and in the oracle.
 #pragma once
-#include "dense_map_impl.h"
+#include "o3d_icp_impl.h"
+#include "submap_impl.h"
+#include "voxel_table.h"
 
 namespace {
 namespace o3s_cloud {
@@ -25,40 +27,10 @@ __global__ void __launch_bounds__(kB) k_ov_keys(const double* __restrict__ pts, 
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
   if (i >= N) return;
   double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-  if (Tm) {
-    double v[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      double s = Tm[r] * x;
-      s = s + Tm[4 + r] * y;
-      s = s + Tm[8 + r] * z;
-      s = s + Tm[12 + r] * 1.0;
-      v[r] = s;
-    }
-    x = v[0] / v[3];
-    y = v[1] / v[3];
-    z = v[2] / v[3];
-  }
-  const double fx = floor(x * inv), fy = floor(y * inv), fz = floor(z * inv);
-  if (dm_in_range(fx) && dm_in_range(fy) && dm_in_range(fz)) {
-    keys[i] = dm_pack((int32_t)fx, (int32_t)fy, (int32_t)fz);
-  } else {
-    keys[i] = kDmEmpty;
-    *err = 1u;
-  }
-}
-
-struct __attribute__((aligned(16))) OvSlot {
-  unsigned long long key1;  // packed voxel key + 1; 0 = empty
-  uint32_t n[2];            // points of the source layer, of the target layer
-};
-__device__ __forceinline__ uint32_t ov_hash(uint64_t k) {  // splitmix64 finaliser
-  k ^= k >> 30;
-  k *= 0xbf58476d1ce4e5b9ull;
-  k ^= k >> 27;
-  k *= 0x94d049bb133111ebull;
-  k ^= k >> 31;
-  return (uint32_t)k;
+  if (Tm) o3d_transform_point(Tm, x, y, z);
+  const uint64_t k = vm_key(x, y, z, inv);
+  keys[i] = k;
+  if (k == kDmEmpty) *err = 1u;
 }
 
 // counts the points of `layer` per voxel and notes every point's slot.  keys[i] must hold the voxel key of point i (k_ov_keys);
@@ -74,28 +46,11 @@ __global__ void __launch_bounds__(kB) k_ov_count(const uint64_t* __restrict__ ke
     const unsigned long long open = __ballot(pending);
     if (!open) break;
     const int leader = __ffsll((long long)open) - 1;
-    const uint64_t lk = ((uint64_t)(uint32_t)__shfl((int)(k >> 32), leader) << 32) | (uint64_t)(uint32_t)__shfl((int)(k & 0xffffffffu), leader);
+    const uint64_t lk = wave_bcast_u64(k, leader);
     const bool same = pending && k == lk;
     const unsigned long long grp = __ballot(same);
     uint32_t h = 0xffffffffu;
-    if (lane == leader) {
-      const unsigned long long k1 = lk + 1ull;
-      h = ov_hash(k1) & mask;
-      bool done = false;
-      for (uint32_t probe = 0; probe <= mask; ++probe) {
-        const unsigned long long prev = atomicCAS(&tab[h].key1, 0ull, k1);
-        if (prev == 0ull || prev == k1) {
-          atomicAdd(&tab[h].n[layer], (uint32_t)__popcll(grp));
-          done = true;
-          break;
-        }
-        h = (h + 1u) & mask;
-      }
-      if (!done) {
-        err[1] = 1u;
-        h = 0xffffffffu;
-      }
-    }
+    if (lane == leader) h = ov_count_key(lk, tab, mask, layer, (uint32_t)__popcll(grp), err + 1);
     h = (uint32_t)__shfl((int)h, leader);
     my_slot = same ? h : my_slot;
     pending = pending && !same;
@@ -181,12 +136,6 @@ __global__ void __launch_bounds__(kB) k_ov_indices(const uint32_t* __restrict__ 
   if (i < N && flag[i]) out[off[i]] = i;
 }
 
-constexpr uint32_t kOvFirstSlots = 1u << 16;
-inline uint32_t ov_slots_for(int64_t n_points) {  // room for one voxel per point at half load
-  uint32_t c = 1u << 10;
-  while ((int64_t)c < 2 * n_points && c < (1u << 31)) c <<= 1;
-  return c;
-}
 // work area of the overlap selection of a source of ns and a target of nt points (tb_scan: a scan of max(ns, nt) flags)
 struct OverlapArea {
   static constexpr size_t kSlack = 4096;
@@ -532,15 +481,10 @@ int o3s_o3d_registration_icp_submaps_overlap_batch_ex(int32_t n, const o3s_subma
 
 // ---- occupancy snapshot of a resident submap and the overlap fitness (include/o3s_submap.h) ---------------------------------------
 // Submap::voxelMap_ as the revisit check reads it (Submap.cpp:260-264, SubmapCollection.cpp:392-407): only WHETHER a voxel holds a
-// map point matters, so the snapshot is a key-only open-addressing table (packed key + 1, 0 = empty; dm_pack, ov_hash) that stays in
-// HBM with the submap.  Keys are getVoxelIdx in the reciprocal form, the arithmetic of k_ov_keys.
+// map point matters, so the snapshot is a key-only open-addressing table (voxel_table.h: vm_claim, vm_find) that stays in
+// HBM with the submap.  Keys are vm_key's, the arithmetic of k_ov_keys.
 namespace {
 namespace o3s_cloud {
-
-__device__ __forceinline__ uint64_t vm_key(double x, double y, double z, double inv) {  // kDmEmpty: NaN or beyond the packable range
-  const double fx = floor(x * inv), fy = floor(y * inv), fz = floor(z * inv);
-  return (dm_in_range(fx) && dm_in_range(fy) && dm_in_range(fz)) ? dm_pack((int32_t)fx, (int32_t)fy, (int32_t)fz) : kDmEmpty;
-}
 
 // Inserts the voxel of every point.  The lanes of a wave that share the voxel of its first lane are served by that lane (a map in
 // voxel order: whole waves fall into one voxel and make one compare-and-swap); every other lane inserts its own key, all of them at
@@ -556,18 +500,12 @@ __global__ void __launch_bounds__(kB) k_vm_insert(const double* __restrict__ pts
   const unsigned long long open = __ballot(pending);
   if (!open) return;  // (uniform)
   const int leader = __ffsll((long long)open) - 1;
-  const uint64_t lk = ((uint64_t)(uint32_t)__shfl((int)(k >> 32), leader) << 32) | (uint64_t)(uint32_t)__shfl((int)(k & 0xffffffffu), leader);
+  const uint64_t lk = wave_bcast_u64(k, leader);
   if (lane != leader && k == lk) pending = false;
   if (!pending) return;
-  const unsigned long long k1 = k + 1ull;
-  uint32_t h = ov_hash(k1) & mask;
-  for (uint32_t probe = 0; probe < max_probe; ++probe) {
-    const unsigned long long prev = atomicCAS(&tab[h], 0ull, k1);
-    if (prev == 0ull) atomicAdd(&cnt[0], 1u);  // exactly one lane of the whole launch makes a voxel's entry
-    if (prev == 0ull || prev == k1) return;
-    h = (h + 1u) & mask;
-  }
-  cnt[1] = 1u;
+  const VmClaim c = vm_claim(k, tab, mask, max_probe);
+  if (c == kVmMade) atomicAdd(&cnt[0], 1u);  // exactly one lane of the whole launch makes a voxel's entry
+  if (c == kVmFull) cnt[1] = 1u;
 }
 
 // p' = R p + t as an isometry product — fp64, no FMA (the TU is compiled with -ffp-contract=off), ((R0 x + R1 y) + R2 z) + t — then
@@ -591,16 +529,7 @@ __global__ void __launch_bounds__(kB) k_vm_count(const double* __restrict__ pts,
       q[a] = s + T.t[a];
     }
     const uint64_t k = vm_key(q[0], q[1], q[2], inv);
-    if (k != kDmEmpty) {
-      const unsigned long long k1 = k + 1ull;
-      uint32_t h = ov_hash(k1) & mask;
-      for (uint32_t probe = 0; probe <= mask; ++probe) {  // (the table is never full: an empty slot ends every miss)
-        const unsigned long long v = tab[h];
-        if (v == k1) hit = true;
-        if (v == k1 || v == 0ull) break;
-        h = (h + 1u) & mask;
-      }
-    }
+    hit = k != kDmEmpty && vm_find(k, tab, mask);
   }
   const unsigned long long b = __ballot(hit);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(total, (uint32_t)__popcll(b));

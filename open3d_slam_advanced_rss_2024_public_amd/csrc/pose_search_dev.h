@@ -1,6 +1,7 @@
 // pose_search_dev.h — kernels of the initial pose search (include/pose_search/o3s_pose_search.h); gfx950 only.  Included at the
-// end of cloud_ops.hip behind overlap_impl.h: the voxel key (vm_key's arithmetic, dm_pack), the hash (ov_hash) and the isometry
-// arithmetic of k_vm_count are used as they are, so the score of a pose is the count k_vm_count gives for it, bit for bit.
+// end of cloud_ops.hip.  The voxel key (vm_key's arithmetic, field by field: dm_field) and the hash (ov_hash) are voxel_table.h's
+// and the isometry arithmetic is k_vm_count's (overlap_impl.h, of which nothing is used here), so the score of a pose is the count
+// k_vm_count gives for it, bit for bit.
 //
 // k_ps_score is the hot kernel: P poses x M points lookups into the snapshot table, which is small (77 k voxels: 2 MB) and stays
 // in L2, so the kernel is bound by dependent lookups, not by bandwidth.  Its shape:
@@ -15,7 +16,8 @@
 //     + column).  The four waves, which split the points, are summed through LDS.
 #pragma once
 #include "../../include/pose_search/o3s_pose_search.h"
-#include "overlap_impl.h"
+#include "cloud_dev.h"
+#include "voxel_table.h"
 
 namespace {
 namespace o3s_cloud {
@@ -97,21 +99,21 @@ __global__ void __launch_bounds__(kB) k_ps_score(const double* __restrict__ pts,
     // the key, axis by axis: dm_pack's fields
     const double fz = floor((s[2] + tz) * inv);
     const bool okz = have && dm_in_range(fz);
-    const unsigned long long kz = okz ? (unsigned long long)(uint32_t)((int32_t)fz + kDmBias) << 42 : 0ull;
+    const unsigned long long kz = okz ? dm_field((int32_t)fz, 2) : 0ull;
     unsigned long long kx[kPsTile];
     uint32_t okx = 0;
 #pragma unroll
     for (int u = 0; u < kPsTile; ++u) {
       const double fx = floor((s[0] + tcol[u]) * inv);
       const bool ok = okz && u < cols && dm_in_range(fx);
-      kx[u] = ok ? (unsigned long long)(uint32_t)((int32_t)fx + kDmBias) : 0ull;
+      kx[u] = ok ? dm_field((int32_t)fx, 0) : 0ull;
       okx |= ok ? 1u << u : 0u;
     }
     for (int r = 0; r < rows; ++r) {
       const double trow = g.tc[1] + (double)(j0 + r - g.ny) * g.step_xy;
       const double fy = floor((s[1] + trow) * inv);
       const bool oky = dm_in_range(fy);
-      const unsigned long long kzy = kz | (oky ? (unsigned long long)(uint32_t)((int32_t)fy + kDmBias) << 21 : 0ull);
+      const unsigned long long kzy = kz | (oky ? dm_field((int32_t)fy, 1) : 0ull);
       const uint32_t valid = oky ? okx : 0u;
       unsigned long long k1[kPsTile], v[kPsTile];
       uint32_t h[kPsTile];

@@ -1,5 +1,5 @@
 // pose_search_impl.h — host side and C entry points of the initial pose search (include/pose_search/o3s_pose_search.h).
-// Included at the end of cloud_ops.hip behind overlap_impl.h; the kernels are in pose_search_dev.h.
+// Included at the end of cloud_ops.hip behind submap_impl.h (the snapshot it searches is the submap's); the kernels are in pose_search_dev.h.
 //
 // One call: the yaw rotations (formed here, with libm) go up, k_ps_score writes the P scores, k_ps_peaks marks the eligible poses
 // and counts them per score, k_ps_threshold finds the score at which top_k is reached, the poses above it take a slot each, the
@@ -7,6 +7,7 @@
 // winners.  One small copy brings the result block back; the scores cross the bus only when scores_out is given.
 #pragma once
 #include "pose_search_dev.h"
+#include "submap_impl.h"
 
 #include <cmath>
 

@@ -10,14 +10,24 @@
 
 namespace {
 
-// o3d_slam::transform (helpers.cpp:283-318): p' = (T [p 1]).head<3>() / w, n' = (T [n 0]).head<3>(); the 4-term
-// products are accumulated k = 0..3 in fp64 without contraction
-struct Mat4d {  // a pose as a kernel argument: no 128-byte host-to-device copy in front of the launch
-  double m[16];
-};
+// o3d_slam::transform (helpers.cpp:283-318): p' = (T [p 1]).head<3>() / w, n' = (T [n 0]).head<3>() (o3d_transform_point /
+// o3d_transform_dir, cloud_dev.h)
 __device__ __forceinline__ void transform_append_one(const double* __restrict__ pts, const double* __restrict__ nrm, int64_t i, const double* T,
-                                                     double* __restrict__ out_pts, double* __restrict__ out_n);
-__global__ void __launch_bounds__(kB) k_transform_append_v(const double* __restrict__ pts, const double* __restrict__ nrm, int64_t N, Mat4d Tm,
+                                                     double* __restrict__ out_pts, double* __restrict__ out_n) {
+  double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+  o3d_transform_point(T, x, y, z);
+  out_pts[3 * i] = x;
+  out_pts[3 * i + 1] = y;
+  out_pts[3 * i + 2] = z;
+  if (nrm) {
+    double w[3];
+    o3d_transform_dir(T, nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2], w);
+    out_n[3 * i] = w[0];
+    out_n[3 * i + 1] = w[1];
+    out_n[3 * i + 2] = w[2];
+  }
+}
+__global__ void __launch_bounds__(kB) k_transform_append_v(const double* __restrict__ pts, const double* __restrict__ nrm, int64_t N, Pose4d Tm,
                                                            double* __restrict__ out_pts, double* __restrict__ out_n) {
   const int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
   if (i >= N) return;
@@ -33,33 +43,6 @@ __global__ void __launch_bounds__(kB) k_transform_append(const double* __restric
   for (int k = 0; k < 16; ++k) T[k] = Tm[k];
   transform_append_one(pts, nrm, i, T, out_pts, out_n);
 }
-__device__ __forceinline__ void transform_append_one(const double* __restrict__ pts, const double* __restrict__ nrm, int64_t i, const double* T,
-                                                     double* __restrict__ out_pts, double* __restrict__ out_n) {
-  const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-  double v[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    double s = T[r] * x;
-    s = s + T[4 + r] * y;
-    s = s + T[8 + r] * z;
-    s = s + T[12 + r] * 1.0;
-    v[r] = s;
-  }
-  out_pts[3 * i] = v[0] / v[3];
-  out_pts[3 * i + 1] = v[1] / v[3];
-  out_pts[3 * i + 2] = v[2] / v[3];
-  if (nrm) {
-    const double a = nrm[3 * i], b = nrm[3 * i + 1], c = nrm[3 * i + 2];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      double s = T[r] * a;
-      s = s + T[4 + r] * b;
-      s = s + T[8 + r] * c;
-      s = s + T[12 + r] * 0.0;
-      out_n[3 * i + r] = s;
-    }
-  }
-}
 
 // Open3D PointCloud::Transform on a resident submap, in place (o3s_submap_transform): lanes [0, n_map) take the map cloud, lanes
 // [n_map, n_map + n_feat) the feature cloud.  The arithmetic is transform_append_one's; there is no almost-identity branch here
@@ -67,7 +50,7 @@ __device__ __forceinline__ void transform_append_one(const double* __restrict__ 
 // which is what makes the in-place form safe (undistort_dev.h).  No LDS, no atomics, no scratch
 // (profiles/pose_graph/resource_usage.txt).
 __global__ void __launch_bounds__(kB) k_submap_transform(double* map_p, double* map_n /*nullable*/, int64_t n_map, double* feat_p, double* feat_n,
-                                                         int64_t n_feat, Mat4d Tm) {
+                                                         int64_t n_feat, Pose4d Tm) {
   int64_t i = (int64_t)blockIdx.x * kB + threadIdx.x;
   if (i >= n_map + n_feat) return;
   double* p = map_p;
@@ -77,31 +60,14 @@ __global__ void __launch_bounds__(kB) k_submap_transform(double* map_p, double* 
     p = feat_p;
     q = feat_n;
   }
-  const double* T = Tm.m;
-  const double x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
-  double v[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    double s = T[r] * x;
-    s = s + T[4 + r] * y;
-    s = s + T[8 + r] * z;
-    s = s + T[12 + r] * 1.0;
-    v[r] = s;
-  }
-  p[3 * i] = v[0] / v[3];
-  p[3 * i + 1] = v[1] / v[3];
-  p[3 * i + 2] = v[2] / v[3];
+  double x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
+  o3d_transform_point(Tm.m, x, y, z);
+  p[3 * i] = x;
+  p[3 * i + 1] = y;
+  p[3 * i + 2] = z;
   if (q) {
-    const double a = q[3 * i], b = q[3 * i + 1], c = q[3 * i + 2];
     double w[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      double s = T[r] * a;
-      s = s + T[4 + r] * b;
-      s = s + T[8 + r] * c;
-      s = s + T[12 + r] * 0.0;
-      w[r] = s;
-    }
+    o3d_transform_dir(Tm.m, q[3 * i], q[3 * i + 1], q[3 * i + 2], w);
     q[3 * i] = w[0];
     q[3 * i + 1] = w[1];
     q[3 * i + 2] = w[2];
@@ -236,7 +202,7 @@ __global__ void __launch_bounds__(kB) k_center_part(const double* __restrict__ p
   for (int a = 0; a < 3; ++a) {
     double v = s[a];
 #pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_down(v, m, 64);
+    for (int m = 32; m > 0; m >>= 1) v += __shfl_down(v, m, 64);  // its own tree (halves first): not wave_sum's, so it stays
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][a] = v;
   }
   __syncthreads();
@@ -709,7 +675,7 @@ bool transform_valid(const double* T) {
 int submap_transform_enqueue(o3s_submap* m, const double* T) {
   const int rc = set_dev(m);
   if (rc != O3S_OK) return rc;
-  Mat4d Tv;
+  Pose4d Tv;
   for (int k = 0; k < 16; ++k) Tv.m[k] = T[k];
   const int c = m->cur;  // whichever ping-pong array is current (a closed submap's tight copy)
   const int64_t nf = m->n_feat > 0 ? m->n_feat : 0;
@@ -838,7 +804,7 @@ int insert_dev(o3s_submap* m, const double* d_pts, const double* d_nrm, int64_t 
   const int64_t add = doubled ? 2 * N : N;
   const int64_t n_tmp = m->n + add;
   if (n_tmp > (int64_t)0x7fffffff) return O3S_ERR_BAD_ARGUMENT;
-  Mat4d Tv;
+  Pose4d Tv;
   for (int k = 0; k < 16; ++k) Tv.m[k] = T_map_sensor[k];
   const int c = m->cur;
   CK(m->pts[c].ensure((size_t)n_tmp * 24, (size_t)m->n * 24, s));
