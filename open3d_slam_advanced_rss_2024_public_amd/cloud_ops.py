@@ -143,6 +143,57 @@ def computeFPFHFeature(points, normals, radius: float, knn: int, want_spfh: bool
     return res if len(res) > 1 else out
 
 
+# ---- Open3D's outlier filters (include/outlier_removal/o3s_outlier_removal.h) --------------------------------------------------
+class OutlierParamsC(C.Structure):   # o3s_outlier_params
+    _fields_ = [("kind", C.c_int32), ("nb", C.c_int32), ("value", C.c_double)]
+
+
+OUTLIER_NONE, OUTLIER_RADIUS, OUTLIER_STATISTICAL = 0, 1, 2
+
+
+def outlier_params(kind=OUTLIER_NONE, nb: int = 0, value: float = 0.0) -> OutlierParamsC:
+    """kind: 0 / 'none', 1 / 'radius' (nb = nb_points, value = search radius), 2 / 'statistical' (nb = nb_neighbors, value = std_ratio)"""
+    k = {"none": 0, "radius": 1, "statistical": 2}.get(kind, kind)
+    return OutlierParamsC(int(k), int(nb), float(value))
+
+
+def _remove_outliers(params: OutlierParamsC, points, normals, device):
+    p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    n = None if normals is None else np.ascontiguousarray(normals, np.float64).reshape(-1, 3)
+    if n is not None and n.shape != p.shape:
+        raise ValueError("points and normals differ in shape")
+    N = p.shape[0]
+    op = np.zeros_like(p)
+    on = np.zeros_like(p) if n is not None else None
+    idx = np.zeros(N, np.int64)
+    stat = params.kind == OUTLIER_STATISTICAL
+    avg = np.zeros(N, np.float64) if stat else None
+    st = np.zeros(4, np.float64) if stat else None
+    k = C.c_int64()
+    fn = _L().o3s_remove_outliers
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.POINTER(OutlierParamsC), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double),
+                   C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    _check(fn(device, C.byref(params), _d(p), _d(n), N, _d(op), _d(on), idx.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(k), _d(avg), _d(st)),
+           "o3s_remove_outliers")
+    m = k.value
+    return op[:m].copy(), (None if on is None else on[:m].copy()), idx[:m].copy(), avg, st
+
+
+def remove_radius_outlier(points, nb_points: int, radius: float, normals=None, device: int = 0):
+    """PointCloud::RemoveRadiusOutliers(nb_points, radius) -> (points, normals | None, kept indices): a point stays iff more than
+    nb_points points (itself included) lie at a squared distance < radius^2.  Input order is kept."""
+    op, on, idx, _, _ = _remove_outliers(outlier_params(OUTLIER_RADIUS, nb_points, radius), points, normals, device)
+    return op, on, idx
+
+
+def remove_statistical_outlier(points, nb_neighbors: int, std_ratio: float, normals=None, device: int = 0):
+    """PointCloud::RemoveStatisticalOutliers(nb_neighbors, std_ratio) -> (points, normals | None, kept indices, avg_dist (N,),
+    stats = [mean, std, thr, valid]): a point stays iff the mean distance to its nb_neighbors nearest points (itself included) is
+    positive and below mean + std_ratio * std of those means over the cloud.  Input order is kept."""
+    return _remove_outliers(outlier_params(OUTLIER_STATISTICAL, nb_neighbors, std_ratio), points, normals, device)
+
+
 # ---- the same operators with colours / covariances riding along (include/o3s_cloud_ops.h, *_attr entry points) ----------
 def _attr_call(fn_name, lead_args, points, normals, colors, covariances, want_idx, device):
     p = np.ascontiguousarray(points, np.float64)

@@ -24,6 +24,7 @@
 #include "degeneracy/o3s_degeneracy.h"
 #include "degeneracy/o3s_degeneracy_partial.h"
 #include "localizability/o3s_localizability.h"
+#include "outlier_removal/o3s_outlier_removal.h"
 
 namespace o3s {
 
@@ -168,6 +169,18 @@ class SubmapHip {
     std::int64_t removed = 0;
     if (o3s_submap_carve(m_, &p, rawPoints3xN, N, mapToRangeSensor4x4, &removed) != O3S_OK) throw std::runtime_error("o3s_submap_carve failed");
     return removed;
+  }
+  // Open3D's outlier filters on the sparse map, in place (outlier_removal/o3s_outlier_removal.h); returns the number of removed
+  // points.  stats4 (nullable, statistical): mean, std, thr, valid
+  std::int64_t removeOutliers(const o3s_outlier_params& p, double* stats4 = nullptr) {
+    std::int64_t removed = 0;
+    const int rc = o3s_submap_remove_outliers(m_, &p, &removed, stats4);
+    if (rc != O3S_OK) throw std::runtime_error("o3s_submap_remove_outliers failed (status " + std::to_string(rc) + ")");
+    return removed;
+  }
+  std::int64_t removeRadiusOutliers(std::int32_t nbPoints, double searchRadius) { return removeOutliers(o3s_outlier_params{1, nbPoints, searchRadius}); }
+  std::int64_t removeStatisticalOutliers(std::int32_t nbNeighbors, double stdRatio, double* stats4 = nullptr) {
+    return removeOutliers(o3s_outlier_params{2, nbNeighbors, stdRatio}, stats4);
   }
   std::int64_t size() const { return o3s_submap_size(m_); }
   // the two questions the per-scan loop asks about the size, answered without waiting for an insert whose completion is pending

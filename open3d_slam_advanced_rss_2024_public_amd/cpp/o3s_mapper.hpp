@@ -53,6 +53,7 @@
 #include "o3s_pose_search.hpp"
 #include "o3s_scan.h"
 #include "o3s_submap_collection.hpp"
+#include "outlier_removal/o3s_outlier_removal.h"
 
 namespace o3s {
 
@@ -114,6 +115,11 @@ struct MapperParams {
   // (IcpHip::setDegeneracyPartial, include/degeneracy/o3s_degeneracy_partial.h) instead of to zero (remapMinCategory 2) or not
   // at all (remapMinCategory 1)
   bool degeneracyPartial = false;
+  // An outlier filter (include/outlier_removal/o3s_outlier_removal.h: Open3D's RemoveRadiusOutliers / RemoveStatisticalOutliers) on
+  // every sweep the mapper pre-processes ITSELF, right behind the pre-processing: stray returns then reach neither the registration
+  // nor the map.  kind 0 (the default): no call is made.  A caller that hands over an already pre-processed scan
+  // (addRangeMeasurement(o3s_scan*&, ...)) filters it itself, with o3s_scan_remove_outliers and this mapper's scanMatcherCropper
+  o3s_outlier_params scanOutlierRemoval{0, 0, 0.0};
   static o3s_localizability_params defaultLocalizability() {
     o3s_localizability_params p;
     o3s_localizability_default_params(&p);
@@ -488,19 +494,28 @@ class MapperHip {
       check(o3s_scan_preprocess_staged(scan_, &params_.mapBuilderCropper, params_.scanVoxelSize, &params_.scanMatcherCropper, deskewStage_, &nMerge,
                                        &nMatch),
             "o3s_scan_preprocess_staged");
+      removeScanOutliers();
       return;
     }
-    if (raw.ready) {
+    if (raw.ready) {  // pre-processed — and, where wanted, filtered — by the caller
       o3s_scan* filled = *raw.ready;
       *raw.ready = submaps_.exchangeScanForNextMeasurement(filled);
       scan_ = filled;
-    } else if (raw.staged)
+      return;
+    }
+    if (raw.staged)
       check(o3s_scan_preprocess_staged(scan_, &params_.mapBuilderCropper, params_.scanVoxelSize, &params_.scanMatcherCropper, raw.staged, &nMerge, &nMatch),
             "o3s_scan_preprocess_staged");
     else
       check(o3s_scan_preprocess(scan_, &params_.mapBuilderCropper, params_.scanVoxelSize, &params_.scanMatcherCropper, raw.pts, raw.normals, raw.N, &nMerge,
                                 &nMatch),
             "o3s_scan_preprocess");
+    removeScanOutliers();
+  }
+  // MapperParams::scanOutlierRemoval on the sweep just pre-processed; kind 0: no call, the loop is what it was
+  void removeScanOutliers() {
+    if (params_.scanOutlierRemoval.kind == 0) return;
+    check(o3s_scan_remove_outliers(scan_, &params_.scanMatcherCropper, &params_.scanOutlierRemoval, nullptr, nullptr), "o3s_scan_remove_outliers");
   }
   static void check(int rc, const char* what) {
     if (rc != O3S_OK) throw std::runtime_error(std::string(what) + " failed (status " + std::to_string(rc) + ")");

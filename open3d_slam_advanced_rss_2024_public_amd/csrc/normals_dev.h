@@ -164,19 +164,24 @@ __device__ inline D3 fast_eigen3x3(double (*A)[3]) {
   return {0, 0, 1};
 }
 
-// One lane per point (in cell-sorted order, so neighbouring lanes walk neighbouring cells).  The K nearest candidates
-// live in registers as a sorted list; an insertion is an unrolled compare-exchange chain (no dynamic indexing).
+// THE squared distance of the neighbour searches (normals, FPFH lists, the outlier filters): three rounded products, two rounded
+// sums, in this order
+__device__ __forceinline__ double dist2(double qx, double qy, double qz, double px, double py, double pz) {
+  const double ddx = qx - px, ddy = qy - py, ddz = qz - pz;
+  double d = ddx * ddx;
+  d = d + ddy * ddy;
+  d = d + ddz * ddz;
+  return d;
+}
+
+// The exact max_nn nearest points of a query in a grid index, ascending (d2, index), into D / J (unused slots: +inf / 0x7fffffff);
+// points at d2 >= r2 may be missing from the list and are cut by the caller (r2 = +inf: no cut, the rings run to the grid's
+// extent).  One lane per query; the K nearest candidates live in registers as a sorted list; an insertion is an unrolled
+// compare-exchange chain (no dynamic indexing).  Called once per kernel, from uniform control flow (it owns LDS slots per thread).
 template <int K>
-__global__ void __launch_bounds__(kB) k_normals(const double* __restrict__ sp /*cell-sorted points*/, const uint32_t* __restrict__ vals /*sorted -> original*/,
-                                                const double* __restrict__ pts /*original order*/, int64_t N, NGrid g,
-                                                const uint32_t* __restrict__ cbeg, const uint32_t* __restrict__ cend, int max_nn, double r2,
-                                                double* __restrict__ out_n, int32_t* __restrict__ out_idx /*nullable, N x max_nn*/) {
-  const int64_t t = (int64_t)blockIdx.x * kB + threadIdx.x;
-  if (t >= N) return;
-  const double qx = sp[3 * t], qy = sp[3 * t + 1], qz = sp[3 * t + 2];
-  const int64_t self = vals[t];
-  double D[K];
-  int32_t J[K];
+__device__ __forceinline__ void knn_grid_search(const double* sp /*cell-sorted points*/, const uint32_t* vals /*sorted -> original*/, const double qx,
+                                                const double qy, const double qz, const NGrid g, const uint32_t* cbeg, const uint32_t* cend,
+                                                const int max_nn, const double r2, double (&D)[K], int32_t (&J)[K]) {
 #pragma unroll
   for (int s = 0; s < K; ++s) {
     D[s] = __builtin_huge_val();
@@ -223,10 +228,7 @@ __global__ void __launch_bounds__(kB) k_normals(const double* __restrict__ sp /*
       uint32_t mask = 0u;
 #pragma unroll
       for (int u = 0; u < kNb; ++u) {
-        const double ddx = qx - px[u], ddy = qy - py[u], ddz = qz - pz[u];
-        double d = ddx * ddx;
-        d = d + ddy * ddy;
-        d = d + ddz * ddz;
+        const double d = dist2(qx, qy, qz, px[u], py[u], pz[u]);
         s_cd[u][threadIdx.x] = d;
         s_cj[u][threadIdx.x] = pid[u];
         if (j0 + (uint32_t)u < je && ((d < D[K - 1]) || (d == D[K - 1] && pid[u] < J[K - 1]))) mask |= 1u << u;
@@ -354,6 +356,21 @@ __global__ void __launch_bounds__(kB) k_normals(const double* __restrict__ sp /*
     }
     done = done_after(r);
   }
+}
+
+// One lane per point (in cell-sorted order, so neighbouring lanes walk neighbouring cells).
+template <int K>
+__global__ void __launch_bounds__(kB) k_normals(const double* __restrict__ sp /*cell-sorted points*/, const uint32_t* __restrict__ vals /*sorted -> original*/,
+                                                const double* __restrict__ pts /*original order*/, int64_t N, NGrid g,
+                                                const uint32_t* __restrict__ cbeg, const uint32_t* __restrict__ cend, int max_nn, double r2,
+                                                double* __restrict__ out_n, int32_t* __restrict__ out_idx /*nullable, N x max_nn*/) {
+  const int64_t t = (int64_t)blockIdx.x * kB + threadIdx.x;
+  if (t >= N) return;
+  const double qx = sp[3 * t], qy = sp[3 * t + 1], qz = sp[3 * t + 2];
+  const int64_t self = vals[t];
+  double D[K];
+  int32_t J[K];
+  knn_grid_search<K>(sp, vals, qx, qy, qz, g, cbeg, cend, max_nn, r2, D, J);
   // KDTreeFlann::SearchHybrid: the max_nn nearest, cut at d2 < radius^2
   int k = 0;
 #pragma unroll
@@ -483,10 +500,12 @@ constexpr size_t kGridMaxCells = (size_t)1 << 24;
 
 // cell0: first guess of the cell edge; the cell is then re-sized once so that an occupied cell holds ~target_rho points
 // (surface-like data: density ~ cell^2), never above cell_max.  Any cell size keeps the searches exact.
+// keep_cell: no re-sizing — the cell stays at cell0 unless the grid's extent forces a coarser one (a caller whose search walks a fixed block
+// of cells needs cell >= its radius, never less).  max_cells: the cap on the dense cell arrays (at most kGridMaxCells).
 // known_bb (nullable): the cloud's bounds as the six order-preserving bit patterns bounds_fetch gives (minima, maxima) — a caller that has
 // just written the cloud has them for free, and the build then starts without its first pass over the cloud and its first wait
 inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, double cell0, double target_rho, double cell_max, GridIndex* out,
-                            hipStream_t s, const unsigned long long* known_bb = nullptr) {
+                            hipStream_t s, const unsigned long long* known_bb = nullptr, bool keep_cell = false, size_t max_cells = kGridMaxCells) {
   if (N <= 0 || N > (int64_t)0x7fffffff) return O3S_ERR_BAD_ARGUMENT;
   const size_t n = (size_t)N;
   const size_t tb_scan = scan_temp_bytes(N), tb_sort = sort_temp_bytes(N);
@@ -509,7 +528,7 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
   }
   const double ext = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
   double cell = std::max(std::max(cell0, ext / 512.0), 1e-9);
-  const double kMaxCells = (double)kGridMaxCells;
+  const double kMaxCells = (double)std::min(std::max<size_t>(max_cells, 8), kGridMaxCells);
   int64_t dims[3];
   O3S_NGRID_NOTE(int cap_steps = 0);
   O3S_NGRID_NOTE(bool resized = false);
@@ -544,7 +563,7 @@ inline int build_grid_index(NormalsWork& w, const double* d_pts, int64_t N, doub
     hipLaunchKernelGGL(k_grid_keys<FlatPoints>, dim3(nblk(N)), dim3(kB), 0, s, FlatPoints{d_pts}, N, cell, lo[0], lo[1], lo[2], (uint64_t)dims[0], (uint64_t)dims[1], ar.keys, ar.vals);
     size_t tb = tb_sort;
     CK(sort_pairs(ar.tmp, tb, ar.keys, ar.keys2, ar.vals, ar.vals2, n, key_bits((uint64_t)dims[0] * (uint64_t)dims[1] * (uint64_t)dims[2]), s));  // keys are cell indices of the grid just sized
-    if (attempt == 0) {
+    if (attempt == 0 && !keep_cell) {
       hipLaunchKernelGGL(k_heads, dim3(nblk(N)), dim3(kB), 0, s, ar.keys2, N, ~0ull, ar.head);
       int64_t n_occ = 0;
       const int rc = scan_flags(ar.head, ar.ord, N, ar.tmp, tb_scan, &n_occ, s);

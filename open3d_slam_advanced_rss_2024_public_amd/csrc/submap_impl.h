@@ -950,6 +950,32 @@ int o3s_submap_download_colors(const o3s_submap* m, double* colors) {
   return O3S_OK;
 }
 
+// removeByIds on a settled submap (space carving, the outlier filters): SelectByIndex(ids, invert) keeps the survivors in their
+// order.  keep: one flag per map point, off: its exclusive scan, n_keep: the number set — on the submap's device, written on its
+// stream.  The survivors go to the other half of the ping-pong, normals and colours with them; the call returns on a drained stream
+static int submap_keep_flagged(o3s_submap* m, const uint32_t* keep, const uint32_t* off, int64_t n_keep) {
+  const int64_t Nm = m->n;
+  if (n_keep >= Nm) return O3S_OK;
+  hipStream_t s = m->stream;
+  const int c = m->cur;
+  const bool hn = m->has_normals == 1;
+  CK(m->pts[1 - c].ensure((size_t)Nm * 24, 0, s));
+  CK(m->nrm[1 - c].ensure((size_t)Nm * 24, 0, s));
+  hipLaunchKernelGGL(k_compact, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].as<double>(), hn ? m->nrm[c].as<double>() : nullptr, Nm, keep, off, m->pts[1 - c].as<double>(),
+                     m->nrm[1 - c].as<double>(), (int32_t*)nullptr);
+  if (m->has_colors == 1) {  // SelectByIndex carries the colours along
+    CK(m->col[1 - c].ensure((size_t)Nm * 24, 0, s));
+    hipLaunchKernelGGL(k_compact_attr, dim3(nblk(Nm)), dim3(kB), 0, s, (const double*)m->col[c].as<double>(), (const double*)nullptr, Nm, keep, off,
+                       m->col[1 - c].as<double>(), (double*)nullptr);
+  }
+  CK(hipGetLastError());
+  CK(hipStreamSynchronize(s));
+  m->cur = 1 - c;
+  m->n = n_keep;
+  m->layout_valid = false;  // order is kept, but how many pass-through points survived is not known here
+  return O3S_OK;
+}
+
 int o3s_submap_carve(o3s_submap* m, const o3s_carving_params* cp, const double* raw_pts, int64_t N, const double T_map_sensor[16], int64_t* n_removed) {
   if (const int rs_ = submap_settle(m); rs_ != O3S_OK) return rs_;  // a pending insert is completed first
   if (n_removed) *n_removed = 0;
@@ -1006,22 +1032,8 @@ int o3s_submap_carve(o3s_submap* m, const o3s_carving_params* cp, const double* 
   int64_t n_keep = 0;
   rc = scan_flags(w.keep, w.off, Nm, w.tmp, tb_scan, &n_keep, s);
   if (rc != O3S_OK) return rc;
-  if (n_keep < Nm) {
-    CK(m->pts[1 - c].ensure((size_t)Nm * 24, 0, s));
-    CK(m->nrm[1 - c].ensure((size_t)Nm * 24, 0, s));
-    hipLaunchKernelGGL(k_compact, dim3(nblk(Nm)), dim3(kB), 0, s, m->pts[c].as<double>(), hn ? m->nrm[c].as<double>() : nullptr, Nm, w.keep, w.off, m->pts[1 - c].as<double>(),
-                       m->nrm[1 - c].as<double>(), (int32_t*)nullptr);
-    if (m->has_colors == 1) {  // SelectByIndex carries the colours along
-      CK(m->col[1 - c].ensure((size_t)Nm * 24, 0, s));
-      hipLaunchKernelGGL(k_compact_attr, dim3(nblk(Nm)), dim3(kB), 0, s, (const double*)m->col[c].as<double>(), (const double*)nullptr, Nm, w.keep, w.off,
-                         m->col[1 - c].as<double>(), (double*)nullptr);
-    }
-    CK(hipGetLastError());
-    CK(hipStreamSynchronize(s));
-    m->cur = 1 - c;
-    m->n = n_keep;
-    m->layout_valid = false;  // order is kept, but how many pass-through points survived is not known here
-  }
+  rc = submap_keep_flagged(m, w.keep, w.off, n_keep);
+  if (rc != O3S_OK) return rc;
   if (n_removed) *n_removed = Nm - n_keep;
   return O3S_OK;
 }

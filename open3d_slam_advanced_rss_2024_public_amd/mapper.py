@@ -97,6 +97,9 @@ class Mapper:
         self.last_remap_replaced = 0
         self.last_registration_pose = np.eye(4)
         self._degeneracy_armed = None         # what the ICP handle was last told (Constrain): (params, min_category)
+        # MapperParams::scanOutlierRemoval: an outlier filter (cloud_ops.outlier_params) on the pre-processed sweep, right behind the
+        # pre-processing — stray returns then reach neither the registration nor the map.  None / kind 0: no call is made
+        self.scan_outlier_removal = None
 
     def set_calibration(self, C_):
         self.calibration = np.array(C_, np.float64).reshape(4, 4)
@@ -204,6 +207,9 @@ class Mapper:
             from .odometry import undistort_cloud
             sp = undistort_cloud(sp, self.last_motion, getattr(self.icp, "device", 0))
         self.ps.preprocess(self.wide, self.scan_voxel, self.narrow, sp, sn)
+        q = self.scan_outlier_removal
+        if q is not None and q.kind != 0:   # kind 0 / None: no call at all — the loop is what it was
+            self.ps.removeOutliers(self.narrow, q)
 
     def _arm_degeneracy(self):
         """Constrain: the handle's degeneracy mode follows the policy (set again only when the policy or its parameters change)."""

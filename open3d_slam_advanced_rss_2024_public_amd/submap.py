@@ -324,6 +324,29 @@ class Submap(_lib.Handle):
         self._check(self._lib.o3s_submap_carve(self._h, C.byref(cp), _d(p), p.shape[0], _d(_pose(mapToRangeSensor)), C.byref(k)), "o3s_submap_carve")
         return int(k.value)
 
+    def removeOutliers(self, params):
+        """The outlier filter `params` (cloud_ops.outlier_params) on the sparse map, in place -> (number of removed points, stats |
+        None): bit for bit what cloud_ops.remove_*_outlier returns on the downloaded map; normals and colours follow their points.
+        Like a carve it leaves the feature set, the voxel-map snapshot and an ICP reference describing the map as it was."""
+        fn = self._lib.o3s_submap_remove_outliers
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+        k = C.c_int64()
+        st = np.zeros(4, np.float64)
+        self._check(fn(self._h, C.byref(params), C.byref(k), _d(st)), "o3s_submap_remove_outliers")
+        return int(k.value), (st if params.kind == 2 else None)
+
+    def removeRadiusOutliers(self, nb_points: int, radius: float) -> int:
+        """PointCloud::RemoveRadiusOutliers(nb_points, radius) on the sparse map, in place; returns the number of removed points."""
+        from .cloud_ops import outlier_params
+        return self.removeOutliers(outlier_params(1, nb_points, radius))[0]
+
+    def removeStatisticalOutliers(self, nb_neighbors: int, std_ratio: float):
+        """PointCloud::RemoveStatisticalOutliers(nb_neighbors, std_ratio) on the sparse map, in place -> (number of removed points,
+        [mean, std, thr, valid])."""
+        from .cloud_ops import outlier_params
+        return self.removeOutliers(outlier_params(2, nb_neighbors, std_ratio))
+
     def insertProcessed(self, scan: "ProcessedScan", mapToRangeSensor) -> bool:
         """insertScan(rawScan, *processed.merge_, mapToRangeSensor) (Mapper.cpp:487) from the resident merge cloud."""
         self._check(self._lib.o3s_submap_insert_processed(self._h, scan._h, _d(_pose(mapToRangeSensor))), "o3s_submap_insert_processed")
@@ -469,6 +492,19 @@ class ProcessedScan(_lib.Handle):
             raise RuntimeError("the scan has no normals and set_normal_estimation() was not called")
         if rc != _lib.OK:
             raise RuntimeError(f"o3s_scan_preprocess failed with o3s_status {rc}")
+        self.n_merge, self.n_match = int(a.value), int(b.value)
+        return self.n_merge, self.n_match
+
+    def removeOutliers(self, scan_matcher_cropper: CropperC, params):
+        """The outlier filter `params` (cloud_ops.outlier_params) on the merge cloud, in place; the match cloud becomes the
+        scan_matcher_cropper crop of what is left.  Returns (n_merge, n_match).  kind 0 does nothing."""
+        fn = self._lib.o3s_scan_remove_outliers
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(CropperC), C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        a, b = C.c_int64(self.n_merge), C.c_int64(self.n_match)
+        rc = fn(self._h, C.byref(scan_matcher_cropper), C.byref(params), C.byref(a), C.byref(b))
+        if rc != _lib.OK:
+            raise RuntimeError(f"o3s_scan_remove_outliers failed with o3s_status {rc}")
         self.n_merge, self.n_match = int(a.value), int(b.value)
         return self.n_merge, self.n_match
 
