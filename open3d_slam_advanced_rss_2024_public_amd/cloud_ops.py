@@ -194,6 +194,58 @@ def remove_statistical_outlier(points, nb_neighbors: int, std_ratio: float, norm
     return _remove_outliers(outlier_params(OUTLIER_STATISTICAL, nb_neighbors, std_ratio), points, normals, device)
 
 
+# ---- DBSCAN clustering and small-cluster removal (include/clustering/o3s_clustering.h) ---------------------------------------
+class DbscanParamsC(C.Structure):   # o3s_dbscan_params
+    _fields_ = [("eps", C.c_double), ("min_points", C.c_int32), ("min_cluster_size", C.c_int32)]
+
+
+def dbscan_params(eps: float = 0.0, min_points: int = 0, min_cluster_size: int = 0) -> DbscanParamsC:
+    """eps: neighbourhood radius; min_points: neighbours, itself included, that make a point core (0 = off); min_cluster_size:
+    clusters with fewer points are removed (0 / 1: only noise goes)"""
+    return DbscanParamsC(float(eps), int(min_points), int(min_cluster_size))
+
+
+def cluster_dbscan(points, eps: float, min_points: int, device: int = 0):
+    """PointCloud::ClusterDBSCAN(eps, min_points) -> (labels (N,) int32 with -1 = noise, n_clusters, sizes (n_clusters,) int32):
+    clusters are numbered by their smallest core index; a border point takes the smallest id among its core neighbours."""
+    p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    N = p.shape[0]
+    labels = np.full(N, -1, np.int32)
+    sizes = np.zeros(N, np.int32)
+    k = C.c_int32()
+    fn = _L().o3s_cluster_dbscan
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.POINTER(DbscanParamsC), C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    q = dbscan_params(eps, min_points, 0)
+    _check(fn(device, C.byref(q), _d(p), N, labels.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(k), sizes.ctypes.data_as(C.POINTER(C.c_int32))),
+           "o3s_cluster_dbscan")
+    return labels, int(k.value), sizes[:k.value].copy()
+
+
+def remove_small_clusters(points, eps: float, min_points: int, min_cluster_size: int, normals=None, device: int = 0):
+    """ClusterDBSCAN(eps, min_points), then every point without a cluster or in a cluster of fewer than min_cluster_size points is
+    dropped -> (points, normals | None, kept indices, labels of the INPUT points).  Input order is kept."""
+    p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    n = None if normals is None else np.ascontiguousarray(normals, np.float64).reshape(-1, 3)
+    if n is not None and n.shape != p.shape:
+        raise ValueError("points and normals differ in shape")
+    N = p.shape[0]
+    op = np.zeros_like(p)
+    on = np.zeros_like(p) if n is not None else None
+    idx = np.zeros(N, np.int64)
+    labels = np.full(N, -1, np.int32)
+    k, nc = C.c_int64(), C.c_int32()
+    fn = _L().o3s_remove_small_clusters
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.POINTER(DbscanParamsC), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double),
+                   C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    q = dbscan_params(eps, min_points, min_cluster_size)
+    _check(fn(device, C.byref(q), _d(p), _d(n), N, _d(op), _d(on), idx.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(k),
+              labels.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nc)), "o3s_remove_small_clusters")
+    m = k.value
+    return op[:m].copy(), (None if on is None else on[:m].copy()), idx[:m].copy(), labels
+
+
 # ---- the same operators with colours / covariances riding along (include/o3s_cloud_ops.h, *_attr entry points) ----------
 def _attr_call(fn_name, lead_args, points, normals, colors, covariances, want_idx, device):
     p = np.ascontiguousarray(points, np.float64)

@@ -25,6 +25,7 @@
 #include "degeneracy/o3s_degeneracy_partial.h"
 #include "localizability/o3s_localizability.h"
 #include "outlier_removal/o3s_outlier_removal.h"
+#include "clustering/o3s_clustering.h"
 
 namespace o3s {
 
@@ -181,6 +182,24 @@ class SubmapHip {
   std::int64_t removeRadiusOutliers(std::int32_t nbPoints, double searchRadius) { return removeOutliers(o3s_outlier_params{1, nbPoints, searchRadius}); }
   std::int64_t removeStatisticalOutliers(std::int32_t nbNeighbors, double stdRatio, double* stats4 = nullptr) {
     return removeOutliers(o3s_outlier_params{2, nbNeighbors, stdRatio}, stats4);
+  }
+  // Open3D's ClusterDBSCAN(eps, minPoints) of the sparse map (clustering/o3s_clustering.h): one label per map point, -1 = noise;
+  // returns the number of clusters.  Nothing in the map changes
+  std::int32_t clusterDBSCAN(double eps, std::int32_t minPoints, std::vector<std::int32_t>& labels) {
+    const o3s_dbscan_params p{eps, minPoints, 0};
+    labels.assign(static_cast<std::size_t>(o3s_submap_size(m_)), -1);
+    std::int32_t n = 0;
+    const int rc = o3s_submap_cluster_dbscan(m_, &p, labels.data(), &n);
+    if (rc != O3S_OK) throw std::runtime_error("o3s_submap_cluster_dbscan failed (status " + std::to_string(rc) + ")");
+    return n;
+  }
+  // ... and the removal of every point without a cluster or in a cluster below p.min_cluster_size points, in place; returns the
+  // number of removed points.  nClusters nullable
+  std::int64_t removeSmallClusters(const o3s_dbscan_params& p, std::int32_t* nClusters = nullptr) {
+    std::int64_t removed = 0;
+    const int rc = o3s_submap_remove_small_clusters(m_, &p, &removed, nClusters);
+    if (rc != O3S_OK) throw std::runtime_error("o3s_submap_remove_small_clusters failed (status " + std::to_string(rc) + ")");
+    return removed;
   }
   std::int64_t size() const { return o3s_submap_size(m_); }
   // the two questions the per-scan loop asks about the size, answered without waiting for an insert whose completion is pending

@@ -54,6 +54,7 @@
 #include "o3s_scan.h"
 #include "o3s_submap_collection.hpp"
 #include "outlier_removal/o3s_outlier_removal.h"
+#include "clustering/o3s_clustering.h"
 
 namespace o3s {
 
@@ -120,6 +121,11 @@ struct MapperParams {
   // nor the map.  kind 0 (the default): no call is made.  A caller that hands over an already pre-processed scan
   // (addRangeMeasurement(o3s_scan*&, ...)) filters it itself, with o3s_scan_remove_outliers and this mapper's scanMatcherCropper
   o3s_outlier_params scanOutlierRemoval{0, 0, 0.0};
+  // Small-cluster removal (include/clustering/o3s_clustering.h: Open3D's ClusterDBSCAN, then every cluster below min_cluster_size
+  // points and all noise dropped) on the same sweeps, right behind the outlier filter: what that filter cannot take out — the
+  // supported blob a pedestrian or a dust cloud leaves.  min_points 0 (the default): no call is made.  A caller that hands over
+  // an already pre-processed scan filters it itself, with o3s_scan_remove_small_clusters and this mapper's scanMatcherCropper
+  o3s_dbscan_params scanClusterRemoval{0.0, 0, 0};
   static o3s_localizability_params defaultLocalizability() {
     o3s_localizability_params p;
     o3s_localizability_default_params(&p);
@@ -512,10 +518,14 @@ class MapperHip {
             "o3s_scan_preprocess");
     removeScanOutliers();
   }
-  // MapperParams::scanOutlierRemoval on the sweep just pre-processed; kind 0: no call, the loop is what it was
+  // MapperParams::scanOutlierRemoval, then ::scanClusterRemoval, on the sweep just pre-processed; kind 0 / min_points 0: no call,
+  // the loop is what it was
   void removeScanOutliers() {
-    if (params_.scanOutlierRemoval.kind == 0) return;
-    check(o3s_scan_remove_outliers(scan_, &params_.scanMatcherCropper, &params_.scanOutlierRemoval, nullptr, nullptr), "o3s_scan_remove_outliers");
+    if (params_.scanOutlierRemoval.kind != 0)
+      check(o3s_scan_remove_outliers(scan_, &params_.scanMatcherCropper, &params_.scanOutlierRemoval, nullptr, nullptr), "o3s_scan_remove_outliers");
+    if (params_.scanClusterRemoval.min_points != 0)
+      check(o3s_scan_remove_small_clusters(scan_, &params_.scanMatcherCropper, &params_.scanClusterRemoval, nullptr, nullptr),
+            "o3s_scan_remove_small_clusters");
   }
   static void check(int rc, const char* what) {
     if (rc != O3S_OK) throw std::runtime_error(std::string(what) + " failed (status " + std::to_string(rc) + ")");

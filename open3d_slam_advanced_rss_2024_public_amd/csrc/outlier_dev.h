@@ -33,53 +33,51 @@ __global__ void __launch_bounds__(kB) k_or_fmap(const uint32_t* __restrict__ fla
   if (i < N && flag[i]) fmap[off[i]] = (uint32_t)i;
 }
 
-// Radius filter.  The grid's cell edge is at least the radius, so every point at d2 < r2 lies in the 3 x 3 x 3 block around the
-// query's cell.  One query per lane (cell-sorted order: neighbouring lanes walk the same cells); the three cells of a row are
-// consecutive keys, so their points are one run of the sorted copy.  A lane stops at the first candidate that takes its count
-// above nb: in a dense map (0.1 m voxels, 0.5 m radius) that is after a few dozen candidates of the several hundred in the block.
-// keep[input index] = count > nb (the array is zeroed beforehand: non-finite points stay 0).
-__global__ void __launch_bounds__(kB) k_or_count(const double* __restrict__ sp, const uint32_t* __restrict__ vals, int64_t N, NGrid g,
-                                                 const uint32_t* __restrict__ cbeg, const uint32_t* __restrict__ cend, int nb, double r2,
-                                                 const uint32_t* __restrict__ fmap /*nullable: identity*/, uint32_t* __restrict__ keep) {
-  const int64_t t = (int64_t)blockIdx.x * kB + threadIdx.x;
-  if (t >= N) return;
-  const double qx = sp[3 * t], qy = sp[3 * t + 1], qz = sp[3 * t + 2];
-  // the query's cell: the expression that built the keys (k_grid_keys)
+// The 3 x 3 x 3 block of cells around the point (qx, qy, qz) as nine runs of the cell-sorted copy: the three cells of a row are
+// consecutive keys, so their points are one run.  The 27 cell headers go out as one batch of independent loads.  The cell is
+// found by the expression that built the keys (k_grid_keys).  Row 4 is the query's own row.
+__device__ __forceinline__ void block_runs(double qx, double qy, double qz, const NGrid& g, const uint32_t* __restrict__ cbeg,
+                                           const uint32_t* __restrict__ cend, uint32_t (&lo)[9], uint32_t (&hi)[9]) {
   const int cx = (int)floor((qx - g.ox) / g.cell), cy = (int)floor((qy - g.oy) / g.cell), cz = (int)floor((qz - g.oz) / g.cell);
-  uint32_t lo[9], hi[9];
-  {  // 27 cell headers as one batch of independent loads, folded into nine runs
-    uint32_t cb[27], ce[27];
+  uint32_t cb[27], ce[27];
 #pragma unroll
-    for (int u = 0; u < 27; ++u) {
-      const int z = cz + u / 9 - 1, y = cy + (u / 3) % 3 - 1, x = cx + u % 3 - 1;
-      const bool in = z >= 0 && z < g.nz && y >= 0 && y < g.ny && x >= 0 && x < g.nx;
-      const size_t c = in ? ((size_t)z * (size_t)g.ny + (size_t)y) * (size_t)g.nx + (size_t)x : 0;
-      const uint32_t b0 = cbeg[c], e0 = cend[c];
-      cb[u] = in ? b0 : 0u;
-      ce[u] = in ? e0 : 0u;
-    }
-#pragma unroll
-    for (int row = 0; row < 9; ++row) {
-      uint32_t l = 0xffffffffu, h = 0u;
-#pragma unroll
-      for (int u = 0; u < 3; ++u) {
-        const int q = row * 3 + u;
-        if (ce[q] > cb[q]) {  // empty cells carry begin = end = 0
-          l = min(l, cb[q]);
-          h = max(h, ce[q]);
-        }
-      }
-      lo[row] = h > l ? l : 0u;
-      hi[row] = h > l ? h : 0u;
-    }
+  for (int u = 0; u < 27; ++u) {
+    const int z = cz + u / 9 - 1, y = cy + (u / 3) % 3 - 1, x = cx + u % 3 - 1;
+    const bool in = z >= 0 && z < g.nz && y >= 0 && y < g.ny && x >= 0 && x < g.nx;
+    const size_t c = in ? ((size_t)z * (size_t)g.ny + (size_t)y) * (size_t)g.nx + (size_t)x : 0;
+    const uint32_t b0 = cbeg[c], e0 = cend[c];
+    cb[u] = in ? b0 : 0u;
+    ce[u] = in ? e0 : 0u;
   }
-  int count = 0;
-  constexpr int kNb = 8;  // candidates per batch: their loads go out together
+#pragma unroll
+  for (int row = 0; row < 9; ++row) {
+    uint32_t l = 0xffffffffu, h = 0u;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      const int q = row * 3 + u;
+      if (ce[q] > cb[q]) {  // empty cells carry begin = end = 0
+        l = min(l, cb[q]);
+        h = max(h, ce[q]);
+      }
+    }
+    lo[row] = h > l ? l : 0u;
+    hi[row] = h > l ? h : 0u;
+  }
+}
+
+// The walk over those runs, the own row first (it holds the query itself and its nearest neighbours), in batches of kWalkBatch
+// candidates whose loads go out together: hits(j0, m) for every batch with a candidate at d2 < r2 — bit u of m: candidate j0 + u
+// (an index into the cell-sorted copy) passed; done() is asked before every batch and ends the walk.
+constexpr int kWalkBatch = 8;
+template <class Hits, class Done>
+__device__ __forceinline__ void walk_block(const double* __restrict__ sp, const uint32_t (&lo)[9], const uint32_t (&hi)[9], double qx, double qy, double qz,
+                                           double r2, Hits hits, Done done) {
+  constexpr int kNb = kWalkBatch;
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
-    const int row = k == 0 ? 4 : (k <= 4 ? k - 1 : k);  // the own row first: it holds the query itself and its nearest neighbours
+    const int row = k == 0 ? 4 : (k <= 4 ? k - 1 : k);
     const uint32_t jb = lo[row], je = hi[row];
-    for (uint32_t j0 = jb; j0 < je && count <= nb; j0 += kNb) {
+    for (uint32_t j0 = jb; j0 < je && !done(); j0 += kNb) {
       double px[kNb], py[kNb], pz[kNb];
 #pragma unroll
       for (int u = 0; u < kNb; ++u) {
@@ -88,11 +86,29 @@ __global__ void __launch_bounds__(kB) k_or_count(const double* __restrict__ sp, 
         py[u] = sp[3 * j + 1];
         pz[u] = sp[3 * j + 2];
       }
+      uint32_t m = 0u;
 #pragma unroll
       for (int u = 0; u < kNb; ++u)
-        if (j0 + (uint32_t)u < je && dist2(qx, qy, qz, px[u], py[u], pz[u]) < r2) ++count;
+        if (j0 + (uint32_t)u < je && dist2(qx, qy, qz, px[u], py[u], pz[u]) < r2) m |= 1u << u;
+      if (m) hits(j0, m);
     }
   }
+}
+
+// Radius filter.  The grid's cell edge is at least the radius, so every point at d2 < r2 lies in the 3 x 3 x 3 block around the
+// query's cell.  One query per lane (cell-sorted order: neighbouring lanes walk the same cells).  A lane stops at the first batch
+// that takes its count above nb: in a dense map (0.1 m voxels, 0.5 m radius) that is after a few dozen candidates of the several
+// hundred in the block.  keep[input index] = count > nb (the array is zeroed beforehand: non-finite points stay 0).
+__global__ void __launch_bounds__(kB) k_or_count(const double* __restrict__ sp, const uint32_t* __restrict__ vals, int64_t N, NGrid g,
+                                                 const uint32_t* __restrict__ cbeg, const uint32_t* __restrict__ cend, int nb, double r2,
+                                                 const uint32_t* __restrict__ fmap /*nullable: identity*/, uint32_t* __restrict__ keep) {
+  const int64_t t = (int64_t)blockIdx.x * kB + threadIdx.x;
+  if (t >= N) return;
+  const double qx = sp[3 * t], qy = sp[3 * t + 1], qz = sp[3 * t + 2];
+  uint32_t lo[9], hi[9];
+  block_runs(qx, qy, qz, g, cbeg, cend, lo, hi);
+  int count = 0;
+  walk_block(sp, lo, hi, qx, qy, qz, r2, [&](uint32_t, uint32_t m) { count += __popc(m); }, [&]() { return count > nb; });
   const uint32_t f = vals[t];
   keep[fmap ? fmap[f] : f] = count > nb ? 1u : 0u;
 }

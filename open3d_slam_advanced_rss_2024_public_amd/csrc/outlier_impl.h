@@ -18,6 +18,39 @@ inline bool outlier_params_valid(const o3s_outlier_params* p) {
   return p->kind == 1 || p->nb <= kNnMax;
 }
 
+// the two halves of a filter on a resident pre-processed scan (the outlier filters, the small-cluster removal)
+// ... the survivors of the merge cloud, in order, through the pre-process's staging arrays (N <= the raw scan they were sized for);
+// keep / off: one flag per merge point and its exclusive scan, on the scan's stream.  Returns on a drained stream
+inline int scan_keep_flagged(o3s_scan* sc, const uint32_t* keep, const uint32_t* off, int64_t n_keep) {
+  const int64_t N = sc->n_wide;
+  if (n_keep >= N) return O3S_OK;
+  hipStream_t s = sc->stream;
+  CK(sc->tmp_p.ensure((size_t)N * 24, 0, s));
+  CK(sc->tmp_n.ensure((size_t)N * 24, 0, s));
+  hipLaunchKernelGGL(k_compact, dim3(nblk(N)), dim3(kB), 0, s, (const double*)sc->wide_p.as<double>(), (const double*)sc->wide_n.as<double>(), N, keep, off,
+                     sc->tmp_p.as<double>(), sc->tmp_n.as<double>(), (int32_t*)nullptr);
+  CK(hipGetLastError());
+  CK(hipStreamSynchronize(s));
+  std::swap(sc->wide_p, sc->tmp_p);
+  std::swap(sc->wide_n, sc->tmp_n);
+  return O3S_OK;
+}
+// ... and narrowCropped = scanMatcherCropper_->crop(*wideCropped), as scan_preprocess_impl applies it, over the n_keep survivors
+inline int scan_recrop(o3s_scan* sc, const o3s_cropper* scan_matcher_cropper, int64_t n_keep, int64_t* n_merge, int64_t* n_match) {
+  hipStream_t s = sc->stream;
+  int64_t n_narrow = 0;
+  const int rc = crop_dev(sc->arena, *scan_matcher_cropper, sc->wide_p.as<double>(), sc->wide_n.as<double>(), n_keep, sc->narrow_p.as<double>(), sc->narrow_n.as<double>(),
+                          &n_narrow, s);
+  if (rc != O3S_OK) return rc;
+  CK(hipStreamSynchronize(s));
+  sc->n_wide = n_keep;
+  sc->n_narrow = n_narrow;
+  sc->pm_ready = false;  // the reading in the ICP layout is rebuilt by the next o3s_scan_set_reading
+  if (n_merge) *n_merge = n_keep;
+  if (n_match) *n_match = n_narrow;
+  return O3S_OK;
+}
+
 }  // namespace o3s_cloud
 }  // namespace
 
@@ -118,29 +151,10 @@ int o3s_scan_remove_outliers(o3s_scan* sc, const o3s_cropper* scan_matcher_cropp
     int rc = outlier_flags_dev(*w, p->kind, p->nb, p->value, sc->wide_p.as<double>(), N, &r, s);
     if (rc != O3S_OK) return rc;
     n_keep = r.n_keep;
-    if (n_keep < N) {  // the survivors, in order, through the pre-process's staging arrays (N <= the raw scan they were sized for)
-      CK(sc->tmp_p.ensure((size_t)N * 24, 0, s));
-      CK(sc->tmp_n.ensure((size_t)N * 24, 0, s));
-      hipLaunchKernelGGL(k_compact, dim3(nblk(N)), dim3(kB), 0, s, (const double*)sc->wide_p.as<double>(), (const double*)sc->wide_n.as<double>(), N, r.keep, r.off,
-                         sc->tmp_p.as<double>(), sc->tmp_n.as<double>(), (int32_t*)nullptr);
-      CK(hipGetLastError());
-      CK(hipStreamSynchronize(s));
-      std::swap(sc->wide_p, sc->tmp_p);
-      std::swap(sc->wide_n, sc->tmp_n);
-    }
+    rc = scan_keep_flagged(sc, r.keep, r.off, n_keep);
+    if (rc != O3S_OK) return rc;
   }
-  // narrowCropped = scanMatcherCropper_->crop(*wideCropped), as scan_preprocess_impl applies it
-  int64_t n_narrow = 0;
-  const int rc = crop_dev(sc->arena, *scan_matcher_cropper, sc->wide_p.as<double>(), sc->wide_n.as<double>(), n_keep, sc->narrow_p.as<double>(), sc->narrow_n.as<double>(),
-                          &n_narrow, s);
-  if (rc != O3S_OK) return rc;
-  CK(hipStreamSynchronize(s));
-  sc->n_wide = n_keep;
-  sc->n_narrow = n_narrow;
-  sc->pm_ready = false;  // the reading in the ICP layout is rebuilt by the next o3s_scan_set_reading
-  if (n_merge) *n_merge = n_keep;
-  if (n_match) *n_match = n_narrow;
-  return O3S_OK;
+  return scan_recrop(sc, scan_matcher_cropper, n_keep, n_merge, n_match);
 }
 
 }  // extern "C"

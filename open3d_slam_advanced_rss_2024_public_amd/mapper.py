@@ -100,6 +100,10 @@ class Mapper:
         # MapperParams::scanOutlierRemoval: an outlier filter (cloud_ops.outlier_params) on the pre-processed sweep, right behind the
         # pre-processing — stray returns then reach neither the registration nor the map.  None / kind 0: no call is made
         self.scan_outlier_removal = None
+        # MapperParams::scanClusterRemoval: small-cluster removal (cloud_ops.dbscan_params) on the pre-processed sweep, right behind
+        # the outlier filter — a blob of a few dozen supported points then reaches neither the registration nor the map.
+        # None / min_points 0: no call is made
+        self.scan_cluster_removal = None
 
     def set_calibration(self, C_):
         self.calibration = np.array(C_, np.float64).reshape(4, 4)
@@ -210,6 +214,9 @@ class Mapper:
         q = self.scan_outlier_removal
         if q is not None and q.kind != 0:   # kind 0 / None: no call at all — the loop is what it was
             self.ps.removeOutliers(self.narrow, q)
+        c = self.scan_cluster_removal
+        if c is not None and c.min_points != 0:   # min_points 0 / None: no call at all — the loop is what it was
+            self.ps.removeSmallClusters(self.narrow, c)
 
     def _arm_degeneracy(self):
         """Constrain: the handle's degeneracy mode follows the policy (set again only when the policy or its parameters change)."""

@@ -347,6 +347,32 @@ class Submap(_lib.Handle):
         from .cloud_ops import outlier_params
         return self.removeOutliers(outlier_params(2, nb_neighbors, std_ratio))
 
+    def clusterDBSCAN(self, eps: float, min_points: int):
+        """PointCloud::ClusterDBSCAN(eps, min_points) of the sparse map -> (labels (size,) int32, n_clusters): what
+        cloud_ops.cluster_dbscan returns on the downloaded map.  Nothing in the map changes."""
+        from .cloud_ops import dbscan_params
+        fn = self._lib.o3s_submap_cluster_dbscan
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        q = dbscan_params(eps, min_points, 0)
+        n = len(self)   # settles a pending insert: the size the call will see
+        labels = np.full(max(n, 1), -1, np.int32)
+        k = C.c_int32()
+        self._check(fn(self._h, C.byref(q), labels.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(k)), "o3s_submap_cluster_dbscan")
+        return labels[:n], int(k.value)
+
+    def removeSmallClusters(self, params):
+        """Small-cluster removal `params` (cloud_ops.dbscan_params) on the sparse map, in place -> (number of removed points,
+        n_clusters): bit for bit what cloud_ops.remove_small_clusters returns on the downloaded map; normals and colours follow
+        their points.  Like a carve it leaves the feature set, the voxel-map snapshot and an ICP reference describing the map as
+        it was."""
+        fn = self._lib.o3s_submap_remove_small_clusters
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        k, nc = C.c_int64(), C.c_int32()
+        self._check(fn(self._h, C.byref(params), C.byref(k), C.byref(nc)), "o3s_submap_remove_small_clusters")
+        return int(k.value), int(nc.value)
+
     def insertProcessed(self, scan: "ProcessedScan", mapToRangeSensor) -> bool:
         """insertScan(rawScan, *processed.merge_, mapToRangeSensor) (Mapper.cpp:487) from the resident merge cloud."""
         self._check(self._lib.o3s_submap_insert_processed(self._h, scan._h, _d(_pose(mapToRangeSensor))), "o3s_submap_insert_processed")
@@ -505,6 +531,19 @@ class ProcessedScan(_lib.Handle):
         rc = fn(self._h, C.byref(scan_matcher_cropper), C.byref(params), C.byref(a), C.byref(b))
         if rc != _lib.OK:
             raise RuntimeError(f"o3s_scan_remove_outliers failed with o3s_status {rc}")
+        self.n_merge, self.n_match = int(a.value), int(b.value)
+        return self.n_merge, self.n_match
+
+    def removeSmallClusters(self, scan_matcher_cropper: CropperC, params):
+        """Small-cluster removal `params` (cloud_ops.dbscan_params) on the merge cloud, in place; the match cloud becomes the
+        scan_matcher_cropper crop of what is left.  Returns (n_merge, n_match).  min_points 0 does nothing."""
+        fn = self._lib.o3s_scan_remove_small_clusters
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(CropperC), C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        a, b = C.c_int64(self.n_merge), C.c_int64(self.n_match)
+        rc = fn(self._h, C.byref(scan_matcher_cropper), C.byref(params), C.byref(a), C.byref(b))
+        if rc != _lib.OK:
+            raise RuntimeError(f"o3s_scan_remove_small_clusters failed with o3s_status {rc}")
         self.n_merge, self.n_match = int(a.value), int(b.value)
         return self.n_merge, self.n_match
 
