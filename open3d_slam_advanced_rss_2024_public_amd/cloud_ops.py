@@ -246,6 +246,126 @@ def remove_small_clusters(points, eps: float, min_points: int, min_cluster_size:
     return op[:m].copy(), (None if on is None else on[:m].copy()), idx[:m].copy(), labels
 
 
+# ---- RANSAC plane segmentation (include/plane_segmentation/o3s_plane_segmentation.h) -----------------------------------------
+PLANE_PASS, PLANE_REPEATED, PLANE_NONFINITE, PLANE_DEGENERATE = 0, 1, 2, 3
+
+
+class PlaneParamsC(C.Structure):   # o3s_plane_params
+    _fields_ = [("distance_threshold", C.c_double), ("confidence", C.c_double), ("seed", C.c_uint64), ("num_iterations", C.c_int32),
+                ("ransac_n", C.c_int32), ("max_planes", C.c_int32), ("min_inliers", C.c_int32)]
+
+
+def plane_params(distance_threshold: float = 0.0, ransac_n: int = 0, num_iterations: int = 0, confidence: float = 0.0, seed: int = 0,
+                 max_planes: int = 0, min_inliers: int = 0) -> PlaneParamsC:
+    """distance_threshold: a point is an inlier iff its distance to the plane is below it; ransac_n: indices per sample (3 .. 8, the
+    first three define the plane); num_iterations: 0 = off (the zeroed struct); confidence: (0, 1], 1 never stops early; max_planes:
+    planes peeled one after another (1 .. 16); min_inliers: a plane with fewer inliers ends the peel."""
+    return PlaneParamsC(float(distance_threshold), float(confidence), int(seed), int(num_iterations), int(ransac_n), int(max_planes),
+                        int(min_inliers))
+
+
+class PlaneResult:
+    """What segment_plane found beside (plane_model, inliers): best_iteration (-1: nothing passed), the final est_k and the number of
+    PASS iterations the serial loop reached."""
+
+    def __init__(self, plane_model, inliers, best_iteration, est_k, evaluated):
+        self.plane_model, self.inliers = plane_model, inliers
+        self.best_iteration, self.est_k, self.evaluated = int(best_iteration), int(est_k), int(evaluated)
+
+    def __iter__(self):   # plane_model, inliers = segment_plane(...)
+        return iter((self.plane_model, self.inliers))
+
+
+def _samples(samples, ransac_n):
+    if samples is None:
+        return None, 0
+    t = np.ascontiguousarray(samples, np.int32).reshape(-1, ransac_n)
+    return t, t.shape[0]
+
+
+def segment_plane(points, distance_threshold: float, ransac_n: int = 3, num_iterations: int = 100, confidence: float = 1.0, seed: int = 0,
+                  samples=None, device: int = 0) -> PlaneResult:
+    """PointCloud::SegmentPlane(distance_threshold, ransac_n, num_iterations) -> (plane_model (4,), inliers (n,) int64 ascending), a
+    PlaneResult that unpacks as that pair.  Reproducible: the samples come from a counter-based stream of `seed` (or from the rows of
+    `samples`), and the result does not depend on how the device batches the hypotheses."""
+    p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    N = p.shape[0]
+    t, nt = _samples(samples, ransac_n)
+    model = np.zeros(4)
+    idx = np.zeros(max(N, 1), np.int64)
+    k, best, est, ev = C.c_int64(0), C.c_int64(-1), C.c_int64(0), C.c_int64(0)
+    lp = C.POINTER(C.c_int64)
+    fn = _L().o3s_segment_plane
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.POINTER(PlaneParamsC), C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_double), lp, lp, lp,
+                   lp, lp]
+    q = plane_params(distance_threshold, ransac_n, num_iterations, confidence, seed, 1, 0)
+    _check(fn(device, C.byref(q), _d(p), N, _i(t), nt, _d(model), idx.ctypes.data_as(lp), C.byref(k), C.byref(best), C.byref(est), C.byref(ev)),
+           "o3s_segment_plane")
+    return PlaneResult(model, idx[:k.value].copy(), best.value, est.value, ev.value)
+
+
+def segment_planes(points, distance_threshold: float, max_planes: int, min_inliers: int = 3, ransac_n: int = 3, num_iterations: int = 100,
+                   confidence: float = 1.0, seed: int = 0, device: int = 0):
+    """Up to max_planes planes peeled one after another, each a segment_plane of what the planes before left ->
+    (labels (N,) int32 with -1 = no plane, models (n_planes, 4), counts (n_planes,) int64)."""
+    p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    N = p.shape[0]
+    labels = np.full(N, -1, np.int32)
+    models = np.zeros((max(int(max_planes), 1), 4))
+    counts = np.zeros(max(int(max_planes), 1), np.int64)
+    k = C.c_int32(0)
+    fn = _L().o3s_segment_planes
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.POINTER(PlaneParamsC), C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                   C.POINTER(C.c_int64)]
+    q = plane_params(distance_threshold, ransac_n, num_iterations, confidence, seed, max_planes, min_inliers)
+    _check(fn(device, C.byref(q), _d(p), N, _i(labels), C.byref(k), _d(models), counts.ctypes.data_as(C.POINTER(C.c_int64))), "o3s_segment_planes")
+    return labels, models[:k.value].copy(), counts[:k.value].copy()
+
+
+def plane_evaluate_samples(points, distance_threshold: float, ransac_n: int = 3, seed: int = 0, samples=None, first_iteration: int = 0,
+                           count: int = None, device: int = 0):
+    """The stages of a segmentation for `count` iterations of the stream from first_iteration, or for the rows of `samples`, nothing
+    selected -> (outcome (count,) int32, planes (count, 4), n_in (count,) int64, err (count,)); zeros where the outcome is not PASS."""
+    p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    t, nt = _samples(samples, ransac_n)
+    H = nt if count is None else int(count)
+    outcome = np.zeros(H, np.int32)
+    planes = np.zeros((H, 4))
+    n_in = np.zeros(H, np.int64)
+    err = np.zeros(H)
+    fn = _L().o3s_plane_evaluate_samples
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.POINTER(PlaneParamsC), C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.POINTER(C.c_int32),
+                   C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    q = plane_params(distance_threshold, ransac_n, max(H, 1), 1.0, seed, 1, 0)
+    _check(fn(device, C.byref(q), _d(p), p.shape[0], _i(t), int(first_iteration), H, _i(outcome), _d(planes), n_in.ctypes.data_as(C.POINTER(C.c_int64)),
+              _d(err)), "o3s_plane_evaluate_samples")
+    return outcome, planes, n_in, err
+
+
+def plane_reserve(max_points: int, num_iterations: int, device: int = 0) -> None:
+    fn = _L().o3s_plane_reserve
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.c_int64, C.c_int32]
+    _check(fn(device, int(max_points), int(num_iterations)), "o3s_plane_reserve")
+
+
+def plane_release(device: int = 0) -> None:
+    fn = _L().o3s_plane_release
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int]
+    _check(fn(device), "o3s_plane_release")
+
+
+def plane_device_bytes(device: int = 0) -> int:
+    fn = _L().o3s_plane_device_bytes
+    fn.restype = C.c_int64
+    fn.argtypes = [C.c_int]
+    return int(fn(device))
+
+
 # ---- the same operators with colours / covariances riding along (include/o3s_cloud_ops.h, *_attr entry points) ----------
 def _attr_call(fn_name, lead_args, points, normals, colors, covariances, want_idx, device):
     p = np.ascontiguousarray(points, np.float64)

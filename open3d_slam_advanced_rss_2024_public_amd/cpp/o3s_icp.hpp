@@ -26,6 +26,7 @@
 #include "localizability/o3s_localizability.h"
 #include "outlier_removal/o3s_outlier_removal.h"
 #include "clustering/o3s_clustering.h"
+#include "plane_segmentation/o3s_plane_segmentation.h"
 
 namespace o3s {
 
@@ -201,6 +202,32 @@ class SubmapHip {
     if (rc != O3S_OK) throw std::runtime_error("o3s_submap_remove_small_clusters failed (status " + std::to_string(rc) + ")");
     return removed;
   }
+  // RANSAC plane segmentation of the sparse map where it lies (plane_segmentation/o3s_plane_segmentation.h): one label per map
+  // point, -1 = no plane; models gets 4 doubles per reported plane, counts (nullable) its inliers; returns the number of planes.
+  // Nothing in the map changes
+  std::int32_t segmentPlanes(const o3s_plane_params& p, std::vector<std::int32_t>& labels, std::vector<double>& models,
+                             std::vector<std::int64_t>* counts = nullptr) {
+    labels.assign(static_cast<std::size_t>(o3s_submap_size(m_)), -1);
+    models.assign(16 * 4, 0.0);
+    std::vector<std::int64_t> c(16, 0);
+    std::int32_t n = 0;
+    const int rc = o3s_submap_segment_planes(m_, &p, labels.data(), &n, models.data(), c.data());
+    if (rc != O3S_OK) throw std::runtime_error("o3s_submap_segment_planes failed (status " + std::to_string(rc) + ")");
+    models.resize(static_cast<std::size_t>(n) * 4);
+    c.resize(static_cast<std::size_t>(n));
+    if (counts) *counts = c;
+    return n;
+  }
+  // ... and every point a reported plane took removed, in place; returns the number of removed points.  models nullable
+  std::int64_t removePlanes(const o3s_plane_params& p, std::vector<double>* models = nullptr) {
+    std::int64_t removed = 0;
+    std::int32_t n = 0;
+    double m[16 * 4] = {0.0};
+    const int rc = o3s_submap_remove_planes(m_, &p, &removed, &n, m);
+    if (rc != O3S_OK) throw std::runtime_error("o3s_submap_remove_planes failed (status " + std::to_string(rc) + ")");
+    if (models) models->assign(m, m + static_cast<std::size_t>(n) * 4);
+    return removed;
+  }
   std::int64_t size() const { return o3s_submap_size(m_); }
   // the two questions the per-scan loop asks about the size, answered without waiting for an insert whose completion is pending
   // (o3s_submap_size_bounds) whenever the bounds decide them
@@ -351,5 +378,36 @@ class DenseMapHip {
   }
   o3s_dense_map* m_ = nullptr;
 };
+
+// RANSAC plane segmentation of host arrays (plane_segmentation/o3s_plane_segmentation.h).  points3xN: std::vector<Eigen::Vector3d>::data()
+// cast to double*.  Open3D's SegmentPlane returns (plane_model, inliers); bestIteration / estK / evaluated are what the search did.
+struct PlaneSegmentation {
+  std::array<double, 4> model{};
+  std::vector<std::int64_t> inliers;
+  std::int64_t bestIteration = -1, estK = 0, evaluated = 0;
+};
+inline PlaneSegmentation segmentPlane(const double* points3xN, std::int64_t N, const o3s_plane_params& p, int device = 0) {
+  PlaneSegmentation r;
+  r.inliers.resize(static_cast<std::size_t>(N > 0 ? N : 1));
+  std::int64_t n = 0;
+  const int rc = o3s_segment_plane(device, &p, points3xN, N, nullptr, 0, r.model.data(), r.inliers.data(), &n, &r.bestIteration, &r.estK, &r.evaluated);
+  if (rc != O3S_OK) throw std::runtime_error("o3s_segment_plane failed (status " + std::to_string(rc) + ")");
+  r.inliers.resize(static_cast<std::size_t>(n));
+  return r;
+}
+// ... and the peel: one label per point (-1 = no plane), 4 doubles per reported plane, counts nullable; returns the number of planes
+inline std::int32_t segmentPlanes(const double* points3xN, std::int64_t N, const o3s_plane_params& p, std::vector<std::int32_t>& labels,
+                                  std::vector<double>& models, std::vector<std::int64_t>* counts = nullptr, int device = 0) {
+  labels.assign(static_cast<std::size_t>(N > 0 ? N : 0), -1);
+  models.assign(16 * 4, 0.0);
+  std::vector<std::int64_t> c(16, 0);
+  std::int32_t n = 0;
+  const int rc = o3s_segment_planes(device, &p, points3xN, N, labels.data(), &n, models.data(), c.data());
+  if (rc != O3S_OK) throw std::runtime_error("o3s_segment_planes failed (status " + std::to_string(rc) + ")");
+  models.resize(static_cast<std::size_t>(n) * 4);
+  c.resize(static_cast<std::size_t>(n));
+  if (counts) *counts = c;
+  return n;
+}
 
 }  // namespace o3s

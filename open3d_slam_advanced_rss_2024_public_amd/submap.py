@@ -373,6 +373,34 @@ class Submap(_lib.Handle):
         self._check(fn(self._h, C.byref(params), C.byref(k), C.byref(nc)), "o3s_submap_remove_small_clusters")
         return int(k.value), int(nc.value)
 
+    def segmentPlanes(self, params):
+        """RANSAC plane segmentation `params` (cloud_ops.plane_params) of the sparse map, where it lies -> (labels (size,) int32 with
+        -1 = no plane, models (n_planes, 4), counts (n_planes,) int64): what cloud_ops.segment_planes returns on the downloaded
+        map.  Nothing in the map changes."""
+        fn = self._lib.o3s_submap_segment_planes
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        n = len(self)   # settles a pending insert: the size the call will see
+        labels = np.full(max(n, 1), -1, np.int32)
+        models, counts = np.zeros((16, 4)), np.zeros(16, np.int64)
+        k = C.c_int32(0)
+        self._check(fn(self._h, C.byref(params), labels.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(k), _d(models),
+                       counts.ctypes.data_as(C.POINTER(C.c_int64))), "o3s_submap_segment_planes")
+        return labels[:n], models[:k.value].copy(), counts[:k.value].copy()
+
+    def removePlanes(self, params):
+        """Every point a plane of `params` (cloud_ops.plane_params) took removed from the sparse map, in place -> (number of removed
+        points, models (n_planes, 4)): bit for bit and in order what is left of the downloaded map without the labelled points;
+        normals and colours follow their points.  Like a carve it leaves the feature set, the voxel-map snapshot and an ICP
+        reference describing the map as it was."""
+        fn = self._lib.o3s_submap_remove_planes
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+        models = np.zeros((16, 4))
+        r, k = C.c_int64(0), C.c_int32(0)
+        self._check(fn(self._h, C.byref(params), C.byref(r), C.byref(k), _d(models)), "o3s_submap_remove_planes")
+        return int(r.value), models[:k.value].copy()
+
     def insertProcessed(self, scan: "ProcessedScan", mapToRangeSensor) -> bool:
         """insertScan(rawScan, *processed.merge_, mapToRangeSensor) (Mapper.cpp:487) from the resident merge cloud."""
         self._check(self._lib.o3s_submap_insert_processed(self._h, scan._h, _d(_pose(mapToRangeSensor))), "o3s_submap_insert_processed")
@@ -546,6 +574,22 @@ class ProcessedScan(_lib.Handle):
             raise RuntimeError(f"o3s_scan_remove_small_clusters failed with o3s_status {rc}")
         self.n_merge, self.n_match = int(a.value), int(b.value)
         return self.n_merge, self.n_match
+
+    def removePlanes(self, scan_matcher_cropper: CropperC, params):
+        """Every point a plane of `params` (cloud_ops.plane_params) took removed from the merge cloud, in place; the match cloud
+        becomes the scan_matcher_cropper crop of what is left.  Returns (n_merge, n_match, models (n_planes, 4)).
+        num_iterations 0 does nothing."""
+        fn = self._lib.o3s_scan_remove_planes
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(CropperC), C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                       C.POINTER(C.c_double)]
+        a, b, k = C.c_int64(self.n_merge), C.c_int64(self.n_match), C.c_int32(0)
+        models = np.zeros((16, 4))
+        rc = fn(self._h, C.byref(scan_matcher_cropper), C.byref(params), C.byref(a), C.byref(b), C.byref(k), _d(models))
+        if rc != _lib.OK:
+            raise RuntimeError(f"o3s_scan_remove_planes failed with o3s_status {rc}")
+        self.n_merge, self.n_match = int(a.value), int(b.value)
+        return self.n_merge, self.n_match, models[:k.value].copy()
 
     def _get(self, which):
         n = int(self._lib.o3s_scan_get(self._h, which, None, None))
