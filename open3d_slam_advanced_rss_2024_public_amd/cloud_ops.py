@@ -246,6 +246,46 @@ def remove_small_clusters(points, eps: float, min_points: int, min_cluster_size:
     return op[:m].copy(), (None if on is None else on[:m].copy()), idx[:m].copy(), labels
 
 
+# ---- ISS keypoints (include/keypoints/o3s_keypoints.h) -------------------------------------------------------------------------
+class IssParamsC(C.Structure):   # o3s_iss_params
+    _fields_ = [("salient_radius", C.c_double), ("non_max_radius", C.c_double), ("gamma_21", C.c_double), ("gamma_32", C.c_double),
+                ("min_neighbors", C.c_int32), ("reserved", C.c_int32)]
+
+
+def iss_params(salient_radius: float = 0.0, non_max_radius: float = 0.0, gamma_21: float = 0.0, gamma_32: float = 0.0,
+               min_neighbors: int = 0) -> IssParamsC:
+    """salient_radius / non_max_radius: 0 = six / four times the cloud's resolution; gamma_21 / gamma_32: the bounds on the
+    eigenvalue ratios (Open3D: 0.975); min_neighbors: neighbours, itself included, below which a point has no saliency (Open3D: 5;
+    0 = off, the zeroed struct)"""
+    return IssParamsC(float(salient_radius), float(non_max_radius), float(gamma_21), float(gamma_32), int(min_neighbors), 0)
+
+
+def compute_iss_keypoints(points, salient_radius: float = 0.0, non_max_radius: float = 0.0, gamma_21: float = 0.975, gamma_32: float = 0.975,
+                          min_neighbors: int = 5, normals=None, device: int = 0):
+    """geometry::keypoint::ComputeISSKeypoints -> (points, normals | None, indices, saliency (N,) of the INPUT points, radii =
+    [salient, non_max] as used).  Keypoints come as ascending input indices; normals ride along."""
+    p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    n = None if normals is None else np.ascontiguousarray(normals, np.float64).reshape(-1, 3)
+    if n is not None and n.shape != p.shape:
+        raise ValueError("points and normals differ in shape")
+    N = p.shape[0]
+    op = np.zeros_like(p)
+    on = np.zeros_like(p) if n is not None else None
+    idx = np.zeros(N, np.int64)
+    sal = np.zeros(N, np.float64)
+    radii = np.zeros(2, np.float64)
+    k = C.c_int64()
+    fn = _L().o3s_iss_keypoints
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.POINTER(IssParamsC), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double),
+                   C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    q = iss_params(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors)
+    _check(fn(device, C.byref(q), _d(p), _d(n), N, _d(op), _d(on), idx.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(k), _d(sal), _d(radii)),
+           "o3s_iss_keypoints")
+    m = k.value
+    return op[:m].copy(), (None if on is None else on[:m].copy()), idx[:m].copy(), sal, radii
+
+
 # ---- RANSAC plane segmentation (include/plane_segmentation/o3s_plane_segmentation.h) -----------------------------------------
 PLANE_PASS, PLANE_REPEATED, PLANE_NONFINITE, PLANE_DEGENERATE = 0, 1, 2, 3
 

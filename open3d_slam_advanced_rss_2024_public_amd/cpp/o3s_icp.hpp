@@ -27,6 +27,7 @@
 #include "outlier_removal/o3s_outlier_removal.h"
 #include "clustering/o3s_clustering.h"
 #include "plane_segmentation/o3s_plane_segmentation.h"
+#include "keypoints/o3s_keypoints.h"
 
 namespace o3s {
 
@@ -201,6 +202,33 @@ class SubmapHip {
     const int rc = o3s_submap_remove_small_clusters(m_, &p, &removed, nClusters);
     if (rc != O3S_OK) throw std::runtime_error("o3s_submap_remove_small_clusters failed (status " + std::to_string(rc) + ")");
     return removed;
+  }
+  // ISS keypoints of the resident SPARSE cloud (keypoints/o3s_keypoints.h; o3s_submap_compute_features must have run), then the
+  // feature set — sparse points, normals, FPFH columns — reduced to them, in order: correspondences, RANSAC and place recognition
+  // then search the keypoints alone.  indices (nullable): which sparse points stayed; radii2 (nullable): the radii used.  Returns
+  // the number of keypoints (the feature set's size when p.min_neighbors is 0: nothing happens then)
+  std::int64_t selectKeypoints(const o3s_iss_params& p, std::vector<std::int64_t>* indices = nullptr, double* radii2 = nullptr) {
+    const std::int64_t before = o3s_submap_features_size(m_);
+    std::int64_t n = before > 0 ? before : 0;
+    std::vector<std::int64_t> idx(static_cast<std::size_t>(n));
+    for (std::size_t k = 0; k < idx.size(); ++k) idx[k] = static_cast<std::int64_t>(k);
+    const int rc = o3s_submap_select_keypoints(m_, &p, idx.data(), &n, radii2);
+    if (rc != O3S_OK) throw std::runtime_error("o3s_submap_select_keypoints failed (status " + std::to_string(rc) + ")");
+    idx.resize(static_cast<std::size_t>(n));
+    if (indices) *indices = idx;
+    return n;
+  }
+  // ... labels only: one flag (1 = keypoint) and one saliency per sparse point; nothing in the submap changes.  saliency, radii2
+  // nullable; returns the number of keypoints
+  std::int64_t featureKeypoints(const o3s_iss_params& p, std::vector<std::int32_t>& flags, std::vector<double>* saliency = nullptr, double* radii2 = nullptr) {
+    const std::int64_t nf = o3s_submap_features_size(m_);
+    flags.assign(static_cast<std::size_t>(nf > 0 ? nf : 0), 0);
+    std::vector<double> sal(flags.size(), 0.0);
+    std::int64_t n = 0;
+    const int rc = o3s_submap_feature_keypoints(m_, &p, flags.data(), sal.data(), &n, radii2);
+    if (rc != O3S_OK) throw std::runtime_error("o3s_submap_feature_keypoints failed (status " + std::to_string(rc) + ")");
+    if (saliency) *saliency = sal;
+    return n;
   }
   // RANSAC plane segmentation of the sparse map where it lies (plane_segmentation/o3s_plane_segmentation.h): one label per map
   // point, -1 = no plane; models gets 4 doubles per reported plane, counts (nullable) its inliers; returns the number of planes.
@@ -408,6 +436,27 @@ inline std::int32_t segmentPlanes(const double* points3xN, std::int64_t N, const
   c.resize(static_cast<std::size_t>(n));
   if (counts) *counts = c;
   return n;
+}
+
+// ISS keypoints of host arrays (keypoints/o3s_keypoints.h; Open3D's geometry::keypoint::ComputeISSKeypoints).  indices: the
+// keypoints as ascending input indices; saliency: one value per INPUT point; radii: the salient and the non-max radius used.
+struct IssKeypoints {
+  std::vector<std::int64_t> indices;
+  std::vector<double> points, saliency;  // 3 x indices.size(); N
+  std::array<double, 2> radii{};
+};
+inline IssKeypoints computeIssKeypoints(const double* points3xN, std::int64_t N, const o3s_iss_params& p, int device = 0) {
+  IssKeypoints r;
+  const std::size_t n0 = static_cast<std::size_t>(N > 0 ? N : 0);
+  r.indices.resize(n0);
+  r.points.resize(3 * n0);
+  r.saliency.assign(n0, 0.0);
+  std::int64_t n = 0;
+  const int rc = o3s_iss_keypoints(device, &p, points3xN, nullptr, N, r.points.data(), nullptr, r.indices.data(), &n, r.saliency.data(), r.radii.data());
+  if (rc != O3S_OK) throw std::runtime_error("o3s_iss_keypoints failed (status " + std::to_string(rc) + ")");
+  r.indices.resize(static_cast<std::size_t>(n));
+  r.points.resize(3 * static_cast<std::size_t>(n));
+  return r;
 }
 
 }  // namespace o3s

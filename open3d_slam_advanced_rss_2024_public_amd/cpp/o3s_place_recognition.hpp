@@ -49,6 +49,9 @@ struct PlaceRecognitionParams {  // PLACE_RECOGNITION_PARAMETERS (param/default/
   std::int32_t registrationType = O3S_O3D_GENERALIZED;  // scan_to_map_refinement_type
   double gicpEpsilon = 1e-3;
   std::int32_t maxIcpIterations = 30;
+  // not the reference's: match at ISS keypoints only (keypoints/o3s_keypoints.h).  min_neighbors 0, the zeroed struct = off: every
+  // sparse point is matched.  PlaceRecognitionHip::computeFeatures hands it to the collection, nothing else reads it
+  o3s_iss_params featureKeypoints{0.0, 0.0, 0.0, 0.0, 0, 0};
   static o3s_ransac_params defaultRansac() {
     o3s_ransac_params p;
     o3s_ransac_default_params(&p);
@@ -126,6 +129,12 @@ class PlaceRecognitionHip {
   const PlaceRecognitionParams& params() const { return params_; }
   void setParams(const PlaceRecognitionParams& p) { params_ = p; }
   bool isRegistrationConsistent(const Mat4& T) const { return o3s::isRegistrationConsistent(T, params_.consistencyCheck); }
+  // collection.computeFeatures(...) with this object's featureKeypoints: the one place where the keypoint selection is switched
+  // on for everything buildLoopClosureConstraints later searches
+  template <class Collection, class Finished>
+  void computeFeatures(Collection& collection, const Finished& finished, const o3s_submap_feature_params* params = nullptr) {
+    collection.computeFeatures(finished, params, params_.featureKeypoints.min_neighbors != 0 ? &params_.featureKeypoints : nullptr);
+  }
   const std::vector<Candidate>& lastCandidates() const { return last_; }
 
   // (mapToRangeSensor is not used by the reference either: its distance test is commented out, :259)

@@ -205,12 +205,15 @@ class SubmapCollectionHip {
   std::size_t numSubmaps() const { return submaps_.size(); }
   std::size_t activeSubmapIdx() const { return activeIdx_; }
   SubmapHip& activeSubmap() { return *submaps_[activeIdx_].map; }
-  // Submap::computeFeatures of submap `idx` (sparse cloud, normals, FPFH stay resident in it); returns the number of sparse points
-  std::int64_t computeFeatures(std::size_t idx, const o3s_submap_feature_params* params = nullptr) {
+  // Submap::computeFeatures of submap `idx` (sparse cloud, normals, FPFH stay resident in it); returns the number of sparse points.
+  // keypoints (nullable = off): ISS keypoint selection right behind the features (SubmapHip::selectKeypoints) — the feature set
+  // place recognition searches is then the keypoints' alone, and the number returned is theirs
+  std::int64_t computeFeatures(std::size_t idx, const o3s_submap_feature_params* params = nullptr, const o3s_iss_params* keypoints = nullptr) {
     o3s_submap_feature_params p;
     o3s_submap_feature_params_default(&p);
     if (params) p = *params;
     if (o3s_submap_compute_features(submaps_.at(idx).map->handle(), &p) != O3S_OK) throw std::runtime_error("o3s_submap_compute_features failed");
+    if (keypoints) submaps_.at(idx).map->selectKeypoints(*keypoints);
     if (voxel_ > 0.0) submaps_.at(idx).map->buildVoxelMap(kVoxelExpansionFactorAdjacencyBasedRevisiting * voxel_);  // Submap.cpp:260-264
     return o3s_submap_features_size(submaps_.at(idx).map->handle());
   }
@@ -218,9 +221,10 @@ class SubmapCollectionHip {
   // loop-closure candidates, and the odometry constraints of the finished submaps into the collection's own list (one device call:
   // o3s_constraint_builders.hpp).  The reference runs the features on a second thread; here the two steps run one after the other on
   // the caller (both settle and use the streams of the same submaps).
-  void computeFeatures(const std::vector<std::pair<std::size_t, double>>& finishedSubmapIds, const o3s_submap_feature_params* params = nullptr) {
+  void computeFeatures(const std::vector<std::pair<std::size_t, double>>& finishedSubmapIds, const o3s_submap_feature_params* params = nullptr,
+                       const o3s_iss_params* keypoints = nullptr) {
     for (const auto& id : finishedSubmapIds) {
-      computeFeatures(id.first, params);
+      computeFeatures(id.first, params, keypoints);
       loopClosureCandidates_.push_back(id);
     }
     computeOdometryConstraints(*this, finishedSubmapIds, &odometryConstraints_);

@@ -307,6 +307,7 @@ int o3s_undistort_cloud_trajectory(int device, const o3s_stamped_pose* poses, in
 #include "outlier_impl.h"  // (includes outlier_dev.h, the kernels)
 #include "cluster_impl.h"  // (includes cluster_dev.h, the kernels)
 #include "plane_impl.h"    // (includes plane_dev.h, the kernels)
+#include "keypoints_impl.h"  // (includes keypoints_dev.h, the kernels)
 
 #ifdef O3S_TEST_HOOKS
 // hooks build only (tools/trajectory_deskew_bench.py): the host's share of one trajectory de-skew — A, C^-1, the extrapolation and

@@ -119,7 +119,9 @@ class PlaceRecognitionParameters:
     """PlaceRecognitionParameters with the defaults of PLACE_RECOGNITION_PARAMETERS.  overlap_voxel_size is
     magic::voxelExpansionFactorOverlapComputation x the map voxel size — the caller's, required by buildLoopClosureConstraints;
     registration_type / gicp_epsilon / max_icp_iterations describe the refinement (scan_to_map_refinement_type, GeneralizedIcp in the
-    reference's parameter sets; icpRunUntilConvergenceNumberOfIterations is the caller's to raise)."""
+    reference's parameter sets; icpRunUntilConvergenceNumberOfIterations is the caller's to raise).  feature_keypoints is not the
+    reference's: PlaceRecognition.computeFeatures hands it to the collection, which then reduces every finished submap's feature
+    set to its ISS keypoints."""
     loop_closure_search_radius: float = 20.0
     min_submaps_between_loop_closures: int = 2
     ransac: reg.RansacParams = field(default_factory=reg.RansacParams)
@@ -132,6 +134,7 @@ class PlaceRecognitionParameters:
     registration_type: str = "GeneralizedIcp"
     gicp_epsilon: float = 1e-3
     max_icp_iterations: int = 30
+    feature_keypoints: object = None   # cloud_ops.iss_params: match at ISS keypoints only (None = off: every sparse point)
 
 
 # ---- host policy ---------------------------------------------------------------------------------------------------------------
@@ -235,6 +238,11 @@ class PlaceRecognition:
 
     def isRegistrationConsistent(self, T) -> bool:
         return is_registration_consistent(T, self.params.consistency_check)
+
+    def computeFeatures(self, collection, finished, params=None):
+        """collection.computeFeatures(finished, params) with this object's feature_keypoints: the one place where the keypoint
+        selection is switched on for everything buildLoopClosureConstraints later searches."""
+        return collection.computeFeatures(finished, params, keypoints=self.params.feature_keypoints)
 
     def getLoopClosureCandidatesIdxs(self, mapToRangeSensor, collection, lastFinishedSubmapIdx, activeSubmapIdx):
         # (mapToRangeSensor is not used by the reference either: its distance test was commented out, :259)

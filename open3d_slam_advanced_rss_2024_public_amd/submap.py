@@ -373,6 +373,37 @@ class Submap(_lib.Handle):
         self._check(fn(self._h, C.byref(params), C.byref(k), C.byref(nc)), "o3s_submap_remove_small_clusters")
         return int(k.value), int(nc.value)
 
+    def selectKeypoints(self, params):
+        """ISS keypoints `params` (cloud_ops.iss_params) of the resident SPARSE cloud; the feature set — sparse points, normals, FPFH
+        columns — is then reduced to them, in order -> (indices of the sparse points that stayed, radii = [salient, non_max] as
+        used).  Correspondences, RANSAC, place recognition, clone, hand_over, trim and transform work on the reduced set; the next
+        computeFeatures rebuilds the full one.  With min_neighbors 0 nothing happens and every index stays."""
+        fn = self._lib.o3s_submap_select_keypoints
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+        n = self.features_size()   # -1 without a feature set: the call then fails with O3S_ERR_NOT_INITIALIZED
+        idx = np.arange(max(n, 1), dtype=np.int64)
+        k = C.c_int64(max(n, 0))
+        radii = np.zeros(2, np.float64)
+        self._check(fn(self._h, C.byref(params), idx.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(k), _d(radii)), "o3s_submap_select_keypoints")
+        return idx[:k.value].copy(), radii
+
+    def featureKeypoints(self, params):
+        """ISS keypoints `params` (cloud_ops.iss_params) of the resident SPARSE cloud, labels only -> (flags (features_size,) int32
+        with 1 = keypoint, saliency (features_size,), radii): what cloud_ops.compute_iss_keypoints returns on the downloaded sparse
+        cloud.  Nothing in the submap changes."""
+        fn = self._lib.o3s_submap_feature_keypoints
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+        n = max(self.features_size(), 0)   # without a feature set the call fails with O3S_ERR_NOT_INITIALIZED
+        flags = np.zeros(max(n, 1), np.int32)
+        sal = np.zeros(max(n, 1), np.float64)
+        k = C.c_int64(0)
+        radii = np.zeros(2, np.float64)
+        self._check(fn(self._h, C.byref(params), flags.ctypes.data_as(C.POINTER(C.c_int32)), _d(sal), C.byref(k), _d(radii)),
+                    "o3s_submap_feature_keypoints")
+        return flags[:n], sal[:n], radii
+
     def segmentPlanes(self, params):
         """RANSAC plane segmentation `params` (cloud_ops.plane_params) of the sparse map, where it lies -> (labels (size,) int32 with
         -1 = no plane, models (n_planes, 4), counts (n_planes,) int64): what cloud_ops.segment_planes returns on the downloaded

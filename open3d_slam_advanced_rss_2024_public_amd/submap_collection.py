@@ -115,25 +115,30 @@ class SubmapCollection:
             distance += 1
         return max(0, distance - 1)
 
-    def computeFeatures(self, i, params=None):
+    def computeFeatures(self, i, params=None, keypoints=None):
         """Submap::computeFeatures of submap i (Submap.cpp:255-275): the feature set and, with it, the occupancy snapshot voxelMap_ at
         2.5 x the map voxel size (:239-240, :260-264).  Returns the number of sparse points.
         With a list of finished (submap id, time stamp) instead of an index: SubmapCollection::computeFeatures(finishedSubmapIds)
         (SubmapCollection.cpp:257-281) — the features of every finished submap, each pushed to the loop-closure candidates, and the
         odometry constraints of the finished submaps into the collection's own list (one device call).  The reference runs the
         features on a second thread; here the two steps run one after the other on the caller (both settle and use the streams of
-        the same submaps).  Returns the list of sparse-point counts."""
+        the same submaps).  Returns the list of sparse-point counts.
+        keypoints (cloud_ops.iss_params; None = off): ISS keypoint selection right behind the features of each submap
+        (Submap.selectKeypoints) — the feature set that place recognition searches is then the keypoints' alone, and the count
+        returned is theirs."""
         if not isinstance(i, (int, np.integer)):
             from .constraint_builders import compute_odometry_constraints
 
             finished = [(int(f[0]), f[1]) for f in i]
             counts = []
             for f in finished:
-                counts.append(self.computeFeatures(f[0], params))
+                counts.append(self.computeFeatures(f[0], params, keypoints))
                 self.loop_closure_candidates.append(f)
             compute_odometry_constraints(self, self.odometry_constraints, finished, self._odometry_call, self._refine_call)
             return counts
         n = self.maps[i].computeFeatures(params)
+        if keypoints is not None:
+            n = len(self.maps[i].selectKeypoints(keypoints)[0])
         if self.map_voxel > 0.0:
             self.maps[i].buildVoxelMap(VOXEL_EXPANSION_FACTOR_ADJACENCY_BASED_REVISITING * self.map_voxel)
         return n
