@@ -98,6 +98,12 @@ int pick_device(int device) {
 struct PinnedArea {
   uint32_t* p = nullptr;        // 4 KB landing area for small device-to-host copies
   PostBlock<> mb;               // mailbox a kernel writes directly (host_post.h): 32 words, the last 8 the lazy slot (kLazySlot)
+  // The lazy slot's outstanding post (lazy_post_open).  It is kept with the SLOT, not with the thread: a thread may end with its
+  // last lazy post still in flight, and the area — slot included — is then leased by the next thread that asks.  Only the
+  // thread that holds the lease touches these; LeasePool's mutex orders one holder's writes before the next one's reads.
+  bool lazy_busy = false;
+  uint32_t lazy_seq = 0;
+  hipStream_t lazy_stream = nullptr;
   PinnedArea() {
     if (hipHostMalloc(reinterpret_cast<void**>(&p), 4096, hipHostMallocPortable) != hipSuccess) p = nullptr;
     (void)mb.alloc(128);
@@ -617,30 +623,24 @@ struct LazyPost {
   uint32_t seq = 0;
   hipStream_t stream = nullptr;
 };
-// One post per slot at a time: a thread that opens a second lazy post while its first has not landed yet (pending inserts on two submaps,
-// never the per-scan loop) waits for the first one here, so that a reader never sees the values of one post under the sequence number of
-// another.  The wait ends with the post or with its stream drained (or gone).
-struct LazySlotGuard {
-  bool busy = false;
-  uint32_t seq = 0;
-  hipStream_t stream = nullptr;
-};
-inline LazySlotGuard& lazy_slot_guard() {
-  static thread_local LazySlotGuard g;
-  return g;
-}
+// One post per slot at a time: whoever opens a second lazy post in a slot while the first has not landed yet (pending inserts on two
+// submaps, never the per-scan loop) waits for the first one here, so that a reader never sees the values of one post under the sequence
+// number of another.  The wait ends with the post or with its stream drained (or gone).  "Whoever" is the slot's holder, which need not
+// be the thread that issued the first post: a thread that ended with its post in flight has handed the area back, and the next thread
+// to lease it finds the outstanding post recorded in the area (PinnedArea::lazy_*) — a record kept per thread would let that thread
+// launch a second writer into the slot on another stream, and the seqlock of host_post.h holds for one writer only (two tails
+// interleaved: 0, 0, values of both, one number — a reader accepts the mix).
 inline bool lazy_post_open(PinnedArea& pa, uint32_t* dev_out, hipStream_t s, LazyPost* lp) {
   if (!mailbox_enabled(pa) || !dev_out) return false;
-  LazySlotGuard& g = lazy_slot_guard();
-  if (g.busy) (void)mailbox_wait(pa.mb.host + kLazySlot, g.seq, g.stream);  // landed, drained or gone
+  if (pa.lazy_busy) (void)mailbox_wait(pa.mb.host + kLazySlot, pa.lazy_seq, pa.lazy_stream);  // landed, drained or gone
   lp->mb_host = pa.mb.host + kLazySlot;
   lp->mb_dev = pa.mb.dev + kLazySlot;
   lp->dev_out = dev_out;
   lp->seq = pa.mb.next();
   lp->stream = s;
-  g.busy = true;
-  g.seq = lp->seq;
-  g.stream = s;
+  pa.lazy_busy = true;
+  pa.lazy_seq = lp->seq;
+  pa.lazy_stream = s;
   return true;
 }
 // the four words of a lazy post; waits for them if they are not there yet
