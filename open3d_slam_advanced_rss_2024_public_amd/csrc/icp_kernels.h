@@ -933,24 +933,23 @@ __device__ __forceinline__ void match_search(const int i, const int sub, const b
                                              unsigned long long& n_cand, unsigned long long& n_rows O3S_DBG_PARAM);
 
 constexpr int kFrontWaves = 4;  // waves per SIMD the settle front is compiled for: it has half / a quarter of the waves, and the list's loop keeps more alive
-// the kernel's parameters, shared by its two entry points below (the launch without the front keeps its six template arguments
+// the kernel's parameters, shared by its two entry points below: what the first round trip needs stands first, inside the 14 dwords
+// that arrive preloaded in SGPRs, the by-value grid last (a struct ends the preloaded run) (the launch without the front keeps its six template arguments
 // and so its symbol, which the trace tools and tools/isa_round_trips.py know it by; the front is the overload with a seventh)
 #define O3S_MATCH2_PARAMS                                                                                                          \
-  const float *__restrict__ rx, const float *__restrict__ ry, const float *__restrict__ rz, int N, const float4 *__restrict__ ref,  \
-      const uint32_t *__restrict__ cell_start, GridParams g, IcpState *__restrict__ st, int32_t *__restrict__ pos_out,               \
-      float *__restrict__ d2_out, float4 *__restrict__ mq, uint32_t *__restrict__ hist_rep,                                          \
-      const float4 *__restrict__ refn /*reference normals in slot order (nullable)*/,                                               \
-      float4 *__restrict__ mn /*out (nullable): the matched normal of every query*/, const float *__restrict__ rnx,                  \
-      const float *__restrict__ rny, const float *__restrict__ rnz /*FAR: the reading's normals (nullable): the seed probe's direction*/, \
-      int rep_mask /*level-1 replicas - 1 (15; fewer in the sharded mode, where they travel)*/,                                     \
-      uint32_t *__restrict__ spec /*nullable: speculative digit histograms [kSpecWords]*/,                                          \
-      float *__restrict__ cert /*CERT: the queries' certificates [N], read and rewritten; else null*/                               \
+  const float *__restrict__ r /*the reading: x, y, z, N floats each*/, IcpState *__restrict__ st, float4 *__restrict__ mq,          \
+      float *__restrict__ cert /*CERT: the queries' certificates [N], read and rewritten; else null*/,                              \
+      int32_t *__restrict__ pos_out, int N, int rep_mask /*level-1 replicas - 1 (15; fewer in the sharded mode, where they travel)*/, \
+      const float4 *__restrict__ ref, const uint32_t *__restrict__ cell_start, float *__restrict__ d2_out,                          \
+      uint32_t *__restrict__ hist_rep, const float4 *__restrict__ refn /*reference normals in slot order (nullable)*/,              \
+      float4 *__restrict__ mn /*out (nullable): the matched normal of every query*/,                                                \
+      const float *__restrict__ rn /*FAR: the reading's normals x, y, z, N floats each (nullable): the seed probe's direction*/,     \
+      uint32_t *__restrict__ spec /*nullable: speculative digit histograms [kSpecWords]*/, GridParams g                             \
       O3S_DBG_PARAM /*hooks build only: timing experiments (o3s_icp_profile_match)*/                                                \
       O3S_HOOK_PARAM(uint32_t *__restrict__ settled_cnt /*nullable: [kHistReplicas][2][kSpecTrace] per iteration: queries whose      \
                      certificate held, queries of the waves in which every valid query settled*/)
 #define O3S_MATCH2_ARGS                                                                                                             \
-  rx, ry, rz, N, ref, cell_start, g, st, pos_out, d2_out, mq, hist_rep, refn, mn, rnx, rny, rnz, rep_mask, spec, cert O3S_DBG_ARG(dbg) \
-      O3S_DBG_ARG(settled_cnt)
+  r, st, mq, cert, pos_out, N, rep_mask, ref, cell_start, d2_out, hist_rep, refn, mn, rn, spec, g O3S_DBG_ARG(dbg) O3S_DBG_ARG(settled_cnt)
 template <bool STATS, int G, int UN, int RCB, bool FAR, bool CERT, bool FRONT>
 __device__ __forceinline__ void match2_body(O3S_MATCH2_PARAMS);
 template <bool STATS, int G, int UN, int RCB, bool FAR, bool CERT>
@@ -963,6 +962,8 @@ __global__ void __launch_bounds__(kBlock, FRONT ? kFrontWaves : FAR ? kFarWaves 
 }
 template <bool STATS, int G, int UN, int RCB, bool FAR, bool CERT, bool FRONT>
 __device__ __forceinline__ void match2_body(O3S_MATCH2_PARAMS) {
+  const float *const rx = r, *const ry = r + (size_t)N, *const rz = r + 2 * (size_t)N;
+  const float *const rnx = rn, *const rny = rn ? rn + (size_t)N : nullptr, *const rnz = rn ? rn + 2 * (size_t)N : nullptr;
   __shared__ uint32_t s_hist[kHistBins];
   __shared__ uint32_t s_cnt[2];  // the block's bin counters {F, Bl}: one LDS add per wave, one global atomic per block and counter
   if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0u;
@@ -980,7 +981,9 @@ __device__ __forceinline__ void match2_body(O3S_MATCH2_PARAMS) {
   const int sub = threadIdx.x & (GA - 1);
   const int qib = threadIdx.x / GA;
   // XCD-aware: gridDim.x is a multiple of 8; blocks b, b + 8, ... (one XCD) walk a contiguous range of the sorted reading
-  const int tile = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  // (gridDim.x >> 3 formed from N as launch_match2 sizes the grid — round_up8 of one block per tile: gridDim itself is a hidden kernel
+  // argument that has to be fetched, and the query's index, hence every address of the first round trip, would wait for it)
+  const int tile = (blockIdx.x & 7) * ((((N + TQ - 1) / TQ) + 7) >> 3) + (blockIdx.x >> 3);
   const int i = tile * TQ + qib;
   const bool valid = i < N;
   // the state header, the query and its incumbent travel in the same round trip
@@ -1659,26 +1662,36 @@ constexpr int kFinThreads = 512;    // k_sel_finish: fewer waves per barrier, tw
 constexpr int kFinPerSmall = 4, kFinPerBig = 8;  // candidate records in flight per thread and batch of the selection sweep (<= 2 048 candidates: one batch of 4)
 constexpr int kSelCap = 32768;   // candidates resolved in LDS; larger bins are resolved in global memory
 
-enum { kModeCentroid = 1, kModeGate = 2, kModeNormalReady = 4 /*k_match2 has already written the matched normals (mn)*/ };
+enum {
+  kModeCentroid = 1,
+  kModeGate = 2 /*the chain has a SurfaceNormalOutlierFilter (ChainParams::has_normal_gate; the caller folds it in here because `mode` arrives
+                   preloaded in an SGPR and k_classify's first round trip depends on it)*/,
+  kModeNormalReady = 4 /*k_match2 has already written the matched normals (mn)*/
+};
 constexpr int kClsBlock = 512;  // threads (= points) per k_classify block: halves the blocks that each re-sum the histogram replicas
 
-__global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz,
-                                                     const float* __restrict__ rnx, const float* __restrict__ rny, const float* __restrict__ rnz,
-                                                     int N, const float4* __restrict__ ref, const float4* __restrict__ refn,
-                                                     int32_t* __restrict__ pos, const float* __restrict__ d2,
-                                                     const uint32_t* __restrict__ hist_rep, ChainParams cp, IcpState* __restrict__ st,
+// Parameters: what the first round trip reads through stands first — r .. mode are the 14 dwords that arrive preloaded in SGPRs — and
+// the by-value ChainParams last (a struct ends the preloaded run).
+__global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict__ r /*the reading: x, y, z and its normals' x, y, z, N floats each*/,
+                                                     IcpState* __restrict__ st, int32_t* __restrict__ pos, const float* __restrict__ d2,
+                                                     const float4* __restrict__ mq /*matched point of every query (k_match2 / k_import_matches)*/,
+                                                     const uint32_t* __restrict__ spec /*k_match2's speculative digit histograms and
+                                                     bin counters [kSpecWords] (+ the hooks build's depth trace); null: level 1 only*/,
+                                                     int N, int mode,
+                                                     float4* __restrict__ mn /*out: matched normal, streamed by k_normal_eq*/,
+                                                     const float4* __restrict__ ref, const float4* __restrict__ refn,
+                                                     const uint32_t* __restrict__ hist_rep,
                                                      SelScratch* __restrict__ ss, CandRec* __restrict__ cand /*[grid][kClsBlock]*/,
                                                      uint32_t* __restrict__ cand_cnt /*[grid]*/, uint32_t* __restrict__ hist2 /*[1024]*/,
-                                                     const float4* __restrict__ mq /*matched point of every query (k_match2 / k_import_matches)*/,
-                                                     float4* __restrict__ mn /*out: matched normal, streamed by k_normal_eq*/,
-                                                     double* __restrict__ part /*[7][grid]*/, int mode,
+                                                     double* __restrict__ part /*[7][grid]*/,
                                                      int n_rep /*level-1 replicas to sum: kHistReplicas; fewer in the sharded mode, where they travel*/,
-                                                     int l2_shift = 10, uint32_t l2_mask = 1023u /*the level-2 digit: bits 19..10; the sharded chain takes
+                                                     int l2_shift, uint32_t l2_mask /*the level-2 digit: 10, 1023 (bits 19..10); the sharded chain takes
                                                      thirteen bits (shift 7, mask 8191: csrc/icp_shard_kernels.h)*/,
-                                                     const uint32_t* __restrict__ spec = nullptr /*k_match2's speculative digit histograms and
-                                                     bin counters [kSpecWords] (+ the hooks build's depth trace); null: level 1 only*/,
-                                                     float max_r2 = kInfF /*the matcher's maxDist^2: no match lies in a level-1 bin above its own*/
+                                                     float max_r2 /*the matcher's maxDist^2: no match lies in a level-1 bin above its own (kInfF: none)*/,
+                                                     ChainParams cp
                                                      O3S_HOOK_PARAM(int no_bin_counters = 0 /*hooks build: always sum the replicas*/)) {
+  const float *const rx = r, *const ry = r + (size_t)N, *const rz = r + 2 * (size_t)N;
+  const float *const rnx = r + 3 * (size_t)N, *const rny = r + 4 * (size_t)N, *const rnz = r + 5 * (size_t)N;
   __shared__ uint32_t s_sc[48 + 2];
   __shared__ uint32_t s_res[8];
   __shared__ uint32_t s_wcnt[kClsBlock / 64];
@@ -1697,7 +1710,7 @@ __global__ void __launch_bounds__(kClsBlock) k_classify(const float* __restrict_
   const float4 q = inb ? mq[i] : make_float4(0.f, 0.f, 0.f, 0.f);  // the matched point arrives with the query: no gather
   const bool nready = (mode & kModeNormalReady) != 0;               // ... and so does its normal when the matcher wrote it
   const float4 rn_in = (nready && inb) ? mn[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-  const bool gate = (mode & kModeGate) && cp.has_normal_gate;
+  const bool gate = (mode & kModeGate) != 0;
   float a0 = 0.f, b0 = 0.f, c0 = 0.f;
   if (gate && inb) {
     a0 = rnx[i];
@@ -2523,13 +2536,15 @@ __device__ __forceinline__ bool sel_finish_body(uint32_t* __restrict__ hist_rep,
   return go_on;
 }
 
-__global__ void __launch_bounds__(kFinThreads) k_sel_finish(uint32_t* __restrict__ hist_rep, ChainParams cp, IcpState* __restrict__ st,
-                                                            SelScratch* __restrict__ ss, const CandRec* __restrict__ cand,
+// (parameters: hist_rep .. mode are the 14 dwords that arrive preloaded in SGPRs, everything the first round trip reads through; the
+// by-value ChainParams stands last)
+__global__ void __launch_bounds__(kFinThreads) k_sel_finish(uint32_t* __restrict__ hist_rep, IcpState* __restrict__ st, SelScratch* __restrict__ ss,
                                                             const uint32_t* __restrict__ cand_cnt, const uint32_t* __restrict__ hist2,
-                                                            uint32_t* __restrict__ base_scratch /*[nb + 1], used when nb > kBaseCap*/,
                                                             const double* __restrict__ part /*[7][nb]*/, int nb, int mode,
+                                                            uint32_t* __restrict__ base_scratch /*[nb + 1], used when nb > kBaseCap*/,
+                                                            const CandRec* __restrict__ cand,
                                                             const double* __restrict__ part2 /*nullable: [7][nbp] of k_sel_partial*/, int nbp,
-                                                            const CandRec* __restrict__ park_rec, const uint32_t* __restrict__ park_key) {
+                                                            const CandRec* __restrict__ park_rec, const uint32_t* __restrict__ park_key, ChainParams cp) {
   __shared__ float s_out[8];
   const float hv = hdr_load(st);
   (void)sel_finish_body<false>(hist_rep, cp, st, ss, cand, cand_cnt, hist2, base_scratch, part, nb, mode, hv, s_out, part2, nbp, park_rec, park_key,
@@ -2550,11 +2565,13 @@ __device__ __forceinline__ bool kept_pair(int pe, float d, float limit, float ma
 
 // k_normal_eq — formulatePointMatchingConstraints (PointToPlane.cpp:108-156): G = [(p-mp) x n ; n], h = n.((p-mp)-(q-mq)),
 // A = G G^T, b = -(G h^T).  Per-pair arithmetic is fp32 in the reference's order; the K-long sums are fp64.
-__global__ void __launch_bounds__(kBlock) k_normal_eq(const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz, int N,
+// (parameters: r .. N arrive preloaded in SGPRs, everything the first round trip reads through; the by-value ChainParams stands last)
+__global__ void __launch_bounds__(kBlock) k_normal_eq(const float* __restrict__ r /*the reading: x, y, z, N floats each*/, const IcpState* __restrict__ st,
+                                                      const int32_t* __restrict__ pos, const float* __restrict__ d2,
                                                       const float4* __restrict__ mq /*matched points*/, const float4* __restrict__ mn /*matched normals*/,
-                                                      const int32_t* __restrict__ pos, const float* __restrict__ d2, ChainParams cp,
-                                                      const IcpState* __restrict__ st, double* __restrict__ part /*[27][grid]*/,
-                                                      uint32_t* __restrict__ hist_zero /*nullable: level-1 replicas to clear*/) {
+                                                      int N, double* __restrict__ part /*[27][grid]*/,
+                                                      uint32_t* __restrict__ hist_zero /*nullable: level-1 replicas to clear*/, ChainParams cp) {
+  const float *const rx = r, *const ry = r + (size_t)N, *const rz = r + 2 * (size_t)N;
   using Sum = BlockSum<kNeComps, kBlock>;
   __shared__ double s_a[Sum::kWordsA];
   __shared__ double s_b[Sum::kWordsB];
@@ -2853,9 +2870,11 @@ __device__ __forceinline__ void solve_body(const double* __restrict__ part, int 
 
 // k_solve — the closing step as a launch of its own (the two-kernel chain of large readings and of batches, the sharded chain,
 // the module-level minimiser)
-__global__ void __launch_bounds__(kBlock) k_solve(const double* __restrict__ part, int nb, int N, ChainParams cp, IcpState* __restrict__ st,
+// (the by-value ChainParams stands last: a struct ends the run of arguments that arrive preloaded in SGPRs, and the first round trip —
+// the state and the partials — needs only what stands in front of it)
+__global__ void __launch_bounds__(kBlock) k_solve(const double* __restrict__ part, int nb, int N, IcpState* __restrict__ st,
                                                   float* __restrict__ trace_T, float* __restrict__ trace_limit, int64_t* __restrict__ trace_kept,
-                                                  int trace_cap, int update_pose, HostPost* __restrict__ post) {
+                                                  int trace_cap, int update_pose, HostPost* __restrict__ post, ChainParams cp) {
   __shared__ SolveLds lds;
   solve_body(part, nb, N, cp, st, trace_T, trace_limit, trace_kept, trace_cap, update_pose, post, lds, nullptr);
 }
@@ -2872,14 +2891,22 @@ constexpr int kFusedMaxBlocks = 256;   // one block per CU (the selection's LDS 
 // The normal-equation half uses the first kBlock (256) threads with kNePPT points each and the same fixed-order block sum
 // as k_normal_eq: with the same number of blocks the 27 x blocks partials — and therefore the pose — are bit-identical to the
 // two-kernel chain's (o3s_icp_compute_batch runs that one; a pair must not depend on how it was issued).  k_solve follows.
-__global__ void __launch_bounds__(kFinThreads) k_sel_ne(ChainParams cp, IcpState* __restrict__ st, SelScratch* __restrict__ ss,
-                                                        const CandRec* __restrict__ cand, const uint32_t* __restrict__ cand_cnt,
-                                                        const uint32_t* __restrict__ hist2, uint32_t* __restrict__ base_scratch,
-                                                        const double* __restrict__ part_cent /*[7][nb_cls]*/, int nb_cls, int mode,
-                                                        const float* __restrict__ rx, const float* __restrict__ ry, const float* __restrict__ rz, int N,
-                                                        const float4* __restrict__ mq, const float4* __restrict__ mn, const int32_t* __restrict__ pos,
-                                                        const float* __restrict__ d2, double* __restrict__ part_ne /*[27][grid]*/,
-                                                        uint32_t* __restrict__ hist_zero /*level-1 replicas*/) {
+// Parameters: the first round trip reads through ten pointers, which is more than the 14 dwords of arguments that arrive preloaded
+// in SGPRs hold.  The header and this block's points stand first — they are the bulk of the trip and go out at once (the compiler
+// waits for all fetched arguments in one place, ahead of the first load that needs one, so the selection's own requests, which come
+// later in program order, follow the fetch) — and the by-value ChainParams last.  The level-2 histogram lies behind the level-1
+// replicas, the bases behind the counts and y, z behind x: one base each.
+__global__ void __launch_bounds__(kFinThreads) k_sel_ne(IcpState* __restrict__ st, const float* __restrict__ r /*the reading: x, y, z, N floats each*/,
+                                                        const int32_t* __restrict__ pos, const float* __restrict__ d2,
+                                                        const float4* __restrict__ mq, const float4* __restrict__ mn, int N, int nb_cls, int mode,
+                                                        SelScratch* __restrict__ ss,
+                                                        uint32_t* __restrict__ cand_cnt /*counts [nb_cls], then the bases [nb_cls + 1]*/,
+                                                        uint32_t* __restrict__ hist_zero /*level-1 replicas, then level 2*/,
+                                                        const double* __restrict__ part_cent /*[7][nb_cls]*/,
+                                                        const CandRec* __restrict__ cand, double* __restrict__ part_ne /*[27][grid]*/, ChainParams cp) {
+  const float *const rx = r, *const ry = r + (size_t)N, *const rz = r + 2 * (size_t)N;
+  const uint32_t* const hist2 = hist_zero + (size_t)kHistReplicas * kHistBins;
+  uint32_t* const base_scratch = cand_cnt + nb_cls;
   extern __shared__ __align__(16) uint32_t s_dyn[];
   __shared__ float s_out[8];
   using Sum = BlockSum<kNeComps, kBlock>;

@@ -700,16 +700,17 @@ void launch_match2(o3s_icp* h, const ChainArgs& a, const ChainParams& cp, const 
   uint32_t* const settled = CERT ? h->d_hist.as<uint32_t>() + kHistWords + kSpecWords + kSpecTrace : nullptr;
 #endif
   const int nb = round_up8(nblocks(a.N, kern::kBlock / (FRONT ? 1 : G)));  // one tile of kBlock / G queries per block (FRONT: kBlock)
+  // (O3S_MATCH2_PARAMS: the reading and its normals go in as one base each)
   if (h->far_rows)
-    hipLaunchKernelGGL((match2_kernel<STATS, G, 2, 4, true, CERT, FRONT>()), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, ix.ref, ix.cell_start, ix.g,
-                       h->d_state.as<IcpState>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_mq.as<float4>(), chain_hist(h), ix.refn,
-                       normals_from_matcher(a) ? h->d_mn.as<float4>() : (float4*)nullptr, a.has_n ? a.rnx : (const float*)nullptr, a.rny, a.rnz,
-                       chain_replicas(h) - 1, spec, CERT ? cert : (float*)nullptr O3S_DBG_ARG(cp.dbg) O3S_DBG_ARG(settled));
+    hipLaunchKernelGGL((match2_kernel<STATS, G, 2, 4, true, CERT, FRONT>()), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, h->d_state.as<IcpState>(),
+                       h->d_mq.as<float4>(), CERT ? cert : (float*)nullptr, h->d_pos.as<int32_t>(), a.N, chain_replicas(h) - 1, ix.ref, ix.cell_start,
+                       h->d_d2.as<float>(), chain_hist(h), ix.refn, normals_from_matcher(a) ? h->d_mn.as<float4>() : (float4*)nullptr,
+                       a.has_n ? a.rnx : (const float*)nullptr, spec, ix.g O3S_DBG_ARG(cp.dbg) O3S_DBG_ARG(settled));
   else
-    hipLaunchKernelGGL((match2_kernel<STATS, G, 2, 2, false, CERT, FRONT>()), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, ix.ref, ix.cell_start, ix.g,
-                       h->d_state.as<IcpState>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_mq.as<float4>(), chain_hist(h), ix.refn,
-                       normals_from_matcher(a) ? h->d_mn.as<float4>() : (float4*)nullptr, a.has_n ? a.rnx : (const float*)nullptr, a.rny, a.rnz,
-                       chain_replicas(h) - 1, spec, CERT ? cert : (float*)nullptr O3S_DBG_ARG(cp.dbg) O3S_DBG_ARG(settled));
+    hipLaunchKernelGGL((match2_kernel<STATS, G, 2, 2, false, CERT, FRONT>()), dim3(nb), dim3(kern::kBlock), 0, s, a.rx, h->d_state.as<IcpState>(),
+                       h->d_mq.as<float4>(), CERT ? cert : (float*)nullptr, h->d_pos.as<int32_t>(), a.N, chain_replicas(h) - 1, ix.ref, ix.cell_start,
+                       h->d_d2.as<float>(), chain_hist(h), ix.refn, normals_from_matcher(a) ? h->d_mn.as<float4>() : (float4*)nullptr,
+                       a.has_n ? a.rnx : (const float*)nullptr, spec, ix.g O3S_DBG_ARG(cp.dbg) O3S_DBG_ARG(settled));
 }
 // `first`: the first iteration of a call — no incumbents yet, half the queries go through the far search.  Up to 200 k points
 // it runs with FOUR lanes per query whatever the steady-state choice: the far search is a chain of dependent round trips per lane,
@@ -828,27 +829,28 @@ void launch_constrain(o3s_icp* h, const ChainArgs& a, int nb, hipStream_t s, con
 void launch_iteration(o3s_icp* h, const ChainArgs& a, bool stats, hipEvent_t* ev /*6 events or null*/, int it) {
   IcpState* st = h->d_state.as<IcpState>();
   hipStream_t s = h->stream;
-  const int mode = kern::kModeCentroid | kern::kModeGate | (normals_from_matcher(a) ? kern::kModeNormalReady : 0);
+  const int mode = kern::kModeCentroid | (a.cp.has_normal_gate ? kern::kModeGate : 0) | (normals_from_matcher(a) ? kern::kModeNormalReady : 0);
   if (ev) (void)hipEventRecord(ev[0], s);
   const RefIndex ix = chain_index(h, a.cp, it);
   launch_match_chain(h, a, stats, s, it, ix);
   if (ev) (void)hipEventRecord(ev[1], s);
-  hipLaunchKernelGGL(kern::k_classify, dim3(a.nb_cls), dim3(kern::kClsBlock), 0, s, a.rx, a.ry, a.rz, a.rnx, a.rny, a.rnz, a.N, ix.ref,
-                     ix.refn, h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_hist.as<uint32_t>(), a.cp, st,
-                     h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(), h->d_cand_cnt.as<uint32_t>(), h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins, h->d_mq.as<float4>(), h->d_mn.as<float4>(), h->d_cent.as<double>(), mode, kHistReplicas,
-                     10, 1023u, a.spec, a.cp.mirror ? kern::kInfF : ix.g.max_r2 O3S_DBG_ARG(a.no_bin_counters));
+  hipLaunchKernelGGL(kern::k_classify, dim3(a.nb_cls), dim3(kern::kClsBlock), 0, s, a.rx, st, h->d_pos.as<int32_t>(), h->d_d2.as<float>(),
+                     h->d_mq.as<float4>(), a.spec, a.N, mode, h->d_mn.as<float4>(), ix.ref, ix.refn, h->d_hist.as<uint32_t>(),
+                     h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(), h->d_cand_cnt.as<uint32_t>(),
+                     h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins, h->d_cent.as<double>(), kHistReplicas, 10, 1023u,
+                     a.cp.mirror ? kern::kInfF : ix.g.max_r2, a.cp O3S_DBG_ARG(a.no_bin_counters));
   if (ev) (void)hipEventRecord(ev[2], s);
   uint32_t* hist2 = h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins;
   if (a.nb_fused > 0) {  // selection + normal equations in one launch (kern::k_sel_ne); timed under "sel_finish"
-    hipLaunchKernelGGL(kern::k_sel_ne, dim3(a.nb_fused), dim3(kern::kFinThreads), kern::kSelCap * 4, s, a.cp, st, h->d_sel.as<SelScratch>(),
-                       h->d_cand.as<CandRec>(), h->d_cand_cnt.as<uint32_t>(), hist2, h->d_cand_cnt.as<uint32_t>() + a.nb_cls, h->d_cent.as<double>(),
-                       a.nb_cls, mode, a.rx, a.ry, a.rz, a.N, h->d_mq.as<float4>(), h->d_mn.as<float4>(), h->d_pos.as<int32_t>(),
-                       h->d_d2.as<float>(), h->d_ne.as<double>(), h->d_hist.as<uint32_t>());
+    hipLaunchKernelGGL(kern::k_sel_ne, dim3(a.nb_fused), dim3(kern::kFinThreads), kern::kSelCap * 4, s, st, a.rx, h->d_pos.as<int32_t>(),
+                       h->d_d2.as<float>(), h->d_mq.as<float4>(), h->d_mn.as<float4>(), a.N, a.nb_cls, mode, h->d_sel.as<SelScratch>(),
+                       h->d_cand_cnt.as<uint32_t>(), h->d_hist.as<uint32_t>(), h->d_cent.as<double>(), h->d_cand.as<CandRec>(),
+                       h->d_ne.as<double>(), a.cp);
     if (ev) (void)hipEventRecord(ev[3], s);
     if (ev) (void)hipEventRecord(ev[4], s);
     if (h->deg.mode != O3S_DEGENERACY_OFF) launch_constrain(h, a, a.nb_fused, s);  // (a profiled call times it with k_solve)
-    hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), a.nb_fused, a.N, a.cp, st, h->d_trace_T.as<float>(),
-                       h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 1, h->post.dev);
+    hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), a.nb_fused, a.N, st, h->d_trace_T.as<float>(),
+                       h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 1, h->post.dev, a.cp);
     if (ev) (void)hipEventRecord(ev[5], s);
     return;
   }
@@ -860,18 +862,18 @@ void launch_iteration(o3s_icp* h, const ChainArgs& a, bool stats, hipEvent_t* ev
     if (partial)
       hipLaunchKernelGGL(kern::k_sel_partial, dim3(nbp), dim3(kern::kFinThreads), 0, s, st, h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(),
                          h->d_cand_cnt.as<uint32_t>(), hist2, a.nb_cls, mode, h->d_sel_part2.as<double>(), park_rec, park_key);
-    hipLaunchKernelGGL(kern::k_sel_finish, dim3(1), dim3(kern::kFinThreads), kern::kSelCap * 4, s, (uint32_t*)nullptr, a.cp, st,
-                       h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(), h->d_cand_cnt.as<uint32_t>(), hist2,
-                       h->d_cand_cnt.as<uint32_t>() + a.nb_cls, h->d_cent.as<double>(), a.nb_cls, mode,
-                       partial ? h->d_sel_part2.as<double>() : (const double*)nullptr, nbp, park_rec, park_key);
+    hipLaunchKernelGGL(kern::k_sel_finish, dim3(1), dim3(kern::kFinThreads), kern::kSelCap * 4, s, (uint32_t*)nullptr, st,
+                       h->d_sel.as<SelScratch>(), h->d_cand_cnt.as<uint32_t>(), hist2, h->d_cent.as<double>(), a.nb_cls, mode,
+                       h->d_cand_cnt.as<uint32_t>() + a.nb_cls, h->d_cand.as<CandRec>(),
+                       partial ? h->d_sel_part2.as<double>() : (const double*)nullptr, nbp, park_rec, park_key, a.cp);
   }
   if (ev) (void)hipEventRecord(ev[3], s);
-  hipLaunchKernelGGL(kern::k_normal_eq, dim3(a.nb_part), dim3(kern::kBlock), 0, s, a.rx, a.ry, a.rz, a.N, h->d_mq.as<float4>(),
-                     h->d_mn.as<float4>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), a.cp, st, h->d_ne.as<double>(), h->d_hist.as<uint32_t>());
+  hipLaunchKernelGGL(kern::k_normal_eq, dim3(a.nb_part), dim3(kern::kBlock), 0, s, a.rx, (const IcpState*)st, h->d_pos.as<int32_t>(),
+                     h->d_d2.as<float>(), h->d_mq.as<float4>(), h->d_mn.as<float4>(), a.N, h->d_ne.as<double>(), h->d_hist.as<uint32_t>(), a.cp);
   if (ev) (void)hipEventRecord(ev[4], s);
   if (h->deg.mode != O3S_DEGENERACY_OFF) launch_constrain(h, a, a.nb_part, s);
-  hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), a.nb_part, a.N, a.cp, st, h->d_trace_T.as<float>(),
-                     h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 1, h->post.dev);
+  hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, s, h->d_ne.as<double>(), a.nb_part, a.N, st, h->d_trace_T.as<float>(),
+                     h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 1, h->post.dev, a.cp);
   if (ev) (void)hipEventRecord(ev[5], s);
 }
 
@@ -882,7 +884,7 @@ int launch_iteration_sharded(o3s_icp* h, const ChainArgs& a, bool stats, int it)
   IcpState* st = h->d_state.as<IcpState>();
   hipStream_t s = h->stream;
   // no centroid partials from k_classify here: the raw moments of k_shard_moments carry the sums of p and q themselves
-  const int mode = kern::kModeGate | (normals_from_matcher(a) ? kern::kModeNormalReady : 0);
+  const int mode = (a.cp.has_normal_gate ? kern::kModeGate : 0) | (normals_from_matcher(a) ? kern::kModeNormalReady : 0);
   uint8_t* xb = h->shard.xbuf;
   double* xm = reinterpret_cast<double*>(xb + kXchgMOff);
   uint32_t* l1 = reinterpret_cast<uint32_t*>(xb + kXchgI32Off);
@@ -900,10 +902,10 @@ int launch_iteration_sharded(o3s_icp* h, const ChainArgs& a, bool stats, int it)
   const RefIndex ix = chain_index(h, a.cp, it);  // (every rank holds the same reference, so every rank picks the same index)
   launch_match_chain(h, a, stats, s, it, ix);  // level-1 replicas = region I of the exchange buffer (chain_hist), R of them
   if ((rc = exchange(kXchgI32Off, (int64_t)R * kHistBins, O3S_XCHG_INT32)) != O3S_OK) return rc;
-  hipLaunchKernelGGL(kern::k_classify, dim3(a.nb_cls), dim3(kern::kClsBlock), 0, s, a.rx, a.ry, a.rz, a.rnx, a.rny, a.rnz, a.N, ix.ref,
-                     ix.refn, h->d_pos.as<int32_t>(), h->d_d2.as<float>(), l1, a.cp, st, h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(),
-                     h->d_cand_cnt.as<uint32_t>(), l2, h->d_mq.as<float4>(), h->d_mn.as<float4>(), h->d_cent.as<double>(), mode, R, 20 - kShardL2Bits,
-                     (uint32_t)(kShardL2Bins - 1));
+  hipLaunchKernelGGL(kern::k_classify, dim3(a.nb_cls), dim3(kern::kClsBlock), 0, s, a.rx, st, h->d_pos.as<int32_t>(), h->d_d2.as<float>(),
+                     h->d_mq.as<float4>(), (const uint32_t*)nullptr, a.N, mode, h->d_mn.as<float4>(), ix.ref, ix.refn, l1, h->d_sel.as<SelScratch>(),
+                     h->d_cand.as<CandRec>(), h->d_cand_cnt.as<uint32_t>(), l2, h->d_cent.as<double>(), R, 20 - kShardL2Bits,
+                     (uint32_t)(kShardL2Bins - 1), kern::kInfF, a.cp);
   if (a.cp.has_trim && (rc = exchange(kXchgI32Off + (int64_t)kXchgL1Words * 4, kShardL2Bins, O3S_XCHG_INT32)) != O3S_OK) return rc;
   hipLaunchKernelGGL(kern::k_shard_moments, dim3(a.nb_part + 1), dim3(kern::kBlock), 0, s, a.cp, st, h->d_sel.as<SelScratch>(), l2, a.rx, a.ry, a.rz, a.N,
                      h->d_mq.as<float4>(), h->d_mn.as<float4>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), xm, a.nb_part, l1, R,
@@ -2086,16 +2088,15 @@ int o3s_icp_outlier_weights(o3s_icp* h, const float* reading_normals, const int3
   hipLaunchKernelGGL(kern::k_hist, dim3(nblocks(N)), dim3(kern::kBlock), 0, h->stream, h->d_d2.as<float>(), (int)N, h->d_hist.as<uint32_t>());
   {
     float* r = h->d_r.as<float>();
-    const size_t n = (size_t)N;
     const int nbc = nblocks(N, kern::kClsBlock);
-    hipLaunchKernelGGL(kern::k_classify, dim3(nbc), dim3(kern::kClsBlock), 0, h->stream, r, r + n, r + 2 * n, r + 3 * n, r + 4 * n, r + 5 * n,
-                       (int)N, h->d_ref.as<float4>(), h->d_refn.as<float4>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(),
-                       h->d_hist.as<uint32_t>(), cp, h->d_state.as<IcpState>(), h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(),
-                       h->d_cand_cnt.as<uint32_t>(), h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins, h->d_mq.as<float4>(), h->d_mn.as<float4>(), h->d_cent.as<double>(), 0, kHistReplicas);
-    hipLaunchKernelGGL(kern::k_sel_finish, dim3(1), dim3(kern::kFinThreads), kern::kSelCap * 4, h->stream, h->d_hist.as<uint32_t>(), cp,
-                       h->d_state.as<IcpState>(), h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(), h->d_cand_cnt.as<uint32_t>(), h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins,
-                       h->d_cand_cnt.as<uint32_t>() + nbc, h->d_cent.as<double>(), nbc, 0, (const double*)nullptr, 0, (const CandRec*)nullptr,
-                       (const uint32_t*)nullptr);
+    hipLaunchKernelGGL(kern::k_classify, dim3(nbc), dim3(kern::kClsBlock), 0, h->stream, r, h->d_state.as<IcpState>(), h->d_pos.as<int32_t>(),
+                       h->d_d2.as<float>(), h->d_mq.as<float4>(), (const uint32_t*)nullptr, (int)N, 0, h->d_mn.as<float4>(), h->d_ref.as<float4>(),
+                       h->d_refn.as<float4>(), h->d_hist.as<uint32_t>(), h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(), h->d_cand_cnt.as<uint32_t>(),
+                       h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins, h->d_cent.as<double>(), kHistReplicas, 10, 1023u, kern::kInfF, cp);
+    hipLaunchKernelGGL(kern::k_sel_finish, dim3(1), dim3(kern::kFinThreads), kern::kSelCap * 4, h->stream, h->d_hist.as<uint32_t>(),
+                       h->d_state.as<IcpState>(), h->d_sel.as<SelScratch>(), h->d_cand_cnt.as<uint32_t>(),
+                       h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins, h->d_cent.as<double>(), nbc, 0, h->d_cand_cnt.as<uint32_t>() + nbc,
+                       h->d_cand.as<CandRec>(), (const double*)nullptr, 0, (const CandRec*)nullptr, (const uint32_t*)nullptr, cp);
   }
   const float* d_rn = nullptr;
   if (reading_normals) {
@@ -2146,19 +2147,20 @@ static int minimize_impl(o3s_icp* h, const float* reading_xyzw, const int32_t* i
   HIP_TRY(h, hipMemsetAsync(h->d_sel.p, 0, sizeof(SelScratch), h->stream));
   const ChainArgs a = chain_args(h, cp);
   IcpState* st = h->d_state.as<IcpState>();
-  hipLaunchKernelGGL(kern::k_classify, dim3(a.nb_cls), dim3(kern::kClsBlock), 0, h->stream, a.rx, a.ry, a.rz, a.rnx, a.rny, a.rnz, a.N,
-                     h->d_ref.as<float4>(), h->d_refn.as<float4>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), h->d_hist.as<uint32_t>(), cp, st,
-                     h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(), h->d_cand_cnt.as<uint32_t>(), h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins, h->d_mq.as<float4>(), h->d_mn.as<float4>(),
-                     h->d_cent.as<double>(), kern::kModeCentroid, kHistReplicas);
-  hipLaunchKernelGGL(kern::k_sel_finish, dim3(1), dim3(kern::kFinThreads), kern::kSelCap * 4, h->stream, h->d_hist.as<uint32_t>(), cp, st,
-                     h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(), h->d_cand_cnt.as<uint32_t>(), h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins,
-                     h->d_cand_cnt.as<uint32_t>() + a.nb_cls, h->d_cent.as<double>(), a.nb_cls, kern::kModeCentroid, (const double*)nullptr, 0,
-                     (const CandRec*)nullptr, (const uint32_t*)nullptr);
-  hipLaunchKernelGGL(kern::k_normal_eq, dim3(a.nb_part), dim3(kern::kBlock), 0, h->stream, a.rx, a.ry, a.rz, a.N, h->d_mq.as<float4>(),
-                     h->d_mn.as<float4>(), h->d_pos.as<int32_t>(), h->d_d2.as<float>(), cp, st, h->d_ne.as<double>(), (uint32_t*)nullptr);
+  hipLaunchKernelGGL(kern::k_classify, dim3(a.nb_cls), dim3(kern::kClsBlock), 0, h->stream, a.rx, st, h->d_pos.as<int32_t>(),
+                     h->d_d2.as<float>(), h->d_mq.as<float4>(), (const uint32_t*)nullptr, a.N, kern::kModeCentroid, h->d_mn.as<float4>(),
+                     h->d_ref.as<float4>(), h->d_refn.as<float4>(), h->d_hist.as<uint32_t>(), h->d_sel.as<SelScratch>(), h->d_cand.as<CandRec>(),
+                     h->d_cand_cnt.as<uint32_t>(), h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins, h->d_cent.as<double>(), kHistReplicas,
+                     10, 1023u, kern::kInfF, cp);
+  hipLaunchKernelGGL(kern::k_sel_finish, dim3(1), dim3(kern::kFinThreads), kern::kSelCap * 4, h->stream, h->d_hist.as<uint32_t>(), st,
+                     h->d_sel.as<SelScratch>(), h->d_cand_cnt.as<uint32_t>(), h->d_hist.as<uint32_t>() + (size_t)kHistReplicas * kHistBins,
+                     h->d_cent.as<double>(), a.nb_cls, kern::kModeCentroid, h->d_cand_cnt.as<uint32_t>() + a.nb_cls, h->d_cand.as<CandRec>(),
+                     (const double*)nullptr, 0, (const CandRec*)nullptr, (const uint32_t*)nullptr, cp);
+  hipLaunchKernelGGL(kern::k_normal_eq, dim3(a.nb_part), dim3(kern::kBlock), 0, h->stream, a.rx, (const IcpState*)st, h->d_pos.as<int32_t>(),
+                     h->d_d2.as<float>(), h->d_mq.as<float4>(), h->d_mn.as<float4>(), a.N, h->d_ne.as<double>(), (uint32_t*)nullptr, cp);
   if (set) launch_constrain(h, a, a.nb_part, h->stream, set, vals);
-  hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, h->stream, h->d_ne.as<double>(), a.nb_part, a.N, cp, st,
-                     h->d_trace_T.as<float>(), h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 0, (HostPost*)nullptr);
+  hipLaunchKernelGGL(kern::k_solve, dim3(1), dim3(kern::kBlock), 0, h->stream, h->d_ne.as<double>(), a.nb_part, a.N, st,
+                     h->d_trace_T.as<float>(), h->d_trace_limit.as<float>(), h->d_trace_kept.as<int64_t>(), h->trace_cap, 0, (HostPost*)nullptr, cp);
   HIP_TRY(h, hipGetLastError());
   rc = pull_state(h);
   if (rc != O3S_OK) return rc;

@@ -6,6 +6,7 @@ resource report.  Reads text only; runs on a CPU.
     tools/isa_round_trips.py                      # compiles csrc/o3s_icp.hip (the Makefile's flags) into a temporary directory
     tools/isa_round_trips.py o3s_icp.s            # reads device assembly made with `hipcc ... --cuda-device-only -S`
     tools/isa_round_trips.py -k k_solve -k 'k_match2<false,2,2,4,true,true>'
+    tools/isa_round_trips.py --kernarg-front      # the front of every launch: what stands between a wave's start and its first loads
 
 The chain kernels are one generation of waves and latency-bound: what a launch costs is its number of DEPENDENT memory round
 trips.  A wait is *serial* when it retires at least one outstanding load and another load is issued after it (ahead of the
@@ -16,6 +17,14 @@ When the tool compiles it compiles twice, side by side: once as the library is b
 every load takes the source line it came from.  A region can then be named by a piece of its source text: `--ignore TEXT` leaves
 out the loads whose source line contains TEXT (regions the measured chain never enters), `region_waits()` looks at the loads of
 one source line.  Assembly given on the command line is read as it is (source lines if it carries .loc directives).
+
+`--kernarg-front` reads the very first thing a launch does.  Every address comes out of a kernel argument; an
+argument is either delivered in SGPRs at wave launch (the leading ones, up to `.amdhsa_user_sgpr_kernarg_preload_length` dwords:
+-amdgpu-kernarg-preload-count in HIPFLAGS) or fetched with a scalar load from the kernarg segment, which the first vector load that
+needs it has to wait for (`s_waitcnt lgkmcnt`).  Per kernel the report gives the preload length, the kernarg scalar loads that
+stand between the end of the compatibility prologue (the copy of the preloaded arguments' loads that firmware without the feature
+enters through) and the first vector load, the lgkmcnt wait that load sits behind, if any, and whether a kernarg load is waited for
+between loads of the first batch of vector loads (tests/test_isa_kernarg_front.py pins the preload length and the first wait).
 """
 from __future__ import annotations
 
@@ -29,6 +38,9 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "open3d_slam_advanced_rss_2024_public_amd", "csrc")
 DEFAULT_KERNELS = ["k_match2<false,2,2,4,true,true>", "k_classify", "k_sel_ne", "k_solve", "k_sel_finish", "k_sel_partial", "k_normal_eq"]
+# --kernarg-front: every kernel the chain and the reading's preparation launch (the settle front is the seven-argument overload)
+FRONT_KERNELS = ["k_match2<false,4,2,4,true,true,true>", "k_match2<false,2,2,4,true,true>", "k_match2<false,4,2,4,true,false>", "k_classify", "k_sel_ne",
+                 "k_solve", "k_sel_partial", "k_sel_finish", "k_normal_eq", "k_read_prep", "k_read_starts", "k_read_scatter", "k_read_place"]
 # Regions the converged C2 chain never enters, by a piece of their source line: not counted, each with the branch region around it.
 # The one list: tests/test_isa_round_trips.py pins its bounds on the same regions this tool leaves out of its table.
 DEFAULT_IGNORE = {
@@ -42,6 +54,8 @@ DEFAULT_IGNORE = {
 _LOAD = re.compile(r"^(global|buffer|flat|scratch)_load_\w+")
 _VMEM_OTHER = re.compile(r"^(global|buffer|flat|scratch)_(store|atomic)_\w+")
 _VMCNT = re.compile(r"vmcnt\((\d+)\)")
+_LGKMCNT = re.compile(r"lgkmcnt\((\d+)\)")
+_SPAIR = re.compile(r"s\[(\d+):(\d+)\]")
 
 
 def makefile_flags() -> list[str]:
@@ -92,6 +106,10 @@ class Kernel:
         self.symbol = symbol
         self.ops: list[tuple[str, str, str]] = []  # (kind, text, source line text); kind: load / vmem / wait / barrier / label / branch
         self.resources: list[str] = []
+        # the kernarg front: scalar loads, every s_waitcnt, vector loads, barriers and unconditional branches in program order
+        # (kind, text); kind: sload / swait / load / barrier / jump / smov64
+        self.front_ops: list[tuple[str, str]] = []
+        self.hsa: dict[str, int] = {}  # the .amdhsa_user_sgpr_* lines of the kernel descriptor
 
 
 def parse(asm_path: str, src_dir: str = CSRC) -> dict[str, Kernel]:
@@ -118,6 +136,7 @@ def parse(asm_path: str, src_dir: str = CSRC) -> dict[str, Kernel]:
     last: Kernel | None = None
     loc = ""
     pending_type: set[str] = set()
+    hsa_of: Kernel | None = None
     for raw in open(asm_path, errors="replace"):
         s = raw.strip()
         if not s:
@@ -126,6 +145,14 @@ def parse(asm_path: str, src_dir: str = CSRC) -> dict[str, Kernel]:
             m = re.match(r'\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', s)
             if m:
                 files[int(m.group(1))] = os.path.join(m.group(2), m.group(3)) if m.group(3) else m.group(2)
+            continue
+        if s.startswith(".amdhsa_kernel "):
+            hsa_of = kernels.get(s.split()[1])
+            continue
+        if s.startswith(".amdhsa_user_sgpr_") and hsa_of is not None:
+            key, val = s.split()[:2]
+            if val.isdigit():
+                hsa_of.hsa[key[len(".amdhsa_user_sgpr_"):]] = int(val)
             continue
         if s.startswith(".type") and s.endswith(",@function"):
             pending_type.add(s.split()[1].split(",")[0])
@@ -155,6 +182,18 @@ def parse(asm_path: str, src_dir: str = CSRC) -> dict[str, Kernel]:
             continue
         ins = s.split(";")[0].strip()
         mnem = ins.split()[0] if ins else ""
+        if mnem.startswith("s_load_"):
+            cur.front_ops.append(("sload", ins))
+        elif mnem == "s_waitcnt":
+            cur.front_ops.append(("swait", ins))
+        elif mnem == "s_branch":
+            cur.front_ops.append(("jump", ins))
+        elif mnem == "s_mov_b64":
+            cur.front_ops.append(("smov64", ins))
+        elif _LOAD.match(mnem):
+            cur.front_ops.append(("load", ins))
+        elif mnem == "s_barrier":
+            cur.front_ops.append(("barrier", ins))
         if mnem.startswith("s_cbranch_"):
             cur.ops.append(("branch", ins, ""))
         elif _LOAD.match(mnem):
@@ -258,6 +297,73 @@ def region_waits(k: Kernel, text: str, batch: int):
     return [tuple(g) for g in groups]
 
 
+def kernarg_front(k: Kernel) -> dict:
+    """The front of a launch: what stands between a wave's start and its first batch of vector loads.
+      preload        dwords of arguments delivered in SGPRs at wave launch
+      sloads         the kernarg scalar loads between the end of the compatibility prologue and the first vector load
+      first_wait     the lgkmcnt wait, with a kernarg load outstanding, that the first vector load sits behind (None: it goes out at once)
+      batch_wait     the first such wait with another vector load of the first batch behind it, in program order, branches not followed
+                     (None: the whole batch goes out without waiting for an argument; a wait behind the batch's last load overlaps
+                     with the loads in flight); the batch ends at the first vmcnt wait that retires one of its loads, or a barrier
+      batch_loads    vector loads of that first batch"""
+    preload = k.hsa.get("kernarg_preload_length", 0)
+    # the kernarg pointer's SGPR pair: the user SGPRs in front of it are the private segment buffer (4), the dispatch and queue pointers (2 each)
+    base = 4 * k.hsa.get("private_segment_buffer", 0) + 2 * k.hsa.get("dispatch_ptr", 0) + 2 * k.hsa.get("queue_ptr", 0)
+    karg = {(base, base + 1)}
+    ops = k.front_ops
+    if preload:  # the prologue ends with the jump over the padding to the entry that hardware with the feature starts at
+        j = next((j for j, (kind, _) in enumerate(ops) if kind == "jump"), -1)
+        ops = ops[j + 1:]
+    out = {"preload": preload, "sloads": [], "first_wait": None, "batch_wait": None, "batch_loads": 0}
+    pending = 0    # kernarg scalar loads not waited for yet
+    inflight = 0   # vector loads in flight
+    held = None    # a kernarg wait seen inside the batch: it counts once another load of the batch follows it
+    for kind, ins in ops:
+        if kind == "smov64":
+            pairs = _SPAIR.findall(ins)
+            if len(pairs) == 2 and (int(pairs[1][0]), int(pairs[1][1])) in karg:
+                karg.add((int(pairs[0][0]), int(pairs[0][1])))
+        elif kind == "sload":
+            pairs = _SPAIR.findall(ins.split(",", 1)[1]) if "," in ins else []
+            if pairs and (int(pairs[0][0]), int(pairs[0][1])) in karg:
+                pending += 1
+                if out["batch_loads"] == 0:
+                    out["sloads"].append(ins)
+        elif kind == "swait":
+            m = _LGKMCNT.search(ins)
+            if m and pending:  # scalar loads return out of order: any lgkmcnt wait with one outstanding waits for it
+                if out["batch_loads"] == 0 and out["first_wait"] is None:
+                    out["first_wait"] = ins
+                if out["batch_wait"] is None and held is None:
+                    held = ins
+                pending = 0
+            v = _VMCNT.search(ins)
+            if v and int(v.group(1)) < inflight:
+                break
+        elif kind == "load":
+            inflight += 1
+            out["batch_loads"] += 1
+            if held is not None and out["batch_wait"] is None:
+                out["batch_wait"] = held
+        elif kind == "barrier":
+            break
+    return out
+
+
+def report_kernarg_front(kernels: dict[str, Kernel], specs: list[str], out=sys.stdout) -> dict[str, dict]:
+    res = {}
+    for spec in specs:
+        k = find(kernels, spec)
+        f = res[spec] = kernarg_front(k)
+        print(f"== {spec}: preload length {f['preload']} dwords, first batch of {f['batch_loads']} vector load(s)", file=out)
+        print(f"   kernarg scalar loads ahead of the first vector load: {len(f['sloads'])}", file=out)
+        for ins in f["sloads"]:
+            print(f"      {ins}", file=out)
+        print(f"   the first vector load sits behind: {f['first_wait'] or 'no kernarg wait'}", file=out)
+        print(f"   a kernarg load is waited for between loads of the first batch: {f['batch_wait'] or 'no'}", file=out)
+    return res
+
+
 def compile_both(out_dir: str, src: str = "o3s_icp.hip") -> dict[str, Kernel]:
     """Two compiles side by side: the Makefile's flags (the instructions and the resource report of the library) and the same with
     -gline-tables-only (the source line of every instruction; it makes a non-inlined callee save one more register, which shows in the
@@ -299,7 +405,19 @@ def main() -> int:
     ap.add_argument("--ignore", action="append", default=[], help="leave out loads whose source line contains this text")
     ap.add_argument("--src-dir", default=CSRC, help="the directory the given assembly was compiled in (for its source lines)")
     ap.add_argument("--barriers", type=int, default=0, help="read on through this many s_barrier (default: stop at the first)")
+    ap.add_argument("--kernarg-front", action="store_true", help="report the kernarg front of every chain and reading kernel instead")
     a = ap.parse_args()
+    if a.kernarg_front:
+        specs = a.kernel or FRONT_KERNELS
+        if a.asm:
+            report_kernarg_front(parse(a.asm, a.src_dir), specs)
+        elif not hipcc():
+            print("hipcc not found", file=sys.stderr)
+            return 2
+        else:
+            with tempfile.TemporaryDirectory() as d:
+                report_kernarg_front(parse(compile_asm(d)), specs)
+        return 0
     specs = a.kernel or DEFAULT_KERNELS
     ignore = {s.split("<")[0]: list(DEFAULT_IGNORE.get(s.split("<")[0], [])) + a.ignore for s in specs}
     if a.asm:
