@@ -72,7 +72,17 @@ void o3s_o3d_default_estimation(o3s_o3d_estimation* e);
  * upper triangle is read), all nullable.  GENERALIZED needs normals or covariances on each cloud (covariances win, as in Open3D;
  * Open3D's KNN(20) normal estimation for a cloud with neither is not restated: O3S_ERR_BAD_SHAPE); POINT_TO_PLANE needs target
  * normals (O3S_ERR_BAD_SHAPE); POINT_TO_POINT needs neither.  An unknown type, gicp_epsilon <= 0 or a NULL cloud / pose / result /
- * est is O3S_ERR_BAD_ARGUMENT before any device call. */
+ * est is O3S_ERR_BAD_ARGUMENT before any device call.
+ * Degenerate correspondence sets.  POINT_TO_PLANE and GENERALIZED solve J^T J x = -J^T r as Eigen's LDLT does (largest-diagonal
+ * pivoting, D^-1 a pseudo-inverse): an unknown whose row, column and right-hand side are exactly zero comes back exactly 0.0 (a
+ * plane z = c with normals e3 under an identity init leaves the pose's x and y exactly where they were); on a system that is
+ * rank-deficient only to rounding, x solves it to rounding and its component in the system's range is the minimum-norm
+ * solution's, while the component along the unobserved directions is rounding noise divided by rounding-sized pivots — as with
+ * Eigen, it is not specified.  POINT_TO_POINT: the update is always a proper rotation (R^T R = I, det R = +1) that attains the
+ * optimum of Umeyama's objective tr(R sigma^T) and t = mean(t) - R mean(s).  Where the centred cross-covariance sigma has rank >= 2
+ * (and, when det sigma < 0, a simple smallest singular value) that rotation is unique and is Eigen::umeyama's; at rank <= 1 — one
+ * or two correspondences, collinear ones, copies of one pair — Open3D defines none and WHICH of the optimal rotations comes back
+ * is not specified (one exact pair gives R = I). */
 int o3s_o3d_registration_icp_ex(int device, const double* source, const double* source_normals, const double* source_cov,
                                 int64_t Ns, const double* target, const double* target_normals, const double* target_cov,
                                 int64_t Nt, double max_correspondence_distance, const double init[16],

@@ -293,6 +293,9 @@ def load(variant: str | None = None) -> C.CDLL:
         L.o3s_icp_hook_bin_path.argtypes = [vp, ip, C.c_int32]
         L.o3s_icp_hook_export_matches.argtypes = [vp, ip, fp, C.c_int64]
         L.o3s_icp_hook_export_matches.restype = C.c_int64
+    if hasattr(L, "o3s_test_o3d_update"):  # the hooks build: the loop-closure ICP's host update and first pass (cloud_ops.hip)
+        L.o3s_test_o3d_update.argtypes = [C.c_int, dp, dp, dp, dp]
+        L.o3s_test_o3d_first_pass.argtypes = [C.c_int, dp, dp, dp, C.c_int64, dp, dp, dp, C.c_int64, C.c_double, dp, vp, dp, ip, dp, dp, dp]
     _loaded[key] = L
     return L
 

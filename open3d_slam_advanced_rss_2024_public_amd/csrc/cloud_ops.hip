@@ -426,4 +426,59 @@ extern "C" int o3s_test_cloud_bounds(int device, const double* pts, int64_t n, d
   for (int a = 0; a < 6; ++a) out6[a] = from_ordered_bits(bb[a]);
   return O3S_OK;
 }
+// hooks build only (tests/test_o3d_update_host.py, tests/test_gpu_registration_edges.py): the host arithmetic of one
+// ComputeTransformation of the loop-closure ICP, as o3d_icp_run calls it (o3d_host_update) — type: o3s_o3d_estimation_type, sums: the 30
+// sums of a pass, shift: what the point-to-point sums are relative to (else unread, nullable), update: 4 x 4 column-major, x (nullable):
+// the solved 6-vector.  Touches no device
+extern "C" int o3s_test_o3d_update(int type, const double* sums, const double* shift, double* update, double* x) {
+  using namespace o3s_cloud;
+  if ((type != kEstPlane && type != kEstPoint && type != kEstGicp) || !sums || !update || (type == kEstPoint && !shift)) return O3S_ERR_BAD_ARGUMENT;
+  o3d_host_update(type, sums, shift, update, x);
+  return O3S_OK;
+}
+// hooks build only (tests/test_gpu_registration_edges.py): o3s_o3d_registration_icp_ex up to and including its first pass
+// (o3d_icp_setup + one o3d_corr_pass) on host clouds.  sums: the 30 sums; corr: the correspondence of every SOURCE INDEX (the
+// device holds them in search order: undone with the work area's `order`); scov / tcov (GICP only, nullable): xx xy xz yy yz zz of
+// every source / target point by point index, the source's as placed (untransformed); shift (nullable): the point-to-point shift
+extern "C" int o3s_test_o3d_first_pass(int device, const double* source, const double* source_normals, const double* source_cov, int64_t Ns,
+                                       const double* target, const double* target_normals, const double* target_cov, int64_t Nt, double max_dist,
+                                       const double init[16], const o3s_o3d_estimation* est, double* sums, int32_t* corr, double* scov, double* tcov,
+                                       double* shift) {
+  using namespace o3s_cloud;
+  if (!o3d_est_valid(est) || !sums || !corr) return O3S_ERR_BAD_ARGUMENT;
+  O3dEstIn e;
+  e.type = est->type;
+  e.eps = est->gicp_epsilon;
+  e.src_n = source_normals;
+  e.src_cov = source_cov;
+  e.tgt_cov = target_cov;
+  const int rc = pick_device(device);
+  if (rc != O3S_OK) return rc;
+  RegLease area(device, nullptr);
+  O3dIcpWork& w = area->reg;
+  GridIndex gi;
+  double Racc[9];
+  int r = o3d_icp_setup(w, source, Ns, target, target_normals, Nt, max_dist, init, e, &gi, Racc, nullptr, false, nullptr);
+  if (r == O3S_OK) r = o3d_corr_pass(w, Ns, gi, max_dist * max_dist, 0, sums, nullptr);
+  if (r != O3S_OK) return area.end(r);
+  auto fetch = [&]() -> int {
+    const size_t n = (size_t)Ns;
+    std::vector<uint32_t> order(n);
+    std::vector<int32_t> c(n);
+    CK(hipMemcpy(order.data(), w.order, n * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(c.data(), w.d_corr.p, n * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) corr[order[i]] = c[i];
+    if (e.type == kEstGicp && scov) {
+      std::vector<double> sc(6 * n);
+      CK(hipMemcpy(sc.data(), w.d_scov.p, 48 * n, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 6; ++k) scov[6 * (size_t)order[i] + k] = sc[6 * i + k];
+    }
+    if (e.type == kEstGicp && tcov) CK(hipMemcpy(tcov, w.d_tcov.p, 48 * (size_t)Nt, hipMemcpyDeviceToHost));
+    if (e.type == kEstPoint && shift)
+      for (int a = 0; a < 3; ++a) shift[a] = w.ea.c[a];
+    return O3S_OK;
+  };
+  return area.end(fetch());
+}
 #endif

@@ -1060,7 +1060,8 @@ inline void h_vec6_to_T(const double* v, double* T) {
 
 // Eigen::JacobiSVD<Matrix3d> (ComputeFullU | ComputeFullV) as umeyama uses it: A = U diag(s) V^T, s descending.  One-sided
 // (Hestenes) Jacobi on the columns of A in fp64; a different rotation sequence from Eigen's two-sided one, the same factors to
-// rounding wherever they are unique — and R = U S V^T below is unique whenever A has rank >= 2.
+// rounding wherever they are unique — and R = U S V^T below is unique whenever A has rank >= 2 (and, for det A < 0, a simple smallest
+// singular value).  At rank <= 1 R is a proper rotation that attains Umeyama's optimum; which one is not specified (include/o3s_registration.h).
 inline void h_svd3(const double Ain[3][3], double U[3][3], double sv[3], double V[3][3]) {
   double A[3][3];
   for (int r = 0; r < 3; ++r)
@@ -1509,44 +1510,85 @@ inline int o3d_gicp_covariances(O3dIcpWork& w, int64_t Ns, int64_t Nt, const O3d
   return O3S_OK;
 }
 
-// RegistrationICP for one pair on stream s (the device is already current on the calling thread); w: grow-only work area.
-// est (nullable: point-to-plane): the estimation; point-to-plane runs exactly the kernels and host arithmetic it always has.
-int o3d_icp_run(O3dIcpWork& w, const double* source, int64_t Ns, const double* target, const double* target_normals, int64_t Nt, double max_dist,
-                const double init[16], const o3s_o3d_icp_criteria* criteria, o3s_o3d_icp_result* result, hipStream_t s, bool on_device = false,
-                const unsigned long long* target_bounds = nullptr /*of the target, when the caller has them (build_grid_index)*/,
-                const O3dEstIn* est = nullptr) {
-  if (!source || !target || !init || !result || Ns <= 0 || Nt <= 0 || !(max_dist > 0.0)) return O3S_ERR_BAD_ARGUMENT;
-  const O3dEstIn e = est ? *est : O3dEstIn{};
+// ComputeTransformation of one iteration on the host, from the 30 sums of a pass: the identity for an empty correspondence set;
+// point-to-point: Eigen::umeyama (c: the shift the sums are relative to); point-to-plane, GICP:
+// SolveJacobianSystemAndObtainExtrinsicMatrix — J^T J x = -J^T r by LDLT, then TransformVector6dToMatrix4d.  x (nullable): the
+// solved vector (zeros where none is solved).  Touches no device.
+inline void o3d_host_update(int type, const double* sums, const double* c, double* update, double* x_out = nullptr) {
+  for (int k = 0; k < 16; ++k) update[k] = (k % 5 == 0) ? 1.0 : 0.0;
+  double x[6] = {0, 0, 0, 0, 0, 0};
+  if (sums[29] > 0 && type == kEstPoint) {  // ComputeTransformation: empty correspondence set -> identity
+    h_umeyama(sums, c, update);
+  } else if (sums[29] > 0) {  // point-to-plane, GICP: SolveJacobianSystemAndObtainExtrinsicMatrix
+    double JTJ[6][6], nb[6];
+    int t = 0;
+    for (int a = 0; a < 6; ++a)
+      for (int b = a; b < 6; ++b) {
+        JTJ[a][b] = sums[t];
+        JTJ[b][a] = sums[t];
+        ++t;
+      }
+    for (int a = 0; a < 6; ++a) nb[a] = -sums[21 + a];
+    h_ldlt_solve6(JTJ, nb, x);
+    h_vec6_to_T(x, update);
+  }
+  if (x_out)
+    for (int a = 0; a < 6; ++a) x_out[a] = x[a];
+}
+
+// RegistrationICP up to its first pass: the index over the target, the source placed by init in search order, and what the
+// estimation reads besides the clouds (GICP: both clouds' covariances and Racc, the rotation the source's have gone through;
+// point-to-point: the shift of its sums).  After it, o3d_corr_pass(w, Ns, *gi, max_dist^2, 0, ...) is the first pass.
+inline int o3d_icp_setup(O3dIcpWork& w, const double* source, int64_t Ns, const double* target, const double* target_normals, int64_t Nt, double max_dist,
+                         const double init[16], const O3dEstIn& e, GridIndex* gi_out, double Racc[9], hipStream_t s, bool on_device,
+                         const unsigned long long* target_bounds) {
+  if (!source || !target || !init || Ns <= 0 || Nt <= 0 || !(max_dist > 0.0)) return O3S_ERR_BAD_ARGUMENT;
   if (e.type == kEstPlane && !target_normals) return O3S_ERR_BAD_SHAPE;  // "requires target pointcloud to have normals"
   if (e.type == kEstGicp && ((!e.src_n && !e.src_cov) || (!target_normals && !e.tgt_cov))) return O3S_ERR_BAD_SHAPE;  // no KNN(20) normals here
-  o3s_o3d_icp_criteria cr;
-  o3s_o3d_icp_default_criteria(&cr);
-  if (criteria) cr = *criteria;
   int rc = O3S_OK;
   GridIndex gi;
   rc = o3d_prepare(w, source, Ns, target, target_normals, Nt, max_dist, &gi, s, on_device, target_bounds);
   if (rc != O3S_OK) return rc;
-  const double r2 = max_dist * max_dist;
-  double T[16];
-  std::memcpy(T, init, sizeof(T));
   rc = o3d_place_source(w, Ns, gi, init, s);
   if (rc != O3S_OK) return rc;
   w.est = e.type;
   // GICP: the rotation the source's covariances have gone through — init's (PointCloud::Transform(init), skipped for an identity),
   // then every update's — applied where they are used (the covariances stay as placed: no 48 B per point rewritten per pass)
-  double Racc[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  for (int k = 0; k < 9; ++k) Racc[k] = (k % 4 == 0) ? 1.0 : 0.0;
   if (e.type == kEstGicp) {
     rc = o3d_gicp_covariances(w, Ns, Nt, e, on_device, s);
     if (rc != O3S_OK) return rc;
     if (!h_is_identity(init))
       for (int c = 0; c < 3; ++c)
         for (int r = 0; r < 3; ++r) Racc[c * 3 + r] = init[c * 4 + r];
-    std::memcpy(w.ea.R, Racc, sizeof(Racc));
+    std::memcpy(w.ea.R, Racc, 9 * sizeof(double));
   } else if (e.type == kEstPoint) {
     w.ea.c[0] = gi.g.ox + 0.5 * gi.g.nx * gi.g.cell;  // the centre of the target's grid
     w.ea.c[1] = gi.g.oy + 0.5 * gi.g.ny * gi.g.cell;
     w.ea.c[2] = gi.g.oz + 0.5 * gi.g.nz * gi.g.cell;
   }
+  *gi_out = gi;
+  return O3S_OK;
+}
+
+// RegistrationICP for one pair on stream s (the device is already current on the calling thread); w: grow-only work area.
+// est (nullable: point-to-plane): the estimation; point-to-plane runs exactly the kernels and host arithmetic it always has.
+int o3d_icp_run(O3dIcpWork& w, const double* source, int64_t Ns, const double* target, const double* target_normals, int64_t Nt, double max_dist,
+                const double init[16], const o3s_o3d_icp_criteria* criteria, o3s_o3d_icp_result* result, hipStream_t s, bool on_device = false,
+                const unsigned long long* target_bounds = nullptr /*of the target, when the caller has them (build_grid_index)*/,
+                const O3dEstIn* est = nullptr) {
+  if (!result) return O3S_ERR_BAD_ARGUMENT;
+  const O3dEstIn e = est ? *est : O3dEstIn{};
+  o3s_o3d_icp_criteria cr;
+  o3s_o3d_icp_default_criteria(&cr);
+  if (criteria) cr = *criteria;
+  GridIndex gi;
+  double Racc[9];
+  int rc = o3d_icp_setup(w, source, Ns, target, target_normals, Nt, max_dist, init, e, &gi, Racc, s, on_device, target_bounds);
+  if (rc != O3S_OK) return rc;
+  const double r2 = max_dist * max_dist;
+  double T[16];
+  std::memcpy(T, init, sizeof(T));
   double sums[kAccComps];
   rc = o3d_corr_pass(w, Ns, gi, r2, 0, sums, s);
   if (rc != O3S_OK) return rc;
@@ -1555,22 +1597,7 @@ int o3d_icp_run(O3dIcpWork& w, const double* source, int64_t Ns, const double* t
   int it = 0;
   for (int i = 0; i < cr.max_iteration; ++i) {
     double update[16];
-    for (int k = 0; k < 16; ++k) update[k] = (k % 5 == 0) ? 1.0 : 0.0;
-    if (sums[29] > 0 && e.type == kEstPoint) {  // ComputeTransformation: empty correspondence set -> identity
-      h_umeyama(sums, w.ea.c, update);
-    } else if (sums[29] > 0) {  // point-to-plane, GICP: SolveJacobianSystemAndObtainExtrinsicMatrix
-      double JTJ[6][6], nb[6], x[6];
-      int t = 0;
-      for (int a = 0; a < 6; ++a)
-        for (int b = a; b < 6; ++b) {
-          JTJ[a][b] = sums[t];
-          JTJ[b][a] = sums[t];
-          ++t;
-        }
-      for (int a = 0; a < 6; ++a) nb[a] = -sums[21 + a];
-      h_ldlt_solve6(JTJ, nb, x);
-      h_vec6_to_T(x, update);
-    }
+    o3d_host_update(e.type, sums, w.ea.c, update);
     double Tn[16];
     h_mul4(update, T, Tn);
     std::memcpy(T, Tn, sizeof(T));

@@ -94,9 +94,10 @@ def vec6_to_T(x):
     return T
 
 
-def solve_jtj(JTJ, JTr):
-    """SolveJacobianSystemAndObtainExtrinsicMatrix: JTJ x = -JTr (Open3D: Eigen LDLT), then vec6_to_T."""
-    return vec6_to_T(np.linalg.solve(JTJ, -JTr))
+def solve_jtj(JTJ, JTr, solver=None):
+    """SolveJacobianSystemAndObtainExtrinsicMatrix: JTJ x = -JTr (Open3D: Eigen LDLT), then vec6_to_T.  solver(A, b) -> x: what
+    solves the system (default np.linalg.solve, which raises on a singular one; tests/o3d_solve_ref.py has Eigen's LDLT)."""
+    return vec6_to_T((solver or np.linalg.solve)(JTJ, -JTr))
 
 
 def skew(v):
@@ -116,14 +117,14 @@ def inv_sqrt_spd(M):
     return (V * np.sqrt(lam)[:, None, :]) @ np.transpose(V, (0, 2, 1))
 
 
-def update_point_to_plane(pcd, tgt, tn, si, tj):
+def update_point_to_plane(pcd, tgt, tn, si, tj, solver=None):
     vs, vt, nt = pcd[si], tgt[tj], tn[tj]
     r = ((vs - vt) * nt).sum(axis=1)
     J = np.concatenate([np.cross(vs, nt), nt], axis=1)
-    return solve_jtj(J.T @ J, J.T @ r)
+    return solve_jtj(J.T @ J, J.T @ r, solver)
 
 
-def update_generalized(pcd, tgt, cs, ct, si, tj):
+def update_generalized(pcd, tgt, cs, ct, si, tj, solver=None):
     """TransformationEstimationForGeneralizedICP::ComputeTransformation in Open3D's own form: W = (Ct + Cs)^-1.sqrt(),
     J = W [-[vs]x | I], r = W d; JTJ += J^T J, JTr += J^T r over the three rows of every correspondence."""
     vs, vt = pcd[si], tgt[tj]
@@ -134,7 +135,7 @@ def update_generalized(pcd, tgt, cs, ct, si, tj):
     r = (W @ d[:, :, None])[:, :, 0]       # n x 3
     JTJ = np.einsum("nka,nkb->ab", J, J)
     JTr = np.einsum("nka,nk->a", J, r)
-    return solve_jtj(JTJ, JTr)
+    return solve_jtj(JTJ, JTr, solver)
 
 
 def umeyama(src, dst):
@@ -154,9 +155,10 @@ def umeyama(src, dst):
 
 def registration_icp(source, target, max_correspondence_distance, init=None, registration_type="PointToPlaneIcp", target_normals=None,
                      source_normals=None, source_covariances=None, target_covariances=None, epsilon=1e-3, relative_fitness=1e-6,
-                     relative_rmse=1e-6, max_iteration=30, workers=1, bounded=False):
+                     relative_rmse=1e-6, max_iteration=30, workers=1, bounded=False, solver=None):
     """RegistrationICP(source, target, max_dist, init, <estimation>, criteria); GeneralizedIcp: RegistrationGeneralizedICP (the
-    covariances of InitializePointCloudForGeneralizedICP first).  Returns the fields of RegistrationResult as a dict."""
+    covariances of InitializePointCloudForGeneralizedICP first).  Returns the fields of RegistrationResult as a dict.
+    solver: see solve_jtj."""
     assert registration_type in TYPES
     src = np.asarray(source, np.float64)
     tgt = np.ascontiguousarray(target, np.float64)
@@ -182,11 +184,11 @@ def registration_icp(source, target, max_correspondence_distance, init=None, reg
         if len(si) == 0:
             update = np.eye(4)
         elif registration_type == "PointToPlaneIcp":
-            update = update_point_to_plane(pcd, tgt, tn, si, tj)
+            update = update_point_to_plane(pcd, tgt, tn, si, tj, solver)
         elif registration_type == "PointToPointIcp":
             update = umeyama(pcd[si], tgt[tj])
         else:
-            update = update_generalized(pcd, tgt, cs, ct, si, tj)
+            update = update_generalized(pcd, tgt, cs, ct, si, tj, solver)
         T = update @ T
         pcd = transform_points(update, pcd)
         if cs is not None:
